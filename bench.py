@@ -11,7 +11,9 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl == RCCL).  Boots
 independent, so the batch is sharded with no data-path collective (weak scaling: --batch per
 GPU); the only collective is the one-time RCCL broadcast of the evaluation keys from rank 0.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line; --full adds the
+other legs (gate, CMUX, circuit bootstrap, gate graphs, pools, host-pointer calls), the CPU baseline with its parity sample and
+the live counter passes.  --dump-outputs DIR writes what the last timed step computed, for output-for-output comparisons.
 """
 from __future__ import annotations
 
@@ -39,6 +41,8 @@ INT8_MFMA_PEAK_TOPS = 5000.0    # dense int8 MFMA = 2 x the bf16 rate (MI355X_MI
 TRACE_FLOP_PER_CT = 4 * 11 * (8 * 51200 + 12 * 8192 + 6 * 6144 + 2 * 8192)
 # scheme_switch_kernel, per circuit bootstrap: 4 levels x (17 forward + 2 inverse FFT-1024, 30 MAD rows, 17 twists, 2 untwists)
 SCHEME_SWITCH_FLOP_PER_CT = 4 * (19 * 51200 + 30 * 8192 + 17 * 6144 + 2 * 8192)
+# --dump-outputs writes at most this many ciphertexts in all: 1024 x 4096 words x 8 B = 32 MiB of float64 at DEFAULT_128
+DUMP_ROWS = 1024
 
 
 class _stdout_to_stderr:
@@ -106,15 +110,23 @@ def main() -> int:
                          "on several = configs[3], 65536 bootstraps over 8 GPUs)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline duration")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the gate / CMUX / circuit-bootstrap / 32-bit-add / pool / host-pointer legs, "
+                         "the CPU baseline with its parity sample and the live rocprofv3 counter passes (a few minutes).  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64: each output "
+                         "word as a signed torus value in [-0.5, 0.5); a fixed, seeded sample of at most "
+                         f"{DUMP_ROWS} ciphertexts in all)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline step: skip the gate / CMUX / circuit-bootstrap / 32-bit-add / host-pointer legs "
-                         "that the default run appends to the line (a few seconds)")
-    ap.add_argument("--with-keyswitch", action="store_true", help="(default on) time the fused gate (keyswitch + PBS)")
-    ap.add_argument("--with-cmux", action="store_true", help="(default on) time the batched cbs_radix CMUX kernel")
-    ap.add_argument("--with-cbs", action="store_true", help="(default on) time Evaluation::circuit_bootstrap end to end")
+                    help="with --full: only the headline step, skip the gate / CMUX / circuit-bootstrap / 32-bit-add / "
+                         "host-pointer legs")
+    ap.add_argument("--with-keyswitch", action="store_true", help="(on under --full) time the fused gate (keyswitch + PBS)")
+    ap.add_argument("--with-cmux", action="store_true", help="(on under --full) time the batched cbs_radix CMUX kernel")
+    ap.add_argument("--with-cbs", action="store_true", help="(on under --full) time Evaluation::circuit_bootstrap end to end")
     ap.add_argument("--with-add32", type=int, default=-1, metavar="K",
                     help="time K independent 32-bit encrypted additions as ONE gate graph (BASELINE config 3); "
-                         "default 1 on a single GPU")
+                         "default 1 on a single GPU under --full")
     ap.add_argument("--no-live-counters", action="store_true",
                     help="skip the rocprofv3 --pmc child runs that measure roofline.traffic and the SQ busy fractions of the "
                          "dominant kernel for THIS build on THIS box (three short child processes, about a minute)")
@@ -128,6 +140,10 @@ def main() -> int:
                     help="with --single-process: comma-separated HIP ordinals of the group's members (default 0..gpus-1); a "
                          "device may repeat, e.g. 0,0 rehearses a two-member group on a one-GPU box")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline step only
+        args.no_extras = args.no_cpu_baseline = args.no_live_counters = True
 
     if args.single_process:
         return _single_process_main(args)
@@ -235,6 +251,8 @@ def main() -> int:
     kernel_name = eng.last_blind_rotate_kernel()
     eng.set_timing(False)
     kernel_ms_minmax = [kernel_ms, kernel_ms]
+    if args.dump_outputs:   # glwe_out holds the last timed step's result until a leg below overwrites it
+        _dump_outputs(args.dump_outputs, {"glwe_out" if world == 1 else f"glwe_out_rank{rank}": glwe_out}, world)
     if world > 1:
         dt = max_over_ranks(dt, dist, device=dev)
         kernel_ms_minmax = [-max_over_ranks(-kernel_ms, dist, device=dev), max_over_ranks(kernel_ms, dist, device=dev)]
@@ -420,7 +438,8 @@ def main() -> int:
         mul32 = leg("mul32_gate_pool", lambda: _bench_mul32_pool(eng, P, rank, world))
     cmux = leg("cmux", _cmux) if args.with_cmux else None
     devgroup = leg("device_group", lambda: _bench_device_group(P, local_dev, lwe0, blobs, torch)) if (extras and rank == 0 and world == 1) else None
-    leg("restore", restore_headline_output)
+    if args.with_keyswitch:   # the gate leg is the one that writes glwe_out
+        leg("restore", restore_headline_output)
 
     # one collective for all legs: MAX of the per-rank seconds (inf where a rank failed)
     timed_legs = [("gate", gate), ("circuit_bootstrap", cbs), ("mul8_gate_pool", mul8), ("mul32_gate_pool", mul32),
@@ -688,19 +707,28 @@ def _single_process_main(args) -> int:
     value = G * B * args.steps / dt
     kernel_ms = max(kms)
     tf = FLOP_PER_PBS * B / (kernel_ms * 1e-3) / 1e12
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, {"glwe_out" if G == 1 else f"glwe_out_member{i}": out[i] for i in range(G)})
 
     # the host-pointer group call: ONE host batch of G x B ciphertexts, cut into G contiguous ranges inside the library
-    lwe_h = np.concatenate([x.cpu().numpy().view(np.uint64) for x in lwe0])
-    out_h = np.zeros((G * B, P.glwe_words), dtype=np.uint64)
-    grp.circuit_bootstrap_pbs(lwe_h, out=out_h)
-    reps = 2
-    cpu0 = time.process_time()
-    t0 = time.perf_counter()
-    for _ in range(reps):
+    pcie = None
+    if args.full:
+        lwe_h = np.concatenate([x.cpu().numpy().view(np.uint64) for x in lwe0])
+        out_h = np.zeros((G * B, P.glwe_words), dtype=np.uint64)
         grp.circuit_bootstrap_pbs(lwe_h, out=out_h)
-    t_h = (time.perf_counter() - t0) / reps
-    cpu_host = (time.process_time() - cpu0) / reps
-    same = all(bool(np.array_equal(out_h[i * B:(i + 1) * B], out[i].cpu().numpy().view(np.uint64))) for i in range(G))
+        reps = 2
+        cpu0 = time.process_time()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            grp.circuit_bootstrap_pbs(lwe_h, out=out_h)
+        t_h = (time.perf_counter() - t0) / reps
+        cpu_host = (time.process_time() - cpu0) / reps
+        same = all(bool(np.array_equal(out_h[i * B:(i + 1) * B], out[i].cpu().numpy().view(np.uint64))) for i in range(G))
+        pcie = {"pbs_per_s": round(G * B / t_h, 1), "ms_per_batch": round(t_h * 1e3, 3),
+                "note": "spf_group_circuit_bootstrap_pbs_batch: one pageable host batch of G x B ciphertexts cut into G "
+                        "contiguous ranges, each member's H2D / kernels / sliced D2H on its own thread and stream",
+                "same_words_as_device_path": same,
+                "host_cpu_s_per_batch": round(cpu_host, 3), "host_cpu_s_per_member_per_batch": round(cpu_host / G, 4)}
 
     cpu = None
     if G == 1 and not args.no_cpu_baseline:
@@ -738,11 +766,7 @@ def _single_process_main(args) -> int:
                  "replicate_keys_s": round(t_rep, 4), "broadcast_bytes": rep["bytes_per_member"],
                  "broadcast_GBs": round(rep["bytes_per_member"] / max(rep["wire_seconds"], 1e-9) / 1e9, 2)},
         "key_broadcast_s": round(rep["wire_seconds"], 4), "key_broadcast_bytes": rep["bytes_per_member"],
-        "pcie_inclusive": {"pbs_per_s": round(G * B / t_h, 1), "ms_per_batch": round(t_h * 1e3, 3),
-                           "note": "spf_group_circuit_bootstrap_pbs_batch: one pageable host batch of G x B ciphertexts cut into G "
-                                   "contiguous ranges, each member's H2D / kernels / sliced D2H on its own thread and stream",
-                           "same_words_as_device_path": same,
-                           "host_cpu_s_per_batch": round(cpu_host, 3), "host_cpu_s_per_member_per_batch": round(cpu_host / G, 4)},
+        "pcie_inclusive": pcie,
         "host_cpu": {"headline_cpu_s_per_step": round(cpu_headline / args.steps, 5),
                      "note": "process CPU time (all threads): the device-pointer headline only enqueues; the host-pointer call "
                              "stages every member's range through its own thread"},
@@ -853,6 +877,22 @@ def _group_pool_by_handle(grp, P, G, threads_per_member=64, seconds=2.0):
 
 
 DATA_DIR = os.path.join(ROOT, "spf_amd", "data")
+
+
+def _dump_outputs(out_dir, arrays, parts=1):
+    """--dump-outputs: each (ciphertexts x words) device array of u64 torus words as out_dir/<name>.npy in float64, every word
+    read as a signed 64-bit integer over 2^64 (the torus value in [-0.5, 0.5)).  Each array gets an equal share of DUMP_ROWS
+    rows, split further over `parts` processes that dump side by side; of a longer array a fixed, seeded sample of rows is
+    written (the same rows in every run with the same --batch)."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rows = max(1, DUMP_ROWS // (parts * len(arrays)))
+    for name, a in arrays.items():
+        if a.shape[0] > rows:
+            idx = np.sort(np.random.default_rng(0x5EED0D).choice(a.shape[0], rows, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        words = a.cpu().numpy().view(np.int64)
+        np.save(os.path.join(out_dir, name + ".npy"), words.astype(np.float64) * 2.0 ** -64)
 
 
 def _live_counters(kernel_name, B, kernel_ms, n_cu, budget_s=150.0):

@@ -1,10 +1,12 @@
 """bench.py prints ONE JSON line with the fields the driver's contract names, and its parity sample
-(the CPU-baseline leg) agrees with the GPU word for word."""
+(the CPU-baseline leg of --full) agrees with the GPU word for word; a plain run times the headline only and can write
+its outputs."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "512",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1", "--warmup", "1", "--batch", "512",
                         "--cpu-seconds", "2"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -59,7 +61,7 @@ def test_single_process_bench_line_over_a_device_group():
     """`bench.py --gpus N --single-process`: the same line shape from ONE host process driving a device group (here two members
     on the one GPU), keys replicated inside the library."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--single-process", "--devices", "0,0",
-                        "--steps", "1", "--warmup", "1", "--batch", "256", "--no-cpu-baseline"],
+                        "--full", "--steps", "1", "--warmup", "1", "--batch", "256", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     out = r.stdout.strip().splitlines()
@@ -71,3 +73,34 @@ def test_single_process_bench_line_over_a_device_group():
     assert d["pcie_inclusive"]["same_words_as_device_path"] is True
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert key in d["roofline"], key
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: --steps timed steps of the headline and nothing else; --dump-outputs writes the last step's GLWE
+    ciphertexts as float64 torus values, the same words in two runs with the same arguments."""
+    def run(out_dir):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "512",
+                            "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = r.stdout.strip().splitlines()
+        assert len(out) == 1, r.stdout[:500]
+        return json.loads(out[0])
+
+    d = run(tmp_path / "a")
+    for key, typ in [("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str),
+                     ("ms_per_step", float)]:
+        assert isinstance(d[key], typ), (key, d[key])
+    assert d["unit"] == "PBS/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["config"]["batch_per_gpu"] == 512
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 / 512 - 1.0) < 0.01    # value = 512 bootstraps per ms_per_step
+    assert d["cpu_baseline"] is None and d["pcie_inclusive"] is None and d["roofline"]["counters"] is None
+    for leg in ("gate", "cmux", "circuit_bootstrap", "pbs_univariate", "add32", "device_group", "evaluation_pool",
+                "mul8_gate_pool", "leg_errors"):
+        assert leg not in d, leg
+    assert sorted(os.listdir(tmp_path / "a")) == ["glwe_out.npy"]
+    a = np.load(tmp_path / "a" / "glwe_out.npy")
+    assert a.dtype == np.float64 and a.shape == (512, 4096) and a.nbytes <= 64 << 20
+    assert np.all(a >= -0.5) and np.all(a < 0.5) and np.count_nonzero(a) > a.size // 2
+    run(tmp_path / "b")
+    assert np.array_equal(a, np.load(tmp_path / "b" / "glwe_out.npy"))

@@ -420,7 +420,8 @@ def test_pool_reports_how_many_streams_run_side_by_side(rig):
         assert 1 <= c["stream_concurrency"] <= 16, c     # filled; in THIS process, after dozens of pools came and went, the
     finally:                                             # runtime's hardware queues are shared as it happened to hand them out
         pool.close()
-    # the claim itself in a fresh process: the library loaded first, one context, one pool
+    # the claim itself in a fresh process: the library loaded first, one context, one pool.  GPU_MAX_HW_QUEUES is left unset
+    # there, so the library's own request is the one in effect (a value the caller's environment exports would win over it)
     import json
     import subprocess
     import sys
@@ -429,7 +430,8 @@ def test_pool_reports_how_many_streams_run_side_by_side(rig):
             "pool = spf_amd.Pool(eng, max_batch=64, max_wait_us=100)\n"
             "print('COUNTERS ' + json.dumps(pool.counters()))\n"
             "pool.close()\n")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300,
+    env = {k: v for k, v in __import__("os").environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env,
                        cwd=__import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
     line = [l for l in r.stdout.splitlines() if l.startswith("COUNTERS ")]
     assert r.returncode == 0 and line, r.stdout + r.stderr

@@ -104,8 +104,8 @@ def test_rccl_world_size_1_key_broadcast_then_bootstrap():
 def test_bench_self_launches_two_gloo_ranks_on_one_gpu():
     """`python3 bench.py --gpus 2 --backend gloo` with no launcher: rc 0, one JSON line from rank 0, two ranks seen by
     the process group, every leg of the line present on two ranks (the job-sharded gate pools included)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "1",
-                        "--warmup", "1", "--batch", "512"], capture_output=True, text=True, timeout=840, cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full", "--steps",
+                        "1", "--warmup", "1", "--batch", "512"], capture_output=True, text=True, timeout=840, cwd=ROOT,
                        env=_bare_env())
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

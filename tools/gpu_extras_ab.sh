@@ -3,7 +3,7 @@
 set -o pipefail
 for V in "$@"; do
   echo "== $V"
-  env $V timeout -k 10 500 python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-live-counters 2>/dev/null | python3 -c "
+  env $V timeout -k 10 500 python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-live-counters 2>/dev/null | python3 -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):
