@@ -545,6 +545,10 @@ const char *spf_last_blind_rotate_kernel(spf_ctx *ctx);
  * to one gate per CU, the streaming shape beyond, with streaming (non-temporal) selector loads once a launch's selectors
  * exceed the Infinity Cache.  Never NULL. */
 const char *spf_last_cmux_kernel(spf_ctx *ctx);
+/* The same for the LWE keyswitch L1 -> L0 (every entry point that runs one): "ks_gemm_lds_kernel", the int8 matrix-core
+ * formulation, when the tuned context's radix fits it (radix_log <= 8 and its accumulator bound), else "keyswitch_kernel".
+ * Never NULL. */
+const char *spf_last_keyswitch_kernel(spf_ctx *ctx);
 
 /* ---- device groups: every GPU of a node from ONE host process (SURVEY.md §8 b / e) -------------------------------- *
  *

@@ -109,6 +109,7 @@ SYMBOLS = [
     ("spf_last_kernel_ms", _I, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_I)]),
     ("spf_last_blind_rotate_kernel", C.c_char_p, [_P]),
     ("spf_last_cmux_kernel", C.c_char_p, [_P]),
+    ("spf_last_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_device_alloc", _I, [_P, _SZ, C.POINTER(_P)]),
     ("spf_device_free", _I, [_P, _P]),
     ("spf_device_upload", _I, [_P, _P, _P, _SZ]),
@@ -566,6 +567,9 @@ class Engine:
 
     def last_cmux_kernel(self) -> str:
         return (self._lib.spf_last_cmux_kernel(self._h) or b"").decode()
+
+    def last_keyswitch_kernel(self) -> str:
+        return (self._lib.spf_last_keyswitch_kernel(self._h) or b"").decode()
 
     def last_kernel_ms(self, kernel: str = "pbs"):
         ms, n = C.c_double(), C.c_int()

@@ -108,6 +108,7 @@ struct spf_ctx {
     uint64_t buf_epoch = 0;            // bumped whenever a scratch buffer is reallocated (captured gate graphs hold their addresses)
     const char* last_pbs_kernel = "";  // name of the blind-rotation kernel the last launch used
     const char* last_cmux_kernel = ""; // ... and of the CMUX kernel
+    const char* last_ks_kernel = "";   // ... and of the LWE keyswitch
     hipStream_t copy_stream = nullptr; // device-to-host copies of finished slices, under the next slice's kernel
     std::vector<hipEvent_t> slice_ev;  // one "slice k is computed" event per slice in flight
     bool timing = false;
@@ -434,9 +435,11 @@ spf_status launch_keyswitch(spf_ctx* c, hipStream_t s, size_t B, const uint64_t*
         g.in = d_in; g.out = d_out; g.B = a.B; g.n_in = a.n_in; g.n_out = a.n_out; g.K = (uint32_t)K;
         dim3 grid((unsigned)(c->ks_npad / KSG_TILE), (unsigned)(mpad / KSG_TILE));
         hipLaunchKernelGGL(ks_gemm_lds_kernel, grid, dim3(256), kKsLdsBytes, s, g); // operand tiles staged through LDS by LDS-DMA
+        c->last_ks_kernel = "ks_gemm_lds_kernel";
     } else {
         dim3 grid((a.n_out + 1 + 255) / 256, (unsigned)((B + KS_CT - 1) / KS_CT)), block(256);
         hipLaunchKernelGGL(keyswitch_kernel, grid, block, 0, s, a);
+        c->last_ks_kernel = "keyswitch_kernel";
     }
     HIPCHK(c, hipGetLastError());
     return ts.end();
@@ -1844,6 +1847,13 @@ const char* spf_last_cmux_kernel(spf_ctx* c)
     if (!c) return "";
     std::lock_guard<std::recursive_mutex> g(c->mu);
     return c->last_cmux_kernel;
+}
+
+const char* spf_last_keyswitch_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_ks_kernel;
 }
 
 } // extern "C"

@@ -1719,24 +1719,26 @@ __global__ __launch_bounds__(256) void keyswitch_kernel(KeyswitchArgs a)
 #pragma unroll
     for (int t = 0; t < KS_CT; t++) sum[t] = 0;
 
+    // mask and digit state in 64 bits, as scalar.rs:52-71 has them: radix_log may be 32 (l * logB <= 32), where a 32-bit
+    // shift would wrap (the hardware takes the amount mod 32) and the rounded state may carry into bit 32
     const uint32_t shift = 64 - a.radix_log * a.count;
-    const uint32_t mask = (1u << a.radix_log) - 1;
+    const uint64_t mask = ((uint64_t)1 << a.radix_log) - 1;
     for (uint32_t i = 0; i < a.n_in; i++) {
         const uint64_t* lev = a.ksk + (size_t)i * a.count * w + colc;
-        uint32_t st[KS_CT];
+        uint64_t st[KS_CT];
 #pragma unroll
         for (int t = 0; t < KS_CT; t++) {
             uint32_t ct = ct0 + t < a.B ? ct0 + t : a.B - 1;
             uint64_t x = a.in[(size_t)ct * (a.n_in + 1) + i];
-            st[t] = (uint32_t)(x >> shift) + (uint32_t)((x >> (shift - 1)) & 1);
+            st[t] = (x >> shift) + ((x >> (shift - 1)) & 1);
         }
         for (uint32_t j = 0; j < a.count; j++) {
             uint64_t kv = lev[(size_t)(a.count - 1 - j) * w];
 #pragma unroll
             for (int t = 0; t < KS_CT; t++) {
-                uint32_t d = st[t] & mask;
+                uint64_t d = st[t] & mask;
                 st[t] >>= a.radix_log;
-                uint32_t carry = d >> (a.radix_log - 1);
+                uint64_t carry = d >> (a.radix_log - 1);
                 st[t] += carry;
                 int64_t digit = (int64_t)d - ((int64_t)carry << a.radix_log);
                 sum[t] += kv * (uint64_t)digit;
