@@ -123,6 +123,13 @@ class Evaluation {
     {
         check(spf_group_pbs_univariate_batch(grp_, B, input_l0, lut_glwe, lut_stride, output_l1));
     }
+    // sunscreen_tfhe::ops::bootstrapping::programmable_bootstrap_bivariate (lut_glwe: spf_generate_bivariate_lut)
+    void programmable_bootstrap_bivariate(uint64_t* output_l1, const uint64_t* left_l0, const uint64_t* right_l0,
+                                          const uint64_t* lut_glwe, uint32_t plaintext_bits, size_t B = 1,
+                                          size_t lut_stride = 0)
+    {
+        check(spf_group_pbs_bivariate_batch(grp_, B, left_l0, right_l0, lut_glwe, lut_stride, plaintext_bits, output_l1));
+    }
     // sunscreen_tfhe::ops::bootstrapping::generalized_programmable_bootstrap
     void generalized_programmable_bootstrap(uint64_t* output_glwe, const uint64_t* input_l0,
                                             const uint64_t* lut_glwe, uint32_t log_chi, uint32_t log_v,

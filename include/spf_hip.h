@@ -137,6 +137,17 @@ spf_status spf_pbs_univariate_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe0
                                     const uint64_t *lut_glwe, size_t lut_stride,
                                     uint64_t *lwe1_out);
 
+/* B x `programmable_bootstrap_bivariate` (programmable_bootstrapping.rs:575-621): packs
+ * left * 2^plaintext_bits + right on every word, wrapping (`scalar_mul_ciphertext_mad` into a cleared LWE, then
+ * `add_lwe_inplace`, :603-610), then bootstraps the packed input as spf_pbs_univariate_batch does; word-equal to
+ * spf_pbs_univariate_batch of the packed batch.  lwe0_left, lwe0_right: B x (lwe_dimension+1) each (they may be the
+ * same array: f(x, x)); lut_glwe / lut_stride as above, typically from spf_generate_bivariate_lut.  Encoding the inputs
+ * (padding bit, carry room) is the caller's.  plaintext_bits >= 64 is SPF_ERR_INVALID_ARGUMENT.
+ * lwe1_out: B x (k*N+1). */
+spf_status spf_pbs_bivariate_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe0_left, const uint64_t *lwe0_right,
+                                   const uint64_t *lut_glwe, size_t lut_stride, uint32_t plaintext_bits,
+                                   uint64_t *lwe1_out);
+
 /* B x the bootstrap stage of `Evaluation::circuit_bootstrap` (crypto/evaluation.rs:211-226):
  * `hi_noise_lwe_to_lo_noise_glwe` (ops/bootstrapping/circuit_bootstrapping.rs:387-427) =
  * rotate by q/4, multifunctional CBS LUT (:430-482), generalized PBS with
@@ -207,10 +218,11 @@ spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx *ctx, size_t B, const u
 /* ---- device-pointer forms (inputs/outputs resident in HBM, asynchronous on `stream`) -----
  * Contract of every `_dev` entry point: the call only ENQUEUES on `stream`; inputs and outputs must stay valid and
  * unchanged until that work has completed; an output must not overlap any input of the same call.  The entry points that
- * need intermediates (`spf_circuit_bootstrap_dev`, the keyswitch) keep them in buffers of the CONTEXT: enqueue them on ONE
- * stream per context (or order the streams with events) — two such calls running concurrently on different streams would
- * share those buffers.  `spf_mod_switch_trace_and_rotate_dev` additionally uses its OUTPUT as working memory while it runs
- * (the kernel parks half of its accumulator in each unit's 32 KiB of `d_glev_out` between automorphism rounds):
+ * need intermediates (`spf_circuit_bootstrap_dev`, the keyswitch, `spf_pbs_bivariate_dev`'s packed input) keep them in
+ * buffers of the CONTEXT: enqueue them on ONE stream per context (or order the streams with events) — two such calls
+ * running concurrently on different streams would share those buffers.  `spf_mod_switch_trace_and_rotate_dev`
+ * additionally uses its OUTPUT as working memory while it runs (the kernel parks half of its accumulator in each unit's
+ * 32 KiB of `d_glev_out` between automorphism rounds):
  * `d_glev_out` holds intermediate data until the kernel has completed and must not be read, or alias anything read, by
  * work that may run concurrently with it. */
 
@@ -222,6 +234,10 @@ spf_status spf_generalized_pbs_dev(spf_ctx *ctx, void *stream, size_t B, const u
 spf_status spf_pbs_univariate_dev(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_lwe0_in,
                                   const uint64_t *d_lut_glwe, size_t lut_stride,
                                   uint64_t *d_lwe1_out);
+/* spf_pbs_bivariate_batch on device pointers: the packed input lives in a buffer of the context (one stream per context) */
+spf_status spf_pbs_bivariate_dev(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_lwe0_left,
+                                 const uint64_t *d_lwe0_right, const uint64_t *d_lut_glwe, size_t lut_stride,
+                                 uint32_t plaintext_bits, uint64_t *d_lwe1_out);
 spf_status spf_circuit_bootstrap_pbs_dev(spf_ctx *ctx, void *stream, size_t B,
                                          const uint64_t *d_lwe0_in, uint64_t *d_glwe_out);
 spf_status spf_circuit_bootstrap_dev(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_lwe0_in,
@@ -502,6 +518,15 @@ spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keysw
  * A value >= 2^bits is SPF_ERR_INVALID_ARGUMENT (the reference asserts). */
 spf_status spf_generate_lut(const spf_params *params, const uint64_t *map_tables, size_t n_maps,
                             uint32_t plaintext_bits, uint64_t *lut_glwe_out);
+/* `BivariateLookupTable::trivial_from_fn` (sunscreen_tfhe entities/bivariate_lookup_table.rs:36-90) =
+ * `generate_bivariate_lut` (ops/bootstrapping/programmable_bootstrapping.rs:413-452): map_table[l * 2^p + r] = f(l, r)
+ * for p = plaintext_bits, 2^(2p) values.  Writes the trivial GLWE of `generate_lut` at p + carry_bits bits of the table
+ * U[x] = f((x >> p) mod 2^p, x mod 2^p), x < 2^(p + carry_bits) (`bivariate_function`, :413-430: carry bits above 2p
+ * are dropped), (k+1)*N words; outputs come out encoded at p + carry_bits bits without a padding bit
+ * (`decrypt_lwe_with_carry`, high_level.rs:586-611).  Needs 1 <= p <= carry_bits, 2^(p + carry_bits) <= N and every
+ * value < 2^p (the reference asserts), else SPF_ERR_INVALID_ARGUMENT.  No GPU involved; ctx-free. */
+spf_status spf_generate_bivariate_lut(const spf_params *params, const uint64_t *map_table, uint32_t plaintext_bits,
+                                      uint32_t carry_bits, uint64_t *lut_glwe_out);
 /* `safe_bincode::deserialize::<ComputeKey>` + upload (parasol_runtime/src/safe_bincode.rs:16-28,
  * crypto/keys.rs:294-318): `bytes` is what the Rust side wrote with bincode DefaultOptions +
  * with_fixint_encoding — four sequences (u64 LE count, elements) in the order bs_key, ks_key, ss_key, auto_key.
@@ -612,6 +637,9 @@ spf_status spf_group_generalized_pbs_batch(spf_group *grp, size_t B, const uint6
                                            uint64_t *glwe_out);
 spf_status spf_group_pbs_univariate_batch(spf_group *grp, size_t B, const uint64_t *lwe0_in, const uint64_t *lut_glwe,
                                           size_t lut_stride, uint64_t *lwe1_out);
+spf_status spf_group_pbs_bivariate_batch(spf_group *grp, size_t B, const uint64_t *lwe0_left, const uint64_t *lwe0_right,
+                                         const uint64_t *lut_glwe, size_t lut_stride, uint32_t plaintext_bits,
+                                         uint64_t *lwe1_out);
 spf_status spf_group_circuit_bootstrap_pbs_batch(spf_group *grp, size_t B, const uint64_t *lwe0_in, uint64_t *glwe_out);
 spf_status spf_group_circuit_bootstrap_batch(spf_group *grp, size_t B, const uint64_t *lwe0_in, double *ggsw_fft_out);
 spf_status spf_group_mod_switch_trace_and_rotate_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, uint64_t *glev_out);

@@ -52,6 +52,7 @@ SYMBOLS = [
     ("spf_keyswitch_lwe_l1_lwe_l0_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_generalized_pbs_batch", _I, [_P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_batch", _I, [_P, _SZ, _P, _P, _SZ, _P]),
+    ("spf_pbs_bivariate_batch", _I, [_P, _SZ, _P, _P, _P, _SZ, _U32, _P]),
     ("spf_circuit_bootstrap_pbs_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_circuit_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_mod_switch_trace_and_rotate_batch", _I, [_P, _SZ, _P, _P]),
@@ -73,6 +74,7 @@ SYMBOLS = [
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
+    ("spf_pbs_bivariate_dev", _I, [_P, _P, _SZ, _P, _P, _P, _SZ, _U32, _P]),
     ("spf_circuit_bootstrap_pbs_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_circuit_bootstrap_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_mod_switch_trace_and_rotate_dev", _I, [_P, _P, _SZ, _P, _P]),
@@ -116,6 +118,7 @@ SYMBOLS = [
     ("spf_device_download", _I, [_P, _P, _P, _P, _SZ]),
     ("spf_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_generate_lut", _I, [C.POINTER(_CParams), _P, _SZ, _U32, _P]),
+    ("spf_generate_bivariate_lut", _I, [C.POINTER(_CParams), _P, _U32, _U32, _P]),
     ("spf_load_compute_key_bincode", _I, [_P, _P, _SZ]),
     ("spf_ciphertext_words", _SZ, [C.POINTER(_CParams), _I]),
     ("spf_ciphertext_from_bincode", _I, [C.POINTER(_CParams), _I, _P, _SZ, _P]),
@@ -141,6 +144,7 @@ SYMBOLS = [
     ("spf_group_keyswitch_lwe_l1_lwe_l0_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_generalized_pbs_batch", _I, [_P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_group_pbs_univariate_batch", _I, [_P, _SZ, _P, _P, _SZ, _P]),
+    ("spf_group_pbs_bivariate_batch", _I, [_P, _SZ, _P, _P, _P, _SZ, _U32, _P]),
     ("spf_group_circuit_bootstrap_pbs_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_circuit_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_mod_switch_trace_and_rotate_batch", _I, [_P, _SZ, _P, _P]),
@@ -254,6 +258,29 @@ def generate_lut(maps, plaintext_bits: int, params: Params = DEFAULT_128) -> np.
     out = np.empty(params.glwe_words, dtype=np.uint64)
     cp = _CParams(*[getattr(params, n) for n, _ in _CParams._fields_])
     st = lib.spf_generate_lut(C.byref(cp), _ptr(table), len(maps), plaintext_bits, _ptr(out))
+    if st != 0:
+        raise SpfError(st, (lib.spf_last_error(None) or b"").decode())
+    return out
+
+
+def generate_bivariate_lut(f_or_table, plaintext_bits: int, carry_bits: int, params: Params = DEFAULT_128) -> np.ndarray:
+    """`BivariateLookupTable::trivial_from_fn` (entities/bivariate_lookup_table.rs:36-90) = `generate_bivariate_lut`
+    (programmable_bootstrapping.rs:413-452) as the trivial GLWE `pbs_bivariate` takes.  `f_or_table`: a callable
+    (l, r) -> f(l, r) on [0, 2^plaintext_bits)^2, or its table with table[l][r] = f(l, r) (2^p x 2^p or flat).
+    Needs 1 <= plaintext_bits <= carry_bits, 2^(plaintext_bits + carry_bits) <= N and f(l, r) < 2^plaintext_bits.
+    Host only, no GPU."""
+    lib = load_library()
+    # a callable is tabulated only over a plaintext space the C side can accept: otherwise it refuses with its message
+    ok = 1 <= plaintext_bits <= carry_bits and (1 << (plaintext_bits + carry_bits)) <= params.polynomial_degree
+    p = 1 << plaintext_bits if ok else 1
+    if callable(f_or_table):
+        table = np.array([f_or_table(l, r) for l in range(p) for r in range(p)] if ok else [0], dtype=np.uint64)
+    else:
+        table = np.ascontiguousarray(f_or_table, dtype=np.uint64).reshape(-1)
+        if ok and table.size != p * p:
+            raise SpfError(-2, f"generate_bivariate_lut: the table has {table.size} values, expected 2^(2 * {plaintext_bits})")
+    out = np.empty(params.glwe_words, dtype=np.uint64)
+    st = lib.spf_generate_bivariate_lut(C.byref(_cparams(params)), _ptr(table), plaintext_bits, carry_bits, _ptr(out))
     if st != 0:
         raise SpfError(st, (lib.spf_last_error(None) or b"").decode())
     return out
@@ -387,6 +414,17 @@ class Engine:
                                                     _ptr(out)))
         return out
 
+    def pbs_bivariate(self, left, right, lut_glwe, plaintext_bits: int) -> np.ndarray:
+        """`programmable_bootstrap_bivariate` (programmable_bootstrapping.rs:575-621) of each pair (left[i], right[i])"""
+        x = _u64(left).reshape(-1, self.params.lwe0_words)
+        y = _u64(right).reshape(-1, self.params.lwe0_words)
+        _same_rows("pbs_bivariate", x, y)
+        lut, stride = self._lut(lut_glwe, x.shape[0])
+        out = np.empty((x.shape[0], self.params.lwe1_words), dtype=np.uint64)
+        self._ck(self._lib.spf_pbs_bivariate_batch(self._h, x.shape[0], _ptr(x), _ptr(y), _ptr(lut), stride,
+                                                   plaintext_bits, _ptr(out)))
+        return out
+
     def circuit_bootstrap_pbs(self, lwe0, out: Optional[np.ndarray] = None) -> np.ndarray:
         """`out`: caller-allocated (B, glwe_words) uint64 array, as the C ABI's caller does — a fresh np.empty is
         untouched memory, and its first-touch page faults land inside the device-to-host copy"""
@@ -497,6 +535,10 @@ class Engine:
 
     def pbs_univariate_dev(self, stream, B, d_lwe, d_lut, lut_stride, d_out):
         self._ck(self._lib.spf_pbs_univariate_dev(self._h, stream, B, d_lwe, d_lut, lut_stride, d_out))
+
+    def pbs_bivariate_dev(self, stream, B, d_left, d_right, d_lut, lut_stride, plaintext_bits, d_out):
+        self._ck(self._lib.spf_pbs_bivariate_dev(self._h, stream, B, d_left, d_right, d_lut, lut_stride, plaintext_bits,
+                                                 d_out))
 
     def circuit_bootstrap_pbs_dev(self, stream: int, B: int, d_lwe: int, d_out: int):
         self._ck(self._lib.spf_circuit_bootstrap_pbs_dev(self._h, stream, B, d_lwe, d_out))

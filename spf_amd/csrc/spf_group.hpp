@@ -626,6 +626,18 @@ spf_status spf_group_pbs_univariate_batch(spf_group* g, size_t B, const uint64_t
     });
 }
 
+spf_status spf_group_pbs_bivariate_batch(spf_group* g, size_t B, const uint64_t* left, const uint64_t* right, const uint64_t* lut,
+                                         size_t lut_stride, uint32_t plaintext_bits, uint64_t* out)
+{
+    SPF_GROUP_NULL(!left || !right || !lut || !out);
+    if (plaintext_bits >= 64) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "plaintext_bits must be below 64");
+    const size_t wi = lwe0_words(g->prm), wo = lwe1_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
+        return spf_pbs_bivariate_batch(c, n, left + at * wi, right + at * wi, lut + at * lut_stride, lut_stride, plaintext_bits,
+                                       out + at * wo);
+    });
+}
+
 spf_status spf_group_circuit_bootstrap_pbs_batch(spf_group* g, size_t B, const uint64_t* lwe, uint64_t* out)
 {
     SPF_GROUP_NULL(!lwe || !out);

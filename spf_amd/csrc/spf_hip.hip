@@ -92,6 +92,7 @@ struct spf_ctx {
     bool ksk_ready = false;
     uint64_t* d_cbs_lut = nullptr; // fill_multifunctional_cbs_decomposition_lut, constant per params
     DevBuf in, out, mid, aux;      // staging for the host-pointer entry points
+    DevBuf packed;                  // the packed level-0 input of spf_pbs_bivariate_dev
     int8_t* d_ksk_planes = nullptr; // key byte planes for the int8-MFMA keyswitch [Npad][K]
     size_t ks_npad = 0;
     Scratch scr;                    // intermediates of the entry points (keyswitch digits, circuit-bootstrap GLWE / GLEV)
@@ -645,7 +646,7 @@ void spf_destroy(spf_ctx* c)
     for (auto& v : c->timed)
         for (auto& t : v) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     for (void* p : {(void*)c->d_tables, (void*)c->d_bsk, (void*)c->d_bsk_scaled, (void*)c->d_ksk, (void*)c->d_cbs_lut,
-                    c->in.p, c->out.p, c->mid.p, c->aux.p, (void*)c->d_ksk_planes, c->scr.ks_dig.p,
+                    c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, (void*)c->d_ksk_planes, c->scr.ks_dig.p,
                     c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -845,6 +846,37 @@ spf_status spf_pbs_univariate_dev(spf_ctx* c, void* stream, size_t B, const uint
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     return launch_blind_rotate(c, (hipStream_t)stream, B, d_lwe, d_lut, lut_stride, 0, 0, 0, d_out, lwe1_words(c->prm), true);
+}
+
+// d_out = d_left * 2^plaintext_bits + d_right over B level-0 LWEs (lwe_pack_kernel; d_out may be d_left)
+static spf_status launch_lwe_pack(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_left, const uint64_t* d_right,
+                                  uint32_t plaintext_bits, uint64_t* d_out)
+{
+    const size_t words = B * lwe0_words(c->prm);
+    const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 4 * (size_t)c->n_cu);
+    hipLaunchKernelGGL(lwe_pack_kernel, dim3(blocks), dim3(256), 0, s, d_left, d_right, d_out, words, (uint64_t)1 << plaintext_bits);
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+// programmable_bootstrap_bivariate (programmable_bootstrapping.rs:575-621): pack into the context's buffer, then the
+// univariate bootstrap of the packed input
+spf_status spf_pbs_bivariate_dev(spf_ctx* c, void* stream, size_t B, const uint64_t* d_left, const uint64_t* d_right,
+                                 const uint64_t* d_lut, size_t lut_stride, uint32_t plaintext_bits, uint64_t* d_out)
+{
+    if (!c || (B && (!d_left || !d_right || !d_lut || !d_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (plaintext_bits >= 64) return fail(c, SPF_ERR_INVALID_ARGUMENT, "plaintext_bits must be below 64");
+    if (B == 0) return SPF_OK;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->bsk_ready) return fail(c, SPF_ERR_NO_KEY, "bootstrap key not loaded");
+    if (B > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    spf_status st = ensure(c, c->packed, B * lwe0_words(c->prm) * 8);
+    if (st != SPF_OK) return st;
+    uint64_t* d_packed = (uint64_t*)c->packed.p;
+    st = launch_lwe_pack(c, (hipStream_t)stream, B, d_left, d_right, plaintext_bits, d_packed);
+    if (st != SPF_OK) return st;
+    return launch_blind_rotate(c, (hipStream_t)stream, B, d_packed, d_lut, lut_stride, 0, 0, 0, d_out, lwe1_words(c->prm), true);
 }
 
 spf_status spf_circuit_bootstrap_pbs_dev(spf_ctx* c, void* stream, size_t B, const uint64_t* d_lwe, uint64_t* d_out)
@@ -1348,14 +1380,22 @@ static spf_status bootstrap_sliced_to_host(spf_ctx* c, size_t B, const uint64_t*
     return SPF_OK;
 }
 
+// `rhs` (bivariate): the input bootstrapped is lwe * 2^shift_bits + rhs, packed in place in the staging buffer
 static spf_status pbs_host(spf_ctx* c, size_t B, const uint64_t* lwe, const uint64_t* lut, size_t lut_stride,
-                           uint32_t log_chi, uint32_t log_v, uint64_t rot, uint64_t* out, bool extract)
+                           uint32_t log_chi, uint32_t log_v, uint64_t rot, uint64_t* out, bool extract,
+                           const uint64_t* rhs = nullptr, uint32_t shift_bits = 0)
 {
     if (!c || (B && (!lwe || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     STAGE_IN(c->in, lwe, B * lwe0_words(c->prm) * 8);
+    if (rhs) {
+        STAGE_IN(c->mid, rhs, B * lwe0_words(c->prm) * 8);
+        spf_status s = launch_lwe_pack(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, shift_bits,
+                                       (uint64_t*)c->in.p);
+        if (s != SPF_OK) return s;
+    }
     const uint64_t* d_lut = c->d_cbs_lut;
     if (lut) {
         size_t luts = lut_stride ? B : 1;
@@ -1383,6 +1423,14 @@ spf_status spf_pbs_univariate_batch(spf_ctx* c, size_t B, const uint64_t* lwe, c
 {
     if (B && !lut) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null lut");
     return pbs_host(c, B, lwe, lut, lut_stride, 0, 0, 0, out, true);
+}
+
+spf_status spf_pbs_bivariate_batch(spf_ctx* c, size_t B, const uint64_t* left, const uint64_t* right, const uint64_t* lut,
+                                   size_t lut_stride, uint32_t plaintext_bits, uint64_t* out)
+{
+    if (B && (!right || !lut)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (plaintext_bits >= 64) return fail(c, SPF_ERR_INVALID_ARGUMENT, "plaintext_bits must be below 64");
+    return pbs_host(c, B, left, lut, lut_stride, 0, 0, 0, out, true, right, plaintext_bits);
 }
 
 spf_status spf_circuit_bootstrap_pbs_batch(spf_ctx* c, size_t B, const uint64_t* lwe, uint64_t* out)
@@ -1706,6 +1754,32 @@ spf_status spf_generate_lut(const spf_params* prm, const uint64_t* map_tables, s
         body[i] = m < h ? (uint64_t)0 - v : v;
     }
     return SPF_OK;
+}
+
+// `BivariateLookupTable::trivial_from_fn` (entities/bivariate_lookup_table.rs:36-90) = `generate_bivariate_lut`
+// (ops/bootstrapping/programmable_bootstrapping.rs:413-452): the univariate table U[x] = f((x >> p) mod 2^p, x mod 2^p) over
+// x < 2^(p + c) (`bivariate_function`, the left operand taken mod 2^p), written by `generate_lut` at p + c bits.  With
+// map_table[l * 2^p + r] = f(l, r) that index is x mod 2^(2p).
+spf_status spf_generate_bivariate_lut(const spf_params* prm, const uint64_t* map_table, uint32_t plaintext_bits,
+                                      uint32_t carry_bits, uint64_t* lut_glwe_out)
+{
+    if (!prm || !map_table || !lut_glwe_out) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "spf_generate_bivariate_lut: null argument");
+    const uint64_t bits = (uint64_t)plaintext_bits + carry_bits;
+    if (plaintext_bits == 0 || plaintext_bits > carry_bits || bits >= 64 || ((uint64_t)1 << bits) > prm->polynomial_degree)
+        return fail(nullptr, SPF_ERR_INVALID_ARGUMENT,
+                    "spf_generate_bivariate_lut: needs 1 <= plaintext_bits <= carry_bits and 2^(plaintext_bits + carry_bits) <= N");
+    const uint64_t p = (uint64_t)1 << plaintext_bits;
+    for (uint64_t i = 0; i < p * p; i++)
+        if (map_table[i] >= p)
+            return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "spf_generate_bivariate_lut: a map value is not below 2^plaintext_bits");
+    std::vector<uint64_t> u;
+    try {
+        u.resize((size_t)1 << bits);
+    } catch (const std::bad_alloc&) {
+        return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "spf_generate_bivariate_lut: out of host memory");
+    }
+    for (size_t x = 0; x < u.size(); x++) u[x] = map_table[x & (p * p - 1)];
+    return spf_generate_lut(prm, u.data(), 1, (uint32_t)bits, lut_glwe_out);
 }
 
 // `safe_bincode::deserialize::<ComputeKey>` (parasol_runtime/src/safe_bincode.rs:16-28, crypto/keys.rs:294-318):

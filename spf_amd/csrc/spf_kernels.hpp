@@ -1979,6 +1979,18 @@ __global__ void glwe_linear_kernel(const uint64_t* a, const uint64_t* b, uint64_
     }
 }
 
+// The input packing of `programmable_bootstrap_bivariate` (ops/bootstrapping/programmable_bootstrapping.rs:603-610):
+// `scalar_mul_ciphertext_mad` of the left LWE by shift = 2^plaintext_bits into a cleared LWE, then `add_lwe_inplace` of the
+// right one, i.e. out = left * shift + right on every word (mask and body), wrapping.  A flat grid-stride loop over the
+// batch's `words`, streaming (24 bytes per word: 12 us at B = 4096, beside a 40 ms bootstrap).  Each word is read before it is
+// written by the same thread, so `out` may be `left` (in place) and `left` may be `right` (f(x, x)): no __restrict__.
+// Parameter-independent: serves tuned and generic contexts alike.
+__global__ void lwe_pack_kernel(const uint64_t* left, const uint64_t* right, uint64_t* out, size_t words, uint64_t shift)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = left[i] * shift + right[i];
+}
+
 // words u64 from `src` (pinned host memory, read by the GPU over PCIe, or device memory) to `dst`: the pool's copy-in.  A kernel
 // on the batch's own stream instead of a hipMemcpyAsync: the runtime hands those to ONE in-order SDMA queue per direction pair,
 // where a host-to-device copy of a new batch stood behind the device-to-host copy of another batch that was still waiting for

@@ -95,6 +95,12 @@ class Evaluation:
     def programmable_bootstrap_univariate(self, output: np.ndarray, input: np.ndarray, lut: np.ndarray):
         self._store(output, self.engine.pbs_univariate(input, lut))
 
+    # sunscreen_tfhe::ops::bootstrapping::programmable_bootstrap_bivariate
+    # (programmable_bootstrapping.rs:575-621); `lut` from spf_amd.generate_bivariate_lut
+    def programmable_bootstrap_bivariate(self, output: np.ndarray, left: np.ndarray, right: np.ndarray, lut: np.ndarray,
+                                         plaintext_bits: int):
+        self._store(output, self.engine.pbs_bivariate(left, right, lut, plaintext_bits))
+
     # generalized_programmable_bootstrap (programmable_bootstrapping.rs:342-410)
     def generalized_programmable_bootstrap(self, output, input, lut, log_chi: int, log_v: int):
         self._store(output, self.engine.generalized_pbs(input, lut, log_chi, log_v, 0))
