@@ -97,6 +97,22 @@ class Evaluation {
     {
         check(spf_group_sample_extract_l1_batch(grp_, B, input, idx, output));
     }
+    // Packed integers, int-major (bit i of packed ciphertext b is row b * n_bits + i):
+    // DynamicGenericIntGraphNodes::pack (fluent/dynamic_generic_int_graph_nodes.rs:139-200): B * n_bits bit GLWEs -> B GLWEs
+    void pack(uint64_t* output_packed, const uint64_t* bits_glwe, size_t n_bits, size_t B = 1)
+    {
+        check(spf_group_glwe_pack_batch(grp_, B, n_bits, bits_glwe, output_packed));
+    }
+    // PackedDynamicGenericIntGraphNode::unpack (fluent/packed_dynamic_generic_int_graph_node.rs:24-39): B GLWEs -> B * n_bits L1 LWEs
+    void unpack_l1(uint64_t* output_lwe1, const uint64_t* packed_glwe, size_t n_bits, size_t B = 1)
+    {
+        check(spf_group_glwe_unpack_l1_batch(grp_, B, n_bits, packed_glwe, output_lwe1));
+    }
+    // unpack, then FheOp::KeyswitchL1toL0 -> FheOp::CircuitBootstrap of every bit (fhe_circuit.rs:563-625): B * n_bits GGSWs
+    void unpack_circuit_bootstrap(double* output_ggsw_fft, const uint64_t* packed_glwe, size_t n_bits, size_t B = 1)
+    {
+        check(spf_group_unpack_circuit_bootstrap_batch(grp_, B, n_bits, packed_glwe, output_ggsw_fft));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

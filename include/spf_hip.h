@@ -215,6 +215,24 @@ spf_status spf_gate_bootstrap_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe1
 spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe1_in,
                                                  double *ggsw_fft_out);
 
+/* Packed integers (`PackedDynamicGenericInt`, parasol_runtime fluent/generic_int.rs:162-176): an n_bits-bit integer in ONE
+ * L1 GLWE, bit i (least significant first, fluent/int.rs:47-49, uint.rs:30-32) in coefficient X^i.  Every entry point below is
+ * int-major: bit i of packed ciphertext b is row b * n_bits + i.  0 < n_bits <= N (dynamic_generic_int_graph_nodes.rs:146-147)
+ * and B * n_bits <= 0x0fffffff, else SPF_ERR_INVALID_ARGUMENT before any device work; B = 0 is SPF_OK.  Pack and
+ * unpack need no key.
+ * glwe_pack: `DynamicGenericIntGraphNodes::pack` (fluent/dynamic_generic_int_graph_nodes.rs:139-200) = sum over i of
+ *   `MulXN(i)` of bit i's GLWE, one kernel; word-equal to the reference's tree of `GlweAdd`s (addition mod 2^64 is
+ *   associative).  bits_glwe: B * n_bits x (k+1)*N; packed_out: B x (k+1)*N.
+ * glwe_unpack_l1: `PackedDynamicGenericIntGraphNode::unpack` (fluent/packed_dynamic_generic_int_graph_node.rs:24-39) =
+ *   `SampleExtract(i)` for i < n_bits, one kernel.  packed_glwe: B x (k+1)*N; lwe1_out: B * n_bits x (k*N+1).
+ * unpack_circuit_bootstrap: the unpack, then `KeyswitchL1toL0` -> `CircuitBootstrap` of every bit (fhe_circuit.rs:563-625);
+ *   the L1 and L0 LWEs stay on the device.  Bit-equal to spf_keyswitch_circuit_bootstrap_batch of the unpacked LWEs, and
+ *   fails as it does without a key or with an unsupported circuit-bootstrap tail.  ggsw_fft_out: B * n_bits GGSWs. */
+spf_status spf_glwe_pack_batch(spf_ctx *ctx, size_t B, size_t n_bits, const uint64_t *bits_glwe, uint64_t *packed_out);
+spf_status spf_glwe_unpack_l1_batch(spf_ctx *ctx, size_t B, size_t n_bits, const uint64_t *packed_glwe, uint64_t *lwe1_out);
+spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx *ctx, size_t B, size_t n_bits, const uint64_t *packed_glwe,
+                                              double *ggsw_fft_out);
+
 /* ---- device-pointer forms (inputs/outputs resident in HBM, asynchronous on `stream`) -----
  * Contract of every `_dev` entry point: the call only ENQUEUES on `stream`; inputs and outputs must stay valid and
  * unchanged until that work has completed; an output must not overlap any input of the same call.  The entry points that
@@ -259,6 +277,14 @@ spf_status spf_glev_cmux_dev(spf_ctx *ctx, void *stream, size_t B, const double 
                              const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out);
 spf_status spf_multiply_glwe_ggsw_dev(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe,
                                       const double *d_ggsw_fft, uint64_t *d_out);
+/* the packed-integer entry points on device pointers.  spf_glwe_pack_dev refuses an output range that overlaps the input
+ * range; spf_unpack_circuit_bootstrap_dev keeps the unpacked LWEs in buffers of the context (one stream per context). */
+spf_status spf_glwe_pack_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits, const uint64_t *d_bits_glwe,
+                             uint64_t *d_packed_out);
+spf_status spf_glwe_unpack_l1_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits, const uint64_t *d_packed_glwe,
+                                  uint64_t *d_lwe1_out);
+spf_status spf_unpack_circuit_bootstrap_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits,
+                                            const uint64_t *d_packed_glwe, double *d_ggsw_fft_out);
 
 /* ciphertext types (`L0LweCiphertext` ... `L1GlevCiphertext`, crypto/encryption.rs:23-110) and the computing variants of `FheOp`
  * (fhe_circuit.rs:65-126): used by the values, the pool's generic submit and the gate graphs below */
@@ -656,6 +682,12 @@ spf_status spf_group_multiply_glwe_ggsw_batch(spf_group *grp, size_t B, const ui
                                               uint64_t *out);
 spf_status spf_group_gate_bootstrap_batch(spf_group *grp, size_t B, const uint64_t *lwe1_in, uint64_t *glwe_out);
 spf_status spf_group_keyswitch_circuit_bootstrap_batch(spf_group *grp, size_t B, const uint64_t *lwe1_in, double *ggsw_fft_out);
+/* the packed-integer forms, sharded by packed ciphertext (a member's rows are at * n_bits onwards) */
+spf_status spf_group_glwe_pack_batch(spf_group *grp, size_t B, size_t n_bits, const uint64_t *bits_glwe, uint64_t *packed_out);
+spf_status spf_group_glwe_unpack_l1_batch(spf_group *grp, size_t B, size_t n_bits, const uint64_t *packed_glwe,
+                                          uint64_t *lwe1_out);
+spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group *grp, size_t B, size_t n_bits, const uint64_t *packed_glwe,
+                                                    double *ggsw_fft_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

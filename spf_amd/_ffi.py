@@ -69,8 +69,14 @@ SYMBOLS = [
     ("spf_multiply_glwe_ggsw_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_glev_cmux_dev", _I, [_P, _P, _SZ, _P, _P, _P, _P]),
     ("spf_multiply_glwe_ggsw_dev", _I, [_P, _P, _SZ, _P, _P, _P]),
+    ("spf_glwe_pack_dev", _I, [_P, _P, _SZ, _SZ, _P, _P]),
+    ("spf_glwe_unpack_l1_dev", _I, [_P, _P, _SZ, _SZ, _P, _P]),
+    ("spf_unpack_circuit_bootstrap_dev", _I, [_P, _P, _SZ, _SZ, _P, _P]),
     ("spf_gate_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_keyswitch_circuit_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_glwe_pack_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_glwe_unpack_l1_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -158,6 +164,9 @@ SYMBOLS = [
     ("spf_group_multiply_glwe_ggsw_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_group_gate_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_keyswitch_circuit_bootstrap_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_group_glwe_pack_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_group_glwe_unpack_l1_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_group_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -516,6 +525,33 @@ class Engine:
         self._ck(self._lib.spf_keyswitch_circuit_bootstrap_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    # -- packed integers (int-major: bit i of packed ciphertext b is [b, i]; spf_amd.packed has the plaintext side)
+    def glwe_pack(self, bits) -> np.ndarray:
+        """`DynamicGenericIntGraphNodes::pack` (fluent/dynamic_generic_int_graph_nodes.rs:139-200): (B, n, glwe_words)
+        GLWEs of the bits -> (B, glwe_words), the sum of bit i's GLWE times X^i"""
+        x = _u64(bits)
+        if x.ndim != 3 or x.shape[2] != self.params.glwe_words:
+            raise SpfError(-2, f"glwe_pack: bits must have shape (B, n_bits, {self.params.glwe_words}), got {x.shape}")
+        out = np.empty((x.shape[0], self.params.glwe_words), dtype=np.uint64)
+        self._ck(self._lib.spf_glwe_pack_batch(self._h, x.shape[0], x.shape[1], _ptr(x), _ptr(out)))
+        return out
+
+    def glwe_unpack_l1(self, packed, n_bits: int) -> np.ndarray:
+        """`PackedDynamicGenericIntGraphNode::unpack` (fluent/packed_dynamic_generic_int_graph_node.rs:24-39):
+        (B, glwe_words) -> (B, n_bits, lwe1_words), [b, i] = sample_extract(packed[b], i)"""
+        x = _u64(packed).reshape(-1, self.params.glwe_words)
+        out = np.empty((x.shape[0], n_bits, self.params.lwe1_words), dtype=np.uint64)
+        self._ck(self._lib.spf_glwe_unpack_l1_batch(self._h, x.shape[0], n_bits, _ptr(x), _ptr(out)))
+        return out
+
+    def unpack_circuit_bootstrap(self, packed, n_bits: int) -> np.ndarray:
+        """unpack, then KeyswitchL1toL0 -> CircuitBootstrap of every bit: (B, glwe_words) -> (B, n_bits, cbs_ggsw_complex),
+        the GGSWs a mux circuit reads; the LWEs stay on the device"""
+        x = _u64(packed).reshape(-1, self.params.glwe_words)
+        out = np.empty((x.shape[0], n_bits, self.params.cbs_ggsw_complex), dtype=np.complex128)
+        self._ck(self._lib.spf_unpack_circuit_bootstrap_batch(self._h, x.shape[0], n_bits, _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -570,6 +606,15 @@ class Engine:
 
     def sample_extract_l1_dev(self, stream, B, d_glwe, idx, d_out):
         self._ck(self._lib.spf_sample_extract_l1_dev(self._h, stream, B, d_glwe, idx, d_out))
+
+    def glwe_pack_dev(self, stream, B, n_bits, d_bits, d_out):
+        self._ck(self._lib.spf_glwe_pack_dev(self._h, stream, B, n_bits, d_bits, d_out))
+
+    def glwe_unpack_l1_dev(self, stream, B, n_bits, d_packed, d_out):
+        self._ck(self._lib.spf_glwe_unpack_l1_dev(self._h, stream, B, n_bits, d_packed, d_out))
+
+    def unpack_circuit_bootstrap_dev(self, stream, B, n_bits, d_packed, d_ggsw_out):
+        self._ck(self._lib.spf_unpack_circuit_bootstrap_dev(self._h, stream, B, n_bits, d_packed, d_ggsw_out))
 
     # -- device buffers (for chaining the _dev forms without a HIP binding of one's own)
     def device_alloc(self, nbytes: int) -> int:

@@ -673,6 +673,38 @@ spf_status spf_group_sample_extract_l1_batch(spf_group* g, size_t B, const uint6
     return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_sample_extract_l1_batch(c, n, in + at * wi, idx, out + at * wo); });
 }
 
+// packed integers: sharded by packed ciphertext, so the member that takes ciphertexts [at, at + n) takes rows at * n_bits ..
+#define SPF_GROUP_PACKED(in, out)                                                                  \
+    SPF_GROUP_NULL(!(in) || !(out));                                                               \
+    if (const char* why = packed_shape_error(g->prm, B, n_bits)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why)
+
+spf_status spf_group_glwe_pack_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* bits, uint64_t* out)
+{
+    SPF_GROUP_PACKED(bits, out);
+    const size_t w = glwe_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
+        return spf_glwe_pack_batch(c, n, n_bits, bits + at * n_bits * w, out + at * w);
+    });
+}
+
+spf_status spf_group_glwe_unpack_l1_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* glwe, uint64_t* lwe1_out)
+{
+    SPF_GROUP_PACKED(glwe, lwe1_out);
+    const size_t wi = glwe_words(g->prm), wo = lwe1_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
+        return spf_glwe_unpack_l1_batch(c, n, n_bits, glwe + at * wi, lwe1_out + at * n_bits * wo);
+    });
+}
+
+spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* glwe, double* ggsw_out)
+{
+    SPF_GROUP_PACKED(glwe, ggsw_out);
+    const size_t wi = glwe_words(g->prm), wo = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
+        return spf_unpack_circuit_bootstrap_batch(c, n, n_bits, glwe + at * wi, ggsw_out + at * n_bits * wo);
+    });
+}
+
 spf_status spf_group_glwe_not_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
     SPF_GROUP_NULL(!in || !out);

@@ -93,6 +93,7 @@ struct spf_ctx {
     uint64_t* d_cbs_lut = nullptr; // fill_multifunctional_cbs_decomposition_lut, constant per params
     DevBuf in, out, mid, aux;      // staging for the host-pointer entry points
     DevBuf packed;                  // the packed level-0 input of spf_pbs_bivariate_dev
+    DevBuf unpack_l1, unpack_l0;    // the unpacked bits of spf_unpack_circuit_bootstrap_dev, before and after the keyswitch
     int8_t* d_ksk_planes = nullptr; // key byte planes for the int8-MFMA keyswitch [Npad][K]
     size_t ks_npad = 0;
     Scratch scr;                    // intermediates of the entry points (keyswitch digits, circuit-bootstrap GLWE / GLEV)
@@ -646,8 +647,8 @@ void spf_destroy(spf_ctx* c)
     for (auto& v : c->timed)
         for (auto& t : v) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     for (void* p : {(void*)c->d_tables, (void*)c->d_bsk, (void*)c->d_bsk_scaled, (void*)c->d_ksk, (void*)c->d_cbs_lut,
-                    c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, (void*)c->d_ksk_planes, c->scr.ks_dig.p,
-                    c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables})
+                    c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, (void*)c->d_ksk_planes,
+                    c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
@@ -1109,6 +1110,89 @@ spf_status spf_glwe_mul_xn_dev(spf_ctx* c, void* stream, size_t B, const uint64_
     return glwe_linear_dev(c, stream, B, GLWE_MUL_XN, d_in, nullptr, c ? (uint32_t)(n % (2 * (size_t)c->prm.polynomial_degree)) : 0u, d_out);
 }
 
+// ---- packed integers: B ciphertexts of n_bits bits, bit i of ciphertext b in row b * n_bits + i (int-major)
+
+// why (B, n_bits) is refused, or nullptr: 0 < n_bits <= N (dynamic_generic_int_graph_nodes.rs:146-147), and B * n_bits rows
+// within the batch limit of the circuit-bootstrap entry points
+static const char* packed_shape_error(const spf_params& p, size_t B, size_t n_bits)
+{
+    if (n_bits == 0 || n_bits > p.polynomial_degree) return "n_bits must be in 1 ..= polynomial_degree";
+    if (B > 0x0fffffffu / n_bits) return "B * n_bits above 0x0fffffff";
+    return nullptr;
+}
+
+static spf_status packed_args(spf_ctx* c, size_t B, size_t n_bits, const void* in, const void* out)
+{
+    if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const char* why = packed_shape_error(c->prm, B, n_bits)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    return SPF_OK;
+}
+
+static spf_status launch_glwe_pack(spf_ctx* c, hipStream_t s, size_t B, size_t n_bits, const uint64_t* d_bits, uint64_t* d_out)
+{
+    const size_t pieces = (glwe_words(c->prm) + 255) / 256;
+    const unsigned blocks = (unsigned)std::min<size_t>(B * pieces, 8 * (size_t)c->n_cu);
+    hipLaunchKernelGGL(glwe_pack_bits_kernel, dim3(blocks), dim3(256), 0, s, d_bits, d_out, B, (uint32_t)n_bits, c->log_n,
+                       c->prm.glwe_size);
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+// Bits per workgroup: all of a ciphertext's when the batch alone fills the chip (each packed GLWE read once), fewer when it does
+// not, down to one bit per workgroup (a lone integer is unpacked by n_bits workgroups side by side).
+static spf_status launch_glwe_unpack(spf_ctx* c, hipStream_t s, size_t B, size_t n_bits, const uint64_t* d_glwe, uint64_t* d_lwe)
+{
+    const size_t rows = B * n_bits, target = 4 * (size_t)c->n_cu;
+    const uint32_t chunk = (uint32_t)std::min(n_bits, (rows + target - 1) / target);
+    const size_t items = B * ((n_bits + chunk - 1) / chunk);
+    const unsigned blocks = (unsigned)std::min<size_t>(items, 8 * (size_t)c->n_cu);
+    const size_t lds = (size_t)c->prm.glwe_size * c->prm.polynomial_degree * 8;
+    hipLaunchKernelGGL(glwe_unpack_l1_kernel, dim3(blocks), dim3(256), lds, s, d_glwe, d_lwe, B, (uint32_t)n_bits, chunk, c->log_n,
+                       c->prm.glwe_size);
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+spf_status spf_glwe_pack_dev(spf_ctx* c, void* stream, size_t B, size_t n_bits, const uint64_t* d_bits, uint64_t* d_out)
+{
+    spf_status st = packed_args(c, B, n_bits, d_bits, d_out);
+    if (st != SPF_OK || B == 0) return st;
+    const uintptr_t in0 = (uintptr_t)d_bits, in1 = in0 + B * n_bits * glwe_words(c->prm) * 8;
+    const uintptr_t out0 = (uintptr_t)d_out, out1 = out0 + B * glwe_words(c->prm) * 8;
+    if (out0 < in1 && in0 < out1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the packed output overlaps the bit GLWEs");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return launch_glwe_pack(c, (hipStream_t)stream, B, n_bits, d_bits, d_out);
+}
+
+spf_status spf_glwe_unpack_l1_dev(spf_ctx* c, void* stream, size_t B, size_t n_bits, const uint64_t* d_glwe, uint64_t* d_lwe1)
+{
+    spf_status st = packed_args(c, B, n_bits, d_glwe, d_lwe1);
+    if (st != SPF_OK || B == 0) return st;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return launch_glwe_unpack(c, (hipStream_t)stream, B, n_bits, d_glwe, d_lwe1);
+}
+
+// unpack, then FheOp::KeyswitchL1toL0 -> FheOp::CircuitBootstrap of every bit as spf_keyswitch_circuit_bootstrap_batch runs
+// them (same kernels for the same B * n_bits rows); the L1 and L0 LWEs stay in buffers of the context
+spf_status spf_unpack_circuit_bootstrap_dev(spf_ctx* c, void* stream, size_t B, size_t n_bits, const uint64_t* d_glwe,
+                                            double* d_ggsw)
+{
+    spf_status st = packed_args(c, B, n_bits, d_glwe, d_ggsw);
+    if (st != SPF_OK || B == 0) return st;
+    const size_t rows = B * n_bits;
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    st = ensure(c, c->unpack_l1, rows * lwe1_words(c->prm) * 8);
+    if (st == SPF_OK) st = ensure(c, c->unpack_l0, rows * lwe0_words(c->prm) * 8);
+    if (st == SPF_OK) st = launch_glwe_unpack(c, s, B, n_bits, d_glwe, (uint64_t*)c->unpack_l1.p);
+    if (st == SPF_OK) st = launch_keyswitch(c, s, rows, (const uint64_t*)c->unpack_l1.p, (uint64_t*)c->unpack_l0.p);
+    if (st == SPF_OK) st = circuit_bootstrap_chain(c, s, rows, (const uint64_t*)c->unpack_l0.p, d_ggsw, &c->scr, 0);
+    return st;
+}
+
 // At most one gate per CU: the four-waves-per-gate latency shape (a level of a gate graph); beyond
 // that two gates per workgroup, the streaming shape.
 static void launch_cmux_args(spf_ctx* c, hipStream_t s, const CmuxArgs& a)
@@ -1498,6 +1582,40 @@ spf_status spf_glwe_mul_xn_batch(spf_ctx* c, size_t B, const uint64_t* in, size_
     return glwe_linear_host(c, B, GLWE_MUL_XN, in, nullptr, n, out);
 }
 
+spf_status spf_glwe_pack_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* bits, uint64_t* out)
+{
+    spf_status s = packed_args(c, B, n_bits, bits, out);
+    if (s != SPF_OK || B == 0) return s;
+    const size_t gw = glwe_words(c->prm) * 8;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    STAGE_IN(c->in, bits, B * n_bits * gw);
+    s = ensure(c, c->out, B * gw);
+    if (s != SPF_OK) return s;
+    s = spf_glwe_pack_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    if (s != SPF_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * gw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SPF_OK;
+}
+
+spf_status spf_glwe_unpack_l1_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, uint64_t* lwe1_out)
+{
+    spf_status s = packed_args(c, B, n_bits, glwe, lwe1_out);
+    if (s != SPF_OK || B == 0) return s;
+    const size_t ow = B * n_bits * lwe1_words(c->prm) * 8;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    STAGE_IN(c->in, glwe, B * glwe_words(c->prm) * 8);
+    s = ensure(c, c->out, ow);
+    if (s != SPF_OK) return s;
+    s = spf_glwe_unpack_l1_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    if (s != SPF_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(lwe1_out, c->out.p, ow, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SPF_OK;
+}
+
 spf_status spf_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!sel || !a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
@@ -1671,6 +1789,23 @@ spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uin
     s = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->mid.p, (double*)c->out.p);
     if (s != SPF_OK) return s;
     HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, B * sw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SPF_OK;
+}
+
+spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, double* ggsw_out)
+{
+    spf_status s = packed_args(c, B, n_bits, glwe, ggsw_out);
+    if (s != SPF_OK || B == 0) return s;
+    const size_t sw = B * n_bits * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    std::lock_guard<std::recursive_mutex> whole(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    STAGE_IN(c->in, glwe, B * glwe_words(c->prm) * 8);
+    s = ensure(c, c->out, sw);
+    if (s != SPF_OK) return s;
+    s = spf_unpack_circuit_bootstrap_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (double*)c->out.p);
+    if (s != SPF_OK) return s;
+    HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, sw, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SPF_OK;
 }

@@ -1991,6 +1991,60 @@ __global__ void lwe_pack_kernel(const uint64_t* left, const uint64_t* right, uin
         out[i] = left[i] * shift + right[i];
 }
 
+// `DynamicGenericIntGraphNodes::pack` (parasol_runtime fluent/dynamic_generic_int_graph_nodes.rs:139-200): bit i of a
+// packed integer is the GLWE `in[b * n_bits + i]` times X^i (`MulXN(i)`), and the n_bits products are summed (a tree of
+// `GlweAdd`s).  Written out: out[b][p*N + j] = sum_{i < n_bits} s * in[b*n_bits + i][p*N + (j - i mod N)], s = -1 when
+// j < i, wrapping mod 2^64; addition mod 2^64 is associative, so this equals the reference's tree word for word.  One
+// thread per output word, consecutive j on consecutive lanes (the n_bits shifted reads of a wave are coalesced), a
+// block-level grid-stride loop over (ciphertext, 256-word piece) pieces: HBM-bound, reads n_bits GLWEs per output GLWE.
+// N (a power of two, 2^logN) and k at run time: serves tuned and generic contexts alike.
+__global__ void glwe_pack_bits_kernel(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, size_t B, uint32_t n_bits,
+                                      uint32_t logN, uint32_t k)
+{
+    const uint32_t N = 1u << logN, gw = (k + 1) << logN, pieces = (gw + blockDim.x - 1) / blockDim.x;
+    for (size_t item = blockIdx.x; item < B * pieces; item += gridDim.x) {
+        const size_t b = item / pieces;
+        const uint32_t r = (uint32_t)(item - b * pieces) * blockDim.x + threadIdx.x;
+        if (r >= gw) continue;
+        const uint32_t j = r & (N - 1);
+        const uint64_t* x = in + b * n_bits * gw + (r - j); // polynomial r / N of bit 0
+        uint64_t acc = 0;
+#pragma unroll 8
+        for (uint32_t i = 0; i < n_bits; i++, x += gw) acc += j >= i ? x[j - i] : (uint64_t)0 - x[j + N - i];
+        out[b * gw + r] = acc;
+    }
+}
+
+// `PackedDynamicGenericIntGraphNode::unpack` (parasol_runtime fluent/packed_dynamic_generic_int_graph_node.rs:24-39):
+// row b * n_bits + i of `lwe` = `sample_extract(glwe[b], i)` (glwe_ciphertext_ops.rs:31-76), the indexing of
+// sample_extract_kernel: mask word p*N + j = a[p*N + i - j] when j <= i, else -a[p*N + i + N - j]; body a[k*N + i].
+// One workgroup per (ciphertext, chunk of `chunk` bits), grid-stride over those items: the k*N mask words are staged in
+// LDS once per item (k*N*8 bytes of dynamic LDS: 16 KiB at N = 2048, k = 1; every generic shape stays below 64 KiB, as its
+// trace kernel needs more than 4x as much), so HBM reads a packed GLWE once, not once per bit, and the bits' rows are
+// written from LDS.
+__global__ void glwe_unpack_l1_kernel(const uint64_t* __restrict__ glwe, uint64_t* __restrict__ lwe, size_t B, uint32_t n_bits,
+                                      uint32_t chunk, uint32_t logN, uint32_t k)
+{
+    extern __shared__ uint64_t unpack_mask[];
+    const uint32_t N = 1u << logN, kN = k << logN, chunks = (n_bits + chunk - 1) / chunk;
+    for (size_t item = blockIdx.x; item < B * chunks; item += gridDim.x) {
+        const size_t b = item / chunks;
+        const uint32_t i0 = (uint32_t)(item - b * chunks) * chunk, i1 = min(i0 + chunk, n_bits);
+        const uint64_t* a = glwe + b * (kN + N);
+        __syncthreads(); // the previous item's rows have been read out of the LDS
+        for (uint32_t w = threadIdx.x; w < kN; w += blockDim.x) unpack_mask[w] = a[w];
+        __syncthreads();
+        for (uint32_t i = i0; i < i1; i++) {
+            uint64_t* o = lwe + (b * n_bits + i) * (kN + 1);
+            if (threadIdx.x == 0) o[kN] = a[kN + i];
+            for (uint32_t w = threadIdx.x; w < kN; w += blockDim.x) {
+                const uint32_t j = w & (N - 1), p = w - j;
+                o[w] = j <= i ? unpack_mask[p + i - j] : (uint64_t)0 - unpack_mask[p + i + N - j];
+            }
+        }
+    }
+}
+
 // words u64 from `src` (pinned host memory, read by the GPU over PCIe, or device memory) to `dst`: the pool's copy-in.  A kernel
 // on the batch's own stream instead of a hipMemcpyAsync: the runtime hands those to ONE in-order SDMA queue per direction pair,
 // where a host-to-device copy of a new batch stood behind the device-to-host copy of another batch that was still waiting for
