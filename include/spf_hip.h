@@ -22,7 +22,8 @@
  *     interleaved {double re, double im} (num_complex::Complex<f64>).
  *   - "_batch" entry points take HOST pointers (what a Rust shim holding `&[u64]` passes) and
  *     stage through device memory; "_dev" entry points take DEVICE pointers plus a hipStream_t
- *     (passed as void*) and are asynchronous on that stream.
+ *     (passed as void*) and are asynchronous on that stream.  A "_batch" call returns only after
+ *     the device is done with the caller's buffers, on failure as well as on success.
  *   - a context is bound to one GPU.  Calls on one context are serialised internally (thread-safe); use one context per
  *     stream for concurrency.  A device group (spf_group_*) holds one context per GPU of the node for ONE host process.
  */

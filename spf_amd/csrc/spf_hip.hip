@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <new>
 #include <string>
@@ -266,6 +267,14 @@ GenericShape generic_shape(const spf_ctx* c)
     return g;
 }
 
+spf_status blind_rotate_args(spf_ctx* c, size_t B, uint32_t log_chi, uint32_t log_v)
+{
+    if (B > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    // modulus switch needs log_modulus - log_v >= 1 and shifts below 64
+    if (log_v >= c->log_n + 1 || log_chi >= 52) return fail(c, SPF_ERR_INVALID_ARGUMENT, "log_v / log_chi out of range");
+    return SPF_OK;
+}
+
 spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_lwe,
                                const uint64_t* d_lut, size_t lut_stride, uint32_t log_chi,
                                uint32_t log_v, uint64_t body_rotate, uint64_t* d_out,
@@ -273,9 +282,10 @@ spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64
 {
     if (!c->bsk_ready) return fail(c, SPF_ERR_NO_KEY, "bootstrap key not loaded");
     if (B == 0) return SPF_OK;
-    if (B > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    // modulus switch needs log_modulus - log_v >= 1 and shifts below 64
-    if (log_v >= c->log_n + 1 || log_chi >= 52) return fail(c, SPF_ERR_INVALID_ARGUMENT, "log_v / log_chi out of range");
+    {
+        spf_status st = blind_rotate_args(c, B, log_chi, log_v);
+        if (st != SPF_OK) return st;
+    }
     if (c->generic) {
         GenericPbsArgs ga{};
         ga.g = generic_shape(c);
@@ -481,6 +491,53 @@ bool params_supported(const spf_params& p, std::string& why)
     if (p.ks_radix_log == 0 || p.ks_radix_log * p.ks_radix_count > 32) { why = "ks_radix must satisfy 0 < l*logB <= 32"; return false; }
     if (p.cbs_radix_count == 0 || p.cbs_radix_count >= 8 || p.cbs_radix_log == 0) { why = "cbs_radix.count must be in 1..7"; return false; }
     return true;
+}
+
+// ---- staging of the host-pointer forms
+
+// `bytes` from the caller's `host` into the context's buffer `buf` (a null `host`: an operand this call does not have)
+struct HostIn {
+    DevBuf& buf;
+    const void* host;
+    size_t bytes;
+};
+
+// The one way a host-pointer form reaches the device, after its arguments are checked: under c->mu (the staging buffers are
+// shared: one caller at a time), stage `ins`, make c->out hold `out_bytes`, then `work` enqueues on c->stream.  Once anything is
+// enqueued, no return before c->stream is idle: copies from the caller's buffers may still be in flight, and the caller is free
+// to release those after an error.  The first failure's status and message stay in place.
+template <class Work>
+spf_status staged(spf_ctx* c, std::initializer_list<HostIn> ins, size_t out_bytes, Work&& work)
+{
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    auto enqueue = [&]() -> spf_status {
+        for (const HostIn& in : ins) {
+            if (!in.host) continue;
+            spf_status s = ensure(c, in.buf, in.bytes);
+            if (s != SPF_OK) return s;
+            HIPCHK(c, hipMemcpyAsync(in.buf.p, in.host, in.bytes, hipMemcpyHostToDevice, c->stream));
+        }
+        spf_status s = ensure(c, c->out, out_bytes);
+        if (s != SPF_OK) return s;
+        return work();
+    };
+    const spf_status st = enqueue();
+    if (st != SPF_OK) (void)hipStreamSynchronize(c->stream);
+    return st;
+}
+
+// staged(), then c->out to the caller's `host_out`
+template <class Work>
+spf_status host_call(spf_ctx* c, std::initializer_list<HostIn> ins, size_t out_bytes, void* host_out, Work&& work)
+{
+    return staged(c, ins, out_bytes, [&]() -> spf_status {
+        spf_status s = work();
+        if (s != SPF_OK) return s;
+        HIPCHK(c, hipMemcpyAsync(host_out, c->out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SPF_OK;
+    });
 }
 
 } // namespace
@@ -890,6 +947,13 @@ spf_status spf_circuit_bootstrap_pbs_dev(spf_ctx* c, void* stream, size_t B, con
                                (uint64_t)1 << 62, d_out, glwe_words(c->prm), false);
 }
 
+// the circuit-bootstrap tail launches cbs_radix_count units per ciphertext
+static spf_status tail_batch_args(spf_ctx* c, size_t B)
+{
+    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    return SPF_OK;
+}
+
 static spf_status tail_supported(spf_ctx* c)
 {
     const spf_params& p = c->prm;
@@ -988,10 +1052,11 @@ spf_status spf_mod_switch_trace_and_rotate_dev(spf_ctx* c, void* stream, size_t 
 {
     if (!c || (B && (!d_glwe || !d_glev))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    spf_status st = tail_batch_args(c, B);
+    if (st != SPF_OK) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    spf_status st = tail_supported(c);
+    st = tail_supported(c);
     if (st != SPF_OK) return st;
     return launch_trace(c, (hipStream_t)stream, B, d_glwe, d_glev);
 }
@@ -1000,10 +1065,11 @@ spf_status spf_scheme_switch_dev(spf_ctx* c, void* stream, size_t B, const uint6
 {
     if (!c || (B && (!d_glev || !d_ggsw))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    spf_status st = tail_batch_args(c, B);
+    if (st != SPF_OK) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
-    spf_status st = tail_supported(c);
+    st = tail_supported(c);
     if (st != SPF_OK) return st;
     return launch_scheme_switch(c, (hipStream_t)stream, B, d_glev, d_ggsw);
 }
@@ -1030,7 +1096,8 @@ spf_status spf_circuit_bootstrap_dev(spf_ctx* c, void* stream, size_t B, const u
 {
     if (!c || (B && (!d_lwe || !d_ggsw))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    spf_status st = tail_batch_args(c, B);
+    if (st != SPF_OK) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     return circuit_bootstrap_chain(c, (hipStream_t)stream, B, d_lwe, d_ggsw, &c->scr, 0);
@@ -1395,28 +1462,15 @@ spf_status spf_multiply_glwe_ggsw_dev(spf_ctx* c, void* stream, size_t B, const 
 }
 
 // ---------------------------------------------------------------- host-pointer forms
-
-#define STAGE_IN(buf, host, bytes)                                                                \
-    do {                                                                                          \
-        spf_status s_ = ensure(c, buf, bytes);                                                    \
-        if (s_ != SPF_OK) return s_;                                                              \
-        HIPCHK(c, hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, c->stream));          \
-    } while (0)
+//
+// Each form checks every argument it can see, then reaches the device through staged() / host_call() only.
 
 spf_status spf_keyswitch_lwe_l1_lwe_l0_batch(spf_ctx* c, size_t B, const uint64_t* in, uint64_t* out)
 {
     if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, in, B * lwe1_words(c->prm) * 8);
-    spf_status s = ensure(c, c->out, B * lwe0_words(c->prm) * 8);
-    if (s != SPF_OK) return s;
-    s = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * lwe0_words(c->prm) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    return host_call(c, {{c->in, in, B * lwe1_words(c->prm) * 8}}, B * lwe0_words(c->prm) * 8, out,
+                     [&] { return launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p); });
 }
 
 // Bootstrap a device-resident batch and bring the outputs to the caller's host buffer, in SLICES of one
@@ -1471,28 +1525,20 @@ static spf_status pbs_host(spf_ctx* c, size_t B, const uint64_t* lwe, const uint
 {
     if (!c || (B && (!lwe || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, lwe, B * lwe0_words(c->prm) * 8);
-    if (rhs) {
-        STAGE_IN(c->mid, rhs, B * lwe0_words(c->prm) * 8);
-        spf_status s = launch_lwe_pack(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, shift_bits,
-                                       (uint64_t*)c->in.p);
-        if (s != SPF_OK) return s;
-    }
-    const uint64_t* d_lut = c->d_cbs_lut;
-    if (lut) {
-        size_t luts = lut_stride ? B : 1;
-        if (lut_stride && lut_stride < glwe_words(c->prm)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "lut_stride smaller than a GLWE");
-        size_t words = lut_stride ? (luts - 1) * lut_stride + glwe_words(c->prm) : glwe_words(c->prm);
-        STAGE_IN(c->aux, lut, words * 8);
-        d_lut = (const uint64_t*)c->aux.p;
-    }
-    size_t ow = extract ? lwe1_words(c->prm) : glwe_words(c->prm);
-    spf_status s = ensure(c, c->out, B * ow * 8);
+    if (lut_stride && lut_stride < glwe_words(c->prm)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "lut_stride smaller than a GLWE");
+    spf_status s = blind_rotate_args(c, B, log_chi, log_v);
     if (s != SPF_OK) return s;
-    return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->in.p, d_lut, lut ? lut_stride : 0, log_chi, log_v, rot, ow,
-                                    extract, out);
+    const size_t lw = B * lwe0_words(c->prm) * 8, ow = extract ? lwe1_words(c->prm) : glwe_words(c->prm);
+    const size_t lut_words = lut_stride ? (B - 1) * lut_stride + glwe_words(c->prm) : glwe_words(c->prm);
+    return staged(c, {{c->in, lwe, lw}, {c->mid, rhs, lw}, {c->aux, lut, lut_words * 8}}, B * ow * 8, [&]() -> spf_status {
+        if (rhs) {
+            spf_status st = launch_lwe_pack(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, shift_bits,
+                                            (uint64_t*)c->in.p);
+            if (st != SPF_OK) return st;
+        }
+        return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->in.p, lut ? (const uint64_t*)c->aux.p : c->d_cbs_lut,
+                                        lut ? lut_stride : 0, log_chi, log_v, rot, ow, extract, out);
+    });
 }
 
 spf_status spf_generalized_pbs_batch(spf_ctx* c, size_t B, const uint64_t* lwe, const uint64_t* lut, size_t lut_stride,
@@ -1528,58 +1574,37 @@ spf_status spf_sample_extract_l1_batch(spf_ctx* c, size_t B, const uint64_t* glw
     if (!c || (B && (!glwe || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (idx >= c->prm.polynomial_degree) return fail(c, SPF_ERR_INVALID_ARGUMENT, "sample_extract index >= polynomial_degree");
     if (B == 0) return SPF_OK;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->in, glwe, B * glwe_words(c->prm) * 8);
-        spf_status s = ensure(c, c->out, B * lwe1_words(c->prm) * 8);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_sample_extract_l1_dev(c, c->stream, B, (const uint64_t*)c->in.p, idx, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * lwe1_words(c->prm) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
-}
-
-static spf_status glwe_linear_host(spf_ctx* c, size_t B, uint32_t op, const uint64_t* a, const uint64_t* b, size_t n,
-                                   uint64_t* out)
-{
-    if (!c || (B && (!a || !out || (op == GLWE_XOR && !b)))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm) * 8;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->in, a, B * gw);
-        if (op == GLWE_XOR) STAGE_IN(c->mid, b, B * gw);
-        spf_status s = ensure(c, c->out, B * gw);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = glwe_linear_dev(c, c->stream, B, op, (const uint64_t*)c->in.p,
-                                   op == GLWE_XOR ? (const uint64_t*)c->mid.p : nullptr,
-                                   (uint32_t)(n % (2 * (size_t)c->prm.polynomial_degree)), (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * gw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, B * lwe1_words(c->prm) * 8, out, [&] {
+        return spf_sample_extract_l1_dev(c, c->stream, B, (const uint64_t*)c->in.p, idx, (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_glwe_not_batch(spf_ctx* c, size_t B, const uint64_t* in, uint64_t* out)
 {
-    return glwe_linear_host(c, B, GLWE_NOT, in, nullptr, 0, out);
+    if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (B == 0) return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, in, gw}}, gw, out,
+                     [&] { return spf_glwe_not_dev(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p); });
 }
 
 spf_status spf_glwe_xor_batch(spf_ctx* c, size_t B, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
-    return glwe_linear_host(c, B, GLWE_XOR, a, b, 0, out);
+    if (!c || (B && (!a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (B == 0) return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, a, gw}, {c->mid, b, gw}}, gw, out, [&] {
+        return spf_glwe_xor_dev(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_glwe_mul_xn_batch(spf_ctx* c, size_t B, const uint64_t* in, size_t n, uint64_t* out)
 {
-    return glwe_linear_host(c, B, GLWE_MUL_XN, in, nullptr, n, out);
+    if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (B == 0) return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, in, gw}}, gw, out,
+                     [&] { return spf_glwe_mul_xn_dev(c, c->stream, B, (const uint64_t*)c->in.p, n, (uint64_t*)c->out.p); });
 }
 
 spf_status spf_glwe_pack_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* bits, uint64_t* out)
@@ -1587,101 +1612,51 @@ spf_status spf_glwe_pack_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64
     spf_status s = packed_args(c, B, n_bits, bits, out);
     if (s != SPF_OK || B == 0) return s;
     const size_t gw = glwe_words(c->prm) * 8;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, bits, B * n_bits * gw);
-    s = ensure(c, c->out, B * gw);
-    if (s != SPF_OK) return s;
-    s = spf_glwe_pack_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * gw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    return host_call(c, {{c->in, bits, B * n_bits * gw}}, B * gw, out, [&] {
+        return spf_glwe_pack_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_glwe_unpack_l1_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, uint64_t* lwe1_out)
 {
     spf_status s = packed_args(c, B, n_bits, glwe, lwe1_out);
     if (s != SPF_OK || B == 0) return s;
-    const size_t ow = B * n_bits * lwe1_words(c->prm) * 8;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, glwe, B * glwe_words(c->prm) * 8);
-    s = ensure(c, c->out, ow);
-    if (s != SPF_OK) return s;
-    s = spf_glwe_unpack_l1_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(lwe1_out, c->out.p, ow, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, B * n_bits * lwe1_words(c->prm) * 8, lwe1_out, [&] {
+        return spf_glwe_unpack_l1_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!sel || !a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm) * 8, sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->aux, sel, B * sw);
-        STAGE_IN(c->in, a, B * gw);
-        STAGE_IN(c->mid, b, B * gw);
-        spf_status s = ensure(c, c->out, B * gw);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p,
-                                (const uint64_t*)c->mid.p, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * gw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->aux, sel, sw}, {c->in, a, gw}, {c->mid, b, gw}}, gw, out, [&] {
+        return spf_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p,
+                            (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_glev_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!sel || !a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t ev = glwe_words(c->prm) * 8 * c->prm.cbs_radix_count, sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->aux, sel, B * sw);
-        STAGE_IN(c->in, a, B * ev);
-        STAGE_IN(c->mid, b, B * ev);
-        spf_status s = ensure(c, c->out, B * ev);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_glev_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p,
-                                     (const uint64_t*)c->mid.p, (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * ev, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t ev = B * glwe_words(c->prm) * 8 * c->prm.cbs_radix_count;
+    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->aux, sel, sw}, {c->in, a, ev}, {c->mid, b, ev}}, ev, out, [&] {
+        return spf_glev_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p,
+                                 (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_multiply_glwe_ggsw_batch(spf_ctx* c, size_t B, const uint64_t* glwe, const double* ggsw, uint64_t* out)
 {
     if (!c || (B && (!glwe || !ggsw || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm) * 8, sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->aux, ggsw, B * sw);
-        STAGE_IN(c->in, glwe, B * gw);
-        spf_status s = ensure(c, c->out, B * gw);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_multiply_glwe_ggsw_dev(c, c->stream, B, (const uint64_t*)c->in.p, (const double*)c->aux.p,
-                                              (uint64_t*)c->out.p);
-    if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(out, c->out.p, B * gw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->aux, ggsw, sw}, {c->in, glwe, gw}}, gw, out, [&] {
+        return spf_multiply_glwe_ggsw_dev(c, c->stream, B, (const uint64_t*)c->in.p, (const double*)c->aux.p, (uint64_t*)c->out.p);
+    });
 }
 
 static spf_status load_fft_key(spf_ctx* c, int which, const double* src, size_t n_complex, size_t want, bool* ready)
@@ -1715,82 +1690,50 @@ spf_status spf_mod_switch_trace_and_rotate_batch(spf_ctx* c, size_t B, const uin
 {
     if (!c || (B && (!glwe_in || !glev_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm) * 8, ev = gw * c->prm.cbs_radix_count;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->in, glwe_in, B * gw);
-        spf_status s = ensure(c, c->out, B * ev);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_mod_switch_trace_and_rotate_dev(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    spf_status s = tail_batch_args(c, B);
     if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(glev_out, c->out.p, B * ev, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t gw = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, glwe_in, gw}}, gw * c->prm.cbs_radix_count, glev_out, [&] {
+        return spf_mod_switch_trace_and_rotate_dev(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
 }
 
 spf_status spf_scheme_switch_batch(spf_ctx* c, size_t B, const uint64_t* glev_in, double* ggsw_out)
 {
     if (!c || (B && (!glev_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t ev = glwe_words(c->prm) * 8 * c->prm.cbs_radix_count;
-    const size_t sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->in, glev_in, B * ev);
-        spf_status s = ensure(c, c->out, B * sw);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_scheme_switch_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p);
+    spf_status s = tail_batch_args(c, B);
     if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, B * sw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t ev = B * glwe_words(c->prm) * 8 * c->prm.cbs_radix_count;
+    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->in, glev_in, ev}}, sw, ggsw_out,
+                     [&] { return spf_scheme_switch_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p); });
 }
 
 spf_status spf_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe0_in, double* ggsw_out)
 {
     if (!c || (B && (!lwe0_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu); // staging buffers are shared: one caller at a time
-    {
-        HIPCHK(c, hipSetDevice(c->device));
-        STAGE_IN(c->in, lwe0_in, B * lwe0_words(c->prm) * 8);
-        spf_status s = ensure(c, c->out, B * sw);
-        if (s != SPF_OK) return s;
-    }
-    spf_status s = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p);
+    spf_status s = tail_batch_args(c, B);
     if (s != SPF_OK) return s;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, B * sw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->in, lwe0_in, B * lwe0_words(c->prm) * 8}}, sw, ggsw_out,
+                     [&] { return spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p); });
 }
 
 spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe1_in, double* ggsw_out)
 {
     if (!c || (B && (!lwe1_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    const size_t sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, lwe1_in, B * lwe1_words(c->prm) * 8);
-    spf_status s = ensure(c, c->mid, B * lwe0_words(c->prm) * 8); // the level-0 LWE never leaves the device
+    spf_status s = tail_batch_args(c, B);
     if (s != SPF_OK) return s;
-    s = ensure(c, c->out, B * sw);
-    if (s != SPF_OK) return s;
-    s = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
-    if (s != SPF_OK) return s;
-    s = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->mid.p, (double*)c->out.p);
-    if (s != SPF_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, B * sw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->in, lwe1_in, B * lwe1_words(c->prm) * 8}}, sw, ggsw_out, [&] {
+        spf_status st = ensure(c, c->mid, B * lwe0_words(c->prm) * 8); // the level-0 LWE never leaves the device
+        if (st == SPF_OK) st = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
+        if (st == SPF_OK) st = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->mid.p, (double*)c->out.p);
+        return st;
+    });
 }
 
 spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, double* ggsw_out)
@@ -1798,33 +1741,25 @@ spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx* c, size_t B, size_t n_bit
     spf_status s = packed_args(c, B, n_bits, glwe, ggsw_out);
     if (s != SPF_OK || B == 0) return s;
     const size_t sw = B * n_bits * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    std::lock_guard<std::recursive_mutex> whole(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, glwe, B * glwe_words(c->prm) * 8);
-    s = ensure(c, c->out, sw);
-    if (s != SPF_OK) return s;
-    s = spf_unpack_circuit_bootstrap_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (double*)c->out.p);
-    if (s != SPF_OK) return s;
-    HIPCHK(c, hipMemcpyAsync(ggsw_out, c->out.p, sw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SPF_OK;
+    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, sw, ggsw_out, [&] {
+        return spf_unpack_circuit_bootstrap_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (double*)c->out.p);
+    });
 }
 
 spf_status spf_gate_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe1, uint64_t* glwe_out)
 {
     if (!c || (B && (!lwe1 || !glwe_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (B == 0) return SPF_OK;
-    std::lock_guard<std::recursive_mutex> g(c->mu);
-    HIPCHK(c, hipSetDevice(c->device));
-    STAGE_IN(c->in, lwe1, B * lwe1_words(c->prm) * 8);
-    spf_status s = ensure(c, c->mid, B * lwe0_words(c->prm) * 8);
+    const uint32_t log_v = ceil_log2(c->prm.cbs_radix_count);
+    spf_status s = blind_rotate_args(c, B, 0, log_v);
     if (s != SPF_OK) return s;
-    s = ensure(c, c->out, B * glwe_words(c->prm) * 8);
-    if (s != SPF_OK) return s;
-    s = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
-    if (s != SPF_OK) return s;
-    return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->mid.p, c->d_cbs_lut, 0, 0, ceil_log2(c->prm.cbs_radix_count),
-                                    (uint64_t)1 << 62, glwe_words(c->prm), false, glwe_out);
+    return staged(c, {{c->in, lwe1, B * lwe1_words(c->prm) * 8}}, B * glwe_words(c->prm) * 8, [&] {
+        spf_status st = ensure(c, c->mid, B * lwe0_words(c->prm) * 8); // the level-0 LWE never leaves the device
+        if (st == SPF_OK) st = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
+        if (st != SPF_OK) return st;
+        return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->mid.p, c->d_cbs_lut, 0, 0, log_v, (uint64_t)1 << 62,
+                                        glwe_words(c->prm), false, glwe_out);
+    });
 }
 
 // ---------------------------------------------------------------- measurement hooks

@@ -7,7 +7,8 @@
 // Exercised: spf_ciphertext_{words,from_bincode,to_bincode} (safe_bincode::deserialize of the ciphertext newtypes),
 // spf_load_compute_key_bincode's size walk (ComputeKey), spf_generate_lut, params_supported / params_generic, and
 // spf_graph_add_{input,trivial,op,output} (the reference validates per task, task.rs:26-31) — every call must return a status,
-// never crash, never touch memory outside its buffers (every destination is an exact-size heap allocation).
+// never crash, never touch memory outside its buffers (every destination is an exact-size heap allocation).  Before the random
+// cases, a fixed table calls every spf_*_batch entry point with one bad argument each (batch_forms_refuse_bad_arguments).
 // Seeds: the reference's own malformed vector (parasol_runtime/src/safe_bincode.rs:58-66, :105-117) and valid serializations.
 //
 // usage: fuzz_host <cases> [seed]
@@ -54,13 +55,77 @@ std::vector<uint8_t> mutate(const std::vector<uint8_t>& seed, Rng& r)
     return v;
 }
 
-// a context made by hand: only the fields the host-side validators read (no device, no HIP call)
+// a context made by hand: only the fields the host-side validators read (no device: a HIP call that slips through fails at
+// hipSetDevice)
 void fake_ctx(spf_ctx& c, const spf_params& p, bool generic)
 {
     c.prm = p;
+    c.device = -1;
     c.generic = generic;
     c.log_n = 0;
     while ((1u << c.log_n) < p.polynomial_degree) c.log_n++;
+}
+
+// Every spf_*_batch entry point with exactly one bad argument: each must be refused as SPF_ERR_INVALID_ARGUMENT before its first
+// HIP call (the context's device is -1, so a call that reaches HIP returns SPF_ERR_HIP instead).  The buffers are exact-size heap
+// allocations for B ciphertexts; the batch-limit cases hand the same buffers with a larger B and must not read them.
+bool batch_forms_refuse_bad_arguments(spf_ctx* c)
+{
+    const spf_params& p = c->prm;
+    const size_t B = 2, N = p.polynomial_degree, l = p.cbs_radix_count, nb = 3;
+    const size_t l0 = lwe0_words(p), l1 = lwe1_words(p), gw = glwe_words(p), sw = 2 * ggsw_fft_complex(p, p.cbs_radix_count);
+    const size_t over_br = (size_t)0x7fffffff + 1, over_tail = (size_t)0x0fffffff + 1; // one past each batch limit
+    std::vector<uint64_t> lwe0(B * l0), rhs(B * l0), lwe1(B * l1), glwe(B * gw), glwe_b(B * gw), lut(B * gw), glev(B * l * gw),
+        bits(B * nb * gw), o_lwe0(B * l0), o_lwe1(B * l1), o_glwe(B * gw), o_glev(B * l * gw), o_bits(B * nb * l1);
+    std::vector<double> ggsw(B * sw), o_ggsw(B * sw), o_ggsw_bits(B * nb * sw);
+    bool ok = true;
+    auto expect = [&](const char* call, spf_status st) {
+        if (st == SPF_ERR_INVALID_ARGUMENT) return;
+        fprintf(stderr, "spf_*_batch bad argument: %s returned %d, not SPF_ERR_INVALID_ARGUMENT (%s)\n", call, st, c->err.c_str());
+        ok = false;
+    };
+    expect("keyswitch_lwe_l1_lwe_l0 null in", spf_keyswitch_lwe_l1_lwe_l0_batch(c, B, nullptr, o_lwe0.data()));
+    expect("generalized_pbs null lut", spf_generalized_pbs_batch(c, B, lwe0.data(), nullptr, 0, 0, 0, 0, o_glwe.data()));
+    expect("generalized_pbs lut_stride 1", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 1, 0, 0, 0, o_glwe.data()));
+    expect("generalized_pbs log_v 12", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 0, 12, 0, o_glwe.data()));
+    expect("generalized_pbs log_chi 52", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 52, 0, 0, o_glwe.data()));
+    expect("generalized_pbs B 0x80000000",
+           spf_generalized_pbs_batch(c, over_br, lwe0.data(), lut.data(), 0, 0, 0, 0, o_glwe.data()));
+    expect("pbs_univariate lut_stride 1", spf_pbs_univariate_batch(c, B, lwe0.data(), lut.data(), 1, o_lwe1.data()));
+    expect("pbs_univariate null in", spf_pbs_univariate_batch(c, B, nullptr, lut.data(), 0, o_lwe1.data()));
+    expect("pbs_bivariate null right", spf_pbs_bivariate_batch(c, B, lwe0.data(), nullptr, lut.data(), 0, 2, o_lwe1.data()));
+    expect("pbs_bivariate plaintext_bits 64",
+           spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 0, 64, o_lwe1.data()));
+    expect("pbs_bivariate lut_stride 1", spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 1, 2, o_lwe1.data()));
+    expect("circuit_bootstrap_pbs null out", spf_circuit_bootstrap_pbs_batch(c, B, lwe0.data(), nullptr));
+    expect("circuit_bootstrap_pbs B 0x80000000", spf_circuit_bootstrap_pbs_batch(c, over_br, lwe0.data(), o_glwe.data()));
+    expect("circuit_bootstrap null in", spf_circuit_bootstrap_batch(c, B, nullptr, o_ggsw.data()));
+    expect("circuit_bootstrap B 0x10000000", spf_circuit_bootstrap_batch(c, over_tail, lwe0.data(), o_ggsw.data()));
+    expect("mod_switch_trace_and_rotate null out", spf_mod_switch_trace_and_rotate_batch(c, B, glwe.data(), nullptr));
+    expect("mod_switch_trace_and_rotate B 0x10000000",
+           spf_mod_switch_trace_and_rotate_batch(c, over_tail, glwe.data(), o_glev.data()));
+    expect("scheme_switch null in", spf_scheme_switch_batch(c, B, nullptr, o_ggsw.data()));
+    expect("scheme_switch B 0x10000000", spf_scheme_switch_batch(c, over_tail, glev.data(), o_ggsw.data()));
+    expect("sample_extract_l1 idx N", spf_sample_extract_l1_batch(c, B, glwe.data(), N, o_lwe1.data()));
+    expect("sample_extract_l1 null out", spf_sample_extract_l1_batch(c, B, glwe.data(), 0, nullptr));
+    expect("glwe_not null in", spf_glwe_not_batch(c, B, nullptr, o_glwe.data()));
+    expect("glwe_xor null b", spf_glwe_xor_batch(c, B, glwe.data(), nullptr, o_glwe.data()));
+    expect("glwe_mul_xn null out", spf_glwe_mul_xn_batch(c, B, glwe.data(), 3, nullptr));
+    expect("glwe_pack n_bits 0", spf_glwe_pack_batch(c, B, 0, bits.data(), o_glwe.data()));
+    expect("glwe_pack null out", spf_glwe_pack_batch(c, B, nb, bits.data(), nullptr));
+    expect("glwe_unpack_l1 n_bits N + 1", spf_glwe_unpack_l1_batch(c, B, N + 1, glwe.data(), o_bits.data()));
+    expect("cmux null sel", spf_cmux_batch(c, B, nullptr, glwe.data(), glwe_b.data(), o_glwe.data()));
+    expect("glev_cmux null b", spf_glev_cmux_batch(c, B, ggsw.data(), glev.data(), nullptr, o_glev.data()));
+    expect("multiply_glwe_ggsw null ggsw", spf_multiply_glwe_ggsw_batch(c, B, glwe.data(), nullptr, o_glwe.data()));
+    expect("gate_bootstrap null in", spf_gate_bootstrap_batch(c, B, nullptr, o_glwe.data()));
+    expect("gate_bootstrap B 0x80000000", spf_gate_bootstrap_batch(c, over_br, lwe1.data(), o_glwe.data()));
+    expect("keyswitch_circuit_bootstrap null out", spf_keyswitch_circuit_bootstrap_batch(c, B, lwe1.data(), nullptr));
+    expect("keyswitch_circuit_bootstrap B 0x10000000",
+           spf_keyswitch_circuit_bootstrap_batch(c, over_tail, lwe1.data(), o_ggsw.data()));
+    expect("unpack_circuit_bootstrap B * n_bits 0x10000002",
+           spf_unpack_circuit_bootstrap_batch(c, over_tail / 2 + 1, 2, glwe.data(), o_ggsw_bits.data()));
+    expect("unpack_circuit_bootstrap null in", spf_unpack_circuit_bootstrap_batch(c, B, nb, nullptr, o_ggsw_bits.data()));
+    return ok;
 }
 
 } // namespace
@@ -107,6 +172,7 @@ int main(int argc, char** argv)
     spf_ctx tiny_ctx, dflt_ctx;
     fake_ctx(tiny_ctx, tiny, true);
     fake_ctx(dflt_ctx, dflt, false);
+    if (!batch_forms_refuse_bad_arguments(&dflt_ctx)) return 1;
     std::vector<uint8_t> key_seed;
     {
         const size_t want[4] = {(size_t)tiny.lwe_dimension * ggsw_fft_complex(tiny, tiny.pbs_radix_count),
