@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from tests import poly_ref as R
 import spf_amd
 from tests.util import M64, dev_bootstrap, keyset, random_glwe, random_lwe_batch, to_engine_params
 
@@ -219,6 +220,8 @@ def test_external_product_fft_noise_at_pbs_shape():
         for j in range(2):
             for q in range(2):
                 exact[q * N:(q + 1) * N] += O.negacyclic_mul_exact(digs[j], G[p, 1 - j, q])
+    # the exact side no longer rests on the oracle alone: tests/poly_ref.py states the same step independently
+    assert np.array_equal(exact.reshape(2, N), R.generalized_pbs(lwe[0], d0.reshape(2, N), G[None], P.pbs_radix_log, P.pbs_count))
     dist = _torus_distance(got, exact)
     assert dist.max() < 2.0 ** -26, dist.max()
     assert dist.max() > 0.0          # it IS a floating-point transform: not exact, just small

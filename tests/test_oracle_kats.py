@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from tests import poly_ref as R
 
 M64 = (1 << 64) - 1
 
@@ -344,6 +345,8 @@ def test_external_product_fft_error_at_cryptographic_magnitude():
         for j in range(2):
             for q in range(2):
                 exact[q * N:(q + 1) * N] += O.negacyclic_mul_exact(digs[j], G[p, 1 - j, q])
+    # the exact side no longer rests on the oracle alone: tests/poly_ref.py states the same step independently
+    assert np.array_equal(exact.reshape(2, N), R.generalized_pbs(lwe, d0.reshape(2, N), G[None], P.pbs_radix_log, P.pbs_count))
     dist = np.abs((got - exact).astype(np.int64).astype(np.float64)) / 2.0 ** 64
     assert 0.0 < dist.max() < 2.0 ** -26
     assert np.sqrt((dist ** 2).mean()) < 2.0 ** -29
