@@ -34,6 +34,19 @@ struct ComputeKey {
     size_t ss_key_complex = 0;
 };
 
+// `ComputeKeyNonFft` (crypto/keys.rs:145-159): the same keys in standard (integer) form, Torus<u64> words in the reference's
+// layouts; `ComputeKeyNonFft::fft` (keys.rs:258-282) happens on the device.
+struct ComputeKeyNonFft {
+    const uint64_t* bs_key;   // BootstrapKey<u64>
+    size_t bs_key_words;
+    const uint64_t* ks_key;   // LweKeyswitchKey<u64>
+    size_t ks_key_words;
+    const uint64_t* auto_key = nullptr; // AutomorphismKey<u64>
+    size_t auto_key_words = 0;
+    const uint64_t* ss_key = nullptr;   // SchemeSwitchKey<u64>
+    size_t ss_key_words = 0;
+};
+
 // One `Evaluation` per process, shared by every worker thread, as in the reference — and it owns EVERY listed GPU: a device
 // group (spf_group_*) with the keys replicated inside the library; a batch is cut over the devices, B = 1 lands on the first one.
 class Evaluation {
@@ -55,6 +68,24 @@ class Evaluation {
         }
     }
     Evaluation(const ComputeKey& key, const spf_params& params, int device = 0) : Evaluation(key, params, std::vector<int>{device}) {}
+    // Evaluation::new over `ComputeKeyNonFft::fft(params)` (keys.rs:258-282): the keys arrive as integer words and are transformed
+    // on the first device, the spectra replicated to the others
+    Evaluation(const ComputeKeyNonFft& key, const spf_params& params, const std::vector<int>& devices) : params_(params)
+    {
+        check_create(spf_group_create(&params, devices.data(), (int)devices.size(), &grp_));
+        ctx_ = spf_group_ctx(grp_, 0);
+        try {
+            check(spf_group_load_bootstrap_key_std(grp_, key.bs_key, key.bs_key_words));
+            if (key.ks_key) check(spf_group_load_keyswitch_key(grp_, key.ks_key, key.ks_key_words));
+            if (key.auto_key) check(spf_group_load_automorphism_key_std(grp_, key.auto_key, key.auto_key_words));
+            if (key.ss_key) check(spf_group_load_scheme_switch_key_std(grp_, key.ss_key, key.ss_key_words));
+        } catch (...) {
+            spf_group_destroy(grp_);
+            grp_ = nullptr;
+            throw;
+        }
+    }
+    Evaluation(const ComputeKeyNonFft& key, const spf_params& params, int device = 0) : Evaluation(key, params, std::vector<int>{device}) {}
     // Evaluation::with_default_params (evaluation.rs:200-204)
     static Evaluation with_default_params(const ComputeKey& key, int device = 0)
     {
@@ -76,6 +107,10 @@ class Evaluation {
 
     const spf_params& params() const { return params_; }
     spf_ctx* raw() const { return ctx_; }
+
+    // B x `PolynomialRef::fft` (entities/polynomial.rs:257-274) on the first device: n_polys x N words -> n_polys x N/2 complex;
+    // what `GgswCiphertext::fft` / `GlevCiphertext::fft` do to every polynomial of a ciphertext held in integer form
+    void poly_fft(double* output, const uint64_t* input, size_t n_polys = 1) { check(spf_poly_fft_batch(ctx_, n_polys, input, output), ctx_); }
 
     // KeylessEvaluation::not(&mut L1GlweCiphertext, &L1GlweCiphertext) (:48); `not`/`xor` are C++ tokens
     void not_(uint64_t* output, const uint64_t* input, size_t B = 1)

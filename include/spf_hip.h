@@ -103,6 +103,33 @@ spf_status spf_load_automorphism_key(spf_ctx *ctx, const double *ak_fft, size_t 
  * [pair][level<l_ss][poly<k+1][bin<N/2] (entities/scheme_switch_key.rs). */
 spf_status spf_load_scheme_switch_key(spf_ctx *ctx, const double *ssk_fft, size_t n_complex);
 
+/* ---- keys in standard (integer) form: `ComputeKeyNonFft` fields (crypto/keys.rs:145-159) -----------------------------
+ * The reference's portable key form is the integer one: `ComputeKeyNonFft` is what it serializes, and `ComputeKeyNonFft::fft`
+ * (keys.rs:258-282) makes the `ComputeKey` above from it; the float form "can be represented with insufficient precision" in
+ * transit (keys.rs:294-305).  "Standard form" = Torus<u64> words in the reference's layouts `BootstrapKey<u64>`,
+ * `AutomorphismKey<u64>`, `SchemeSwitchKey<u64>`: the FFT layouts above with every block of N/2 complex bins replaced by the
+ * polynomial's N words — the reference's `.fft()` is a flat map over the polynomials in storage order
+ * (entities/bootstrap_key.rs:92-105 -> ggsw_ciphertext.rs:98 -> glev_ciphertext.rs:66 -> glwe_ciphertext.rs:141;
+ * automorphism_key.rs:68 -> glwe_keyswitch_key.rs:80; scheme_switch_key.rs:174), each `PolynomialRef::fft`
+ * (entities/polynomial.rs:257-274).  Handing keys over this way, the library's own forward transform is the
+ * only floating-point step a key goes through: results do not depend on the host's FFT.
+ *
+ * `spf_poly_fft_*`: B x `PolynomialRef::fft` — n_polys x N words in, n_polys x N/2 complex bins out, each word taken as
+ * (double)(int64_t)w; bit-equal to the oracle's transform.  Also what brings an integer-form GGSW / GLEV / GLWE ciphertext into the
+ * transform domain (`GgswCiphertext::fft` & co. above).  A polynomial and its spectrum have the same size: in the `_dev` form
+ * d_out == d_in (in place) is allowed; any other overlap is SPF_ERR_INVALID_ARGUMENT.  n_polys = 0 is SPF_OK. */
+spf_status spf_poly_fft_dev(spf_ctx *ctx, void *stream, size_t n_polys, const uint64_t *d_in, double *d_out);
+spf_status spf_poly_fft_batch(spf_ctx *ctx, size_t n_polys, const uint64_t *in, double *out);
+/* `BootstrapKey::fft` (entities/bootstrap_key.rs:92-105) / `fft_bootstrap_key` + upload: n_words = 2 x the n_complex of
+ * spf_load_bootstrap_key.  The length is checked before the device is touched; the words are copied into the key blob and
+ * transformed there (no second buffer), then the key is finished as spf_load_bootstrap_key finishes it.  On any failure the
+ * context is left without that key. */
+spf_status spf_load_bootstrap_key_std(spf_ctx *ctx, const uint64_t *bsk, size_t n_words);
+/* `AutomorphismKey::fft` (entities/automorphism_key.rs:68): n_words = 2 x the n_complex of spf_load_automorphism_key */
+spf_status spf_load_automorphism_key_std(spf_ctx *ctx, const uint64_t *ak, size_t n_words);
+/* `SchemeSwitchKey::fft` (entities/scheme_switch_key.rs:174): n_words = 2 x the n_complex of spf_load_scheme_switch_key */
+spf_status spf_load_scheme_switch_key_std(spf_ctx *ctx, const uint64_t *ssk, size_t n_words);
+
 /* Multi-GPU key replication (no reference counterpart): the device-resident
  * key blobs, so that a caller can RCCL-broadcast rank 0's keys into every other rank's
  * context.  which: 0 = bootstrap key, 1 = keyswitch key, 2 = automorphism key,
@@ -559,6 +586,11 @@ spf_status spf_generate_bivariate_lut(const spf_params *params, const uint64_t *
  * with_fixint_encoding — four sequences (u64 LE count, elements) in the order bs_key, ks_key, ss_key, auto_key.
  * Every count is checked against the context's parameters before anything is loaded; trailing bytes are allowed. */
 spf_status spf_load_compute_key_bincode(spf_ctx *ctx, const uint8_t *bytes, size_t len);
+/* `safe_bincode::deserialize::<ComputeKeyNonFft>` + `ComputeKeyNonFft::fft` + upload (crypto/keys.rs:145-159, :258-282): the
+ * same bincode conventions, every element one little-endian u64, fields in the order of THAT struct — bs_key, ks_key, auto_key,
+ * ss_key (not `ComputeKey`'s).  Every count is checked before anything is loaded; ks_key goes to spf_load_keyswitch_key, the
+ * others to the `_std` loaders; trailing bytes are allowed. */
+spf_status spf_load_compute_key_nonfft_bincode(spf_ctx *ctx, const uint8_t *bytes, size_t len);
 /* Ciphertext wire format (parasol_runtime/src/crypto/encryption.rs:23-110: L0LweCiphertext, L1LweCiphertext,
  * L1GlweCiphertext, L1GlevCiphertext are serde newtypes over entities with one field `data: AVec<Torus<u64>>`,
  * sunscreen_tfhe/src/dst.rs:25-41) as `safe_bincode::deserialize` reads it (safe_bincode.rs:16-28): bincode
@@ -643,6 +675,12 @@ spf_status spf_group_load_keyswitch_key(spf_group *grp, const uint64_t *ksk, siz
 spf_status spf_group_load_automorphism_key(spf_group *grp, const double *ak_fft, size_t n_complex);
 spf_status spf_group_load_scheme_switch_key(spf_group *grp, const double *ssk_fft, size_t n_complex);
 spf_status spf_group_load_compute_key_bincode(spf_group *grp, const uint8_t *bytes, size_t len);
+/* the standard (integer) forms (`ComputeKeyNonFft`, crypto/keys.rs:145-159, :258-282): member 0 transforms once, the spectra
+ * are replicated as above — every member holds the same bits, the wire carries the same bytes as for the float loaders */
+spf_status spf_group_load_bootstrap_key_std(spf_group *grp, const uint64_t *bsk, size_t n_words);
+spf_status spf_group_load_automorphism_key_std(spf_group *grp, const uint64_t *ak, size_t n_words);
+spf_status spf_group_load_scheme_switch_key_std(spf_group *grp, const uint64_t *ssk, size_t n_words);
+spf_status spf_group_load_compute_key_nonfft_bincode(spf_group *grp, const uint8_t *bytes, size_t len);
 /* replicate whatever member 0 holds (keys put there through spf_group_ctx(grp, 0), e.g. generated on the device into
  * spf_key_blob + spf_key_blob_commit) */
 spf_status spf_group_replicate_keys(spf_group *grp);

@@ -47,6 +47,11 @@ SYMBOLS = [
     ("spf_load_keyswitch_key", _I, [_P, _P, _SZ]),
     ("spf_load_automorphism_key", _I, [_P, _P, _SZ]),
     ("spf_load_scheme_switch_key", _I, [_P, _P, _SZ]),
+    ("spf_poly_fft_dev", _I, [_P, _P, _SZ, _P, _P]),
+    ("spf_poly_fft_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_load_bootstrap_key_std", _I, [_P, _P, _SZ]),
+    ("spf_load_automorphism_key_std", _I, [_P, _P, _SZ]),
+    ("spf_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
     ("spf_key_blob", _I, [_P, _I, C.POINTER(_P), C.POINTER(_SZ)]),
     ("spf_key_blob_commit", _I, [_P, _I]),
     ("spf_keyswitch_lwe_l1_lwe_l0_batch", _I, [_P, _SZ, _P, _P]),
@@ -126,6 +131,7 @@ SYMBOLS = [
     ("spf_generate_lut", _I, [C.POINTER(_CParams), _P, _SZ, _U32, _P]),
     ("spf_generate_bivariate_lut", _I, [C.POINTER(_CParams), _P, _U32, _U32, _P]),
     ("spf_load_compute_key_bincode", _I, [_P, _P, _SZ]),
+    ("spf_load_compute_key_nonfft_bincode", _I, [_P, _P, _SZ]),
     ("spf_ciphertext_words", _SZ, [C.POINTER(_CParams), _I]),
     ("spf_ciphertext_from_bincode", _I, [C.POINTER(_CParams), _I, _P, _SZ, _P]),
     ("spf_ciphertext_to_bincode", _I, [C.POINTER(_CParams), _I, _P, _P, _SZ, C.POINTER(_SZ)]),
@@ -141,6 +147,10 @@ SYMBOLS = [
     ("spf_group_load_automorphism_key", _I, [_P, _P, _SZ]),
     ("spf_group_load_scheme_switch_key", _I, [_P, _P, _SZ]),
     ("spf_group_load_compute_key_bincode", _I, [_P, _P, _SZ]),
+    ("spf_group_load_bootstrap_key_std", _I, [_P, _P, _SZ]),
+    ("spf_group_load_automorphism_key_std", _I, [_P, _P, _SZ]),
+    ("spf_group_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
+    ("spf_group_load_compute_key_nonfft_bincode", _I, [_P, _P, _SZ]),
     ("spf_group_replicate_keys", _I, [_P]),
     ("spf_group_replication_stats", _I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_SZ), C.POINTER(_I),
                                          C.POINTER(C.c_char_p)]),
@@ -379,6 +389,45 @@ class Engine:
     def load_scheme_switch_key(self, ssk_fft: np.ndarray):
         a = np.ascontiguousarray(ssk_fft, dtype=np.complex128).reshape(-1)
         self._ck(self._lib.spf_load_scheme_switch_key(self._h, _ptr(a), a.size))
+
+    # -- keys in standard (integer) form (ComputeKeyNonFft fields, crypto/keys.rs:145-159): transformed on the device
+    def _std_words(self, what: str, words, want_complex: int) -> np.ndarray:
+        if not isinstance(words, np.ndarray) or words.dtype != np.uint64:
+            raise SpfError(-2, f"{what}: a standard-form key is a uint64 array, got {getattr(words, 'dtype', type(words))}")
+        return _in(what, words, np.uint64, 2 * want_complex).reshape(-1)
+
+    def load_bootstrap_key_std(self, bsk: np.ndarray):
+        """`BootstrapKey<u64>` words ([i<n][row][level][poly][N]); `BootstrapKey::fft` happens on the device"""
+        a = self._std_words("load_bootstrap_key_std", bsk, self.params.bsk_complex)
+        self._ck(self._lib.spf_load_bootstrap_key_std(self._h, _ptr(a), a.size))
+
+    def load_automorphism_key_std(self, ak: np.ndarray):
+        a = self._std_words("load_automorphism_key_std", ak, self.params.ak_complex)
+        self._ck(self._lib.spf_load_automorphism_key_std(self._h, _ptr(a), a.size))
+
+    def load_scheme_switch_key_std(self, ssk: np.ndarray):
+        a = self._std_words("load_scheme_switch_key_std", ssk, self.params.ssk_complex)
+        self._ck(self._lib.spf_load_scheme_switch_key_std(self._h, _ptr(a), a.size))
+
+    def load_compute_key_nonfft_bincode(self, blob: bytes):
+        """the bytes `bincode` wrote for a parasol_runtime::ComputeKeyNonFft (keys.rs:145-159), all four keys"""
+        buf = np.frombuffer(blob, dtype=np.uint8)
+        self._ck(self._lib.spf_load_compute_key_nonfft_bincode(self._h, _ptr(buf), buf.size))
+
+    def poly_fft(self, polys) -> np.ndarray:
+        """`PolynomialRef::fft` of every polynomial: uint64 (..., N) -> complex128 (..., N/2)"""
+        N = self.params.polynomial_degree
+        if not isinstance(polys, np.ndarray) or polys.dtype != np.uint64 or polys.ndim == 0 or polys.shape[-1] != N:
+            raise SpfError(-2, f"poly_fft: operand must be a uint64 array of shape (..., {N}), got "
+                               f"{getattr(polys, 'dtype', type(polys))} {getattr(polys, 'shape', '')}")
+        x = np.ascontiguousarray(polys)
+        out = np.empty(x.shape[:-1] + (N // 2,), dtype=np.complex128)
+        self._ck(self._lib.spf_poly_fft_batch(self._h, x.size // N, _ptr(x), _ptr(out)))
+        return out
+
+    def poly_fft_dev(self, stream, n_polys: int, d_in: int, d_out: int):
+        """device pointers; d_out == d_in transforms in place"""
+        self._ck(self._lib.spf_poly_fft_dev(self._h, stream, n_polys, d_in, d_out))
 
     def key_blob(self, which: int):
         """(device pointer, bytes) of the device-resident key; for RCCL broadcast."""

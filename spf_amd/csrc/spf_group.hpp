@@ -538,6 +538,21 @@ spf_status spf_group_load_scheme_switch_key(spf_group* g, const double* ssk_fft,
     return group_load(g, 3, [&](spf_ctx* c) { return spf_load_scheme_switch_key(c, ssk_fft, n_complex); });
 }
 
+// the standard (integer) forms: member 0 transforms, the SPECTRA are replicated (every member holds member 0's bits, and
+// the wire carries what the float loaders put on it)
+spf_status spf_group_load_bootstrap_key_std(spf_group* g, const uint64_t* bsk, size_t n_words)
+{
+    return group_load(g, 0, [&](spf_ctx* c) { return spf_load_bootstrap_key_std(c, bsk, n_words); });
+}
+spf_status spf_group_load_automorphism_key_std(spf_group* g, const uint64_t* ak, size_t n_words)
+{
+    return group_load(g, 2, [&](spf_ctx* c) { return spf_load_automorphism_key_std(c, ak, n_words); });
+}
+spf_status spf_group_load_scheme_switch_key_std(spf_group* g, const uint64_t* ssk, size_t n_words)
+{
+    return group_load(g, 3, [&](spf_ctx* c) { return spf_load_scheme_switch_key_std(c, ssk, n_words); });
+}
+
 spf_status spf_group_replicate_keys(spf_group* g)
 {
     if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
@@ -556,6 +571,17 @@ spf_status spf_group_load_compute_key_bincode(spf_group* g, const uint8_t* bytes
     {
         std::lock_guard<std::mutex> lk(g->key_mu);
         spf_status s = spf_load_compute_key_bincode(g->m[0]->ctx, bytes, len);
+        if (s != SPF_OK) return gfail(g, s, std::string("member 0: ") + spf_last_error(g->m[0]->ctx));
+    }
+    return spf_group_replicate_keys(g);
+}
+
+spf_status spf_group_load_compute_key_nonfft_bincode(spf_group* g, const uint8_t* bytes, size_t len)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    {
+        std::lock_guard<std::mutex> lk(g->key_mu);
+        spf_status s = spf_load_compute_key_nonfft_bincode(g->m[0]->ctx, bytes, len);
         if (s != SPF_OK) return gfail(g, s, std::string("member 0: ") + spf_last_error(g->m[0]->ctx));
     }
     return spf_group_replicate_keys(g);

@@ -8,6 +8,7 @@
 #include "spf_kernels.hpp"
 #include "spf_cbs_tail.hpp"
 #include "spf_generic.hpp"
+#include "spf_poly_fft.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -1686,6 +1687,104 @@ spf_status spf_load_scheme_switch_key(spf_ctx* c, const double* ssk_fft, size_t 
     return load_fft_key(c, 3, ssk_fft, n_complex, ssk_complex(c->prm), &c->ssk_ready);
 }
 
+// ---------------------------------------------------------------- standard (integer) form -> transform domain on the device
+// `PolynomialRef::fft` (entities/polynomial.rs:257-274) of n_polys polynomials (spf_poly_fft.hpp).  d_out == d_in is allowed.
+
+static spf_status launch_poly_fft(spf_ctx* c, hipStream_t s, size_t n_polys, const uint64_t* d_in, c64* d_out)
+{
+    if (n_polys == 0) return SPF_OK;
+    if (c->prm.polynomial_degree == (uint32_t)kN) { // (whatever the radix: the transform does not depend on it)
+        static_assert(kPolyFftLds <= 64 * 1024, "within the default dynamic LDS limit");
+        PolyFftArgs a{d_in, d_out, c->d_tables, (uint32_t)n_polys};
+        // two workgroups fit a CU's LDS; a wave walks the batch with the grid's stride, so the table image is copied once per slot
+        const size_t groups = (n_polys + kPolyFftWaves - 1) / kPolyFftWaves;
+        const unsigned grid = (unsigned)std::min(groups, 2 * (size_t)c->n_cu);
+        hipLaunchKernelGGL(poly_fft2048_kernel, dim3(grid), dim3(64 * kPolyFftWaves), kPolyFftLds, s, a);
+    } else {
+        GenericPolyFftArgs a{generic_shape(c), d_in, d_out};
+        hipLaunchKernelGGL(generic_poly_fft_kernel, dim3((unsigned)n_polys), dim3(kGenericThreads),
+                           generic_poly_fft_lds_bytes(a.g.N), s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+spf_status spf_poly_fft_dev(spf_ctx* c, void* stream, size_t n_polys, const uint64_t* d_in, double* d_out)
+{
+    if (!c || (n_polys && (!d_in || !d_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_polys == 0) return SPF_OK;
+    if (n_polys > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    {
+        // the same memory (in place) or disjoint memory: a partial overlap would let one polynomial's bins land on another's words
+        const uintptr_t a = (uintptr_t)d_in, b = (uintptr_t)d_out, bytes = (uintptr_t)n_polys * c->prm.polynomial_degree * 8;
+        if (a != b && a < b + bytes && b < a + bytes)
+            return fail(c, SPF_ERR_INVALID_ARGUMENT, "spf_poly_fft_dev: d_out must be d_in itself or must not overlap it");
+    }
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return launch_poly_fft(c, (hipStream_t)stream, n_polys, d_in, reinterpret_cast<c64*>(d_out));
+}
+
+spf_status spf_poly_fft_batch(spf_ctx* c, size_t n_polys, const uint64_t* in, double* out)
+{
+    if (!c || (n_polys && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_polys == 0) return SPF_OK;
+    if (n_polys > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    const size_t bytes = n_polys * c->prm.polynomial_degree * 8;
+    return host_call(c, {{c->in, in, bytes}}, bytes, out,
+                     [&] { return spf_poly_fft_dev(c, c->stream, n_polys, (const uint64_t*)c->in.p, (double*)c->out.p); });
+}
+
+// A key in standard form: the words go into the key blob as they are (same bytes as its spectra) and are transformed there;
+// then exactly what the float loader does behind its copy.  The key is not ready from the first touched byte until the end.
+static spf_status load_std_key(spf_ctx* c, int which, const char* name, const uint64_t* words, size_t n_words, size_t want_complex)
+{
+    if (!c || !words) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (n_words / 2 != want_complex || (n_words & 1))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, std::string(name) + " key length " + std::to_string(n_words) + " words != " +
+                                                     std::to_string(2 * want_complex));
+    void* p; size_t bytes;
+    spf_status s = spf_key_blob(c, which, &p, &bytes);
+    if (s != SPF_OK) return s;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    bool& ready = which == 0 ? c->bsk_ready : (which == 2 ? c->ak_ready : c->ssk_ready);
+    ready = false;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto transform = [&]() -> spf_status {
+        HIPCHK(c, hipMemcpyAsync(p, words, bytes, hipMemcpyHostToDevice, c->stream));
+        return launch_poly_fft(c, c->stream, n_words / c->prm.polynomial_degree, (const uint64_t*)p, (c64*)p);
+    };
+    s = transform();
+    {
+        // (no return before the stream is idle: the copy reads the caller's buffer)
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (s == SPF_OK && e != hipSuccess) s = fail(c, SPF_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    if (s == SPF_OK && which == 0) s = finish_bootstrap_key(c);
+    if (s != SPF_OK) return s;
+    ready = true;
+    c->ggsw_const_ready = false;
+    return SPF_OK;
+}
+
+spf_status spf_load_bootstrap_key_std(spf_ctx* c, const uint64_t* bsk, size_t n_words)
+{
+    if (!c) return SPF_ERR_INVALID_ARGUMENT;
+    return load_std_key(c, 0, "bootstrap", bsk, n_words, (size_t)c->prm.lwe_dimension * ggsw_fft_complex(c->prm, c->prm.pbs_radix_count));
+}
+
+spf_status spf_load_automorphism_key_std(spf_ctx* c, const uint64_t* ak, size_t n_words)
+{
+    if (!c) return SPF_ERR_INVALID_ARGUMENT;
+    return load_std_key(c, 2, "automorphism", ak, n_words, ak_complex(c->prm));
+}
+
+spf_status spf_load_scheme_switch_key_std(spf_ctx* c, const uint64_t* ssk, size_t n_words)
+{
+    if (!c) return SPF_ERR_INVALID_ARGUMENT;
+    return load_std_key(c, 3, "scheme-switch", ssk, n_words, ssk_complex(c->prm));
+}
+
 spf_status spf_mod_switch_trace_and_rotate_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, uint64_t* glev_out)
 {
     if (!c || (B && (!glwe_in || !glev_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
@@ -1883,6 +1982,38 @@ spf_status spf_load_compute_key_bincode(spf_ctx* c, const uint8_t* bytes, size_t
     if (st == SPF_OK) st = spf_load_keyswitch_key(c, reinterpret_cast<const uint64_t*>(f[1].data), f[1].want);
     if (st == SPF_OK) st = spf_load_scheme_switch_key(c, reinterpret_cast<const double*>(f[2].data), f[2].want);
     if (st == SPF_OK) st = spf_load_automorphism_key(c, reinterpret_cast<const double*>(f[3].data), f[3].want);
+    return st;
+}
+
+// `safe_bincode::deserialize::<ComputeKeyNonFft>` + `ComputeKeyNonFft::fft` (crypto/keys.rs:145-159, :258-282): the same
+// conventions, every element one little-endian u64 (Torus<u64>), fields in THAT struct's declaration order — bs_key, ks_key,
+// auto_key, ss_key (ComputeKey has ss_key before auto_key).  All four counts are checked before any key is touched.
+spf_status spf_load_compute_key_nonfft_bincode(spf_ctx* c, const uint8_t* bytes, size_t len)
+{
+    if (!c || !bytes) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    struct Field { const char* name; size_t want; const uint8_t* data; };
+    Field f[4] = {{"bs_key", 2 * (size_t)c->prm.lwe_dimension * ggsw_fft_complex(c->prm, c->prm.pbs_radix_count), nullptr},
+                  {"ks_key", (size_t)c->prm.glwe_size * c->prm.polynomial_degree * c->prm.ks_radix_count * lwe0_words(c->prm), nullptr},
+                  {"auto_key", 2 * ak_complex(c->prm), nullptr},
+                  {"ss_key", 2 * ssk_complex(c->prm), nullptr}};
+    size_t off = 0;
+    for (auto& x : f) {
+        if (len - off < 8) return fail(c, SPF_ERR_INVALID_ARGUMENT, std::string("ComputeKeyNonFft: truncated before the length of ") + x.name);
+        uint64_t n = 0;
+        for (int b = 7; b >= 0; b--) n = (n << 8) | bytes[off + b]; // little-endian, any alignment
+        off += 8;
+        if (n != x.want)
+            return fail(c, SPF_ERR_INVALID_ARGUMENT, std::string("ComputeKeyNonFft: ") + x.name + " has " + std::to_string(n) +
+                                                         " elements, the parameters need " + std::to_string(x.want));
+        if ((len - off) / 8 < x.want) return fail(c, SPF_ERR_INVALID_ARGUMENT, std::string("ComputeKeyNonFft: truncated inside ") + x.name);
+        x.data = bytes + off;
+        off += x.want * 8;
+    }
+    // the loaders only copy from these (possibly unaligned) pointers; x86-64 little-endian host = wire order
+    spf_status st = spf_load_bootstrap_key_std(c, reinterpret_cast<const uint64_t*>(f[0].data), f[0].want);
+    if (st == SPF_OK) st = spf_load_keyswitch_key(c, reinterpret_cast<const uint64_t*>(f[1].data), f[1].want);
+    if (st == SPF_OK) st = spf_load_automorphism_key_std(c, reinterpret_cast<const uint64_t*>(f[2].data), f[2].want);
+    if (st == SPF_OK) st = spf_load_scheme_switch_key_std(c, reinterpret_cast<const uint64_t*>(f[3].data), f[3].want);
     return st;
 }
 

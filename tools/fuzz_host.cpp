@@ -5,7 +5,7 @@
 // translation unit (so that it can make a context by hand, without a device, and reach the builders that validate before
 // their first HIP call) and is built with -fsanitize=address,undefined for the host side only (tools/asan_host.sh).
 // Exercised: spf_ciphertext_{words,from_bincode,to_bincode} (safe_bincode::deserialize of the ciphertext newtypes),
-// spf_load_compute_key_bincode's size walk (ComputeKey), spf_generate_lut, params_supported / params_generic, and
+// spf_load_compute_key_bincode's and spf_load_compute_key_nonfft_bincode's size walks (ComputeKey, ComputeKeyNonFft), spf_generate_lut, params_supported / params_generic, and
 // spf_graph_add_{input,trivial,op,output} (the reference validates per task, task.rs:26-31) — every call must return a status,
 // never crash, never touch memory outside its buffers (every destination is an exact-size heap allocation).  Before the random
 // cases, a fixed table calls every spf_*_batch entry point with one bad argument each (batch_forms_refuse_bad_arguments).
@@ -125,6 +125,16 @@ bool batch_forms_refuse_bad_arguments(spf_ctx* c)
     expect("unpack_circuit_bootstrap B * n_bits 0x10000002",
            spf_unpack_circuit_bootstrap_batch(c, over_tail / 2 + 1, 2, glwe.data(), o_ggsw_bits.data()));
     expect("unpack_circuit_bootstrap null in", spf_unpack_circuit_bootstrap_batch(c, B, nb, nullptr, o_ggsw_bits.data()));
+    // the standard-form entry points: polynomials and keys as integer words
+    std::vector<double> o_spec(B * N);
+    expect("poly_fft null in", spf_poly_fft_batch(c, B, nullptr, o_spec.data()));
+    expect("poly_fft null out", spf_poly_fft_batch(c, B, glwe.data(), nullptr));
+    expect("poly_fft n_polys 0x80000000", spf_poly_fft_batch(c, over_br, glwe.data(), o_spec.data()));
+    expect("poly_fft_dev partial overlap", spf_poly_fft_dev(c, nullptr, B, glwe.data(), reinterpret_cast<double*>(glwe.data() + N)));
+    expect("load_bootstrap_key_std null", spf_load_bootstrap_key_std(c, nullptr, 2 * (size_t)p.lwe_dimension * ggsw_fft_complex(p, p.pbs_radix_count)));
+    expect("load_bootstrap_key_std length in complex", spf_load_bootstrap_key_std(c, glwe.data(), (size_t)p.lwe_dimension * ggsw_fft_complex(p, p.pbs_radix_count)));
+    expect("load_automorphism_key_std one word short", spf_load_automorphism_key_std(c, glwe.data(), 2 * ak_complex(p) - 1));
+    expect("load_scheme_switch_key_std one word long", spf_load_scheme_switch_key_std(c, glwe.data(), 2 * ssk_complex(p) + 1));
     return ok;
 }
 
@@ -184,11 +194,30 @@ int main(int argc, char** argv)
             for (size_t j = 0; j < want[i] * elem[i]; j++) key_seed.push_back((uint8_t)r());
         }
     }
+    std::vector<uint8_t> nonfft_seed; // ComputeKeyNonFft: bs_key, ks_key, auto_key, ss_key, every element one u64
+    {
+        const size_t want[4] = {2 * (size_t)tiny.lwe_dimension * ggsw_fft_complex(tiny, tiny.pbs_radix_count),
+                                (size_t)tiny.glwe_size * tiny.polynomial_degree * tiny.ks_radix_count * lwe0_words(tiny), 2 * ak_complex(tiny),
+                                2 * ssk_complex(tiny)};
+        for (int i = 0; i < 4; i++) {
+            uint64_t n = want[i];
+            for (int b = 0; b < 8; b++) nonfft_seed.push_back((uint8_t)(n >> (8 * b)));
+            for (size_t j = 0; j < want[i] * 8; j++) nonfft_seed.push_back((uint8_t)r());
+        }
+    }
 
     uint64_t ok = 0, refused = 0;
     for (uint64_t it = 0; it < cases; it++) {
         const spf_params* p = r.below(2) ? &dflt : &tiny;
-        switch (r.below(6)) {
+        switch (r.below(7)) {
+        case 6: { // ComputeKeyNonFft blob: its own size walk; a ComputeKey blob now and then (other field order and element size)
+            const std::vector<uint8_t> in = mutate(r.below(4) ? nonfft_seed : key_seed, r);
+            std::unique_ptr<uint8_t[]> bytes(new uint8_t[in.size() ? in.size() : 1]);
+            if (!in.empty()) std::memcpy(bytes.get(), in.data(), in.size());
+            const spf_status st = spf_load_compute_key_nonfft_bincode(&tiny_ctx, bytes.get(), in.size());
+            (st == SPF_OK ? ok : refused)++;
+            break;
+        }
         case 0: case 1: { // ciphertext wire format
             const std::vector<uint8_t> in = mutate(ct_seeds[r.below(ct_seeds.size())], r);
             // an exact-size copy on the heap: a read past `len` is a heap-buffer-overflow under ASan
