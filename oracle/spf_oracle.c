@@ -580,14 +580,18 @@ uint64_t spfo_f64_to_torus(double v)
     return (uint64_t)r;
 }
 
-/* entities/polynomial_fft.rs:82-99 */
-void spfo_poly_ifft(const spfo_c64 *in, size_t N, uint64_t *poly)
+/* entities/polynomial_fft.rs:82-99.  `seen`, when given, receives the N doubles handed to spfo_f64_to_torus (the
+ * conversion-regime witness of the spfo_*_conversion_input entry points). */
+static void poly_ifft_seen(const spfo_c64 *in, size_t N, uint64_t *poly, double *seen)
 {
     double *f = (double *)malloc(N * sizeof(double));
     spfo_twisted_fft_reverse(in, N, f);
     for (size_t i = 0; i < N; i++) poly[i] = spfo_f64_to_torus(f[i]);
+    if (seen) memcpy(seen, f, N * sizeof(double));
     free(f);
 }
+
+void spfo_poly_ifft(const spfo_c64 *in, size_t N, uint64_t *poly) { poly_ifft_seen(in, N, poly, NULL); }
 
 /* complex_mad: c += a * b.  The reference dispatches on the host CPU
  * (math/simd/x86_64/mod.rs:59-75):
@@ -661,9 +665,9 @@ void spfo_glwe_ggsw_mad(spfo_c64 *c_fft, const uint64_t *a_glwe, const spfo_c64 
     free(state); free(digit); free(dfft);
 }
 
-/* ops/fft_ops.rs:149-181 */
-void spfo_cmux(uint64_t *c, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
-               size_t N, size_t k, uint32_t radix_log, uint32_t count)
+/* ops/fft_ops.rs:149-181; seen: (k+1)*N doubles or NULL */
+static void cmux_seen(uint64_t *c, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
+                      size_t N, size_t k, uint32_t radix_log, uint32_t count, double *seen)
 {
     size_t len = (k + 1) * N, h = N / 2;
     uint64_t *diff = (uint64_t *)malloc(len * sizeof(uint64_t));
@@ -671,9 +675,23 @@ void spfo_cmux(uint64_t *c, const uint64_t *d0, const uint64_t *d1, const spfo_c
     spfo_c64 *prod_fft = (spfo_c64 *)calloc((k + 1) * h, sizeof(spfo_c64));
     for (size_t i = 0; i < len; i++) diff[i] = d1[i] - d0[i];
     spfo_glwe_ggsw_mad(prod_fft, diff, ggsw_fft, N, k, radix_log, count);
-    for (size_t q = 0; q <= k; q++) spfo_poly_ifft(prod_fft + q * h, N, prod + q * N);
+    for (size_t q = 0; q <= k; q++) poly_ifft_seen(prod_fft + q * h, N, prod + q * N, seen ? seen + q * N : NULL);
     for (size_t i = 0; i < len; i++) c[i] = prod[i] + d0[i];
     free(diff); free(prod); free(prod_fft);
+}
+
+void spfo_cmux(uint64_t *c, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
+               size_t N, size_t k, uint32_t radix_log, uint32_t count)
+{
+    cmux_seen(c, d0, d1, ggsw_fft, N, k, radix_log, count, NULL);
+}
+
+void spfo_cmux_conversion_input(double *seen, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
+                                size_t N, size_t k, uint32_t radix_log, uint32_t count)
+{
+    uint64_t *c = (uint64_t *)malloc((k + 1) * N * sizeof(uint64_t));
+    cmux_seen(c, d0, d1, ggsw_fft, N, k, radix_log, count, seen);
+    free(c);
 }
 
 /* ops/bootstrapping/programmable_bootstrapping.rs:342-410 */
@@ -910,24 +928,31 @@ static void glev_mad(spfo_c64 *c_fft, const uint64_t *poly, const spfo_c64 *glev
     free(state); free(digit); free(dfft);
 }
 
-/* ops/fft_ops.rs:457-495.  ksk layout [row<k][level<count][poly<k+1][N/2] */
-void spfo_keyswitch_glwe_to_glwe(uint64_t *out, const uint64_t *in, const spfo_c64 *ksk_fft, size_t N,
-                                 size_t k, uint32_t radix_log, uint32_t count)
+/* ops/fft_ops.rs:457-495.  ksk layout [row<k][level<count][poly<k+1][N/2]; seen: (k+1)*N doubles or NULL */
+static void keyswitch_glwe_seen(uint64_t *out, const uint64_t *in, const spfo_c64 *ksk_fft, size_t N,
+                                size_t k, uint32_t radix_log, uint32_t count, double *seen)
 {
     size_t h = N / 2, glev_len = (size_t)count * (k + 1) * h;
     spfo_c64 *sum = (spfo_c64 *)calloc((k + 1) * h, sizeof(spfo_c64));
     uint64_t *s = (uint64_t *)malloc((k + 1) * N * sizeof(uint64_t));
     for (size_t i = 0; i < k; i++) glev_mad(sum, in + i * N, ksk_fft + i * glev_len, N, k, radix_log, count);
-    for (size_t q = 0; q <= k; q++) spfo_poly_ifft(sum + q * h, N, s + q * N);
+    for (size_t q = 0; q <= k; q++) poly_ifft_seen(sum + q * h, N, s + q * N, seen ? seen + q * N : NULL);
     /* output = trivial_encrypt(b) - sum */
     for (size_t i = 0; i < k * N; i++) out[i] = (uint64_t)0 - s[i];
     for (size_t i = 0; i < N; i++) out[k * N + i] = in[k * N + i] - s[k * N + i];
     free(sum); free(s);
 }
 
-/* ops/automorphisms/mod.rs:53-85.  ak layout [i<log2 N][glwe ksk] */
-void spfo_trace(uint64_t *out, const uint64_t *x, const spfo_c64 *ak_fft, size_t N, size_t k,
-                uint32_t radix_log, uint32_t count)
+void spfo_keyswitch_glwe_to_glwe(uint64_t *out, const uint64_t *in, const spfo_c64 *ksk_fft, size_t N,
+                                 size_t k, uint32_t radix_log, uint32_t count)
+{
+    keyswitch_glwe_seen(out, in, ksk_fft, N, k, radix_log, count, NULL);
+}
+
+/* ops/automorphisms/mod.rs:53-85.  ak layout [i<log2 N][glwe ksk]; seen (or NULL) receives the conversion input of
+ * round `seen_round` (0-based) */
+static void trace_seen(uint64_t *out, const uint64_t *x, const spfo_c64 *ak_fft, size_t N, size_t k,
+                       uint32_t radix_log, uint32_t count, uint32_t seen_round, double *seen)
 {
     size_t len = (k + 1) * N, ksk_len = k * (size_t)count * (k + 1) * (N / 2);
     uint64_t *glwe_k = (uint64_t *)malloc(len * sizeof(uint64_t));
@@ -938,16 +963,25 @@ void spfo_trace(uint64_t *out, const uint64_t *x, const spfo_c64 *ak_fft, size_t
     for (uint32_t i = 1; i <= logn; i++) {
         size_t kk = N / ((size_t)1 << (i - 1)) + 1;
         for (size_t p = 0; p <= k; p++) spfo_poly_pow_k(glwe_k + p * N, out + p * N, N, kk);
-        spfo_keyswitch_glwe_to_glwe(ks, glwe_k, ak_fft + (size_t)(i - 1) * ksk_len, N, k, radix_log, count);
+        keyswitch_glwe_seen(ks, glwe_k, ak_fft + (size_t)(i - 1) * ksk_len, N, k, radix_log, count,
+                            seen && i - 1 == seen_round ? seen : NULL);
         for (size_t t = 0; t < len; t++) out[t] += ks[t];
     }
     free(glwe_k); free(ks);
 }
 
-/* ops/bootstrapping/circuit_bootstrapping.rs:260-298: glev is cbs_count GLWEs */
-void spfo_mod_switch_trace_and_rotate(uint64_t *glev, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft,
-                                      size_t N, size_t k, uint32_t tr_radix_log, uint32_t tr_count,
-                                      uint32_t cbs_radix_log, uint32_t cbs_count)
+void spfo_trace(uint64_t *out, const uint64_t *x, const spfo_c64 *ak_fft, size_t N, size_t k,
+                uint32_t radix_log, uint32_t count)
+{
+    trace_seen(out, x, ak_fft, N, k, radix_log, count, 0, NULL);
+}
+
+/* ops/bootstrapping/circuit_bootstrapping.rs:260-298: glev is cbs_count GLWEs; seen (or NULL) receives the conversion
+ * input of round `seen_round` of the trace of GLEV level `seen_level` */
+static void mod_switch_trace_and_rotate_seen(uint64_t *glev, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft,
+                                             size_t N, size_t k, uint32_t tr_radix_log, uint32_t tr_count,
+                                             uint32_t cbs_radix_log, uint32_t cbs_count, uint32_t seen_level,
+                                             uint32_t seen_round, double *seen)
 {
     size_t len = (k + 1) * N;
     uint32_t shift_amount = 0;
@@ -964,9 +998,28 @@ void spfo_mod_switch_trace_and_rotate(uint64_t *glev, const uint64_t *lo_noise_g
         for (size_t p = 0; p <= k; p++) spfo_poly_mul_neg_monomial(permuted + p * N, N, i);
         /* glwe_mod_switch_and_expand_pow_2 (ops/ciphertext/glwe_ciphertext_ops.rs:268-281) */
         spfo_poly_shr_round(shifted, permuted, len, shift_amount);
-        spfo_trace(glev + (size_t)i * len, shifted, ak_fft, N, k, tr_radix_log, tr_count);
+        trace_seen(glev + (size_t)i * len, shifted, ak_fft, N, k, tr_radix_log, tr_count, seen_round,
+                   i == seen_level ? seen : NULL);
     }
     free(rotated); free(permuted); free(shifted);
+}
+
+void spfo_mod_switch_trace_and_rotate(uint64_t *glev, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft,
+                                      size_t N, size_t k, uint32_t tr_radix_log, uint32_t tr_count,
+                                      uint32_t cbs_radix_log, uint32_t cbs_count)
+{
+    mod_switch_trace_and_rotate_seen(glev, lo_noise_glwe, ak_fft, N, k, tr_radix_log, tr_count, cbs_radix_log, cbs_count,
+                                     0, 0, NULL);
+}
+
+void spfo_trace_round_conversion_input(double *seen, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft, size_t N,
+                                       size_t k, uint32_t tr_radix_log, uint32_t tr_count, uint32_t cbs_radix_log,
+                                       uint32_t cbs_count, uint32_t level, uint32_t round)
+{
+    uint64_t *glev = (uint64_t *)malloc((size_t)cbs_count * (k + 1) * N * sizeof(uint64_t));
+    mod_switch_trace_and_rotate_seen(glev, lo_noise_glwe, ak_fft, N, k, tr_radix_log, tr_count, cbs_radix_log, cbs_count,
+                                     level, round, seen);
+    free(glev);
 }
 
 static size_t tri_index(size_t i, size_t j, size_t n)

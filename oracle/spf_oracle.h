@@ -135,6 +135,11 @@ void spfo_glwe_ggsw_mad(spfo_c64 *c_fft /*(k+1)*N/2*/, const uint64_t *a_glwe,
 /* ops/fft_ops.rs:149-181 (cmux): c = d0 + IFFT(decomp(d1-d0) . ggsw) */
 void spfo_cmux(uint64_t *c, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
                size_t N, size_t k, uint32_t radix_log, uint32_t count);
+/* The (k+1)*N doubles this oracle hands to spfo_f64_to_torus inside spfo_cmux with the same arguments (the inverse
+ * transform of the external product, already round()ed), polynomial by polynomial: which conversion regime (magnitude,
+ * sign, value mod 2^64) an input reaches.  Computed by spfo_cmux's own code; tests/test_conversion_regimes.py. */
+void spfo_cmux_conversion_input(double *seen, const uint64_t *d0, const uint64_t *d1, const spfo_c64 *ggsw_fft,
+                                size_t N, size_t k, uint32_t radix_log, uint32_t count);
 /* ops/bootstrapping/programmable_bootstrapping.rs:342-410.  bsk layout [n][ggsw]. */
 void spfo_generalized_pbs(uint64_t *glwe_out, const uint64_t *lwe_in, const uint64_t *lut_glwe,
                           const spfo_c64 *bsk_fft, size_t n, size_t N, size_t k,
@@ -161,6 +166,11 @@ void spfo_trace(uint64_t *out, const uint64_t *x, const spfo_c64 *ak_fft, size_t
 void spfo_mod_switch_trace_and_rotate(uint64_t *glev, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft,
                                       size_t N, size_t k, uint32_t tr_radix_log, uint32_t tr_count,
                                       uint32_t cbs_radix_log, uint32_t cbs_count);
+/* The same witness for one automorphism-keyswitch round (0-based, < log2 N) of the trace of GLEV level `level` inside
+ * spfo_mod_switch_trace_and_rotate with the same arguments: (k+1)*N doubles. */
+void spfo_trace_round_conversion_input(double *seen, const uint64_t *lo_noise_glwe, const spfo_c64 *ak_fft, size_t N,
+                                       size_t k, uint32_t tr_radix_log, uint32_t tr_count, uint32_t cbs_radix_log,
+                                       uint32_t cbs_count, uint32_t level, uint32_t round);
 /* ops/fft_ops.rs:403-442 (scheme_switch_fft); out [row<k+1][level<ggsw_count][poly][N/2] */
 void spfo_scheme_switch_fft(spfo_c64 *out, const uint64_t *glev, const spfo_c64 *ssk_fft, size_t N,
                             size_t k, uint32_t ggsw_count, uint32_t ss_radix_log, uint32_t ss_count);

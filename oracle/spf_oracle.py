@@ -98,6 +98,8 @@ def _declare(lib):
     f("spfo_negacyclic_mul_exact", None, P, P, P, sz)
     f("spfo_glwe_ggsw_mad", None, P, P, P, sz, sz, u32, u32)
     f("spfo_cmux", None, P, P, P, P, sz, sz, u32, u32)
+    f("spfo_cmux_conversion_input", None, P, P, P, P, sz, sz, u32, u32)
+    f("spfo_trace_round_conversion_input", None, P, P, P, sz, sz, u32, u32, u32, u32, u32, u32)
     f("spfo_generalized_pbs", None, P, P, P, P, sz, sz, sz, u32, u32, u32, u32)
     f("spfo_pbs_univariate", None, P, P, P, P, sz, sz, sz, u32, u32)
     f("spfo_cbs_pbs", None, P, P, P, sz, sz, sz, u32, u32, u32, u32)
@@ -398,6 +400,15 @@ def cmux(d0, d1, ggsw_fft, N, k, radix_log, count) -> np.ndarray:
     return out
 
 
+def cmux_conversion_input(d0, d1, ggsw_fft, N, k, radix_log, count) -> np.ndarray:
+    """the (k+1, N) doubles `cmux` hands to f64_to_torus for these arguments"""
+    d0, d1, ggsw_fft = _u(d0), _u(d1), _c(ggsw_fft)
+    assert ggsw_fft.size == (k + 1) * count * (k + 1) * (N // 2)
+    out = np.zeros((k + 1, N), dtype=np.float64)
+    _load().spfo_cmux_conversion_input(_p(out), _p(d0), _p(d1), _p(ggsw_fft), N, k, radix_log, count)
+    return out
+
+
 def generalized_pbs(lwe_in, lut_glwe, bsk_fft, params: Params, log_chi=0, log_v=0) -> np.ndarray:
     lwe_in, lut_glwe, bsk_fft = _u(lwe_in), _u(lut_glwe), _c(bsk_fft)
     n = lwe_in.size - 1
@@ -592,6 +603,17 @@ def mod_switch_trace_and_rotate(lo_noise_glwe, ak_fft, params: Params = DEFAULT_
     out = np.zeros((params.cbs_count, params.glwe_len), dtype=np.uint64)
     _load().spfo_mod_switch_trace_and_rotate(_p(out), _p(g), _p(ak_fft), params.N, params.k, params.tr_radix_log,
                                              params.tr_count, params.cbs_radix_log, params.cbs_count)
+    return out
+
+
+def trace_round_conversion_input(lo_noise_glwe, ak_fft, level: int, rnd: int, params: Params = DEFAULT_128) -> np.ndarray:
+    """the (k+1, N) doubles round `rnd` (0-based) of the trace of GLEV level `level` hands to f64_to_torus inside
+    `mod_switch_trace_and_rotate` with these arguments"""
+    g, ak_fft = _u(lo_noise_glwe), _c(ak_fft)
+    assert ak_fft.size == params.ak_fft_len and level < params.cbs_count and rnd < params.N.bit_length() - 1
+    out = np.zeros((params.k + 1, params.N), dtype=np.float64)
+    _load().spfo_trace_round_conversion_input(_p(out), _p(g), _p(ak_fft), params.N, params.k, params.tr_radix_log,
+                                              params.tr_count, params.cbs_radix_log, params.cbs_count, level, rnd)
     return out
 
 
