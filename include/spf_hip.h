@@ -754,8 +754,7 @@ int spf_graph_member(const spf_graph *graph);
  * (per member) and spf_pool_destroy entry points above. */
 spf_status spf_pool_create_group(spf_group *grp, size_t max_batch, uint32_t max_wait_us, spf_pool **out);
 
-/* Library / kernel build information: version, target, the compile-time options of the blind rotation — and "ABLATION(n: timing
- * only, results are WRONG)" right after the target when the library is a timing-only ablation build (-DSPF_ABL=n). */
+/* Library / kernel build information: version, target, the compile-time options of the blind rotation. */
 const char *spf_version(void);
 
 #ifdef __cplusplus

@@ -32,7 +32,7 @@ class _CParams(C.Structure):
 
 
 def lib_path() -> str:
-    # SPF_HIP_LIBRARY lets experiments (e.g. timing-only ablation builds) swap the library
+    # SPF_HIP_LIBRARY lets experiments (e.g. A/B builds of the kept knobs, tools/ab_build.sh) swap the library
     return os.environ.get("SPF_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libspf_hip.so")
 
 

@@ -210,12 +210,12 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
                     accb[e] += v; // out.b += trivial(b_k) ...
                 }
             }
-#ifndef SPF_ABL_NO_PARK // (timing-only ablation: wrong results — what does the parked half's traffic cost?  profiles/r05_experiments_other_kernels.md)
+            // (what the parked half's traffic costs: 0.33 ms of 4.57 per 4096, measured by a timing-only build without the store and the
+            // reload, profiles/r05_experiments_other_kernels.md)
             if (p == 1 && owns_output) {
 #pragma unroll
                 for (int e = 0; e < 16; e++) park[(size_t)e * 64] = accb[e];
             }
-#endif
             wave_lds_fence(); // gathered: the region may be overwritten (next staging / the exchange image)
         }
 
@@ -292,13 +292,8 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
             }
             if (m == 2) {
                 // the parked body half comes back under the last multiply-accumulate and the inverse cross exchange
-#ifndef SPF_ABL_NO_PARK
 #pragma unroll
                 for (int e = 0; e < 16; e++) accb[e] = park[(size_t)e * 64];
-#else
-#pragma unroll
-                for (int e = 0; e < 16; e++) accb[e] = (uint64_t)st[e] * 0x9E3779B97F4A7C15ull; // (something the compiler cannot fold)
-#endif
             }
             // ... - sum_j <digit_j(a), glev row L-1-j>, digits in order, both output polynomials (fft_ops.rs:489-494)
 #pragma unroll
@@ -380,10 +375,8 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
         }
         // the parked accumulator half has landed BEFORE the next key rows are requested: vmcnt counts in order, a wait for
         // it behind the request would wait for the rows as well
-#ifndef SPF_TRACE_LATE_PARK
 #pragma unroll
         for (int e = 0; e < 16; e++) asm volatile("" : "+v"(accb[e]));
-#endif
         if (chunk < total_chunks) { // rows of the next round's first digit pair, this wave's share = the slot it just read
             const uint32_t rnd = chunk / 3;
             const char* src = reinterpret_cast<const char*>(a.ak) +

@@ -151,9 +151,19 @@ __device__ __forceinline__ void sched_fence()
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// One 512-point DFT (same DAG and exchange images as fft512_pair below) held by one wave; used
-// by the two-waves-per-ciphertext kernel, where the partner wave on the SIMD hides the LDS
-// round trips.  `buf` is the wave's private 8 KiB tile.
+// One 512-point DFT, DIF 8x8x8, held by one wave: lane l, register j holds element 64*j + l on entry (time order) and on
+// exit (frequency order).  `buf` is the wave's private 8 KiB LDS tile.
+//   n' = 64*n1 + n0, n0 = 8a + b;   k' = k1 + 8c + 64d
+//   pass 1: radix-8 over n1 -> k1, * W512^{n0 k1} (k1 != 0)     lanes (a,b)  regs k1
+//   exchange 1                                                  lanes (b,k1) regs a
+//   pass 2: radix-8 over a -> c,  * W64^{b c}   (c != 0)        lanes (b,k1) regs c
+//   exchange 2                                                  lanes (c,k1) regs b
+//   pass 3: radix-8 over b -> d                                 lanes (c,k1) regs d
+// Exchange images (16-byte slots): slot(x, y, z) = 64 x + 8 z + (y ^ z) with (x,y,z) =
+// (a,b,k1) resp. (b,c,k1): writes hit 8 distinct slots mod 8 per 8-lane group and reads 16
+// distinct slots mod 16 per ds_read_b128 lane group — conflict-free both ways (measured:
+// SQ_LDS_BANK_CONFLICT = 0).
+// Used where the partner wave on the SIMD hides the LDS round trips (the eight-waves-per-ciphertext kernel, the CMUX gates).
 // PRE (0..7): how many of each pass's seven twiddles are fetched from the LDS image BEFORE the
 // butterflies that precede their use, so the reads travel under ~56 f64 instructions instead of
 // being issued one or two at a time right where they are needed (what the compiler does by itself to
@@ -201,81 +211,6 @@ __device__ __forceinline__ void fft512_single(c64 (&V)[8], char* buf, const c64*
     compiler_fence();
 }
 
-// Two independent 512-point DFTs (the even / odd sample halves of one 1024-point transform),
-// DIF 8x8x8, held by one wave and advanced in lockstep so that one transform's LDS round trip
-// hides under the other's butterflies.  For each: lane l, register j holds element 64*j + l on
-// entry (time order) and on exit (frequency order).  bufE / bufO are private 8 KiB LDS tiles.
-//   n' = 64*n1 + n0, n0 = 8a + b;   k' = k1 + 8c + 64d
-//   pass 1: radix-8 over n1 -> k1, * W512^{n0 k1} (k1 != 0)     lanes (a,b)  regs k1
-//   exchange 1                                                  lanes (b,k1) regs a
-//   pass 2: radix-8 over a -> c,  * W64^{b c}   (c != 0)        lanes (b,k1) regs c
-//   exchange 2                                                  lanes (c,k1) regs b
-//   pass 3: radix-8 over b -> d                                 lanes (c,k1) regs d
-// Exchange images (16-byte slots): slot(x, y, z) = 64 x + 8 z + (y ^ z) with (x,y,z) =
-// (a,b,k1) resp. (b,c,k1): writes hit 8 distinct slots mod 8 per 8-lane group and reads 16
-// distinct slots mod 16 per ds_read_b128 lane group — conflict-free both ways (measured:
-// SQ_LDS_BANK_CONFLICT = 0).
-template <int DIR>
-__device__ __forceinline__ void fft512_pair(c64 (&E)[8], c64 (&O)[8], char* bufE, char* bufO,
-                                            const c64* tab, int lane)
-{
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const int rd = 16 * (8 * lo3 + (hi3 ^ lo3));
-    // pass 1 + exchange-1 writes: writer lane = 8a + b holds reg k1 -> slot 64a + 8k1 + (b ^ k1)
-    {
-        c64 tw[7];
-#pragma unroll
-        for (int k1 = 1; k1 < 8; k1++) tw[k1 - 1] = tab[kT1Off + (k1 - 1) * 64 + lane];
-        radix8<DIR>(E);
-#pragma unroll
-        for (int k1 = 1; k1 < 8; k1++) E[k1] = cmul_tw<DIR>(E[k1], tw[k1 - 1]);
-#pragma unroll
-        for (int k1 = 0; k1 < 8; k1++)
-            *reinterpret_cast<c64*>(bufE + 16 * (64 * hi3 + 8 * k1 + (lo3 ^ k1))) = E[k1];
-        radix8<DIR>(O);
-#pragma unroll
-        for (int k1 = 1; k1 < 8; k1++) O[k1] = cmul_tw<DIR>(O[k1], tw[k1 - 1]);
-#pragma unroll
-        for (int k1 = 0; k1 < 8; k1++)
-            *reinterpret_cast<c64*>(bufO + 16 * (64 * hi3 + 8 * k1 + (lo3 ^ k1))) = O[k1];
-    }
-    wave_lds_fence();
-    // exchange-1 reads: reader lane = 8b + k1 wants reg a <- slot 64a + 8k1 + (b ^ k1)
-#pragma unroll
-    for (int a = 0; a < 8; a++) E[a] = *reinterpret_cast<const c64*>(bufE + 1024 * a + rd);
-#pragma unroll
-    for (int a = 0; a < 8; a++) O[a] = *reinterpret_cast<const c64*>(bufO + 1024 * a + rd);
-    // pass 2 + exchange-2 writes: writer lane = 8b + k1 holds reg c -> slot 64b + 8k1 + (c ^ k1)
-    {
-        c64 tw[7];
-#pragma unroll
-        for (int c = 1; c < 8; c++) tw[c - 1] = tab[kT2Off + (c - 1) * 8 + hi3];
-        compiler_fence();
-        radix8<DIR>(E);
-#pragma unroll
-        for (int c = 1; c < 8; c++) E[c] = cmul_tw<DIR>(E[c], tw[c - 1]);
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            *reinterpret_cast<c64*>(bufE + 16 * (64 * hi3 + 8 * lo3 + (c ^ lo3))) = E[c];
-        radix8<DIR>(O);
-#pragma unroll
-        for (int c = 1; c < 8; c++) O[c] = cmul_tw<DIR>(O[c], tw[c - 1]);
-#pragma unroll
-        for (int c = 0; c < 8; c++)
-            *reinterpret_cast<c64*>(bufO + 16 * (64 * hi3 + 8 * lo3 + (c ^ lo3))) = O[c];
-    }
-    wave_lds_fence();
-    // exchange-2 reads: reader lane = 8c + k1 wants reg b <- slot 64b + 8k1 + (c ^ k1)
-#pragma unroll
-    for (int b = 0; b < 8; b++) E[b] = *reinterpret_cast<const c64*>(bufE + 1024 * b + rd);
-#pragma unroll
-    for (int b = 0; b < 8; b++) O[b] = *reinterpret_cast<const c64*>(bufO + 1024 * b + rd);
-    // pass 3
-    radix8<DIR>(E);
-    radix8<DIR>(O);
-    compiler_fence(); // the tile's next writer stays behind these reads
-}
-
 // ---- register <-> lane transposition without LDS ------------------------------------------------
 // Swap the three bits of the register index r (V[r], r = 4 r2 + 2 r1 + r0) with lane bits 5, 4, 3:
 // afterwards lane (h2 h1 h0 | lo3) register (r2 r1 r0) holds what lane (r2 r1 r0 | lo3) register
@@ -317,9 +252,6 @@ __device__ __forceinline__ void swap_lane8(double& a, double& b)
 }
 __device__ __forceinline__ void lane_transpose_hi3(c64 (&V)[8])
 {
-#if defined(SPF_ABL) && SPF_ABL == 3 // (timing-only ablation: see spf_kernels.hpp)
-    return;
-#endif
 #pragma unroll
     for (int r = 0; r < 4; r++) { // register bit 2 <-> lane bit 5
         swap_halves32(V[r].re, V[r + 4].re);
@@ -338,9 +270,10 @@ __device__ __forceinline__ void lane_transpose_hi3(c64 (&V)[8])
     }
 }
 
-// fft512_pair, software-pipelined for a wave that has its SIMD to itself (the latency kernels): there
-// nothing else covers an LDS round trip, and the lockstep form above costs exactly twice one transform
-// (measured 5 774 vs 2 707 cycles).  A wave's DS instructions execute in issue order, so a read issued
+// Two independent 512-point DFTs (the even / odd sample halves of one 1024-point transform; the DAG and exchange images of
+// fft512_single, each on its own 8 KiB tile bufE / bufO), software-pipelined for a wave that has its SIMD to itself (the latency
+// kernels): there nothing else covers an LDS round trip, and the two advanced in lockstep with the LDS queue drained between
+// the passes cost exactly twice one transform (measured 5 774 vs 2 707 cycles).  A wave's DS instructions execute in issue order, so a read issued
 // behind the writes of the same image needs no drain: every exchange of one transform is issued and then
 // left in flight under a radix-8 pass of the other.  Same butterflies on the same values: same words.
 // (Exchange 2 in registers, `lane_transpose_hi3` as in fft512_pair1, trades the LDS store path the four waves of a CU
@@ -408,7 +341,7 @@ __device__ __forceinline__ void fft512_pair_pipelined(c64 (&E)[8], c64 (&O)[8], 
     compiler_fence(); // the tile's next writer stays behind these reads
 }
 
-// fft512_pair with ONE 8 KiB exchange image for both transforms — the form that fits two waves per
+// A transform pair with ONE 8 KiB exchange image for both transforms — the form that fits two waves per
 // SIMD (blind_rotate2p_kernel: 256 registers, 8 KiB of LDS per wave).  A wave's DS instructions execute
 // in issue order, so the two transforms can take turns on the same image as long as the program
 // order is  A.write, A.read, B.write, B.read, A.write, ...: each read is issued one butterfly pass
@@ -500,13 +433,14 @@ __device__ __forceinline__ void fft512_pair1(c64 (&A)[8], c64 (&B)[8], char* buf
     sched_fence(); // the image's next writer stays behind these reads
 }
 
-// ---- fft512_pair1 with the LDS stores SPREAD through the arithmetic ------------------------------------------------------
+// ---- the LDS stores SPREAD through the arithmetic ------------------------------------------------------------------------
 // tools/microbench/fft_pair_bench.hip (r04): eight waves per CU running transform pairs in lockstep need 7.9 k cycles per pair,
 // the butterflies alone 4.7 k and the LDS traffic alone 4.2 k — the two hardly overlap, because each exchange leaves the wave as
 // a burst of eight `ds_write_b128` (13 cycles of the CU's store path each, all eight waves bursting at once) and the other
 // transform's table reads queue behind it.  Here the eight stores of one transform are issued two at a time between the
-// three butterfly stages and the twiddle products of the OTHER transform (7.4 k cycles per pair in the same probe).  radix8 is
-// cut into its three stages for that; the operations and their order per value are those of `radix8`: same words.
+// three butterfly stages and the twiddle products of the OTHER transform (7.4 k cycles per pair in the same probe; that
+// variant without shared twiddles lives beside the probe, tools/microbench/fft_pair1s.hpp; the library ships fft512_pair1ts).
+// radix8 is cut into its three stages for that; the operations and their order per value are those of `radix8`: same words.
 template <int DIR> __device__ __forceinline__ void radix8_stage1(const c64 (&v)[8], c64 (&s)[4], c64 (&t)[4])
 {
 #pragma unroll
@@ -557,156 +491,6 @@ template <int DIR> __device__ __forceinline__ void radix8_stage3(c64 (&v)[8], co
         v[7] = {u[5].re + u[7].im, u[5].im - u[7].re};
     }
 }
-// radix-8 of X, then its seven twiddle products (table entries tw_base[stride * (k - 1)]), with the eight LDS operations
-// op(0) .. op(7) of the caller issued two at a time between the stages
-template <int DIR, class OP>
-__device__ __forceinline__ void radix8_tw_spread(c64 (&X)[8], const c64* tw_base, int stride, OP op)
-{
-    c64 s[4], t[4], u[8];
-    radix8_stage1<DIR>(X, s, t);
-    sched_fence();
-    op(0); op(1);
-    sched_fence();
-    radix8_stage2<DIR>(s, t, u);
-    sched_fence();
-    op(2); op(3);
-    sched_fence();
-    radix8_stage3<DIR>(X, u);
-    sched_fence();
-    op(4); op(5);
-    sched_fence();
-#pragma unroll
-    for (int k = 1; k < 5; k++) X[k] = cmul_tw<DIR>(X[k], tw_base[stride * (k - 1)]);
-    sched_fence();
-    op(6); op(7);
-    sched_fence();
-#pragma unroll
-    for (int k = 5; k < 8; k++) X[k] = cmul_tw<DIR>(X[k], tw_base[stride * (k - 1)]);
-    sched_fence();
-}
-template <int DIR, int XP = 2, class MID = no_hook>
-__device__ __forceinline__ void fft512_pair1s(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
-{
-    static_assert(XP == 1 || XP == 2, "exchange 2 of B (XP = 2) or of both transforms (XP = 1) in registers");
-    constexpr bool XA = XP == 1;
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const uint32_t rd1 = 16 * (8 * lo3 + (hi3 ^ lo3));
-    const uint32_t rd2 = 16 * (8 * hi3 + (hi3 ^ lo3));
-    const uint32_t wbase = 16 * (64 * hi3 + lo3);
-    char* wr[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) wr[r] = buf + ((wbase ^ (16 * r)) + 128 * r);
-    const c64* t1 = tab + kT1Off + lane;
-    const c64* t2 = tab + kT2Off + hi3;
-    // pass 1 of A
-    radix8<DIR>(A);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; k1++) A[k1] = cmul_tw<DIR>(A[k1], t1[64 * (k1 - 1)]);
-    sched_fence();
-    // pass 1 of B, A's exchange-1 stores spread through it
-    radix8_tw_spread<DIR>(B, t1, 64, [&](int k) { *reinterpret_cast<c64*>(wr[k]) = A[k]; });
-    // A's exchange-1 reads (ahead of B's stores to the same image: a wave's DS instructions execute in issue order), then
-    // pass 2 of A with B's exchange-1 stores spread through it
-#pragma unroll
-    for (int a = 0; a < 8; a++) A[a] = *reinterpret_cast<const c64*>(buf + 1024 * a + rd1);
-    sched_fence();
-    radix8_tw_spread<DIR>(A, t2, 8, [&](int k) { *reinterpret_cast<c64*>(wr[k]) = B[k]; });
-    mid();
-#pragma unroll
-    for (int a = 0; a < 8; a++) B[a] = *reinterpret_cast<const c64*>(buf + 1024 * a + rd1);
-    sched_fence();
-    if constexpr (XA) {
-        lane_transpose_hi3(A);
-        radix8<DIR>(A); // pass 3 of A
-        sched_fence();
-        radix8<DIR>(B);
-#pragma unroll
-        for (int c = 1; c < 8; c++) B[c] = cmul_tw<DIR>(B[c], t2[8 * (c - 1)]);
-        sched_fence();
-        lane_transpose_hi3(B);
-        radix8<DIR>(B);
-    } else {
-        // pass 2 of B, A's exchange-2 stores spread through it
-        radix8_tw_spread<DIR>(B, t2, 8, [&](int k) { *reinterpret_cast<c64*>(wr[k]) = A[k]; });
-#pragma unroll
-        for (int b = 0; b < 8; b++) A[b] = *reinterpret_cast<const c64*>(buf + 1024 * b + rd2);
-        sched_fence();
-        lane_transpose_hi3(B);
-        radix8<DIR>(A); // pass 3 of A, its exchange-2 reads having travelled under B's transposition
-        radix8<DIR>(B);
-    }
-    sched_fence(); // the image's next writer stays behind these reads
-}
-
-// ---- fft512_pair1 with EARLY reads ---------------------------------------------------------------------------------------
-// fft512_pair1 issues the reads of an exchange one butterfly block behind its stores (the registers of the transform that is
-// in LDS are free for the other one's temporaries meanwhile), so the reads have only the next store burst to complete under.
-// Where registers allow (polynomial 0's forward pair: the frequency-domain product is not live yet; the inverse pair: it has
-// just been consumed), the reads go out right behind their own stores — a wave's DS instructions execute in issue order, the
-// image is free again for the other transform's stores as soon as the reads are ISSUED — and have a whole butterfly block of
-// the other transform to land under.  Same butterflies on the same values: same words.
-template <int DIR, int XP = 2, class MID = no_hook>
-__device__ __forceinline__ void fft512_pair1e(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
-{
-    static_assert(XP == 1 || XP == 2, "exchange 2 of B (XP = 2) or of both transforms (XP = 1) in registers");
-    constexpr bool XA = XP == 1;
-    const int hi3 = lane >> 3, lo3 = lane & 7;
-    const uint32_t rd1 = 16 * (8 * lo3 + (hi3 ^ lo3));
-    const uint32_t rd2 = 16 * (8 * hi3 + (hi3 ^ lo3));
-    const uint32_t wbase = 16 * (64 * hi3 + lo3);
-    char* wr[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) wr[r] = buf + ((wbase ^ (16 * r)) + 128 * r);
-    // pass 1 of A, exchange 1 of A out and straight back
-    radix8<DIR>(A);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; k1++) A[k1] = cmul_tw<DIR>(A[k1], tab[kT1Off + (k1 - 1) * 64 + lane]);
-#pragma unroll
-    for (int k1 = 0; k1 < 8; k1++) *reinterpret_cast<c64*>(wr[k1]) = A[k1];
-    sched_fence();
-#pragma unroll
-    for (int a = 0; a < 8; a++) A[a] = *reinterpret_cast<const c64*>(buf + 1024 * a + rd1);
-    sched_fence();
-    // pass 1 of B (A's reads land under it), exchange 1 of B
-    radix8<DIR>(B);
-#pragma unroll
-    for (int k1 = 1; k1 < 8; k1++) B[k1] = cmul_tw<DIR>(B[k1], tab[kT1Off + (k1 - 1) * 64 + lane]);
-    sched_fence();
-#pragma unroll
-    for (int k1 = 0; k1 < 8; k1++) *reinterpret_cast<c64*>(wr[k1]) = B[k1];
-    sched_fence();
-#pragma unroll
-    for (int a = 0; a < 8; a++) B[a] = *reinterpret_cast<const c64*>(buf + 1024 * a + rd1);
-    sched_fence();
-    // pass 2 of A (B's reads land under it)
-    radix8<DIR>(A);
-#pragma unroll
-    for (int c = 1; c < 8; c++) A[c] = cmul_tw<DIR>(A[c], tab[kT2Off + (c - 1) * 8 + hi3]);
-    sched_fence();
-    mid();
-    if constexpr (XA) {
-        lane_transpose_hi3(A);
-        radix8<DIR>(A); // pass 3 of A
-        sched_fence();
-    } else {
-#pragma unroll
-        for (int c = 0; c < 8; c++) *reinterpret_cast<c64*>(wr[c]) = A[c];
-        sched_fence();
-#pragma unroll
-        for (int b = 0; b < 8; b++) A[b] = *reinterpret_cast<const c64*>(buf + 1024 * b + rd2);
-        sched_fence();
-    }
-    // pass 2 of B (A's exchange-2 reads land under it), exchange 2 of B in registers
-    radix8<DIR>(B);
-#pragma unroll
-    for (int c = 1; c < 8; c++) B[c] = cmul_tw<DIR>(B[c], tab[kT2Off + (c - 1) * 8 + hi3]);
-    sched_fence();
-    lane_transpose_hi3(B);
-    if constexpr (!XA) radix8<DIR>(A); // pass 3 of A
-    radix8<DIR>(B);
-    sched_fence(); // the image's next writer stays behind these reads
-}
-
 // ---- fft512_pair1 with the pass twiddles requested EARLY and SHARED by the two transforms ---------------------------------
 // The ISA of fft512_pair1 (r04, `tools/isa_build.sh`) shows what hipcc makes of `X[k] = cmul_tw(X[k], tab[...])` when registers
 // are tight: the seven twiddles of a pass are fetched just in time, one or two at a time, each `ds_read_b128` followed by an
@@ -784,10 +568,11 @@ __device__ __forceinline__ void fft512_pair1t(c64 (&A)[8], c64 (&B)[8], char* bu
     sched_fence(); // the image's next writer stays behind these reads
 }
 
-// fft512_pair1t with (EARLY) the reads of an exchange issued right behind its own stores and / or (SPREAD) the stores of one
-// transform issued two at a time between the butterfly stages of the other — the combinations r04 measured after the
-// shared twiddles had removed the exposed table reads (profiles/r04_experiments_blind_rotate.md).
-// radix8_twr_spread with the stores packed into the three butterfly stages (3 + 3 + 2) and `after()` — the reads of the
+// fft512_pair1ts below: fft512_pair1t with the stores of one transform issued two at a time between the butterfly stages of the
+// other, measured after the shared twiddles had removed the exposed table reads (profiles/r04_experiments_blind_rotate.md; the
+// reads of an exchange issued right behind its own stores, alone or on top of `…t`, lost there: 7 969 against 7 877 and 7 866
+// against 6 638 cycles per pair, 42.45 against 40.25 ms per 4096).
+// radix8_twr_spread2: radix8_twr_spread with the stores packed into the three butterfly stages (3 + 3 + 2) and `after()` — the reads of the
 // transform just stored — issued behind the last store, ahead of the seven twiddle products: the butterfly temporaries are
 // dead there and the stored transform's registers are free, so the reads cost no registers and have the products to land under
 template <int DIR, class OP, class AFTER>
@@ -855,8 +640,8 @@ __device__ __forceinline__ void pair_tail_through_image(c64 (&A)[8], c64 (&B)[8]
     sched_fence();
     radix8<DIR>(B);
 }
-template <int DIR, int XP, bool EARLY, bool SPREAD, class MID = no_hook>
-__device__ __forceinline__ void fft512_pair1x(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
+template <int DIR, int XP = 2, class MID = no_hook>
+__device__ __forceinline__ void fft512_pair1ts(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
 {
     static_assert(XP == 2 || XP == 0, "exchange 2 of B in registers (2) or through the image behind A's (0)");
     const int hi3 = lane >> 3, lo3 = lane & 7;
@@ -875,59 +660,26 @@ __device__ __forceinline__ void fft512_pair1x(c64 (&A)[8], c64 (&B)[8], char* bu
 #pragma unroll
     for (int k = 0; k < 7; k++) tw[k] = tab[kT1Off + k * 64 + lane];
     compiler_fence();
-    // pass 1 of A
+    // pass 1 of A, then pass 1 of B with A's exchange-1 stores spread through it
     radix8<DIR>(A);
 #pragma unroll
     for (int k1 = 1; k1 < 8; k1++) A[k1] = cmul_tw<DIR>(A[k1], tw[k1 - 1]);
-    if constexpr (!SPREAD) {
+    sched_fence();
+    radix8_twr_spread<DIR>(B, tw, [&](int k) { store(A, k); });
+    load(A, rd1);
+    sched_fence();
+    // T2 for both transforms, pass 2 of A with B's exchange-1 stores
 #pragma unroll
-        for (int k = 0; k < 8; k++) store(A, k);
-        sched_fence();
-        if constexpr (EARLY) { load(A, rd1); sched_fence(); }
-        radix8<DIR>(B);
-#pragma unroll
-        for (int k1 = 1; k1 < 8; k1++) B[k1] = cmul_tw<DIR>(B[k1], tw[k1 - 1]);
-        sched_fence();
-    } else {
-        sched_fence();
-        radix8_twr_spread<DIR>(B, tw, [&](int k) { store(A, k); });
-    }
-    if constexpr (!EARLY || SPREAD) { load(A, rd1); sched_fence(); }
-    // exchange 1 of B, T2 for both transforms, pass 2 of A
-    if constexpr (!SPREAD) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) store(B, k);
-        sched_fence();
-        if constexpr (EARLY) { load(B, rd1); sched_fence(); }
-#pragma unroll
-        for (int c = 0; c < 7; c++) tw[c] = tab[kT2Off + c * 8 + hi3];
-        compiler_fence();
-        radix8<DIR>(A);
-#pragma unroll
-        for (int c = 1; c < 8; c++) A[c] = cmul_tw<DIR>(A[c], tw[c - 1]);
-        sched_fence();
-    } else {
-#pragma unroll
-        for (int c = 0; c < 7; c++) tw[c] = tab[kT2Off + c * 8 + hi3];
-        compiler_fence();
-        radix8_twr_spread<DIR>(A, tw, [&](int k) { store(B, k); });
-    }
+    for (int c = 0; c < 7; c++) tw[c] = tab[kT2Off + c * 8 + hi3];
+    compiler_fence();
+    radix8_twr_spread<DIR>(A, tw, [&](int k) { store(B, k); });
     mid();
-    if constexpr (!EARLY || SPREAD) { load(B, rd1); sched_fence(); }
-    // exchange 2 of A, pass 2 of B
-    if constexpr (!SPREAD) {
-#pragma unroll
-        for (int k = 0; k < 8; k++) store(A, k);
-        sched_fence();
-        if constexpr (EARLY) { load(A, rd2); sched_fence(); }
-        radix8<DIR>(B);
-#pragma unroll
-        for (int c = 1; c < 8; c++) B[c] = cmul_tw<DIR>(B[c], tw[c - 1]);
-        sched_fence();
-    } else {
-        radix8_twr_spread<DIR>(B, tw, [&](int k) { store(A, k); });
-    }
-    if constexpr (!EARLY || SPREAD) { load(A, rd2); sched_fence(); }
+    load(B, rd1);
+    sched_fence();
+    // pass 2 of B with A's exchange-2 stores
+    radix8_twr_spread<DIR>(B, tw, [&](int k) { store(A, k); });
+    load(A, rd2);
+    sched_fence();
     if constexpr (XP == 2) {
         lane_transpose_hi3(B);
         radix8<DIR>(A);
@@ -982,16 +734,6 @@ __device__ __forceinline__ void fft512_pair1ts2(c64 (&A)[8], c64 (&B)[8], char* 
     }
     sched_fence();
 }
-template <int DIR, int XP = 2, class MID = no_hook>
-__device__ __forceinline__ void fft512_pair1te(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
-{
-    fft512_pair1x<DIR, XP, true, false>(A, B, buf, tab, lane, mid);
-}
-template <int DIR, int XP = 2, class MID = no_hook>
-__device__ __forceinline__ void fft512_pair1ts(c64 (&A)[8], c64 (&B)[8], char* buf, const c64* tab, int lane, MID mid = MID())
-{
-    fft512_pair1x<DIR, XP, false, true>(A, B, buf, tab, lane, mid);
-}
 
 // round half away from zero, then reduce mod 2^64 into the torus exactly as
 // PolynomialFftRef::ifft does (entities/polynomial_fft.rs:82-99 -> simd/scalar.rs:26-35,
@@ -1012,27 +754,9 @@ __device__ __forceinline__ uint64_t f64_round_to_torus(double x)
     return (uint64_t)r;
 }
 
-// Same result as f64_round_to_torus for an input that is already an integer with |v| >= 2^52
-// (so round() is the identity): the low 64 bits of v in two's complement via two exact
-// floor/fma splits, then the saturating-cast quirk (v mod 2^64 == -2^63 reached from below
-// zero becomes +2^63 and saturates to 0x7FFF...F).
-__device__ __forceinline__ uint64_t f64_bigint_to_torus(double v)
-{
-    const double two32 = 4294967296.0, inv32 = 1.0 / 4294967296.0;
-    double hi = __builtin_floor(v * inv32);
-    double lo = __builtin_fma(hi, -two32, v);   // in [0, 2^32), exact
-    double hi2 = __builtin_floor(hi * inv32);
-    double hil = __builtin_fma(hi2, -two32, hi); // in [0, 2^32), exact
-    uint32_t ulo = (uint32_t)lo, uhi = (uint32_t)hil;
-    bool quirk = (v < 0.0) && (ulo == 0u) && (uhi == 0x80000000u);
-    uhi = quirk ? 0x7FFFFFFFu : uhi;
-    ulo = quirk ? 0xFFFFFFFFu : ulo;
-    return ((uint64_t)uhi << 32) | ulo;
-}
-
-// Integer form of f64_bigint_to_torus: for an integer-valued v with 2^52 <= |v| < 2^116 the low 64
-// bits of v in two's complement are (mantissa << (exponent - 1075)), negated for v < 0 — nine 32-bit
-// VALU instructions instead of seven f64 ones and two conversions.  `sh_or` collects the shift
+// Fast form of f64_round_to_torus for an input that is already an integer (so round() is the identity): for an
+// integer-valued v with 2^52 <= |v| < 2^116 the low 64 bits of v in two's complement are
+// (mantissa << (exponent - 1075)), negated for v < 0 — nine 32-bit VALU instructions.  `sh_or` collects the shift
 // amounts (the caller checks once per wave that every one is in [0, 64): that IS the magnitude
 // test), `quirk_min` becomes 0 if some value hits the saturating-cast quirk (v < 0 and low 64 bits
 // == 2^63, which `as i64` turns into 0x7FFF...F): the caller then redoes the wave's values with the
@@ -1065,7 +789,7 @@ __device__ __forceinline__ void torus_bits16_mantissa(const double (&tv)[16], ui
         for (int e = 0; e < 16; e++) t[e] = f64_round_to_torus(tv[e]);
     }
 }
-// untwist_to_torus with an integer conversion on the fast path (r03: 42.8 -> 42.3 ms per 4096 against r02's mantissa-extracting form).  For an integer-valued v with
+// The conversion of the sixteen values of a wave with an integer fast path (r03: 42.8 -> 42.3 ms per 4096 against r02's mantissa-extracting form).  For an integer-valued v with
 // 2^64 <= |v| < 2^116 the double's own bits shifted left by (exponent - 1075) mod 64 = (exponent + 13) & 63 ARE the low 64
 // bits of |v|: the shift is at least 12, so sign, exponent field and the implicit one all leave the word.  Negated for
 // v < 0.  Two checks per wave decide whether the sixteen values take this path: every exponent in [1087, 1138] (that IS the
@@ -1095,31 +819,17 @@ __device__ __forceinline__ void torus_bits16(const double (&tv)[16], uint64_t (&
         for (int e = 0; e < 16; e++) t[e] = f64_round_to_torus(tv[e]);
     }
 }
-#ifndef SPF_UNTWIST_PRE
-#define SPF_UNTWIST_PRE 0
-#endif
-// PRESCALED: the 1/1024 of the inverse transform is already in V — the blind-rotation kernels multiply with a bootstrap key
-// whose device image carries it (`scale_bootstrap_key_kernel`); a power of two commutes with every rounding on the way, so the
-// words are the same and 32 multiplications per polynomial are not executed
-template <bool MANTISSA_FORM = false, bool PRESCALED = false>
+// inverse side of a transform: (z * 1/1024) * conj(twist), then round / mod 2^64 / saturating cast of the 16 values
+// (polynomial_fft.rs:82-99), the twist factors read from the LDS image where they are used (all eight requested at once was
+// within run-to-run: 40.11 / 42.78 against 40.11 / 42.76 ms per 4096, profiles/r04_experiments_blind_rotate.md)
+template <bool MANTISSA_FORM = false>
 __device__ __forceinline__ void untwist_to_torus_bits(const c64 (&V)[8], const c64* twist_lds, uint64_t (&t)[16])
 {
     double tv[16];
-#if SPF_UNTWIST_PRE
-    c64 twf[8];
-#pragma unroll
-    for (int n1 = 0; n1 < 8; n1++) twf[n1] = twist_lds[64 * n1];
-    compiler_fence();
-#endif
 #pragma unroll
     for (int n1 = 0; n1 < 8; n1++) {
-        c64 xs = V[n1];
-        if constexpr (!PRESCALED) xs = {V[n1].re * (1.0 / 1024.0), V[n1].im * (1.0 / 1024.0)};
-#if SPF_UNTWIST_PRE
-        c64 u = cmul_nf_conj(xs, twf[n1]);
-#else
+        c64 xs = {V[n1].re * (1.0 / 1024.0), V[n1].im * (1.0 / 1024.0)};
         c64 u = cmul_nf_conj(xs, twist_lds[64 * n1]);
-#endif
         tv[n1] = u.re;
         tv[8 + n1] = u.im;
     }
@@ -1135,7 +845,7 @@ __device__ __forceinline__ uint64_t add_u32_to_u64(uint64_t a, uint32_t b)
     return out;
 }
 
-// NEGATED-ACCUMULATOR form of untwist_to_torus_bits + `acc += t` (blind_rotate2p_body with SPF_BR_NEG): the caller keeps
+// NEGATED-ACCUMULATOR form of untwist_to_torus_bits + `acc += t` (the blind-rotation bodies): the caller keeps
 // nacc = -acc (mod 2^64) and this does nacc -= t, i.e. nacc += (-t).  Same words as the plain form, fewer VALU cycles
 // (tools/microbench/valu_rates.hip, profiles/r05_valu_rates.md: a v_sub_co / v_subb pair costs 9.8 cycles of a SIMD, the
 // 64-bit add v_lshl_add_u64 4.8, a VOP2 32-bit operation 2.5, a VOP3 one 4.5):
@@ -1147,9 +857,12 @@ __device__ __forceinline__ uint64_t add_u32_to_u64(uint64_t a, uint32_t b)
 //     bit-field extract — and the saturating-cast quirk by a running signed minimum of the results' high words (INT_MIN
 //     <=> some magnitude has the high word 0x80000000; VOP2) instead of one 64-bit compare per value.
 // The literal fall-back takes the original value (-tvn, exact) and is subtracted.
+// The 1/1024 of the inverse transform is already in V: the blind-rotation kernels multiply with a bootstrap key whose device image
+// carries it (`scale_bootstrap_key_kernel`); a power of two commutes with every rounding on the way, so the words are the same
+// and 32 multiplications per polynomial are not executed.
 // TWIST_AT_ONCE: the eight twist factors requested together ahead of the products (the latency shapes, one wave per SIMD: 3.572 ->
 // 3.542 ms per 64, 6.695 -> 6.669 per 512; the four-per-workgroup shape is 0.1 % slower with it)
-template <bool PRESCALED, bool TWIST_AT_ONCE = false>
+template <bool TWIST_AT_ONCE = false>
 __device__ __forceinline__ void untwist_sub_from_negated(const c64 (&V)[8], const c64* twist_lds, uint64_t (&nacc)[16])
 {
     double tvn[16];
@@ -1161,8 +874,7 @@ __device__ __forceinline__ void untwist_sub_from_negated(const c64 (&V)[8], cons
     }
 #pragma unroll
     for (int n1 = 0; n1 < 8; n1++) {
-        c64 xs = V[n1];
-        if constexpr (!PRESCALED) xs = {V[n1].re * (1.0 / 1024.0), V[n1].im * (1.0 / 1024.0)};
+        const c64 xs = V[n1];
         const c64 tw = TWIST_AT_ONCE ? twf[TWIST_AT_ONCE ? n1 : 0] : twist_lds[64 * n1];
         // cmul_nf_conj negated: re = -(a.re b.re) - (a.im b.im), im = a.re b.im - a.im b.re
         tvn[n1] = -(xs.re * tw.re) - xs.im * tw.im;
@@ -1231,13 +943,9 @@ __device__ __forceinline__ uint32_t gadget_digits_packed(uint64_t x)
 
 // complex sample of digit j: re from the packed word of coefficient c, im from that of c + N/2,
 // sign-extended, converted to f64 and twisted (entities/polynomial.rs:257-274, scalar.rs:19-23)
-// The two-digit case (L = 2, LOGB = 16) without the packed form: the rounded top word s itself is kept, and
+// The two-digit case (L = 2, LOGB = 16) without the packed form: the rounded top word s = (x + 2^31) >> 32 itself is kept, and
 //   digit 0 = sext16(s),   digit 1 = sext16((s >> 16) + bit15(s)) = (int)(s + 0x8000) >> 16
 // (radix.rs:157-162: digit, shift, carry of digit >= B/2 into the next, digits as two's-complement small integers).
-__device__ __forceinline__ uint32_t gadget_round_top32(uint64_t x)
-{
-    return (uint32_t)(x >> 32) + (uint32_t)((x >> 31) & 1);
-}
 __device__ __forceinline__ c64 twisted_digit_top32(uint32_t s_re, uint32_t s_im, int j, c64 tw)
 {
     const int dre = j == 0 ? (int)(int16_t)(s_re & 0xFFFFu) : (int)(s_re + 0x8000u) >> 16;
@@ -1252,31 +960,6 @@ __device__ __forceinline__ c64 twisted_digit(uint32_t packed_re, uint32_t packed
     int dre = ((int)(packed_re << (32 - LOGB - sh))) >> (32 - LOGB);
     int dim = ((int)(packed_im << (32 - LOGB - sh))) >> (32 - LOGB);
     return cmul_nf({(double)dre, (double)dim}, tw);
-}
-
-// inverse side of a transform: (z * 1/1024) * conj(twist), then round / mod 2^64 / saturating cast
-// of the 16 values (polynomial_fft.rs:82-99): the short exact path when every value of the wave is
-// already an integer of magnitude >= 2^52, else the literal sequence; identical words either way.
-__device__ __forceinline__ void untwist_to_torus(const c64 (&V)[8], const c64 (&twist)[8], uint64_t (&t)[16])
-{
-    double tv[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 8; n1++) {
-        c64 xs = {V[n1].re * (1.0 / 1024.0), V[n1].im * (1.0 / 1024.0)};
-        c64 u = cmul_nf_conj(xs, twist[n1]);
-        tv[n1] = u.re;
-        tv[8 + n1] = u.im;
-    }
-    double mn = __builtin_fabs(tv[0]);
-#pragma unroll
-    for (int e = 1; e < 16; e++) mn = __builtin_fmin(mn, __builtin_fabs(tv[e]));
-    if (__all(mn >= 4503599627370496.0)) {
-#pragma unroll
-        for (int e = 0; e < 16; e++) t[e] = f64_bigint_to_torus(tv[e]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < 16; e++) t[e] = f64_round_to_torus(tv[e]);
-    }
 }
 
 } // namespace spf

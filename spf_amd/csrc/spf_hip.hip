@@ -34,27 +34,14 @@ using namespace spf;
 // otherwise.  The runtime reads the variable when it initialises (first HIP call of the process); this runs when the library is
 // loaded.  A process that has initialised HIP before loading the library keeps its setting: export GPU_MAX_HW_QUEUES there.
 __attribute__((constructor(101))) static void spf_ask_for_hw_queues() { (void)setenv("GPU_MAX_HW_QUEUES", "24", 0); }
-#if defined(SPF_ABL) && SPF_ABL != 0
-// a timing-only ablation build (spf_kernels.hpp, SPF_ABL) computes WRONG results on purpose: it says so when it is loaded
-__attribute__((constructor(102))) static void spf_ablation_banner()
-{
-    fprintf(stderr, "libspf_hip: TIMING-ONLY ablation build (SPF_ABL=%d): the blind rotation's results are WRONG by construction\n", (int)SPF_ABL);
-}
-#endif
 
 namespace {
 
 thread_local std::string g_create_error;
 
-// The three-ciphertexts-per-workgroup blind rotation for 2 x #CU < B <= 3 x #CU (r05, the 512 -> 513 step of the launch time:
-// 6.95 -> 9.76 ms).  Built, bit-equal (same output checksums at B = 513 / 520 / 600 / 700 / 768, both instantiations), and no faster
-// than four per workgroup — 9.90-9.97 ms against 9.74-9.82 (plain PBS 10.61 against 10.28): two of the four SIMDs still carry two
-// waves, and the step of a workgroup is the step of its slowest SIMD.  Off; -DSPF_TRIO_SHAPE=1 re-runs the row
-// (profiles/r05_experiments_other_kernels.md).  The alternative "512 on the two-per-workgroup shape + the rest on the eight-wave shape" runs
-// back to back (both shapes take a whole CU's LDS): 6.95 + 3.72 ms.
-#ifndef SPF_TRIO_SHAPE
-#define SPF_TRIO_SHAPE 0
-#endif
+// (A three-ciphertexts-per-workgroup blind rotation for 2 x #CU < B <= 3 x #CU — r05, the 512 -> 513 step of the launch time,
+// 6.95 -> 9.76 ms — was built, bit-equal and no faster than four per workgroup: 9.90-9.97 ms against 9.74-9.82, plain PBS 10.61
+// against 10.28; profiles/r05_experiments_other_kernels.md, source in profiles/r09_experimental_sources/retired_knobs.patch.)
 constexpr size_t kMaxGridRows = 32768; // rows per launch of the one-grid-row-per-ciphertext kernels
 
 struct DevBuf {
@@ -303,7 +290,7 @@ spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64
         return tsg.end();
     }
     BlindRotateArgs a{};
-    a.lwe_in = d_lwe; a.lut = d_lut; a.lut_stride = lut_stride; a.bsk = SPF_BSK_PRESCALED ? c->d_bsk_scaled : c->d_bsk;
+    a.lwe_in = d_lwe; a.lut = d_lut; a.lut_stride = lut_stride; a.bsk = c->d_bsk_scaled;
     a.tables = c->d_tables; a.out = d_out; a.out_stride = out_stride;
     a.n = c->prm.lwe_dimension; a.B = (uint32_t)B; a.log_chi = log_chi; a.log_v = log_v;
     a.body_rotate = body_rotate; a.sample_extract = extract ? 1u : 0u;
@@ -315,9 +302,8 @@ spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64
     const size_t n_cu = (size_t)c->n_cu;
     const bool quad = B <= n_cu && per_wg_hint <= 1;
     const bool pair2 = !quad && B <= 2 * n_cu && per_wg_hint <= 2;
-    const bool trio = !quad && !pair2 && B <= 3 * n_cu && per_wg_hint <= 3 && SPF_TRIO_SHAPE; // three per workgroup: fills the chip up to 3 x #CU
-    const size_t per_wg = quad ? 1 : (pair2 ? 2 : (trio ? 3 : 4));
-    dim3 grid((unsigned)((B + per_wg - 1) / per_wg)), block(pair2 ? 256 : (trio ? 384 : 512));
+    const size_t per_wg = quad ? 1 : (pair2 ? 2 : 4);
+    dim3 grid((unsigned)((B + per_wg - 1) / per_wg)), block(pair2 ? 256 : 512);
     TimedScope ts(c, s, T_PBS);
     {
         spf_status st = ts.begin();
@@ -342,10 +328,6 @@ spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64
     else if (quad) SPF_LAUNCH("blind_rotate8_kernel<2,16,even>", (blind_rotate8_kernel<2, 16, 0>), kBlindRotate8Lds);
     else if (pair2 && log_v == 0) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ">", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 1>), kBlindRotate2p2Lds);
     else if (pair2) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ",even>", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 0>), kBlindRotate2p2Lds);
-#if SPF_TRIO_SHAPE
-    else if (trio && log_v == 0) SPF_LAUNCH("blind_rotate2p3_kernel<2,16," SPF_STR(SPF_BR_OPT) ">", (blind_rotate2p3_kernel<2, 16, SPF_BR_OPT, 1>), kBlindRotate2p3Lds);
-    else if (trio) SPF_LAUNCH("blind_rotate2p3_kernel<2,16," SPF_STR(SPF_BR_OPT) ",even>", (blind_rotate2p3_kernel<2, 16, SPF_BR_OPT, 0>), kBlindRotate2p3Lds);
-#endif
     else if (log_v == 0) SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT_MIX) ">", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT_MIX, 1>), kBlindRotate2pLds);
     else SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT) ",even>", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT, 0>), kBlindRotate2pLds);
 #undef SPF_LAUNCH
@@ -551,18 +533,13 @@ void spf_default_params(spf_params* o)
     *o = spf_params{637, 2048, 1, 16, 2, 4, 4, 2, 6, 7, 6, 3, 15};
 }
 
-// the build's identity: version, target, the compile-time options of the blind rotation as built — and, first of all, whether
-// this is a TIMING-ONLY ablation build whose results are wrong by construction (SPF_ABL, spf_kernels.hpp)
+// the build's identity: version, target, the compile-time options of the blind rotation as built
 #define SPF_VSTR2(x) #x
 #define SPF_VSTR(x) SPF_VSTR2(x)
 const char* spf_version(void)
 {
     return "spf_hip 0.6 gfx950"
-#if defined(SPF_ABL) && SPF_ABL != 0
-           " ABLATION(" SPF_VSTR(SPF_ABL) ": timing only, results are WRONG)"
-#endif
            " (blind rotation: BR_OPT=" SPF_VSTR(SPF_BR_OPT) " BR_OPT_MIX=" SPF_VSTR(SPF_BR_OPT_MIX) " BR2_OPT=" SPF_VSTR(SPF_BR2_OPT)
-           " BR_NEG=" SPF_VSTR(SPF_BR_NEG) " BSK_PRESCALED=" SPF_VSTR(SPF_BSK_PRESCALED) " TRIO_SHAPE=" SPF_VSTR(SPF_TRIO_SHAPE)
 #ifdef SPF_STAMPS
            " STAMPS"
 #endif
@@ -672,12 +649,6 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                            hipFuncAttributeMaxDynamicSharedMemorySize, kBlindRotate2p2Lds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 0>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kBlindRotate2p2Lds));
-#if SPF_TRIO_SHAPE
-    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&blind_rotate2p3_kernel<2, 16, SPF_BR_OPT, 1>),
-                           hipFuncAttributeMaxDynamicSharedMemorySize, kBlindRotate2p3Lds));
-    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&blind_rotate2p3_kernel<2, 16, SPF_BR_OPT, 0>),
-                           hipFuncAttributeMaxDynamicSharedMemorySize, kBlindRotate2p3Lds));
-#endif
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&blind_rotate8_kernel<2, 16, 1>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kBlindRotate8Lds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&blind_rotate8_kernel<2, 16, 0>),
@@ -722,7 +693,6 @@ void spf_destroy(spf_ctx* c)
 static spf_status finish_bootstrap_key(spf_ctx* c)
 {
     if (c->generic) return SPF_OK; // (the generic kernels read the caller's spectra as they are)
-#if SPF_BSK_PRESCALED
     c->bsk_ready = false;
     const size_t n_complex = (size_t)c->prm.lwe_dimension * ggsw_fft_complex(c->prm, c->prm.pbs_radix_count);
     if (!c->d_bsk_scaled) HIPCHK(c, hipMalloc((void**)&c->d_bsk_scaled, n_complex * sizeof(c64)));
@@ -739,7 +709,6 @@ static spf_status finish_bootstrap_key(spf_ctx* c)
     if (bad)
         return fail(c, SPF_ERR_INVALID_ARGUMENT,
                     "bootstrap key holds a value that is no forward transform of a torus polynomial (NaN, or a non-zero magnitude outside [2^-900, 2^1000))");
-#endif
     return SPF_OK;
 }
 

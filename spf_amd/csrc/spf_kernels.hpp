@@ -70,15 +70,6 @@ __device__ __forceinline__ void lds_dma_piece(const void* sbase, uint32_t voff, 
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(saved_m0) : "v"(voff), "s"(sbase), "s"(lds) : "memory");
 }
-// the same for the waves whose (wave-uniform) flag is set, as ONE opaque group: a C++ branch on the wave index around a piece makes
-// hipcc restructure the step loop (1 060 B of scratch per lane in the three-ciphertext shape, 28.7 ms instead of 9)
-__device__ __forceinline__ void lds_dma_piece_if(uint32_t flag, const void* sbase, uint32_t voff, uint32_t lds)
-{
-    uint32_t saved_m0, tmp;
-    asm volatile("v_readfirstlane_b32 %1, %2\n\ts_cmp_eq_u32 %1, 0\n\ts_cbranch_scc1 .Ldmaskip%=\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %3, %4\n\ts_mov_b32 m0, %0\n.Ldmaskip%=:"
-                 : "=&s"(saved_m0), "=&s"(tmp) : "v"(flag), "v"(voff), "s"(sbase), "s"(lds) : "memory", "scc");
-}
 __device__ __forceinline__ uint32_t lds_address(const void* p)
 {
     return (uint32_t)(size_t)(const __attribute__((address_space(3))) void*)p;
@@ -189,57 +180,21 @@ static_assert(sizeof(SPF_PRIO_SCHED_EVEN) == 21 && sizeof(SPF_PRIO_SCHED_MIX) ==
 #ifndef SPF_BR2_OPT
 #define SPF_BR2_OPT 6  // blind_rotate2p2_kernel (two per workgroup): 6.87 ms per 512 against 6.96 with 14 (plain PBS 7.07 / 7.08)
 #endif
-#ifndef SPF_BSK_PRESCALED
-#define SPF_BSK_PRESCALED 1 // the device image of the bootstrap key carries the inverse transform's 1/1024 (scale_bootstrap_key_kernel)
-#endif
-#ifndef SPF_TWIST_PRE
-#define SPF_TWIST_PRE 1     // the eight twist factors of a polynomial requested at once ...
-#endif
-#ifndef SPF_TWIST_PRE_E4
-#define SPF_TWIST_PRE_E4 0  // ... except in the even-rotation instantiation of the four-per-workgroup shape (r05, see the twist)
-#endif
-#ifndef SPF_GATHER_FENCE
-#define SPF_GATHER_FENCE 1  // ... and all sixteen rotation-gather reads out before the first is consumed (together −0.2 / −0.4 %)
-#endif
-#ifndef SPF_COMBINE_PRE
-#define SPF_COMBINE_PRE 0
-#endif
-// SPF_BR_NEG = 1: the wave keeps the NEGATED accumulator nacc = -acc (mod 2^64) in its registers and stages that.  Every 64-bit
+// The wave keeps the NEGATED accumulator nacc = -acc (mod 2^64) in its registers and stages that.  Every 64-bit
 // subtraction of the step becomes an addition — the rotate-and-subtract `(+-acc[src]) - acc[me]` is `(+-nacc[src]) + nacc[me]`
 // with the gather's sign flipped, the rounding bit 2^31 and the +1 of the two's complement ride on ONE 32-bit addend
 // (v_mad_u64_u32), and the rounded top word is simply the high word of the sum; the torus conversion adds the integer of the
 // negated value (untwist_sub_from_negated).  hipcc emits a 9.8-cycle v_sub_co / v_subb pair for a 64-bit subtraction and a
 // 4.8-cycle v_lshl_add_u64 for an addition (tools/microbench/valu_rates.hip).  Same words: integer identities only.
-#ifndef SPF_BR_NEG
-#define SPF_BR_NEG 1
-#endif
-// SPF_ABL = n: TIMING-ONLY ablations of blind_rotate2p_body (wrong results; never in the library): what does the step cost without
-// 1 the torus conversion, 2 the rotation gather + decomposition, 3 the register-side exchange, 4 the multiply-accumulate and its
-// key reads, 5 the forward pairs, 6 the inverse pair.  profiles/r05_valu_rates.md, "what the step is made of".
-#ifndef SPF_ABL
-#define SPF_ABL 0
-#endif
+// The device image of the bootstrap key carries the inverse transform's 1/1024 (scale_bootstrap_key_kernel).
+// (The compile-time alternatives r02-r06 measured against this body and settled — the plain accumulator, the unscaled key, the
+// combine's cross values requested at once, the rotation gather without its fence, per-pair exchange-2 overrides, a free MAD
+// depth, the three-per-workgroup shape, the timing-only ablations — are listed with their numbers in
+// profiles/r09_retired_knobs.md and put back by profiles/r09_experimental_sources/retired_knobs.patch.)
 template <int L, int LOGB, int OPT, int W, int CTS = 4, int MIX = 1>
 __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, char* smem)
 {
     constexpr int XP = (OPT & 1) ? 1 : ((OPT & 2) ? 2 : 0);
-    // (A/B knobs: the exchange-2 choice of each of the three pairs of a step separately; default = the one OPT selects)
-#ifdef SPF_XP_F0
-    constexpr int XPF0 = SPF_XP_F0;
-#else
-    constexpr int XPF0 = XP;
-#endif
-#ifdef SPF_XP_F1
-    constexpr int XPF1 = SPF_XP_F1;
-#else
-    constexpr int XPF1 = XP;
-#endif
-#ifdef SPF_XP_I
-    constexpr int XPI = SPF_XP_I;
-#else
-    constexpr int XPI = XP;
-#endif
-    constexpr bool NEG = SPF_BR_NEG != 0;
 #ifdef SPF_STAMPS
     // per-phase wall cycles of this wave (diagnostic build; s_memtime drains lgkmcnt: ~5 % overhead)
     uint64_t st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -279,20 +234,13 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
     const uint32_t dma_voff = (uint32_t)tid * 16u;                   // this lane's bytes inside an 8 KiB piece row
     const uint32_t dma_dst = lds_address(bskring) + wv * 1024;        // this wave's 1 KiB of each piece row
     constexpr int kPieces = 2 * kBskSlotBytes / 1024, NW = 2 * CTS;   // 1 KiB pieces of a chunk; waves of the workgroup
+    static_assert(kPieces % NW == 0, "every wave copies the same number of 1 KiB pieces of a chunk (a three-per-workgroup shape would not)");
     auto ring_dma = [&](uint32_t chunk) {
         const char* src = reinterpret_cast<const char*>(a.bsk) +
                           (size_t)__builtin_amdgcn_readfirstlane(chunk) * (2 * kBskSlotBytes); // uniform
-        if constexpr (kPieces % NW == 0) {
 #pragma unroll
-            for (int k = 0; k < 2 * kBskSlotBytes / (NT * 16); k++)
-                lds_dma_piece(src + k * NT * 16, dma_voff, dma_dst + k * NT * 16);
-        } else {
-            // (three ciphertexts per workgroup: 64 pieces over six waves — wave v takes pieces v, v + 6, ...)
-            const uint32_t lane16 = (uint32_t)lane * 16u, ring0 = lds_address(bskring);
-#pragma unroll
-            for (int k = 0; k < kPieces / NW; k++) lds_dma_piece(src + (k * NW + wv) * 1024, lane16, ring0 + (k * NW + wv) * 1024);
-            lds_dma_piece_if(wv < kPieces % NW ? 1u : 0u, src + ((kPieces / NW) * NW + wv) * 1024, lane16, ring0 + ((kPieces / NW) * NW + wv) * 1024);
-        }
+        for (int k = 0; k < 2 * kBskSlotBytes / (NT * 16); k++)
+            lds_dma_piece(src + k * NT * 16, dma_voff, dma_dst + k * NT * 16);
     };
     ring_dma(0);
 
@@ -307,8 +255,7 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             for (int e = 0; e < 16; e++) {
                 uint32_t idx = (uint32_t)coef2(e) + bt;
                 uint64_t v = lut[p * kN + (idx & (kN - 1))];
-                if constexpr (NEG) acc[p][e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (NEG: acc[][] holds -accumulator throughout)
-                else acc[p][e] = ((idx >> 11) & 1) ? (uint64_t)0 - v : v;
+                acc[p][e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (acc[][] holds -accumulator throughout)
             }
     }
     __syncthreads();
@@ -376,53 +323,40 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             STAMP(0);
             if (p == 0) SPF_PRIO_POINT(2); else SPF_PRIO_POINT(9);
             uint32_t dig[16];
-#if SPF_ABL == 2 // (timing-only ablation, wrong results: no rotation gather, no subtraction, no rounding)
-#pragma unroll
-            for (int e = 0; e < 16; e++) dig[e] = (uint32_t)(acc[p][e] >> 32) ^ at;
-#else
             {
                 // source coefficient of element e: (c_e - at) mod 2N with c_e = c_0 + 128 m (m = e & 7, +1024
                 // for e >= 8): region (parity) and the low address bits do not depend on e
                 const uint32_t t0 = (uint32_t)(2 * lane + w) + 2 * kN - at;
                 const char* region = tile + (t0 & 1) * 8192;
-                uint32_t T0 = (t0 + 2048u) << 20; // (NEG) bit 31 = complement of bit 11 of t0; opaque so that it is re-derived per polynomial
-                if constexpr (NEG) asm volatile("" : "+v"(T0));
+                uint32_t T0 = (t0 + 2048u) << 20; // bit 31 = complement of bit 11 of t0; opaque so that it is re-derived per polynomial
+                asm volatile("" : "+v"(T0));
                 uint64_t gin[16];
 #pragma unroll
                 for (int e = 0; e < 16; e++) {
                     const uint32_t t = t0 + (e >> 3) * 1024 + (e & 7) * 128;
                     gin[e] = *reinterpret_cast<const uint64_t*>(region + ((t << 2) & 0x1FF8u));
                 }
-#if SPF_GATHER_FENCE
-                sched_fence(); // all sixteen reads out before the first is consumed (hipcc otherwise issues them four at a time)
-#else
-                compiler_fence();
-#endif
+                // all sixteen reads out before the first is consumed (hipcc otherwise issues them four at a time; r05, on OPT 14: 39.25 ms per
+                // 4096 without the fence against 39.01, profiles/r05_experiments_blind_rotate.md)
+                sched_fence();
 #pragma unroll
                 for (int e = 0; e < 16; e++) {
-                    const uint32_t t = t0 + (e >> 3) * 1024 + (e & 7) * 128;
-                    if constexpr (NEG) {
-                        // gin = nacc[src]; x = rot - acc[me] = (-+ nacc[src]) + nacc[me]: the sign mask m is the complement of bit 11 of t
-                        // (= bit 11 of t + 2048, brought to bit 31 once per polynomial: T0 + a literal per element);
-                        // x + 2^31 = (gin ^ m) + (nacc[me] + (2^31 + (m ? 1 : 0))), and the rounded top word is its high word.
-                        // The small pieces are pinned (opaque values, one v_mad_u64_u32): left to itself hipcc rebuilds the mask from a
-                        // bit-field extract, widens the 32-bit addend to a register pair and keeps all of it live across the transforms.
-                        const uint32_t m32 = (uint32_t)((int32_t)(T0 + (uint32_t)(((e >> 3) * 1024 + (e & 7) * 128) << 20)) >> 31);
-                        const uint64_t m = ((uint64_t)m32 << 32) | m32;
-                        uint32_t k32 = 0x80000000u - m32;
-                        dig[e] = (uint32_t)(((gin[e] ^ m) + add_u32_to_u64(acc[p][e], k32)) >> 32);
-                    } else {
-                        const uint64_t sgn = (uint64_t)((int64_t)((uint64_t)t << 52) >> 63); // bit 11 of t, spread
-                        const uint64_t rot = (gin[e] ^ sgn) - sgn;
-                        dig[e] = gadget_round_top32(rot - acc[p][e]); // the rounded top word; its two digits are taken at the twist
-                    }
+                    // gin = nacc[src]; x = rot - acc[me] = (-+ nacc[src]) + nacc[me]: the sign mask m is the complement of bit 11 of
+                    // t = t0 + 1024 (e >> 3) + 128 (e & 7) (= bit 11 of t + 2048, brought to bit 31 once per polynomial: T0 + a literal
+                    // per element); x + 2^31 = (gin ^ m) + (nacc[me] + (2^31 + (m ? 1 : 0))), and the rounded top word — its two digits
+                    // are taken at the twist — is its high word.
+                    // The small pieces are pinned (opaque values, one v_mad_u64_u32): left to itself hipcc rebuilds the mask from a
+                    // bit-field extract, widens the 32-bit addend to a register pair and keeps all of it live across the transforms.
+                    const uint32_t m32 = (uint32_t)((int32_t)(T0 + (uint32_t)(((e >> 3) * 1024 + (e & 7) * 128) << 20)) >> 31);
+                    const uint64_t m = ((uint64_t)m32 << 32) | m32;
+                    uint32_t k32 = 0x80000000u - m32;
+                    dig[e] = (uint32_t)(((gin[e] ^ m) + add_u32_to_u64(acc[p][e], k32)) >> 32);
                 }
             }
-#endif
             c64 VV[2][8];
             // (r05, on the negated-accumulator build: requested one by one 37.86-37.92 ms per 4096 against 38.20-38.24 for even rotations
             // on the four-per-workgroup shape; the mixing instantiation and the two-per-workgroup shape keep the batch: 39.85 against 39.95, 6.68 against 6.72)
-            constexpr bool kTwistBatch = (!MIX && CTS == 4) ? (SPF_TWIST_PRE_E4 != 0) : (SPF_TWIST_PRE != 0);
+            constexpr bool kTwistBatch = MIX || CTS != 4;
             if constexpr (kTwistBatch) {
                 // the eight twist factors in one go (hipcc fetches them two at a time, each pair waited for on the spot)
                 c64 twf[8];
@@ -451,15 +385,13 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             // (r03c: polynomial 0: the older waves lead through the forward transforms; polynomial 1: the younger)
             if (p == 0) SPF_PRIO_POINT(4); else SPF_PRIO_POINT(10);
             if (p == 1) ring_dma(chunk);
-#if SPF_ABL != 5 // (5: timing-only, the forward transform pairs are not executed)
             if constexpr (MIX) {
-                if (p == 0) SPF_PAIR_M0<+1, XPF0>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(17); });
-                else SPF_PAIR_M1<+1, XPF1>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(18); });
+                if (p == 0) SPF_PAIR_M0<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(17); });
+                else SPF_PAIR_M1<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(18); });
             } else {
-                if (p == 0) SPF_PAIR_E0<+1, XPF0>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(17); });
-                else SPF_PAIR_E1<+1, XPF1>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(18); });
+                if (p == 0) SPF_PAIR_E0<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(17); });
+                else SPF_PAIR_E1<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(18); });
             }
-#endif
             STAMP(3);
             if (p == 0) SPF_PRIO_POINT(5);
             // radix-2 stage across the two waves, both digits in one exchange: wave 0 finishes bins with
@@ -486,28 +418,8 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             STAMP(4);
             if (p == 0) SPF_PRIO_POINT(6); else SPF_PRIO_POINT(12);
             // X[i] = E[i] + W^k O[i], X[i+4] = E[i] - W^k O[i]: wave 0 holds E and receives O, wave 1 the reverse
-#if SPF_COMBINE_PRE
-            {
-                // all eight cross values and the four cross twiddles requested at once behind the barrier
-                c64 xin[2][4], wcf[4];
-#pragma unroll
-                for (int i = 0; i < 4; i++) wcf[i] = wc[64 * i];
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) xin[j][i] = reinterpret_cast<const c64*>(theirs)[(j * 4 + i) * 64 + lane];
-                compiler_fence();
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        const c64 Ei = w == 0 ? VV[j][i] : xin[j][i];
-                        const c64 t = cmul_tw<+1>(w == 0 ? xin[j][i] : VV[j][4 + i], wcf[i]);
-                        VV[j][i] = cadd(Ei, t);
-                        VV[j][i + 4] = csub(Ei, t);
-                    }
-            }
-#else
+            // (the eight cross values and four cross twiddles requested at once behind the barrier lost: 38.47 ms per 4096 against 38.23, r05;
+            // profiles/r05_experiments_blind_rotate.md)
             if constexpr (w == 0) {
 #pragma unroll
                 for (int j = 0; j < 2; j++)
@@ -530,28 +442,12 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                         VV[j][i + 4] = csub(Ei, t);
                     }
             }
-#endif
             STAMP(5);
-#if SPF_ABL == 4 // (timing-only: no key reads from the ring, no multiply-accumulate)
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int r = 0; r < 8; r++)
-#pragma unroll
-                    for (int q = 0; q < 2; q++) { // (scaled into the magnitude window of the conversion's short path)
-                        const bool first = p == 0 && j == 0;
-                        prod[q][r].re = __builtin_fma(VV[j][r].re, 0x1p58, first ? 0.0 : prod[q][r].re);
-                        prod[q][r].im = __builtin_fma(VV[j][r].im, 0x1p58, first ? 0.0 : prod[q][r].im);
-                    }
-#else
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const c64* row = reinterpret_cast<const c64*>(bskring + (1 - j) * kBskSlotBytes) + 256 * w + lane;
-#ifdef SPF_MAD_KD
-                constexpr int KD = SPF_MAD_KD;
-#else
-                constexpr int KD = (OPT & 4) ? 2 : 3; // key pairs in flight (bit 2: two — 8 registers fewer across the MAD)
-#endif
+                // key pairs in flight (bit 2: two — 8 registers fewer across the MAD; four lost 1.6 ms per 4096, r04: profiles/r04_experiments_blind_rotate.md)
+                constexpr int KD = (OPT & 4) ? 2 : 3;
                 c64 kb[KD][2];
                 auto key2 = [&](int grp, c64 (&dst)[2]) {
 #pragma unroll
@@ -562,7 +458,6 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                 };
                 key2(0, kb[0]);
                 if constexpr (KD >= 3) key2(1, kb[1]);
-                if constexpr (KD >= 4) key2(2, kb[2]);
 #pragma unroll
                 for (int grp = 0; grp < 8; grp++) {
                     if (grp + KD - 1 < 8) key2(grp + KD - 1, kb[(grp + KD - 1) % KD]);
@@ -579,7 +474,6 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                     }
                 }
             }
-#endif
             STAMP(6);
             if (p == 0) SPF_PRIO_POINT(7);
             __syncthreads(); // every wave is done with the ring and with its partner's cross data
@@ -640,18 +534,11 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                 for (int k = 0; k < 8; k++) // the slot just read
                     lds_dma_piece(src + (wv ^ 1) * 8192 + k * 1024, lane16, ring0 + (wv ^ 1) * 8192 + k * 1024);
                 constexpr int kRest = (2 * kBskSlotBytes - 2 * CTS * 8192) / 1024; // (fewer waves than slots: the rest of the ring)
-                if constexpr (kRest % NW == 0) {
+                static_assert(kRest % NW == 0, "every wave copies the same number of 1 KiB pieces of the rest of the ring");
 #pragma unroll
-                    for (int k = 0; k < kRest / NW; k++)
-                        lds_dma_piece(src + 2 * CTS * 8192 + (wv * (kRest / NW) + k) * 1024, lane16,
-                                      ring0 + 2 * CTS * 8192 + (wv * (kRest / NW) + k) * 1024);
-                } else {
-#pragma unroll
-                    for (int k = 0; k < kRest / NW; k++)
-                        lds_dma_piece(src + 2 * CTS * 8192 + (k * NW + wv) * 1024, lane16, ring0 + 2 * CTS * 8192 + (k * NW + wv) * 1024);
-                    lds_dma_piece_if(wv < kRest % NW ? 1u : 0u, src + 2 * CTS * 8192 + ((kRest / NW) * NW + wv) * 1024, lane16,
-                                     ring0 + 2 * CTS * 8192 + ((kRest / NW) * NW + wv) * 1024);
-                }
+                for (int k = 0; k < kRest / NW; k++)
+                    lds_dma_piece(src + 2 * CTS * 8192 + (wv * (kRest / NW) + k) * 1024, lane16,
+                                  ring0 + 2 * CTS * 8192 + (wv * (kRest / NW) + k) * 1024);
             }
         } else {
             if constexpr (w == 0) {
@@ -682,27 +569,13 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             SPF_PRIO_POINT(14);
             if (chunk < total_chunks) ring_dma(chunk); // rows of the next step's polynomial 0
         }
-#if SPF_ABL != 6 // (6: timing-only, the inverse transform pair is not executed)
-        if constexpr (MIX) SPF_PAIR_MI<-1, XPI>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
-        else SPF_PAIR_EI<-1, XPI>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
-#endif
+        if constexpr (MIX) SPF_PAIR_MI<-1, XP>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
+        else SPF_PAIR_EI<-1, XP>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
         STAMP(9);
         SPF_PRIO_POINT(15);
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-#if SPF_ABL == 1 // (timing-only: no untwist, no conversion to the torus)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[q][e] += (uint64_t)__double_as_longlong(e < 8 ? WW[q][e].re : WW[q][e - 8].im);
-#else
-            if constexpr (NEG) {
-                untwist_sub_from_negated<SPF_BSK_PRESCALED, CTS != 4>(WW[q], twist, acc[q]);
-            } else {
-                uint64_t t[16];
-                untwist_to_torus_bits<false, SPF_BSK_PRESCALED>(WW[q], twist, t);
-#pragma unroll
-                for (int e = 0; e < 16; e++) acc[q][e] += t[e];
-            }
-#endif
+            untwist_sub_from_negated<CTS != 4>(WW[q], twist, acc[q]);
             if (q == 0) SPF_PRIO_POINT(16);
         }
         STAMP(10);
@@ -718,12 +591,10 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
 
     if (!owns_output) return;
     uint64_t* out = a.out + (size_t)ct * a.out_stride;
-    if constexpr (NEG) {
 #pragma unroll
-        for (int p = 0; p < 2; p++)
+    for (int p = 0; p < 2; p++)
 #pragma unroll
-            for (int e = 0; e < 16; e++) acc[p][e] = (uint64_t)0 - acc[p][e];
-    }
+        for (int e = 0; e < 16; e++) acc[p][e] = (uint64_t)0 - acc[p][e];
     if (!a.sample_extract) {
 #pragma unroll
         for (int p = 0; p < 2; p++)
@@ -765,17 +636,6 @@ __global__ __launch_bounds__(256, 1) void blind_rotate2p2_kernel(BlindRotateArgs
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) blind_rotate2p_body<L, LOGB, OPT, 1, 2, MIX>(a, smem);
     else blind_rotate2p_body<L, LOGB, OPT, 0, 2, MIX>(a, smem);
-}
-
-// THREE ciphertexts per workgroup (six waves: two SIMDs carry two waves, two carry one; one workgroup per CU): for batches
-// between two and three ciphertexts per CU, where the four-ciphertext shape would leave a third of the CUs idle.  Same words.
-constexpr int kBlindRotate2p3Lds = kTableBytes + 3 * kWaveBufBytes + 2 * kBskSlotBytes;
-template <int L, int LOGB, int OPT, int MIX = 1>
-__global__ __launch_bounds__(384, 1) void blind_rotate2p3_kernel(BlindRotateArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) blind_rotate2p_body<L, LOGB, OPT, 1, 3, MIX>(a, smem);
-    else blind_rotate2p_body<L, LOGB, OPT, 0, 3, MIX>(a, smem);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -826,7 +686,7 @@ template <int L, int LOGB, int W, int J, int MIX>
 __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, char* smem)
 {
     static_assert(L == 2 && L * LOGB <= 32, "two digits, one per wave of a pair");
-    constexpr bool NEG = SPF_BR_NEG != 0; // negated accumulator, as in blind_rotate2p_body (3.72 -> 3.6x ms: the j = 0 wave's integer work is on the step's critical path)
+    // (negated accumulator, as in blind_rotate2p_body: 3.72 -> 3.6x ms, the j = 0 wave's integer work is on the step's critical path)
     c64* tab = reinterpret_cast<c64*>(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -860,8 +720,7 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
         for (int e = 0; e < 16; e++) {
             uint32_t idx = (uint32_t)coef2(e) + bt;
             uint64_t v = lut[h * kN + (idx & (kN - 1))];
-            if constexpr (NEG) acc[e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (NEG: acc[] holds -accumulator throughout)
-            else acc[e] = ((idx >> 11) & 1) ? (uint64_t)0 - v : v;
+            acc[e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (acc[] holds -accumulator throughout)
         }
     }
     __syncthreads(); // twiddle image in place
@@ -914,8 +773,8 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             STAMP8(1);
             const uint32_t t0 = (uint32_t)(2 * lane + w) + 2 * kN - at;
             const char* src = spectra((int)(t0 & 1), h);
-            uint32_t T0 = (t0 + 2048u) << 20; // (NEG) bit 31 = complement of bit 11 of t0
-            if constexpr (NEG) asm volatile("" : "+v"(T0));
+            uint32_t T0 = (t0 + 2048u) << 20; // bit 31 = complement of bit 11 of t0
+            asm volatile("" : "+v"(T0));
             uint64_t gin[16];
 #pragma unroll
             for (int e = 0; e < 16; e++) {
@@ -929,19 +788,12 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             uint32_t dig[16];
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                const uint32_t t = t0 + (e >> 3) * 1024 + (e & 7) * 128;
-                if constexpr (NEG) {
-                    // x + 2^31 = (gin ^ m) + (nacc[me] + (2^31 + (m ? 1 : 0))), m = complement of bit 11 of t (see blind_rotate2p_body)
-                    const uint32_t m32 = (uint32_t)((int32_t)(T0 + (uint32_t)(((e >> 3) * 1024 + (e & 7) * 128) << 20)) >> 31);
-                    const uint64_t m = ((uint64_t)m32 << 32) | m32;
-                    const uint32_t k32 = 0x80000000u - m32;
-                    const uint32_t s = (uint32_t)(((gin[e] ^ m) + add_u32_to_u64(acc[e], k32)) >> 32); // the rounded top word
-                    dig[e] = (s & 0xFFFFu) | ((s + 0x8000u) & 0xFFFF0000u); // digit 0 | digit 1 = (s >> 16) + carry of digit 0, as packed fields
-                } else {
-                    const uint64_t sgn = (uint64_t)((int64_t)((uint64_t)t << 52) >> 63); // bit 11 of t, spread
-                    const uint64_t rot = (gin[e] ^ sgn) - sgn;
-                    dig[e] = gadget_digits_packed<L, LOGB>(rot - acc[e]);
-                }
+                // x + 2^31 = (gin ^ m) + (nacc[me] + (2^31 + (m ? 1 : 0))), m = complement of bit 11 of t (see blind_rotate2p_body)
+                const uint32_t m32 = (uint32_t)((int32_t)(T0 + (uint32_t)(((e >> 3) * 1024 + (e & 7) * 128) << 20)) >> 31);
+                const uint64_t m = ((uint64_t)m32 << 32) | m32;
+                const uint32_t k32 = 0x80000000u - m32;
+                const uint32_t s = (uint32_t)(((gin[e] ^ m) + add_u32_to_u64(acc[e], k32)) >> 32); // the rounded top word
+                dig[e] = (s & 0xFFFFu) | ((s + 0x8000u) & 0xFFFF0000u); // digit 0 | digit 1 = (s >> 16) + carry of digit 0, as packed fields
             }
             static_assert(LOGB == 16, "digit 1 of the real and of the imaginary element share a 32-bit word");
             uint32_t pk[8];
@@ -1051,14 +903,7 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             fft512_single<-1, 7>(U, mine, tab, lane); // its exchanges follow the inbox reads in this wave's own LDS queue
             STAMP8(10);
             if constexpr (!LAST) SPF_KEY_PIECE(3);
-            if constexpr (NEG) {
-                untwist_sub_from_negated<SPF_BSK_PRESCALED, true>(U, twist_lds, acc);
-            } else {
-                uint64_t t[16];
-                untwist_to_torus_bits<false, SPF_BSK_PRESCALED>(U, twist_lds, t);
-#pragma unroll
-                for (int e = 0; e < 16; e++) acc[e] += t[e];
-            }
+            untwist_sub_from_negated<true>(U, twist_lds, acc);
             STAMP8(11);
         } else {
             if constexpr (!LAST) { SPF_KEY_PIECE(2); SPF_KEY_PIECE(3); }
@@ -1075,10 +920,8 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
 #undef STAMP8
 #undef SPF_KEY_PIECE
     if constexpr (J == 0) {
-        if constexpr (NEG) {
 #pragma unroll
-            for (int e = 0; e < 16; e++) acc[e] = (uint64_t)0 - acc[e];
-        }
+        for (int e = 0; e < 16; e++) acc[e] = (uint64_t)0 - acc[e];
         uint64_t* out = a.out + (size_t)ct * a.out_stride;
         if (!a.sample_extract) {
 #pragma unroll
@@ -1141,9 +984,6 @@ constexpr int cmux_lds_bytes(int gates) { return kTableBytes + gates * kWaveBufB
 
 #ifndef SPF_CMUX_INV_PAIR
 #define SPF_CMUX_INV_PAIR fft512_pair1
-#endif
-#ifndef SPF_CMUX_FWD_PRE
-#define SPF_CMUX_FWD_PRE 0
 #endif
 template <int L, int LOGB, int G, int W, bool STREAM>
 __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
@@ -1285,7 +1125,7 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
         STAMPS_(2);
         if (m > 0) cmux_sync(); // partner is done with my last cross data
         STAMPS_(3);
-        fft512_single<+1, SPF_CMUX_FWD_PRE>(V, mine, tab, lane);
+        fft512_single<+1>(V, mine, tab, lane);
         STAMPS_(4);
         c64 Ei[4], Oi[4];
         if (w == 0) {

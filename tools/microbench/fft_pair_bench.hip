@@ -24,6 +24,7 @@
 #else
 #include "../../spf_amd/csrc/spf_device.hpp"
 #endif
+#include "fft_pair1s.hpp"
 
 using namespace spf;
 
@@ -154,7 +155,7 @@ __device__ __forceinline__ void pair_lds_only(c64 (&A)[8], c64 (&B)[8], char* bu
     A[4] = cadd(A[4], tw[4]); A[5] = cadd(A[5], tw[5]); A[6] = cadd(A[6], tw[6]);
 }
 
-// variant 5 is spf_device.hpp's fft512_pair1s: the stores of one transform spread through the other's butterflies
+// variant 5 is fft_pair1s.hpp's fft512_pair1s: the stores of one transform spread through the other's butterflies
 
 // STG: waves 4-7 (the SIMD partners of waves 0-3) sleep STG x 64 cycles at the start of every pair (a small phase offset, so
 // that one wave's exchanges fall under the other's butterflies); PRI: 1 = waves 4-7 at s_setprio 1 for the whole pair,
@@ -200,6 +201,7 @@ __global__ __launch_bounds__(512, 2) void pair_loop(const c64* tables, unsigned 
         else if constexpr (V == 2) fft512_pair1<+1, 1>(A, B, buf, tab, lane);
         else if constexpr (V == 3) pair_arith_only<+1>(A, B, tab, lane);
         else if constexpr (V == 4) pair_lds_only(A, B, buf, tab, lane);
+        else if constexpr (V == 5) fft512_pair1s<+1, 2>(A, B, buf, tab, lane);
         else if constexpr (V == 13) pair_arith_only_folded<+1>(A, B, tab, lane);
         else if constexpr (V == 8) fft512_pair1t<+1, 2>(A, B, buf, tab, lane);
         else if constexpr (V == 9) fft512_pair1t<+1, 1>(A, B, buf, tab, lane);
@@ -313,6 +315,8 @@ int main(int argc, char** argv)
     run<13, 1>("13 arithmetic only, FMA-folded radix-8 (DAG-II gate)", d_tab, d_out, n_cu, iters);
     run<4, 0>("4 LDS traffic only (LDS floor)", d_tab, d_out, n_cu, iters);
     run<4, 1>("4 LDS traffic only (LDS floor)", d_tab, d_out, n_cu, iters);
+    run<5, 0>("5 fft512_pair1s: stores spread through the butterflies", d_tab, d_out, n_cu, iters);
+    run<5, 1>("5 fft512_pair1s: stores spread through the butterflies", d_tab, d_out, n_cu, iters);
     run<8, 1>("8 fft512_pair1t<+1,2>: factors requested early, shared", d_tab, d_out, n_cu, iters);
     run<11, 1>("11 fft512_pair1ts: shared twiddles + spread stores", d_tab, d_out, n_cu, iters);
     run<12, 1>("12 fft512_pair1ts2: + reads under the twiddle products", d_tab, d_out, n_cu, iters);
