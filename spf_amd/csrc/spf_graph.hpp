@@ -107,18 +107,6 @@ struct spf_graph {
     uint64_t exec_epoch = 0;
     uint32_t runs_since_plan = 0, captured_launches = 0;
 
-    size_t value_bytes(int kind) const
-    {
-        const size_t k = prm.glwe_size, N = prm.polynomial_degree, l = prm.cbs_radix_count;
-        switch (kind) {
-        case SPF_VAL_LWE0: return ((size_t)prm.lwe_dimension + 1) * 8;
-        case SPF_VAL_LWE1: return (k * N + 1) * 8;
-        case SPF_VAL_GLWE1: return (k + 1) * N * 8;
-        case SPF_VAL_GGSW1: return (k + 1) * l * (k + 1) * (N / 2) * 16;
-        case SPF_VAL_GLEV1: return l * (k + 1) * N * 8;
-        default: return 0;
-        }
-    }
     void drop_exec()
     {
         if (exec) (void)hipGraphExecDestroy(exec);
@@ -141,33 +129,8 @@ struct spf_graph {
 
 namespace spf_graph_impl {
 
-struct OpInfo {
-    int arity;
-    int in_kind[3];
-    int out_kind;
-};
-
-inline bool op_info(int op, OpInfo* o)
-{
-    switch (op) {
-    case SPF_OP_SAMPLE_EXTRACT: *o = {1, {SPF_VAL_GLWE1, -1, -1}, SPF_VAL_LWE1}; return true;
-    case SPF_OP_KEYSWITCH_L1_TO_L0: *o = {1, {SPF_VAL_LWE1, -1, -1}, SPF_VAL_LWE0}; return true;
-    case SPF_OP_NOT: *o = {1, {SPF_VAL_GLWE1, -1, -1}, SPF_VAL_GLWE1}; return true;
-    case SPF_OP_GLWE_ADD: *o = {2, {SPF_VAL_GLWE1, SPF_VAL_GLWE1, -1}, SPF_VAL_GLWE1}; return true;
-    case SPF_OP_CMUX: *o = {3, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1}; return true;
-    case SPF_OP_GLEV_CMUX: *o = {3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1}; return true;
-    case SPF_OP_MULTIPLY_GGSW_GLWE: *o = {2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, -1}, SPF_VAL_GLWE1}; return true;
-    case SPF_OP_CIRCUIT_BOOTSTRAP: *o = {1, {SPF_VAL_LWE0, -1, -1}, SPF_VAL_GGSW1}; return true;
-    case SPF_OP_SCHEME_SWITCH: *o = {1, {SPF_VAL_GLEV1, -1, -1}, SPF_VAL_GGSW1}; return true;
-    case SPF_OP_MUL_XN: *o = {1, {SPF_VAL_GLWE1, -1, -1}, SPF_VAL_GLWE1}; return true;
-    default: return false;
-    }
-}
-
-inline bool is_cmux_family(int op)
-{
-    return op == SPF_OP_CMUX || op == SPF_OP_GLEV_CMUX || op == SPF_OP_MULTIPLY_GGSW_GLWE;
-}
+// the table row (spf_ops.hpp) of a node's operation: a spf_graph_op that spf_graph_add_op has accepted
+inline const spf_ops::OpRow& op_row(int graph_op) { return spf_ops::row(spf_ops::pool_op_of(graph_op)); }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -184,7 +147,7 @@ inline spf_status plan(spf_graph* g)
         if (n.op < 0) {
             n.level = 0;
             n.off = off;
-            off = align_up(off + g->value_bytes(n.kind), 256);
+            off = align_up(off + value_bytes(g->prm, n.kind), 256);
         }
     g->inputs_bytes = off;
     uint32_t max_level = 0;
@@ -267,9 +230,8 @@ inline spf_status plan(spf_graph* g)
     // outputs of a group are consecutive rows
     size_t stage = 0;
     for (auto& gr : g->groups) {
-        OpInfo info{};
-        op_info(gr.op, &info);
-        const size_t ob = g->value_bytes(info.out_kind);
+        const spf_ops::OpRow& info = op_row(gr.op);
+        const size_t ob = value_bytes(g->prm, info.out_kind);
         gr.out_off = off;
         for (size_t i = 0; i < gr.members.size(); i++) g->nodes[gr.members[i]].off = off + i * ob;
         off = align_up(off + gr.members.size() * ob, 256);
@@ -279,13 +241,12 @@ inline spf_status plan(spf_graph* g)
     // operand access per group
     std::vector<void*> table;
     for (auto& gr : g->groups) {
-        OpInfo info{};
-        op_info(gr.op, &info);
+        const spf_ops::OpRow& info = op_row(gr.op);
         const size_t B = gr.members.size();
-        if (is_cmux_family(gr.op)) {
+        if (info.cmux_family) {
             // units: one per GLWE pair; {selector, low (a), high (b), out}
             const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
-            const size_t gw = g->value_bytes(SPF_VAL_GLWE1);
+            const size_t gw = value_bytes(g->prm, SPF_VAL_GLWE1);
             gr.ptr_index[0] = table.size();
             struct Unit { void* p[4]; };
             std::vector<Unit> units;
@@ -316,7 +277,7 @@ inline spf_status plan(spf_graph* g)
             continue;
         }
         for (int s = 0; s < info.arity; s++) {
-            const size_t ib = g->value_bytes(info.in_kind[s]);
+            const size_t ib = value_bytes(g->prm, info.in_kind[s]);
             bool contig = true;
             const size_t first = g->nodes[g->nodes[gr.members[0]].in[s]].off;
             for (size_t i = 1; i < B && contig; i++)
@@ -342,7 +303,7 @@ inline spf_status plan(spf_graph* g)
     if (getenv("SPF_GRAPH_WIDTHS")) { // diagnostic: CMUX-family launch widths (units) of the plan
         std::map<size_t, size_t> hist;
         for (auto& gr : g->groups)
-            if (is_cmux_family(gr.op)) hist[gr.members.size() * (gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1)]++;
+            if (op_row(gr.op).cmux_family) hist[gr.members.size() * (gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1)]++;
         for (auto& kv : hist) fprintf(stderr, "[graph widths] %zu units x %zu launches\n", kv.first, kv.second);
     }
     if (!g->h_inputs.resize(g->inputs_bytes)) return fail(c, SPF_ERR_HIP, "graph: out of host memory for the inputs");
@@ -357,29 +318,28 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
     spf_ctx* c = g->ctx;
     for (const auto& n : g->nodes)
         if (n.op == -2 && n.kind == SPF_VAL_GGSW1) {
-            const size_t sw = g->value_bytes(SPF_VAL_GGSW1);
+            const size_t sw = value_bytes(g->prm, SPF_VAL_GGSW1);
             HIPCHK(c, hipMemcpyAsync(g->d_arena + n.off, (const char*)c->d_ggsw_const + (size_t)(n.param & 1) * sw, sw,
                                      hipMemcpyDeviceToDevice, s));
         }
     g->n_launches = 0;
     for (const auto& gr : g->groups) {
-        OpInfo info{};
-        op_info(gr.op, &info);
+        const spf_ops::OpRow& info = op_row(gr.op);
         const size_t B = gr.members.size();
         char* out = g->d_arena + gr.out_off;
-        if (is_cmux_family(gr.op)) {
+        if (info.cmux_family) {
             const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
             spf_status st = spf_cmux_scattered_dev(c, s, B * per, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
         }
-        const char* in[2] = {nullptr, nullptr};
+        const void* in[3] = {nullptr, nullptr, nullptr};
         for (int sl = 0; sl < info.arity; sl++) {
             if (gr.contiguous[sl]) {
                 in[sl] = g->d_arena + gr.first_off[sl];
             } else {
-                spf_status st = spf_gather_rows_dev(c, s, B, g->value_bytes(info.in_kind[sl]) / 8,
+                spf_status st = spf_gather_rows_dev(c, s, B, value_bytes(g->prm, info.in_kind[sl]) / 8,
                                                     (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[sl]),
                                                     (uint64_t*)g->d_stage[sl]);
                 if (st != SPF_OK) return st;
@@ -387,32 +347,7 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                 in[sl] = g->d_stage[sl];
             }
         }
-        spf_status st = SPF_OK;
-        switch (gr.op) {
-        case SPF_OP_SAMPLE_EXTRACT:
-            st = spf_sample_extract_l1_dev(c, s, B, (const uint64_t*)in[0], (size_t)gr.param, (uint64_t*)out);
-            break;
-        case SPF_OP_KEYSWITCH_L1_TO_L0:
-            st = spf_keyswitch_lwe_l1_lwe_l0_dev(c, s, B, (const uint64_t*)in[0], (uint64_t*)out);
-            break;
-        case SPF_OP_CIRCUIT_BOOTSTRAP:
-            st = spf_circuit_bootstrap_dev(c, s, B, (const uint64_t*)in[0], (double*)out);
-            break;
-        case SPF_OP_SCHEME_SWITCH:
-            st = spf_scheme_switch_dev(c, s, B, (const uint64_t*)in[0], (double*)out);
-            break;
-        case SPF_OP_NOT:
-            st = spf_glwe_not_dev(c, s, B, (const uint64_t*)in[0], (uint64_t*)out);
-            break;
-        case SPF_OP_GLWE_ADD:
-            st = spf_glwe_xor_dev(c, s, B, (const uint64_t*)in[0], (const uint64_t*)in[1], (uint64_t*)out);
-            break;
-        case SPF_OP_MUL_XN:
-            st = spf_glwe_mul_xn_dev(c, s, B, (const uint64_t*)in[0], (size_t)gr.param, (uint64_t*)out);
-            break;
-        default:
-            st = fail(c, SPF_ERR_INVALID_ARGUMENT, "unknown graph operation");
-        }
+        const spf_status st = spf_ops::launch_op(c, s, info.op, B, in, out, gr.param, nullptr, 0, nullptr);
         if (st != SPF_OK) return st;
         g->n_launches++;
     }
@@ -427,8 +362,8 @@ inline spf_status plan_outputs(spf_graph* g)
     std::map<size_t, spf_graph::OutClass> by_words;
     for (size_t i = 0; i < g->outputs.size(); i++) {
         const auto& n = g->nodes[g->outputs[i].first];
-        auto& oc = by_words[g->value_bytes(n.kind) / 8];
-        oc.words = g->value_bytes(n.kind) / 8;
+        auto& oc = by_words[value_bytes(g->prm, n.kind) / 8];
+        oc.words = value_bytes(g->prm, n.kind) / 8;
         oc.which.push_back(i);
     }
     std::vector<void*> table;
@@ -469,19 +404,19 @@ inline spf_status run(spf_graph* g)
     // inputs: read the callers' buffers now (they may have changed since the last run)
     for (const auto& n : g->nodes) {
         if (n.op == -1) {
-            std::memcpy(g->h_inputs.data() + n.off, n.host, g->value_bytes(n.kind));
+            std::memcpy(g->h_inputs.data() + n.off, n.host, value_bytes(g->prm, n.kind));
         } else if (n.op == -2 && n.kind == SPF_VAL_GLEV1) {
             // trivial_glev_l1_{zero,one} (crypto/encryption.rs:434-451 -> trivially_encrypt_glev_ciphertext,
             // ops/encryption/glev_encryption.rs:23-80): GLWE j = zero mask, body = bit * q / B^(j+1) at coefficient 0
             uint64_t* v = reinterpret_cast<uint64_t*>(g->h_inputs.data() + n.off);
-            std::memset(v, 0, g->value_bytes(n.kind));
+            std::memset(v, 0, value_bytes(g->prm, n.kind));
             for (size_t j = 0; j < g->prm.cbs_radix_count; j++)
                 v[j * (k + 1) * N + k * N] = (n.param & 1) << (64 - g->prm.cbs_radix_log * (j + 1));
         } else if (n.op == -2 && n.kind != SPF_VAL_GGSW1) {
             // trivial_lwe / trivial_glwe of a bit at one plaintext bit (crypto/encryption.rs:345-412):
             // zero mask, body (coefficient 0) = bit << 63
             uint64_t* v = reinterpret_cast<uint64_t*>(g->h_inputs.data() + n.off);
-            std::memset(v, 0, g->value_bytes(n.kind));
+            std::memset(v, 0, value_bytes(g->prm, n.kind));
             const size_t body = n.kind == SPF_VAL_LWE0 ? g->prm.lwe_dimension : k * N;
             v[body] = (n.param & 1) << 63;
         }
@@ -574,7 +509,7 @@ void spf_graph_destroy(spf_graph* g)
 spf_status spf_graph_add_input(spf_graph* g, spf_value_kind kind, const void* host, uint32_t* node)
 {
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
-    if (!host || !node || g->value_bytes(kind) == 0) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph input: bad kind or null pointer");
+    if (!host || !node || value_bytes(g->prm, kind) == 0) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph input: bad kind or null pointer");
     spf_graph::Node n{};
     n.op = -1; n.kind = kind; n.host = host;
     *node = (uint32_t)g->nodes.size();
@@ -586,7 +521,7 @@ spf_status spf_graph_add_input(spf_graph* g, spf_value_kind kind, const void* ho
 spf_status spf_graph_add_trivial(spf_graph* g, spf_value_kind kind, uint64_t bit, uint32_t* node)
 {
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
-    if (!node || g->value_bytes(kind) == 0 || bit > 1)
+    if (!node || value_bytes(g->prm, kind) == 0 || bit > 1)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph constant: LWE0 / LWE1 / GLWE1 / GGSW1 / GLEV1 of bit 0 or 1");
     spf_graph::Node n{};
     n.op = -2; n.kind = kind; n.param = bit;
@@ -602,8 +537,9 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
                             uint32_t* node)
 {
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
-    spf_graph_impl::OpInfo info{};
-    if (!node || !spf_graph_impl::op_info(op, &info)) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    const int pop = spf_ops::pool_op_of(op);
+    if (!node || pop == spf_ops::kNone) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    const spf_ops::OpRow& info = spf_ops::row(pop);
     if (n_inputs != (size_t)info.arity || (n_inputs && !inputs))
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: wrong number of operands");
     spf_graph::Node n{};
@@ -613,9 +549,9 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
         if (g->nodes[inputs[i]].kind != info.in_kind[i]) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: operand has the wrong ciphertext type");
         n.in[i] = inputs[i];
     }
-    if (op == SPF_OP_SAMPLE_EXTRACT && param >= g->prm.polynomial_degree)
-        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: sample_extract index >= polynomial_degree");
-    n.param = (op == SPF_OP_SAMPLE_EXTRACT) ? param : (op == SPF_OP_MUL_XN ? param % (2 * (uint64_t)g->prm.polynomial_degree) : 0);
+    const char* why = nullptr;
+    if (spf_ops::op_param(g->prm, pop, &param, &why) != SPF_OK) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph op: ") + why);
+    n.param = param;
     *node = (uint32_t)g->nodes.size();
     g->nodes.push_back(n);
     g->planned = false;

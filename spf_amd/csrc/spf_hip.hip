@@ -189,13 +189,11 @@ spf_status ensure(spf_ctx* c, DevBuf& b, size_t bytes)
     return SPF_OK;
 }
 
-size_t lwe0_words(const spf_params& p) { return (size_t)p.lwe_dimension + 1; }
-size_t lwe1_words(const spf_params& p) { return (size_t)p.glwe_size * p.polynomial_degree + 1; }
-size_t glwe_words(const spf_params& p) { return (size_t)(p.glwe_size + 1) * p.polynomial_degree; }
-size_t ggsw_fft_complex(const spf_params& p, uint32_t count)
-{
-    return (size_t)(p.glwe_size + 1) * count * (p.glwe_size + 1) * (p.polynomial_degree / 2);
-}
+} // namespace
+
+#include "spf_ops.hpp" // ciphertext sizes, the operation table, the parameter rule, the dispatcher: where an operation is declared
+
+namespace {
 
 size_t ak_complex(const spf_params& p)
 {
@@ -1989,14 +1987,9 @@ spf_status spf_load_compute_key_nonfft_bincode(spf_ctx* c, const uint8_t* bytes,
 // Ciphertext wire format: see include/spf_hip.h.  (encryption.rs:23-110, 454-519; safe_bincode.rs:16-28.)
 size_t spf_ciphertext_words(const spf_params* p, spf_value_kind kind)
 {
-    if (!p) return 0;
-    switch (kind) {
-    case SPF_VAL_LWE0: return lwe0_words(*p);
-    case SPF_VAL_LWE1: return lwe1_words(*p);
-    case SPF_VAL_GLWE1: return glwe_words(*p);
-    case SPF_VAL_GLEV1: return (size_t)p->cbs_radix_count * glwe_words(*p);
-    default: return 0;
-    }
+    // (L1GgswCiphertext is not Serialize in the reference: the one kind that has a size in memory and none on the wire)
+    if (!p || kind == SPF_VAL_GGSW1) return 0;
+    return value_words(*p, kind);
 }
 
 static const char* wire_kind_name(spf_value_kind k)
@@ -2313,74 +2306,76 @@ void spf_pool_destroy(spf_pool* p)
 // (defined with the group, spf_group.hpp)
 static spf_pool* pool_deal(spf_pool* top, int* member);
 
-static spf_status pool_submit(spf_pool* p, int op, const void* a, const void* b, const void* c, void* out, uint64_t* ticket,
-                              uint64_t param = 0)
+// a host-pointer submit: the null and parameter checks of every wrapper below, then the operation goes to the pool the calling
+// thread is dealt to.  (Refusals are a bare status: no message is set.)
+static spf_status pool_submit(spf_pool* p, int op, std::initializer_list<const void*> in, void* out, uint64_t* ticket, uint64_t param = 0)
 {
-    if (!p) return SPF_ERR_INVALID_ARGUMENT;
+    if (!p || !out || !ticket) return SPF_ERR_INVALID_ARGUMENT;
+    const void* src[3] = {nullptr, nullptr, nullptr};
+    size_t k = 0;
+    for (const void* x : in) {
+        if (!x) return SPF_ERR_INVALID_ARGUMENT;
+        src[k++] = x;
+    }
+    const char* why = nullptr;
+    if (spf_ops::op_param(p->prm, op, &param, &why) != SPF_OK) return SPF_ERR_INVALID_ARGUMENT;
     int member = 0;
     spf_pool* q = pool_deal(p, &member);
     if (!q) return SPF_ERR_HIP; // no member of the group is in rotation
-    const spf_status st = q->submit(op, a, b, c, out, ticket, param);
+    const spf_status st = q->submit_impl(op, false, src, out, nullptr, nullptr, ticket, param);
     if (st == SPF_OK && q != p) *ticket |= (uint64_t)member << spf_pool::kMemberShift;
     return st;
 }
 
 extern "C" {
 
+// one per `FheOp` kind of `CircuitProcessor::exec_op` (circuit_processor/mod.rs:341-540), and the KeyswitchL1toL0 -> CircuitBootstrap chain
 spf_status spf_pool_submit_keyswitch(spf_pool* p, const uint64_t* in, uint64_t* out, uint64_t* ticket)
 {
-    return pool_submit(p, spf_pool_impl::OP_KEYSWITCH, in, nullptr, nullptr, out, ticket);
+    return pool_submit(p, spf_ops::OP_KEYSWITCH, {in}, out, ticket);
 }
 spf_status spf_pool_submit_circuit_bootstrap(spf_pool* p, const uint64_t* in, double* out, uint64_t* ticket)
 {
-    return pool_submit(p, spf_pool_impl::OP_CBS, in, nullptr, nullptr, out, ticket);
+    return pool_submit(p, spf_ops::OP_CBS, {in}, out, ticket);
 }
 spf_status spf_pool_submit_keyswitch_circuit_bootstrap(spf_pool* p, const uint64_t* in, double* out, uint64_t* ticket)
 {
-    return pool_submit(p, spf_pool_impl::OP_GATE_CBS, in, nullptr, nullptr, out, ticket);
+    return pool_submit(p, spf_ops::OP_GATE_CBS, {in}, out, ticket);
 }
 spf_status spf_pool_submit_cmux(spf_pool* p, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out,
                                 uint64_t* ticket)
 {
-    if (!p || !a || !b) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_CMUX, sel, a, b, out, ticket);
+    return pool_submit(p, spf_ops::OP_CMUX, {sel, a, b}, out, ticket);
 }
-
-// the remaining `FheOp` kinds of `CircuitProcessor::exec_op` (circuit_processor/mod.rs:341-540)
 spf_status spf_pool_submit_sample_extract(spf_pool* p, const uint64_t* glwe_in, size_t idx, uint64_t* lwe1_out, uint64_t* ticket)
 {
-    if (!p || idx >= p->prm.polynomial_degree) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_SAMPLE_EXTRACT, glwe_in, nullptr, nullptr, lwe1_out, ticket, idx);
+    return pool_submit(p, spf_ops::OP_SAMPLE_EXTRACT, {glwe_in}, lwe1_out, ticket, idx);
 }
 spf_status spf_pool_submit_not(spf_pool* p, const uint64_t* glwe_in, uint64_t* glwe_out, uint64_t* ticket)
 {
-    return pool_submit(p, spf_pool_impl::OP_NOT, glwe_in, nullptr, nullptr, glwe_out, ticket);
+    return pool_submit(p, spf_ops::OP_NOT, {glwe_in}, glwe_out, ticket);
 }
 spf_status spf_pool_submit_glwe_add(spf_pool* p, const uint64_t* a, const uint64_t* b, uint64_t* glwe_out, uint64_t* ticket)
 {
-    if (!p || !b) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_GLWE_ADD, a, b, nullptr, glwe_out, ticket);
+    return pool_submit(p, spf_ops::OP_GLWE_ADD, {a, b}, glwe_out, ticket);
 }
 spf_status spf_pool_submit_mul_xn(spf_pool* p, const uint64_t* glwe_in, size_t n, uint64_t* glwe_out, uint64_t* ticket)
 {
-    if (!p) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_MUL_XN, glwe_in, nullptr, nullptr, glwe_out, ticket, n % (2 * (size_t)p->prm.polynomial_degree));
+    return pool_submit(p, spf_ops::OP_MUL_XN, {glwe_in}, glwe_out, ticket, n);
 }
 spf_status spf_pool_submit_multiply_ggsw_glwe(spf_pool* p, const double* ggsw_fft, const uint64_t* glwe, uint64_t* glwe_out,
                                               uint64_t* ticket)
 {
-    if (!p || !glwe) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_MULTIPLY_GGSW_GLWE, ggsw_fft, glwe, nullptr, glwe_out, ticket);
+    return pool_submit(p, spf_ops::OP_MULTIPLY_GGSW_GLWE, {ggsw_fft, glwe}, glwe_out, ticket);
 }
 spf_status spf_pool_submit_glev_cmux(spf_pool* p, const double* sel_ggsw_fft, const uint64_t* a, const uint64_t* b, uint64_t* glev_out,
                                      uint64_t* ticket)
 {
-    if (!p || !a || !b) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit(p, spf_pool_impl::OP_GLEV_CMUX, sel_ggsw_fft, a, b, glev_out, ticket);
+    return pool_submit(p, spf_ops::OP_GLEV_CMUX, {sel_ggsw_fft, a, b}, glev_out, ticket);
 }
 spf_status spf_pool_submit_scheme_switch(spf_pool* p, const uint64_t* glev_in, double* ggsw_fft_out, uint64_t* ticket)
 {
-    return pool_submit(p, spf_pool_impl::OP_SCHEME_SWITCH, glev_in, nullptr, nullptr, ggsw_fft_out, ticket);
+    return pool_submit(p, spf_ops::OP_SCHEME_SWITCH, {glev_in}, ggsw_fft_out, ticket);
 }
 
 spf_status spf_pool_wait(spf_pool* p, uint64_t ticket)
@@ -2416,39 +2411,6 @@ spf_status spf_pool_stats(spf_pool* p, uint64_t* ops, uint64_t* launches)
 // ---------------------------------------------------------------- values: device-resident operands of the per-operation boundary
 namespace {
 
-size_t value_bytes(const spf_params& p, int kind)
-{
-    const size_t k = p.glwe_size, N = p.polynomial_degree, l = p.cbs_radix_count;
-    switch (kind) {
-    case SPF_VAL_LWE0: return ((size_t)p.lwe_dimension + 1) * 8;
-    case SPF_VAL_LWE1: return (k * N + 1) * 8;
-    case SPF_VAL_GLWE1: return (k + 1) * N * 8;
-    case SPF_VAL_GGSW1: return (k + 1) * l * (k + 1) * (N / 2) * 16;
-    case SPF_VAL_GLEV1: return l * (k + 1) * N * 8;
-    default: return 0;
-    }
-}
-
-// operand kinds and result kind of a pool operation (the `FheOp` arms of circuit_processor/mod.rs:255-540)
-struct PoolOpInfo { int arity; int in_kind[3]; int out_kind; };
-bool pool_op_info(int op, PoolOpInfo* o)
-{
-    using namespace spf_pool_impl;
-    switch (op) {
-    case OP_KEYSWITCH: *o = {1, {SPF_VAL_LWE1, -1, -1}, SPF_VAL_LWE0}; return true;
-    case OP_CBS: *o = {1, {SPF_VAL_LWE0, -1, -1}, SPF_VAL_GGSW1}; return true;
-    case OP_GATE_CBS: *o = {1, {SPF_VAL_LWE1, -1, -1}, SPF_VAL_GGSW1}; return true;
-    case OP_CMUX: *o = {3, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1}; return true;
-    case OP_SAMPLE_EXTRACT: *o = {1, {SPF_VAL_GLWE1, -1, -1}, SPF_VAL_LWE1}; return true;
-    case OP_NOT: case OP_MUL_XN: *o = {1, {SPF_VAL_GLWE1, -1, -1}, SPF_VAL_GLWE1}; return true;
-    case OP_GLWE_ADD: *o = {2, {SPF_VAL_GLWE1, SPF_VAL_GLWE1, -1}, SPF_VAL_GLWE1}; return true;
-    case OP_MULTIPLY_GGSW_GLWE: *o = {2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, -1}, SPF_VAL_GLWE1}; return true;
-    case OP_GLEV_CMUX: *o = {3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1}; return true;
-    case OP_SCHEME_SWITCH: *o = {1, {SPF_VAL_GLEV1, -1, -1}, SPF_VAL_GGSW1}; return true;
-    default: return false;
-    }
-}
-
 // the pool of one context that a value of `member` belongs to: the pool itself, or — a group pool — that member's pool
 // (member < 0: the calling thread's home member, dealt as for the host-pointer submits)
 spf_pool* value_pool(spf_pool* top, int member, int* which)
@@ -2461,12 +2423,17 @@ spf_pool* value_pool(spf_pool* top, int member, int* which)
     return top->members[member];
 }
 
+// a submit by handle: the checks of every `_v` wrapper below.  `explain`: a refused parameter leaves its reason in the context's
+// last error (spf_pool_submit_op_v) instead of a bare status (the named wrappers).
 spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, size_t n_vals, uint64_t param, spf_value** out,
-                         uint64_t* ticket)
+                         uint64_t* ticket, bool explain = false)
 {
-    if (!top || !out || !vals) return SPF_ERR_INVALID_ARGUMENT; // (ticket may be null: nobody will wait for this operation itself)
-    PoolOpInfo info{};
-    if (!pool_op_info(op, &info) || n_vals != (size_t)info.arity) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: wrong number of operands");
+    if (!top) return SPF_ERR_INVALID_ARGUMENT;
+    const char* why = nullptr;
+    if (spf_ops::op_param(top->prm, op, &param, &why) != SPF_OK) return explain ? fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, why) : SPF_ERR_INVALID_ARGUMENT;
+    if (!out || !vals) return SPF_ERR_INVALID_ARGUMENT; // (ticket may be null: nobody will wait for this operation itself)
+    const spf_ops::OpRow& info = spf_ops::row(op);
+    if (n_vals != (size_t)info.arity) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: wrong number of operands");
     spf_value* v[3] = {nullptr, nullptr, nullptr};
     for (int k = 0; k < info.arity; k++) {
         v[k] = const_cast<spf_value*>(vals[k]);
@@ -2483,7 +2450,7 @@ spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, si
     if (!mine) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
     spf_value* res = spf_value::make(leaf->arena, leaf, member, info.out_kind, value_bytes(leaf->prm, info.out_kind));
     if (!res) return fail(leaf->ctx, SPF_ERR_HIP, "out of host memory");
-    const spf_status st = leaf->submit_v(op, v, res, ticket, param);
+    const spf_status st = leaf->submit_impl(op, true, nullptr, nullptr, v, res, ticket, param);
     if (st != SPF_OK) {
         res->release();
         return st == SPF_ERR_INVALID_ARGUMENT ? fail(top->ctx, st, "pool operation by handle: refused (pool closing, or an operand's producing operation failed)") : st;
@@ -2491,6 +2458,10 @@ spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, si
     if (leaf != top && ticket) *ticket |= (uint64_t)member << spf_pool::kMemberShift;
     *out = res;
     return SPF_OK;
+}
+spf_status pool_submit_v(spf_pool* top, int op, std::initializer_list<const spf_value*> vals, uint64_t param, spf_value** out, uint64_t* ticket)
+{
+    return pool_submit_v(top, op, vals.begin(), vals.size(), param, out, ticket);
 }
 
 } // namespace
@@ -2791,56 +2762,50 @@ spf_status spf_pool_counters_get(spf_pool* p, spf_pool_counters* out)
 // ---- the pool's submits by handle
 spf_status spf_pool_submit_keyswitch_v(spf_pool* p, const spf_value* lwe1, spf_value** lwe0_out, uint64_t* ticket)
 {
-    return pool_submit_v(p, spf_pool_impl::OP_KEYSWITCH, &lwe1, 1, 0, lwe0_out, ticket);
+    return pool_submit_v(p, spf_ops::OP_KEYSWITCH, {lwe1}, 0, lwe0_out, ticket);
 }
 spf_status spf_pool_submit_circuit_bootstrap_v(spf_pool* p, const spf_value* lwe0, spf_value** ggsw_out, uint64_t* ticket)
 {
-    return pool_submit_v(p, spf_pool_impl::OP_CBS, &lwe0, 1, 0, ggsw_out, ticket);
+    return pool_submit_v(p, spf_ops::OP_CBS, {lwe0}, 0, ggsw_out, ticket);
 }
 spf_status spf_pool_submit_keyswitch_circuit_bootstrap_v(spf_pool* p, const spf_value* lwe1, spf_value** ggsw_out, uint64_t* ticket)
 {
-    return pool_submit_v(p, spf_pool_impl::OP_GATE_CBS, &lwe1, 1, 0, ggsw_out, ticket);
+    return pool_submit_v(p, spf_ops::OP_GATE_CBS, {lwe1}, 0, ggsw_out, ticket);
 }
 spf_status spf_pool_submit_cmux_v(spf_pool* p, const spf_value* sel, const spf_value* a, const spf_value* b, spf_value** out,
                                   uint64_t* ticket)
 {
-    const spf_value* v[3] = {sel, a, b};
-    return pool_submit_v(p, spf_pool_impl::OP_CMUX, v, 3, 0, out, ticket);
+    return pool_submit_v(p, spf_ops::OP_CMUX, {sel, a, b}, 0, out, ticket);
 }
 spf_status spf_pool_submit_sample_extract_v(spf_pool* p, const spf_value* glwe, size_t idx, spf_value** lwe1_out, uint64_t* ticket)
 {
-    if (!p || idx >= p->prm.polynomial_degree) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit_v(p, spf_pool_impl::OP_SAMPLE_EXTRACT, &glwe, 1, idx, lwe1_out, ticket);
+    return pool_submit_v(p, spf_ops::OP_SAMPLE_EXTRACT, {glwe}, idx, lwe1_out, ticket);
 }
 spf_status spf_pool_submit_not_v(spf_pool* p, const spf_value* glwe, spf_value** out, uint64_t* ticket)
 {
-    return pool_submit_v(p, spf_pool_impl::OP_NOT, &glwe, 1, 0, out, ticket);
+    return pool_submit_v(p, spf_ops::OP_NOT, {glwe}, 0, out, ticket);
 }
 spf_status spf_pool_submit_glwe_add_v(spf_pool* p, const spf_value* a, const spf_value* b, spf_value** out, uint64_t* ticket)
 {
-    const spf_value* v[2] = {a, b};
-    return pool_submit_v(p, spf_pool_impl::OP_GLWE_ADD, v, 2, 0, out, ticket);
+    return pool_submit_v(p, spf_ops::OP_GLWE_ADD, {a, b}, 0, out, ticket);
 }
 spf_status spf_pool_submit_mul_xn_v(spf_pool* p, const spf_value* glwe, size_t n, spf_value** out, uint64_t* ticket)
 {
-    if (!p) return SPF_ERR_INVALID_ARGUMENT;
-    return pool_submit_v(p, spf_pool_impl::OP_MUL_XN, &glwe, 1, n % (2 * (size_t)p->prm.polynomial_degree), out, ticket);
+    return pool_submit_v(p, spf_ops::OP_MUL_XN, {glwe}, n, out, ticket);
 }
 spf_status spf_pool_submit_multiply_ggsw_glwe_v(spf_pool* p, const spf_value* ggsw, const spf_value* glwe, spf_value** out,
                                                 uint64_t* ticket)
 {
-    const spf_value* v[2] = {ggsw, glwe};
-    return pool_submit_v(p, spf_pool_impl::OP_MULTIPLY_GGSW_GLWE, v, 2, 0, out, ticket);
+    return pool_submit_v(p, spf_ops::OP_MULTIPLY_GGSW_GLWE, {ggsw, glwe}, 0, out, ticket);
 }
 spf_status spf_pool_submit_glev_cmux_v(spf_pool* p, const spf_value* sel, const spf_value* a, const spf_value* b, spf_value** out,
                                        uint64_t* ticket)
 {
-    const spf_value* v[3] = {sel, a, b};
-    return pool_submit_v(p, spf_pool_impl::OP_GLEV_CMUX, v, 3, 0, out, ticket);
+    return pool_submit_v(p, spf_ops::OP_GLEV_CMUX, {sel, a, b}, 0, out, ticket);
 }
 spf_status spf_pool_submit_scheme_switch_v(spf_pool* p, const spf_value* glev, spf_value** ggsw_out, uint64_t* ticket)
 {
-    return pool_submit_v(p, spf_pool_impl::OP_SCHEME_SWITCH, &glev, 1, 0, ggsw_out, ticket);
+    return pool_submit_v(p, spf_ops::OP_SCHEME_SWITCH, {glev}, 0, ggsw_out, ticket);
 }
 
 // one entry for `exec_op`'s whole match (circuit_processor/mod.rs:255-540): the operation as a spf_graph_op, operands in the
@@ -2848,26 +2813,10 @@ spf_status spf_pool_submit_scheme_switch_v(spf_pool* p, const spf_value* glev, s
 spf_status spf_pool_submit_op_v(spf_pool* p, spf_graph_op op, const spf_value* const* inputs, size_t n_inputs, uint64_t param,
                                 spf_value** out, uint64_t* ticket)
 {
-    using namespace spf_pool_impl;
     if (!p) return SPF_ERR_INVALID_ARGUMENT;
-    int pop;
-    switch (op) {
-    case SPF_OP_SAMPLE_EXTRACT:
-        if (param >= p->prm.polynomial_degree) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "sample_extract index >= polynomial_degree");
-        pop = OP_SAMPLE_EXTRACT;
-        break;
-    case SPF_OP_KEYSWITCH_L1_TO_L0: pop = OP_KEYSWITCH; param = 0; break;
-    case SPF_OP_NOT: pop = OP_NOT; param = 0; break;
-    case SPF_OP_GLWE_ADD: pop = OP_GLWE_ADD; param = 0; break;
-    case SPF_OP_CMUX: pop = OP_CMUX; param = 0; break;
-    case SPF_OP_GLEV_CMUX: pop = OP_GLEV_CMUX; param = 0; break;
-    case SPF_OP_MULTIPLY_GGSW_GLWE: pop = OP_MULTIPLY_GGSW_GLWE; param = 0; break;
-    case SPF_OP_CIRCUIT_BOOTSTRAP: pop = OP_CBS; param = 0; break;
-    case SPF_OP_SCHEME_SWITCH: pop = OP_SCHEME_SWITCH; param = 0; break;
-    case SPF_OP_MUL_XN: pop = OP_MUL_XN; param %= 2 * (uint64_t)p->prm.polynomial_degree; break;
-    default: return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "unknown operation");
-    }
-    return pool_submit_v(p, pop, inputs, n_inputs, param, out, ticket);
+    const int pop = spf_ops::pool_op_of(op);
+    if (pop == spf_ops::kNone) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "unknown operation");
+    return pool_submit_v(p, pop, inputs, n_inputs, param, out, ticket, true);
 }
 
 } // extern "C"

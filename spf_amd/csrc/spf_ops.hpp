@@ -1,0 +1,184 @@
+// spf_ops.hpp — the host-side facts about ciphertext kinds and operations, stated once.
+//
+// The library runs the ten `FheOp` kinds of `CircuitProcessor::exec_op` (circuit_processor/mod.rs:255-540) through the gate graph,
+// the pool by host pointer, the pool by handle and the device group.  Everything those routes have to agree on lives here:
+//   * the size of a ciphertext of each spf_value_kind (value_words / value_bytes over the four word helpers);
+//   * ONE table row per operation: the spf_graph_op it answers to, arity, operand kinds, result kind, the scheduling flags and
+//     the rule for its parameter — an operation is DECLARED by adding its row (and its arm in launch_op);
+//   * the parameter rule as a function (op_param);
+//   * the dispatcher from an operation over contiguous operand rows to the `_dev` / `pool_*` launchers (launch_op).
+// Host only.  Included by spf_hip.hip behind `Scratch`, `spf_ctx` and `fail`, ahead of spf_values.hpp / spf_pool.hpp.
+#pragma once
+#include "../../include/spf_hip.h"
+
+#include <cstddef>
+#include <cstdint>
+
+// ---------------------------------------------------------------- sizes (the only formulas)
+inline size_t lwe0_words(const spf_params& p) { return (size_t)p.lwe_dimension + 1; }
+inline size_t lwe1_words(const spf_params& p) { return (size_t)p.glwe_size * p.polynomial_degree + 1; }
+inline size_t glwe_words(const spf_params& p) { return (size_t)(p.glwe_size + 1) * p.polynomial_degree; }
+inline size_t ggsw_fft_complex(const spf_params& p, uint32_t count)
+{
+    return (size_t)(p.glwe_size + 1) * count * (p.glwe_size + 1) * (p.polynomial_degree / 2);
+}
+
+// 64-bit words of one ciphertext of `kind` as it lies in memory (a complex f64 of a GGSW spectrum is two); 0 = unknown kind
+inline size_t value_words(const spf_params& p, int kind)
+{
+    switch (kind) {
+    case SPF_VAL_LWE0: return lwe0_words(p);
+    case SPF_VAL_LWE1: return lwe1_words(p);
+    case SPF_VAL_GLWE1: return glwe_words(p);
+    case SPF_VAL_GGSW1: return 2 * ggsw_fft_complex(p, p.cbs_radix_count);
+    case SPF_VAL_GLEV1: return (size_t)p.cbs_radix_count * glwe_words(p);
+    default: return 0;
+    }
+}
+inline size_t value_bytes(const spf_params& p, int kind) { return 8 * value_words(p, kind); }
+
+// ---------------------------------------------------------------- the operation table
+namespace spf_ops {
+
+// The pool's numbering: one kind per `FheOp` that `exec_op` hands to `Evaluation`, plus the KeyswitchL1toL0 -> CircuitBootstrap
+// chain.  The pool's lanes, the SPF_POOL_TRACE lines and tools/pool_trace_phases.py carry these numbers.
+enum Op {
+    OP_KEYSWITCH = 0, OP_CBS = 1, OP_CMUX = 2, OP_GATE_CBS = 3,
+    OP_SAMPLE_EXTRACT = 4, OP_NOT = 5, OP_GLWE_ADD = 6, OP_MUL_XN = 7, OP_MULTIPLY_GGSW_GLWE = 8, OP_GLEV_CMUX = 9, OP_SCHEME_SWITCH = 10,
+    N_OPS = 11
+};
+
+enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N };
+constexpr int kNone = -1; // no spf_graph_op / no operand in this slot
+
+struct OpRow {
+    int op;           // its own index (checked below: the rows stand in the enum's order)
+    int graph_op;     // the spf_graph_op it answers to, or kNone
+    int arity;
+    int in_kind[3];   // spf_value_kind per operand, in the order spf_graph_add_op takes them; kNone beyond the arity
+    int out_kind;
+    bool cmux_family; // read scattered operands in place through a pointer table (spf_cmux_scattered_dev)
+    bool heavy;       // milliseconds on the GPU: caller groups, pacing and the "previous batch still out" rule apply (spf_pool.hpp)
+    ParamRule param;
+};
+
+constexpr OpRow kOps[N_OPS] = {
+    {OP_KEYSWITCH, SPF_OP_KEYSWITCH_L1_TO_L0, 1, {SPF_VAL_LWE1, kNone, kNone}, SPF_VAL_LWE0, false, false, PARAM_NONE},
+    {OP_CBS, SPF_OP_CIRCUIT_BOOTSTRAP, 1, {SPF_VAL_LWE0, kNone, kNone}, SPF_VAL_GGSW1, false, true, PARAM_NONE},
+    {OP_CMUX, SPF_OP_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1, true, false, PARAM_NONE},
+    {OP_GATE_CBS, kNone, 1, {SPF_VAL_LWE1, kNone, kNone}, SPF_VAL_GGSW1, false, true, PARAM_NONE},
+    {OP_SAMPLE_EXTRACT, SPF_OP_SAMPLE_EXTRACT, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_LWE1, false, false, PARAM_INDEX_BELOW_N},
+    {OP_NOT, SPF_OP_NOT, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_GLWE1, false, false, PARAM_NONE},
+    {OP_GLWE_ADD, SPF_OP_GLWE_ADD, 2, {SPF_VAL_GLWE1, SPF_VAL_GLWE1, kNone}, SPF_VAL_GLWE1, false, false, PARAM_NONE},
+    {OP_MUL_XN, SPF_OP_MUL_XN, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_GLWE1, false, false, PARAM_AMOUNT_MOD_2N},
+    {OP_MULTIPLY_GGSW_GLWE, SPF_OP_MULTIPLY_GGSW_GLWE, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, kNone}, SPF_VAL_GLWE1, true, false, PARAM_NONE},
+    {OP_GLEV_CMUX, SPF_OP_GLEV_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1, true, false, PARAM_NONE},
+    {OP_SCHEME_SWITCH, SPF_OP_SCHEME_SWITCH, 1, {SPF_VAL_GLEV1, kNone, kNone}, SPF_VAL_GGSW1, false, false, PARAM_NONE},
+};
+
+constexpr const OpRow& row(int op) { return kOps[op]; } // op: a valid pool operation
+constexpr bool heavy(int op) { return kOps[op].heavy; }
+constexpr bool cmux_family(int op) { return kOps[op].cmux_family; }
+// the pool operation a spf_graph_op stands for; kNone for a value that is none of the ten
+constexpr int pool_op_of(int graph_op)
+{
+    for (int op = 0; op < N_OPS; op++)
+        if (graph_op != kNone && kOps[op].graph_op == graph_op) return op;
+    return kNone;
+}
+
+inline void in_out_bytes(const spf_params& p, int op, size_t (&in)[3], size_t& out)
+{
+    for (int k = 0; k < 3; k++) in[k] = value_bytes(p, kOps[op].in_kind[k]); // (kNone: 0 bytes)
+    out = value_bytes(p, kOps[op].out_kind);
+}
+
+// The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN
+// amount is reduced mod 2N, every other operation's parameter is 0 whatever the caller passed.
+inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const char** why)
+{
+    switch (kOps[op].param) {
+    case PARAM_INDEX_BELOW_N:
+        if (*param < p.polynomial_degree) return SPF_OK;
+        *why = "sample_extract index >= polynomial_degree";
+        return SPF_ERR_INVALID_ARGUMENT;
+    case PARAM_AMOUNT_MOD_2N: *param %= 2 * (uint64_t)p.polynomial_degree; return SPF_OK;
+    default: *param = 0; return SPF_OK;
+    }
+}
+
+namespace check {
+constexpr bool is_kind(int k) { return k >= SPF_VAL_LWE0 && k <= SPF_VAL_GLEV1; }
+constexpr bool row_ok(const OpRow& r, int index)
+{
+    if (r.op != index || r.arity < 1 || r.arity > 3 || !is_kind(r.out_kind)) return false;
+    for (int k = 0; k < 3; k++)
+        if (k < r.arity ? !is_kind(r.in_kind[k]) : r.in_kind[k] != kNone) return false;
+    return true;
+}
+constexpr bool rows_ok()
+{
+    for (int op = 0; op < N_OPS; op++)
+        if (!row_ok(kOps[op], op)) return false;
+    return true;
+}
+constexpr bool graph_ops_ok() // the ten public values name ten rows (distinct: each row names its value back), OP_GATE_CBS alone has none
+{
+    for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_MUL_XN; g++)
+        if (pool_op_of(g) == kNone) return false;
+    for (int op = 0; op < N_OPS; op++) {
+        const int g = kOps[op].graph_op;
+        if (op == OP_GATE_CBS ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_MUL_XN || pool_op_of(g) != op)) return false;
+    }
+    return true;
+}
+static_assert(rows_ok(), "a row is out of the enum's order, or its arity and its operand kinds disagree, or a kind is no spf_value_kind");
+static_assert(graph_ops_ok(), "every spf_graph_op needs exactly one row, and only OP_GATE_CBS goes without a spf_graph_op");
+} // namespace check
+
+} // namespace spf_ops
+
+// ---------------------------------------------------------------- the dispatcher
+// (defined further down in spf_hip.hip: a batch of a pool's staging set, on the set's stream and intermediates)
+static spf_status pool_keyswitch(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_in, uint64_t* d_out, Scratch* sc);
+static spf_status pool_circuit_bootstrap(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_lwe, double* d_ggsw, Scratch* sc,
+                                         int per_wg_hint);
+
+namespace spf_ops {
+
+// The kernels of B operations of one kind: operands in[0 .. arity) and `out` are contiguous device rows.  (The CMUX family over
+// SCATTERED operands — by handle on the tuned parameter sets, and in gate graphs — goes to spf_cmux_scattered_dev instead.)
+//   scr != null: a pool's batch — the staging set's intermediates, the population's workgroup shape (per_wg, launch_blind_rotate),
+//                no batch-limit check (a set never holds that many); d_mid = the set's level-0 row for OP_GATE_CBS;
+//   scr == null: a gate graph's level — the public `_dev` entry points on the context's own intermediates, with their checks.
+inline spf_status launch_op(spf_ctx* c, hipStream_t s, int op, size_t B, const void* const in[3], void* out, uint64_t param,
+                            Scratch* scr, int per_wg, void* d_mid)
+{
+    const auto u64 = [](const void* p) { return static_cast<const uint64_t*>(p); };
+    const auto f64 = [](const void* p) { return static_cast<const double*>(p); };
+    const auto keyswitch = [&](const void* lwe1, void* lwe0) {
+        return scr ? pool_keyswitch(c, s, B, u64(lwe1), (uint64_t*)lwe0, scr) : spf_keyswitch_lwe_l1_lwe_l0_dev(c, s, B, u64(lwe1), (uint64_t*)lwe0);
+    };
+    const auto bootstrap = [&](const void* lwe0, void* ggsw) {
+        return scr ? pool_circuit_bootstrap(c, s, B, u64(lwe0), (double*)ggsw, scr, per_wg) : spf_circuit_bootstrap_dev(c, s, B, u64(lwe0), (double*)ggsw);
+    };
+    switch (op) {
+    case OP_KEYSWITCH: return keyswitch(in[0], out);
+    case OP_CBS: return bootstrap(in[0], out);
+    case OP_GATE_CBS: { // FheOp::KeyswitchL1toL0 -> FheOp::CircuitBootstrap, the level-0 LWE stays in HBM
+        const spf_status st = keyswitch(in[0], d_mid);
+        return st == SPF_OK ? bootstrap(d_mid, out) : st;
+    }
+    case OP_CMUX: return spf_cmux_dev(c, s, B, f64(in[0]), u64(in[1]), u64(in[2]), (uint64_t*)out);
+    case OP_SAMPLE_EXTRACT: return spf_sample_extract_l1_dev(c, s, B, u64(in[0]), (size_t)param, (uint64_t*)out);
+    case OP_NOT: return spf_glwe_not_dev(c, s, B, u64(in[0]), (uint64_t*)out);
+    case OP_GLWE_ADD: return spf_glwe_xor_dev(c, s, B, u64(in[0]), u64(in[1]), (uint64_t*)out);
+    case OP_MUL_XN: return spf_glwe_mul_xn_dev(c, s, B, u64(in[0]), (size_t)param, (uint64_t*)out);
+    case OP_MULTIPLY_GGSW_GLWE: return spf_multiply_glwe_ggsw_dev(c, s, B, u64(in[1]), f64(in[0]), (uint64_t*)out);
+    case OP_GLEV_CMUX: return spf_glev_cmux_dev(c, s, B, f64(in[0]), u64(in[1]), u64(in[2]), (uint64_t*)out);
+    case OP_SCHEME_SWITCH: return spf_scheme_switch_dev(c, s, B, u64(in[0]), (double*)out);
+    default: return fail(c, SPF_ERR_INVALID_ARGUMENT, "unknown graph operation");
+    }
+}
+
+} // namespace spf_ops

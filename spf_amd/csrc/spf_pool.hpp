@@ -75,17 +75,9 @@
 
 namespace spf_pool_impl {
 
-// one kind per `FheOp` that `CircuitProcessor::exec_op` hands to `Evaluation` (circuit_processor/mod.rs:329-540), plus the
-// KeyswitchL1toL0 -> CircuitBootstrap chain
-enum Op {
-    OP_KEYSWITCH = 0, OP_CBS = 1, OP_CMUX = 2, OP_GATE_CBS = 3,
-    OP_SAMPLE_EXTRACT = 4, OP_NOT = 5, OP_GLWE_ADD = 6, OP_MUL_XN = 7, OP_MULTIPLY_GGSW_GLWE = 8, OP_GLEV_CMUX = 9, OP_SCHEME_SWITCH = 10,
-    N_OPS = 11
-};
-// the kinds whose batches are worth keeping resident side by side (milliseconds on the GPU): caller groups, pacing and the
-// "previous batch still out" rule apply to these; everything else is microseconds per launch
-inline bool heavy(int op) { return op == OP_CBS || op == OP_GATE_CBS; }
-inline bool cmux_family(int op) { return op == OP_CMUX || op == OP_GLEV_CMUX || op == OP_MULTIPLY_GGSW_GLWE; }
+// the operation kinds (OP_*, N_OPS) and what the pool asks about them — heavy(op): batches worth keeping resident side by side
+// (milliseconds on the GPU; everything else is microseconds per launch); cmux_family(op) — are rows of the table in spf_ops.hpp
+using namespace spf_ops;
 constexpr int kMaxGroups = 4;     // caller groups per operation kind: that many batches of a kind resident on the GPU at once
 constexpr int kSets = 4 * kMaxGroups; // per group one batch in flight / being collected and one filling; by handle up to split + 2 bootstrap batches
                                       // resident beside the cheap kinds' batches
@@ -376,42 +368,17 @@ struct spf_pool {
     hipStream_t stream_of(const Batch& b) const { return table_batch(b) ? s_def : sets[b.set].sk; }
     std::chrono::milliseconds grace{200}; // after this long an uncollected output is delivered by the launcher
     std::vector<uintptr_t> last_members[kLanes]; // threads of the most recently finished batch of a lane, sorted
-    size_t cap_hint[kKinds] = {64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64, 64}; // slots of the next batch of a kind: doubles whenever a batch fills up
+    size_t cap_hint[kKinds];                                  // slots of the next batch of a kind (64 to begin with): doubles whenever a batch fills up
                                                               // (pinned staging is sized by what the callers actually produce:
                                                               // 2048 slots of 256 KiB would pin 0.5 GiB per set up front)
     bool preparing[kLanes] = {}; // a submitter is allocating a set for this lane (lock dropped)
     int outstanding[kLanes] = {}; // closed batches of the lane that have not completed yet
 
-    size_t lwe0_bytes() const { return ((size_t)prm.lwe_dimension + 1) * 8; }
-    size_t lwe1_bytes() const { return ((size_t)prm.glwe_size * prm.polynomial_degree + 1) * 8; }
-    size_t glwe_bytes() const { return (size_t)(prm.glwe_size + 1) * prm.polynomial_degree * 8; }
-    size_t ggsw_bytes() const
-    {
-        return (size_t)(prm.glwe_size + 1) * prm.cbs_radix_count * (prm.glwe_size + 1) * (prm.polynomial_degree / 2) * 16;
-    }
-
-    void in_out_sizes(int op, size_t (&in)[3], size_t& out) const
-    {
-        using namespace spf_pool_impl;
-        in[0] = in[1] = in[2] = 0;
-        const size_t glev = glwe_bytes() * prm.cbs_radix_count;
-        switch (op) {
-        case OP_KEYSWITCH: in[0] = lwe1_bytes(); out = lwe0_bytes(); break;
-        case OP_CBS: in[0] = lwe0_bytes(); out = ggsw_bytes(); break;
-        case OP_GATE_CBS: in[0] = lwe1_bytes(); out = ggsw_bytes(); break;
-        case OP_SAMPLE_EXTRACT: in[0] = glwe_bytes(); out = lwe1_bytes(); break;
-        case OP_NOT: case OP_MUL_XN: in[0] = glwe_bytes(); out = glwe_bytes(); break;
-        case OP_GLWE_ADD: in[0] = in[1] = glwe_bytes(); out = glwe_bytes(); break;
-        case OP_MULTIPLY_GGSW_GLWE: in[0] = ggsw_bytes(); in[1] = glwe_bytes(); out = glwe_bytes(); break;
-        case OP_GLEV_CMUX: in[0] = ggsw_bytes(); in[1] = in[2] = glev; out = glev; break;
-        case OP_SCHEME_SWITCH: in[0] = glev; out = ggsw_bytes(); break;
-        default: in[0] = ggsw_bytes(); in[1] = glwe_bytes(); in[2] = glwe_bytes(); out = glwe_bytes(); break; // OP_CMUX
-        }
-    }
+    spf_pool() { std::fill(cap_hint, cap_hint + kKinds, (size_t)64); }
     size_t batch_cap(int op) const
     {
         size_t in[3], out;
-        in_out_sizes(op, in, out);
+        spf_ops::in_out_bytes(prm, op, in, out);
         const size_t big = std::max(std::max(in[0], in[1]), std::max(in[2], out));
         return std::max<size_t>(1, std::min(max_batch, spf_pool_impl::kMaxStagingBytes / big));
     }
@@ -449,7 +416,7 @@ struct spf_pool {
     bool prepare_set(spf_pool_impl::Staging& s, int op, size_t cap, bool by_handle, bool table_set = false)
     {
         size_t in[3], out;
-        in_out_sizes(op, in, out);
+        spf_ops::in_out_bytes(prm, op, in, out);
         if (hipSetDevice(ctx->device) != hipSuccess) return false;
         for (int k = 0; k < 3; k++) {
             if (!in[k]) continue;
@@ -467,7 +434,7 @@ struct spf_pool {
             if (!grow_dev(s.d_out, s.dcap_out, cap * out)) return false;
             if (!grow_host(s.h_out, s.cap_out, cap * out)) return false;
         }
-        if (op == spf_pool_impl::OP_GATE_CBS && !grow_dev(s.d_mid, s.cap_mid, cap * lwe0_bytes())) return false;
+        if (op == spf_pool_impl::OP_GATE_CBS && !grow_dev(s.d_mid, s.cap_mid, cap * value_bytes(prm, SPF_VAL_LWE0))) return false;
         if ((op == spf_pool_impl::OP_KEYSWITCH || op == spf_pool_impl::OP_CBS || op == spf_pool_impl::OP_GATE_CBS) && s.scr_cap < cap) {
             // (both: a staging set serves any kind later; a table set only ever sees the keyswitch — no 160 KB of circuit-bootstrap
             // intermediates per slot for it)
@@ -500,7 +467,7 @@ struct spf_pool {
     void deliver(const Batch& b, size_t slot) const
     {
         size_t in[3], out;
-        in_out_sizes(b.op, in, out);
+        spf_ops::in_out_bytes(prm, b.op, in, out);
         std::memcpy(b.slots[slot].out, static_cast<const uint8_t*>(sets[b.set].h_out) + slot * out, out);
     }
     // called with `mu` held when a ticket of `b` has been collected (or delivered on its owner's behalf)
@@ -530,19 +497,9 @@ struct spf_pool {
         if (launcher_asleep.load(std::memory_order_acquire)) cv_work.notify_all();
     }
 
-    spf_status submit(int op, const void* a, const void* b_in, const void* c, void* out, uint64_t* ticket, uint64_t param = 0)
-    {
-        if (!a || !out || !ticket) return SPF_ERR_INVALID_ARGUMENT;
-        const void* src[3] = {a, b_in, c};
-        return submit_impl(op, false, src, out, nullptr, nullptr, ticket, param);
-    }
-    // by handle: `v` are values of this pool, valid or still pending (checked by the caller, pool_submit_v); *result is a new value
+    // One operation.  By host pointer: src[0 .. arity), `out` and `ticket` are not null (checked by the caller, pool_submit).  By
+    // handle: `vin` are values of this pool, valid or still pending (checked by the caller, pool_submit_v); `vout` is a new value
     // that becomes valid when its batch has run (spf_pool_wait for the ticket, or spf_value_wait); `ticket` may be null
-    spf_status submit_v(int op, spf_value* const* v, spf_value* result, uint64_t* ticket, uint64_t param = 0)
-    {
-        return submit_impl(op, true, nullptr, nullptr, v, result, ticket, param);
-    }
-
     spf_status submit_impl(int op, bool by_handle, const void* const* src, void* out, spf_value* const* vin, spf_value* vout,
                            uint64_t* ticket, uint64_t param)
     {
@@ -784,7 +741,7 @@ struct spf_pool {
         (void)registered;
         if (by_handle) return SPF_OK;
         size_t in[3], outsz;
-        in_out_sizes(op, in, outsz);
+        spf_ops::in_out_bytes(prm, op, in, outsz);
         const Staging& s = sets[b->set]; // (a set's buffers are stable while its batch is open)
         // the caller's own bytes, by the caller's own thread, straight into pinned memory
         for (int k = 0; k < 3; k++)
@@ -1067,36 +1024,7 @@ struct spf_pool {
     // the kernels of one batch: inputs d[0..2] (contiguous rows), output d_out, on the set's stream and intermediates
     spf_status run_kernels(const Batch& b, const spf_pool_impl::Staging& s, size_t B, void* const d[3], void* d_out)
     {
-        using namespace spf_pool_impl;
-        hipStream_t sk = stream_of(b);
-        Scratch* scr = const_cast<Scratch*>(&s.scr);
-        spf_status st;
-        switch (b.op) {
-        case OP_KEYSWITCH:
-            return pool_keyswitch(ctx, sk, B, (const uint64_t*)d[0], (uint64_t*)d_out, scr);
-        case OP_CBS:
-            return pool_circuit_bootstrap(ctx, sk, B, (const uint64_t*)d[0], (double*)d_out, scr, b.per_wg);
-        case OP_GATE_CBS: // FheOp::KeyswitchL1toL0 -> FheOp::CircuitBootstrap, the level-0 LWE stays in HBM
-            st = pool_keyswitch(ctx, sk, B, (const uint64_t*)d[0], (uint64_t*)s.d_mid, scr);
-            if (st == SPF_OK) st = pool_circuit_bootstrap(ctx, sk, B, (const uint64_t*)s.d_mid, (double*)d_out, scr, b.per_wg);
-            return st;
-        case OP_SAMPLE_EXTRACT:
-            return spf_sample_extract_l1_dev(ctx, sk, B, (const uint64_t*)d[0], (size_t)b.param, (uint64_t*)d_out);
-        case OP_NOT:
-            return spf_glwe_not_dev(ctx, sk, B, (const uint64_t*)d[0], (uint64_t*)d_out);
-        case OP_GLWE_ADD:
-            return spf_glwe_xor_dev(ctx, sk, B, (const uint64_t*)d[0], (const uint64_t*)d[1], (uint64_t*)d_out);
-        case OP_MUL_XN:
-            return spf_glwe_mul_xn_dev(ctx, sk, B, (const uint64_t*)d[0], (size_t)b.param, (uint64_t*)d_out);
-        case OP_MULTIPLY_GGSW_GLWE:
-            return spf_multiply_glwe_ggsw_dev(ctx, sk, B, (const uint64_t*)d[1], (const double*)d[0], (uint64_t*)d_out);
-        case OP_GLEV_CMUX:
-            return spf_glev_cmux_dev(ctx, sk, B, (const double*)d[0], (const uint64_t*)d[1], (const uint64_t*)d[2], (uint64_t*)d_out);
-        case OP_SCHEME_SWITCH:
-            return spf_scheme_switch_dev(ctx, sk, B, (const uint64_t*)d[0], (double*)d_out);
-        default:
-            return spf_cmux_dev(ctx, sk, B, (const double*)d[0], (const uint64_t*)d[1], (const uint64_t*)d[2], (uint64_t*)d_out);
-        }
+        return spf_ops::launch_op(ctx, stream_of(b), b.op, B, d, d_out, b.param, const_cast<Scratch*>(&s.scr), b.per_wg, s.d_mid);
     }
 
     // A batch by handle: no copies.  The outputs are one block of the arena; the operands are read where they are (CMUX family)
@@ -1105,7 +1033,7 @@ struct spf_pool {
     {
         using namespace spf_pool_impl;
         size_t in[3], out;
-        in_out_sizes(b.op, in, out);
+        spf_ops::in_out_bytes(prm, b.op, in, out);
         const Staging& s = staging_of(b);
         const size_t B = b.n;
         if (hipSetDevice(ctx->device) != hipSuccess) return SPF_ERR_HIP;
@@ -1121,7 +1049,7 @@ struct spf_pool {
         if (scattered_cmux(b.op)) {
             // units {selector, low (taken when the selector is 0; null = the zero ciphertext), high, out}; units of one selector next
             // to each other (neighbouring workgroups then hit the same 256 KiB in L2: spf_graph.hpp)
-            const size_t per = b.op == OP_GLEV_CMUX ? prm.cbs_radix_count : 1, gw = glwe_bytes();
+            const size_t per = b.op == OP_GLEV_CMUX ? prm.cbs_radix_count : 1, gw = value_bytes(prm, SPF_VAL_GLWE1);
             struct Unit { void* p[4]; };
             Unit* units = reinterpret_cast<Unit*>(s.h_ptrs);
             size_t n_units = 0;
@@ -1172,7 +1100,7 @@ struct spf_pool {
         using namespace spf_pool_impl;
         if (b.by_handle) return enqueue_v(b);
         size_t in[3], out;
-        in_out_sizes(b.op, in, out);
+        spf_ops::in_out_bytes(prm, b.op, in, out);
         const Staging& s = sets[b.set];
         const size_t B = b.n;
         if (hipSetDevice(ctx->device) != hipSuccess) return SPF_ERR_HIP;

@@ -557,3 +557,81 @@ def test_batch_upload_and_download_and_a_failing_batch(rig):
         gc.collect()
         pool.close()
         bare.close()
+
+
+def test_every_operation_by_its_named_submit_by_the_generic_submit_and_as_a_gate_graph():
+    """The ten `FheOp` kinds are declared once (spf_amd/csrc/spf_ops.hpp) and reached three ways: the named
+    `spf_pool_submit_<op>_v`, `spf_pool_submit_op_v`, and `spf_graph_add_op`.  Three operations of every kind through each of
+    the three, on the smallest generic parameter set of tests/test_gpu_generic.py (N = 16, k = 1): the three results are word-equal
+    to each other and to the oracle.  With a SampleExtract index of N - 1, a MulXN amount of 2N + 3 (= 3), and — through
+    spf_pool_submit_op_v — a non-zero `param` on every operation that takes none, which is ignored."""
+    from tests.test_gpu_generic import SMALL16, _eng_params
+    P = SMALL16.replace(tr_radix_log=6, tr_count=5, ss_radix_log=5, ss_count=6)
+    ks = O.gen_keyset(0x5EED0010, P)
+    r = O.Rng(0x7A16)
+    ak, ssk = O.gen_auto_key_fft(r, ks.glwe_sk, P), O.gen_ssk_fft(r, ks.glwe_sk, P)
+    eng = spf_amd.Engine(_eng_params(P))
+    eng.load_bootstrap_key(ks.bsk_fft)
+    eng.load_keyswitch_key(ks.ksk)
+    eng.load_automorphism_key(ak)
+    eng.load_scheme_switch_key(ssk)
+    n, N, k, L = 3, P.N, P.k, P.cbs_count
+    a, b = random_glwe(0x8100, n, P.glwe_len), random_glwe(0x8101, n, P.glwe_len)
+    lwe1, lwe0 = random_lwe_batch(0x8102, n, k * N), random_lwe_batch(0x8103, n, P.lwe_n)
+    ga, gb = random_glwe(0x8104, n * L, P.glwe_len).reshape(n, -1), random_glwe(0x8105, n * L, P.glwe_len).reshape(n, -1)
+    ggsw = np.stack([O.circuit_bootstrap(x, ks.bsk_fft, ak, ssk, P) for x in random_lwe_batch(0x8106, n, P.lwe_n)])
+    cmux = lambda lo, hi, g: O.cmux(lo, hi, g, N, k, P.cbs_radix_log, L)  # noqa: E731
+
+    def multiply(g, x):
+        fft = O.glwe_ggsw_mad(np.zeros(P.glwe_len // 2, dtype=np.complex128), x, g, N, k, P.cbs_radix_log, L)
+        return np.concatenate([O.poly_ifft(fft[q * (N // 2):(q + 1) * (N // 2)]) for q in range(k + 1)])
+
+    K = ValueKind
+    IGNORED = 0x1234   # handed to spf_pool_submit_op_v where the operation takes no parameter
+    # operation, suffix of its named submit, (kind, operands) per slot, parameter or None, result kind, oracle of operation i
+    cases = [
+        (FheOp.SampleExtract, "sample_extract", [(K.GLWE1, a)], N - 1, K.LWE1, lambda i: O.sample_extract(a[i], N - 1, N, k)),
+        (FheOp.KeyswitchL1toL0, "keyswitch", [(K.LWE1, lwe1)], None, K.LWE0,
+         lambda i: O.keyswitch_lwe(lwe1[i], ks.ksk, k * N, P.lwe_n, P.ks_radix_log, P.ks_count)),
+        (FheOp.Not, "not", [(K.GLWE1, a)], None, K.GLWE1, lambda i: O.glwe_not(a[i], N, k)),
+        (FheOp.GlweAdd, "glwe_add", [(K.GLWE1, a), (K.GLWE1, b)], None, K.GLWE1, lambda i: O.glwe_xor(a[i], b[i], N, k)),
+        (FheOp.CMux, "cmux", [(K.GGSW1, ggsw), (K.GLWE1, a), (K.GLWE1, b)], None, K.GLWE1, lambda i: cmux(a[i], b[i], ggsw[i])),
+        (FheOp.GlevCMux, "glev_cmux", [(K.GGSW1, ggsw), (K.GLEV1, ga), (K.GLEV1, gb)], None, K.GLEV1,
+         lambda i: np.concatenate([cmux(ga[i].reshape(L, -1)[j], gb[i].reshape(L, -1)[j], ggsw[i]) for j in range(L)])),
+        (FheOp.MultiplyGgswGlwe, "multiply_ggsw_glwe", [(K.GGSW1, ggsw), (K.GLWE1, a)], None, K.GLWE1, lambda i: multiply(ggsw[i], a[i])),
+        (FheOp.CircuitBootstrap, "circuit_bootstrap", [(K.LWE0, lwe0)], None, K.GGSW1,
+         lambda i: O.circuit_bootstrap(lwe0[i], ks.bsk_fft, ak, ssk, P)),
+        (FheOp.SchemeSwitch, "scheme_switch", [(K.GLEV1, ga)], None, K.GGSW1, lambda i: O.scheme_switch_fft(ga[i].reshape(L, -1), ssk, P)),
+        (FheOp.MulXN, "mul_xn", [(K.GLWE1, a)], 2 * N + 3, K.GLWE1, lambda i: O.glwe_mul_xn(a[i], 3, N, k)),
+    ]
+    assert sorted(c[0] for c in cases) == list(FheOp)
+    words = lambda x: np.ascontiguousarray(x).view(np.uint64).reshape(-1)  # noqa: E731
+    pool = spf_amd.Pool(eng, max_batch=16, max_wait_us=200)
+    try:
+        for op, name, operands, param, out_kind, oracle in cases:
+            want = [words(oracle(i)) for i in range(n)]
+            vals = [[pool.upload(kind, rows[i]) for kind, rows in operands] for i in range(n)]
+            named_fn = getattr(pool._lib, f"spf_pool_submit_{name}_v")
+            named, generic = [], []
+            for i in range(n):
+                h, t = C.c_void_p(), C.c_uint64()
+                handles = [v._h for v in vals[i]]
+                args = [pool._h] + handles + ([param] if param is not None else []) + [C.byref(h), C.byref(t)]
+                pool._ck(named_fn(*args), named_fn.__name__)
+                named.append((spf_amd._ffi.Value(pool, h), t.value))
+                generic.append(pool.submit_v(op, vals[i], IGNORED if param is None else param))
+            g = spf_amd.FheCircuit(eng)
+            outs = [g.add_output(g.add_op(op, [g.add_input(kind, rows[i]) for kind, rows in operands], param or 0), out_kind)
+                    for i in range(n)]
+            g.run()
+            g.close()
+            for i in range(n):
+                for route, (v, t) in (("named", named[i]), ("spf_pool_submit_op_v", generic[i])):
+                    pool.wait(t)
+                    assert v.info()["kind"] == int(out_kind), (op.name, route)
+                    assert np.array_equal(words(v.download()), want[i]), (op.name, route, i)
+                assert np.array_equal(words(outs[i]), want[i]), (op.name, "graph", i)
+    finally:
+        import gc
+        gc.collect()
+        pool.close()

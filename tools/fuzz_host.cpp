@@ -8,7 +8,9 @@
 // spf_load_compute_key_bincode's and spf_load_compute_key_nonfft_bincode's size walks (ComputeKey, ComputeKeyNonFft), spf_generate_lut, params_supported / params_generic, and
 // spf_graph_add_{input,trivial,op,output} (the reference validates per task, task.rs:26-31) — every call must return a status,
 // never crash, never touch memory outside its buffers (every destination is an exact-size heap allocation).  Before the random
-// cases, a fixed table calls every spf_*_batch entry point with one bad argument each (batch_forms_refuse_bad_arguments).
+// cases, a fixed table calls every spf_*_batch entry point with one bad argument each (batch_forms_refuse_bad_arguments) and
+// holds spf_graph_add_op and spf_ciphertext_words to the header's own statement of the ten operations and the four wire
+// sizes (graph_ops_match_the_header, wire_sizes_match_the_header).
 // Seeds: the reference's own malformed vector (parasol_runtime/src/safe_bincode.rs:58-66, :105-117) and valid serializations.
 //
 // usage: fuzz_host <cases> [seed]
@@ -138,6 +140,106 @@ bool batch_forms_refuse_bad_arguments(spf_ctx* c)
     return ok;
 }
 
+// The ten computing `FheOp` arms as include/spf_hip.h documents them ("Operand order per operation", the gate graphs' comment):
+// operation, operand kinds in order, result kind.  Written out here on purpose — NOT read from the library's table (spf_ops.hpp),
+// which is what it checks.
+struct HeaderOp { spf_graph_op op; int arity; spf_value_kind in[3]; spf_value_kind out; };
+const HeaderOp kHeaderOps[10] = {
+    {SPF_OP_SAMPLE_EXTRACT, 1, {SPF_VAL_GLWE1}, SPF_VAL_LWE1},
+    {SPF_OP_KEYSWITCH_L1_TO_L0, 1, {SPF_VAL_LWE1}, SPF_VAL_LWE0},
+    {SPF_OP_CIRCUIT_BOOTSTRAP, 1, {SPF_VAL_LWE0}, SPF_VAL_GGSW1},
+    {SPF_OP_SCHEME_SWITCH, 1, {SPF_VAL_GLEV1}, SPF_VAL_GGSW1},
+    {SPF_OP_NOT, 1, {SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+    {SPF_OP_GLWE_ADD, 2, {SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+    {SPF_OP_MUL_XN, 1, {SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+    {SPF_OP_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+    {SPF_OP_GLEV_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1},
+    {SPF_OP_MULTIPLY_GGSW_GLWE, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+};
+const HeaderOp* header_op(int op)
+{
+    for (const HeaderOp& h : kHeaderOps)
+        if (h.op == op) return &h;
+    return nullptr;
+}
+
+// spf_graph_add_op against kHeaderOps, for every operation: the right operand kinds are accepted and give a node of the stated
+// result kind (which spf_graph_add_output takes); a wrong kind in any one slot, one operand too few and one too many are refused
+// with the builder's messages; the parameter follows the rule of the header (SampleExtract index below N, MulXN amount mod 2N,
+// ignored elsewhere).  Nothing is run: the context has no device.
+bool graph_ops_match_the_header(spf_ctx* c)
+{
+    const uint64_t N = c->prm.polynomial_degree;
+    static uint64_t host_buf[4];
+    spf_graph* g = nullptr;
+    if (spf_graph_create(c, &g) != SPF_OK) return false;
+    bool ok = true;
+    auto expect = [&](const char* what, int op, spf_status st, spf_status want, const char* msg) {
+        if (st == want && (!msg || c->err == msg)) return;
+        fprintf(stderr, "spf_graph_add_op, operation %d, %s: status %d (%s), expected %d (%s)\n", op, what, st, c->err.c_str(), want, msg ? msg : "");
+        ok = false;
+    };
+    uint32_t input_of[5]; // one input node per ciphertext kind
+    for (int k = 0; k < 5; k++) expect("input", -1, spf_graph_add_input(g, (spf_value_kind)k, host_buf, &input_of[k]), SPF_OK, nullptr);
+    for (const HeaderOp& h : kHeaderOps) {
+        uint32_t in[4] = {0, 0, 0, 0}, node = 0;
+        for (int s = 0; s < h.arity; s++) in[s] = input_of[h.in[s]];
+        in[h.arity] = input_of[h.in[0]];
+        expect("right kinds", h.op, spf_graph_add_op(g, h.op, in, h.arity, 0, &node), SPF_OK, nullptr);
+        if (ok && (node + 1 != g->nodes.size() || g->nodes[node].kind != h.out || g->nodes[node].n_in != (uint32_t)h.arity)) {
+            fprintf(stderr, "spf_graph_add_op, operation %d: the node has kind %d, the header says %d\n", h.op, g->nodes[node].kind, h.out);
+            ok = false;
+        }
+        expect("its node as an output", h.op, spf_graph_add_output(g, node, host_buf), SPF_OK, nullptr);
+        const size_t n_nodes = g->nodes.size();
+        for (int s = 0; s < h.arity; s++)
+            for (int wrong = 0; wrong < 5; wrong++) {
+                if (wrong == h.in[s]) continue;
+                uint32_t bad[3] = {in[0], in[1], in[2]};
+                bad[s] = input_of[wrong];
+                expect("a wrong kind in one slot", h.op, spf_graph_add_op(g, h.op, bad, h.arity, 0, &node), SPF_ERR_INVALID_ARGUMENT,
+                       "graph op: operand has the wrong ciphertext type");
+            }
+        expect("one operand too few", h.op, spf_graph_add_op(g, h.op, in, h.arity - 1, 0, &node), SPF_ERR_INVALID_ARGUMENT,
+               "graph op: wrong number of operands");
+        expect("one operand too many", h.op, spf_graph_add_op(g, h.op, in, h.arity + 1, 0, &node), SPF_ERR_INVALID_ARGUMENT,
+               "graph op: wrong number of operands");
+        if (h.op == SPF_OP_SAMPLE_EXTRACT)
+            expect("index N", h.op, spf_graph_add_op(g, h.op, in, h.arity, N, &node), SPF_ERR_INVALID_ARGUMENT,
+                   "graph op: sample_extract index >= polynomial_degree");
+        if (g->nodes.size() != n_nodes) { fprintf(stderr, "spf_graph_add_op, operation %d: a refused call left a node\n", h.op); ok = false; }
+        // the parameter the node keeps
+        const uint64_t given = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : 2 * N + 3;
+        const uint64_t kept = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : (h.op == SPF_OP_MUL_XN ? 3 : 0);
+        expect("with a parameter", h.op, spf_graph_add_op(g, h.op, in, h.arity, given, &node), SPF_OK, nullptr);
+        if (ok && g->nodes[node].param != kept) {
+            fprintf(stderr, "spf_graph_add_op, operation %d: parameter %" PRIu64 " kept as %" PRIu64 ", expected %" PRIu64 "\n", h.op, given, g->nodes[node].param, kept);
+            ok = false;
+        }
+    }
+    uint32_t node = 0;
+    expect("no such operation", 10, spf_graph_add_op(g, (spf_graph_op)10, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    g->nodes.clear(); // (nothing was planned: no device memory to give back)
+    delete g;
+    return ok;
+}
+
+// spf_ciphertext_words against the formulas in the comments of include/spf_hip.h (spf_value_kind): n+1, k*N+1, (k+1)*N, l_cbs GLWEs;
+// the GGSW has no wire format
+bool wire_sizes_match_the_header(const spf_params& p)
+{
+    const size_t n = p.lwe_dimension, k = p.glwe_size, N = p.polynomial_degree, l = p.cbs_radix_count;
+    const struct { spf_value_kind kind; size_t words; } want[5] = {
+        {SPF_VAL_LWE0, n + 1}, {SPF_VAL_LWE1, k * N + 1}, {SPF_VAL_GLWE1, (k + 1) * N}, {SPF_VAL_GLEV1, l * (k + 1) * N}, {SPF_VAL_GGSW1, 0}};
+    bool ok = true;
+    for (const auto& w : want)
+        if (spf_ciphertext_words(&p, w.kind) != w.words) {
+            fprintf(stderr, "spf_ciphertext_words(kind %d) = %zu, the header says %zu\n", w.kind, spf_ciphertext_words(&p, w.kind), w.words);
+            ok = false;
+        }
+    return ok;
+}
+
 } // namespace
 
 int main(int argc, char** argv)
@@ -183,6 +285,8 @@ int main(int argc, char** argv)
     fake_ctx(tiny_ctx, tiny, true);
     fake_ctx(dflt_ctx, dflt, false);
     if (!batch_forms_refuse_bad_arguments(&dflt_ctx)) return 1;
+    if (!graph_ops_match_the_header(&dflt_ctx) || !graph_ops_match_the_header(&tiny_ctx)) return 1;
+    if (!wire_sizes_match_the_header(dflt) || !wire_sizes_match_the_header(tiny)) return 1;
     std::vector<uint8_t> key_seed;
     {
         const size_t want[4] = {(size_t)tiny.lwe_dimension * ggsw_fft_complex(tiny, tiny.pbs_radix_count),
@@ -296,10 +400,10 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < g->nodes.size(); i++) {
                 const auto& n = g->nodes[i];
                 if (n.op < 0) continue;
-                spf_graph_impl::OpInfo info{};
-                if (!spf_graph_impl::op_info(n.op, &info) || n.n_in != (uint32_t)info.arity) { fprintf(stderr, "graph: bad node accepted\n"); return 1; }
+                const HeaderOp* info = header_op(n.op);
+                if (!info || n.n_in != (uint32_t)info->arity || n.kind != info->out) { fprintf(stderr, "graph: bad node accepted\n"); return 1; }
                 for (uint32_t j = 0; j < n.n_in; j++)
-                    if (n.in[j] >= i || g->nodes[n.in[j]].kind != info.in_kind[j]) { fprintf(stderr, "graph: bad operand accepted\n"); return 1; }
+                    if (n.in[j] >= i || g->nodes[n.in[j]].kind != info->in[j]) { fprintf(stderr, "graph: bad operand accepted\n"); return 1; }
             }
             g->nodes.clear(); // (nothing was planned: no device memory to give back)
             delete g;
