@@ -279,6 +279,21 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_op(g_, o, operands.begin(), operands.size(), param, &n), ctx_);
         return n;
     }
+    // `PackedDynamicGenericIntGraphNode::unpack` (fluent/packed_dynamic_generic_int_graph_node.rs:24-39): the n_bits L1 LWE
+    // nodes of a packed integer, bit i = SampleExtract(i) of `packed_glwe`
+    std::vector<Node> unpack(Node packed_glwe, size_t n_bits)
+    {
+        std::vector<Node> bits(n_bits);
+        Evaluation::check(spf_graph_add_unpack(g_, packed_glwe, n_bits, bits.data()), ctx_);
+        return bits;
+    }
+    // `DynamicGenericIntGraphNodes::pack` (fluent/dynamic_generic_int_graph_nodes.rs:139-200): sum over i of X^i * bits[i]
+    Node pack(const std::vector<Node>& bits)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_pack(g_, bits.data(), bits.size(), &n), ctx_);
+        return n;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }

@@ -538,6 +538,22 @@ spf_status spf_graph_add_input(spf_graph *graph, spf_value_kind kind, const void
 spf_status spf_graph_add_trivial(spf_graph *graph, spf_value_kind kind, uint64_t bit, uint32_t *node);
 spf_status spf_graph_add_op(spf_graph *graph, spf_graph_op op, const uint32_t *inputs, size_t n_inputs,
                             uint64_t param, uint32_t *node);
+/* Packed integers in and out of a graph (an n-bit integer in one L1 GLWE, bit i at X^i: see spf_glwe_pack_batch).  Node
+ * constructors, not operations — as in the reference, where `PackedGenericInt::graph_input(ctx).unpack(ctx)` and
+ * `.pack(ctx, enc).collect_output(ctx, enc)` are nodes of the fluent layer and no `FheOp`s (fluent/generic_int.rs:261,
+ * fluent/packed_dynamic_generic_int_graph_node.rs:24-60, fluent/dynamic_generic_int_graph_nodes.rs:139-200).
+ *   add_unpack: `glwe_node` is any glwe1 node (input or computed), 0 < n_bits <= polynomial_degree; creates n_bits lwe1 nodes,
+ *     nodes_out[i] word-equal to SAMPLE_EXTRACT(param = i) of glwe_node, one level above it.  All unpacks of a level with the
+ *     same n_bits are ONE launch (SAMPLE_EXTRACT nodes batch by index: n_bits launches).
+ *   add_pack: nodes[0 .. n_bits) are glwe1 nodes of any origin and level, repeats allowed; creates one glwe1 node
+ *     = sum over i of X^i * nodes[i] mod 2^64, word-equal to spf_glwe_pack_batch of those rows (and so to the reference's
+ *     MulXN(i) + GlweAdd tree), one level above its highest operand.  All packs of a level with the same n_bits are ONE launch
+ *     that reads the rows where they lie.
+ * The new nodes are ordinary: operands of any operation, outputs, counted by spf_graph_stats.  A wrong argument
+ * (n_bits out of range, a node that does not exist or is no glwe1, a null pointer) is SPF_ERR_INVALID_ARGUMENT from the call,
+ * and the graph stays usable. */
+spf_status spf_graph_add_unpack(spf_graph *graph, uint32_t glwe_node, size_t n_bits, uint32_t *nodes_out /* n_bits */);
+spf_status spf_graph_add_pack(spf_graph *graph, const uint32_t *nodes, size_t n_bits, uint32_t *node_out);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */

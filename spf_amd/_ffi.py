@@ -113,6 +113,8 @@ SYMBOLS = [
     ("spf_graph_add_input", _I, [_P, _I, _P, C.POINTER(_U32)]),
     ("spf_graph_add_trivial", _I, [_P, _I, _U64, C.POINTER(_U32)]),
     ("spf_graph_add_op", _I, [_P, _I, C.POINTER(_U32), _SZ, _U64, C.POINTER(_U32)]),
+    ("spf_graph_add_unpack", _I, [_P, _U32, _SZ, C.POINTER(_U32)]),
+    ("spf_graph_add_pack", _I, [_P, C.POINTER(_U32), _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_output", _I, [_P, _U32, _P]),
     ("spf_graph_run", _I, [_P]),
     ("spf_graph_stats", _I, [_P, C.POINTER(_U32), C.POINTER(_U32), C.POINTER(_U32)]),

@@ -11,6 +11,14 @@
 // copying), the small operands of the other kinds are packed by `gather_rows_kernel` unless they are
 // already contiguous (the common KeyswitchL1toL0 -> CircuitBootstrap chain).
 //
+// Packed integers enter and leave a graph through two node constructors, as `PackedGenericInt::graph_input(..).unpack(..)` and
+// `.pack(..).collect_output(..)` do in the reference's fluent layer (fluent/packed_dynamic_generic_int_graph_node.rs:24-60,
+// fluent/dynamic_generic_int_graph_nodes.rs:139-200) — they are no `FheOp`s there and no spf_graph_op here.  Composed from
+// SampleExtract(i) / MulXN(i) / GlweAdd nodes, one 32-bit integer costs 32 + 31 launches and five more levels, because a level is
+// batched by parameter; spf_graph_add_unpack makes the n_bits LWEs of all integers of a level in ONE glwe_unpack_l1_kernel
+// launch, spf_graph_add_pack sums the rows of all packs of a level in ONE glwe_pack_rows_kernel launch that reads them where
+// they lie.
+//
 // Included at the end of spf_hip.hip: uses its `fail` / HIPCHK helpers and the `_dev` entry points.
 #pragma once
 
@@ -47,19 +55,23 @@ struct spf_pinned_buf {
 };
 
 struct spf_graph {
+    // the two node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack)
+    enum : int32_t { kNodeUnpack = 64, kNodePack = 65 };
     struct Node {
-        int32_t op;        // spf_graph_op, or -1 input, -2 trivial constant
+        int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack, or -1 input, -2 trivial constant
         int32_t kind;      // spf_value_kind of the value the node produces
-        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit
+        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node
         uint32_t in[3];
         uint32_t n_in;
+        uint32_t n_bits;   // unpack and pack nodes: width of the integer
+        uint32_t ext;      // pack nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
         uint32_t level;
         size_t off;        // byte offset of the value in the arena
         const void* host;  // inputs: caller's buffer, read at every run
     };
     struct Group {
         int32_t op;
-        uint64_t param;
+        uint64_t param;    // (unpack and pack groups: n_bits)
         std::vector<uint32_t> members;
         size_t out_off = 0;
         // per operand slot: offset of the first operand when the members' operands are contiguous
@@ -73,6 +85,14 @@ struct spf_graph {
     struct spf_group* grp = nullptr; // a graph of a device group (spf_group_graph_create): placed on a member when it is run
     int member = -1;                 // ... the member its most recent run took place on
     std::vector<Node> nodes;
+    std::vector<uint32_t> pack_in; // operand lists of the pack nodes
+    // f(operand id) for every operand of a node
+    template <class F> void for_operands(const Node& n, F f) const
+    {
+        for (uint32_t i = 0; i < n.n_in; i++) f(n.in[i]);
+        if (n.op == kNodePack)
+            for (uint32_t i = 0; i < n.n_bits; i++) f(pack_in[n.ext + i]);
+    }
     std::vector<std::pair<uint32_t, void*>> outputs;
     bool planned = false;
     std::vector<Group> groups;
@@ -154,7 +174,7 @@ inline spf_status plan(spf_graph* g)
     for (auto& n : g->nodes)
         if (n.op >= 0) {
             uint32_t lv = 0;
-            for (uint32_t i = 0; i < n.n_in; i++) lv = std::max(lv, g->nodes[n.in[i]].level);
+            g->for_operands(n, [&](uint32_t in) { lv = std::max(lv, g->nodes[in].level); });
             n.level = lv + 1;
             max_level = std::max(max_level, n.level);
         }
@@ -171,8 +191,9 @@ inline spf_status plan(spf_graph* g)
         for (size_t id = nn; id-- > 0;) {
             const auto& n = g->nodes[id];
             if (n.op < 0) continue;
-            for (uint32_t i = 0; i < n.n_in; i++)
-                if (g->nodes[n.in[i]].op >= 0) alap[n.in[i]] = std::min(alap[n.in[i]], alap[id] - 1);
+            g->for_operands(n, [&](uint32_t in) {
+                if (g->nodes[in].op >= 0) alap[in] = std::min(alap[in], alap[id] - 1);
+            });
         }
         std::vector<uint32_t> cbs;
         for (uint32_t id = 0; id < nn; id++)
@@ -191,7 +212,7 @@ inline spf_status plan(spf_graph* g)
             auto& n = g->nodes[id];
             if (n.op < 0) continue;
             uint32_t lv = 0;
-            for (uint32_t i = 0; i < n.n_in; i++) lv = std::max(lv, g->nodes[n.in[i]].level);
+            g->for_operands(n, [&](uint32_t in) { lv = std::max(lv, g->nodes[in].level); });
             n.level = std::max(lv + 1, fixed[id]);
         }
         // pull the conversion chain's head (SampleExtract -> KeyswitchL1toL0) up against its bootstrap
@@ -201,22 +222,25 @@ inline spf_status plan(spf_graph* g)
             if (n.op < 0) continue;
             if ((n.op == SPF_OP_KEYSWITCH_L1_TO_L0 || n.op == SPF_OP_SAMPLE_EXTRACT) && min_user[id] != 0xffffffffu)
                 n.level = std::max(n.level, min_user[id] - 1);
-            for (uint32_t i = 0; i < n.n_in; i++) min_user[n.in[i]] = std::min(min_user[n.in[i]], n.level);
+            g->for_operands(n, [&](uint32_t in) { min_user[in] = std::min(min_user[in], n.level); });
         }
     }
     g->n_levels = max_level;
-    // one group per (level, kind, parameter), members in node order
+    // one group per (level, kind, parameter), members in node order.  Unpack and pack nodes group by their width: the bit
+    // nodes of one spf_graph_add_unpack call have consecutive ids and one level (their source's + 1; nothing below moves
+    // them), so a group's members are whole integers, int-major
     std::map<std::tuple<uint32_t, int32_t, uint64_t>, size_t> index;
     for (uint32_t id = 0; id < g->nodes.size(); id++) {
         const auto& n = g->nodes[id];
         if (n.op < 0) continue;
-        auto key = std::make_tuple(n.level, n.op, n.param);
+        const uint64_t key_param = n.op >= spf_graph::kNodeUnpack ? n.n_bits : n.param;
+        auto key = std::make_tuple(n.level, n.op, key_param);
         auto it = index.find(key);
         if (it == index.end()) {
             it = index.emplace(key, g->groups.size()).first;
             g->groups.emplace_back();
             g->groups.back().op = n.op;
-            g->groups.back().param = n.param;
+            g->groups.back().param = key_param;
         }
         g->groups[it->second].members.push_back(id);
     }
@@ -230,8 +254,7 @@ inline spf_status plan(spf_graph* g)
     // outputs of a group are consecutive rows
     size_t stage = 0;
     for (auto& gr : g->groups) {
-        const spf_ops::OpRow& info = op_row(gr.op);
-        const size_t ob = value_bytes(g->prm, info.out_kind);
+        const size_t ob = value_bytes(g->prm, g->nodes[gr.members[0]].kind);
         gr.out_off = off;
         for (size_t i = 0; i < gr.members.size(); i++) g->nodes[gr.members[i]].off = off + i * ob;
         off = align_up(off + gr.members.size() * ob, 256);
@@ -241,8 +264,30 @@ inline spf_status plan(spf_graph* g)
     // operand access per group
     std::vector<void*> table;
     for (auto& gr : g->groups) {
-        const spf_ops::OpRow& info = op_row(gr.op);
         const size_t B = gr.members.size();
+        if (gr.op == spf_graph::kNodePack) {
+            // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table
+            gr.ptr_index[0] = table.size();
+            for (uint32_t id : gr.members)
+                g->for_operands(g->nodes[id], [&](uint32_t in) { table.push_back(g->d_arena + g->nodes[in].off); });
+            continue;
+        }
+        if (gr.op == spf_graph::kNodeUnpack) {
+            // one source GLWE per integer (every n_bits-th member): in place when they are consecutive, else gathered
+            const size_t ints = B / gr.param, ib = value_bytes(g->prm, SPF_VAL_GLWE1);
+            auto src = [&](size_t m) { return g->nodes[g->nodes[gr.members[m * gr.param]].in[0]].off; };
+            bool contig = true;
+            for (size_t m = 1; m < ints && contig; m++) contig = src(m) == src(0) + m * ib;
+            gr.contiguous[0] = contig;
+            gr.first_off[0] = src(0);
+            if (!contig) {
+                gr.ptr_index[0] = table.size();
+                for (size_t m = 0; m < ints; m++) table.push_back(g->d_arena + src(m));
+                stage = std::max(stage, ints * ib);
+            }
+            continue;
+        }
+        const spf_ops::OpRow& info = op_row(gr.op);
         if (info.cmux_family) {
             // units: one per GLWE pair; {selector, low (a), high (b), out}
             const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
@@ -303,7 +348,7 @@ inline spf_status plan(spf_graph* g)
     if (getenv("SPF_GRAPH_WIDTHS")) { // diagnostic: CMUX-family launch widths (units) of the plan
         std::map<size_t, size_t> hist;
         for (auto& gr : g->groups)
-            if (op_row(gr.op).cmux_family) hist[gr.members.size() * (gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1)]++;
+            if (gr.op < spf_graph::kNodeUnpack && op_row(gr.op).cmux_family) hist[gr.members.size() * (gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1)]++;
         for (auto& kv : hist) fprintf(stderr, "[graph widths] %zu units x %zu launches\n", kv.first, kv.second);
     }
     if (!g->h_inputs.resize(g->inputs_bytes)) return fail(c, SPF_ERR_HIP, "graph: out of host memory for the inputs");
@@ -324,9 +369,30 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
         }
     g->n_launches = 0;
     for (const auto& gr : g->groups) {
-        const spf_ops::OpRow& info = op_row(gr.op);
         const size_t B = gr.members.size();
         char* out = g->d_arena + gr.out_off;
+        if (gr.op == spf_graph::kNodePack) {
+            spf_status st = launch_glwe_pack_rows(c, s, B, gr.param, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
+        if (gr.op == spf_graph::kNodeUnpack) {
+            const size_t ints = B / gr.param;
+            const uint64_t* src = (const uint64_t*)(g->d_arena + gr.first_off[0]);
+            if (!gr.contiguous[0]) {
+                spf_status st = spf_gather_rows_dev(c, s, ints, value_bytes(g->prm, SPF_VAL_GLWE1) / 8,
+                                                    (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)g->d_stage[0]);
+                if (st != SPF_OK) return st;
+                g->n_launches++;
+                src = (const uint64_t*)g->d_stage[0];
+            }
+            spf_status st = launch_glwe_unpack(c, s, ints, gr.param, src, (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
+        const spf_ops::OpRow& info = op_row(gr.op);
         if (info.cmux_family) {
             const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
             spf_status st = spf_cmux_scattered_dev(c, s, B * per, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
@@ -554,6 +620,57 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
     n.param = param;
     *node = (uint32_t)g->nodes.size();
     g->nodes.push_back(n);
+    g->planned = false;
+    return SPF_OK;
+}
+
+// `PackedDynamicGenericIntGraphNode::unpack` as a node constructor: n_bits LWE1 nodes, node i = sample_extract(glwe_node, i)
+spf_status spf_graph_add_unpack(spf_graph* g, uint32_t glwe_node, size_t n_bits, uint32_t* nodes_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!nodes_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: null pointer");
+    if (n_bits == 0 || n_bits > g->prm.polynomial_degree)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: n_bits must be in 1 ..= polynomial_degree");
+    if (glwe_node >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not a node of this graph");
+    if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not an L1 GLWE");
+    spf_graph::Node n{};
+    n.op = spf_graph::kNodeUnpack; n.kind = SPF_VAL_LWE1; n.n_in = 1; n.in[0] = glwe_node; n.n_bits = (uint32_t)n_bits;
+    const uint32_t first = (uint32_t)g->nodes.size();
+    try {
+        g->nodes.reserve(g->nodes.size() + n_bits); // all of the integer's nodes or none
+    } catch (const std::exception&) {
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    for (size_t i = 0; i < n_bits; i++) {
+        n.param = i;
+        g->nodes.push_back(n);
+        nodes_out[i] = first + (uint32_t)i;
+    }
+    g->planned = false;
+    return SPF_OK;
+}
+
+// `DynamicGenericIntGraphNodes::pack` as a node constructor: one GLWE1 node = sum over i of X^i * nodes[i]
+spf_status spf_graph_add_pack(spf_graph* g, const uint32_t* nodes, size_t n_bits, uint32_t* node_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
+    if (n_bits == 0 || n_bits > g->prm.polynomial_degree)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: n_bits must be in 1 ..= polynomial_degree");
+    for (size_t i = 0; i < n_bits; i++) {
+        if (nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not a node of this graph");
+        if (g->nodes[nodes[i]].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not an L1 GLWE");
+    }
+    spf_graph::Node n{};
+    n.op = spf_graph::kNodePack; n.kind = SPF_VAL_GLWE1; n.n_bits = (uint32_t)n_bits; n.ext = (uint32_t)g->pack_in.size();
+    try {
+        g->pack_in.insert(g->pack_in.end(), nodes, nodes + n_bits);
+        g->nodes.push_back(n);
+    } catch (const std::exception&) {
+        g->pack_in.resize(n.ext);
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    *node_out = (uint32_t)g->nodes.size() - 1;
     g->planned = false;
     return SPF_OK;
 }

@@ -830,11 +830,13 @@ spf_status merge_jobs(spf_ctx* c, const std::vector<spf_graph*>& jobs, spf_graph
     if (st != SPF_OK) return st;
     try {
         for (const spf_graph* j : jobs) {
-            const uint32_t base = (uint32_t)m->nodes.size();
+            const uint32_t base = (uint32_t)m->nodes.size(), ext_base = (uint32_t)m->pack_in.size();
             for (spf_graph::Node n : j->nodes) {
                 for (uint32_t i = 0; i < n.n_in; i++) n.in[i] += base;
+                if (n.op == spf_graph::kNodePack) n.ext += ext_base; // (their operand lists move with them)
                 m->nodes.push_back(n);
             }
+            for (uint32_t in : j->pack_in) m->pack_in.push_back(in + base);
             for (const auto& o : j->outputs) m->outputs.emplace_back(o.first + base, o.second);
         }
     } catch (const std::exception&) {

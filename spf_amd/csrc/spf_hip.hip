@@ -1173,6 +1173,19 @@ static spf_status launch_glwe_pack(spf_ctx* c, hipStream_t s, size_t B, size_t n
     return SPF_OK;
 }
 
+// the pack of rows that are not contiguous (a level of a gate graph, spf_graph.hpp): d_rows is a device table of B * n_bits
+// device pointers, d_out B contiguous GLWEs that overlap none of the rows
+static spf_status launch_glwe_pack_rows(spf_ctx* c, hipStream_t s, size_t B, size_t n_bits, const uint64_t* const* d_rows,
+                                        uint64_t* d_out)
+{
+    const size_t pieces = (glwe_words(c->prm) + 255) / 256;
+    const unsigned blocks = (unsigned)std::min<size_t>(B * pieces, 8 * (size_t)c->n_cu);
+    hipLaunchKernelGGL(glwe_pack_rows_kernel, dim3(blocks), dim3(256), 0, s, d_rows, d_out, B, (uint32_t)n_bits, c->log_n,
+                       c->prm.glwe_size);
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
 // Bits per workgroup: all of a ciphertext's when the batch alone fills the chip (each packed GLWE read once), fewer when it does
 // not, down to one bit per workgroup (a lone integer is unpacked by n_bits workgroups side by side).
 static spf_status launch_glwe_unpack(spf_ctx* c, hipStream_t s, size_t B, size_t n_bits, const uint64_t* d_glwe, uint64_t* d_lwe)

@@ -1855,6 +1855,31 @@ __global__ void glwe_pack_bits_kernel(const uint64_t* __restrict__ in, uint64_t*
     }
 }
 
+// The same sum over rows that lie anywhere: bit i of integer b is the GLWE at rows[b * n_bits + i] (a device table of device
+// pointers; repeats allowed).  A gate graph packs values that sit wherever their producers wrote them (the 33 sum bits of an
+// adder come from 33 levels); gathering 32 KiB rows first would double the traffic of an HBM-bound step.  The row pointer of
+// an iteration is the same in every lane (a scalar load), the shifted reads are the coalesced ones of glwe_pack_bits_kernel,
+// `out` is contiguous and must not overlap any row.  Same grid-stride shape, no LDS, no scratch, N and k at run time.
+__global__ void glwe_pack_rows_kernel(const uint64_t* const* __restrict__ rows, uint64_t* __restrict__ out, size_t B,
+                                      uint32_t n_bits, uint32_t logN, uint32_t k)
+{
+    const uint32_t N = 1u << logN, gw = (k + 1) << logN, pieces = (gw + blockDim.x - 1) / blockDim.x;
+    for (size_t item = blockIdx.x; item < B * pieces; item += gridDim.x) {
+        const size_t b = item / pieces;
+        const uint32_t r = (uint32_t)(item - b * pieces) * blockDim.x + threadIdx.x;
+        if (r >= gw) continue;
+        const uint32_t j = r & (N - 1), p = r - j; // coefficient j of polynomial r / N
+        const uint64_t* const* row = rows + b * n_bits;
+        uint64_t acc = 0;
+#pragma unroll 8
+        for (uint32_t i = 0; i < n_bits; i++) {
+            const uint64_t* x = row[i] + p;
+            acc += j >= i ? x[j - i] : (uint64_t)0 - x[j + N - i];
+        }
+        out[b * gw + r] = acc;
+    }
+}
+
 // `PackedDynamicGenericIntGraphNode::unpack` (parasol_runtime fluent/packed_dynamic_generic_int_graph_node.rs:24-39):
 // row b * n_bits + i of `lwe` = `sample_extract(glwe[b], i)` (glwe_ciphertext_ops.rs:31-76), the indexing of
 // sample_extract_kernel: mask word p*N + j = a[p*N + i - j] when j <= i, else -a[p*N + i + N - j]; body a[k*N + i].

@@ -40,6 +40,23 @@ class FheOp(enum.IntEnum):
     MulXN = 9
 
 
+# RecordedCircuit's codes of the two node constructors that are no FheOp (spf_graph_add_unpack / spf_graph_add_pack)
+NODE_UNPACK = 64
+NODE_PACK = 65
+
+
+def _check_n_bits(what: str, n_bits: int, degree: int) -> int:
+    if isinstance(n_bits, bool) or not isinstance(n_bits, (int, np.integer)) or not 0 < n_bits <= degree:
+        raise SpfError(1, f"{what}: n_bits must be in 1 ..= {degree}, got {n_bits!r}")
+    return int(n_bits)
+
+
+def _check_node(what: str, node, n_nodes: int) -> int:
+    if isinstance(node, bool) or not isinstance(node, (int, np.integer)) or not 0 <= node < n_nodes:
+        raise SpfError(1, f"{what}: {node!r} is not a node of this circuit")
+    return int(node)
+
+
 class FheCircuit:
     def __init__(self, engine: Engine):
         self._eng = engine
@@ -93,6 +110,26 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_op(self._g, int(op), arr, len(inputs), param, C.byref(node)))
         return node.value
 
+    # PackedGenericInt::graph_input(ctx).unpack(ctx): n_bits LWE1 nodes, node i = SampleExtract(i) of the packed GLWE1 node
+    def add_unpack(self, glwe_node: int, n_bits: int) -> List[int]:
+        n_bits = _check_n_bits("add_unpack", n_bits, self._eng.params.polynomial_degree)
+        if isinstance(glwe_node, bool) or not isinstance(glwe_node, (int, np.integer)) or not 0 <= glwe_node < 1 << 32:
+            raise SpfError(1, f"add_unpack: {glwe_node!r} is not a node id")
+        out = (C.c_uint32 * n_bits)()
+        self._eng._ck(self._lib.spf_graph_add_unpack(self._g, int(glwe_node), n_bits, out))
+        return list(out)
+
+    # ....pack(ctx, enc): one GLWE1 node = sum over i of X^i * nodes[i]
+    def add_pack(self, nodes: Sequence[int]) -> int:
+        nodes = list(nodes)
+        n_bits = _check_n_bits("add_pack", len(nodes), self._eng.params.polynomial_degree)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 1 << 32 for x in nodes):
+            raise SpfError(1, "add_pack: the operands must be node ids")
+        arr = (C.c_uint32 * n_bits)(*[int(x) for x in nodes])
+        node = C.c_uint32()
+        self._eng._ck(self._lib.spf_graph_add_pack(self._g, arr, n_bits, C.byref(node)))
+        return node.value
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -125,13 +162,15 @@ class RecordedCircuit:
                  FheOp.MultiplyGgswGlwe: ValueKind.GLWE1, FheOp.CircuitBootstrap: ValueKind.GGSW1,
                  FheOp.SchemeSwitch: ValueKind.GGSW1, FheOp.MulXN: ValueKind.GLWE1}
 
-    def __init__(self):
-        self.op: List[int] = []        # FheOp, -1 input, -2 trivial constant
+    def __init__(self, polynomial_degree: int = 2048):
+        self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK, -1 input, -2 trivial constant
         self.kind: List[int] = []
-        self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit
-        self.inputs: List[tuple] = []
+        self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
+        self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands)
         self.host: List = []           # inputs: the caller's array
         self.outputs: List[int] = []   # nodes, in add_output order
+        self._unpack_width: dict = {}  # unpack node -> n_bits of its add_unpack call
 
     def _add(self, op, kind, param, inputs, host=None) -> int:
         self.op.append(int(op)); self.kind.append(int(kind)); self.param.append(int(param))
@@ -149,6 +188,24 @@ class RecordedCircuit:
             raise SpfError(1, "operand is not a node of this circuit")
         return self._add(FheOp(op), self._OUT_KIND[FheOp(op)], param, inputs)
 
+    def add_unpack(self, glwe_node: int, n_bits: int) -> List[int]:
+        n_bits = _check_n_bits("add_unpack", n_bits, self.polynomial_degree)
+        glwe_node = _check_node("add_unpack", glwe_node, len(self.op))
+        if self.kind[glwe_node] != int(ValueKind.GLWE1):
+            raise SpfError(1, "add_unpack: the operand is not an L1 GLWE")
+        out = [self._add(NODE_UNPACK, ValueKind.LWE1, i, (glwe_node,)) for i in range(n_bits)]
+        for n in out:
+            self._unpack_width[n] = n_bits
+        return out
+
+    def add_pack(self, nodes: Sequence[int]) -> int:
+        nodes = list(nodes)
+        _check_n_bits("add_pack", len(nodes), self.polynomial_degree)
+        nodes = [_check_node("add_pack", x, len(self.op)) for x in nodes]
+        if any(self.kind[x] != int(ValueKind.GLWE1) for x in nodes):
+            raise SpfError(1, "add_pack: an operand is not an L1 GLWE")
+        return self._add(NODE_PACK, ValueKind.GLWE1, len(nodes), nodes)
+
     def add_output(self, node: int, kind: ValueKind) -> int:
         if self.kind[node] != int(kind):
             raise SpfError(1, "output kind does not match the node")
@@ -158,14 +215,24 @@ class RecordedCircuit:
     def lower(self, engine: Engine):
         """-> (FheCircuit, [output arrays]) with the same nodes in the same order"""
         g = FheCircuit(engine)
-        for i in range(len(self.op)):
-            if self.op[i] == -1:
+        i = 0
+        while i < len(self.op):
+            if self.op[i] == NODE_UNPACK:    # the bit nodes of one add_unpack call are consecutive
+                n_bits = self._unpack_width[i]
+                bits = g.add_unpack(self.inputs[i][0], n_bits)
+                assert bits == list(range(i, i + n_bits))
+                i += n_bits
+                continue
+            if self.op[i] == NODE_PACK:
+                n = g.add_pack(self.inputs[i])
+            elif self.op[i] == -1:
                 n = g.add_input(ValueKind(self.kind[i]), self.host[i])
             elif self.op[i] == -2:
                 n = g.add_trivial(ValueKind(self.kind[i]), self.param[i])
             else:
                 n = g.add_op(FheOp(self.op[i]), self.inputs[i], self.param[i])
             assert n == i
+            i += 1
         return g, [g.add_output(n, ValueKind(self.kind[n])) for n in self.outputs]
 
     def arrays(self) -> dict:
@@ -179,11 +246,53 @@ class RecordedCircuit:
 
     def _build_arrays(self) -> dict:
         n = len(self.op)
+        # a pack node's operands do not fit the three columns: they are ext[ext_at[i] : ext_at[i] + n_bits[i]] and its n_in is 0
+        # (the executor's own layout, spf_graph.hpp).  n_bits is the integer's width on unpack and pack nodes, 0 elsewhere;
+        # an unpack node's param is its bit index.
         ins = np.zeros((n, 3), dtype=np.uint32)
+        n_in = np.zeros(n, dtype=np.uint32)
+        n_bits = np.zeros(n, dtype=np.uint32)
+        ext_at = np.zeros(n, dtype=np.uint32)
+        ext: List[int] = []
         for i, t in enumerate(self.inputs):
+            if self.op[i] == NODE_PACK:
+                n_bits[i], ext_at[i] = len(t), len(ext)
+                ext.extend(t)
+                continue
+            if self.op[i] == NODE_UNPACK:
+                n_bits[i] = self._unpack_width[i]
             ins[i, :len(t)] = t
+            n_in[i] = len(t)
         keep = np.zeros(n, dtype=np.uint8)
         keep[self.outputs] = 1
-        return {"op": np.array([o if o >= 0 else -1 for o in self.op], dtype=np.int32), "in": ins,
-                "n_in": np.array([len(t) for t in self.inputs], dtype=np.uint32),
-                "param": np.array(self.param, dtype=np.uint64), "keep": keep}
+        return {"op": np.array([o if o >= 0 else -1 for o in self.op], dtype=np.int32), "in": ins, "n_in": n_in,
+                "param": np.array(self.param, dtype=np.uint64), "keep": keep,
+                "n_bits": n_bits, "ext_at": ext_at, "ext": np.array(ext, dtype=np.uint32)}
+
+    @classmethod
+    def from_arrays(cls, a: dict, kind: Sequence[int], host: Sequence, polynomial_degree: int = 2048) -> "RecordedCircuit":
+        """the circuit that `arrays()` describes.  arrays() folds inputs and constants into op -1 (a per-operation driver is
+        handed their values), so `kind` and `host` per node come with it, as in `self.kind` / `self.host`: a node with a host
+        array is an input, one without a constant.  Outputs come back in node order."""
+        g = cls(polynomial_degree)
+        i, n = 0, len(a["op"])
+        while i < n:
+            op = int(a["op"][i])
+            if op == NODE_UNPACK:
+                w = int(a["n_bits"][i])
+                g.add_unpack(int(a["in"][i, 0]), w)
+                i += w
+                continue
+            if op == NODE_PACK:
+                at = int(a["ext_at"][i])
+                g.add_pack([int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]])
+            elif op == -1 and host[i] is not None:
+                g.add_input(ValueKind(kind[i]), host[i])
+            elif op == -1:
+                g.add_trivial(ValueKind(kind[i]), int(a["param"][i]))
+            else:
+                g.add_op(FheOp(op), [int(x) for x in a["in"][i, :int(a["n_in"][i])]], int(a["param"][i]))
+            i += 1
+        for node in np.flatnonzero(a["keep"]):
+            g.add_output(int(node), ValueKind(g.kind[int(node)]))
+        return g

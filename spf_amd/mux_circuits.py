@@ -446,6 +446,13 @@ class GraphBuilder:
         x = self.graph.add_op(FheOp.KeyswitchL1toL0, [x])
         return self.graph.add_op(FheOp.CircuitBootstrap, [x])
 
+    # packed integers (`PackedGenericInt::graph_input(ctx).unpack(ctx)`, `....pack(ctx, enc)`): the graph's node constructors
+    def add_unpack(self, packed_glwe_node, n_bits: int) -> list:
+        return self.graph.add_unpack(packed_glwe_node, n_bits)
+
+    def add_pack(self, glwe_nodes) -> int:
+        return self.graph.add_pack(glwe_nodes)
+
 
 def append_uint_multiply(builder, a: Sequence, b: Sequence, blocks: Callable[[int, int], MuxCircuit]) -> list:
     """`mul_impl` (parasol_runtime/src/circuits/mul.rs:90-200): recursive gradeschool multiplication of two unsigned

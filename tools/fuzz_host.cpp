@@ -219,6 +219,47 @@ bool graph_ops_match_the_header(spf_ctx* c)
     }
     uint32_t node = 0;
     expect("no such operation", 10, spf_graph_add_op(g, (spf_graph_op)10, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    // the two node constructors of packed integers: n_bits nodes of kind LWE1 with the bit index as parameter / one GLWE1 node
+    // whose operand list is kept whole; every refusal of the header, and a refused call leaves nothing behind
+    {
+        const uint32_t glwe = input_of[SPF_VAL_GLWE1], lwe1 = input_of[SPF_VAL_LWE1];
+        std::vector<uint32_t> bits(N + 1, 0), rows(N + 1, glwe);
+        const size_t before = g->nodes.size();
+        expect("unpack, N bits", -1, spf_graph_add_unpack(g, glwe, N, bits.data()), SPF_OK, nullptr);
+        for (uint64_t i = 0; ok && i < N; i++)
+            if (bits[i] != before + i || g->nodes[bits[i]].kind != SPF_VAL_LWE1 || g->nodes[bits[i]].param != i || g->nodes[bits[i]].in[0] != glwe) {
+                fprintf(stderr, "spf_graph_add_unpack: node %" PRIu64 " is not bit %" PRIu64 " of its operand\n", (uint64_t)bits[i], i);
+                ok = false;
+            }
+        expect("pack, N rows", -1, spf_graph_add_pack(g, rows.data(), N, &node), SPF_OK, nullptr);
+        if (ok && (node + 1 != g->nodes.size() || g->nodes[node].kind != SPF_VAL_GLWE1 || g->nodes[node].n_bits != N ||
+                   g->pack_in.size() != N || g->nodes[node].ext != 0)) {
+            fprintf(stderr, "spf_graph_add_pack: the node does not keep its %" PRIu64 " operands\n", N);
+            ok = false;
+        }
+        expect("the pack node as an output", -1, spf_graph_add_output(g, node, host_buf), SPF_OK, nullptr);
+        expect("a bit node as an output", -1, spf_graph_add_output(g, bits[N - 1], host_buf), SPF_OK, nullptr);
+        const size_t n_nodes = g->nodes.size();
+        const char* range_u = "graph unpack: n_bits must be in 1 ..= polynomial_degree";
+        const char* range_p = "graph pack: n_bits must be in 1 ..= polynomial_degree";
+        expect("unpack, 0 bits", -1, spf_graph_add_unpack(g, glwe, 0, bits.data()), SPF_ERR_INVALID_ARGUMENT, range_u);
+        expect("unpack, N + 1 bits", -1, spf_graph_add_unpack(g, glwe, N + 1, bits.data()), SPF_ERR_INVALID_ARGUMENT, range_u);
+        expect("unpack, no such node", -1, spf_graph_add_unpack(g, (uint32_t)n_nodes, 1, bits.data()), SPF_ERR_INVALID_ARGUMENT,
+               "graph unpack: operand is not a node of this graph");
+        expect("unpack of an LWE", -1, spf_graph_add_unpack(g, lwe1, 1, bits.data()), SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not an L1 GLWE");
+        expect("unpack, null out", -1, spf_graph_add_unpack(g, glwe, 1, nullptr), SPF_ERR_INVALID_ARGUMENT, "graph unpack: null pointer");
+        expect("unpack, null graph", -1, spf_graph_add_unpack(nullptr, glwe, 1, bits.data()), SPF_ERR_INVALID_ARGUMENT, nullptr);
+        expect("pack, 0 rows", -1, spf_graph_add_pack(g, rows.data(), 0, &node), SPF_ERR_INVALID_ARGUMENT, range_p);
+        expect("pack, N + 1 rows", -1, spf_graph_add_pack(g, rows.data(), N + 1, &node), SPF_ERR_INVALID_ARGUMENT, range_p);
+        rows[N - 1] = (uint32_t)n_nodes;
+        expect("pack, no such node", -1, spf_graph_add_pack(g, rows.data(), N, &node), SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not a node of this graph");
+        rows[N - 1] = bits[0];
+        expect("pack of an LWE", -1, spf_graph_add_pack(g, rows.data(), N, &node), SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not an L1 GLWE");
+        expect("pack, null rows", -1, spf_graph_add_pack(g, nullptr, 1, &node), SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
+        expect("pack, null out", -1, spf_graph_add_pack(g, rows.data(), 1, nullptr), SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
+        expect("pack, null graph", -1, spf_graph_add_pack(nullptr, rows.data(), 1, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
+        if (g->nodes.size() != n_nodes || g->pack_in.size() != N) { fprintf(stderr, "a refused unpack or pack left a node\n"); ok = false; }
+    }
     g->nodes.clear(); // (nothing was planned: no device memory to give back)
     delete g;
     return ok;
