@@ -84,13 +84,7 @@ template <int L, int LOGB, int W>
 __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
 {
     static_assert(L == 6 && LOGB == 7, "three digit pairs; the state after the first pair fits 32 bits");
-#ifdef SPF_STAMPS
-    uint64_t st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMPT(i) do { uint64_t t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMPT(i) do { } while (0)
-#endif
+    PhaseStamps<12> stamps;
     constexpr int XP = 2;
     constexpr int NT = 512;
     c64* tab = reinterpret_cast<c64*>(smem);
@@ -112,7 +106,6 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
     const bool owns_output = unit_raw < a.units;
     const uint32_t unit = owns_output ? unit_raw : a.units - 1;
     const uint32_t ct = unit / a.cbs_count, lvl = unit % a.cbs_count;
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
 
     // key chunk c = 3 (round - 1) + m: the 64 KiB [level L-2-2m | level L-1-2m] of that round, copied as it lies: the
     // first digit of the pair (j = 2m, level L-1-2m) is the ring's second half
@@ -136,7 +129,7 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
         for (int p = 0; p < 2; p++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                uint32_t idx = (uint32_t)coef2(e) + lvl; // X^-lvl: out[c] = +-in[c + lvl]
+                uint32_t idx = (uint32_t)coef2(e, lane, w) + lvl; // X^-lvl: out[c] = +-in[c + lvl]
                 uint32_t src = idx & (kN - 1);
                 uint64_t v = g[p * kN + src];
                 if (p == 1 && src <= lvl) // glwe_rotated.b[t] += encode(1, cbs_radix_log*(t+1)+1), t <= lvl
@@ -219,7 +212,7 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
             wave_lds_fence(); // gathered: the region may be overwritten (next staging / the exchange image)
         }
 
-        STAMPT(0);
+        stamps.mark(0);
         c64 prod[2][8];
 #pragma unroll
         for (int m = 0; m < 3; m++, chunk++) {
@@ -246,28 +239,18 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
             }
             // the ring is free since the barrier behind the previous MADs: rows of this pair (those of a round's first
             // pair were requested ahead of the previous round's inverse transforms)
-            STAMPT(1);
+            stamps.mark(1);
             if (m == 0) young_prio<0>(is_young);
             if (m == 2) young_prio<1>(is_young);
             if (m > 0) ring_dma(chunk);
             SPF_TRACE_PAIR<+1, XP>(VV[0], VV[1], mine, tab, lane);
-            STAMPT(2);
+            stamps.mark(2);
             // radix-2 stage across the two waves, both digits in one exchange
-            if constexpr (w == 0) {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][4 + i];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][i];
-            }
+            cross_put<w>(mine, lane, VV);
             if (m == 2) young_prio<0>(is_young);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // my share of the key rows has landed
             __syncthreads();
-            STAMPT(3);
+            stamps.mark(3);
             if constexpr (w == 0) {
 #pragma unroll
                 for (int j = 0; j < 2; j++)
@@ -315,34 +298,26 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
                         const int r = (grp * 2 + i) & 7, q = grp >> 2;
-                        const c64 k = kb[grp % 2][i];
                         const bool first = m == 0 && j == 0;
-                        double re = __builtin_fma(k.re, VV[j][r].re, first ? 0.0 : prod[q][r].re);
-                        double im = __builtin_fma(k.re, VV[j][r].im, first ? 0.0 : prod[q][r].im);
-                        prod[q][r].re = __builtin_fma(-k.im, VV[j][r].im, re);
-                        prod[q][r].im = __builtin_fma(k.im, VV[j][r].re, im);
+                        c64 acc = {first ? 0.0 : prod[q][r].re, first ? 0.0 : prod[q][r].im};
+                        cmad(acc, kb[grp % 2][i], VV[j][r]);
+                        prod[q][r] = acc;
                     }
                 }
             }
-            STAMPT(4);
+            stamps.mark(4);
             __syncthreads(); // every wave is done with the ring and with its partner's cross data
-            STAMPT(5);
+            stamps.mark(5);
         }
 
         // ---- back to the torus, both output polynomials together
         c64 WW[2][8];
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const c64 wci = wc[64 * i];
-                WW[q][i] = cadd(prod[q][i], prod[q][i + 4]);
-                WW[q][4 + i] = cmul_tw<-1>(csub(prod[q][i], prod[q][i + 4]), wci);
-            }
+        inverse_split(prod, wc, WW);
         // The inverse cross exchange goes through the KEY RING (free between the barrier behind the last MADs and the next
         // refill): wave v writes its outgoing half into slot v (8 KiB), reads slot v^1 behind ONE barrier and then refills
         // exactly that slot with its 8 KiB of the next key chunk — the slot's only reader is the wave that overwrites it,
         // in program order, so no second barrier ("cross reads retired") is needed; the transforms run in the tile.
+        // (written out, not cross_put / cross_take: through the helpers hipcc allocates this kernel's registers differently)
         {
             c64* slot_mine = reinterpret_cast<c64*>(ring + wv * 8192);
             const c64* slot_theirs = reinterpret_cast<const c64*>(ring + (wv ^ 1) * 8192);
@@ -370,7 +345,7 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
                     for (int i = 0; i < 4; i++) WW[q][i] = slot_theirs[(q * 4 + i) * 64 + lane];
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the slot's contents are in registers
-            STAMPT(6);
+            stamps.mark(6);
             young_prio<1>(is_young);
         }
         // the parked accumulator half has landed BEFORE the next key rows are requested: vmcnt counts in order, a wait for
@@ -386,9 +361,9 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
 #pragma unroll
             for (int k = 0; k < 8; k++) lds_dma_piece(src + k * 1024, lane16, dst + k * 1024);
         }
-        STAMPT(7);
+        stamps.mark(7);
         SPF_TRACE_PAIR<-1, XP>(WW[0], WW[1], mine, tab, lane);
-        STAMPT(8);
+        stamps.mark(8);
         {
             uint64_t t[16];
             untwist_to_torus_bits<true>(WW[0], twist, t);
@@ -398,21 +373,15 @@ __device__ __forceinline__ void cbs_trace_body(const TraceArgs& a, char* smem)
 #pragma unroll
             for (int e = 0; e < 16; e++) accb[e] -= t[e];
         }
-        STAMPT(9);
+        stamps.mark(9);
     }
-#ifdef SPF_STAMPS
-    if (a.stamps && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) a.stamps[((size_t)blockIdx.x * 8 + wv) * 16 + i] = st_acc[i];
-    }
-#endif
-#undef STAMPT
+    stamps.flush(a.stamps, (size_t)blockIdx.x * 8 + wv, lane);
     if (!owns_output) return;
     uint64_t* out = a.glev_out + (size_t)unit * 2 * kN;
 #pragma unroll
     for (int e = 0; e < 16; e++) {
-        out[coef2(e)] = accm[e];
-        out[kN + coef2(e)] = accb[e];
+        out[coef2(e, lane, w)] = accm[e];
+        out[kN + coef2(e, lane, w)] = accb[e];
     }
 }
 
@@ -464,7 +433,6 @@ __device__ __forceinline__ void scheme_switch_body(const SchemeSwitchArgs& a, ch
     const bool owns_output = unit_raw < a.units;
     const uint32_t unit = owns_output ? unit_raw : a.units - 1;
     const uint32_t ct = unit / a.cbs_count, lvl = unit % a.cbs_count;
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
     const uint64_t* x = a.glev + (size_t)unit * 2 * kN;
     // GGSW-FFT [row][level][poly][bin]; this wave's bins start at 256*w + lane
     c64* out_row0 = a.ggsw_out + (size_t)ct * (2 * a.cbs_count * 2 * kHalf) + (size_t)(lvl * 2) * kHalf + 256 * w + lane;
@@ -495,17 +463,7 @@ __device__ __forceinline__ void scheme_switch_body(const SchemeSwitchArgs& a, ch
     // forward transform pair with the radix-2 stage across the two waves; leaves this wave's bins in VV
     auto forward_pair = [&](c64 (&VV)[2][8]) {
         SPF_SS_PAIR<+1, XP>(VV[0], VV[1], mine, tab, lane);
-        if constexpr (w == 0) {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][4 + i];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; j++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][i];
-        }
+        cross_put<w>(mine, lane, VV);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // my share of the key rows has landed
         __syncthreads();
         if constexpr (w == 0) {
@@ -541,8 +499,8 @@ __device__ __forceinline__ void scheme_switch_body(const SchemeSwitchArgs& a, ch
         for (int p = 0; p < 2; p++)
 #pragma unroll
             for (int n1 = 0; n1 < 8; n1++) {
-                const double re = (double)(long long)x[p * kN + coef2(n1)];
-                const double im = (double)(long long)x[p * kN + coef2(8 + n1)];
+                const double re = (double)(long long)x[p * kN + coef2(n1, lane, w)];
+                const double im = (double)(long long)x[p * kN + coef2(8 + n1, lane, w)];
                 VV[p][n1] = cmul_nf({re, im}, twist[64 * n1]);
             }
         forward_pair(VV);
@@ -556,7 +514,7 @@ __device__ __forceinline__ void scheme_switch_body(const SchemeSwitchArgs& a, ch
     }
     uint64_t st[16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) st[e] = radix_round_state<L, LOGB>(x[coef2(e)]);
+    for (int e = 0; e < 16; e++) st[e] = radix_round_state<L, LOGB>(x[coef2(e, lane, w)]);
 #pragma unroll 1
     for (int c = 0; c < PAIRS; c++) {
         const bool single = 2 * c + 1 >= L;
@@ -591,12 +549,10 @@ __device__ __forceinline__ void scheme_switch_body(const SchemeSwitchArgs& a, ch
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     const int r = (grp * 2 + i) & 7, q = grp >> 2;
-                    const c64 k = kb[grp % 2][i];
                     const bool zero = c == 0 && j == 0 && q == 1; // row 0's second polynomial starts from zero
-                    double re = __builtin_fma(k.re, VV[j][r].re, zero ? 0.0 : prod[q][r].re);
-                    double im = __builtin_fma(k.re, VV[j][r].im, zero ? 0.0 : prod[q][r].im);
-                    prod[q][r].re = __builtin_fma(-k.im, VV[j][r].im, re);
-                    prod[q][r].im = __builtin_fma(k.im, VV[j][r].re, im);
+                    c64 acc = {zero ? 0.0 : prod[q][r].re, zero ? 0.0 : prod[q][r].im};
+                    cmad(acc, kb[grp % 2][i], VV[j][r]);
+                    prod[q][r] = acc;
                 }
             }
         }

@@ -962,4 +962,90 @@ __device__ __forceinline__ c64 twisted_digit(uint32_t packed_re, uint32_t packed
     return cmul_nf({(double)dre, (double)dim}, tw);
 }
 
+// ---- steps the two-waves-per-ciphertext kernels share (blind_rotate2p / cmux / cbs_trace / scheme_switch) ----
+// Wave w of a pair owns the complex samples of parity w.  Parity is a template parameter wherever it selects registers: every
+// choice is static, as in the bodies themselves (profiles/r12_shared_kernel_pieces.md: same code object with and without these).
+
+// polynomial coefficient behind register e of the wave of parity w: c = half*1024 + 128*n1 + 2*lane + w, e = 8*half + n1
+__device__ __forceinline__ int coef2(int e, int lane, int w) { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; }
+
+// acc += k * x of the frequency-domain multiply-accumulate (complex_mad, AVX-512 order): four FMAs in this association
+__device__ __forceinline__ void cmad(c64& acc, c64 k, c64 x)
+{
+    double re = __builtin_fma(k.re, x.re, acc.re);
+    double im = __builtin_fma(k.re, x.im, acc.im);
+    acc.re = __builtin_fma(-k.im, x.im, re);
+    acc.im = __builtin_fma(k.im, x.re, im);
+}
+
+// The radix-2 stage across the two waves of a pair: wave 0 keeps registers 0..3 of a spectrum and hands over 4..7, wave 1 the
+// other way round.  cross_put writes the half this wave does not keep into `image` (its own tile half or ring slot: 4 KiB
+// per spectrum, value i of spectrum j at [(4j + i) * 64 + lane]); cross_take reads the partner's image into those registers.
+template <int W> __device__ __forceinline__ void cross_put(char* image, int lane, const c64 (&x)[8])
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(image)[i * 64 + lane] = x[W == 0 ? 4 + i : i];
+}
+template <int W> __device__ __forceinline__ void cross_put(char* image, int lane, const c64 (&x)[2][8])
+{
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(image)[(j * 4 + i) * 64 + lane] = x[j][W == 0 ? 4 + i : i];
+}
+template <int W> __device__ __forceinline__ void cross_take(const char* image, int lane, c64 (&x)[8])
+{
+#pragma unroll
+    for (int i = 0; i < 4; i++) x[W == 0 ? 4 + i : i] = reinterpret_cast<const c64*>(image)[i * 64 + lane];
+}
+template <int W> __device__ __forceinline__ void cross_take(const char* image, int lane, c64 (&x)[2][8])
+{
+#pragma unroll
+    for (int j = 0; j < 2; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) x[j][W == 0 ? 4 + i : i] = reinterpret_cast<const c64*>(image)[(j * 4 + i) * 64 + lane];
+}
+
+// Ahead of the inverse transform pair: Ep = X[i] + X[i+4] (registers 0..3, kept by wave 0) and Op = (X[i] - X[i+4]) conj(W^k)
+// (registers 4..7, kept by wave 1) of both product spectra; wc = this lane's cross twiddles, W1024^{lane + 64 (4w + i)} at wc[64 i]
+__device__ __forceinline__ void inverse_split(const c64 (&prod)[2][8], const c64* wc, c64 (&WW)[2][8])
+{
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const c64 wci = wc[64 * i];
+            WW[q][i] = cadd(prod[q][i], prod[q][i + 4]);
+            WW[q][4 + i] = cmul_tw<-1>(csub(prod[q][i], prod[q][i + 4]), wci);
+        }
+}
+
+// Per-phase wall cycles of one wave, for the diagnostic build (-DSPF_STAMPS; s_memtime drains lgkmcnt: ~5 % overhead); empty
+// otherwise.  mark(i) adds the time since the previous mark to slot i; flush writes the N sums to the wave's 16 words of
+// `stamps` (null: nothing), where the host's stamp_report finds them.
+template <int N> struct PhaseStamps {
+    static_assert(N <= 16, "16 words per wave");
+#ifdef SPF_STAMPS
+    uint64_t acc[N], prev;
+    __device__ __forceinline__ PhaseStamps() : acc{}, prev(__builtin_amdgcn_s_memtime()) {}
+    __device__ __forceinline__ void mark(int i)
+    {
+        const uint64_t t = __builtin_amdgcn_s_memtime();
+        acc[i] += t - prev;
+        prev = t;
+    }
+    __device__ __forceinline__ void flush(uint64_t* stamps, size_t wave_index, int lane) const
+    {
+        if (stamps && lane == 0) {
+#pragma unroll
+            for (int i = 0; i < N; i++) stamps[wave_index * 16 + i] = acc[i];
+        }
+    }
+#else
+    __device__ __forceinline__ PhaseStamps() {}
+    __device__ __forceinline__ void mark(int) {}
+    __device__ __forceinline__ void flush(uint64_t*, size_t, int) const {}
+#endif
+};
+
 } // namespace spf

@@ -244,6 +244,63 @@ struct TimedScope {
     }
 };
 
+#ifdef SPF_STAMPS
+// Diagnostic build (-DSPF_STAMPS): one launch with a zeroed stamp buffer — 16 words per wave, slot i = the cycles the wave spent in
+// phase i (PhaseStamps, spf_device.hpp) — then one line per phase on stderr: the median over the waves, divided by `per` (the steps
+// of a launch); with `share` the phase's part of the total, with `halves` the medians of the older (0-3) and of the younger (4-7)
+// waves of the eight-wave workgroups as well.  The caller prints the heading; `name_fmt` is a line's prefix and name column,
+// `total_fmt` the closing line.  `launch(stamps)` launches on `s` with the buffer and returns its status.
+template <class LAUNCH>
+static spf_status stamp_report(spf_ctx* c, hipStream_t s, size_t waves, const char* const* names, size_t n_names, double per,
+                               bool share, bool halves, const char* name_fmt, const char* total_fmt, LAUNCH launch)
+{
+    uint64_t* d_st = nullptr;
+    HIPCHK(c, hipMalloc(&d_st, waves * 16 * 8));
+    HIPCHK(c, hipMemsetAsync(d_st, 0, waves * 16 * 8, s));
+    spf_status st = launch(d_st);
+    if (st != SPF_OK) return st;
+    HIPCHK(c, hipStreamSynchronize(s));
+    std::vector<uint64_t> h(waves * 16);
+    HIPCHK(c, hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(d_st);
+    auto median = [&](size_t i, int half) { // half 0 / 1: the older / younger waves of each workgroup, -1: all
+        std::vector<uint64_t> v;
+        for (size_t wv = 0; wv < waves; wv++)
+            if (half < 0 || (int)(wv % 8) / 4 == half) v.push_back(h[wv * 16 + i]);
+        std::sort(v.begin(), v.end());
+        return (double)v[v.size() / 2] / per;
+    };
+    double total = 0;
+    for (size_t i = 0; i < n_names; i++) total += median(i, -1);
+    for (size_t i = 0; i < n_names; i++) {
+        fprintf(stderr, name_fmt, names[i]);
+        fprintf(stderr, " %8.0f", median(i, -1));
+        if (share) fprintf(stderr, " %5.1f%%", 100.0 * median(i, -1) / total);
+        if (halves) fprintf(stderr, " | %8.0f | %8.0f", median(i, 0), median(i, 1));
+        fprintf(stderr, "\n");
+    }
+    fprintf(stderr, total_fmt, total);
+    return SPF_OK;
+}
+// what the slots of each kernel hold (the stamps.mark(i) of its body)
+static const char* const kStampNames2p[12] = {"stage+rendezvous", "gather+decomp+twist", "rendezvous(gathered) + key-row wait", "fwd transform pair",
+    "cross write+key barrier", "cross read+combine", "MAD x2", "ring barrier", "inverse cross exchange",
+    "inv transform pair", "untwist+convert+acc", "step head"};
+static const char* const kStampNames8[12] = {"step head+stage", "barrier A (j=1: A+F)", "gather+decomp+post+F+twist", "fwd transform", "cross write+barrier B",
+    "cross read+combine+publish", "barrier C", "MAD+inverse split+post", "barrier D", "inbox read", "inv transform", "untwist+convert+acc"};
+static const char* const kStampNamesTrace[10] = {"round head: stage, gather, digits 0-1 (+park)", "digits + twist x3", "fwd transform pair x3",
+    "cross write + key barrier x3", "cross read + combine + MAD x3", "ring barrier x3", "inverse cross exchange",
+    "next rows requested", "inv transform pair", "untwist + convert + acc"};
+static const char* const kStampNamesCmux4[9] = {"entry: pointers, loads issued, table copy", "barrier (table in place)", "twist tables to registers",
+    "decompose + 2 x (transform pair, cross)", "key1 issue + spectra out + 2 barriers", "8-row accumulation chain",
+    "inverse cross (3 barriers)", "inverse transform + untwist + store issue", "store drain"};
+static const char* const kStampNamesCmux[16] = {"entry: operand words in, decomposition", "barrier (table in place)", "digit + twist x8",
+    "hand-over (cross data consumed) x7", "forward transform x8", "cross write + hand-over x8", "cross read + combine x8",
+    "wait for the round's selector rows x8", "MAD + next rows requested x8", "inverse cross exchange (3 hand-overs)",
+    "inverse transform pair", "untwist + d0 + store issue", "entry: kernel arguments + pointer table", "entry: 64 operand loads issued",
+    "(unused)", "(unused)"};
+#endif
+
 GenericShape generic_shape(const spf_ctx* c)
 {
     GenericShape g{};
@@ -302,71 +359,34 @@ spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64
     const bool pair2 = !quad && B <= 2 * n_cu && per_wg_hint <= 2;
     const size_t per_wg = quad ? 1 : (pair2 ? 2 : 4);
     dim3 grid((unsigned)((B + per_wg - 1) / per_wg)), block(pair2 ? 256 : 512);
-    TimedScope ts(c, s, T_PBS);
-    {
+    // one launch of the shape's kernel (`stamps`: the diagnostic build's phase buffer, otherwise null)
+    auto launch = [&](uint64_t* stamps) -> spf_status {
+        a.stamps = stamps;
+        TimedScope ts(c, s, T_PBS);
         spf_status st = ts.begin();
         if (st != SPF_OK) return st;
-    }
-#ifdef SPF_STAMPS
-    static uint64_t* d_stamps = nullptr;
-    const size_t stamp_waves = 8;
-    const size_t n_stamp = (size_t)grid.x * stamp_waves * 16;
-    if (!pair2) {
-        if (d_stamps) (void)hipFree(d_stamps);
-        HIPCHK(c, hipMalloc(&d_stamps, n_stamp * 8));
-        HIPCHK(c, hipMemsetAsync(d_stamps, 0, n_stamp * 8, s));
-        a.stamps = d_stamps;
-    }
-#endif
 #define SPF_STR2(x) #x
 #define SPF_STR(x) SPF_STR2(x)
 #define SPF_LAUNCH(NAME, KERNEL, LDS) do { c->last_pbs_kernel = NAME; hipLaunchKernelGGL(KERNEL, grid, block, LDS, s, a); } while (0)
-    // log_v >= 1 makes every rotation amount even: the kernels then skip the hand-overs around the rotation gather (",even")
-    if (quad && log_v == 0) SPF_LAUNCH("blind_rotate8_kernel<2,16>", (blind_rotate8_kernel<2, 16, 1>), kBlindRotate8Lds);
-    else if (quad) SPF_LAUNCH("blind_rotate8_kernel<2,16,even>", (blind_rotate8_kernel<2, 16, 0>), kBlindRotate8Lds);
-    else if (pair2 && log_v == 0) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ">", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 1>), kBlindRotate2p2Lds);
-    else if (pair2) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ",even>", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 0>), kBlindRotate2p2Lds);
-    else if (log_v == 0) SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT_MIX) ">", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT_MIX, 1>), kBlindRotate2pLds);
-    else SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT) ",even>", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT, 0>), kBlindRotate2pLds);
+        // log_v >= 1 makes every rotation amount even: the kernels then skip the hand-overs around the rotation gather (",even")
+        if (quad && log_v == 0) SPF_LAUNCH("blind_rotate8_kernel<2,16>", (blind_rotate8_kernel<2, 16, 1>), kBlindRotate8Lds);
+        else if (quad) SPF_LAUNCH("blind_rotate8_kernel<2,16,even>", (blind_rotate8_kernel<2, 16, 0>), kBlindRotate8Lds);
+        else if (pair2 && log_v == 0) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ">", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 1>), kBlindRotate2p2Lds);
+        else if (pair2) SPF_LAUNCH("blind_rotate2p2_kernel<2,16," SPF_STR(SPF_BR2_OPT) ",even>", (blind_rotate2p2_kernel<2, 16, SPF_BR2_OPT, 0>), kBlindRotate2p2Lds);
+        else if (log_v == 0) SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT_MIX) ">", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT_MIX, 1>), kBlindRotate2pLds);
+        else SPF_LAUNCH("blind_rotate2p_kernel<2,16," SPF_STR(SPF_BR_OPT) ",even>", (blind_rotate2p_kernel<2, 16, SPF_BR_OPT, 0>), kBlindRotate2pLds);
 #undef SPF_LAUNCH
-    HIPCHK(c, hipGetLastError());
-    {
-        spf_status st = ts.end();
-        if (st != SPF_OK) return st;
-    }
+        HIPCHK(c, hipGetLastError());
+        return ts.end();
+    };
 #ifdef SPF_STAMPS
-    if (a.stamps) { // diagnostic build: median over waves of the per-phase cycle sums, per CMUX step
-        HIPCHK(c, hipStreamSynchronize(s));
-        std::vector<uint64_t> h(n_stamp);
-        HIPCHK(c, hipMemcpy(h.data(), a.stamps, n_stamp * 8, hipMemcpyDeviceToHost));
-        static const char* names[12] = {"stage+rendezvous", "gather+decomp+twist", "rendezvous(gathered) + key-row wait", "fwd transform pair",
-            "cross write+key barrier", "cross read+combine", "MAD x2", "ring barrier", "inverse cross exchange",
-            "inv transform pair", "untwist+convert+acc", "step head"};
-        static const char* names8[12] = {"step head+stage", "barrier A (j=1: A+F)", "gather+decomp+post+F+twist", "fwd transform", "cross write+barrier B",
-            "cross read+combine+publish", "barrier C", "MAD+inverse split+post", "barrier D", "inbox read", "inv transform", "untwist+convert+acc"};
-        double total = 0;
-        std::vector<double> med(12), med_old(12), med_young(12);
-        for (int i = 0; i < 12; i++) {
-            std::vector<uint64_t> v, vo, vy;
-            for (size_t wv = 0; wv < (size_t)grid.x * stamp_waves; wv++) {
-                v.push_back(h[wv * 16 + i]);
-                ((wv % stamp_waves) < stamp_waves / 2 ? vo : vy).push_back(h[wv * 16 + i]);
-            }
-            std::sort(v.begin(), v.end());
-            std::sort(vo.begin(), vo.end());
-            std::sort(vy.begin(), vy.end());
-            med[i] = (double)v[v.size() / 2] / a.n;
-            med_old[i] = (double)vo[vo.size() / 2] / a.n;
-            med_young[i] = (double)vy[vy.size() / 2] / a.n;
-            total += med[i];
-        }
-        fprintf(stderr, "[stamps] per CMUX step, median over %zu waves (cycles, share | waves 0-3 | waves 4-7)\n", (size_t)grid.x * stamp_waves);
-        for (int i = 0; i < 12; i++)
-            fprintf(stderr, "[stamps] %-30s %8.0f %5.1f%% | %8.0f | %8.0f\n", (quad ? names8 : names)[i], med[i], 100.0 * med[i] / total, med_old[i], med_young[i]);
-        fprintf(stderr, "[stamps] %-26s %8.0f\n", "total", total);
+    if (!pair2) { // every launch of the eight-wave workgroups reports, per CMUX step
+        const size_t waves = (size_t)grid.x * 8;
+        fprintf(stderr, "[stamps] per CMUX step, median over %zu waves (cycles, share | waves 0-3 | waves 4-7)\n", waves);
+        return stamp_report(c, s, waves, quad ? kStampNames8 : kStampNames2p, 12, a.n, true, true, "[stamps] %-30s", "[stamps] total                      %8.0f\n", launch);
     }
 #endif
-    return SPF_OK;
+    return launch(nullptr);
 }
 
 // the int8-MFMA formulation applies when digits fit int8, K is a multiple of the MFMA depth and
@@ -950,45 +970,25 @@ static spf_status launch_trace(spf_ctx* c, hipStream_t s, size_t B, const uint64
     a.units = (uint32_t)(B * c->prm.cbs_radix_count); a.cbs_count = c->prm.cbs_radix_count;
     a.cbs_radix_log = c->prm.cbs_radix_log;
     dim3 grid((a.units + kWavesPerBlock - 1) / kWavesPerBlock), block(512);
-    TimedScope ts(c, s, T_TRACE);
-    spf_status st = ts.begin();
-    if (st != SPF_OK) return st;
+    auto launch = [&](uint64_t* stamps) -> spf_status { // (`stamps`: the diagnostic build's phase buffer, otherwise null)
+        a.stamps = stamps;
+        TimedScope ts(c, s, T_TRACE);
+        spf_status st = ts.begin();
+        if (st != SPF_OK) return st;
+        hipLaunchKernelGGL((cbs_trace_kernel<6, 7>), grid, block, kTraceLds, s, a);
+        HIPCHK(c, hipGetLastError());
+        return ts.end();
+    };
 #ifdef SPF_STAMPS
     static int reported_t = 0;
-    if (reported_t < 1 && a.units >= 4096) { // diagnostic build: per-phase cycles per round, median over waves
-        const size_t waves = (size_t)grid.x * 8;
-        uint64_t* d_st = nullptr;
-        HIPCHK(c, hipMalloc(&d_st, waves * 16 * 8));
-        HIPCHK(c, hipMemsetAsync(d_st, 0, waves * 16 * 8, s));
-        a.stamps = d_st;
-        hipLaunchKernelGGL((cbs_trace_kernel<6, 7>), grid, block, kTraceLds, s, a);
-        HIPCHK(c, hipStreamSynchronize(s));
-        std::vector<uint64_t> h(waves * 16);
-        HIPCHK(c, hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost));
-        (void)hipFree(d_st);
-        static const char* nm[10] = {"round head: stage, gather, digits 0-1 (+park)", "digits + twist x3", "fwd transform pair x3",
-            "cross write + key barrier x3", "cross read + combine + MAD x3", "ring barrier x3", "inverse cross exchange",
-            "next rows requested", "inv transform pair", "untwist + convert + acc"};
-        fprintf(stderr, "[trace stamps] per automorphism round, median over %zu waves (cycles | waves 0-3 | waves 4-7)\n", waves);
-        double tot = 0;
-        for (int i = 0; i < 10; i++) {
-            std::vector<uint64_t> v, vo, vy;
-            for (size_t wv = 0; wv < waves; wv++) {
-                v.push_back(h[wv * 16 + i]);
-                ((wv % 8) < 4 ? vo : vy).push_back(h[wv * 16 + i]);
-            }
-            std::sort(v.begin(), v.end()); std::sort(vo.begin(), vo.end()); std::sort(vy.begin(), vy.end());
-            fprintf(stderr, "[trace stamps] %-48s %8.0f | %8.0f | %8.0f\n", nm[i], v[v.size() / 2] / 11.0, vo[vo.size() / 2] / 11.0, vy[vy.size() / 2] / 11.0);
-            tot += v[v.size() / 2] / 11.0;
-        }
-        fprintf(stderr, "[trace stamps] total %.0f\n", tot);
+    if (reported_t < 1 && a.units >= 4096) { // the first large launch reports, per automorphism round
         reported_t++;
-        return ts.end();
+        const size_t waves = (size_t)grid.x * 8;
+        fprintf(stderr, "[trace stamps] per automorphism round, median over %zu waves (cycles | waves 0-3 | waves 4-7)\n", waves);
+        return stamp_report(c, s, waves, kStampNamesTrace, 10, 11.0, false, true, "[trace stamps] %-48s", "[trace stamps] total %.0f\n", launch);
     }
 #endif
-    hipLaunchKernelGGL((cbs_trace_kernel<6, 7>), grid, block, kTraceLds, s, a);
-    HIPCHK(c, hipGetLastError());
-    return ts.end();
+    return launch(nullptr);
 }
 
 static spf_status launch_scheme_switch(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_glev, double* d_ggsw)
@@ -1248,32 +1248,17 @@ static void launch_cmux_args(spf_ctx* c, hipStream_t s, const CmuxArgs& a)
     if (a.B <= (uint32_t)c->n_cu) {
         c->last_cmux_kernel = "cmux4_kernel<4,4>";
 #ifdef SPF_STAMPS
-        // diagnostic build: per-phase cycles of the first few cmux4 launches (median over waves)
         static int reported = 0;
-        static uint64_t* d_st = nullptr;
-        if (reported < 6 && a.B <= 256) {
-            if (!d_st) (void)hipMalloc(&d_st, 256 * 4 * 16 * 8);
-            (void)hipMemsetAsync(d_st, 0, 256 * 4 * 16 * 8, s);
-            CmuxArgs b = a;
-            b.stamps = d_st;
-            hipLaunchKernelGGL((cmux4_kernel<4, 4>), dim3(a.B), dim3(256), kCmux4Lds, s, b);
-            (void)hipStreamSynchronize(s);
-            std::vector<uint64_t> h((size_t)a.B * 4 * 16);
-            (void)hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost);
-            static const char* nm[9] = {"entry: pointers, loads issued, table copy", "barrier (table in place)", "twist tables to registers",
-                "decompose + 2 x (transform pair, cross)", "key1 issue + spectra out + 2 barriers", "8-row accumulation chain",
-                "inverse cross (3 barriers)", "inverse transform + untwist + store issue", "store drain"};
-            fprintf(stderr, "[cmux4 stamps] B=%u\n", a.B);
-            double tot = 0;
-            for (int i = 0; i < 9; i++) {
-                std::vector<uint64_t> v;
-                for (size_t wv = 0; wv < (size_t)a.B * 4; wv++) v.push_back(h[wv * 16 + i]);
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, "[cmux4 stamps] %-44s %8llu\n", nm[i], (unsigned long long)v[v.size() / 2]);
-                tot += (double)v[v.size() / 2];
-            }
-            fprintf(stderr, "[cmux4 stamps] total %.0f cycles\n", tot);
+        if (reported < 6 && a.B <= 256) { // the first few cmux4 launches report
             reported++;
+            fprintf(stderr, "[cmux4 stamps] B=%u\n", a.B);
+            (void)stamp_report(c, s, (size_t)a.B * 4, kStampNamesCmux4, 9, 1.0, false, false, "[cmux4 stamps] %-44s", "[cmux4 stamps] total %.0f cycles\n",
+                               [&](uint64_t* stamps) {
+                                   CmuxArgs b = a;
+                                   b.stamps = stamps;
+                                   hipLaunchKernelGGL((cmux4_kernel<4, 4>), dim3(a.B), dim3(256), kCmux4Lds, s, b);
+                                   return SPF_OK;
+                               });
             return;
         }
 #endif
@@ -1283,36 +1268,18 @@ static void launch_cmux_args(spf_ctx* c, hipStream_t s, const CmuxArgs& a)
         // the two halves drift apart, so one half's selector requests fly while the other computes, and a barrier
         // ties four waves instead of eight (0.329 -> 0.316 ms per 4096 gates against four gates per 512-thread workgroup)
 #ifdef SPF_STAMPS
-        // diagnostic build: per-phase cycles of the first few streaming-shape launches (median over waves)
         static int reported_s = 0;
-        if (reported_s < 2 && a.B >= 512) {
-            const size_t waves = (size_t)((a.B + 1) / 2) * 4;
-            uint64_t* d_st = nullptr;
-            (void)hipMalloc(&d_st, waves * 16 * 8);
-            (void)hipMemsetAsync(d_st, 0, waves * 16 * 8, s);
-            CmuxArgs b = a;
-            b.stamps = d_st;
-            hipLaunchKernelGGL((cmux_kernel<4, 4, 2>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, b);
-            (void)hipStreamSynchronize(s);
-            std::vector<uint64_t> h(waves * 16);
-            (void)hipMemcpy(h.data(), d_st, h.size() * 8, hipMemcpyDeviceToHost);
-            (void)hipFree(d_st);
-            static const char* nm[16] = {"entry: operand words in, decomposition", "barrier (table in place)", "digit + twist x8",
-                "hand-over (cross data consumed) x7", "forward transform x8", "cross write + hand-over x8", "cross read + combine x8",
-                "wait for the round's selector rows x8", "MAD + next rows requested x8", "inverse cross exchange (3 hand-overs)",
-                "inverse transform pair", "untwist + d0 + store issue", "entry: kernel arguments + pointer table", "entry: 64 operand loads issued",
-                "(unused)", "(unused)"};
-            fprintf(stderr, "[cmux stamps] B=%u (cycles per gate, median over %zu waves)\n", a.B, waves);
-            double tot = 0;
-            for (int i = 0; i < 16; i++) {
-                std::vector<uint64_t> v;
-                for (size_t wv = 0; wv < waves; wv++) v.push_back(h[wv * 16 + i]);
-                std::sort(v.begin(), v.end());
-                fprintf(stderr, "[cmux stamps] %-52s %8llu\n", nm[i], (unsigned long long)v[v.size() / 2]);
-                tot += (double)v[v.size() / 2];
-            }
-            fprintf(stderr, "[cmux stamps] total %.0f cycles\n", tot);
+        if (reported_s < 2 && a.B >= 512) { // the first few streaming-shape launches report
             reported_s++;
+            const size_t waves = (size_t)((a.B + 1) / 2) * 4;
+            fprintf(stderr, "[cmux stamps] B=%u (cycles per gate, median over %zu waves)\n", a.B, waves);
+            (void)stamp_report(c, s, waves, kStampNamesCmux, 16, 1.0, false, false, "[cmux stamps] %-52s", "[cmux stamps] total %.0f cycles\n",
+                               [&](uint64_t* stamps) {
+                                   CmuxArgs b = a;
+                                   b.stamps = stamps;
+                                   hipLaunchKernelGGL((cmux_kernel<4, 4, 2>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, b);
+                                   return SPF_OK;
+                               });
             return;
         }
 #endif

@@ -195,14 +195,7 @@ template <int L, int LOGB, int OPT, int W, int CTS = 4, int MIX = 1>
 __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, char* smem)
 {
     constexpr int XP = (OPT & 1) ? 1 : ((OPT & 2) ? 2 : 0);
-#ifdef SPF_STAMPS
-    // per-phase wall cycles of this wave (diagnostic build; s_memtime drains lgkmcnt: ~5 % overhead)
-    uint64_t st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMP(i) do { uint64_t t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMP(i) do { } while (0)
-#endif
+    PhaseStamps<12> stamps; // per-phase wall cycles of this wave (diagnostic build)
     static_assert(L == 2 && LOGB == 16, "two 16-bit digits, taken straight from the rounded top word and processed as a pair");
     constexpr int NT = 128 * CTS; // CTS ciphertexts per workgroup, two waves each
     c64* tab = reinterpret_cast<c64*>(smem);
@@ -244,8 +237,6 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
     };
     ring_dma(0);
 
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
-
     uint64_t acc[2][16];
     {
         uint32_t bt = mod_switch_2n(lwe[a.n] + a.body_rotate, a.log_chi, a.log_v);
@@ -253,7 +244,7 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
         for (int p = 0; p < 2; p++)
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                uint32_t idx = (uint32_t)coef2(e) + bt;
+                uint32_t idx = (uint32_t)coef2(e, lane, w) + bt;
                 uint64_t v = lut[p * kN + (idx & (kN - 1))];
                 acc[p][e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (acc[][] holds -accumulator throughout)
             }
@@ -304,7 +295,7 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
     for (uint32_t step = 0; step < a.n; step++) {
         const uint32_t at = mod_switch_2n(a_next, a.log_chi, a.log_v);
         a_next = lwe[step + 1];
-        STAMP(11);
+        stamps.mark(11);
 
         // bins lane + 64 (4w + i) + 512 s at index i + 4 s; starts at zero, which the first row's FMAs
         // take as a literal (no zeroed registers live across polynomial 0's transforms)
@@ -320,7 +311,7 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
             // With log_v >= 1 (MIX = 0: the modulus switch clears the low log_v bits — the circuit bootstrap uses log_v = 2)
             // the two gather hand-overs of a polynomial are not needed: four of the ten barriers of a step go.
             rendezvous_if_mixing(); // both parities staged
-            STAMP(0);
+            stamps.mark(0);
             if (p == 0) SPF_PRIO_POINT(2); else SPF_PRIO_POINT(9);
             uint32_t dig[16];
             {
@@ -376,10 +367,10 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                     VV[1][n1] = twisted_digit_top32(dig[n1], dig[8 + n1], 1, tw);
                 }
             }
-            STAMP(1);
+            stamps.mark(1);
             if (p == 0) SPF_PRIO_POINT(3);
             rendezvous_if_mixing(); // partner is done gathering from my region
-            STAMP(2);
+            stamps.mark(2);
             // the ring is free since the barrier behind the last MADs: bring in polynomial 1's rows (those
             // of polynomial 0 were requested ahead of the previous step's inverse transforms)
             // (r03c: polynomial 0: the older waves lead through the forward transforms; polynomial 1: the younger)
@@ -392,30 +383,20 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                 if (p == 0) SPF_PAIR_E0<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(17); });
                 else SPF_PAIR_E1<+1, XP>(VV[0], VV[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(18); });
             }
-            STAMP(3);
+            stamps.mark(3);
             if (p == 0) SPF_PRIO_POINT(5);
             // radix-2 stage across the two waves, both digits in one exchange: wave 0 finishes bins with
             // d < 4 and sends registers 4..7, wave 1 the other way round
-            if constexpr (w == 0) {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][4 + i];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(j * 4 + i) * 64 + lane] = VV[j][i];
-            }
+            cross_put<w>(mine, lane, VV);
             if (p == 1) SPF_PRIO_POINT(11);
 #ifdef SPF_STAMPS
-            STAMP(4);
+            stamps.mark(4);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            STAMP(2); // diagnostic: the wait for the key rows alone (slot 2 is otherwise empty for even rotations)
+            stamps.mark(2); // diagnostic: the wait for the key rows alone (slot 2 is otherwise empty for even rotations)
 #endif
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // my share of the key rows has landed
             __syncthreads();
-            STAMP(4);
+            stamps.mark(4);
             if (p == 0) SPF_PRIO_POINT(6); else SPF_PRIO_POINT(12);
             // X[i] = E[i] + W^k O[i], X[i+4] = E[i] - W^k O[i]: wave 0 holds E and receives O, wave 1 the reverse
             // (the eight cross values and four cross twiddles requested at once behind the barrier lost: 38.47 ms per 4096 against 38.23, r05;
@@ -442,7 +423,7 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                         VV[j][i + 4] = csub(Ei, t);
                     }
             }
-            STAMP(5);
+            stamps.mark(5);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const c64* row = reinterpret_cast<const c64*>(bskring + (1 - j) * kBskSlotBytes) + 256 * w + lane;
@@ -465,65 +446,59 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
                         const int r = (grp * 2 + i) & 7, q = grp >> 2;
-                        const c64 k = kb[grp % KD][i];
                         const bool first = p == 0 && j == 0;
-                        double re = __builtin_fma(k.re, VV[j][r].re, first ? 0.0 : prod[q][r].re);
-                        double im = __builtin_fma(k.re, VV[j][r].im, first ? 0.0 : prod[q][r].im);
-                        prod[q][r].re = __builtin_fma(-k.im, VV[j][r].im, re);
-                        prod[q][r].im = __builtin_fma(k.im, VV[j][r].re, im);
+                        c64 acc = {first ? 0.0 : prod[q][r].re, first ? 0.0 : prod[q][r].im};
+                        cmad(acc, kb[grp % KD][i], VV[j][r]);
+                        prod[q][r] = acc;
                     }
                 }
             }
-            STAMP(6);
+            stamps.mark(6);
             if (p == 0) SPF_PRIO_POINT(7);
             __syncthreads(); // every wave is done with the ring and with its partner's cross data
-            STAMP(7);
+            stamps.mark(7);
             if (p == 1) SPF_PRIO_POINT(13);
         }
 
         // ---- back to the torus, both output polynomials together
         c64 WW[2][8];
+        inverse_split(prod, wc, WW);
+        // OPT bit 3: the inverse cross exchange goes through the KEY RING (free between the barrier behind the last MADs and
+        // the next refill): wave v writes its outgoing half into slot v (8 KiB), reads slot v^1 behind ONE barrier, and then
+        // refills exactly that slot with its 8 KiB of the next key chunk — the only reader of the slot is the wave that
+        // overwrites it, in program order, so the second barrier of the exchange ("cross reads retired before the
+        // image is overwritten") is not needed: the transforms run in the tile, which nobody else touches any more.
+        // Without bit 3 the halves go through the tile, as everywhere else.  (One exchange for both, on the base pointers; written
+        // out, not cross_put / cross_take: through the helpers hipcc allocates the registers of three instantiations differently.)
+        constexpr bool kCrossInRing = (OPT & 8) != 0;
+        c64* slot_mine = reinterpret_cast<c64*>(kCrossInRing ? bskring + wv * 8192 : mine);
+        const c64* slot_theirs = reinterpret_cast<const c64*>(kCrossInRing ? bskring + (wv ^ 1) * 8192 : theirs);
+        if constexpr (w == 0) {
 #pragma unroll
-        for (int q = 0; q < 2; q++)
+            for (int q = 0; q < 2; q++)
 #pragma unroll
-            for (int i = 0; i < 4; i++) {
-                const c64 wci = wc[64 * i];
-                WW[q][i] = cadd(prod[q][i], prod[q][i + 4]);                      // Ep: kept by wave 0
-                WW[q][4 + i] = cmul_tw<-1>(csub(prod[q][i], prod[q][i + 4]), wci); // Op: kept by wave 1
-            }
-        if constexpr ((OPT & 8) != 0) {
-            // The inverse cross exchange goes through the KEY RING (free between the barrier behind the last MADs and the
-            // next refill): wave v writes its outgoing half into slot v (8 KiB), reads slot v^1 behind ONE barrier, and then
-            // refills exactly that slot with its 8 KiB of the next key chunk — the only reader of the slot is the wave that
-            // overwrites it, in program order, so the second barrier of the exchange ("cross reads retired before the
-            // image is overwritten") is not needed: the transforms run in the tile, which nobody else touches any more.
-            c64* slot_mine = reinterpret_cast<c64*>(bskring + wv * 8192);
-            const c64* slot_theirs = reinterpret_cast<const c64*>(bskring + (wv ^ 1) * 8192);
-            if constexpr (w == 0) {
+                for (int i = 0; i < 4; i++) slot_mine[(q * 4 + i) * 64 + lane] = WW[q][4 + i];
+        } else {
 #pragma unroll
-                for (int q = 0; q < 2; q++)
+            for (int q = 0; q < 2; q++)
 #pragma unroll
-                    for (int i = 0; i < 4; i++) slot_mine[(q * 4 + i) * 64 + lane] = WW[q][4 + i];
-            } else {
+                for (int i = 0; i < 4; i++) slot_mine[(q * 4 + i) * 64 + lane] = WW[q][i];
+        }
+        rendezvous();
+        if constexpr (w == 0) {
 #pragma unroll
-                for (int q = 0; q < 2; q++)
+            for (int q = 0; q < 2; q++)
 #pragma unroll
-                    for (int i = 0; i < 4; i++) slot_mine[(q * 4 + i) * 64 + lane] = WW[q][i];
-            }
-            rendezvous();
-            if constexpr (w == 0) {
+                for (int i = 0; i < 4; i++) WW[q][4 + i] = slot_theirs[(q * 4 + i) * 64 + lane];
+        } else {
 #pragma unroll
-                for (int q = 0; q < 2; q++)
+            for (int q = 0; q < 2; q++)
 #pragma unroll
-                    for (int i = 0; i < 4; i++) WW[q][4 + i] = slot_theirs[(q * 4 + i) * 64 + lane];
-            } else {
-#pragma unroll
-                for (int q = 0; q < 2; q++)
-#pragma unroll
-                    for (int i = 0; i < 4; i++) WW[q][i] = slot_theirs[(q * 4 + i) * 64 + lane];
-            }
+                for (int i = 0; i < 4; i++) WW[q][i] = slot_theirs[(q * 4 + i) * 64 + lane];
+        }
+        if constexpr (kCrossInRing) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the slot's contents are in registers
-            STAMP(8);
+            stamps.mark(8);
             SPF_PRIO_POINT(14); // (r03c: the long stretch starts: the younger waves lead)
             if (chunk < total_chunks) {
                 const char* src = reinterpret_cast<const char*>(a.bsk) +
@@ -541,52 +516,23 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
                                   ring0 + 2 * CTS * 8192 + (wv * (kRest / NW) + k) * 1024);
             }
         } else {
-            if constexpr (w == 0) {
-    #pragma unroll
-                for (int q = 0; q < 2; q++)
-    #pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(q * 4 + i) * 64 + lane] = WW[q][4 + i];
-            } else {
-    #pragma unroll
-                for (int q = 0; q < 2; q++)
-    #pragma unroll
-                    for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(q * 4 + i) * 64 + lane] = WW[q][i];
-            }
-            rendezvous();
-            if constexpr (w == 0) {
-    #pragma unroll
-                for (int q = 0; q < 2; q++)
-    #pragma unroll
-                    for (int i = 0; i < 4; i++) WW[q][4 + i] = reinterpret_cast<const c64*>(theirs)[(q * 4 + i) * 64 + lane];
-            } else {
-    #pragma unroll
-                for (int q = 0; q < 2; q++)
-    #pragma unroll
-                    for (int i = 0; i < 4; i++) WW[q][i] = reinterpret_cast<const c64*>(theirs)[(q * 4 + i) * 64 + lane];
-            }
             rendezvous(); // both cross reads retired before either region is overwritten
-            STAMP(8);
+            stamps.mark(8);
             SPF_PRIO_POINT(14);
             if (chunk < total_chunks) ring_dma(chunk); // rows of the next step's polynomial 0
         }
         if constexpr (MIX) SPF_PAIR_MI<-1, XP>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
         else SPF_PAIR_EI<-1, XP>(WW[0], WW[1], mine, tab, lane, [&]() { SPF_PRIO_POINT(19); });
-        STAMP(9);
+        stamps.mark(9);
         SPF_PRIO_POINT(15);
 #pragma unroll
         for (int q = 0; q < 2; q++) {
             untwist_sub_from_negated<CTS != 4>(WW[q], twist, acc[q]);
             if (q == 0) SPF_PRIO_POINT(16);
         }
-        STAMP(10);
+        stamps.mark(10);
     }
-#ifdef SPF_STAMPS
-    if (a.stamps && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) a.stamps[((size_t)blockIdx.x * (2 * CTS) + wv) * 16 + i] = st_acc[i];
-    }
-#endif
-#undef STAMP
+    stamps.flush(a.stamps, (size_t)blockIdx.x * (2 * CTS) + wv, lane);
 #undef SPF_PRIO_POINT
 
     if (!owns_output) return;
@@ -599,11 +545,11 @@ __device__ __forceinline__ void blind_rotate2p_body(const BlindRotateArgs& a, ch
 #pragma unroll
         for (int p = 0; p < 2; p++)
 #pragma unroll
-            for (int e = 0; e < 16; e++) out[p * kN + coef2(e)] = acc[p][e];
+            for (int e = 0; e < 16; e++) out[p * kN + coef2(e, lane, w)] = acc[p][e];
     } else {
 #pragma unroll
         for (int e = 0; e < 16; e++) {
-            int c = coef2(e);
+            int c = coef2(e, lane, w);
             if (c == 0) {
                 out[0] = acc[0][e];
                 out[kN] = acc[1][e];
@@ -711,14 +657,13 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
     const uint32_t ct = blockIdx.x; // grid = B
     const uint64_t* lwe = a.lwe_in + (size_t)ct * (a.n + 1);
     const uint64_t* lut = a.lut + (size_t)ct * a.lut_stride;
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
 
     uint64_t acc[16]; // polynomial h, parity w: lives in the j = 0 wave only
     if constexpr (J == 0) {
         uint32_t bt = mod_switch_2n(lwe[a.n] + a.body_rotate, a.log_chi, a.log_v);
 #pragma unroll
         for (int e = 0; e < 16; e++) {
-            uint32_t idx = (uint32_t)coef2(e) + bt;
+            uint32_t idx = (uint32_t)coef2(e, lane, w) + bt;
             uint64_t v = lut[h * kN + (idx & (kN - 1))];
             acc[e] = ((idx >> 11) & 1) ? v : (uint64_t)0 - v; // (acc[] holds -accumulator throughout)
         }
@@ -744,13 +689,7 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
 #define SPF_KEY_PIECE(i) request_keys(std::integral_constant<int, i>{})
     SPF_KEY_PIECE(0); SPF_KEY_PIECE(1); SPF_KEY_PIECE(2); SPF_KEY_PIECE(3);
     uint64_t a_next = lwe[0];
-#ifdef SPF_STAMPS
-    uint64_t st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMP8(i) do { uint64_t t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMP8(i) do { } while (0)
-#endif
+    PhaseStamps<12> stamps;
     // One CMUX step; LAST = the final one, compiled without the requests for a next step's rows (no dead loads)
     auto cmux_step = [&](uint32_t step, auto last_c) {
         constexpr bool LAST = decltype(last_c)::value;
@@ -765,12 +704,12 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             uint64_t* stage = reinterpret_cast<uint64_t*>(spectra(w, h));
 #pragma unroll
             for (int e = 0; e < 16; e++) stage[(e >> 3) * 512 + (e & 7) * 64 + lane] = acc[e];
-            STAMP8(0);
+            stamps.mark(0);
             // A: both parities staged.  Not needed when every rotation amount is even (MIX = 0): the wave then gathers only from
             // the region it staged itself
             if constexpr (MIX) wg_barrier();
             else compiler_fence();
-            STAMP8(1);
+            stamps.mark(1);
             const uint32_t t0 = (uint32_t)(2 * lane + w) + 2 * kN - at;
             const char* src = spectra((int)(t0 & 1), h);
             uint32_t T0 = (t0 + 2048u) << 20; // bit 31 = complement of bit 11 of t0
@@ -805,28 +744,28 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
 #pragma unroll
             for (int n1 = 0; n1 < 8; n1++) V[n1] = twisted_digit<LOGB>(dig[n1], dig[8 + n1], 0, twist[n1]);
         } else {
-            STAMP8(0);
+            stamps.mark(0);
             if constexpr (MIX) wg_barrier(); // A
             c64 twist[8];
 #pragma unroll
             for (int n1 = 0; n1 < 8; n1++) twist[n1] = twist_lds[64 * n1];
             wg_barrier(); // F
-            STAMP8(1);
+            stamps.mark(1);
             const uint4 lo = digits1[lane], hi = digits1[64 + lane];
             const uint32_t pk[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
 #pragma unroll
             for (int n1 = 0; n1 < 8; n1++)
                 V[n1] = cmul_nf({(double)(((int)(pk[n1] << 16)) >> 16), (double)(((int)pk[n1]) >> 16)}, twist[n1]);
         }
-        STAMP8(2);
+        stamps.mark(2);
         fft512_single<+1, 7>(V, mine, tab, lane);
-        STAMP8(3);
+        stamps.mark(3);
         // radix-2 stage across the parities
 #pragma unroll
         for (int i = 0; i < 4; i++)
             reinterpret_cast<c64*>(mine)[i * 64 + lane] = {w == 0 ? V[4 + i].re : V[i].re, w == 0 ? V[4 + i].im : V[i].im};
         wg_barrier(); // B
-        STAMP8(4);
+        stamps.mark(4);
         {
             c64 xin[4], wc[4];
 #pragma unroll
@@ -847,10 +786,10 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
 #pragma unroll
             for (int r = 0; r < 8; r++) reinterpret_cast<c64*>(spectra(w, h))[(j * 8 + r) * 64 + lane] = X[r];
         }
-        STAMP8(5);
+        stamps.mark(5);
         wg_barrier(); // C: all four transforms of parity w are in the regions (the gathers from them ended before B)
 
-        STAMP8(6);
+        stamps.mark(6);
         // ---- multiply-accumulate, this wave's four bins of output polynomial h, chain order of glwe_ggsw_mad
         c64 P[4];
 #pragma unroll
@@ -870,14 +809,7 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
 #pragma unroll
                 for (int jj = 0; jj < 2; jj++)
 #pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const c64 k = key[p][jj][q];
-                        const c64 x = X[p][jj][q];
-                        double re = __builtin_fma(k.re, x.re, P[q].re);
-                        double im = __builtin_fma(k.re, x.im, P[q].im);
-                        P[q].re = __builtin_fma(-k.im, x.im, re);
-                        P[q].im = __builtin_fma(k.im, x.re, im);
-                    }
+                    for (int q = 0; q < 4; q++) cmad(P[q], key[p][jj][q], X[p][jj][q]);
         }
         key_next = key_base + (size_t)(step + 1) * (2 * L) * (2 * kHalf);
         if constexpr (!LAST) SPF_KEY_PIECE(0);
@@ -889,9 +821,9 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             reinterpret_cast<c64*>(image(0, h, 0))[(w * 4 + 2 * j + i) * 64 + lane] = Ep;
             reinterpret_cast<c64*>(image(1, h, 0))[(w * 4 + 2 * j + i) * 64 + lane] = Op;
         }
-        STAMP8(7);
+        stamps.mark(7);
         wg_barrier(); // D
-        STAMP8(8);
+        stamps.mark(8);
         if constexpr (!LAST) SPF_KEY_PIECE(1);
         if constexpr (J == 0) {
             c64 U[8];
@@ -899,25 +831,19 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
             for (int r = 0; r < 8; r++) U[r] = reinterpret_cast<const c64*>(mine)[r * 64 + lane];
             sched_fence();
             if constexpr (!LAST) SPF_KEY_PIECE(2);
-            STAMP8(9);
+            stamps.mark(9);
             fft512_single<-1, 7>(U, mine, tab, lane); // its exchanges follow the inbox reads in this wave's own LDS queue
-            STAMP8(10);
+            stamps.mark(10);
             if constexpr (!LAST) SPF_KEY_PIECE(3);
             untwist_sub_from_negated<true>(U, twist_lds, acc);
-            STAMP8(11);
+            stamps.mark(11);
         } else {
             if constexpr (!LAST) { SPF_KEY_PIECE(2); SPF_KEY_PIECE(3); }
         }
     };
     for (uint32_t step = 0; step + 1 < a.n; step++) cmux_step(step, std::false_type{});
     cmux_step(a.n - 1, std::true_type{});
-#ifdef SPF_STAMPS
-    if (a.stamps && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) a.stamps[((size_t)blockIdx.x * 8 + wv) * 16 + i] = st_acc[i];
-    }
-#endif
-#undef STAMP8
+    stamps.flush(a.stamps, (size_t)blockIdx.x * 8 + wv, lane);
 #undef SPF_KEY_PIECE
     if constexpr (J == 0) {
 #pragma unroll
@@ -925,11 +851,11 @@ __device__ __forceinline__ void blind_rotate8_body(const BlindRotateArgs& a, cha
         uint64_t* out = a.out + (size_t)ct * a.out_stride;
         if (!a.sample_extract) {
 #pragma unroll
-            for (int e = 0; e < 16; e++) out[h * kN + coef2(e)] = acc[e];
+            for (int e = 0; e < 16; e++) out[h * kN + coef2(e, lane, w)] = acc[e];
         } else {
 #pragma unroll
             for (int e = 0; e < 16; e++) {
-                int c = coef2(e);
+                int c = coef2(e, lane, w);
                 if (h == 0) {
                     if (c == 0) out[0] = acc[e]; else out[kN - c] = (uint64_t)0 - acc[e];
                 } else if (c == 0) {
@@ -989,13 +915,7 @@ template <int L, int LOGB, int G, int W, bool STREAM>
 __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
 {
     static_assert(L * LOGB <= 32, "packed digits need L*LOGB <= 32");
-#ifdef SPF_STAMPS
-    uint64_t st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMPS_(i) do { uint64_t t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMPS_(i) do { } while (0)
-#endif
+    PhaseStamps<16> stamps;
     c64* tab = reinterpret_cast<c64*>(smem);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1031,10 +951,9 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     }
     const gu64_cptr gd0 = global_view(d0), gd1 = global_view(d1);
     const gu64_ptr gout = global_view(out_ct);
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
 #ifdef SPF_STAMPS
     asm volatile("" :: "v"(gd0), "v"(gd1), "v"(gout)); // (diagnostic: the pointers are in)
-    STAMPS_(12);
+    stamps.mark(12);
 #endif
 
     // All 64 operand words are requested before anything else happens (left to itself hipcc keeps about fourteen loads
@@ -1049,34 +968,22 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     for (int p = 0; p < 2; p++)
 #pragma unroll
         for (int e = 0; e < 16; e++) {
-            const int c = p * kN + coef2(e);
+            const int c = p * kN + coef2(e, lane, w);
             x1[p][e] = gd1[c];
             x0[p][e] = gd0[c]; // d0 aliases d1 when it is the zero ciphertext: no branch around the load
         }
     sched_fence();
-    STAMPS_(13);
+    stamps.mark(13);
     uint32_t dig[2][16];
 #pragma unroll
     for (int p = 0; p < 2; p++)
 #pragma unroll
-        for (int e = 0; e < 16; e++) {
-            uint64_t diff = x1[p][e] - (d0_zero ? 0 : x0[p][e]); // sub_glwe_ciphertexts(diff, d_1, d_0) (fft_ops.rs:168)
-            constexpr int shift = 64 - L * LOGB;
-            uint32_t s = (uint32_t)(diff >> shift) + (uint32_t)((diff >> (shift - 1)) & 1);
-            uint32_t packed = 0;
-#pragma unroll
-            for (int j = 0; j < L; j++) {
-                uint32_t d = s & ((1u << LOGB) - 1);
-                s >>= LOGB;
-                s += d >> (LOGB - 1);
-                packed |= d << (j * LOGB);
-            }
-            dig[p][e] = packed;
-        }
-    STAMPS_(0);
+        for (int e = 0; e < 16; e++) // sub_glwe_ciphertexts(diff, d_1, d_0) (fft_ops.rs:168), then the gadget digits
+            dig[p][e] = gadget_digits_packed<L, LOGB>(x1[p][e] - (d0_zero ? 0 : x0[p][e]));
+    stamps.mark(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // my pieces of the twiddle image have landed (LDS-DMA counts on vmcnt)
     __syncthreads(); // twiddle image ready
-    STAMPS_(1);
+    stamps.mark(1);
 
     const c64* twist = tab + kTWOff + w * 512 + lane;
     const c64* wc = tab + kWCOff + 256 * w + lane;
@@ -1115,70 +1022,47 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
         const gc64_ptr next = key_row(LAST ? m : m + 1);
         c64 V[8];
 #pragma unroll
-        for (int n1 = 0; n1 < 8; n1++) {
+        for (int n1 = 0; n1 < 8; n1++) { // (twisted_digit<LOGB>, written out: through the helper the round comes out two instructions longer)
             uint32_t wre = p ? dig[1][n1] : dig[0][n1];
             uint32_t wim = p ? dig[1][8 + n1] : dig[0][8 + n1];
             int dre = ((int)(wre << (32 - LOGB - sh))) >> (32 - LOGB);
             int dim = ((int)(wim << (32 - LOGB - sh))) >> (32 - LOGB);
             V[n1] = cmul_nf({(double)dre, (double)dim}, twist[64 * n1]);
         }
-        STAMPS_(2);
+        stamps.mark(2);
         if (m > 0) cmux_sync(); // partner is done with my last cross data
-        STAMPS_(3);
+        stamps.mark(3);
         fft512_single<+1>(V, mine, tab, lane);
-        STAMPS_(4);
-        c64 Ei[4], Oi[4];
-        if (w == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[i * 64 + lane] = V[4 + i];
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[i * 64 + lane] = V[i];
-        }
+        stamps.mark(4);
+        cross_put<w>(mine, lane, V);
         cmux_sync();
-        STAMPS_(5);
-        if (w == 0) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) { Ei[i] = V[i]; Oi[i] = reinterpret_cast<const c64*>(theirs)[i * 64 + lane]; }
-        } else {
-#pragma unroll
-            for (int i = 0; i < 4; i++) { Ei[i] = reinterpret_cast<const c64*>(theirs)[i * 64 + lane]; Oi[i] = V[4 + i]; }
-        }
+        stamps.mark(5);
+        cross_take<w>(theirs, lane, V); // V[0..3] = E, V[4..7] = O
         c64 X[8];
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            c64 t = cmul_tw<+1>(Oi[i], wc[64 * i]);
-            X[i] = cadd(Ei[i], t);
-            X[i + 4] = csub(Ei[i], t);
+            c64 t = cmul_tw<+1>(V[4 + i], wc[64 * i]);
+            X[i] = cadd(V[i], t);
+            X[i + 4] = csub(V[i], t);
         }
-        STAMPS_(6);
+        stamps.mark(6);
 #ifdef SPF_STAMPS
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // diagnostic: time spent waiting for this round's selector rows
-        STAMPS_(7);
+        stamps.mark(7);
 #endif
 #pragma unroll
-        for (int r = 0; r < 8; r++) {
-            double re = __builtin_fma(k0[r].re, X[r].re, prod[0][r].re);
-            double im = __builtin_fma(k0[r].re, X[r].im, prod[0][r].im);
-            prod[0][r].re = __builtin_fma(-k0[r].im, X[r].im, re);
-            prod[0][r].im = __builtin_fma(k0[r].im, X[r].re, im);
-        }
+        for (int r = 0; r < 8; r++) cmad(prod[0][r], k0[r], X[r]);
         if constexpr (!LAST) {
 #pragma unroll
             for (int r = 0; r < 8; r++) k0[r] = key_load(next + 64 * (r & 3) + 512 * (r >> 2));
         }
 #pragma unroll
-        for (int r = 0; r < 8; r++) {
-            double re = __builtin_fma(k1[r].re, X[r].re, prod[1][r].re);
-            double im = __builtin_fma(k1[r].re, X[r].im, prod[1][r].im);
-            prod[1][r].re = __builtin_fma(-k1[r].im, X[r].im, re);
-            prod[1][r].im = __builtin_fma(k1[r].im, X[r].re, im);
-        }
+        for (int r = 0; r < 8; r++) cmad(prod[1][r], k1[r], X[r]);
         if constexpr (!LAST) {
 #pragma unroll
             for (int r = 0; r < 8; r++) k1[r] = key_load(next + kHalf + 64 * (r & 3) + 512 * (r >> 2));
         }
-        STAMPS_(8);
+        stamps.mark(8);
     };
 #pragma unroll 1
     for (int m = 0; m < 2 * L - 1; m++) round(m, std::false_type{});
@@ -1199,50 +1083,29 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     // kernel of thousands of short workgroups pays for every byte of scratch it declares (0.32 -> 0.40 ms per 4096).
     int lane_late = lane;
     asm volatile("" : "+v"(lane_late));
-    auto coef2_late = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane_late + w; };
     uint64_t d0w[2][16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) d0w[0][e] = gd0[coef2_late(e)];
+    for (int e = 0; e < 16; e++) d0w[0][e] = gd0[coef2(e, lane_late, w)];
     c64 WW[2][8];
 #pragma unroll
-    for (int q = 0; q < 2; q++)
+    for (int q = 0; q < 2; q++) // (inverse_split with the twiddle read BEHIND the sum: that order is this kernel's code)
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             WW[q][i] = cadd(prod[q][i], prod[q][i + 4]);                             // Ep: kept by wave 0
             WW[q][4 + i] = cmul_tw<-1>(csub(prod[q][i], prod[q][i + 4]), wc[64 * i]); // Op: kept by wave 1
         }
     cmux_sync(); // partner is done with my last cross data
-    if constexpr (w == 0) {
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(q * 4 + i) * 64 + lane] = WW[q][4 + i];
-    } else {
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) reinterpret_cast<c64*>(mine)[(q * 4 + i) * 64 + lane] = WW[q][i];
-    }
+    cross_put<w>(mine, lane, WW);
     cmux_sync();
-    if constexpr (w == 0) {
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) WW[q][4 + i] = reinterpret_cast<const c64*>(theirs)[(q * 4 + i) * 64 + lane];
-    } else {
-#pragma unroll
-        for (int q = 0; q < 2; q++)
-#pragma unroll
-            for (int i = 0; i < 4; i++) WW[q][i] = reinterpret_cast<const c64*>(theirs)[(q * 4 + i) * 64 + lane];
-    }
+    cross_take<w>(theirs, lane, WW);
     cmux_sync(); // both cross reads retired before either image is overwritten
-    STAMPS_(9);
+    stamps.mark(9);
     SPF_CMUX_INV_PAIR<-1, 2>(WW[0], WW[1], mine, tab, lane);
-    STAMPS_(10);
+    stamps.mark(10);
     // (the second polynomial's words only now: all 32 across the transform pair do not fit the registers, and a
     // spilled load waits for everything in flight; they land under the first polynomial's conversion)
 #pragma unroll
-    for (int e = 0; e < 16; e++) d0w[1][e] = gd0[kN + coef2_late(e)];
+    for (int e = 0; e < 16; e++) d0w[1][e] = gd0[kN + coef2(e, lane_late, w)];
 #pragma unroll
     for (int q = 0; q < 2; q++) {
         uint64_t t[16];
@@ -1250,17 +1113,11 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
 #pragma unroll
         for (int e = 0; e < 16; e++) {
             const uint64_t v = (d0_zero ? 0 : d0w[q][e]) + t[e];
-            if (owns_output) gout[q * kN + coef2_late(e)] = v;
+            if (owns_output) gout[q * kN + coef2(e, lane_late, w)] = v;
         }
     }
-    STAMPS_(11);
-#ifdef SPF_STAMPS
-    if (a.stamps && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) a.stamps[((size_t)blockIdx.x * (2 * G) + wv) * 16 + i] = st_acc[i];
-    }
-#endif
-#undef STAMPS_
+    stamps.mark(11);
+    stamps.flush(a.stamps, (size_t)blockIdx.x * (2 * G) + wv, lane);
 }
 
 template <int L, int LOGB, int G, bool STREAM = false>
@@ -1296,13 +1153,7 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int w = W; // sample parity: one copy of the body per parity (see blind_rotate2p_kernel)
     const int h = wv >> 1;
-#ifdef SPF_STAMPS
-    uint64_t st_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t st_prev = __builtin_amdgcn_s_memtime();
-#define STAMPC(i) do { uint64_t t_ = __builtin_amdgcn_s_memtime(); st_acc[i] += t_ - st_prev; st_prev = t_; } while (0)
-#else
-#define STAMPC(i) do { } while (0)
-#endif
+    PhaseStamps<9> stamps;
     // region of wave (w, h): 32 KiB = two exchange images while transforming, then its four transforms
     auto region = [&](int ww, int hh) -> char* { return smem + kTableBytes + (hh * 2 + ww) * 32768; };
     char* mine = region(w, h);
@@ -1344,7 +1195,6 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
         d1 = a.d1 + (size_t)ct * 2 * kN;
         out_ct = a.out + (size_t)ct * 2 * kN;
     }
-    auto coef2 = [&](int e) -> int { return (e >> 3) * 1024 + (e & 7) * 128 + 2 * lane + w; };
     // operand pointers may come from the per-gate table: pin them to global memory so that the loads count on
     // vmcnt only and stay in flight across the LDS waits and barriers of the transforms (see global_view)
     const gc64_ptr gkey = global_view(ggsw) + 256 * w + lane;
@@ -1359,9 +1209,9 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     // d0 aliases d1 when it is the zero ciphertext, so its loads need no branch
     uint64_t x1[16], x0[16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) x1[e] = gd1[coef2(e)];
+    for (int e = 0; e < 16; e++) x1[e] = gd1[coef2(e, lane, w)];
 #pragma unroll
-    for (int e = 0; e < 16; e++) x0[e] = gd0[coef2(e)];
+    for (int e = 0; e < 16; e++) x0[e] = gd0[coef2(e, lane, w)];
     compiler_fence();
     {
         f64x2_t* dst = reinterpret_cast<f64x2_t*>(smem);
@@ -1375,16 +1225,16 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     c64 key0[L][8], key1[L][8];
 #pragma unroll
     for (int j = 0; j < L; j++) load_row(key0[j], 0, j);
-    STAMPC(0);
+    stamps.mark(0);
     wg_barrier(); // twiddle image in place
-    STAMPC(1);
+    stamps.mark(1);
     c64 twist[8], wc[4];
 #pragma unroll
     for (int n1 = 0; n1 < 8; n1++) twist[n1] = tab[kTWOff + w * 512 + lane + 64 * n1];
 #pragma unroll
     for (int i = 0; i < 4; i++) wc[i] = tab[kWCOff + 256 * w + lane + 64 * i];
 
-    STAMPC(2);
+    stamps.mark(2);
     uint32_t dig[16];
 #pragma unroll
     for (int e = 0; e < 16; e++) // sub_glwe_ciphertexts(diff, d_1, d_0) (fft_ops.rs:168), then the gadget digits
@@ -1428,7 +1278,7 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
             for (int r = 0; r < 8; r++) X[jj + j][r] = Y[r];
         }
     }
-    STAMPC(3);
+    stamps.mark(3);
     wg_barrier(); // cross reads retired: the regions can carry the transforms
     // spectra out, and behind each one — into the registers it frees — the matching one of the last four selector
     // rows: the 32 requests trickle into the vector-memory queue between the LDS stores instead of stalling in a block
@@ -1439,7 +1289,7 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
         load_row(key1[j], 1, j);
     }
     wg_barrier(); // every wave's four transforms are in its region
-    STAMPC(4);
+    stamps.mark(4);
 
     // ---- accumulation chain of output polynomial h: rows (0, j = 0..3) then (1, j = 0..3)
     c64 V[8];
@@ -1465,15 +1315,11 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
 #pragma unroll
             for (int r = 0; r < 8; r++) {
                 const c64 k = {p == 0 ? key0[j][r].re : key1[j][r].re, p == 0 ? key0[j][r].im : key1[j][r].im};
-                const c64 x = sx[m & 1][r];
-                double re = __builtin_fma(k.re, x.re, V[r].re);
-                double im = __builtin_fma(k.re, x.im, V[r].im);
-                V[r].re = __builtin_fma(-k.im, x.im, re);
-                V[r].im = __builtin_fma(k.im, x.re, im);
+                cmad(V[r], k, sx[m & 1][r]);
             }
         }
     }
-    STAMPC(5);
+    stamps.mark(5);
     wg_barrier(); // sibling reads retired; regions free again
 
     // ---- polynomial h back to the torus, plus d0
@@ -1503,24 +1349,21 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     // add_glwe_ciphertexts(c, prod, d_0) (fft_ops.rs:180): d_0 re-read under the inverse transform
     uint64_t d0w[16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) d0w[e] = gd0[coef2(e)];
-    STAMPC(6);
+    for (int e = 0; e < 16; e++) d0w[e] = gd0[coef2(e, lane, w)];
+    stamps.mark(6);
     fft512_single<-1, 7>(V, mine, tab, lane);
     uint64_t t[16];
     untwist_to_torus_bits(V, twist, t);
 #pragma unroll
-    for (int e = 0; e < 16; e++) gout[coef2(e)] = (d0_zero ? 0 : d0w[e]) + t[e];
-    STAMPC(7);
+    for (int e = 0; e < 16; e++) gout[coef2(e, lane, w)] = (d0_zero ? 0 : d0w[e]) + t[e];
+    stamps.mark(7);
 #ifdef SPF_STAMPS
     if (a.stamps && lane == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // count the stores' drain
-        const uint64_t t_end = __builtin_amdgcn_s_memtime();
-#pragma unroll
-        for (int i = 0; i < 8; i++) a.stamps[((size_t)blockIdx.x * 4 + wv) * 16 + i] = st_acc[i];
-        a.stamps[((size_t)blockIdx.x * 4 + wv) * 16 + 8] = t_end - st_prev;
+        stamps.mark(8);
     }
 #endif
-#undef STAMPC
+    stamps.flush(a.stamps, (size_t)blockIdx.x * 4 + wv, lane);
 }
 
 template <int L, int LOGB>
