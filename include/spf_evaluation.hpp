@@ -148,6 +148,14 @@ class Evaluation {
     {
         check(spf_group_unpack_circuit_bootstrap_batch(grp_, B, n_bits, packed_glwe, output_ggsw_fft));
     }
+    // blind_rotation (sunscreen_tfhe ops/bootstrapping/blind_rotation.rs:202-223): output = input * X^-(s << log_stride), the shift
+    // as the GGSWs of its n_bits bits (least significant first, item b's bit i is selector b * n_bits + i: what
+    // unpack_circuit_bootstrap writes); the reference's call is n_bits = log2 N, log_stride = 0
+    void blind_rotation(uint64_t* output, const double* shift_ggsw_fft, const uint64_t* input, size_t n_bits, size_t log_stride = 0,
+                        size_t B = 1)
+    {
+        check(spf_group_blind_rotation_batch(grp_, B, n_bits, log_stride, shift_ggsw_fft, input, output));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

@@ -261,10 +261,25 @@ spf_status spf_glwe_unpack_l1_batch(spf_ctx *ctx, size_t B, size_t n_bits, const
 spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx *ctx, size_t B, size_t n_bits, const uint64_t *packed_glwe,
                                               double *ggsw_fft_out);
 
+/* `blind_rotation` (sunscreen_tfhe/src/ops/bootstrapping/blind_rotation.rs:202-223): out = in * X^-(s << log_stride), the shift s
+ * given as GGSW encryptions of its bits in cbs_radix shape (`BlindRotationShiftFft`, entities/blind_rotation_shift.rs), int-major
+ * like the packed integers above: bit i (least significant first) of item b is selector b * n_bits + i — what
+ * spf_unpack_circuit_bootstrap_* produces.  For i ascending, acc = `cmux`(shift[b][i], acc, X^-(2^(i + log_stride)) * acc)
+ * (ops/fft_ops.rs:149-181; `rotate_glwe_negative_monomial_negacyclic`, blind_rotation.rs:107-116: coefficient j of the rotated
+ * GLWE is coefficient j + r of the input, negated where j + r >= N), one kernel per bit whose high operand is a rotated read of
+ * the low one.  Word-equal to the same loop of spf_glwe_mul_xn_batch (amount 2N - r) and spf_cmux_batch.  The reference's call
+ * is n_bits = log2 N, log_stride = 0; log_stride indexes entries of 2^log_stride coefficients (a packed table).  No key.
+ * shift_ggsw_fft: B * n_bits x (k+1)*l_cbs*(k+1)*N/2 complex; glwe_in, glwe_out: B x (k+1)*N.
+ * n_bits >= 1, n_bits + log_stride <= log2 N and B * n_bits <= 0x0fffffff, else SPF_ERR_INVALID_ARGUMENT before any device
+ * work; B = 0 is SPF_OK; a tuned context whose cbs radix is not 4 x 4 bits: SPF_ERR_UNSUPPORTED, as for spf_cmux_batch. */
+spf_status spf_blind_rotation_batch(spf_ctx *ctx, size_t B, size_t n_bits, size_t log_stride, const double *shift_ggsw_fft,
+                                    const uint64_t *glwe_in, uint64_t *glwe_out);
+
 /* ---- device-pointer forms (inputs/outputs resident in HBM, asynchronous on `stream`) -----
  * Contract of every `_dev` entry point: the call only ENQUEUES on `stream`; inputs and outputs must stay valid and
  * unchanged until that work has completed; an output must not overlap any input of the same call.  The entry points that
- * need intermediates (`spf_circuit_bootstrap_dev`, the keyswitch, `spf_pbs_bivariate_dev`'s packed input) keep them in
+ * need intermediates (`spf_circuit_bootstrap_dev`, the keyswitch, `spf_pbs_bivariate_dev`'s packed input,
+ * `spf_blind_rotation_dev`'s accumulator between steps) keep them in
  * buffers of the CONTEXT: enqueue them on ONE stream per context (or order the streams with events) — two such calls
  * running concurrently on different streams would share those buffers.  `spf_mod_switch_trace_and_rotate_dev`
  * additionally uses its OUTPUT as working memory while it runs (the kernel parks half of its accumulator in each unit's
@@ -313,6 +328,12 @@ spf_status spf_glwe_unpack_l1_dev(spf_ctx *ctx, void *stream, size_t B, size_t n
                                   uint64_t *d_lwe1_out);
 spf_status spf_unpack_circuit_bootstrap_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits,
                                             const uint64_t *d_packed_glwe, double *d_ggsw_fft_out);
+
+/* spf_blind_rotation_batch (`blind_rotation`, ops/bootstrapping/blind_rotation.rs:202-223) on device pointers.  With
+ * n_bits > 1 the accumulator alternates between a B x GLWE buffer of the context (one stream per context) and d_glwe_out, the
+ * last step writing d_glwe_out; d_glwe_in is only read.  An output range that overlaps an input range is refused. */
+spf_status spf_blind_rotation_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits, size_t log_stride,
+                                  const double *d_shift_ggsw_fft, const uint64_t *d_glwe_in, uint64_t *d_glwe_out);
 
 /* ciphertext types (`L0LweCiphertext` ... `L1GlevCiphertext`, crypto/encryption.rs:23-110) and the computing variants of `FheOp`
  * (fhe_circuit.rs:65-126): used by the values, the pool's generic submit and the gate graphs below */
@@ -643,7 +664,8 @@ spf_status spf_device_download(spf_ctx *ctx, void *stream, void *host_dst, const
 const char *spf_last_blind_rotate_kernel(spf_ctx *ctx);
 /* The same for the CMUX family (spf_cmux*, spf_glev_cmux*, spf_multiply_glwe_ggsw*, gate graphs): four waves per gate up
  * to one gate per CU, the streaming shape beyond, with streaming (non-temporal) selector loads once a launch's selectors
- * exceed the Infinity Cache.  Never NULL. */
+ * exceed the Infinity Cache.  The steps of spf_blind_rotation* report the same names with ",rot" appended
+ * ("cmux4_kernel<4,4,rot>", "cmux_kernel<4,4,2,rot>", "cmux_kernel<4,4,2,stream,rot>").  Never NULL. */
 const char *spf_last_cmux_kernel(spf_ctx *ctx);
 /* The same for the LWE keyswitch L1 -> L0 (every entry point that runs one): "ks_gemm_lds_kernel", the int8 matrix-core
  * formulation, when the tuned context's radix fits it (radix_log <= 8 and its accumulator bound), else "keyswitch_kernel".
@@ -743,6 +765,9 @@ spf_status spf_group_glwe_unpack_l1_batch(spf_group *grp, size_t B, size_t n_bit
                                           uint64_t *lwe1_out);
 spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group *grp, size_t B, size_t n_bits, const uint64_t *packed_glwe,
                                                     double *ggsw_fft_out);
+/* `blind_rotation` (ops/bootstrapping/blind_rotation.rs:202-223), sharded by item (a member's selectors are at * n_bits onwards) */
+spf_status spf_group_blind_rotation_batch(spf_group *grp, size_t B, size_t n_bits, size_t log_stride, const double *shift_ggsw_fft,
+                                          const uint64_t *glwe_in, uint64_t *glwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

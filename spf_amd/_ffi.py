@@ -82,6 +82,8 @@ SYMBOLS = [
     ("spf_glwe_pack_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_glwe_unpack_l1_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_blind_rotation_batch", _I, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    ("spf_blind_rotation_dev", _I, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -179,6 +181,7 @@ SYMBOLS = [
     ("spf_group_glwe_pack_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_glwe_unpack_l1_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_group_blind_rotation_batch", _I, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -603,6 +606,20 @@ class Engine:
         self._ck(self._lib.spf_unpack_circuit_bootstrap_batch(self._h, x.shape[0], n_bits, _ptr(x), _ptr(out)))
         return out
 
+    def blind_rotation(self, shift_ggsw_fft, glwe, log_stride: int = 0) -> np.ndarray:
+        """`blind_rotation` (sunscreen_tfhe ops/bootstrapping/blind_rotation.rs:202-223): glwe[b] * X^-(s_b << log_stride), the
+        shift s_b given as the GGSWs of its bits, least significant first (what unpack_circuit_bootstrap returns):
+        (B, n_bits, cbs_ggsw_complex) and (B, glwe_words) -> (B, glwe_words); spf_amd.packed.trivial_table_glwe makes a table
+        whose entry s_b this brings to coefficient 0"""
+        g = np.ascontiguousarray(shift_ggsw_fft, dtype=np.complex128)
+        if g.ndim != 3 or g.shape[2] != self.params.cbs_ggsw_complex:
+            raise SpfError(-2, f"blind_rotation: shift must have shape (B, n_bits, {self.params.cbs_ggsw_complex}), got {g.shape}")
+        x = _u64(glwe).reshape(-1, self.params.glwe_words)
+        _same_rows("blind_rotation", g, x)
+        out = np.empty_like(x)
+        self._ck(self._lib.spf_blind_rotation_batch(self._h, x.shape[0], g.shape[1], int(log_stride), _ptr(g), _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -666,6 +683,9 @@ class Engine:
 
     def unpack_circuit_bootstrap_dev(self, stream, B, n_bits, d_packed, d_ggsw_out):
         self._ck(self._lib.spf_unpack_circuit_bootstrap_dev(self._h, stream, B, n_bits, d_packed, d_ggsw_out))
+
+    def blind_rotation_dev(self, stream, B, n_bits, log_stride, d_shift, d_in, d_out):
+        self._ck(self._lib.spf_blind_rotation_dev(self._h, stream, B, n_bits, log_stride, d_shift, d_in, d_out))
 
     # -- device buffers (for chaining the _dev forms without a HIP binding of one's own)
     def device_alloc(self, nbytes: int) -> int:

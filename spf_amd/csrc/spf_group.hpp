@@ -731,6 +731,18 @@ spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group* g, size_t B, size
     });
 }
 
+// blind rotation by an encrypted shift: sharded by item, an item's n_bits selectors go with it
+spf_status spf_group_blind_rotation_batch(spf_group* g, size_t B, size_t n_bits, size_t log_stride, const double* shift,
+                                          const uint64_t* in, uint64_t* out)
+{
+    SPF_GROUP_NULL(!shift || !in || !out);
+    if (const char* why = blind_rotation_shape_error(g->prm, B, n_bits, log_stride)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
+    const size_t w = glwe_words(g->prm), sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
+        return spf_blind_rotation_batch(c, n, n_bits, log_stride, shift + at * n_bits * sw, in + at * w, out + at * w);
+    });
+}
+
 spf_status spf_group_glwe_not_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
     SPF_GROUP_NULL(!in || !out);

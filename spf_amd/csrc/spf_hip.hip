@@ -83,6 +83,7 @@ struct spf_ctx {
     DevBuf in, out, mid, aux;      // staging for the host-pointer entry points
     DevBuf packed;                  // the packed level-0 input of spf_pbs_bivariate_dev
     DevBuf unpack_l1, unpack_l0;    // the unpacked bits of spf_unpack_circuit_bootstrap_dev, before and after the keyswitch
+    DevBuf brot_mid, brot_high;     // spf_blind_rotation_dev: the accumulator between steps; generic contexts: X^-r * accumulator
     int8_t* d_ksk_planes = nullptr; // key byte planes for the int8-MFMA keyswitch [Npad][K]
     size_t ks_npad = 0;
     Scratch scr;                    // intermediates of the entry points (keyswitch digits, circuit-bootstrap GLWE / GLEV)
@@ -677,6 +678,12 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                            hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux4_kernel<4, 4>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kCmux4Lds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux_kernel<4, 4, 2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                           cmux_lds_bytes(2)));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux_kernel<4, 4, 2, false, true>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux4_kernel<4, 4, true>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kCmux4Lds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cbs_trace_kernel<6, 7>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&scheme_switch_kernel<15, 3>),
@@ -694,7 +701,7 @@ void spf_destroy(spf_ctx* c)
     for (auto& v : c->timed)
         for (auto& t : v) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     for (void* p : {(void*)c->d_tables, (void*)c->d_bsk, (void*)c->d_bsk_scaled, (void*)c->d_ksk, (void*)c->d_cbs_lut,
-                    c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, (void*)c->d_ksk_planes,
+                    c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
                     c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -1409,6 +1416,101 @@ spf_status spf_multiply_glwe_ggsw_dev(spf_ctx* c, void* stream, size_t B, const 
     return launch_cmux(c, (hipStream_t)stream, B, 1, d_ggsw, nullptr, d_glwe, d_out);
 }
 
+// ---- blind rotation by an encrypted shift (`blind_rotation`, sunscreen_tfhe/src/ops/bootstrapping/blind_rotation.rs:202-223)
+
+// One step on a tuned context: out = cmux(sel = selector `sel_stride` * u of d_sel, low = acc, high = X^-rot * acc), the high operand
+// a rotated read of the low one (the ROT instantiations).  Shapes as launch_cmux_args picks them, one selector per unit.
+static void launch_cmux_rot(spf_ctx* c, hipStream_t s, size_t B, const c64* d_sel, uint32_t sel_stride, uint32_t rot,
+                            const uint64_t* d_acc, uint64_t* d_out)
+{
+    CmuxArgs a{};
+    a.ggsw = d_sel; a.d0 = d_acc; a.out = d_out; a.tables = c->d_tables; a.B = (uint32_t)B; a.per_ggsw = 1;
+    a.rot = rot; a.sel_stride = sel_stride;
+    if (a.B <= (uint32_t)c->n_cu) {
+        c->last_cmux_kernel = "cmux4_kernel<4,4,rot>";
+        hipLaunchKernelGGL((cmux4_kernel<4, 4, true>), dim3(a.B), dim3(256), kCmux4Lds, s, a);
+    } else if (B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * sizeof(c64) >= ((size_t)224 << 20)) {
+        c->last_cmux_kernel = "cmux_kernel<4,4,2,stream,rot>";
+        hipLaunchKernelGGL((cmux_kernel<4, 4, 2, true, true>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, a);
+    } else {
+        c->last_cmux_kernel = "cmux_kernel<4,4,2,rot>";
+        hipLaunchKernelGGL((cmux_kernel<4, 4, 2, false, true>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, a);
+    }
+}
+
+// why (B, n_bits, log_stride) is refused, or nullptr: every step's rotation 2^(i + log_stride) stays below N
+static const char* blind_rotation_shape_error(const spf_params& p, size_t B, size_t n_bits, size_t log_stride)
+{
+    uint32_t log_n = 0;
+    while ((1u << log_n) < p.polynomial_degree) log_n++;
+    if (n_bits == 0) return "n_bits must be at least 1";
+    if (n_bits > log_n || log_stride > log_n - n_bits) return "n_bits + log_stride above log2(polynomial_degree)";
+    if (B > 0x0fffffffu / n_bits) return "B * n_bits above 0x0fffffff";
+    return nullptr;
+}
+
+static spf_status blind_rotation_args(spf_ctx* c, size_t B, size_t n_bits, size_t log_stride, const void* shift, const void* in,
+                                      const void* out)
+{
+    if (!c || (B && (!shift || !in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const char* why = blind_rotation_shape_error(c->prm, B, n_bits, log_stride)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    return SPF_OK;
+}
+
+// `blind_rotation` (blind_rotation.rs:202-223) with the shift as `BlindRotationShiftFft` (entities/blind_rotation_shift.rs): for
+// bit i ascending, acc = cmux(shift[b][i], acc, X^-(2^(i + log_stride)) * acc) (`cmux`, fft_ops.rs:149-181;
+// `rotate_glwe_negative_monomial_negacyclic`, blind_rotation.rs:107-116).  One launch per bit; the steps alternate between a buffer
+// of the context and d_out so that the last one writes d_out.
+spf_status spf_blind_rotation_dev(spf_ctx* c, void* stream, size_t B, size_t n_bits, size_t log_stride, const double* d_shift,
+                                  const uint64_t* d_in, uint64_t* d_out)
+{
+    spf_status st = blind_rotation_args(c, B, n_bits, log_stride, d_shift, d_in, d_out);
+    if (st != SPF_OK) return st;
+    if (!c->generic && (c->prm.cbs_radix_log != 4 || c->prm.cbs_radix_count != 4))
+        return fail(c, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
+    if (B == 0) return SPF_OK;
+    const size_t gw = glwe_words(c->prm), sel = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count);
+    const uintptr_t out0 = (uintptr_t)d_out, out1 = out0 + B * gw * 8;
+    const uintptr_t in0 = (uintptr_t)d_in, sh0 = (uintptr_t)d_shift;
+    if ((out0 < in0 + B * gw * 8 && in0 < out1) || (out0 < sh0 + B * n_bits * sel * sizeof(c64) && sh0 < out1))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps an input");
+    hipStream_t s = (hipStream_t)stream;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n_bits > 1) {
+        st = ensure(c, c->brot_mid, B * gw * 8);
+        if (st != SPF_OK) return st;
+    }
+    if (c->generic) {
+        st = ensure(c, c->brot_high, B * gw * 8);
+        if (st != SPF_OK) return st;
+    }
+    const c64* shift = reinterpret_cast<const c64*>(d_shift);
+    const uint64_t* acc = d_in;
+    for (size_t i = 0; i < n_bits; i++) {
+        uint64_t* dst = ((n_bits - 1 - i) & 1) ? (uint64_t*)c->brot_mid.p : d_out;
+        const uint32_t rot = 1u << (i + log_stride);
+        if (c->generic) {
+            // X^-rot = X^(2N - rot) into scratch, then the CMUX; an item's selectors are n_bits apart: one launch per item
+            st = spf_glwe_mul_xn_dev(c, stream, B, acc, 2 * (size_t)c->prm.polynomial_degree - rot, (uint64_t*)c->brot_high.p);
+            for (size_t b = 0; b < B && st == SPF_OK; b++)
+                st = launch_cmux(c, s, 1, 1, d_shift + 2 * (b * n_bits + i) * sel, acc + b * gw, (const uint64_t*)c->brot_high.p + b * gw,
+                                 dst + b * gw);
+            if (st != SPF_OK) return st;
+        } else {
+            TimedScope ts(c, s, T_CMUX);
+            st = ts.begin();
+            if (st != SPF_OK) return st;
+            launch_cmux_rot(c, s, B, shift + i * sel, (uint32_t)n_bits, rot, acc, dst);
+            HIPCHK(c, hipGetLastError());
+            st = ts.end();
+            if (st != SPF_OK) return st;
+        }
+        acc = dst;
+    }
+    return SPF_OK;
+}
+
 // ---------------------------------------------------------------- host-pointer forms
 //
 // Each form checks every argument it can see, then reaches the device through staged() / host_call() only.
@@ -1582,6 +1684,18 @@ spf_status spf_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_
     return host_call(c, {{c->aux, sel, sw}, {c->in, a, gw}, {c->mid, b, gw}}, gw, out, [&] {
         return spf_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p,
                             (uint64_t*)c->out.p);
+    });
+}
+
+spf_status spf_blind_rotation_batch(spf_ctx* c, size_t B, size_t n_bits, size_t log_stride, const double* shift, const uint64_t* in,
+                                    uint64_t* out)
+{
+    spf_status s = blind_rotation_args(c, B, n_bits, log_stride, shift, in, out);
+    if (s != SPF_OK || B == 0) return s;
+    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * n_bits * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
+    return host_call(c, {{c->aux, shift, sw}, {c->in, in, gw}}, gw, out, [&] {
+        return spf_blind_rotation_dev(c, c->stream, B, n_bits, log_stride, (const double*)c->aux.p, (const uint64_t*)c->in.p,
+                                      (uint64_t*)c->out.p);
     });
 }
 

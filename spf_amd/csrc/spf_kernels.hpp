@@ -15,6 +15,7 @@
 //
 // Reference path reproduced (sunscreen_tfhe/src):
 //   ops/bootstrapping/programmable_bootstrapping.rs:342-410  generalized_programmable_bootstrap
+//   ops/bootstrapping/blind_rotation.rs:202-223 blind_rotation (one cmux per bit of an encrypted shift: the ROT instantiations)
 //   ops/fft_ops.rs:149-181 cmux, :23-56 glwe_ggsw_mad, :67-98 decomposed_polynomial_glev_mad
 //   math/radix.rs:157-162 round, math/simd/scalar.rs:52-71 vector_next_decomp
 //   entities/polynomial.rs:171-236 monomial rotation, :257-274 fft
@@ -905,13 +906,19 @@ struct CmuxArgs {
     // {ggsw, d0 (null = zero ciphertext), d1, out} from ptrs[4u .. 4u+3] instead of the arrays above.
     const void* const* ptrs;
     uint64_t* stamps;     // diagnostic builds (-DSPF_STAMPS): per-phase cycle counts of cmux4_kernel, else null
+    // The ROT instantiations only (one step of spf_blind_rotation_dev, blind_rotation.rs:202-223): d1 is no buffer but
+    // X^-rot * d0 (`rotate_glwe_negative_monomial_negacyclic`), read from d0 at (coefficient + rot) mod N and negated where
+    // the sum wrapped; unit u takes selector u * sel_stride from `ggsw` (int-major bits: this step's bit of every item).
+    // ptrs, d1, per_ggsw and d0_zero are not read there.
+    uint32_t rot;         // 0 < rot < N
+    uint32_t sel_stride;
 };
 constexpr int cmux_lds_bytes(int gates) { return kTableBytes + gates * kWaveBufBytes + 64; }
 
 #ifndef SPF_CMUX_INV_PAIR
 #define SPF_CMUX_INV_PAIR fft512_pair1
 #endif
-template <int L, int LOGB, int G, int W, bool STREAM>
+template <int L, int LOGB, int G, int W, bool STREAM, bool ROT = false>
 __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
 {
     static_assert(L * LOGB <= 32, "packed digits need L*LOGB <= 32");
@@ -935,8 +942,12 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     const c64* ggsw;
     const uint64_t *d0, *d1;
     uint64_t* out_ct;
-    bool d0_zero = a.d0_zero != 0;
-    if (a.ptrs) {
+    bool d0_zero = ROT ? false : a.d0_zero != 0;
+    if constexpr (ROT) {
+        ggsw = a.ggsw + (size_t)ct * a.sel_stride * (2 * L * 2 * kHalf);
+        d0 = d1 = a.d0 + (size_t)ct * 2 * kN; // d1 = X^-rot * d0: the rotated read below
+        out_ct = a.out + (size_t)ct * 2 * kN;
+    } else if (a.ptrs) {
         const void* const* t = a.ptrs + 4 * (size_t)ct;
         ggsw = static_cast<const c64*>(t[0]);
         d1 = static_cast<const uint64_t*>(t[2]);
@@ -969,10 +980,18 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
 #pragma unroll
         for (int e = 0; e < 16; e++) {
             const int c = p * kN + coef2(e, lane, w);
-            x1[p][e] = gd1[c];
+            if constexpr (ROT) x1[p][e] = gd0[p * kN + ((coef2(e, lane, w) + (int)a.rot) & (kN - 1))];
+            else x1[p][e] = gd1[c];
             x0[p][e] = gd0[c]; // d0 aliases d1 when it is the zero ciphertext: no branch around the load
         }
     sched_fence();
+    if constexpr (ROT) { // coefficient j of X^-rot * d0 is coefficient j + rot of d0, negated where j + rot >= N
+#pragma unroll
+        for (int p = 0; p < 2; p++)
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+                if (coef2(e, lane, w) + (int)a.rot >= kN) x1[p][e] = (uint64_t)0 - x1[p][e];
+    }
     stamps.mark(13);
     uint32_t dig[2][16];
 #pragma unroll
@@ -1120,12 +1139,12 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     stamps.flush(a.stamps, (size_t)blockIdx.x * (2 * G) + wv, lane);
 }
 
-template <int L, int LOGB, int G, bool STREAM = false>
+template <int L, int LOGB, int G, bool STREAM = false, bool ROT = false>
 __global__ __launch_bounds__(128 * G, 2) void cmux_kernel(CmuxArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux_body<L, LOGB, G, 1, STREAM>(a, smem);
-    else cmux_body<L, LOGB, G, 0, STREAM>(a, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux_body<L, LOGB, G, 1, STREAM, ROT>(a, smem);
+    else cmux_body<L, LOGB, G, 0, STREAM, ROT>(a, smem);
 
 }
 
@@ -1143,7 +1162,7 @@ __global__ __launch_bounds__(128 * G, 2) void cmux_kernel(CmuxArgs a)
 // forward transforms.  Same operations in the same order on every value as cmux_kernel: same words.
 constexpr int kCmux4Lds = kTableBytes + 4 * 4 * 8192;
 
-template <int L, int LOGB, int W>
+template <int L, int LOGB, int W, bool ROT = false>
 __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
 {
     static_assert(L == 4 && L * LOGB <= 32, "four digits, processed as two pairs");
@@ -1181,8 +1200,12 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     const c64* ggsw;
     const uint64_t *d0, *d1;
     uint64_t* out_ct;
-    bool d0_zero = a.d0_zero != 0;
-    if (a.ptrs) {
+    bool d0_zero = ROT ? false : a.d0_zero != 0;
+    if constexpr (ROT) {
+        ggsw = a.ggsw + (size_t)ct * a.sel_stride * (2 * L * 2 * kHalf);
+        d0 = d1 = a.d0 + (size_t)ct * 2 * kN; // d1 = X^-rot * d0: the rotated read below
+        out_ct = a.out + (size_t)ct * 2 * kN;
+    } else if (a.ptrs) {
         const void* const* t = a.ptrs + 4 * (size_t)ct;
         ggsw = static_cast<const c64*>(t[0]);
         d1 = static_cast<const uint64_t*>(t[2]);
@@ -1209,7 +1232,10 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     // d0 aliases d1 when it is the zero ciphertext, so its loads need no branch
     uint64_t x1[16], x0[16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) x1[e] = gd1[coef2(e, lane, w)];
+    for (int e = 0; e < 16; e++) {
+        if constexpr (ROT) x1[e] = gd0[(coef2(e, lane, w) + (int)a.rot) & (kN - 1)];
+        else x1[e] = gd1[coef2(e, lane, w)];
+    }
 #pragma unroll
     for (int e = 0; e < 16; e++) x0[e] = gd0[coef2(e, lane, w)];
     compiler_fence();
@@ -1237,8 +1263,12 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     stamps.mark(2);
     uint32_t dig[16];
 #pragma unroll
-    for (int e = 0; e < 16; e++) // sub_glwe_ciphertexts(diff, d_1, d_0) (fft_ops.rs:168), then the gadget digits
+    for (int e = 0; e < 16; e++) { // sub_glwe_ciphertexts(diff, d_1, d_0) (fft_ops.rs:168), then the gadget digits
+        if constexpr (ROT) { // coefficient j of X^-rot * d0 is coefficient j + rot of d0, negated where j + rot >= N
+            if (coef2(e, lane, w) + (int)a.rot >= kN) x1[e] = (uint64_t)0 - x1[e];
+        }
         dig[e] = gadget_digits_packed<L, LOGB>(x1[e] - (d0_zero ? 0 : x0[e]));
+    }
     // ---- the four digit transforms of polynomial h, two at a time
     c64 X[L][8];
 #pragma unroll
@@ -1366,12 +1396,12 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     stamps.flush(a.stamps, (size_t)blockIdx.x * 4 + wv, lane);
 }
 
-template <int L, int LOGB>
+template <int L, int LOGB, bool ROT = false>
 __global__ __launch_bounds__(256, 1) void cmux4_kernel(CmuxArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux4_body<L, LOGB, 1>(a, smem);
-    else cmux4_body<L, LOGB, 0>(a, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux4_body<L, LOGB, 1, ROT>(a, smem);
+    else cmux4_body<L, LOGB, 0, ROT>(a, smem);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The plaintext side of packed integers (`PackedDynamicGenericInt`, parasol_runtime/src/fluent/generic_int.rs:162-176): an
 n-bit integer in one L1 GLWE, bit i (least significant first, `to_bits`, fluent/int.rs:47-49, uint.rs:30-32) in coefficient
 X^i of the message polynomial at one plaintext bit.  Host only, no GPU; the ciphertext side is Engine.glwe_pack /
-glwe_unpack_l1 / unpack_circuit_bootstrap."""
+glwe_unpack_l1 / unpack_circuit_bootstrap, and Engine.blind_rotation for the packed tables at the end of this file."""
 from __future__ import annotations
 
 import numpy as np
@@ -46,3 +46,32 @@ def trivial_packed_glwe(value: int, n_bits: int, params: Params = DEFAULT_128) -
     out = np.zeros(params.glwe_words, dtype=np.uint64)
     out[params.glwe_size * params.polynomial_degree:] = packed_plaintext(value, n_bits, params) << np.uint64(63)
     return out
+
+
+def table_plaintext(values, entry_bits: int, params: Params = DEFAULT_128):
+    """A table of `entry_bits`-bit entries in one message polynomial, for Engine.blind_rotation: bit j of entry t at
+    coefficient t * S + j, S the smallest power of two >= entry_bits.  Returns (coefficients, log_stride) with
+    log_stride = log2 S.  len(values) * S <= N, and every value fits entry_bits bits as packed_plaintext asks.
+
+    Rotating by an encrypted index t with this log_stride multiplies by X^-(t * S): coefficients 0 .. entry_bits-1 then hold
+    entry t.  The coefficients above them hold the OTHER entries (those below t come back negated), so the result is meant for
+    glwe_unpack_l1(.., entry_bits) and is no operand of glwe_pack, which expects zeros above its bits."""
+    _check_bits(entry_bits, params)
+    log_stride = (entry_bits - 1).bit_length()
+    S = 1 << log_stride
+    values = [int(v) for v in values]
+    if len(values) * S > params.polynomial_degree:
+        raise ValueError(f"{len(values)} entries of stride {S} do not fit {params.polynomial_degree} coefficients")
+    out = np.zeros(params.polynomial_degree, dtype=np.uint64)
+    for t, v in enumerate(values):
+        out[t * S:t * S + entry_bits] = packed_plaintext(v, entry_bits, params)[:entry_bits]
+    return out, log_stride
+
+
+def trivial_table_glwe(values, entry_bits: int, params: Params = DEFAULT_128):
+    """the zero-mask GLWE of table_plaintext at one plaintext bit (body coefficient = bit << 63), as trivial_packed_glwe is
+    of packed_plaintext: ((k+1)*N words, log_stride).  See table_plaintext for what the rotated table may be used for."""
+    coeffs, log_stride = table_plaintext(values, entry_bits, params)
+    out = np.zeros(params.glwe_words, dtype=np.uint64)
+    out[params.glwe_size * params.polynomial_degree:] = coeffs << np.uint64(63)
+    return out, log_stride
