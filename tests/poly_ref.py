@@ -122,6 +122,26 @@ def sample_extract(glwe, h: int) -> np.ndarray:
     return np.concatenate([mask.reshape(-1), glwe[k, h:h + 1]])
 
 
+def pack(bits_glwe) -> np.ndarray:
+    """sum_i bit_i * X^i over GLWEs (n_bits, k+1, N): bit i's message moves to coefficient i
+    (parasol_runtime fluent/dynamic_generic_int_graph_nodes.rs:139-200)"""
+    bits = _u(bits_glwe)
+    out = np.zeros(bits.shape[1:], dtype=np.uint64)
+    for i, b in enumerate(bits):
+        out += mul_monomial(b, i)
+    return out
+
+
+def unpack(glwe, n_bits: int) -> np.ndarray:
+    """sample_extract(glwe, i) for i < n_bits: (n_bits, k N + 1)   (fluent/packed_dynamic_generic_int_graph_node.rs:24-39)"""
+    return np.stack([sample_extract(glwe, i) for i in range(n_bits)])
+
+
+def bivariate_pack(left, right, plaintext_bits: int) -> np.ndarray:
+    """left * 2^p + right on every LWE word, wrapping (ops/bootstrapping/programmable_bootstrapping.rs:603-610)"""
+    return _u(left) * U((1 << plaintext_bits) & M64) + _u(right)
+
+
 def modulus_switch(x: int, log_chi: int, log_v: int, log_modulus: int) -> int:
     """x * 2^log_chi (mod 2^64) rounded half up to its top (log_modulus - log_v) bits, times 2^log_v
     (ops/ciphertext/lwe_ciphertext_ops.rs:130-142)"""
@@ -180,6 +200,16 @@ class NumpyFft:
         n = spec.shape[-1]
         return float_to_torus((np.fft.ifft(spec, axis=-1) * np.conj(_twist(n))).real)
 
+    @staticmethod
+    def forward_bins(p_signed, twist=None) -> np.ndarray:
+        """the N/2 bins of the folded transform (math/fft/negacyclic/mod.rs:96-107) in natural order, as the oracle and the
+        kernels store a polynomial's spectrum: fold z_j = p_j + i p_{j+N/2}, twist by e^{i pi j / N}, one N/2-point np.fft.fft.
+        The yardstick of forward_twisted_dft_longdouble's error measure; `twist` replaces the N/2 twist factors."""
+        p = np.asarray(p_signed, dtype=np.float64)
+        h = p.shape[-1] // 2
+        tw = _twist(2 * h)[:h] if twist is None else twist
+        return np.fft.fft((p[..., :h] + 1j * p[..., h:]) * tw, axis=-1)
+
     @classmethod
     def through_transform(cls, x) -> np.ndarray:
         return cls.inverse(cls.forward(signed(x)))
@@ -209,7 +239,9 @@ def inverse_twisted_dft_longdouble(bins) -> np.ndarray:
     """Torus words of the polynomial whose N/2 transform bins are `bins` (..., N/2), by a direct O(N^2) inverse in
     np.longdouble.  The forward transform (math/fft/negacyclic/mod.rs:96-107) folds p into z_j = (p_j + i p_{j+N/2}) and
     evaluates X_m = sum_j z_j e^{i pi j / N} e^{-2 pi i j m / (N/2)}; hence z_j = e^{-i pi j / N} (2/N) sum_m X_m e^{+4 pi i j m / N}."""
-    bins = np.asarray(bins, dtype=np.complex128)
+    bins = np.asarray(bins)
+    if bins.dtype != np.clongdouble:               # long-double bins (forward_twisted_dft_longdouble's) are taken as they are
+        bins = bins.astype(np.complex128)
     h = bins.shape[-1]
     ld = np.longdouble
     cr, ci = _inverse_kernel(h)
@@ -222,6 +254,23 @@ def inverse_twisted_dft_longdouble(bins) -> np.ndarray:
     hi = np.floor(r / two32)                       # exact: |r| < 2^64 is an integer of at most 64 bits
     lo = r - hi * two32
     return (hi.astype(np.int64).view(np.uint64) << U(32)) + lo.astype(np.int64).view(np.uint64)
+
+
+def forward_twisted_dft_longdouble(p_signed) -> np.ndarray:
+    """The N/2 transform bins (natural order) of the polynomial with the exact signed integer coefficients `p_signed` (..., N),
+    |p| <= 2^63, by a direct O(N^2) sum in np.longdouble (np.clongdouble out): the counterpart of the inverse above,
+    X_m = sum_j (p_j + i p_{j+N/2}) e^{i pi (j - 4 j m) / N}.  The angles are those of _inverse_kernel negated (reduced mod 2N in
+    integers there); a 64-bit mantissa holds every coefficient without loss."""
+    p = np.asarray(p_signed)
+    assert p.dtype == np.int64, p.dtype
+    h = p.shape[-1] // 2
+    ld = np.longdouble
+    cr, ci = _inverse_kernel(h)                    # cos, sin of pi (4 j m - j) / N at [j, m]
+    zr, zi = p[..., :h].astype(ld), p[..., h:].astype(ld)
+    out = np.empty(zr.shape, dtype=np.clongdouble)
+    out.real = zr @ cr + zi @ ci
+    out.imag = zi @ cr - zr @ ci
+    return out
 
 
 # ----------------------------------------------------------------------------------------------- GGSW (x) GLWE
@@ -266,6 +315,24 @@ def multiply_glwe_ggsw(glwe, ggsw, radix_log: int, count: int, be=EXACT) -> np.n
 def blind_rotate_step(acc, a_tilde: int, ggsw, radix_log: int, count: int, be=EXACT) -> np.ndarray:
     """acc <- cmux(acc, acc * X^a~, GGSW(s_i))   (ops/bootstrapping/programmable_bootstrapping.rs:342-410)"""
     return cmux(acc, mul_monomial(acc, a_tilde), ggsw, radix_log, count, be)
+
+
+def rotate_cmux_step(acc, r: int, ggsw, radix_log: int, count: int, be=EXACT) -> np.ndarray:
+    """one step of the rotation by an encrypted shift: acc <- cmux(acc, acc * X^-r, GGSW(bit))   (blind_rotation.rs:216-221)"""
+    return cmux(acc, mul_monomial(acc, -r), ggsw, radix_log, count, be)
+
+
+def blind_rotation_by_shift(glwe, shift_ggsws, log_stride: int, radix_log: int, count: int, be=EXACT, steps=None) -> np.ndarray:
+    """glwe * X^-(s << log_stride), s given as the GGSWs of its bits, least significant first (n_bits, k+1, L, k+1, N): step i
+    rotates by r = 2^(i + log_stride), i ascending (ops/bootstrapping/blind_rotation.rs:202-223; the reference has log_stride 0).
+    A list given as `steps` receives (accumulator before the step, r) for every step."""
+    acc = _u(glwe)
+    for i, g in enumerate(shift_ggsws):
+        r = 1 << (i + log_stride)
+        if steps is not None:
+            steps.append((acc, r))
+        acc = rotate_cmux_step(acc, r, g, radix_log, count, be)
+    return acc
 
 
 def generalized_pbs(lwe, lut_glwe, bsk, radix_log: int, count: int, log_chi=0, log_v=0, body_rotate=0, be=EXACT, steps=None):

@@ -4,10 +4,12 @@ bring integer key rows into the transform domain (key preparation) and for its p
 
 A tier-A case is one key (uniform or shaped time-domain rows, NOT an encryption of anything) and a few input items; a
 structural deviation (level order, row, sign, rotation) then moves every output word by a uniform amount, distance ~ 1/4.
-Where the bounds come from is written in profiles/r07_fft_error.md; the model is
+Where the bounds come from is written in profiles/r07_fft_error.md (the rotation by an encrypted shift, the forward transform
+and the packed operations: profiles/r14_exact_reference_new_ops.md); the model is
     sigma_model = 2^(beta - 1 - 53) * sqrt(T * N)     of the torus,
 T digit x key polynomial products of radix 2^beta summed into one output polynomial.
 """
+import functools
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -165,6 +167,47 @@ def glev_of(c: Case):
     return a, b
 
 
+# ----------------------------------------------------------------------------------------------- tier A: rotate-fused CMUX
+
+ROT_SEED = 0        # last word of the rng seed of rot_cases; chosen for the oracle's |z| <= 3 in the uniform case, see the note
+
+
+def rot_cases(cls: str):
+    """one step of the rotation by an encrypted shift at DEFAULT_128, cbs radix 4 x 4 (the rotate-fused kernels' only shape).
+    Item = (acc (k+1, N), r): the step is cmux(acc, X^-r acc, key); uniform accumulators go through r = 1, 2, 64 and N/2.
+    The decomposed words are X^-r acc - acc and cannot be chosen freely, and r <= N/2 rules out pbs_cases' X^N; the shaped
+    classes use r = N/2 and acc = -(X^(-N/2) + 1) (w >> 1): since
+    (X^(-N/2) - 1)(X^(-N/2) + 1) = X^-N - 1 = -2, the decomposed words are 2 (w >> 1), the wanted w up to its lowest bit."""
+    P = D128
+    n, k, lb, cnt = P.N, P.k, P.cbs_radix_log, P.cbs_count
+    rng = np.random.default_rng([0xA4, n, k, lb, CLASSES.index(cls), ROT_SEED])
+    out = []
+    for label, key in _key_variants(cls, (k + 1, cnt, k + 1), n, rng):
+        c = Case(f"rot-default128_4x4-{cls}{'-' + label if label else ''}", cls, P, key, sigma=sigma_model(lb, (k + 1) * cnt, n))
+        if cls in ("uniform", "small"):
+            accs = rng.integers(0, 1 << 64, (4, k + 1, n), dtype=np.uint64)
+            c.items = [(acc, r) for r in (1, 2, 64, n // 2) for acc in accs]    # a launch takes one r: four distinct items each
+        else:
+            for w in _shaped_polys(cls, label, lb, cnt, (k + 1,), n, rng):
+                half = w >> np.uint64(1)
+                acc = np.uint64(0) - (R.mul_monomial(half, -(n // 2)) + half)
+                assert np.array_equal(R.mul_monomial(acc, -(n // 2)) - acc, half << np.uint64(1))
+                c.items.append((acc, n // 2))
+        out.append(c)
+    return out
+
+
+def rot_exact(c: Case, item, be=R.EXACT):
+    return R.rotate_cmux_step(item[0], item[1], c.key, c.P.cbs_radix_log, c.P.cbs_count, be)
+
+
+def rot_oracle(c: Case, item, g):
+    """the oracle's statement of the step: glwe_mul_xn by 2N - r, then cmux"""
+    P, (acc, r) = c.P, item
+    high = O.glwe_mul_xn(acc.reshape(-1), 2 * P.N - r, P.N, P.k)
+    return O.cmux(acc.reshape(-1), high, g, P.N, P.k, P.cbs_radix_log, P.cbs_count).reshape(acc.shape)
+
+
 # ----------------------------------------------------------------------------------------------- tier A: scheme switch
 
 
@@ -210,6 +253,7 @@ MEASURED_ABOVE_1_5 = {
     "pbs-N128k2-one_bin-bin63": (1.868, 1.615),
     "pbs-N256k3-one_bin-bin3": (1.686, 0.958),
     "cmux-default128_4x4-one_bin-bin3": (1.527, 0.952),
+    "rot-default128_4x4-one_bin-bin3": (1.527, 0.952),      # profiles/r14_exact_reference_new_ops.md
     "cmux-N128k2_3x4-extreme-key2^63": (1.627, 1.500),
     "cmux-N128k2_3x4-one_bin-bin0": (1.928, 1.696),
     "cmux-N128k2_3x4-one_bin-bin63": (1.868, 1.615),
@@ -333,6 +377,144 @@ def rotation_inputs(P, seed: int, count: int):
     rng = np.random.default_rng([0xB2, seed, P.N])
     return (rng.integers(0, 1 << 64, (count, P.lwe_n + 1), dtype=np.uint64),
             rng.integers(0, 1 << 64, (count, P.k + 1, P.N), dtype=np.uint64))
+
+
+# ----------------------------------------------------------------------------------------------- tier B: rotation by an encrypted shift
+
+# name -> (parameters, n_bits, log_stride, the shifts of the four items, seed of keys / inputs / selectors).  The second shape is
+# the table lookup's (16 entries of stride 8) and the other ping-pong parity.  Seeds: the oracle's |z| <= 3, see the note.
+ENC_SHIFT_SHAPES = {"default128_11bit": (D128, 11, 0, (0, 1, 1365, 2047), 7),
+                    "default128_4bit_stride8": (D128, 4, 3, (0, 5, 10, 15), 11)}
+
+
+def bit_ggsws(rng, hk, value: int, n_bits: int) -> np.ndarray:
+    """honest GGSWs (cbs radix, time domain) of the bits of `value`, least significant first: (n_bits, k+1, L, k+1, N)"""
+    P = hk.P
+    const = np.zeros(P.N, dtype=np.uint64)
+    out = []
+    for i in range(n_bits):
+        const[0] = (value >> i) & 1
+        out.append(R.ggsw_encrypt(rng, hk.glwe_sk, const, P.N, P.k, P.cbs_radix_log, P.cbs_count, NOISE))
+    return np.stack(out)
+
+
+@dataclass
+class EncShiftCase:
+    name: str
+    P: object
+    n_bits: int
+    log_stride: int
+    shifts: tuple
+    hk: HonestKeys
+    glwe: np.ndarray                # (items, k+1, N)
+    sel: np.ndarray                 # (items, n_bits, k+1, L, k+1, N), time domain
+    exact: np.ndarray = None        # phases of the exact chain and of the numpy chain, (items, N)
+    numpy: np.ndarray = None
+    steps: list = None              # for every item: [(exact accumulator before step j, r_j)], and the exact result last, (acc, None)
+
+
+_ENC_SHIFT = {}
+
+
+def enc_shift_case(shape: str) -> EncShiftCase:
+    """the case of a shape with both chains run, built once in a process; the functional condition is asserted on the exact
+    chain here: its phase is the input's times X^-(s << log_stride) within 2^-8 of the torus (the gadget's 16 bits over up to 11
+    steps, a property of the scheme: measured 2^-9.2 at worst)"""
+    if shape not in _ENC_SHIFT:
+        P, n_bits, log_stride, shifts, seed = ENC_SHIFT_SHAPES[shape]
+        hk = honest_keys(P, seed)
+        rng = np.random.default_rng([0xB3, seed, P.N, n_bits])
+        c = EncShiftCase(f"encshift-{shape}", P, n_bits, log_stride, shifts, hk, honest_glwes(P, hk, seed, len(shifts)),
+                         np.stack([bit_ggsws(rng, hk, s, n_bits) for s in shifts]))
+        c.steps = [[] for _ in shifts]
+        chain = lambda be, steps: R.glwe_phase(np.stack([R.blind_rotation_by_shift(  # noqa: E731
+            c.glwe[i], c.sel[i], log_stride, P.cbs_radix_log, P.cbs_count, be, steps and steps[i]) for i in range(len(shifts))]), hk.glwe_sk)
+        c.exact, c.numpy = chain(R.EXACT, c.steps), chain(R.NUMPY, None)
+        for i, st in enumerate(c.steps):
+            st.append((R.blind_rotation_by_shift(st[-1][0], c.sel[i][-1:], st[-1][1].bit_length() - 1, P.cbs_radix_log, P.cbs_count), None))
+        check_rotated_phase(c, c.exact, "exact")
+        _ENC_SHIFT[shape] = c
+    return _ENC_SHIFT[shape]
+
+
+def enc_shift_oracle(c: EncShiftCase, i: int, sel_fft, glwe=None) -> np.ndarray:
+    """the oracle's loop for item i (or for `glwe` under item i's selectors): glwe_mul_xn by 2N - 2^(step + log_stride), then
+    cmux, steps ascending; sel_fft (n_bits, bins)"""
+    P = c.P
+    acc = (c.glwe[i] if glwe is None else glwe).reshape(-1)
+    for step in range(c.n_bits):
+        high = O.glwe_mul_xn(acc, 2 * P.N - (1 << (step + c.log_stride)), P.N, P.k)
+        acc = O.cmux(acc, high, sel_fft[step], P.N, P.k, P.cbs_radix_log, P.cbs_count)
+    return acc.reshape(P.k + 1, P.N)
+
+
+def check_step_bias(c: EncShiftCase, step, who: str):
+    """The bias of the chain, asserted on WORDS as tests/test_polynomial_reference.py's rotation_case does: every step restarted
+    from the exact accumulator by `step(item, j, acc, r)`, its signed word error against the exact next accumulator pooled over all
+    steps of all items.  Word errors of a step are independent roundings; a bias of b a step would grow to n_bits b over the chain.
+    (The phases' own mean is no such statistic: every mask error enters every phase coefficient through the same key.)"""
+    d = []
+    for i, st in enumerate(c.steps):
+        for j in range(c.n_bits):
+            d.append(R.signed_difference(step(i, j, st[j][0], st[j][1]), st[j + 1][0]))
+    d = np.concatenate(d, axis=None)
+    z = d.mean() / (d.std() / np.sqrt(d.size))
+    print(f"{c.name:44s} {who:6s} per-step word bias over {d.size} words: rms 2^{np.log2(d.std()):.2f}  mean/(rms/sqrt n) {z:6.2f}")
+    assert 0.0 < d.std() <= 2.0 ** 2.5 * sigma_model(c.P.cbs_radix_log, (c.P.k + 1) * c.P.cbs_count, c.P.N), (c.name, who, d.std())
+    assert abs(z) <= 6.0, (c.name, who, z)
+
+
+def check_rotated_phase(c: EncShiftCase, phase, who: str):
+    """the chain means what it should: phase_in * X^-(s << log_stride), within 2^-8"""
+    want = np.stack([R.mul_monomial(R.glwe_phase(c.glwe[i], c.hk.glwe_sk), -(s << c.log_stride)) for i, s in enumerate(c.shifts)])
+    d = float(R.torus_distance(phase, want).max())
+    print(f"{c.name:44s} {who:6s} distance to the rotated input phase: max 2^{np.log2(d):.2f}")
+    assert d <= 2.0 ** -8, (c.name, who, d)
+
+
+# ----------------------------------------------------------------------------------------------- the forward transform
+
+FFT_SIZES = (2048, 256, 16)
+
+
+def fft_cases(n: int):
+    """[(name, polynomials (P, N) uint64)] for the forward transform alone.  A delta has a single twiddle in every bin: it reads
+    the tables directly."""
+    rng = np.random.default_rng([0xA5, n])
+    delta = np.zeros((8, n), dtype=np.uint64)
+    at = (0, 1, 3, n // 3, n // 2 - 1, n // 2, n // 2 + 1, n - 1)
+    assert len(set(at)) == 8
+    delta[np.arange(8), at] = 1 << 62
+    return [(f"fft-N{n}-uniform", rng.integers(0, 1 << 64, (8, n), dtype=np.uint64)),
+            (f"fft-N{n}-small", rng.integers(0, 1 << 20, (3, n), dtype=np.uint64)),
+            (f"fft-N{n}-delta", delta),
+            (f"fft-N{n}-const2^63", np.full((1, n), 1 << 63, dtype=np.uint64)),
+            (f"fft-N{n}-one_bin", np.stack([cos_poly(n, m, (1 << 63) - 1) for m in (0, 3, n // 2 - 1)]))]
+
+
+@functools.lru_cache(maxsize=None)
+def fft_references(n: int):
+    """{name: (long-double bins, numpy bins)} of fft_cases(n), computed once in a process"""
+    return {name: (R.forward_twisted_dft_longdouble(R.signed(p)), R.NUMPY.forward_bins(R.signed(p))) for name, p in fft_cases(n)}
+
+
+def forward_error(bins, exact):
+    """|X - X_exact| of every bin over the rms bin magnitude of its polynomial: (rms, max) over the case"""
+    exact = np.asarray(exact, dtype=np.clongdouble)
+    e = np.abs(np.asarray(bins).astype(np.clongdouble) - exact) / np.sqrt((np.abs(exact) ** 2).mean(axis=-1, keepdims=True))
+    return float(np.sqrt((e ** 2).mean())), float(e.max())
+
+
+def check_forward(name: str, bins, exact, numpy_bins, who: str):
+    """the transform's error against the long-double DFT, held to the numpy yardstick's on the same inputs: rms <= 2 x, max <= 4 x
+    (measured for the oracle: rms ratio <= 1.1, max ratio <= 2.1; the max is one sample's, hence the factor two over it)"""
+    rms, mx = forward_error(bins, exact)
+    nrms, nmx = forward_error(numpy_bins, exact)
+    print(f"{name:44s} {who:6s} rms {rms:9.3e} max {mx:9.3e}  numpy rms {nrms:9.3e} max {nmx:9.3e}  "
+          f"ratio {rms / nrms if nrms else float('nan'):6.3f} / {mx / nmx if nmx else float('nan'):6.3f}")
+    assert rms <= 2.0 * nrms, (name, who, rms, nrms)
+    assert mx <= 4.0 * nmx, (name, who, mx, nmx)
+    return rms, mx, nrms, nmx
 
 
 # ----------------------------------------------------------------------------------------------- the model across shapes

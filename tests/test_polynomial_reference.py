@@ -2,7 +2,8 @@
 shares nothing with the oracle (CPU only; the HIP kernels meet the same expectations in tests/test_gpu_polynomial_reference.py).
 
 Tier A: single operations under uniform / shaped time-domain "keys", distance word by word.  Tier B: chains under honest
-integer keys, distance between exact phases.  Bounds and their origin: tests/polyref_cases.py, profiles/r07_fft_error.md.
+integer keys, distance between exact phases.  Bounds and their origin: tests/polyref_cases.py, profiles/r07_fft_error.md,
+profiles/r14_exact_reference_new_ops.md.
 Run with -s to see every figure."""
 import ast
 import json
@@ -231,3 +232,135 @@ def test_circuit_bootstrap_feeding_an_exact_cmux_against_the_exact_chain():
     # and the chain means what it should: the phase of the selected ciphertext (uniform message words), up to the noise of a
     # circuit-bootstrapped selector at 4 x 4 bits (measured 2^-15.4; a wrong selection is a uniform distance, 1/4 on average)
     assert R.torus_distance(ex, np.stack(want)).max() < 2.0 ** -10
+
+
+# ----------------------------------------------------------------------------------------------- rotation by an encrypted shift
+
+
+@pytest.mark.parametrize("cls", C.CLASSES)
+def test_rotate_cmux_step_against_exact_arithmetic(cls):
+    for c in C.rot_cases(cls):
+        g = C.key_fft(c.key)
+        C.check_tier_a(c, [C.rot_oracle(c, it, g) for it in c.items], [C.rot_exact(c, it) for it in c.items],
+                       [C.rot_exact(c, it, R.NUMPY) for it in c.items], "oracle")
+
+
+@pytest.mark.parametrize("shape", list(C.ENC_SHIFT_SHAPES))
+def test_encrypted_shift_rotation_phases_against_the_exact_chain(shape):
+    c = C.enc_shift_case(shape)             # asserts that the exact chain rotates the input's phase
+    # (the issue of the bias condition on these phases, and why the seed of a shape is chosen: profiles/r14_exact_reference_new_ops.md)
+    got = np.stack([C.enc_shift_oracle(c, i, C.key_fft(c.sel[i]).reshape(c.n_bits, -1)) for i in range(len(c.shifts))])
+    C.check_tier_b(c.name, R.glwe_phase(got, c.hk.glwe_sk), c.exact, c.numpy, "oracle")
+    sel = [C.key_fft(g).reshape(c.n_bits, -1) for g in c.sel]
+    P = c.P
+    C.check_step_bias(c, lambda i, j, acc, r: O.cmux(acc.reshape(-1), O.glwe_mul_xn(acc.reshape(-1), 2 * P.N - r, P.N, P.k), sel[i][j],
+                                                     P.N, P.k, P.cbs_radix_log, P.cbs_count).reshape(acc.shape), "oracle")
+
+
+# ----------------------------------------------------------------------------------------------- the forward transform
+
+
+@pytest.mark.parametrize("n", C.FFT_SIZES)
+def test_forward_transform_against_the_long_double_dft(n):
+    refs = C.fft_references(n)
+    for name, polys in C.fft_cases(n):
+        C.check_forward(name, np.stack([O.poly_fft(p) for p in polys]), *refs[name], "oracle")
+    # the two long-double transforms are inverses of each other, word for word.  Their round trip's own rounding is about 2^-60
+    # of the coefficients' magnitude (two N/2-term sums at a 64-bit mantissa; up to 16 words on full 64-bit coefficients at
+    # N = 2048), so the polynomial is uniform below 2^55: 2^-5 of a word
+    p = np.random.default_rng([0xA6, n]).integers(-(1 << 55), 1 << 55, n, dtype=np.int64)
+    assert np.array_equal(R.inverse_twisted_dft_longdouble(R.forward_twisted_dft_longdouble(p)), p.view(np.uint64))
+    # and a delta at coefficient 1 has the twiddle e^{i pi (1 - 4m) / N} in bin m
+    d = np.zeros(n, dtype=np.int64)
+    d[1] = 1 << 62
+    m = np.arange(n // 2)
+    want = 2.0 ** 62 * np.exp(1j * np.pi * ((1 - 4 * m) % (2 * n)) / n)
+    assert np.abs(R.forward_twisted_dft_longdouble(d).astype(np.complex128) - want).max() <= 2.0 ** 62 * 2.0 ** -50
+
+
+# ----------------------------------------------------------------------------------------------- packed integers
+
+
+def test_pack_unpack_and_bivariate_pack_statements():
+    """the oracle has no pack, unpack or bivariate packing of its own: the project states them with its glwe_mul_xn + glwe_xor
+    tree (tests/test_packed_plaintext.py), its sample_extract, and a wrapping multiply-add (tests/test_gpu_bivariate.py)"""
+    from tests.test_packed_plaintext import oracle_tree_pack
+    for P in (C.D128, C.N128K2):
+        n, k = P.N, P.k
+        rng = np.random.default_rng([0xA7, n, k])
+        for n_bits in (1, 16, n):
+            bits = rng.integers(0, 1 << 64, (n_bits, k + 1, n), dtype=np.uint64)
+            packed = R.pack(bits)
+            if n_bits <= 16 or n <= 128:        # the tree costs a glwe_mul_xn for each bit
+                assert np.array_equal(packed.reshape(-1), oracle_tree_pack(bits.reshape(n_bits, -1), n, k)), (n, n_bits)
+            lwes = R.unpack(packed, n_bits)
+            assert lwes.shape == (n_bits, k * n + 1)
+            for i in sorted({0, n_bits // 2, n_bits - 1}):
+                assert np.array_equal(lwes[i], O.sample_extract(packed.reshape(-1), i, n, k)), (n, n_bits, i)
+        # honest encryptions of constant polynomials: the packed phase carries bit i in coefficient i, and unpacking returns it
+        sk = R.binary_key(rng, k * n)
+        value = [int(b) for b in rng.integers(0, 2, 16)]
+        msgs = np.zeros((16, n), dtype=np.uint64)
+        msgs[:, 0] = np.array(value, dtype=np.uint64) << np.uint64(63)
+        packed = R.pack(R.glwe_encrypt(rng, sk, msgs, C.NOISE))
+        ph = R.glwe_phase(packed, sk)
+        want = np.zeros(n, dtype=np.uint64)
+        want[:16] = msgs[:, 0]
+        assert R.torus_distance(ph, want).max() <= 16 * C.NOISE / 2.0 ** 64
+        for i, lwe in enumerate(R.unpack(packed, 16)):
+            assert (lwe[-1:] - (lwe[:-1] * sk).sum(dtype=np.uint64, keepdims=True))[0] == ph[i]
+    left, right = rng.integers(0, 1 << 64, (2, 5, 638), dtype=np.uint64)
+    for p in (1, 2, 7, 63):
+        want = [[(int(a) * (1 << p) + int(b)) & M64 for a, b in zip(ra, rb)] for ra, rb in zip(left, right)]
+        assert R.bivariate_pack(left, right, p).tolist() == want, p
+
+
+# ----------------------------------------------------------------------------------------------- the new conditions bite
+
+
+def _must_fail(what: str, check) -> str:
+    """the check raises an AssertionError for the wrong variant; its message is printed (profiles/r14_exact_reference_new_ops.md)"""
+    with pytest.raises(AssertionError) as e:
+        check()
+    print(f"bites: {what}: {str(e.value).splitlines()[0][:160]}")
+    return str(e.value)
+
+
+def test_the_new_conditions_bite():
+    """wrong variants built from poly_ref's own pieces in EXACT arithmetic (or numpy's transform), so that the structure alone is
+    wrong: each must fail the condition that holds the oracle and the kernels"""
+    c = C.rot_cases("uniform")[0]
+    lb, cnt = c.P.cbs_radix_log, c.P.cbs_count
+
+    def no_flip(acc, r):
+        return np.roll(acc, -r, axis=-1)
+
+    wrong_steps = {"r + 1 for r": lambda acc, r: R.mul_monomial(acc, -(r + 1)),
+                   "no sign flip at the wrap": no_flip,
+                   "X^+r for X^-r": lambda acc, r: R.mul_monomial(acc, r)}
+    for what, high in wrong_steps.items():
+        for it in c.items[::4]:             # every r on its own: r = 1 moves a single coefficient of each polynomial past the wrap
+            one = C.Case(c.name, c.cls, c.P, c.key, [it], c.sigma)
+            bad = R.cmux(it[0], high(*it), c.key, lb, cnt)
+            _must_fail(f"{what}, r = {it[1]}",
+                       lambda: C.check_tier_a(one, [bad], [C.rot_exact(one, it)], [C.rot_exact(one, it, R.NUMPY)], "wrong"))
+
+    e = C.enc_shift_case("default128_4bit_stride8")
+    P = e.P
+    bad = R.glwe_phase(np.stack([R.blind_rotation_by_shift(e.glwe[i], e.sel[i][::-1], e.log_stride, P.cbs_radix_log, P.cbs_count)
+                                 for i in range(len(e.shifts))]), e.hk.glwe_sk)
+    # (shifts 0 and 15 read the same backwards and still rotate as they should; 5 and 10 are each other's reverse)
+    _must_fail("bits consumed in descending order, against the exact chain", lambda: C.check_tier_b(e.name, bad, e.exact, e.numpy, "wrong"))
+    _must_fail("bits consumed in descending order, against the rotated input", lambda: C.check_rotated_phase(e, bad, "wrong"))
+
+    for n in C.FFT_SIZES:
+        refs = C.fft_references(n)
+        tw = np.exp(1j * np.pi * np.arange(n // 2) / n)
+        tw[3] *= 1.0 + 2.0 ** -40
+        h = n // 2
+        rev = np.array([int(format(m, f"0{h.bit_length() - 1}b")[::-1], 2) for m in range(h)])
+        for name, polys in C.fft_cases(n):
+            exact, nb = refs[name]
+            _must_fail(f"{name}: one twist entry off by 2^-40",       # entry 3: the delta at coefficient 3 reads it in every bin
+                       lambda: C.check_forward(name, R.NUMPY.forward_bins(R.signed(polys), tw), exact, nb, "wrong"))
+            _must_fail(f"{name}: bins in bit-reversed order", lambda: C.check_forward(name, nb[..., rev], exact, nb, "wrong"))
