@@ -18,7 +18,8 @@
 //     (everything that arrives during kernel k, and the callers of batch k coming straight back, is batch k + 1), and enqueues
 //     host-to-device copy, kernels and device-to-host copy on three streams tied by events: the copies of batch k + 1
 //     and k - 1 run under the kernels of batch k;
-//   * a completion thread waits for each batch's last event and wakes its waiters — through ONE futex word per batch, not
+//   * a completion thread waits for each batch's last event and wakes its waiters — through futex words of the BATCH (one per
+//     64 slots by host pointers, one per group of eight by handle: spf_wake.hpp holds both protocols), not
 //     a condition variable of the pool: a thousand sleeping callers on one condition variable + mutex cost 24 s of kernel
 //     time per 1.9 s of wall time (a wake storm per batch, then a convoy on the mutex) and ran the process into its CPU
 //     quota (tools/pool_probe.py: 15 of 18 scheduler periods throttled); the pool's mutex is held for a few hundred
@@ -50,6 +51,7 @@
 // every batch whose operands came out of it).
 #pragma once
 #include "../../include/spf_hip.h"
+#include "spf_wake.hpp"
 
 #include <algorithm>
 #include <map>
@@ -57,9 +59,6 @@
 #include <atomic>
 #include <chrono>
 #include <climits>
-#include <linux/futex.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 #include <condition_variable>
 #include <cstring>
 #include <deque>
@@ -111,8 +110,8 @@ struct Staging {
     size_t scr_cap = 0;       // operations the intermediates are sized for
 };
 
-inline void futex_wait(std::atomic<uint32_t>* w, uint32_t expected);
-inline void futex_wake_all(std::atomic<uint32_t>* w);
+using spf_wake::futex_wait; // (spf_wake.hpp: the futex helpers and the two protocols the waiters sleep by)
+using spf_wake::futex_wake_all;
 // The pool's mutex.  Its critical sections are a few hundred nanoseconds (slot bookkeeping) but dozens of callers reach them in
 // the same microseconds — the gates of one circuit level returning from their wait and submitting the next (r06: with a plain
 // pthread mutex every one of them slept on the futex and was woken in turn, a convoy of ~10 us per caller: 300 us per level of a
@@ -147,15 +146,6 @@ struct PoolMutex {
     }
 };
 
-inline void futex_wait(std::atomic<uint32_t>* w, uint32_t expected)
-{
-    (void)syscall(SYS_futex, reinterpret_cast<uint32_t*>(w), FUTEX_WAIT_PRIVATE, expected, nullptr, nullptr, 0);
-}
-inline void futex_wake_all(std::atomic<uint32_t>* w)
-{
-    (void)syscall(SYS_futex, reinterpret_cast<uint32_t*>(w), FUTEX_WAKE_PRIVATE, INT_MAX, nullptr, nullptr, 0);
-}
-
 struct Batch {
     int op = 0, set = 0, lane = 0; // lane = ((by handle ? N_OPS : 0) + op) * kMaxGroups + caller group
     bool by_handle = false;
@@ -176,18 +166,11 @@ struct Batch {
     int64_t depth = 0;
     int rank = 0; // bootstrap batches on the longest path to the batch's operations (part of its key: see submit_impl)
     std::vector<std::shared_ptr<Batch>> deps;
-    // The outputs leave the GPU in up to kMaxChunks copies (each a multiple of kWordSlots slots, all but the last equal), each with
-    // its own event.  The waiters sleep on the word of their slot group (futex, 0 -> 1 when the group's bytes are in pinned
-    // memory or the batch failed): the callers of the first chunk copy out and come back while the later chunks are still
-    // crossing PCIe.  (Words per 64 slots rather than per chunk: a waiter may go to sleep before the batch is closed, when
-    // its size — and so the chunk boundaries — is not known yet.)
-    static constexpr size_t kWordSlots = 64;
-    static constexpr int kMaxWords = 64; // 4096 slots; the last word also takes whatever lies beyond
-    static constexpr int kMaxChunks = 16;
-    static int word_of(size_t slot) { return (int)std::min<size_t>(slot / kWordSlots, kMaxWords - 1); }
-    std::atomic<uint32_t> chunk_word[kMaxWords] = {};
-    size_t chunk_slots = 0; // slots per copy (set with n_chunks)
-    int n_chunks = 0; // set when the batch is enqueued
+    // How the waiters sleep and are woken is spf_wake.hpp's: host-pointer batches wake a word per 64 slots as each of up to
+    // kMaxChunks copies of the outputs arrives (`words`), batches by handle wake groups of eight as a tree (`tree`).
+    static constexpr int kMaxChunks = spf_wake::ChunkWords::kMaxChunks;
+    spf_wake::ChunkWords words;
+    spf_wake::GroupTree tree; // by handle (init: when the batch is opened)
     std::atomic<spf_status> st{SPF_OK}; // (atomic: the completion thread may still record a late copy failure while the waiters
                                         // of an earlier chunk read it)
     std::chrono::steady_clock::time_point t0, t_last, t_done, t_close, t_enq, t_ready, t_sync;
@@ -200,45 +183,6 @@ struct Batch {
             if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
         for (hipEvent_t& e : ev_chunk)
             if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    }
-    void wake_word(int w)
-    {
-        chunk_word[w].store(1, std::memory_order_release);
-        futex_wake_all(&chunk_word[w]);
-    }
-    // By handle the waiters are woken as a TREE: they sleep in groups of eight on a word per group; whoever completes the batch
-    // sets every word, wakes group 0, and every waiter that comes through wakes one child group (group g's member j: group
-    // 8 g + 1 + j) before it goes on.  One thread waking a thousand sleepers one by one took 6 us each (r06: 1.5 ms of a 256-caller
-    // batch's 5.8 ms cycle); the tree is three levels deep.  The completing thread also walks all groups in order and wakes what
-    // nobody has woken yet, so a waiter that never comes (an abandoned ticket) leaves no group asleep.
-    static constexpr size_t kTreeGroup = 8;
-    std::unique_ptr<std::atomic<uint32_t>[]> gword, gwoken, gsleep; // by handle: [cap / 8 + 1]
-    size_t n_groups() const { return (n + kTreeGroup - 1) / kTreeGroup; }
-    // a waiter announces itself in gsleep before it looks at the word for the last time; the waker sets the word before it looks at
-    // gsleep (both sequentially consistent): a group nobody sleeps on costs no system call — operations pushed without a ticket have
-    // no waiters at all, and a batch of 400 of them was 50 futex calls of ~2 us on the launcher's critical path
-    void sleep_on_group(size_t g)
-    {
-        gsleep[g].fetch_add(1, std::memory_order_seq_cst);
-        while (gword[g].load(std::memory_order_seq_cst) == 0) futex_wait(&gword[g], 0);
-    }
-    void wake_group(size_t g)
-    {
-        if (gwoken[g].exchange(1, std::memory_order_acq_rel) == 0 && gsleep[g].load(std::memory_order_seq_cst) != 0) futex_wake_all(&gword[g]);
-    }
-    void wake_tree() // by the thread that completed the batch (n is final)
-    {
-        const size_t ng = n_groups();
-        for (size_t g = 0; g < ng; g++) gword[g].store(1, std::memory_order_seq_cst);
-        for (size_t g = 0; g < ng; g++) wake_group(g);
-    }
-    void wake_chunk(int i) // the words of copy i
-    {
-        // (the last word stands for every slot from 64 * (kMaxWords - 1) on, however many: only the last copy wakes it)
-        const int w0 = word_of((size_t)i * chunk_slots);
-        const int w1 = i + 1 < n_chunks ? std::min(word_of((size_t)(i + 1) * chunk_slots - 1), kMaxWords - 2) : kMaxWords - 1;
-        for (int w = w0; w <= w1; w++)
-            if (chunk_word[w].load(std::memory_order_relaxed) == 0) wake_word(w);
     }
 };
 
@@ -579,11 +523,7 @@ struct spf_pool {
                         const size_t cap = std::min(batch_cap(op), std::max<size_t>(cap_hint[kind], 64));
                         b = std::make_shared<Batch>();
                         b->slots.resize(cap);
-                        const size_t ng = cap / Batch::kTreeGroup + 1;
-                        b->gword.reset(new std::atomic<uint32_t>[ng]);
-                        b->gwoken.reset(new std::atomic<uint32_t>[ng]);
-                        b->gsleep.reset(new std::atomic<uint32_t>[ng]);
-                        for (size_t g = 0; g < ng; g++) { b->gword[g].store(0); b->gwoken[g].store(0); b->gsleep[g].store(0); }
+                        b->tree.init(cap);
                         b->op = op; b->set = -1; b->cap = cap; b->lane = lane; b->param = param; b->by_handle = true;
                         b->deferred = true; b->depth = depth; b->rank = rank;
                         const bool first = deferred.empty() && deferred_full.empty();
@@ -636,13 +576,7 @@ struct spf_pool {
             try {
                 b = std::make_shared<Batch>();
                 b->slots.resize(cap); // (never grows: a slot's address is stable, its owner reads it without the mutex)
-                if (by_handle) {
-                    const size_t ng = cap / Batch::kTreeGroup + 1;
-                    b->gword.reset(new std::atomic<uint32_t>[ng]);
-                    b->gwoken.reset(new std::atomic<uint32_t>[ng]);
-                        b->gsleep.reset(new std::atomic<uint32_t>[ng]);
-                    for (size_t g = 0; g < ng; g++) { b->gword[g].store(0); b->gwoken[g].store(0); b->gsleep[g].store(0); }
-                }
+                if (by_handle) b->tree.init(cap);
             } catch (const std::exception&) {
                 sets[set].busy = false;
                 cv_set.notify_all();
@@ -940,13 +874,12 @@ struct spf_pool {
             if (!b->closed) flush_deferred();
         }
         if (b->by_handle) {
-            const size_t g = slot / Batch::kTreeGroup;
-            std::atomic<uint32_t>& word = b->gword[g];
+            const size_t g = spf_wake::GroupTree::group_of(slot);
             if (!is_heavy && spin_us > 0) {
                 // a cheap operation is back in tens of microseconds: look for a moment before going to sleep (a sleeping thread
                 // costs its waker a system call and itself a wake-up, ~40 us end to end on the bench's host)
                 const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(spin_us);
-                for (int i = 0; word.load(std::memory_order_acquire) == 0; i++) {
+                for (int i = 0; !b->tree.is_set(g); i++) {
                     for (int k = 0; k < 32; k++) __builtin_ia32_pause();
                     if ((i & 7) == 7) {
                         if (std::chrono::steady_clock::now() >= until) break;
@@ -954,12 +887,9 @@ struct spf_pool {
                     }
                 }
             }
-            if (word.load(std::memory_order_acquire) == 0) b->sleep_on_group(g);
-            const size_t child = Batch::kTreeGroup * g + 1 + slot % Batch::kTreeGroup; // this waiter's share of the waking
-            if (child < b->n_groups()) b->wake_group(child);
+            b->tree.wait_slot(slot); // sleeps unless the word is set, then does this waiter's share of the waking
         } else {
-            std::atomic<uint32_t>& word = b->chunk_word[Batch::word_of(slot)];
-            while (word.load(std::memory_order_acquire) == 0) futex_wait(&word, 0);
+            b->words.wait_slot(slot);
         }
         const spf_status st = b->st;
         if (!b->by_handle) {
@@ -1011,10 +941,7 @@ struct spf_pool {
                 // closed instead of sitting out the quiet time; spf_pool_wait, the blocking callers' way, leaves it to gather)
                 else if (b && !b->deferred && !b->closed && filling[b->lane] == b) close_batch(b->lane);
             }
-            if (b) {
-                const size_t g = v->slot / Batch::kTreeGroup;
-                if (b->gword[g].load(std::memory_order_acquire) == 0) b->sleep_on_group(g);
-            }
+            if (b) b->tree.wait_value(v->slot);
         }
         const int st = v->state.load(std::memory_order_acquire);
         return st == spf_value_impl::READY ? SPF_OK : (st == spf_value_impl::FAILED ? SPF_ERR_HIP : SPF_ERR_INVALID_ARGUMENT);
@@ -1107,15 +1034,10 @@ struct spf_pool {
         // (timing events on purpose: with hipEventDisableTiming the same run gave 32.8 k instead of 46.2 k operations per second at 256
         // callers — hipEventSynchronize on such an event returned late, by about the batch's remaining work in its stream — r05q)
         constexpr unsigned kEvFlags = hipEventDefault;
-        {
-            const size_t groups = (B + Batch::kWordSlots - 1) / Batch::kWordSlots;
-            b.n_chunks = (int)std::min<size_t>(groups, Batch::kMaxChunks);
-            b.chunk_slots = (groups + b.n_chunks - 1) / b.n_chunks * Batch::kWordSlots;
-            b.n_chunks = (int)((B + b.chunk_slots - 1) / b.chunk_slots);
-        }
+        b.words.plan(B);
         if (hipEventCreateWithFlags(&b.ev_in, kEvFlags) != hipSuccess || hipEventCreateWithFlags(&b.ev_k, kEvFlags) != hipSuccess)
             return SPF_ERR_HIP;
-        for (int i = 0; i < b.n_chunks; i++)
+        for (int i = 0; i < b.words.n_chunks; i++)
             if (hipEventCreateWithFlags(&b.ev_chunk[i], kEvFlags) != hipSuccess) return SPF_ERR_HIP;
         // Everything of a batch — copy in, kernels, copies out — goes on the SET's stream, in order, and nothing waits for an event
         // of another stream: batches of different sets run side by side, a batch's copies run under the other batches' kernels
@@ -1130,9 +1052,9 @@ struct spf_pool {
         if (st != SPF_OK) return st;
         if (hipEventRecord(b.ev_k, sk) != hipSuccess) return SPF_ERR_HIP;
         hipStream_t so = sk;
-        for (int i = 0; i < b.n_chunks; i++) {
-            const size_t first = (size_t)i * b.chunk_slots;
-            const size_t count = std::min(b.chunk_slots, B - first);
+        for (int i = 0; i < b.words.n_chunks; i++) {
+            const size_t first = (size_t)i * b.words.chunk_slots;
+            const size_t count = std::min(b.words.chunk_slots, B - first);
             if (hipMemcpyAsync(static_cast<uint8_t*>(s.h_out) + first * out, static_cast<const uint8_t*>(s.d_out) + first * out, count * out,
                                hipMemcpyDeviceToHost, so) != hipSuccess)
                 return SPF_ERR_HIP;
@@ -1199,7 +1121,7 @@ struct spf_pool {
             n_ops += b->n;
             poke(); // the launcher closes the batch that filled meanwhile
         }
-        b->wake_tree();
+        b->tree.wake_tree(b->n);
     }
 
     void launch_loop()
@@ -1506,11 +1428,11 @@ struct spf_pool {
                 // all chunks but the last: their waiters copy out while the rest is still on its way.  (A failure from here on
                 // reaches the waiters of the chunks still asleep; the bytes already handed out were complete.)  The last chunk is
                 // woken below, behind the bookkeeping that its waiters' `collected_one` relies on.
-                for (int i = 0; i + 1 < b->n_chunks; i++) {
+                for (int i = 0; i + 1 < b->words.n_chunks; i++) {
                     if (b->st == SPF_OK && hipEventSynchronize(b->ev_chunk[i]) != hipSuccess) b->st = SPF_ERR_HIP;
-                    b->wake_chunk(i);
+                    b->words.wake_chunk(i);
                 }
-                if (b->st == SPF_OK && hipEventSynchronize(b->ev_chunk[b->n_chunks - 1]) != hipSuccess) b->st = SPF_ERR_HIP;
+                if (b->st == SPF_OK && hipEventSynchronize(b->ev_chunk[b->words.n_chunks - 1]) != hipSuccess) b->st = SPF_ERR_HIP;
                 if (b->st != SPF_OK) (void)hipStreamSynchronize(stream_of(*b)); // nothing may still be writing the staging set
                 b->t_sync = std::chrono::steady_clock::now();
             } else {
@@ -1537,8 +1459,8 @@ struct spf_pool {
             {
                 auto us = [](auto d) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(d).count(); };
                 float gpu_ms = -1.f;
-                if (b->ev_in && b->n_chunks > 0 && b->ev_chunk[b->n_chunks - 1])
-                    (void)hipEventElapsedTime(&gpu_ms, b->ev_in, b->ev_chunk[b->n_chunks - 1]);
+                if (b->ev_in && b->words.n_chunks > 0 && b->ev_chunk[b->words.n_chunks - 1])
+                    (void)hipEventElapsedTime(&gpu_ms, b->ev_in, b->ev_chunk[b->words.n_chunks - 1]);
                 fprintf(stderr, "[pool] batch op %d%s n %zu: filled %ld us, closed->inputs in %ld us, enqueue %ld us, enqueued->event %ld us (gpu h2d..d2h %.0f us), event->marked %ld us\n", b->op, b->by_handle ? " (by handle)" : "", b->n,
                         us(b->t_close - b->t0), us(b->t_ready - b->t_close), us(b->t_enq - b->t_ready), us(b->t_sync - b->t_enq), gpu_ms * 1e3f, us(b->t_done - b->t_sync));
             }
@@ -1547,8 +1469,7 @@ struct spf_pool {
             outstanding[b->lane]--;
             n_launches++;
             n_ops += b->n;
-            for (int w = 0; w < spf_pool_impl::Batch::kMaxWords; w++) // the last chunk — or, for a batch that failed, all of them
-                if (b->chunk_word[w].load(std::memory_order_relaxed) == 0) b->wake_word(w);
+            b->words.wake_rest(); // the last chunk — or, for a batch that failed, all of them
             poke(); // the launcher closes the batch that filled meanwhile
         }
     }
