@@ -302,6 +302,14 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_pack(g_, bits.data(), bits.size(), &n), ctx_);
         return n;
     }
+    // `blind_rotation` (sunscreen_tfhe ops/bootstrapping/blind_rotation.rs:202-223) as nodes: glwe * X^-(s << log_stride), s given
+    // by the L1 GGSW nodes of its bits (bit 0 first); one GLWE node per bit, the last is returned
+    Node blind_rotation(Node glwe, const std::vector<Node>& shift_ggsw, size_t log_stride = 0)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_blind_rotation(g_, glwe, shift_ggsw.data(), shift_ggsw.size(), log_stride, &n), ctx_);
+        return n;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }
@@ -450,6 +458,24 @@ class PooledEvaluation {
         uint64_t t = 0;
         check(spf_pool_submit_keyswitch_circuit_bootstrap_v(pool_, input.raw(), &out, pushed_ ? nullptr : &t));
         finish(output, out, t);
+    }
+
+    // blind_rotation (blind_rotation.rs:202-223) by handle: output = input * X^-(s << log_stride), the shift as the span
+    // shift_ggsw[0 .. n_bits) of the L1 GGSWs of its bits (bit 0 first; valid or, in pushed mode, still pending)
+    void blind_rotation(L1GlweCiphertext& output, const L1GgswCiphertext* shift_ggsw, size_t n_bits, const L1GlweCiphertext& input,
+                        size_t log_stride = 0) const
+    {
+        std::vector<const spf_value*> sel(n_bits);
+        for (size_t i = 0; i < n_bits; i++) sel[i] = shift_ggsw[i].raw();
+        spf_value* out = nullptr;
+        uint64_t t = 0;
+        check(spf_pool_submit_blind_rotation_v(pool_, input.raw(), sel.data(), n_bits, log_stride, &out, pushed_ ? nullptr : &t));
+        finish(output, out, t);
+    }
+    void blind_rotation(L1GlweCiphertext& output, const std::vector<L1GgswCiphertext>& shift_ggsw, const L1GlweCiphertext& input,
+                        size_t log_stride = 0) const
+    {
+        blind_rotation(output, shift_ggsw.data(), shift_ggsw.size(), input, log_stride);
     }
 
   private:

@@ -524,6 +524,15 @@ spf_status spf_pool_submit_multiply_ggsw_glwe_v(spf_pool *pool, const spf_value 
 spf_status spf_pool_submit_glev_cmux_v(spf_pool *pool, const spf_value *sel_ggsw, const spf_value *a, const spf_value *b,
                                        spf_value **glev_out, uint64_t *ticket);
 spf_status spf_pool_submit_scheme_switch_v(spf_pool *pool, const spf_value *glev, spf_value **ggsw_out, uint64_t *ticket);
+/* `blind_rotation` (blind_rotation.rs:202-223) by handle: *out = glwe * X^-(s << log_stride), s given as the n_bits glwe-level
+ * GGSW values of its bits (bit 0 first; valid or still pending, e.g. results of spf_pool_submit_keyswitch_circuit_bootstrap_v;
+ * repeats allowed).  Word-equal to spf_blind_rotation_batch.  n_bits >= 1 and n_bits + log_stride <= log2(polynomial_degree);
+ * operands on different members of a group are SPF_ERR_INVALID_ARGUMENT, a tuned context whose cbs radix is not 4 x 4 bits
+ * SPF_ERR_UNSUPPORTED; everything is checked before anything is queued.  One step per bit is queued, each on the pending result
+ * of the one before: step i of every caller that pushed the same (i, log_stride) is ONE launch over a pointer table.  The
+ * intermediate values are the library's; `ticket` (may be NULL) is the last step's. */
+spf_status spf_pool_submit_blind_rotation_v(spf_pool *pool, const spf_value *glwe, const spf_value *const *shift_ggsw /* n_bits */,
+                                            size_t n_bits, size_t log_stride, spf_value **out, uint64_t *ticket);
 /* `exec_op`'s whole match in one entry (circuit_processor/mod.rs:255-540): the operation as a spf_graph_op, operands in the order
  * spf_graph_add_op takes them (CMUX: selector, low, high), `param` = SampleExtract index / MulXN amount */
 spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value *const *inputs, size_t n_inputs, uint64_t param,
@@ -575,6 +584,17 @@ spf_status spf_graph_add_op(spf_graph *graph, spf_graph_op op, const uint32_t *i
  * and the graph stays usable. */
 spf_status spf_graph_add_unpack(spf_graph *graph, uint32_t glwe_node, size_t n_bits, uint32_t *nodes_out /* n_bits */);
 spf_status spf_graph_add_pack(spf_graph *graph, const uint32_t *nodes, size_t n_bits, uint32_t *node_out);
+/* `blind_rotation` (ops/bootstrapping/blind_rotation.rs:202-223) as a node constructor — no FheOp there, no spf_graph_op here:
+ * creates n_bits chained glwe1 nodes acc_{i+1} = cmux(shift_nodes[i], acc_i, X^-(2^(i + log_stride)) * acc_i) with
+ * acc_0 = glwe_node, so that *node_out (the last one) = glwe_node * X^-(s << log_stride), s = the integer whose bits the ggsw1
+ * nodes shift_nodes[0 .. n_bits) encrypt (bit 0 first; inputs, trivial GGSWs or CIRCUIT_BOOTSTRAP results at any level, repeats
+ * allowed).  Word-equal to spf_blind_rotation_batch and to MUL_XN(2N - 2^(i + log_stride)) + CMUX nodes.  Each node is one
+ * level above the higher of its two operands and writes its own row; all such nodes of one level with one rotation amount are
+ * ONE launch whose high operand is a rotated read of the low one.  The new nodes are ordinary glwe1 nodes.  n_bits >= 1 and
+ * n_bits + log_stride <= log2(polynomial_degree); a wrong argument is SPF_ERR_INVALID_ARGUMENT from the call (a tuned context
+ * whose cbs radix is not 4 x 4 bits: SPF_ERR_UNSUPPORTED), nothing is recorded and the graph stays usable. */
+spf_status spf_graph_add_blind_rotation(spf_graph *graph, uint32_t glwe_node, const uint32_t *shift_nodes /* n_bits ggsw1 nodes, bit 0 first */,
+                                        size_t n_bits, size_t log_stride, uint32_t *node_out);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */
@@ -665,7 +685,9 @@ const char *spf_last_blind_rotate_kernel(spf_ctx *ctx);
 /* The same for the CMUX family (spf_cmux*, spf_glev_cmux*, spf_multiply_glwe_ggsw*, gate graphs): four waves per gate up
  * to one gate per CU, the streaming shape beyond, with streaming (non-temporal) selector loads once a launch's selectors
  * exceed the Infinity Cache.  The steps of spf_blind_rotation* report the same names with ",rot" appended
- * ("cmux4_kernel<4,4,rot>", "cmux_kernel<4,4,2,rot>", "cmux_kernel<4,4,2,stream,rot>").  Never NULL. */
+ * ("cmux4_kernel<4,4,rot>", "cmux_kernel<4,4,2,rot>", "cmux_kernel<4,4,2,stream,rot>"); the same step over scattered operands
+ * (spf_graph_add_blind_rotation, spf_pool_submit_blind_rotation_v) appends ",scattered" ("cmux4_kernel<4,4,rot,scattered>",
+ * "cmux_kernel<4,4,2,rot,scattered>"; generic contexts: "generic_cmux_rot_kernel").  Never NULL. */
 const char *spf_last_cmux_kernel(spf_ctx *ctx);
 /* The same for the LWE keyswitch L1 -> L0 (every entry point that runs one): "ks_gemm_lds_kernel", the int8 matrix-core
  * formulation, when the tuned context's radix fits it (radix_log <= 8 and its accumulator bound), else "keyswitch_kernel".

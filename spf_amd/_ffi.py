@@ -117,6 +117,7 @@ SYMBOLS = [
     ("spf_graph_add_op", _I, [_P, _I, C.POINTER(_U32), _SZ, _U64, C.POINTER(_U32)]),
     ("spf_graph_add_unpack", _I, [_P, _U32, _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_pack", _I, [_P, C.POINTER(_U32), _SZ, C.POINTER(_U32)]),
+    ("spf_graph_add_blind_rotation", _I, [_P, _U32, C.POINTER(_U32), _SZ, _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_output", _I, [_P, _U32, _P]),
     ("spf_graph_run", _I, [_P]),
     ("spf_graph_stats", _I, [_P, C.POINTER(_U32), C.POINTER(_U32), C.POINTER(_U32)]),
@@ -215,6 +216,7 @@ SYMBOLS = [
     ("spf_pool_submit_glev_cmux_v", _I, [_P, _P, _P, _P, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_scheme_switch_v", _I, [_P, _P, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_op_v", _I, [_P, _I, C.POINTER(_P), _SZ, _U64, C.POINTER(_P), C.POINTER(_U64)]),
+    ("spf_pool_submit_blind_rotation_v", _I, [_P, _P, C.POINTER(_P), _SZ, _SZ, C.POINTER(_P), C.POINTER(_U64)]),
 ]
 
 
@@ -1083,6 +1085,30 @@ class Pool:
                  "spf_pool_submit_keyswitch_circuit_bootstrap_v")
         v = Value(self, h)
         self._wait(t.value)
+        return v
+
+    def _submit_blind_rotation_v(self, glwe: "Value", shift_values, log_stride: int, ticket):
+        shift_values = list(shift_values)
+        arr = (C.c_void_p * max(len(shift_values), 1))(*[v._h for v in shift_values])
+        h = C.c_void_p()
+        self._ck(self._lib.spf_pool_submit_blind_rotation_v(self._h, glwe._h, arr, len(shift_values), int(log_stride), C.byref(h), ticket),
+                 "spf_pool_submit_blind_rotation_v")
+        return Value(self, h)
+
+    def push_blind_rotation_v(self, glwe: "Value", shift_values, log_stride: int = 0) -> "Value":
+        """`spf_pool_submit_blind_rotation_v` without a ticket: glwe * X^-(s << log_stride), s given by the GGSW values of its bits
+        (bit 0 first); the operands may still be pending, Value.wait() on the result makes the chain run"""
+        return self._submit_blind_rotation_v(glwe, shift_values, log_stride, None)
+
+    def blind_rotation_v(self, glwe: "Value", shift_values, log_stride: int = 0) -> "Value":
+        """the same, waited for: word-equal to `Engine.blind_rotation` of the downloaded operands"""
+        t = C.c_uint64()
+        v = self._submit_blind_rotation_v(glwe, shift_values, log_stride, C.byref(t))
+        try:
+            self._wait(t.value)
+        except SpfError:
+            v.release()
+            raise
         return v
 
     def value_stats(self) -> dict:

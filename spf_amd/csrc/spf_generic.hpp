@@ -321,12 +321,16 @@ struct GenericCmuxArgs {
     uint64_t* out;
     uint32_t units, per_ggsw, d0_zero, radix_log, count;
     const void* const* ptrs; // non-null: 4 pointers per unit {selector, d0 (null = the zero ciphertext), d1, out} instead (gate graphs, values)
+    uint32_t rot;            // generic_cmux_rot_kernel only (0 < rot < N, over `ptrs`): d1 is X^-rot * d0, slot 2 of a unit is not read
 };
 
-// cmux (fft_ops.rs:149-181): out = d0 + IFFT(decomp(d1 - d0) [*] ggsw); with d0_zero: multiply_glwe_ggsw
-__global__ __launch_bounds__(kGenericThreads) void generic_cmux_kernel(GenericCmuxArgs a)
+// cmux (fft_ops.rs:149-181): out = d0 + IFFT(decomp(d1 - d0) [*] ggsw); with d0_zero: multiply_glwe_ggsw.
+// ROT: one step of a blind rotation by an encrypted shift over a pointer table (`blind_rotation`, blind_rotation.rs:202-223):
+// the high operand is X^-rot * d0, coefficient i read from d0 at (i + rot) mod N and negated where i + rot >= N — the word
+// generic_linear_kernel's X^(2N - rot) writes, without the row in between.
+template <bool ROT>
+__device__ __forceinline__ void generic_cmux_body(const GenericCmuxArgs& a, char* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const GenericShape& g = a.g;
     const uint32_t tid = threadIdx.x, N = g.N, h = N / 2, k = g.k, len = (k + 1) * N;
     c64* accf = reinterpret_cast<c64*>(smem);
@@ -346,11 +350,30 @@ __global__ __launch_bounds__(kGenericThreads) void generic_cmux_kernel(GenericCm
         d0 = zero ? d1 : static_cast<const uint64_t*>(q[1]);
         out = static_cast<uint64_t*>(const_cast<void*>(q[3]));
     }
-    generic_glwe_ggsw_mad(g, accf, buf, state, ggsw, a.radix_log, a.count,
-                          [&](uint32_t p, uint32_t i) { return zero ? d1[p * N + i] : d1[p * N + i] - d0[p * N + i]; });
+    generic_glwe_ggsw_mad(g, accf, buf, state, ggsw, a.radix_log, a.count, [&](uint32_t p, uint32_t i) {
+        if constexpr (ROT) {
+            const uint32_t idx = i + a.rot;
+            const uint64_t v = d0[p * N + (idx & (N - 1))];
+            return (idx >= N ? (uint64_t)0 - v : v) - d0[p * N + i];
+        } else {
+            return zero ? d1[p * N + i] : d1[p * N + i] - d0[p * N + i];
+        }
+    });
     for (uint32_t q = 0; q <= k; q++)
         generic_poly_ifft(g, accf + (size_t)q * h, buf, reinterpret_cast<c64*>(state + N), [&](uint32_t i, uint64_t t) { out[q * N + i] = zero ? t : t + d0[q * N + i]; });
     (void)tid;
+}
+
+__global__ __launch_bounds__(kGenericThreads) void generic_cmux_kernel(GenericCmuxArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    generic_cmux_body<false>(a, smem);
+}
+
+__global__ __launch_bounds__(kGenericThreads) void generic_cmux_rot_kernel(GenericCmuxArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    generic_cmux_body<true>(a, smem);
 }
 
 // sample_extract at index h of every GLWE (glwe_ciphertext_ops.rs:31-76)

@@ -19,6 +19,11 @@
 // launch, spf_graph_add_pack sums the rows of all packs of a level in ONE glwe_pack_rows_kernel launch that reads them where
 // they lie.
 //
+// A blind rotation by an encrypted shift (`blind_rotation`, blind_rotation.rs:202-223) is a third constructor and no `FheOp` either:
+// spf_graph_add_blind_rotation creates one GLWE1 node per bit, acc' = cmux(bit, acc, X^-r * acc), whose high operand is a rotated
+// read of the low one — composed from MulXN(2N - r) + CMux nodes the same words cost two levels and two launches per bit.  All such
+// nodes of one level and one rotation are ONE launch over a pointer table (launch_cmux_rot_scattered), each writing its own row.
+//
 // Included at the end of spf_hip.hip: uses its `fail` / HIPCHK helpers and the `_dev` entry points.
 #pragma once
 
@@ -55,13 +60,13 @@ struct spf_pinned_buf {
 };
 
 struct spf_graph {
-    // the two node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack)
-    enum : int32_t { kNodeUnpack = 64, kNodePack = 65 };
+    // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation)
+    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66 };
     struct Node {
-        int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack, or -1 input, -2 trivial constant
+        int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack / kNodeRotCmux, or -1 input, -2 trivial constant
         int32_t kind;      // spf_value_kind of the value the node produces
-        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node
-        uint32_t in[3];
+        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node
+        uint32_t in[3];    // (rotate-CMUX nodes: {selector, accumulator})
         uint32_t n_in;
         uint32_t n_bits;   // unpack and pack nodes: width of the integer
         uint32_t ext;      // pack nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
@@ -233,7 +238,7 @@ inline spf_status plan(spf_graph* g)
     for (uint32_t id = 0; id < g->nodes.size(); id++) {
         const auto& n = g->nodes[id];
         if (n.op < 0) continue;
-        const uint64_t key_param = n.op >= spf_graph::kNodeUnpack ? n.n_bits : n.param;
+        const uint64_t key_param = n.op == spf_graph::kNodeUnpack || n.op == spf_graph::kNodePack ? n.n_bits : n.param;
         auto key = std::make_tuple(n.level, n.op, key_param);
         auto it = index.find(key);
         if (it == index.end()) {
@@ -285,6 +290,21 @@ inline spf_status plan(spf_graph* g)
                 for (size_t m = 0; m < ints; m++) table.push_back(g->d_arena + src(m));
                 stage = std::max(stage, ints * ib);
             }
+            continue;
+        }
+        if (gr.op == spf_graph::kNodeRotCmux) {
+            // units {selector, accumulator, unused (the high operand is a rotated read of the accumulator), out}; units of one
+            // selector next to each other, as below
+            gr.ptr_index[0] = table.size();
+            struct Unit { void* p[4]; };
+            std::vector<Unit> units;
+            units.reserve(B);
+            for (uint32_t id : gr.members) {
+                const auto& n = g->nodes[id];
+                units.push_back(Unit{{g->d_arena + g->nodes[n.in[0]].off, g->d_arena + g->nodes[n.in[1]].off, nullptr, g->d_arena + n.off}});
+            }
+            std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.p[0] < y.p[0]; });
+            for (const Unit& u : units) for (void* q : u.p) table.push_back(q);
             continue;
         }
         const spf_ops::OpRow& info = op_row(gr.op);
@@ -388,6 +408,12 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                 src = (const uint64_t*)g->d_stage[0];
             }
             spf_status st = launch_glwe_unpack(c, s, ints, gr.param, src, (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
+        if (gr.op == spf_graph::kNodeRotCmux) {
+            spf_status st = launch_cmux_rot_scattered(c, s, B, (uint32_t)gr.param, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
@@ -671,6 +697,41 @@ spf_status spf_graph_add_pack(spf_graph* g, const uint32_t* nodes, size_t n_bits
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
     *node_out = (uint32_t)g->nodes.size() - 1;
+    g->planned = false;
+    return SPF_OK;
+}
+
+// `blind_rotation` (blind_rotation.rs:202-223) as a node constructor: n_bits chained GLWE1 nodes,
+// acc_{i+1} = cmux(shift_nodes[i], acc_i, X^-(2^(i + log_stride)) * acc_i), acc_0 = glwe_node; *node_out = the last one
+spf_status spf_graph_add_blind_rotation(spf_graph* g, uint32_t glwe_node, const uint32_t* shift_nodes, size_t n_bits, size_t log_stride,
+                                        uint32_t* node_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!shift_nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: null pointer");
+    if (const char* why = blind_rotation_shape_error(g->prm, 1, n_bits, log_stride))
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph blind rotation: ") + why);
+    if (glwe_node >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: operand is not a node of this graph");
+    if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: operand is not an L1 GLWE");
+    for (size_t i = 0; i < n_bits; i++) {
+        if (shift_nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: selector is not a node of this graph");
+        if (g->nodes[shift_nodes[i]].kind != SPF_VAL_GGSW1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: selector is not an L1 GGSW");
+    }
+    if (!g->ctx->generic && (g->prm.cbs_radix_log != 4 || g->prm.cbs_radix_count != 4))
+        return fail(g->ctx, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
+    try {
+        g->nodes.reserve(g->nodes.size() + n_bits); // all of the chain's nodes or none
+    } catch (const std::exception&) {
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    spf_graph::Node n{};
+    n.op = spf_graph::kNodeRotCmux; n.kind = SPF_VAL_GLWE1; n.n_in = 2;
+    uint32_t acc = glwe_node;
+    for (size_t i = 0; i < n_bits; i++) {
+        n.in[0] = shift_nodes[i]; n.in[1] = acc; n.param = (uint64_t)1 << (i + log_stride);
+        acc = (uint32_t)g->nodes.size();
+        g->nodes.push_back(n);
+    }
+    *node_out = acc;
     g->planned = false;
     return SPF_OK;
 }

@@ -651,6 +651,8 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                                (int)generic_lds_bytes(N, params->glwe_size, true)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_cmux_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_lds_bytes(N, params->glwe_size, false)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_cmux_rot_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)generic_lds_bytes(N, params->glwe_size, false)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_trace_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_scheme_switch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -683,6 +685,10 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux_kernel<4, 4, 2, false, true>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux4_kernel<4, 4, true>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kCmux4Lds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux_rot_scattered_kernel<4, 4, 2>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cmux4_rot_scattered_kernel<4, 4>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kCmux4Lds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&cbs_trace_kernel<6, 7>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
@@ -1436,6 +1442,44 @@ static void launch_cmux_rot(spf_ctx* c, hipStream_t s, size_t B, const c64* d_se
         c->last_cmux_kernel = "cmux_kernel<4,4,2,rot>";
         hipLaunchKernelGGL((cmux_kernel<4, 4, 2, false, true>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, a);
     }
+}
+
+// The same step over SCATTERED operands (a level of spf_graph_add_blind_rotation nodes, a batch of the pool's rotate-CMUX kind):
+// d_ptrs holds 4 pointers per unit {selector GGSW-FFT, accumulator, unused, out}, the layout of spf_cmux_scattered_dev; the high
+// operand is X^-rot * accumulator, `rot` one value per launch.  Shapes as launch_cmux_args picks them for a pointer table: four
+// waves per unit up to one unit per CU, two units per workgroup beyond; plain loads (selectors are shared between units).
+// Generic contexts: generic_cmux_rot_kernel, the rotated read in the pointer-table path — no row of X^-rot * accumulator exists.
+static spf_status launch_cmux_rot_scattered(spf_ctx* c, hipStream_t s, size_t units, uint32_t rot, const void* const* d_ptrs)
+{
+    if (!c || (units && !d_ptrs)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (!c->generic && (c->prm.cbs_radix_log != 4 || c->prm.cbs_radix_count != 4))
+        return fail(c, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
+    if (rot == 0 || rot >= c->prm.polynomial_degree) return fail(c, SPF_ERR_INVALID_ARGUMENT, "rotation must be in 1 .. polynomial_degree - 1");
+    if (units == 0) return SPF_OK;
+    if (units > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->generic) {
+        GenericCmuxArgs ga{};
+        ga.g = generic_shape(c);
+        ga.units = (uint32_t)units; ga.per_ggsw = 1; ga.ptrs = d_ptrs; ga.rot = rot;
+        ga.radix_log = c->prm.cbs_radix_log; ga.count = c->prm.cbs_radix_count;
+        c->last_cmux_kernel = "generic_cmux_rot_kernel";
+        hipLaunchKernelGGL(generic_cmux_rot_kernel, dim3((unsigned)units), dim3(kGenericThreads), generic_lds_bytes(ga.g.N, ga.g.k, false), s, ga);
+        HIPCHK(c, hipGetLastError());
+        return SPF_OK;
+    }
+    CmuxArgs a{};
+    a.tables = c->d_tables; a.B = (uint32_t)units; a.per_ggsw = 1; a.ptrs = d_ptrs; a.rot = rot;
+    if (a.B <= (uint32_t)c->n_cu) {
+        c->last_cmux_kernel = "cmux4_kernel<4,4,rot,scattered>";
+        hipLaunchKernelGGL((cmux4_rot_scattered_kernel<4, 4>), dim3(a.B), dim3(256), kCmux4Lds, s, a);
+    } else {
+        c->last_cmux_kernel = "cmux_kernel<4,4,2,rot,scattered>";
+        hipLaunchKernelGGL((cmux_rot_scattered_kernel<4, 4, 2>), dim3((a.B + 1) / 2), dim3(256), cmux_lds_bytes(2), s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
 }
 
 // why (B, n_bits, log_stride) is refused, or nullptr: every step's rotation 2^(i + log_stride) stays below N
@@ -2900,6 +2944,43 @@ spf_status spf_pool_submit_glev_cmux_v(spf_pool* p, const spf_value* sel, const 
 spf_status spf_pool_submit_scheme_switch_v(spf_pool* p, const spf_value* glev, spf_value** ggsw_out, uint64_t* ticket)
 {
     return pool_submit_v(p, spf_ops::OP_SCHEME_SWITCH, {glev}, 0, ggsw_out, ticket);
+}
+
+// `blind_rotation` (blind_rotation.rs:202-223) by handle: n_bits pushes of the rotate-CMUX kind, step i on the still-pending
+// result of step i - 1 — the deferred table's (depth, kind, rotation) key then makes step i of every caller one scattered launch.
+// Everything is checked before the first push; the intermediate values are the library's and are let go as the chain advances
+// (each lives until the step that reads it has run: its batch holds it).
+spf_status spf_pool_submit_blind_rotation_v(spf_pool* p, const spf_value* glwe, const spf_value* const* shift_ggsw, size_t n_bits,
+                                            size_t log_stride, spf_value** out, uint64_t* ticket)
+{
+    if (!p) return SPF_ERR_INVALID_ARGUMENT;
+    if (!glwe || !shift_ggsw || !out) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: null pointer");
+    if (const char* why = blind_rotation_shape_error(p->prm, 1, n_bits, log_stride))
+        return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("pool blind rotation: ") + why);
+    if (glwe->kind != SPF_VAL_GLWE1) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: operand is not an L1 GLWE");
+    for (size_t i = 0; i < n_bits; i++) {
+        if (!shift_ggsw[i]) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: null selector");
+        if (shift_ggsw[i]->kind != SPF_VAL_GGSW1) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: selector is not an L1 GGSW");
+        if (shift_ggsw[i]->home != glwe->home)
+            return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: operands live on different members of the group (spf_value_copy_to_member moves one)");
+        if (shift_ggsw[i]->state.load(std::memory_order_acquire) == spf_value_impl::FAILED)
+            return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: the operation that was to produce a selector failed");
+    }
+    const spf_pool* leaf = glwe->home;
+    if (leaf && !leaf->ctx->generic && (leaf->prm.cbs_radix_log != 4 || leaf->prm.cbs_radix_count != 4))
+        return fail(p->ctx, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
+    const spf_value* acc = glwe;
+    for (size_t i = 0; i < n_bits; i++) {
+        spf_value* next = nullptr;
+        const spf_value* in[2] = {shift_ggsw[i], acc};
+        const spf_status st = pool_submit_v(p, spf_ops::OP_ROT_CMUX, in, 2, (uint64_t)1 << (i + log_stride), &next,
+                                            i + 1 == n_bits ? ticket : nullptr, true);
+        if (acc != glwe) const_cast<spf_value*>(acc)->release(); // (step i holds it until it has run)
+        if (st != SPF_OK) return st;
+        acc = next;
+    }
+    *out = const_cast<spf_value*>(acc);
+    return SPF_OK;
 }
 
 // one entry for `exec_op`'s whole match (circuit_processor/mod.rs:255-540): the operation as a spf_graph_op, operands in the

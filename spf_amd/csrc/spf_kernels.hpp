@@ -909,7 +909,8 @@ struct CmuxArgs {
     // The ROT instantiations only (one step of spf_blind_rotation_dev, blind_rotation.rs:202-223): d1 is no buffer but
     // X^-rot * d0 (`rotate_glwe_negative_monomial_negacyclic`), read from d0 at (coefficient + rot) mod N and negated where
     // the sum wrapped; unit u takes selector u * sel_stride from `ggsw` (int-major bits: this step's bit of every item).
-    // ptrs, d1, per_ggsw and d0_zero are not read there.
+    // ptrs, d1, per_ggsw and d0_zero are not read there.  The *_rot_scattered kernels (a level of spf_graph_add_blind_rotation
+    // nodes, a batch of the pool's rotate-CMUX kind) read `ptrs` instead: unit u = {selector, accumulator, unused, out}.
     uint32_t rot;         // 0 < rot < N
     uint32_t sel_stride;
 };
@@ -918,7 +919,7 @@ constexpr int cmux_lds_bytes(int gates) { return kTableBytes + gates * kWaveBufB
 #ifndef SPF_CMUX_INV_PAIR
 #define SPF_CMUX_INV_PAIR fft512_pair1
 #endif
-template <int L, int LOGB, int G, int W, bool STREAM, bool ROT = false>
+template <int L, int LOGB, int G, int W, bool STREAM, bool ROT = false, bool ROT_PTRS = false>
 __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
 {
     static_assert(L * LOGB <= 32, "packed digits need L*LOGB <= 32");
@@ -943,7 +944,12 @@ __device__ __forceinline__ void cmux_body(const CmuxArgs& a, char* smem)
     const uint64_t *d0, *d1;
     uint64_t* out_ct;
     bool d0_zero = ROT ? false : a.d0_zero != 0;
-    if constexpr (ROT) {
+    if constexpr (ROT && ROT_PTRS) { // the step over scattered operands: {selector, accumulator, unused, out} per unit
+        const void* const* t = a.ptrs + 4 * (size_t)ct;
+        ggsw = static_cast<const c64*>(t[0]);
+        d0 = d1 = static_cast<const uint64_t*>(t[1]);
+        out_ct = static_cast<uint64_t*>(const_cast<void*>(t[3]));
+    } else if constexpr (ROT) {
         ggsw = a.ggsw + (size_t)ct * a.sel_stride * (2 * L * 2 * kHalf);
         d0 = d1 = a.d0 + (size_t)ct * 2 * kN; // d1 = X^-rot * d0: the rotated read below
         out_ct = a.out + (size_t)ct * 2 * kN;
@@ -1148,6 +1154,16 @@ __global__ __launch_bounds__(128 * G, 2) void cmux_kernel(CmuxArgs a)
 
 }
 
+// One blind-rotation step over SCATTERED operands (gate graphs, values): the ROT body with unit u's {selector, accumulator,
+// unused, out} taken from ptrs[4u .. 4u+3] (the layout of spf_cmux_scattered_dev); plain loads, selectors are shared between units.
+template <int L, int LOGB, int G>
+__global__ __launch_bounds__(128 * G, 2) void cmux_rot_scattered_kernel(CmuxArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux_body<L, LOGB, G, 1, false, true, true>(a, smem);
+    else cmux_body<L, LOGB, G, 0, false, true, true>(a, smem);
+}
+
 // ------------------------------------------------------------------------------------------
 // cmux4_kernel: the LATENCY shape of cmux_kernel — four waves per gate, one gate per workgroup, for
 // the levels of a gate graph that hold at most one gate per CU (a ripple-carry chain is 1-4 gates per
@@ -1162,7 +1178,7 @@ __global__ __launch_bounds__(128 * G, 2) void cmux_kernel(CmuxArgs a)
 // forward transforms.  Same operations in the same order on every value as cmux_kernel: same words.
 constexpr int kCmux4Lds = kTableBytes + 4 * 4 * 8192;
 
-template <int L, int LOGB, int W, bool ROT = false>
+template <int L, int LOGB, int W, bool ROT = false, bool ROT_PTRS = false>
 __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
 {
     static_assert(L == 4 && L * LOGB <= 32, "four digits, processed as two pairs");
@@ -1201,7 +1217,12 @@ __device__ __forceinline__ void cmux4_body(const CmuxArgs& a, char* smem)
     const uint64_t *d0, *d1;
     uint64_t* out_ct;
     bool d0_zero = ROT ? false : a.d0_zero != 0;
-    if constexpr (ROT) {
+    if constexpr (ROT && ROT_PTRS) { // the step over scattered operands: {selector, accumulator, unused, out} per unit
+        const void* const* t = a.ptrs + 4 * (size_t)ct;
+        ggsw = static_cast<const c64*>(t[0]);
+        d0 = d1 = static_cast<const uint64_t*>(t[1]);
+        out_ct = static_cast<uint64_t*>(const_cast<void*>(t[3]));
+    } else if constexpr (ROT) {
         ggsw = a.ggsw + (size_t)ct * a.sel_stride * (2 * L * 2 * kHalf);
         d0 = d1 = a.d0 + (size_t)ct * 2 * kN; // d1 = X^-rot * d0: the rotated read below
         out_ct = a.out + (size_t)ct * 2 * kN;
@@ -1402,6 +1423,15 @@ __global__ __launch_bounds__(256, 1) void cmux4_kernel(CmuxArgs a)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux4_body<L, LOGB, 1, ROT>(a, smem);
     else cmux4_body<L, LOGB, 0, ROT>(a, smem);
+}
+
+// ... and the four-waves-per-unit shape of the same step
+template <int L, int LOGB>
+__global__ __launch_bounds__(256, 1) void cmux4_rot_scattered_kernel(CmuxArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) cmux4_body<L, LOGB, 1, true, true>(a, smem);
+    else cmux4_body<L, LOGB, 0, true, true>(a, smem);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -41,14 +41,16 @@ inline size_t value_bytes(const spf_params& p, int kind) { return 8 * value_word
 namespace spf_ops {
 
 // The pool's numbering: one kind per `FheOp` that `exec_op` hands to `Evaluation`, plus the KeyswitchL1toL0 -> CircuitBootstrap
-// chain.  The pool's lanes, the SPF_POOL_TRACE lines and tools/pool_trace_phases.py carry these numbers.
+// chain, plus one step of a blind rotation by an encrypted shift (OP_ROT_CMUX: spf_pool_submit_blind_rotation_v pushes one per bit;
+// in gate graphs the same step is a node of spf_graph_add_blind_rotation).  The pool's lanes, the SPF_POOL_TRACE lines and tools/pool_trace_phases.py carry these numbers.
 enum Op {
     OP_KEYSWITCH = 0, OP_CBS = 1, OP_CMUX = 2, OP_GATE_CBS = 3,
     OP_SAMPLE_EXTRACT = 4, OP_NOT = 5, OP_GLWE_ADD = 6, OP_MUL_XN = 7, OP_MULTIPLY_GGSW_GLWE = 8, OP_GLEV_CMUX = 9, OP_SCHEME_SWITCH = 10,
-    N_OPS = 11
+    OP_ROT_CMUX = 11,
+    N_OPS = 12
 };
 
-enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N };
+enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N, PARAM_ROTATION_BELOW_N };
 constexpr int kNone = -1; // no spf_graph_op / no operand in this slot
 
 struct OpRow {
@@ -74,6 +76,8 @@ constexpr OpRow kOps[N_OPS] = {
     {OP_MULTIPLY_GGSW_GLWE, SPF_OP_MULTIPLY_GGSW_GLWE, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, kNone}, SPF_VAL_GLWE1, true, false, PARAM_NONE},
     {OP_GLEV_CMUX, SPF_OP_GLEV_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1, true, false, PARAM_NONE},
     {OP_SCHEME_SWITCH, SPF_OP_SCHEME_SWITCH, 1, {SPF_VAL_GLEV1, kNone, kNone}, SPF_VAL_GGSW1, false, false, PARAM_NONE},
+    // out = cmux(selector, acc, X^-param * acc): the high operand is a rotated read of the low one (launch_cmux_rot_scattered)
+    {OP_ROT_CMUX, kNone, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, kNone}, SPF_VAL_GLWE1, true, false, PARAM_ROTATION_BELOW_N},
 };
 
 constexpr const OpRow& row(int op) { return kOps[op]; } // op: a valid pool operation
@@ -94,7 +98,7 @@ inline void in_out_bytes(const spf_params& p, int op, size_t (&in)[3], size_t& o
 }
 
 // The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN
-// amount is reduced mod 2N, every other operation's parameter is 0 whatever the caller passed.
+// amount is reduced mod 2N, a rotate-CMUX rotation lies in 1 .. N - 1, every other operation's parameter is 0 whatever the caller passed.
 inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const char** why)
 {
     switch (kOps[op].param) {
@@ -103,6 +107,10 @@ inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const c
         *why = "sample_extract index >= polynomial_degree";
         return SPF_ERR_INVALID_ARGUMENT;
     case PARAM_AMOUNT_MOD_2N: *param %= 2 * (uint64_t)p.polynomial_degree; return SPF_OK;
+    case PARAM_ROTATION_BELOW_N:
+        if (*param > 0 && *param < p.polynomial_degree) return SPF_OK;
+        *why = "rotation must be in 1 .. polynomial_degree - 1";
+        return SPF_ERR_INVALID_ARGUMENT;
     default: *param = 0; return SPF_OK;
     }
 }
@@ -122,18 +130,18 @@ constexpr bool rows_ok()
         if (!row_ok(kOps[op], op)) return false;
     return true;
 }
-constexpr bool graph_ops_ok() // the ten public values name ten rows (distinct: each row names its value back), OP_GATE_CBS alone has none
+constexpr bool graph_ops_ok() // the ten public values name ten rows (distinct: each row names its value back), OP_GATE_CBS and OP_ROT_CMUX have none
 {
     for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_MUL_XN; g++)
         if (pool_op_of(g) == kNone) return false;
     for (int op = 0; op < N_OPS; op++) {
         const int g = kOps[op].graph_op;
-        if (op == OP_GATE_CBS ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_MUL_XN || pool_op_of(g) != op)) return false;
+        if (op == OP_GATE_CBS || op == OP_ROT_CMUX ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_MUL_XN || pool_op_of(g) != op)) return false;
     }
     return true;
 }
 static_assert(rows_ok(), "a row is out of the enum's order, or its arity and its operand kinds disagree, or a kind is no spf_value_kind");
-static_assert(graph_ops_ok(), "every spf_graph_op needs exactly one row, and only OP_GATE_CBS goes without a spf_graph_op");
+static_assert(graph_ops_ok(), "every spf_graph_op needs exactly one row, and only OP_GATE_CBS and OP_ROT_CMUX go without a spf_graph_op");
 } // namespace check
 
 } // namespace spf_ops
@@ -177,6 +185,7 @@ inline spf_status launch_op(spf_ctx* c, hipStream_t s, int op, size_t B, const v
     case OP_MULTIPLY_GGSW_GLWE: return spf_multiply_glwe_ggsw_dev(c, s, B, u64(in[1]), f64(in[0]), (uint64_t*)out);
     case OP_GLEV_CMUX: return spf_glev_cmux_dev(c, s, B, f64(in[0]), u64(in[1]), u64(in[2]), (uint64_t*)out);
     case OP_SCHEME_SWITCH: return spf_scheme_switch_dev(c, s, B, u64(in[0]), (double*)out);
+    case OP_ROT_CMUX: return fail(c, SPF_ERR_INVALID_ARGUMENT, "a rotate-CMUX step reads its operands through a pointer table only");
     default: return fail(c, SPF_ERR_INVALID_ARGUMENT, "unknown graph operation");
     }
 }

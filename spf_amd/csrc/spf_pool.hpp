@@ -427,9 +427,11 @@ struct spf_pool {
     }
 
     // the CMUX family reads scattered operands in place where the tuned kernels serve the parameter set (CmuxArgs::ptrs);
-    // elsewhere (generic family, another cbs radix) its operands are packed like everybody else's
+    // elsewhere (generic family, another cbs radix) its operands are packed like everybody else's.  A rotate-CMUX step exists over
+    // a pointer table only, in both kernel families (launch_cmux_rot_scattered; another cbs radix is refused at the submit).
     bool scattered_cmux(int op) const
     {
+        if (op == spf_pool_impl::OP_ROT_CMUX) return true;
         return spf_pool_impl::cmux_family(op) && !ctx->generic && prm.cbs_radix_log == 4 && prm.cbs_radix_count == 4;
     }
 
@@ -988,6 +990,9 @@ struct spf_pool {
                     if (b.op == OP_MULTIPLY_GGSW_GLWE) {
                         u.p[1] = nullptr;
                         u.p[2] = sl.vin[1]->ptr();
+                    } else if (b.op == OP_ROT_CMUX) { // the high operand is X^-param * the low one: a rotated read, no pointer
+                        u.p[1] = sl.vin[1]->ptr();
+                        u.p[2] = nullptr;
                     } else {
                         u.p[1] = static_cast<char*>(sl.vin[1]->ptr()) + j * gw;
                         u.p[2] = static_cast<char*>(sl.vin[2]->ptr()) + j * gw;
@@ -997,7 +1002,8 @@ struct spf_pool {
                 }
             }
             std::stable_sort(units, units + n_units, [](const Unit& x, const Unit& y) { return x.p[0] < y.p[0]; });
-            st = spf_cmux_scattered_dev(ctx, sk, n_units, (const void* const*)s.h_ptrs);
+            st = b.op == OP_ROT_CMUX ? launch_cmux_rot_scattered(ctx, sk, n_units, (uint32_t)b.param, (const void* const*)s.h_ptrs)
+                                     : spf_cmux_scattered_dev(ctx, sk, n_units, (const void* const*)s.h_ptrs);
         } else {
             void* d[3] = {nullptr, nullptr, nullptr};
             for (int k = 0; k < 3 && st == SPF_OK; k++) {

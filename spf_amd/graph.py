@@ -40,15 +40,28 @@ class FheOp(enum.IntEnum):
     MulXN = 9
 
 
-# RecordedCircuit's codes of the two node constructors that are no FheOp (spf_graph_add_unpack / spf_graph_add_pack)
+# RecordedCircuit's codes of the node constructors that are no FheOp (spf_graph_add_unpack / spf_graph_add_pack /
+# spf_graph_add_blind_rotation: one NODE_ROT_CMUX per bit, inputs (selector, accumulator), param = the rotation)
 NODE_UNPACK = 64
 NODE_PACK = 65
+NODE_ROT_CMUX = 66
 
 
 def _check_n_bits(what: str, n_bits: int, degree: int) -> int:
     if isinstance(n_bits, bool) or not isinstance(n_bits, (int, np.integer)) or not 0 < n_bits <= degree:
         raise SpfError(1, f"{what}: n_bits must be in 1 ..= {degree}, got {n_bits!r}")
     return int(n_bits)
+
+
+def _check_blind_rotation(what: str, n_bits: int, log_stride, degree: int) -> int:
+    log_n = degree.bit_length() - 1
+    if isinstance(log_stride, bool) or not isinstance(log_stride, (int, np.integer)) or log_stride < 0:
+        raise SpfError(1, f"{what}: log_stride must be a non-negative integer, got {log_stride!r}")
+    if n_bits < 1:
+        raise SpfError(1, f"{what}: n_bits must be at least 1")
+    if n_bits + log_stride > log_n:
+        raise SpfError(1, f"{what}: n_bits + log_stride above log2(polynomial_degree) = {log_n}")
+    return int(log_stride)
 
 
 def _check_node(what: str, node, n_nodes: int) -> int:
@@ -130,6 +143,18 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_pack(self._g, arr, n_bits, C.byref(node)))
         return node.value
 
+    # blind_rotation (blind_rotation.rs:202-223): glwe_node * X^-(s << log_stride), s given by the GGSW1 nodes of its bits
+    # (bit 0 first); one GLWE1 node per bit, returns the last
+    def add_blind_rotation(self, glwe_node: int, shift_nodes: Sequence[int], log_stride: int = 0) -> int:
+        nodes = list(shift_nodes)
+        log_stride = _check_blind_rotation("add_blind_rotation", len(nodes), log_stride, self._eng.params.polynomial_degree)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 1 << 32 for x in nodes + [glwe_node]):
+            raise SpfError(1, "add_blind_rotation: the operands must be node ids")
+        arr = (C.c_uint32 * len(nodes))(*[int(x) for x in nodes])
+        node = C.c_uint32()
+        self._eng._ck(self._lib.spf_graph_add_blind_rotation(self._g, int(glwe_node), arr, len(nodes), log_stride, C.byref(node)))
+        return node.value
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -164,7 +189,7 @@ class RecordedCircuit:
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX, -1 input, -2 trivial constant
         self.kind: List[int] = []
         self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
         self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands)
@@ -206,6 +231,19 @@ class RecordedCircuit:
             raise SpfError(1, "add_pack: an operand is not an L1 GLWE")
         return self._add(NODE_PACK, ValueKind.GLWE1, len(nodes), nodes)
 
+    def add_blind_rotation(self, glwe_node: int, shift_nodes: Sequence[int], log_stride: int = 0) -> int:
+        nodes = list(shift_nodes)
+        log_stride = _check_blind_rotation("add_blind_rotation", len(nodes), log_stride, self.polynomial_degree)
+        acc = _check_node("add_blind_rotation", glwe_node, len(self.op))
+        nodes = [_check_node("add_blind_rotation", x, len(self.op)) for x in nodes]
+        if self.kind[acc] != int(ValueKind.GLWE1):
+            raise SpfError(1, "add_blind_rotation: the operand is not an L1 GLWE")
+        if any(self.kind[x] != int(ValueKind.GGSW1) for x in nodes):
+            raise SpfError(1, "add_blind_rotation: a selector is not an L1 GGSW")
+        for i, sel in enumerate(nodes):   # acc' = cmux(sel, acc, X^-(2^(i + log_stride)) * acc)
+            acc = self._add(NODE_ROT_CMUX, ValueKind.GLWE1, 1 << (i + log_stride), (sel, acc))
+        return acc
+
     def add_output(self, node: int, kind: ValueKind) -> int:
         if self.kind[node] != int(kind):
             raise SpfError(1, "output kind does not match the node")
@@ -225,6 +263,8 @@ class RecordedCircuit:
                 continue
             if self.op[i] == NODE_PACK:
                 n = g.add_pack(self.inputs[i])
+            elif self.op[i] == NODE_ROT_CMUX:  # one step = a one-bit rotation whose stride is the step's rotation
+                n = g.add_blind_rotation(self.inputs[i][1], [self.inputs[i][0]], self.param[i].bit_length() - 1)
             elif self.op[i] == -1:
                 n = g.add_input(ValueKind(self.kind[i]), self.host[i])
             elif self.op[i] == -2:
@@ -286,6 +326,8 @@ class RecordedCircuit:
             if op == NODE_PACK:
                 at = int(a["ext_at"][i])
                 g.add_pack([int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]])
+            elif op == NODE_ROT_CMUX:
+                g.add_blind_rotation(int(a["in"][i, 1]), [int(a["in"][i, 0])], int(a["param"][i]).bit_length() - 1)
             elif op == -1 and host[i] is not None:
                 g.add_input(ValueKind(kind[i]), host[i])
             elif op == -1:

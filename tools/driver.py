@@ -72,6 +72,14 @@ def upload_circuit_inputs(pool, rec, member=-1):
     return vals
 
 
+def _fhe_ops_only(rec):
+    """the native drivers hand every node to spf_pool_submit_op_v as an FheOp: a node of add_blind_rotation is none"""
+    from spf_amd.graph import NODE_ROT_CMUX
+    if NODE_ROT_CMUX in rec.op:
+        raise RuntimeError("the circuit holds add_blind_rotation nodes, which are no FheOp: the per-operation drivers cannot walk it "
+                           "(lower() it into a gate graph, or push the rotation with Pool.push_blind_rotation_v)")
+
+
 def run_circuit_by_handles(pool, rec, threads=64, member=-1, vals=None):
     """-> (outputs as arrays in rec.outputs order, seconds inside the driver, seconds of upload + driver + download).  Every
     operation of the circuit is ONE spf_pool_submit_op_v + spf_pool_wait from one of `threads` native workers.  The second
@@ -79,6 +87,7 @@ def run_circuit_by_handles(pool, rec, threads=64, member=-1, vals=None):
     back (one gathered copy); the Python bookkeeping around the three calls (handle tables, wrappers) is not in it."""
     import time
     from spf_amd import Value
+    _fhe_ops_only(rec)
     d = load()
     lib = pool._lib
     a = rec.arrays()
@@ -134,6 +143,7 @@ def push_circuit_by_handles(pool, rec, member=-1, order=None, flush_conversions=
     import time
     import numpy as np
     from spf_amd import Value
+    _fhe_ops_only(rec)
     d = load()
     lib = pool._lib
     a = rec.arrays()
