@@ -281,7 +281,8 @@ spf_status spf_blind_rotation_batch(spf_ctx *ctx, size_t B, size_t n_bits, size_
  * need intermediates (`spf_circuit_bootstrap_dev`, the keyswitch, `spf_pbs_bivariate_dev`'s packed input,
  * `spf_blind_rotation_dev`'s accumulator between steps) keep them in
  * buffers of the CONTEXT: enqueue them on ONE stream per context (or order the streams with events) — two such calls
- * running concurrently on different streams would share those buffers.  `spf_mod_switch_trace_and_rotate_dev`
+ * running concurrently on different streams would share those buffers.  A call that has to grow a buffer of the context (a
+ * larger batch than the context has seen) may wait for the device before it returns.  `spf_mod_switch_trace_and_rotate_dev`
  * additionally uses its OUTPUT as working memory while it runs (the kernel parks half of its accumulator in each unit's
  * 32 KiB of `d_glev_out` between automorphism rounds):
  * `d_glev_out` holds intermediate data until the kernel has completed and must not be read, or alias anything read, by
