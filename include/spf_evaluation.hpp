@@ -156,6 +156,18 @@ class Evaluation {
     {
         check(spf_group_blind_rotation_batch(grp_, B, n_bits, log_stride, shift_ggsw_fft, input, output));
     }
+    // public_functional_keyswitch (sunscreen_tfhe ops/keyswitch/public_functional_keyswitch.rs:74-148), message j to coefficient j:
+    // B x lwe_count LWEs of from_dimension + 1 words (input j of output b is row b * lwe_count + j) -> B GLWEs.  Its key is no
+    // field of ComputeKey: `PublicFunctionalKeyswitchKey<u64>` words [from_dimension][radix_count][k+1][N], loaded here
+    void load_public_functional_keyswitch_key(const uint64_t* key, size_t n_words, size_t from_dimension, uint32_t radix_log,
+                                              uint32_t radix_count)
+    {
+        check(spf_group_load_public_functional_keyswitch_key_std(grp_, key, n_words, from_dimension, radix_log, radix_count));
+    }
+    void public_functional_keyswitch(uint64_t* output_glwe, const uint64_t* input_lwes, size_t lwe_count, size_t B = 1)
+    {
+        check(spf_group_public_functional_keyswitch_batch(grp_, B, lwe_count, input_lwes, output_glwe));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

@@ -129,11 +129,22 @@ spf_status spf_load_bootstrap_key_std(spf_ctx *ctx, const uint64_t *bsk, size_t 
 spf_status spf_load_automorphism_key_std(spf_ctx *ctx, const uint64_t *ak, size_t n_words);
 /* `SchemeSwitchKey::fft` (entities/scheme_switch_key.rs:174): n_words = 2 x the n_complex of spf_load_scheme_switch_key */
 spf_status spf_load_scheme_switch_key_std(spf_ctx *ctx, const uint64_t *ssk, size_t n_words);
+/* The key of spf_public_functional_keyswitch_* below: `PublicFunctionalKeyswitchKey<u64>`
+ * (sunscreen_tfhe/src/entities/public_functional_keyswitch_key.rs), [from_dimension][radix_count][k+1][N] words — row (i, lvl) is a
+ * GLWE.  Integer form only, like the other `_std` loaders: the words are copied into a key blob and transformed there by the
+ * library's own forward transform (no host FFT, no float loader).  The radix belongs to the KEY, not to spf_params.
+ * n_words = from_dimension * radix_count * (k+1) * N; from_dimension >= 1, radix_log >= 1, radix_count >= 1,
+ * radix_log * radix_count < 64 and from_dimension * radix_count <= 0x0fffffff, else SPF_ERR_INVALID_ARGUMENT; every check runs
+ * before the device is touched.  On any failure the context is left without this key.  A reload with another from_dimension or
+ * radix replaces the key. */
+spf_status spf_load_public_functional_keyswitch_key_std(spf_ctx *ctx, const uint64_t *key, size_t n_words, size_t from_dimension,
+                                                        uint32_t radix_log, uint32_t radix_count);
 
 /* Multi-GPU key replication (no reference counterpart): the device-resident
  * key blobs, so that a caller can RCCL-broadcast rank 0's keys into every other rank's
  * context.  which: 0 = bootstrap key, 1 = keyswitch key, 2 = automorphism key,
- * 3 = scheme-switch key.  Allocates the blob if needed;
+ * 3 = scheme-switch key, 4 = public functional keyswitch key (once its shape is known from a load on this context or, in a
+ * group, on member 0; before that SPF_ERR_NO_KEY).  Allocates the blob if needed;
  * after filling it externally call spf_key_blob_commit. */
 spf_status spf_key_blob(spf_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 spf_status spf_key_blob_commit(spf_ctx *ctx, int which);
@@ -275,6 +286,19 @@ spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx *ctx, size_t B, size_t n_b
 spf_status spf_blind_rotation_batch(spf_ctx *ctx, size_t B, size_t n_bits, size_t log_stride, const double *shift_ggsw_fft,
                                     const uint64_t *glwe_in, uint64_t *glwe_out);
 
+/* `public_functional_keyswitch` (sunscreen_tfhe/src/ops/keyswitch/public_functional_keyswitch.rs:74-148; its leg of the
+ * reference's benchmark: benches/ops.rs:395-452) with the public map of the reference's test and benchmark, message j to
+ * coefficient j: lwe_count <= N LWE ciphertexts (a_j, b_j) of dimension from_dimension in, ONE GLWE out whose coefficient j holds
+ * message j — an LWE enters GLWE-land without a bootstrap.  poly_i = sum_j a_j[i] X^j; for i ascending
+ * `decomposed_polynomial_glev_mad`(acc_fft, Decomp(poly_i), fft(K[i])) (ops/fft_ops.rs:67-98) into ONE spectrum; out = -(ifft(acc_fft))
+ * on every polynomial, then out.body[j] += b_j.  Rows ascending, digits as the reference has them, one inverse transform: the
+ * order is part of the function.  Key: spf_load_public_functional_keyswitch_key_std.
+ * lwe_in: B * lwe_count rows of from_dimension + 1 words, int-major as in the packed calls (input j of output b is row
+ * b * lwe_count + j); glwe_out: B x (k+1)*N.  No key: SPF_ERR_NO_KEY.  lwe_count = 0, lwe_count > N, B * lwe_count > 0x0fffffff
+ * or a null pointer: SPF_ERR_INVALID_ARGUMENT before any device work.  B = 0 is SPF_OK. */
+spf_status spf_public_functional_keyswitch_batch(spf_ctx *ctx, size_t B, size_t lwe_count, const uint64_t *lwe_in,
+                                                 uint64_t *glwe_out);
+
 /* ---- device-pointer forms (inputs/outputs resident in HBM, asynchronous on `stream`) -----
  * Contract of every `_dev` entry point: the call only ENQUEUES on `stream`; inputs and outputs must stay valid and
  * unchanged until that work has completed; an output must not overlap any input of the same call.  The entry points that
@@ -335,6 +359,13 @@ spf_status spf_unpack_circuit_bootstrap_dev(spf_ctx *ctx, void *stream, size_t B
  * last step writing d_glwe_out; d_glwe_in is only read.  An output range that overlaps an input range is refused. */
 spf_status spf_blind_rotation_dev(spf_ctx *ctx, void *stream, size_t B, size_t n_bits, size_t log_stride,
                                   const double *d_shift_ggsw_fft, const uint64_t *d_glwe_in, uint64_t *d_glwe_out);
+
+/* spf_public_functional_keyswitch_batch (`public_functional_keyswitch`, ops/keyswitch/public_functional_keyswitch.rs:74-148) on
+ * device pointers, under the contract of the `_dev` entry points above: it only enqueues on `stream`; on a tuned context at radix
+ * 4 bits x 8 or 4 x 4 the transposed digits of the inputs live in a buffer of the context (one stream per context), which grows
+ * by the same rule.  An output range that overlaps the input range is refused. */
+spf_status spf_public_functional_keyswitch_enqueue(spf_ctx *ctx, void *stream, size_t B, size_t lwe_count, const uint64_t *d_lwe_in,
+                                                   uint64_t *d_glwe_out);
 
 /* ciphertext types (`L0LweCiphertext` ... `L1GlevCiphertext`, crypto/encryption.rs:23-110) and the computing variants of `FheOp`
  * (fhe_circuit.rs:65-126): used by the values, the pool's generic submit and the gate graphs below */
@@ -694,6 +725,12 @@ const char *spf_last_cmux_kernel(spf_ctx *ctx);
  * formulation, when the tuned context's radix fits it (radix_log <= 8 and its accumulator bound), else "keyswitch_kernel".
  * Never NULL. */
 const char *spf_last_keyswitch_kernel(spf_ctx *ctx);
+/* The same for spf_public_functional_keyswitch_* (public_functional_keyswitch.rs:74-148): on a tuned context at radix 4 bits x 8 or
+ * 4 x 4 "pufks4_kernel<4,8>" / "pufks4_kernel<4,4>" (<LOGB,L>: four waves per output, one output per workgroup) up to one output per
+ * CU, beyond that "pufks_kernel<4,8,G>" / "pufks_kernel<4,4,G>" (<LOGB,L,outputs per workgroup>), G = 2 while the call holds at
+ * most two workgroups per CU, 4 beyond; a launch holds at most 4096 outputs (or what keeps its digits within 8 GiB), larger batches go in
+ * several.  Everything else, N = 2048 / k = 1 at another radix included: "generic_pufks_kernel".  Never NULL. */
+const char *spf_last_public_functional_keyswitch_kernel(spf_ctx *ctx);
 
 /* ---- device groups: every GPU of a node from ONE host process (SURVEY.md §8 b / e) -------------------------------- *
  *
@@ -742,6 +779,9 @@ spf_status spf_group_load_bootstrap_key_std(spf_group *grp, const uint64_t *bsk,
 spf_status spf_group_load_automorphism_key_std(spf_group *grp, const uint64_t *ak, size_t n_words);
 spf_status spf_group_load_scheme_switch_key_std(spf_group *grp, const uint64_t *ssk, size_t n_words);
 spf_status spf_group_load_compute_key_nonfft_bincode(spf_group *grp, const uint8_t *bytes, size_t len);
+/* `PublicFunctionalKeyswitchKey<u64>` (entities/public_functional_keyswitch_key.rs): as spf_load_public_functional_keyswitch_key_std */
+spf_status spf_group_load_public_functional_keyswitch_key_std(spf_group *grp, const uint64_t *key, size_t n_words,
+                                                              size_t from_dimension, uint32_t radix_log, uint32_t radix_count);
 /* replicate whatever member 0 holds (keys put there through spf_group_ctx(grp, 0), e.g. generated on the device into
  * spf_key_blob + spf_key_blob_commit) */
 spf_status spf_group_replicate_keys(spf_group *grp);
@@ -791,6 +831,10 @@ spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group *grp, size_t B, si
 /* `blind_rotation` (ops/bootstrapping/blind_rotation.rs:202-223), sharded by item (a member's selectors are at * n_bits onwards) */
 spf_status spf_group_blind_rotation_batch(spf_group *grp, size_t B, size_t n_bits, size_t log_stride, const double *shift_ggsw_fft,
                                           const uint64_t *glwe_in, uint64_t *glwe_out);
+/* `public_functional_keyswitch` (ops/keyswitch/public_functional_keyswitch.rs:74-148), sharded by output (a member's rows are
+ * at * lwe_count onwards) */
+spf_status spf_group_public_functional_keyswitch_batch(spf_group *grp, size_t B, size_t lwe_count, const uint64_t *lwe_in,
+                                                       uint64_t *glwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

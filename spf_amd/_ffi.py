@@ -52,6 +52,7 @@ SYMBOLS = [
     ("spf_load_bootstrap_key_std", _I, [_P, _P, _SZ]),
     ("spf_load_automorphism_key_std", _I, [_P, _P, _SZ]),
     ("spf_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
+    ("spf_load_public_functional_keyswitch_key_std", _I, [_P, _P, _SZ, _SZ, _U32, _U32]),
     ("spf_key_blob", _I, [_P, _I, C.POINTER(_P), C.POINTER(_SZ)]),
     ("spf_key_blob_commit", _I, [_P, _I]),
     ("spf_keyswitch_lwe_l1_lwe_l0_batch", _I, [_P, _SZ, _P, _P]),
@@ -84,6 +85,8 @@ SYMBOLS = [
     ("spf_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_blind_rotation_batch", _I, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     ("spf_blind_rotation_dev", _I, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    ("spf_public_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_public_functional_keyswitch_enqueue", _I, [_P, _P, _SZ, _SZ, _P, _P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -127,6 +130,7 @@ SYMBOLS = [
     ("spf_last_kernel_ms", _I, [_P, C.c_char_p, C.POINTER(C.c_double), C.POINTER(_I)]),
     ("spf_last_blind_rotate_kernel", C.c_char_p, [_P]),
     ("spf_last_cmux_kernel", C.c_char_p, [_P]),
+    ("spf_last_public_functional_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_last_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_device_alloc", _I, [_P, _SZ, C.POINTER(_P)]),
     ("spf_device_free", _I, [_P, _P]),
@@ -155,6 +159,7 @@ SYMBOLS = [
     ("spf_group_load_bootstrap_key_std", _I, [_P, _P, _SZ]),
     ("spf_group_load_automorphism_key_std", _I, [_P, _P, _SZ]),
     ("spf_group_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
+    ("spf_group_load_public_functional_keyswitch_key_std", _I, [_P, _P, _SZ, _SZ, _U32, _U32]),
     ("spf_group_load_compute_key_nonfft_bincode", _I, [_P, _P, _SZ]),
     ("spf_group_replicate_keys", _I, [_P]),
     ("spf_group_replication_stats", _I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_SZ), C.POINTER(_I),
@@ -183,6 +188,7 @@ SYMBOLS = [
     ("spf_group_glwe_unpack_l1_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_blind_rotation_batch", _I, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
+    ("spf_group_public_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -416,6 +422,21 @@ class Engine:
         a = self._std_words("load_scheme_switch_key_std", ssk, self.params.ssk_complex)
         self._ck(self._lib.spf_load_scheme_switch_key_std(self._h, _ptr(a), a.size))
 
+    def load_public_functional_keyswitch_key_std(self, key: np.ndarray, radix_log: int, radix_count: int):
+        """`PublicFunctionalKeyswitchKey<u64>` words (from_dimension, radix_count, k+1, N) (sunscreen_tfhe
+        entities/public_functional_keyswitch_key.rs); transformed on the device.  The radix belongs to the key."""
+        N, k = self.params.polynomial_degree, self.params.glwe_size
+        if (not isinstance(key, np.ndarray) or key.dtype != np.uint64 or key.ndim != 4
+                or key.shape[1:] != (int(radix_count), k + 1, N)):
+            raise SpfError(-2, f"load_public_functional_keyswitch_key_std: the key is a uint64 array of shape "
+                               f"(from_dimension, {radix_count}, {k + 1}, {N}), got "
+                               f"{getattr(key, 'dtype', type(key))} {getattr(key, 'shape', '')}")
+        a = np.ascontiguousarray(key).reshape(-1)
+        self._pufks_n = None
+        self._ck(self._lib.spf_load_public_functional_keyswitch_key_std(self._h, _ptr(a), a.size, key.shape[0], int(radix_log),
+                                                                        int(radix_count)))
+        self._pufks_n = int(key.shape[0])
+
     def load_compute_key_nonfft_bincode(self, blob: bytes):
         """the bytes `bincode` wrote for a parasol_runtime::ComputeKeyNonFft (keys.rs:145-159), all four keys"""
         buf = np.frombuffer(blob, dtype=np.uint8)
@@ -622,6 +643,19 @@ class Engine:
         self._ck(self._lib.spf_blind_rotation_batch(self._h, x.shape[0], g.shape[1], int(log_stride), _ptr(g), _ptr(x), _ptr(out)))
         return out
 
+    def public_functional_keyswitch(self, lwes) -> np.ndarray:
+        """`public_functional_keyswitch` (sunscreen_tfhe ops/keyswitch/public_functional_keyswitch.rs:74-148), message j to
+        coefficient j: (B, lwe_count, from_dimension + 1) LWEs -> (B, glwe_words), one GLWE per row of lwe_count <= N LWEs"""
+        n = getattr(self, "_pufks_n", None)
+        if n is None:
+            raise SpfError(3, "public functional keyswitch key not loaded")
+        x = _u64(lwes)
+        if x.ndim != 3 or x.shape[2] != n + 1:
+            raise SpfError(-2, f"public_functional_keyswitch: operand must have shape (B, lwe_count, {n + 1}), got {x.shape}")
+        out = np.empty((x.shape[0], self.params.glwe_words), dtype=np.uint64)
+        self._ck(self._lib.spf_public_functional_keyswitch_batch(self._h, x.shape[0], x.shape[1], _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -689,6 +723,9 @@ class Engine:
     def blind_rotation_dev(self, stream, B, n_bits, log_stride, d_shift, d_in, d_out):
         self._ck(self._lib.spf_blind_rotation_dev(self._h, stream, B, n_bits, log_stride, d_shift, d_in, d_out))
 
+    def public_functional_keyswitch_enqueue(self, stream, B, lwe_count, d_lwe_in, d_glwe_out):
+        self._ck(self._lib.spf_public_functional_keyswitch_enqueue(self._h, stream, B, lwe_count, d_lwe_in, d_glwe_out))
+
     # -- device buffers (for chaining the _dev forms without a HIP binding of one's own)
     def device_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()
@@ -727,6 +764,9 @@ class Engine:
 
     def last_cmux_kernel(self) -> str:
         return (self._lib.spf_last_cmux_kernel(self._h) or b"").decode()
+
+    def last_public_functional_keyswitch_kernel(self) -> str:
+        return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()
 
     def last_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_keyswitch_kernel(self._h) or b"").decode()

@@ -553,6 +553,22 @@ spf_status spf_group_load_scheme_switch_key_std(spf_group* g, const uint64_t* ss
     return group_load(g, 3, [&](spf_ctx* c) { return spf_load_scheme_switch_key_std(c, ssk, n_words); });
 }
 
+// the public functional keyswitch key: its shape is not in spf_params, so every other member is told it before the blobs are matched
+spf_status spf_group_load_public_functional_keyswitch_key_std(spf_group* g, const uint64_t* key, size_t n_words, size_t from_dimension,
+                                                              uint32_t radix_log, uint32_t radix_count)
+{
+    return group_load(g, 4, [&](spf_ctx* c) {
+        spf_status s = spf_load_public_functional_keyswitch_key_std(c, key, n_words, from_dimension, radix_log, radix_count);
+        for (size_t i = 1; i < g->m.size(); i++) {
+            spf_ctx* o = g->m[i]->ctx;
+            std::lock_guard<std::recursive_mutex> lk(o->mu);
+            o->pufks_ready = false;
+            if (s == SPF_OK) o->pufks_n = (uint32_t)from_dimension, o->pufks_log = radix_log, o->pufks_count = radix_count;
+        }
+        return s;
+    });
+}
+
 spf_status spf_group_replicate_keys(spf_group* g)
 {
     if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
@@ -740,6 +756,25 @@ spf_status spf_group_blind_rotation_batch(spf_group* g, size_t B, size_t n_bits,
     const size_t w = glwe_words(g->prm), sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
     return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
         return spf_blind_rotation_batch(c, n, n_bits, log_stride, shift + at * n_bits * sw, in + at * w, out + at * w);
+    });
+}
+
+// public functional keyswitch: sharded by output, an output's lwe_count input rows go with it
+spf_status spf_group_public_functional_keyswitch_batch(spf_group* g, size_t B, size_t lwe_count, const uint64_t* in, uint64_t* out)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const char* why = pufks_shape_error(g->prm, B, lwe_count)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
+    size_t n;
+    {
+        spf_ctx* c0 = g->m[0]->ctx;
+        std::lock_guard<std::recursive_mutex> lk(c0->mu);
+        if (!c0->pufks_ready) return gfail(g, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
+        n = c0->pufks_n;
+    }
+    const size_t wi = lwe_count * (n + 1), wo = glwe_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
+        return spf_public_functional_keyswitch_batch(c, cnt, lwe_count, in + at * wi, out + at * wo);
     });
 }
 

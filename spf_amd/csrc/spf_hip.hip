@@ -9,6 +9,7 @@
 #include "spf_cbs_tail.hpp"
 #include "spf_generic.hpp"
 #include "spf_poly_fft.hpp"
+#include "spf_pufks.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -111,6 +112,15 @@ struct spf_ctx {
     bool generic = false;
     uint32_t log_n = 11;
     c64* d_gen_tables = nullptr; // [N/2] twist, then [N/4] transform twiddles
+    // public functional keyswitch (spf_pufks.hpp): the key's spectra [n][count][k+1][N/2]; its shape comes with the key, not with
+    // spf_params.  A tuned context whose key has another radix than the hand-written kernel's runs generic_pufks_kernel and keeps
+    // the generic twist table (d_gen_tables, [N/2] only) for it.
+    c64* d_pufks = nullptr;
+    size_t pufks_bytes = 0;
+    bool pufks_ready = false;
+    uint32_t pufks_n = 0, pufks_log = 0, pufks_count = 0; // from_dimension, radix_log, radix_count (0: no shape yet)
+    DevBuf pufks_dig;                                     // packed digits of pufks_digits_kernel, [outputs of a chunk][n][pstride]
+    const char* last_pufks_kernel = "";
 };
 
 namespace {
@@ -708,7 +718,8 @@ void spf_destroy(spf_ctx* c)
         for (auto& t : v) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
     for (void* p : {(void*)c->d_tables, (void*)c->d_bsk, (void*)c->d_bsk_scaled, (void*)c->d_ksk, (void*)c->d_cbs_lut,
                     c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
-                    c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables})
+                    c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables,
+                    (void*)c->d_pufks, c->pufks_dig.p})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
@@ -743,6 +754,52 @@ static spf_status finish_bootstrap_key(spf_ctx* c)
     return SPF_OK;
 }
 
+// ---- public functional keyswitch: the key's shape and what a context needs besides the key
+
+static size_t pufks_complex(const spf_params& p, uint32_t n, uint32_t count)
+{
+    return (size_t)n * count * (p.glwe_size + 1) * (p.polynomial_degree / 2);
+}
+
+// the hand-written kernel's shapes: N = 2048, k = 1 (a tuned context) at 4 bits x 8 or 4 bits x 4
+static bool pufks_tuned(const spf_ctx* c) { return !c->generic && c->pufks_log == 4 && (c->pufks_count == 8 || c->pufks_count == 4); }
+
+// why (from_dimension, radix) is refused, or nullptr
+static const char* pufks_key_shape_error(size_t from_dimension, uint32_t radix_log, uint32_t radix_count)
+{
+    if (from_dimension == 0) return "from_dimension must be at least 1";
+    if (radix_log == 0 || radix_count == 0 || (uint64_t)radix_log * radix_count >= 64) return "a radix decomposition needs 1 <= radix_log * count < 64";
+    if (from_dimension > 0x0fffffffu / radix_count) return "from_dimension * radix_count above 0x0fffffff";
+    return nullptr;
+}
+
+// what the kernels of this key's shape need on this context besides the key: launch attributes, and on a tuned context that
+// runs the generic kernel the generic twist table e^{+2 pi i j / (2N)}
+static spf_status pufks_prepare(spf_ctx* c)
+{
+    if (pufks_tuned(c)) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks_kernel<4, 8, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks_kernel<4, 8, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(4)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks_kernel<4, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(2)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks_kernel<4, 4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, cmux_lds_bytes(4)));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks4_kernel<4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, kPufks4Lds));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&pufks4_kernel<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, kPufks4Lds));
+        return SPF_OK;
+    }
+    const uint32_t N = c->prm.polynomial_degree, h = N / 2;
+    if (generic_lds_bytes(N, c->prm.glwe_size, false) > 160 * 1024)
+        return fail(c, SPF_ERR_UNSUPPORTED, "(k+1) polynomials of this degree do not fit the generic kernels' LDS");
+    if (!c->d_gen_tables) {
+        std::vector<c64> gt(h);
+        for (uint32_t j = 0; j < h; j++) gt[j] = root_of_unity(j, 2 * (uint64_t)N);
+        HIPCHK(c, hipMalloc((void**)&c->d_gen_tables, gt.size() * sizeof(c64)));
+        HIPCHK(c, hipMemcpy(c->d_gen_tables, gt.data(), gt.size() * sizeof(c64), hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_pufks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)generic_lds_bytes(N, c->prm.glwe_size, false)));
+    return SPF_OK;
+}
+
 spf_status spf_key_blob(spf_ctx* c, int which, void** dev_ptr, size_t* bytes)
 {
     if (!c || !dev_ptr || !bytes) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
@@ -764,8 +821,21 @@ spf_status spf_key_blob(spf_ctx* c, int which, void** dev_ptr, size_t* bytes)
         size_t need = ssk_complex(c->prm) * sizeof(c64);
         if (!c->d_ssk) { HIPCHK(c, hipMalloc((void**)&c->d_ssk, need)); c->ssk_bytes = need; }
         *dev_ptr = c->d_ssk; *bytes = c->ssk_bytes;
+    } else if (which == 4) {
+        // the shape of this key is not in spf_params: it is known once a load (here, or on member 0 of a group) has stated it
+        if (!c->pufks_n) return fail(c, SPF_ERR_NO_KEY, "the public functional keyswitch key has no shape yet: load one first");
+        size_t need = pufks_complex(c->prm, c->pufks_n, c->pufks_count) * sizeof(c64);
+        if (c->d_pufks && c->pufks_bytes != need) { // another shape than the blob was made for
+            c->pufks_ready = false;
+            HIPCHK(c, hipDeviceSynchronize());
+            HIPCHK(c, hipFree(c->d_pufks));
+            c->d_pufks = nullptr; c->pufks_bytes = 0;
+        }
+        if (!c->d_pufks) { HIPCHK(c, hipMalloc((void**)&c->d_pufks, need)); c->pufks_bytes = need; }
+        *dev_ptr = c->d_pufks; *bytes = c->pufks_bytes;
     } else {
-        return fail(c, SPF_ERR_INVALID_ARGUMENT, "which must be 0 (bootstrap), 1 (keyswitch), 2 (automorphism) or 3 (scheme switch)");
+        return fail(c, SPF_ERR_INVALID_ARGUMENT,
+                    "which must be 0 (bootstrap), 1 (keyswitch), 2 (automorphism), 3 (scheme switch) or 4 (public functional keyswitch)");
     }
     return SPF_OK;
 }
@@ -790,6 +860,11 @@ spf_status spf_key_blob_commit(spf_ctx* c, int which)
     }
     else if (which == 2 && c->d_ak) c->ak_ready = true, c->ggsw_const_ready = false;
     else if (which == 3 && c->d_ssk) c->ssk_ready = true, c->ggsw_const_ready = false;
+    else if (which == 4 && c->d_pufks) {
+        spf_status st = pufks_prepare(c);
+        if (st != SPF_OK) return st;
+        c->pufks_ready = true;
+    }
     else return fail(c, SPF_ERR_INVALID_ARGUMENT, "blob not allocated");
     return SPF_OK;
 }
@@ -2208,6 +2283,162 @@ spf_status spf_l1ggsw_constant(spf_ctx* c, int bit, double* ggsw_fft_out)
     const size_t sw = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
     HIPCHK(c, hipMemcpy(ggsw_fft_out, (const char*)c->d_ggsw_const + (size_t)bit * sw, sw, hipMemcpyDeviceToHost));
     return SPF_OK;
+}
+
+// ---------------------------------------------------------------- public functional keyswitch
+// `public_functional_keyswitch` (sunscreen_tfhe/src/ops/keyswitch/public_functional_keyswitch.rs:74-148), map "message j to
+// coefficient j"; the kernels and the order of the arithmetic: spf_pufks.hpp.
+
+// `PublicFunctionalKeyswitchKey<u64>` (entities/public_functional_keyswitch_key.rs), [n][count][k+1][N] words: into the key blob as
+// they are, transformed there polynomial by polynomial (`PolynomialRef::fft`, entities/polynomial.rs:257-274).  Every check runs
+// before the device is touched; the context is without this key from there until the end, and after any failure.
+spf_status spf_load_public_functional_keyswitch_key_std(spf_ctx* c, const uint64_t* key, size_t n_words, size_t from_dimension,
+                                                        uint32_t radix_log, uint32_t radix_count)
+{
+    if (!c) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null context");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    c->pufks_ready = false;
+    if (!key) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const char* why = pufks_key_shape_error(from_dimension, radix_log, radix_count)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    const size_t want = 2 * pufks_complex(c->prm, (uint32_t)from_dimension, radix_count);
+    if (n_words != want)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "public functional keyswitch key length " + std::to_string(n_words) + " words != " +
+                                                     std::to_string(want));
+    c->pufks_n = (uint32_t)from_dimension; c->pufks_log = radix_log; c->pufks_count = radix_count;
+    void* p; size_t bytes;
+    spf_status s = spf_key_blob(c, 4, &p, &bytes);
+    if (s != SPF_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto transform = [&]() -> spf_status {
+        HIPCHK(c, hipMemcpyAsync(p, key, bytes, hipMemcpyHostToDevice, c->stream));
+        const size_t n_polys = n_words / c->prm.polynomial_degree, step = (size_t)1 << 30; // (a grid dimension holds 2^31 - 1)
+        for (size_t at = 0; at < n_polys; at += step) {
+            const size_t nb = std::min(step, n_polys - at);
+            uint64_t* q = (uint64_t*)p + at * c->prm.polynomial_degree;
+            spf_status st = launch_poly_fft(c, c->stream, nb, q, (c64*)q);
+            if (st != SPF_OK) return st;
+        }
+        return SPF_OK;
+    };
+    s = transform();
+    {
+        // (no return before the stream is idle: the copy reads the caller's buffer)
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (s == SPF_OK && e != hipSuccess) s = fail(c, SPF_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    if (s == SPF_OK) s = pufks_prepare(c);
+    if (s != SPF_OK) return s;
+    c->pufks_ready = true;
+    return SPF_OK;
+}
+
+// why (B, lwe_count) is refused, or nullptr
+static const char* pufks_shape_error(const spf_params& p, size_t B, size_t lwe_count)
+{
+    if (lwe_count == 0) return "lwe_count must be at least 1";
+    if (lwe_count > p.polynomial_degree) return "lwe_count above polynomial_degree";
+    if (B > 0x0fffffffu / lwe_count) return "B * lwe_count above 0x0fffffff";
+    return nullptr;
+}
+
+static spf_status pufks_args(spf_ctx* c, size_t B, size_t lwe_count, const void* in, const void* out)
+{
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (const char* why = pufks_shape_error(c->prm, B, lwe_count)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    return SPF_OK;
+}
+
+extern "C++" template <int LOGB, int L>
+static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32_t p, const uint64_t* d_in, uint64_t* d_out)
+{
+    const uint32_t n = c->pufks_n, pstride = (p + 31u) & ~31u;
+    const size_t per_output = (size_t)n * pstride * sizeof(uint32_t), row_words = (size_t)n + 1, gw = glwe_words(c->prm);
+    // outputs per launch: what keeps the digits of a launch within 8 GiB of scratch (half the bytes of the inputs they come from;
+    // at n = 2048, p = 1024 that is the 1024 outputs that fill every CU: with 1 GiB the 128 outputs of a launch left half the
+    // CUs idle, 311 ms per 1024 outputs), a multiple of the outputs per workgroup
+    size_t chunk = std::max<size_t>(4, std::min<size_t>(4096, (((size_t)8 << 30) / per_output) & ~(size_t)3));
+    chunk = std::min(chunk, (B + 3) & ~(size_t)3);
+    spf_status st = ensure(c, c->pufks_dig, chunk * per_output);
+    if (st != SPF_OK) return st;
+    // at most one output per CU: the four-waves-per-output latency shape.  Beyond, two outputs per workgroup while the call fills at
+    // most two workgroups per CU (more CUs at work on a small batch), then four: each key row then serves four outputs from one
+    // trip to memory.  One shape per call, whatever its launches hold.
+    const bool latency = B <= (size_t)c->n_cu, four = B > 4 * (size_t)c->n_cu;
+    for (size_t at = 0; at < B; at += chunk) {
+        const size_t nb = std::min(chunk, B - at);
+        const uint64_t* in = d_in + at * p * row_words;
+        hipLaunchKernelGGL((pufks_digits_kernel<L, LOGB>), dim3((n + 31) / 32, pstride / 32, (unsigned)nb), dim3(256), 0, s, in,
+                           (uint32_t*)c->pufks_dig.p, n, p, pstride);
+        PufksArgs a{c->d_pufks, (const uint32_t*)c->pufks_dig.p, in, d_out + at * gw, c->d_tables, (uint32_t)nb, n, p, pstride};
+        if (latency) {
+            c->last_pufks_kernel = L == 8 ? "pufks4_kernel<4,8>" : "pufks4_kernel<4,4>";
+            hipLaunchKernelGGL((pufks4_kernel<LOGB, L>), dim3((unsigned)nb), dim3(256), kPufks4Lds, s, a);
+        } else if (!four) {
+            c->last_pufks_kernel = L == 8 ? "pufks_kernel<4,8,2>" : "pufks_kernel<4,4,2>";
+            hipLaunchKernelGGL((pufks_kernel<LOGB, L, 2>), dim3((unsigned)((nb + 1) / 2)), dim3(256), cmux_lds_bytes(2), s, a);
+        } else {
+            c->last_pufks_kernel = L == 8 ? "pufks_kernel<4,8,4>" : "pufks_kernel<4,4,4>";
+            hipLaunchKernelGGL((pufks_kernel<LOGB, L, 4>), dim3((unsigned)((nb + 3) / 4)), dim3(512), cmux_lds_bytes(4), s, a);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+spf_status spf_public_functional_keyswitch_enqueue(spf_ctx* c, void* stream, size_t B, size_t lwe_count, const uint64_t* d_lwe_in,
+                                                   uint64_t* d_glwe_out)
+{
+    spf_status st = pufks_args(c, B, lwe_count, d_lwe_in, d_glwe_out);
+    if (st != SPF_OK) return st;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
+    if (B == 0) return SPF_OK;
+    const size_t gw = glwe_words(c->prm), in_bytes = B * lwe_count * ((size_t)c->pufks_n + 1) * 8;
+    {
+        const uintptr_t o0 = (uintptr_t)d_glwe_out, o1 = o0 + B * gw * 8, i0 = (uintptr_t)d_lwe_in;
+        if (o0 < i0 + in_bytes && i0 < o1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (pufks_tuned(c))
+        return c->pufks_count == 8 ? launch_pufks_tuned<4, 8>(c, s, B, (uint32_t)lwe_count, d_lwe_in, d_glwe_out)
+                                   : launch_pufks_tuned<4, 4>(c, s, B, (uint32_t)lwe_count, d_lwe_in, d_glwe_out);
+    GenericPufksArgs ga{};
+    ga.g = generic_shape(c);
+    ga.key = c->d_pufks; ga.n = c->pufks_n; ga.p = (uint32_t)lwe_count; ga.radix_log = c->pufks_log; ga.count = c->pufks_count;
+    c->last_pufks_kernel = "generic_pufks_kernel";
+    const size_t row_words = (size_t)c->pufks_n + 1;
+    for (size_t at = 0; at < B; at += kMaxGridRows) {
+        const size_t nb = std::min(B - at, kMaxGridRows);
+        ga.lwe_in = d_lwe_in + at * lwe_count * row_words; ga.out = d_glwe_out + at * gw;
+        hipLaunchKernelGGL(generic_pufks_kernel, dim3((unsigned)nb), dim3(kGenericThreads), generic_lds_bytes(ga.g.N, ga.g.k, false), s, ga);
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+spf_status spf_public_functional_keyswitch_batch(spf_ctx* c, size_t B, size_t lwe_count, const uint64_t* lwe_in, uint64_t* glwe_out)
+{
+    spf_status s = pufks_args(c, B, lwe_count, lwe_in, glwe_out);
+    if (s != SPF_OK) return s;
+    size_t n;
+    {
+        std::lock_guard<std::recursive_mutex> g(c->mu);
+        if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
+        n = c->pufks_n;
+    }
+    if (B == 0) return SPF_OK;
+    const size_t in_bytes = B * lwe_count * (n + 1) * 8, out_bytes = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, lwe_in, in_bytes}}, out_bytes, glwe_out, [&] {
+        return spf_public_functional_keyswitch_enqueue(c, c->stream, B, lwe_count, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
+}
+
+const char* spf_last_public_functional_keyswitch_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_pufks_kernel;
 }
 
 const char* spf_last_blind_rotate_kernel(spf_ctx* c)
