@@ -168,6 +168,26 @@ class Evaluation {
     {
         check(spf_group_public_functional_keyswitch_batch(grp_, B, lwe_count, input_lwes, output_glwe));
     }
+    // private_functional_keyswitch (sunscreen_tfhe ops/keyswitch/private_functional_keyswitch.rs:107-142) under key `key_index`:
+    // B x lwe_count LWEs of from_dimension + 1 words (input z of output b is row b * lwe_count + z) -> B GLWEs.  Its keys are no
+    // field of ComputeKey: n_keys x `PrivateFunctionalKeyswitchKey<u64>` words [lwe_count][from_dimension+1][radix_count][k+1][N],
+    // back to back (k+1 of them with lwe_count = 1, from_dimension = k N: `CircuitBootstrappingKeyswitchKeys<u64>`), loaded here
+    void load_private_functional_keyswitch_keys(const uint64_t* keys, size_t n_words, size_t n_keys, size_t from_dimension,
+                                                size_t lwe_count, uint32_t radix_log, uint32_t radix_count)
+    {
+        check(spf_group_load_private_functional_keyswitch_keys_std(grp_, keys, n_words, n_keys, from_dimension, lwe_count, radix_log,
+                                                                   radix_count));
+    }
+    void private_functional_keyswitch(uint64_t* output_glwe, const uint64_t* input_lwes, size_t key_index = 0, size_t B = 1)
+    {
+        check(spf_group_private_functional_keyswitch_batch(grp_, key_index, B, input_lwes, output_glwe));
+    }
+    // circuit_bootstrap_via_pfks (ops/bootstrapping/circuit_bootstrapping.rs:162-219): B L0 LWEs -> B GGSW spectra, the layout
+    // `cmux` consumes; needs the bootstrap key and the k+1 keys above
+    void circuit_bootstrap_via_pfks(double* output_ggsw_fft, const uint64_t* input_lwe0, size_t B = 1)
+    {
+        check(spf_group_circuit_bootstrap_via_pfks_batch(grp_, B, input_lwe0, output_ggsw_fft));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

@@ -139,12 +139,25 @@ spf_status spf_load_scheme_switch_key_std(spf_ctx *ctx, const uint64_t *ssk, siz
  * radix replaces the key. */
 spf_status spf_load_public_functional_keyswitch_key_std(spf_ctx *ctx, const uint64_t *key, size_t n_words, size_t from_dimension,
                                                         uint32_t radix_log, uint32_t radix_count);
+/* The keys of spf_private_functional_keyswitch_* below: n_keys x `PrivateFunctionalKeyswitchKey<u64>`
+ * (sunscreen_tfhe/src/entities/private_functional_keyswitch_key.rs:44-46), back to back, each [lwe_count][from_dimension+1][radix_count][k+1][N]
+ * words — row (z, i, lvl) is a GLWE; row i = from_dimension meets the body word.  `CircuitBootstrappingKeyswitchKeys<u64>`
+ * (entities/circuit_bootstrapping_private_keyswitch_keys.rs:28-35) is n_keys = k+1, lwe_count = 1, from_dimension = k*N.  Integer form
+ * only (the operation is integer arithmetic: nothing is transformed).  The radix belongs to the KEYS, not to spf_params.
+ * n_words = n_keys * lwe_count * (from_dimension+1) * radix_count * (k+1) * N; n_keys, from_dimension, lwe_count >= 1, radix_log >= 1,
+ * radix_count >= 1, radix_log * radix_count < 64, n_keys <= 65535, 8 * n_keys * (k+1) * N <= 0x7fffff00 and
+ * lwe_count * (from_dimension+1) * radix_count <= 0x7fffff00, else SPF_ERR_INVALID_ARGUMENT; every check runs before the device is
+ * touched.  On any failure the context is left without these keys.  A reload with another shape or radix replaces them. */
+spf_status spf_load_private_functional_keyswitch_keys_std(spf_ctx *ctx, const uint64_t *keys, size_t n_words, size_t n_keys,
+                                                          size_t from_dimension, size_t lwe_count, uint32_t radix_log,
+                                                          uint32_t radix_count);
 
 /* Multi-GPU key replication (no reference counterpart): the device-resident
  * key blobs, so that a caller can RCCL-broadcast rank 0's keys into every other rank's
  * context.  which: 0 = bootstrap key, 1 = keyswitch key, 2 = automorphism key,
- * 3 = scheme-switch key, 4 = public functional keyswitch key (once its shape is known from a load on this context or, in a
- * group, on member 0; before that SPF_ERR_NO_KEY).  Allocates the blob if needed;
+ * 3 = scheme-switch key, 4 = public functional keyswitch key, 5 = private functional keyswitch keys (the words as loaded; 4 and 5
+ * once their shape is known from a load on this context or, in a group, on member 0; before that SPF_ERR_NO_KEY).  Allocates the
+ * blob if needed;
  * after filling it externally call spf_key_blob_commit. */
 spf_status spf_key_blob(spf_ctx *ctx, int which, void **dev_ptr, size_t *bytes);
 spf_status spf_key_blob_commit(spf_ctx *ctx, int which);
@@ -299,6 +312,31 @@ spf_status spf_blind_rotation_batch(spf_ctx *ctx, size_t B, size_t n_bits, size_
 spf_status spf_public_functional_keyswitch_batch(spf_ctx *ctx, size_t B, size_t lwe_count, const uint64_t *lwe_in,
                                                  uint64_t *glwe_out);
 
+/* `private_functional_keyswitch` (sunscreen_tfhe/src/ops/keyswitch/private_functional_keyswitch.rs:107-142): lwe_count LWE
+ * ciphertexts ct_z = (a_z, b_z) of dimension n = from_dimension in, ONE GLWE out, under the secret linear map baked into key
+ * `key_index` of the loaded set:  out = - sum_z sum_{i <= n} sum_j digit_j(ct_z[i]) * K[z][i][count-1-j], every word mod 2^64
+ * (`ScalarRadixIterator` digits, math/radix.rs; GLEV levels in reverse, `decomposed_scalar_glev_mad`, glev_ciphertext_ops.rs:48-59;
+ * the body word is row i = n and is decomposed like the mask words; no body is added afterwards).  Integer arithmetic only: the
+ * words are the reference's, bit for bit.  Keys: spf_load_private_functional_keyswitch_keys_std.
+ * lwe_in: B * lwe_count rows of from_dimension + 1 words (input z of output b is row b * lwe_count + z); glwe_out: B x (k+1)*N.
+ * No keys: SPF_ERR_NO_KEY.  key_index >= n_keys, B > 0x0fffffff or a null pointer: SPF_ERR_INVALID_ARGUMENT before any device
+ * work.  B = 0 is SPF_OK. */
+spf_status spf_private_functional_keyswitch_batch(spf_ctx *ctx, size_t key_index, size_t B, const uint64_t *lwe_in,
+                                                  uint64_t *glwe_out);
+/* `apply_pfks_on_ggsw_components` (ops/bootstrapping/circuit_bootstrapping.rs:485-514): GGSW row (r, level) is the private
+ * functional keyswitch of LWE `level` under key r.  lwe_in: B * l_cbs rows of k*N + 1 words; ggsw_out: B INTEGER-form GGSWs in the
+ * reference's layout [k+1][l_cbs][k+1][N].  Needs n_keys = k+1, lwe_count = 1, from_dimension = k*N, else
+ * SPF_ERR_INVALID_ARGUMENT.  One launch sequence (the digits of a row are computed once and meet all k+1 keys), word-equal to
+ * k+1 calls of the single operation placed by hand. */
+spf_status spf_apply_pfks_on_ggsw_components_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe_in, uint64_t *ggsw_out);
+/* `circuit_bootstrap_via_pfks` (ops/bootstrapping/circuit_bootstrapping.rs:162-219; its leg of the reference's benchmark:
+ * benches/ops.rs:172-234): `hi_noise_lwe_to_lo_noise_glwe` (what spf_circuit_bootstrap_pbs_* computes), then
+ * `extract_and_rotate_lo_noise_glwe` (:224-252: `sample_extract`(i) and 2^(64 - (cbs_radix_log*(i+1) + 1)) onto the body, i < l_cbs),
+ * then the components call above, then the library's forward transform on every polynomial (spf_poly_fft_*).
+ * ggsw_fft_out: B x (k+1)*l_cbs*(k+1)*N/2 complex, the layout spf_cmux_* consumes.  Needs the bootstrap key and a key set of the
+ * components call's shape. */
+spf_status spf_circuit_bootstrap_via_pfks_batch(spf_ctx *ctx, size_t B, const uint64_t *lwe0_in, double *ggsw_fft_out);
+
 /* ---- device-pointer forms (inputs/outputs resident in HBM, asynchronous on `stream`) -----
  * Contract of every `_dev` entry point: the call only ENQUEUES on `stream`; inputs and outputs must stay valid and
  * unchanged until that work has completed; an output must not overlap any input of the same call.  The entry points that
@@ -366,6 +404,19 @@ spf_status spf_blind_rotation_dev(spf_ctx *ctx, void *stream, size_t B, size_t n
  * by the same rule.  An output range that overlaps the input range is refused. */
 spf_status spf_public_functional_keyswitch_enqueue(spf_ctx *ctx, void *stream, size_t B, size_t lwe_count, const uint64_t *d_lwe_in,
                                                    uint64_t *d_glwe_out);
+
+/* spf_private_functional_keyswitch_batch (`private_functional_keyswitch`, ops/keyswitch/private_functional_keyswitch.rs:107-142),
+ * spf_apply_pfks_on_ggsw_components_batch (`apply_pfks_on_ggsw_components`, circuit_bootstrapping.rs:485-514) and
+ * spf_circuit_bootstrap_via_pfks_batch (`circuit_bootstrap_via_pfks`, circuit_bootstrapping.rs:162-219) on device pointers, under
+ * the contract of the `_dev` entry points above: each only enqueues on `stream`; the int8 limbs of the inputs and, for the circuit
+ * bootstrap, the lo-noise GLWEs and the extracted rows live in buffers of the context (one stream per context), which grow by
+ * the same rule.  An output range that overlaps the input range is refused. */
+spf_status spf_private_functional_keyswitch_enqueue(spf_ctx *ctx, void *stream, size_t key_index, size_t B, const uint64_t *d_lwe_in,
+                                                    uint64_t *d_glwe_out);
+spf_status spf_apply_pfks_on_ggsw_components_enqueue(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_lwe_in,
+                                                     uint64_t *d_ggsw_out);
+spf_status spf_circuit_bootstrap_via_pfks_enqueue(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_lwe0_in,
+                                                  double *d_ggsw_fft_out);
 
 /* ciphertext types (`L0LweCiphertext` ... `L1GlevCiphertext`, crypto/encryption.rs:23-110) and the computing variants of `FheOp`
  * (fhe_circuit.rs:65-126): used by the values, the pool's generic submit and the gate graphs below */
@@ -731,6 +782,12 @@ const char *spf_last_keyswitch_kernel(spf_ctx *ctx);
  * most two workgroups per CU, 4 beyond; a launch holds at most 4096 outputs (or what keeps its digits within 8 GiB), larger batches go in
  * several.  Everything else, N = 2048 / k = 1 at another radix included: "generic_pufks_kernel".  Never NULL. */
 const char *spf_last_public_functional_keyswitch_kernel(spf_ctx *ctx);
+/* The same for spf_private_functional_keyswitch_*, the components call and the circuit bootstrap via PFKS
+ * (private_functional_keyswitch.rs:107-142): "pfks_gemm_kernel<U>" — the int8 matrix-core GEMM with U limbs per digit, U = 1 for
+ * radix_log <= 8, else ceil((radix_log + 1) / 8): 2 up to 15 bits, 3 up to 23 — or "pfks_valu_kernel" for radix_log >= 24 and
+ * for a key whose single tile of 128 rows of limbs would exceed the 1 GiB scratch cap of a launch.  A launch holds the rows whose
+ * limbs fit that cap; larger batches go in several.  Never NULL. */
+const char *spf_last_private_functional_keyswitch_kernel(spf_ctx *ctx);
 
 /* ---- device groups: every GPU of a node from ONE host process (SURVEY.md §8 b / e) -------------------------------- *
  *
@@ -782,6 +839,11 @@ spf_status spf_group_load_compute_key_nonfft_bincode(spf_group *grp, const uint8
 /* `PublicFunctionalKeyswitchKey<u64>` (entities/public_functional_keyswitch_key.rs): as spf_load_public_functional_keyswitch_key_std */
 spf_status spf_group_load_public_functional_keyswitch_key_std(spf_group *grp, const uint64_t *key, size_t n_words,
                                                               size_t from_dimension, uint32_t radix_log, uint32_t radix_count);
+/* n_keys x `PrivateFunctionalKeyswitchKey<u64>` (entities/private_functional_keyswitch_key.rs:44-46): as
+ * spf_load_private_functional_keyswitch_keys_std */
+spf_status spf_group_load_private_functional_keyswitch_keys_std(spf_group *grp, const uint64_t *keys, size_t n_words, size_t n_keys,
+                                                                size_t from_dimension, size_t lwe_count, uint32_t radix_log,
+                                                                uint32_t radix_count);
 /* replicate whatever member 0 holds (keys put there through spf_group_ctx(grp, 0), e.g. generated on the device into
  * spf_key_blob + spf_key_blob_commit) */
 spf_status spf_group_replicate_keys(spf_group *grp);
@@ -835,6 +897,11 @@ spf_status spf_group_blind_rotation_batch(spf_group *grp, size_t B, size_t n_bit
  * at * lwe_count onwards) */
 spf_status spf_group_public_functional_keyswitch_batch(spf_group *grp, size_t B, size_t lwe_count, const uint64_t *lwe_in,
                                                        uint64_t *glwe_out);
+/* `private_functional_keyswitch` (ops/keyswitch/private_functional_keyswitch.rs:107-142), sharded by output (a member's rows are
+ * at * lwe_count onwards), and `circuit_bootstrap_via_pfks` (ops/bootstrapping/circuit_bootstrapping.rs:162-219), sharded by item */
+spf_status spf_group_private_functional_keyswitch_batch(spf_group *grp, size_t key_index, size_t B, const uint64_t *lwe_in,
+                                                        uint64_t *glwe_out);
+spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group *grp, size_t B, const uint64_t *lwe0_in, double *ggsw_fft_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

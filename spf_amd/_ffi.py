@@ -53,6 +53,7 @@ SYMBOLS = [
     ("spf_load_automorphism_key_std", _I, [_P, _P, _SZ]),
     ("spf_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
     ("spf_load_public_functional_keyswitch_key_std", _I, [_P, _P, _SZ, _SZ, _U32, _U32]),
+    ("spf_load_private_functional_keyswitch_keys_std", _I, [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _U32]),
     ("spf_key_blob", _I, [_P, _I, C.POINTER(_P), C.POINTER(_SZ)]),
     ("spf_key_blob_commit", _I, [_P, _I]),
     ("spf_keyswitch_lwe_l1_lwe_l0_batch", _I, [_P, _SZ, _P, _P]),
@@ -87,6 +88,12 @@ SYMBOLS = [
     ("spf_blind_rotation_dev", _I, [_P, _P, _SZ, _SZ, _SZ, _P, _P, _P]),
     ("spf_public_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_public_functional_keyswitch_enqueue", _I, [_P, _P, _SZ, _SZ, _P, _P]),
+    ("spf_private_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_private_functional_keyswitch_enqueue", _I, [_P, _P, _SZ, _SZ, _P, _P]),
+    ("spf_apply_pfks_on_ggsw_components_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_apply_pfks_on_ggsw_components_enqueue", _I, [_P, _P, _SZ, _P, _P]),
+    ("spf_circuit_bootstrap_via_pfks_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_circuit_bootstrap_via_pfks_enqueue", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -131,6 +138,7 @@ SYMBOLS = [
     ("spf_last_blind_rotate_kernel", C.c_char_p, [_P]),
     ("spf_last_cmux_kernel", C.c_char_p, [_P]),
     ("spf_last_public_functional_keyswitch_kernel", C.c_char_p, [_P]),
+    ("spf_last_private_functional_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_last_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_device_alloc", _I, [_P, _SZ, C.POINTER(_P)]),
     ("spf_device_free", _I, [_P, _P]),
@@ -160,6 +168,7 @@ SYMBOLS = [
     ("spf_group_load_automorphism_key_std", _I, [_P, _P, _SZ]),
     ("spf_group_load_scheme_switch_key_std", _I, [_P, _P, _SZ]),
     ("spf_group_load_public_functional_keyswitch_key_std", _I, [_P, _P, _SZ, _SZ, _U32, _U32]),
+    ("spf_group_load_private_functional_keyswitch_keys_std", _I, [_P, _P, _SZ, _SZ, _SZ, _SZ, _U32, _U32]),
     ("spf_group_load_compute_key_nonfft_bincode", _I, [_P, _P, _SZ]),
     ("spf_group_replicate_keys", _I, [_P]),
     ("spf_group_replication_stats", _I, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_SZ), C.POINTER(_I),
@@ -189,6 +198,8 @@ SYMBOLS = [
     ("spf_group_unpack_circuit_bootstrap_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_blind_rotation_batch", _I, [_P, _SZ, _SZ, _SZ, _P, _P, _P]),
     ("spf_group_public_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_group_private_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
+    ("spf_group_circuit_bootstrap_via_pfks_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -437,6 +448,22 @@ class Engine:
                                                                         int(radix_count)))
         self._pufks_n = int(key.shape[0])
 
+    def load_private_functional_keyswitch_keys_std(self, keys: np.ndarray, radix_log: int, radix_count: int):
+        """n_keys x `PrivateFunctionalKeyswitchKey<u64>` words (n_keys, lwe_count, from_dimension + 1, radix_count, k+1, N)
+        (sunscreen_tfhe entities/private_functional_keyswitch_key.rs:44-46); integer form, used as it is.  The radix belongs to
+        the keys.  (k+1, 1, k*N + 1, ...) is `CircuitBootstrappingKeyswitchKeys<u64>`."""
+        N, k = self.params.polynomial_degree, self.params.glwe_size
+        if (not isinstance(keys, np.ndarray) or keys.dtype != np.uint64 or keys.ndim != 6
+                or keys.shape[3:] != (int(radix_count), k + 1, N)):
+            raise SpfError(-2, f"load_private_functional_keyswitch_keys_std: the keys are a uint64 array of shape (n_keys, "
+                               f"lwe_count, from_dimension + 1, {radix_count}, {k + 1}, {N}), got "
+                               f"{getattr(keys, 'dtype', type(keys))} {getattr(keys, 'shape', '')}")
+        a = np.ascontiguousarray(keys).reshape(-1)
+        self._pfks_shape = None
+        self._ck(self._lib.spf_load_private_functional_keyswitch_keys_std(self._h, _ptr(a), a.size, keys.shape[0], keys.shape[2] - 1,
+                                                                          keys.shape[1], int(radix_log), int(radix_count)))
+        self._pfks_shape = (int(keys.shape[0]), int(keys.shape[1]), int(keys.shape[2]) - 1)
+
     def load_compute_key_nonfft_bincode(self, blob: bytes):
         """the bytes `bincode` wrote for a parasol_runtime::ComputeKeyNonFft (keys.rs:145-159), all four keys"""
         buf = np.frombuffer(blob, dtype=np.uint8)
@@ -656,6 +683,44 @@ class Engine:
         self._ck(self._lib.spf_public_functional_keyswitch_batch(self._h, x.shape[0], x.shape[1], _ptr(x), _ptr(out)))
         return out
 
+    def _pfks(self):
+        shape = getattr(self, "_pfks_shape", None)
+        if shape is None:
+            raise SpfError(3, "private functional keyswitch keys not loaded")
+        return shape
+
+    def private_functional_keyswitch(self, lwes, key_index: int = 0) -> np.ndarray:
+        """`private_functional_keyswitch` (sunscreen_tfhe ops/keyswitch/private_functional_keyswitch.rs:107-142) under key
+        `key_index`: (B, lwe_count, from_dimension + 1) LWEs -> (B, glwe_words)"""
+        _, p, n = self._pfks()
+        x = _u64(lwes)
+        if x.ndim != 3 or x.shape[1:] != (p, n + 1):
+            raise SpfError(-2, f"private_functional_keyswitch: operand must have shape (B, {p}, {n + 1}), got {x.shape}")
+        out = np.empty((x.shape[0], self.params.glwe_words), dtype=np.uint64)
+        self._ck(self._lib.spf_private_functional_keyswitch_batch(self._h, int(key_index), x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
+    def apply_pfks_on_ggsw_components(self, lwes) -> np.ndarray:
+        """`apply_pfks_on_ggsw_components` (ops/bootstrapping/circuit_bootstrapping.rs:485-514): (B, l_cbs, k*N + 1) LWEs ->
+        (B, k+1, l_cbs, k+1, N) integer-form GGSWs"""
+        _, _, n = self._pfks()
+        N, k, L = self.params.polynomial_degree, self.params.glwe_size, self.params.cbs_radix_count
+        x = _u64(lwes)
+        if x.ndim != 3 or x.shape[1:] != (L, n + 1):
+            raise SpfError(-2, f"apply_pfks_on_ggsw_components: operand must have shape (B, {L}, {n + 1}), got {x.shape}")
+        out = np.empty((x.shape[0], k + 1, L, k + 1, N), dtype=np.uint64)
+        self._ck(self._lib.spf_apply_pfks_on_ggsw_components_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
+    def circuit_bootstrap_via_pfks(self, lwe0) -> np.ndarray:
+        """`circuit_bootstrap_via_pfks` (ops/bootstrapping/circuit_bootstrapping.rs:162-219): (B, lwe0_words) -> GGSW spectra in
+        the layout `cmux` consumes, as `circuit_bootstrap` returns them"""
+        self._pfks()
+        x = _u64(lwe0).reshape(-1, self.params.lwe0_words)
+        out = np.empty((x.shape[0], self.params.cbs_ggsw_complex), dtype=np.complex128)
+        self._ck(self._lib.spf_circuit_bootstrap_via_pfks_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -726,6 +791,15 @@ class Engine:
     def public_functional_keyswitch_enqueue(self, stream, B, lwe_count, d_lwe_in, d_glwe_out):
         self._ck(self._lib.spf_public_functional_keyswitch_enqueue(self._h, stream, B, lwe_count, d_lwe_in, d_glwe_out))
 
+    def private_functional_keyswitch_enqueue(self, stream, key_index, B, d_lwe_in, d_glwe_out):
+        self._ck(self._lib.spf_private_functional_keyswitch_enqueue(self._h, stream, key_index, B, d_lwe_in, d_glwe_out))
+
+    def apply_pfks_on_ggsw_components_enqueue(self, stream, B, d_lwe_in, d_ggsw_out):
+        self._ck(self._lib.spf_apply_pfks_on_ggsw_components_enqueue(self._h, stream, B, d_lwe_in, d_ggsw_out))
+
+    def circuit_bootstrap_via_pfks_enqueue(self, stream, B, d_lwe0_in, d_ggsw_fft_out):
+        self._ck(self._lib.spf_circuit_bootstrap_via_pfks_enqueue(self._h, stream, B, d_lwe0_in, d_ggsw_fft_out))
+
     # -- device buffers (for chaining the _dev forms without a HIP binding of one's own)
     def device_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()
@@ -767,6 +841,9 @@ class Engine:
 
     def last_public_functional_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()
+
+    def last_private_functional_keyswitch_kernel(self) -> str:
+        return (self._lib.spf_last_private_functional_keyswitch_kernel(self._h) or b"").decode()
 
     def last_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_keyswitch_kernel(self._h) or b"").decode()

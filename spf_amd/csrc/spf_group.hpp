@@ -280,7 +280,8 @@ spf_status group_split(spf_group* g, size_t B, const std::function<spf_status(sp
 bool blob_ready(spf_ctx* c, int which)
 {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
-    return which == 0 ? c->bsk_ready : which == 1 ? c->ksk_ready : which == 2 ? c->ak_ready : c->ssk_ready;
+    return which == 0 ? c->bsk_ready : which == 1 ? c->ksk_ready : which == 2 ? c->ak_ready : which == 3 ? c->ssk_ready
+           : which == 4 ? c->pufks_ready : c->pfks_ready;
 }
 
 spf_status ensure_rccl(spf_group* g)
@@ -569,6 +570,25 @@ spf_status spf_group_load_public_functional_keyswitch_key_std(spf_group* g, cons
     });
 }
 
+// the private functional keyswitch keys: blob 5, the words as loaded; every member derives its own byte planes at the commit
+spf_status spf_group_load_private_functional_keyswitch_keys_std(spf_group* g, const uint64_t* keys, size_t n_words, size_t n_keys,
+                                                                size_t from_dimension, size_t lwe_count, uint32_t radix_log,
+                                                                uint32_t radix_count)
+{
+    return group_load(g, 5, [&](spf_ctx* c) {
+        spf_status s = spf_load_private_functional_keyswitch_keys_std(c, keys, n_words, n_keys, from_dimension, lwe_count, radix_log, radix_count);
+        for (size_t i = 1; i < g->m.size(); i++) {
+            spf_ctx* o = g->m[i]->ctx;
+            std::lock_guard<std::recursive_mutex> lk(o->mu);
+            o->pfks_ready = false;
+            if (s == SPF_OK)
+                o->pfks_keys = (uint32_t)n_keys, o->pfks_n = (uint32_t)from_dimension, o->pfks_p = (uint32_t)lwe_count, o->pfks_log = radix_log,
+                o->pfks_count = radix_count;
+        }
+        return s;
+    });
+}
+
 spf_status spf_group_replicate_keys(spf_group* g)
 {
     if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
@@ -775,6 +795,36 @@ spf_status spf_group_public_functional_keyswitch_batch(spf_group* g, size_t B, s
     const size_t wi = lwe_count * (n + 1), wo = glwe_words(g->prm);
     return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
         return spf_public_functional_keyswitch_batch(c, cnt, lwe_count, in + at * wi, out + at * wo);
+    });
+}
+
+// private functional keyswitch: sharded by output, an output's lwe_count input rows go with it
+spf_status spf_group_private_functional_keyswitch_batch(spf_group* g, size_t key_index, size_t B, const uint64_t* in, uint64_t* out)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t wi;
+    {
+        spf_ctx* c0 = g->m[0]->ctx;
+        std::lock_guard<std::recursive_mutex> lk(c0->mu);
+        if (!c0->pfks_ready) return gfail(g, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
+        if (key_index >= c0->pfks_keys) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
+        wi = pfks_row_words(c0);
+    }
+    if (B > 0x0fffffffu) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    const size_t wo = glwe_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
+        return spf_private_functional_keyswitch_batch(c, key_index, cnt, in + at * wi, out + at * wo);
+    });
+}
+
+// circuit bootstrap via PFKS: sharded by item
+spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
+{
+    SPF_GROUP_NULL(!lwe || !out);
+    const size_t wi = lwe0_words(g->prm), wo = ggsw_words(g->prm);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
+        return spf_circuit_bootstrap_via_pfks_batch(c, cnt, lwe + at * wi, out + at * wo);
     });
 }
 

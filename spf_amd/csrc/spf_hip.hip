@@ -10,6 +10,7 @@
 #include "spf_generic.hpp"
 #include "spf_poly_fft.hpp"
 #include "spf_pufks.hpp"
+#include "spf_pfks.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -121,6 +122,17 @@ struct spf_ctx {
     uint32_t pufks_n = 0, pufks_log = 0, pufks_count = 0; // from_dimension, radix_log, radix_count (0: no shape yet)
     DevBuf pufks_dig;                                     // packed digits of pufks_digits_kernel, [outputs of a chunk][n][pstride]
     const char* last_pufks_kernel = "";
+    // private functional keyswitch (spf_pfks.hpp): n_keys keys back to back, each [lwe_count][n+1][count][k+1][N] words, as loaded
+    // (key blob 5); their byte planes for the matrix-core path (null where that path declines the key: the VALU kernel reads the
+    // words).  The shape comes with the keys.
+    uint64_t* d_pfks = nullptr;
+    size_t pfks_bytes = 0;
+    bool pfks_ready = false;
+    uint32_t pfks_keys = 0, pfks_n = 0, pfks_p = 0, pfks_log = 0, pfks_count = 0; // n_keys, from_dimension, lwe_count, radix (0: no shape yet)
+    int8_t* d_pfks_planes = nullptr;
+    DevBuf pfks_dig, pfks_rowsum; // limbs [U][Mpad][Kpad] and limb sums [nseg][U][Mpad] of one launch
+    DevBuf pfks_glwe, pfks_lwe;   // circuit bootstrap via PFKS: the lo-noise GLWEs and the extracted, rotated LWE rows
+    const char* last_pfks_kernel = "";
 };
 
 namespace {
@@ -719,7 +731,8 @@ void spf_destroy(spf_ctx* c)
     for (void* p : {(void*)c->d_tables, (void*)c->d_bsk, (void*)c->d_bsk_scaled, (void*)c->d_ksk, (void*)c->d_cbs_lut,
                     c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
                     c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables,
-                    (void*)c->d_pufks, c->pufks_dig.p})
+                    (void*)c->d_pufks, c->pufks_dig.p, (void*)c->d_pfks, (void*)c->d_pfks_planes, c->pfks_dig.p, c->pfks_rowsum.p, c->pfks_glwe.p,
+                    c->pfks_lwe.p})
         if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
@@ -800,6 +813,53 @@ static spf_status pufks_prepare(spf_ctx* c)
     return SPF_OK;
 }
 
+// ---- private functional keyswitch: the keys' shape and what a context derives from them (spf_pfks.hpp)
+
+constexpr size_t kPfksDigitCap = (size_t)1 << 30; // bytes of limb scratch one launch may use; larger batches go in several launches
+
+static size_t pfks_row_words(const spf_ctx* c) { return (size_t)c->pfks_p * ((size_t)c->pfks_n + 1); }
+static size_t pfks_K(const spf_ctx* c) { return pfks_row_words(c) * c->pfks_count; }
+static size_t pfks_Kpad(const spf_ctx* c) { return (pfks_K(c) + 127) & ~(size_t)127; }
+
+// why a key set of this shape is refused, or nullptr; *words receives n_keys * lwe_count * (n+1) * count * (k+1) * N
+static const char* pfks_key_shape_error(const spf_params& p, size_t n_keys, size_t from_dimension, size_t lwe_count, uint32_t radix_log,
+                                        uint32_t radix_count, size_t* words)
+{
+    if (n_keys == 0 || from_dimension == 0 || lwe_count == 0) return "n_keys, from_dimension and lwe_count must be at least 1";
+    if (radix_log == 0 || radix_count == 0 || (uint64_t)radix_log * radix_count >= 64) return "a radix decomposition needs 1 <= radix_log * count < 64";
+    const size_t W = glwe_words(p), lim = 0x7fffff00u;
+    if (n_keys > 65535 || n_keys > lim / (8 * W)) return "n_keys * (k+1) * N above the index range";
+    if (from_dimension >= lim || lwe_count > lim / (from_dimension + 1) || lwe_count * (from_dimension + 1) > lim / radix_count)
+        return "lwe_count * (from_dimension + 1) * radix_count above 0x7fffff00";
+    const size_t K = lwe_count * (from_dimension + 1) * radix_count;
+    if (K > ((size_t)1 << 60) / (n_keys * W)) return "the key set is too large";
+    *words = n_keys * K * W;
+    return nullptr;
+}
+
+// the byte planes of the keys in the blob, where the matrix-core path takes them: radix_log <= 23 and a tile of 128 rows of limbs
+// within the scratch cap.  Everything else is served from the words by pfks_valu_kernel.
+static spf_status pfks_prepare(spf_ctx* c)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->d_pfks_planes) {
+        HIPCHK(c, hipDeviceSynchronize());
+        HIPCHK(c, hipFree(c->d_pfks_planes));
+        c->d_pfks_planes = nullptr;
+    }
+    const uint32_t U = pfks_limbs(c->pfks_log);
+    const size_t K = pfks_K(c), Kpad = pfks_Kpad(c), W = glwe_words(c->prm);
+    if (U == 0 || (size_t)PFKS_TILE * Kpad * U > kPfksDigitCap) return SPF_OK;
+    const size_t npad = ((8 * (size_t)c->pfks_keys * W + 127) & ~(size_t)127) + PFKS_TILE; // a tile may start at any key's first plane row
+    HIPCHK(c, hipMalloc((void**)&c->d_pfks_planes, npad * Kpad));
+    HIPCHK(c, hipMemsetAsync(c->d_pfks_planes, 0, npad * Kpad, c->stream));
+    hipLaunchKernelGGL(pfks_planes_kernel, dim3((unsigned)(Kpad / 32), (unsigned)((W + 31) / 32), c->pfks_keys), dim3(256), 0, c->stream,
+                       c->d_pfks, c->d_pfks_planes, c->pfks_count, (uint32_t)W, (uint32_t)K, (uint32_t)Kpad);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SPF_OK;
+}
+
 spf_status spf_key_blob(spf_ctx* c, int which, void** dev_ptr, size_t* bytes)
 {
     if (!c || !dev_ptr || !bytes) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
@@ -833,9 +893,21 @@ spf_status spf_key_blob(spf_ctx* c, int which, void** dev_ptr, size_t* bytes)
         }
         if (!c->d_pufks) { HIPCHK(c, hipMalloc((void**)&c->d_pufks, need)); c->pufks_bytes = need; }
         *dev_ptr = c->d_pufks; *bytes = c->pufks_bytes;
+    } else if (which == 5) {
+        // as for 4: the shape comes with a load
+        if (!c->pfks_keys) return fail(c, SPF_ERR_NO_KEY, "the private functional keyswitch keys have no shape yet: load them first");
+        size_t need = (size_t)c->pfks_keys * pfks_K(c) * glwe_words(c->prm) * 8;
+        if (c->d_pfks && c->pfks_bytes != need) {
+            c->pfks_ready = false;
+            HIPCHK(c, hipDeviceSynchronize());
+            HIPCHK(c, hipFree(c->d_pfks));
+            c->d_pfks = nullptr; c->pfks_bytes = 0;
+        }
+        if (!c->d_pfks) { HIPCHK(c, hipMalloc((void**)&c->d_pfks, need)); c->pfks_bytes = need; }
+        *dev_ptr = c->d_pfks; *bytes = c->pfks_bytes;
     } else {
-        return fail(c, SPF_ERR_INVALID_ARGUMENT,
-                    "which must be 0 (bootstrap), 1 (keyswitch), 2 (automorphism), 3 (scheme switch) or 4 (public functional keyswitch)");
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "which must be 0 (bootstrap), 1 (keyswitch), 2 (automorphism), 3 (scheme switch), "
+                                                 "4 (public functional keyswitch) or 5 (private functional keyswitch)");
     }
     return SPF_OK;
 }
@@ -864,6 +936,12 @@ spf_status spf_key_blob_commit(spf_ctx* c, int which)
         spf_status st = pufks_prepare(c);
         if (st != SPF_OK) return st;
         c->pufks_ready = true;
+    }
+    else if (which == 5 && c->d_pfks) {
+        c->pfks_ready = false;
+        spf_status st = pfks_prepare(c);
+        if (st != SPF_OK) return st;
+        c->pfks_ready = true;
     }
     else return fail(c, SPF_ERR_INVALID_ARGUMENT, "blob not allocated");
     return SPF_OK;
@@ -2439,6 +2517,238 @@ const char* spf_last_public_functional_keyswitch_kernel(spf_ctx* c)
     if (!c) return "";
     std::lock_guard<std::recursive_mutex> g(c->mu);
     return c->last_pufks_kernel;
+}
+
+// ---------------------------------------------------------------- private functional keyswitch
+// `private_functional_keyswitch` (sunscreen_tfhe/src/ops/keyswitch/private_functional_keyswitch.rs:107-142) and
+// `circuit_bootstrap_via_pfks` (ops/bootstrapping/circuit_bootstrapping.rs:162-219); kernels and arithmetic: spf_pfks.hpp.
+
+// `PrivateFunctionalKeyswitchKey<u64>` (entities/private_functional_keyswitch_key.rs:44-46) x n_keys, back to back (n_keys = k+1,
+// lwe_count = 1, n = k N: `CircuitBootstrappingKeyswitchKeys<u64>`, entities/circuit_bootstrapping_private_keyswitch_keys.rs:28-35).
+// Every check runs before the device is touched; the context is without these keys from there until the end, and after any failure.
+spf_status spf_load_private_functional_keyswitch_keys_std(spf_ctx* c, const uint64_t* keys, size_t n_words, size_t n_keys,
+                                                          size_t from_dimension, size_t lwe_count, uint32_t radix_log, uint32_t radix_count)
+{
+    if (!c) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null context");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    c->pfks_ready = false;
+    if (!keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t want = 0;
+    if (const char* why = pfks_key_shape_error(c->prm, n_keys, from_dimension, lwe_count, radix_log, radix_count, &want))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    if (n_words != want)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "private functional keyswitch key length " + std::to_string(n_words) + " words != " +
+                                                     std::to_string(want));
+    c->pfks_keys = (uint32_t)n_keys; c->pfks_n = (uint32_t)from_dimension; c->pfks_p = (uint32_t)lwe_count;
+    c->pfks_log = radix_log; c->pfks_count = radix_count;
+    void* p; size_t bytes;
+    spf_status s = spf_key_blob(c, 5, &p, &bytes);
+    if (s != SPF_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpy(p, keys, bytes, hipMemcpyHostToDevice));
+    s = pfks_prepare(c);
+    if (s != SPF_OK) return s;
+    c->pfks_ready = true;
+    return SPF_OK;
+}
+
+// M rows of lwe_count * (n+1) words against `nk` keys from `key0` on, each result where `dst` places it
+static spf_status launch_pfks(spf_ctx* c, hipStream_t s, size_t M, const uint64_t* d_in, uint32_t key0, uint32_t nk, PfksDest dst)
+{
+    const size_t W = glwe_words(c->prm), rw = pfks_row_words(c), K = pfks_K(c), Kpad = pfks_Kpad(c);
+    if (!c->d_pfks_planes) {
+        c->last_pfks_kernel = "pfks_valu_kernel";
+        const size_t step = kMaxGridRows / dst.rows_per_item * dst.rows_per_item; // whole items per launch
+        for (size_t at = 0; at < M; at += step) {
+            const size_t nb = std::min(M - at, step);
+            PfksDest d = dst;
+            d.out += (at / dst.rows_per_item) * dst.item_stride;
+            PfksValuArgs a{d_in + at * rw, c->d_pfks + (size_t)key0 * K * W, d, (uint32_t)nb, (uint32_t)W, (uint32_t)rw, c->pfks_log, c->pfks_count};
+            hipLaunchKernelGGL(pfks_valu_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)((nb + PFKS_VT - 1) / PFKS_VT), nk), dim3(256), 0, s, a);
+        }
+        HIPCHK(c, hipGetLastError());
+        return SPF_OK;
+    }
+    const uint32_t U = pfks_limbs(c->pfks_log);
+    // rows per launch: what keeps the limbs of a launch within kPfksDigitCap, in whole row tiles of whole items (at least one: a
+    // key whose single tile of rows exceeds the cap has no planes and is served above)
+    const size_t unit = (size_t)PFKS_TILE * dst.rows_per_item;
+    size_t chunk = std::max<size_t>(1, kPfksDigitCap / (Kpad * U) / unit) * unit;
+    if (chunk > kMaxGridRows * PFKS_TILE) chunk = std::max<size_t>(1, kMaxGridRows * PFKS_TILE / unit) * unit; // (grid.y of the GEMM)
+    chunk = std::min(chunk, (M + PFKS_TILE - 1) / PFKS_TILE * PFKS_TILE); // (then one launch holds the whole call)
+    const uint32_t nseg = (uint32_t)((Kpad / 128 + kPfksSegRounds - 1) / kPfksSegRounds);
+    spf_status st = ensure(c, c->pfks_dig, chunk * Kpad * U);
+    if (st != SPF_OK) return st;
+    st = ensure(c, c->pfks_rowsum, (size_t)nseg * U * chunk * sizeof(int));
+    if (st != SPF_OK) return st;
+    c->last_pfks_kernel = U == 1 ? "pfks_gemm_kernel<1>" : U == 2 ? "pfks_gemm_kernel<2>" : "pfks_gemm_kernel<3>";
+    const size_t ncols = (size_t)nk * W;
+    for (size_t at = 0; at < M; at += chunk) {
+        const size_t nb = std::min(chunk, M - at), mpad = (nb + PFKS_TILE - 1) / PFKS_TILE * PFKS_TILE;
+        hipLaunchKernelGGL(pfks_digits_kernel, dim3((unsigned)mpad), dim3(256), 0, s, d_in + at * rw, (int8_t*)c->pfks_dig.p, (uint32_t)rw,
+                           (uint32_t)nb, (uint32_t)mpad, c->pfks_log, c->pfks_count, U, (uint32_t)K, (uint32_t)Kpad);
+        hipLaunchKernelGGL(pfks_rowsum_kernel, dim3((unsigned)mpad, nseg * U), dim3(256), 0, s, (const int8_t*)c->pfks_dig.p,
+                           (int*)c->pfks_rowsum.p, (uint32_t)mpad, U, (uint32_t)Kpad, kPfksSegRounds * 128u);
+        PfksDest d = dst;
+        d.out += (at / dst.rows_per_item) * dst.item_stride;
+        PfksGemmArgs a{(const int8_t*)c->pfks_dig.p, c->d_pfks_planes + 8 * (size_t)key0 * W * Kpad, (const int*)c->pfks_rowsum.p, d,
+                       (uint32_t)nb, (uint32_t)mpad, (uint32_t)Kpad, (uint32_t)W, (uint32_t)ncols};
+        const dim3 grid((unsigned)((8 * ncols + PFKS_TILE - 1) / PFKS_TILE), (unsigned)(mpad / PFKS_TILE));
+        if (U == 1) hipLaunchKernelGGL(pfks_gemm_kernel<1>, grid, dim3(256), 0, s, a);
+        else if (U == 2) hipLaunchKernelGGL(pfks_gemm_kernel<2>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(pfks_gemm_kernel<3>, grid, dim3(256), 0, s, a);
+    }
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+spf_status spf_private_functional_keyswitch_enqueue(spf_ctx* c, void* stream, size_t key_index, size_t B, const uint64_t* d_lwe_in,
+                                                    uint64_t* d_glwe_out)
+{
+    if (!c || !d_lwe_in || !d_glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
+    if (key_index >= c->pfks_keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
+    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    const size_t gw = glwe_words(c->prm);
+    if (ranges_overlap(d_glwe_out, B * gw * 8, d_lwe_in, B * pfks_row_words(c) * 8))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    HIPCHK(c, hipSetDevice(c->device));
+    return launch_pfks(c, (hipStream_t)stream, B, d_lwe_in, (uint32_t)key_index, 1, PfksDest{d_glwe_out, 1, gw, 0, 0});
+}
+
+spf_status spf_private_functional_keyswitch_batch(spf_ctx* c, size_t key_index, size_t B, const uint64_t* lwe_in, uint64_t* glwe_out)
+{
+    if (!c || !lwe_in || !glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t rw;
+    {
+        std::lock_guard<std::recursive_mutex> g(c->mu);
+        if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
+        if (key_index >= c->pfks_keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
+        rw = pfks_row_words(c);
+    }
+    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    const size_t out_bytes = B * glwe_words(c->prm) * 8;
+    return host_call(c, {{c->in, lwe_in, B * rw * 8}}, out_bytes, glwe_out, [&] {
+        return spf_private_functional_keyswitch_enqueue(c, c->stream, key_index, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
+}
+
+// what `apply_pfks_on_ggsw_components` needs of the loaded keys, or why not
+static spf_status pfks_components_shape(spf_ctx* c)
+{
+    if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
+    if (c->pfks_keys != c->prm.glwe_size + 1 || c->pfks_p != 1 || c->pfks_n != c->prm.glwe_size * c->prm.polynomial_degree)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the GGSW components need n_keys = k+1, lwe_count = 1 and from_dimension = k * N");
+    return SPF_OK;
+}
+
+static size_t ggsw_words(const spf_params& p) { return (size_t)(p.glwe_size + 1) * p.cbs_radix_count * glwe_words(p); }
+
+// `apply_pfks_on_ggsw_components` (circuit_bootstrapping.rs:485-514): GGSW row (r, level) = PFKS of LWE `level` under key r.  One
+// launch sequence: a row's digits are computed once and meet all k+1 keys.
+spf_status spf_apply_pfks_on_ggsw_components_enqueue(spf_ctx* c, void* stream, size_t B, const uint64_t* d_lwe_in, uint64_t* d_ggsw_out)
+{
+    if (!c || !d_lwe_in || !d_ggsw_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    spf_status st = pfks_components_shape(c);
+    if (st != SPF_OK) return st;
+    const uint32_t L = c->prm.cbs_radix_count;
+    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    const size_t gw = glwe_words(c->prm);
+    if (ranges_overlap(d_ggsw_out, B * ggsw_words(c->prm) * 8, d_lwe_in, B * L * pfks_row_words(c) * 8))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    HIPCHK(c, hipSetDevice(c->device));
+    return launch_pfks(c, (hipStream_t)stream, B * L, d_lwe_in, 0, c->pfks_keys, PfksDest{d_ggsw_out, L, ggsw_words(c->prm), gw, (size_t)L * gw});
+}
+
+spf_status spf_apply_pfks_on_ggsw_components_batch(spf_ctx* c, size_t B, const uint64_t* lwe_in, uint64_t* ggsw_out)
+{
+    if (!c || !lwe_in || !ggsw_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t rw;
+    {
+        std::lock_guard<std::recursive_mutex> g(c->mu);
+        spf_status st = pfks_components_shape(c);
+        if (st != SPF_OK) return st;
+        rw = pfks_row_words(c);
+    }
+    const uint32_t L = c->prm.cbs_radix_count;
+    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    const size_t out_bytes = B * ggsw_words(c->prm) * 8;
+    return host_call(c, {{c->in, lwe_in, B * L * rw * 8}}, out_bytes, ggsw_out, [&] {
+        return spf_apply_pfks_on_ggsw_components_enqueue(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
+}
+
+// `circuit_bootstrap_via_pfks` (circuit_bootstrapping.rs:162-219): hi_noise_lwe_to_lo_noise_glwe, extract_and_rotate_lo_noise_glwe,
+// apply_pfks_on_ggsw_components, then every polynomial of the integer GGSW through the library's forward transform, in place
+spf_status spf_circuit_bootstrap_via_pfks_enqueue(spf_ctx* c, void* stream, size_t B, const uint64_t* d_lwe0_in, double* d_ggsw_fft_out)
+{
+    if (!c || !d_lwe0_in || !d_ggsw_fft_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    spf_status st = pfks_components_shape(c);
+    if (st != SPF_OK) return st;
+    if (!c->bsk_ready) return fail(c, SPF_ERR_NO_KEY, "bootstrap key not loaded");
+    const uint32_t L = c->prm.cbs_radix_count, N = c->prm.polynomial_degree, k = c->prm.glwe_size;
+    if ((uint64_t)c->prm.cbs_radix_log * L + 1 > 64) return fail(c, SPF_ERR_INVALID_ARGUMENT, "cbs_radix_log * cbs_radix_count above 63");
+    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    if (ranges_overlap(d_ggsw_fft_out, B * ggsw_words(c->prm) * 8, d_lwe0_in, B * lwe0_words(c->prm) * 8))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t gw = glwe_words(c->prm), rw = (size_t)k * N + 1;
+    st = ensure(c, c->pfks_glwe, B * gw * 8);
+    if (st != SPF_OK) return st;
+    st = ensure(c, c->pfks_lwe, B * L * rw * 8);
+    if (st != SPF_OK) return st;
+    uint64_t* d_glwe = (uint64_t*)c->pfks_glwe.p;
+    uint64_t* d_rows = (uint64_t*)c->pfks_lwe.p;
+    st = launch_blind_rotate(c, s, B, d_lwe0_in, c->d_cbs_lut, 0, 0, ceil_log2(L), (uint64_t)1 << 62, d_glwe, gw, false);
+    if (st != SPF_OK) return st;
+    for (size_t at = 0; at < B * L; at += kMaxGridRows / L * L) {
+        const size_t nb = std::min(B * L - at, kMaxGridRows / L * L);
+        hipLaunchKernelGGL(pfks_extract_rotate_kernel, dim3((unsigned)((rw + 255) / 256), (unsigned)nb), dim3(256), 0, s,
+                           d_glwe + at / L * gw, d_rows + at * rw, N, k, L, c->prm.cbs_radix_log);
+    }
+    HIPCHK(c, hipGetLastError());
+    uint64_t* d_ggsw = reinterpret_cast<uint64_t*>(d_ggsw_fft_out);
+    st = launch_pfks(c, s, B * L, d_rows, 0, c->pfks_keys, PfksDest{d_ggsw, L, ggsw_words(c->prm), gw, (size_t)L * gw});
+    if (st != SPF_OK) return st;
+    return launch_poly_fft(c, s, B * (k + 1) * L * (k + 1), d_ggsw, reinterpret_cast<c64*>(d_ggsw));
+}
+
+spf_status spf_circuit_bootstrap_via_pfks_batch(spf_ctx* c, size_t B, const uint64_t* lwe0_in, double* ggsw_fft_out)
+{
+    if (!c || !lwe0_in || !ggsw_fft_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    {
+        std::lock_guard<std::recursive_mutex> g(c->mu);
+        spf_status st = pfks_components_shape(c);
+        if (st != SPF_OK) return st;
+    }
+    if (B > 0x0fffffffu / c->prm.cbs_radix_count) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B == 0) return SPF_OK;
+    const size_t out_bytes = B * ggsw_words(c->prm) * 8;
+    return host_call(c, {{c->in, lwe0_in, B * lwe0_words(c->prm) * 8}}, out_bytes, ggsw_fft_out, [&] {
+        return spf_circuit_bootstrap_via_pfks_enqueue(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p);
+    });
+}
+
+const char* spf_last_private_functional_keyswitch_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_pfks_kernel;
 }
 
 const char* spf_last_blind_rotate_kernel(spf_ctx* c)
