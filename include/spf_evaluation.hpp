@@ -342,6 +342,22 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_blind_rotation(g_, glwe, shift_ggsw.data(), shift_ggsw.size(), log_stride, &n), ctx_);
         return n;
     }
+    // `programmable_bootstrap_univariate` / `programmable_bootstrap_bivariate` (sunscreen_tfhe ops/bootstrapping/
+    // programmable_bootstrapping.rs:291, 575-621) as nodes — no FheOp in the reference: the L1 LWE of f(lwe0) resp. f(left, right),
+    // the table `lut_glwe` any GLWE node (an input, a trivial encryption, something the graph computed).  Graphs and group jobs alike
+    Node pbs_univariate(Node lwe0, Node lut_glwe) { return op(SPF_OP_PBS_UNIVARIATE, {lwe0, lut_glwe}); }
+    Node pbs_bivariate(Node left_lwe0, Node right_lwe0, Node lut_glwe, uint32_t plaintext_bits)
+    {
+        return op(SPF_OP_PBS_BIVARIATE, {left_lwe0, right_lwe0, lut_glwe}, plaintext_bits);
+    }
+    // `public_functional_keyswitch` (ops/keyswitch/public_functional_keyswitch.rs:74-148), message j to coefficient j: the L0 (or
+    // L1) LWE nodes `lwes`, from anywhere in the graph, as ONE GLWE node — an operand of unpack / cmux / blind_rotation or an output
+    Node public_functional_keyswitch(const std::vector<Node>& lwes)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_public_functional_keyswitch(g_, lwes.data(), lwes.size(), &n), ctx_);
+        return n;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }
@@ -490,6 +506,18 @@ class PooledEvaluation {
         uint64_t t = 0;
         check(spf_pool_submit_keyswitch_circuit_bootstrap_v(pool_, input.raw(), &out, pushed_ ? nullptr : &t));
         finish(output, out, t);
+    }
+
+    // programmable_bootstrap_univariate / _bivariate (programmable_bootstrapping.rs:291, 575-621) by handle: the table is an L1 GLWE
+    // like any other (valid or, in pushed mode, still pending); batched and paced like circuit_bootstrap
+    void pbs_univariate(L1LweCiphertext& output, const L0LweCiphertext& input, const L1GlweCiphertext& lut) const
+    {
+        run(SPF_OP_PBS_UNIVARIATE, output, {input.raw(), lut.raw()});
+    }
+    void pbs_bivariate(L1LweCiphertext& output, const L0LweCiphertext& left, const L0LweCiphertext& right, const L1GlweCiphertext& lut,
+                       uint32_t plaintext_bits) const
+    {
+        run(SPF_OP_PBS_BIVARIATE, output, {left.raw(), right.raw(), lut.raw()}, plaintext_bits);
     }
 
     // blind_rotation (blind_rotation.rs:202-223) by handle: output = input * X^-(s << log_stride), the shift as the span

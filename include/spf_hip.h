@@ -437,7 +437,9 @@ typedef enum spf_graph_op {
     SPF_OP_MULTIPLY_GGSW_GLWE = 6,
     SPF_OP_CIRCUIT_BOOTSTRAP = 7,
     SPF_OP_SCHEME_SWITCH = 8,
-    SPF_OP_MUL_XN = 9
+    SPF_OP_MUL_XN = 9,
+    SPF_OP_PBS_UNIVARIATE = 10, /* no FheOp: `programmable_bootstrap_univariate` with the table as an operand (below) */
+    SPF_OP_PBS_BIVARIATE = 11   /* no FheOp: `programmable_bootstrap_bivariate`, param = plaintext_bits */
 } spf_graph_op;
 
 /* ---- call coalescing: many threads, one ciphertext each -> one batch per launch ----------
@@ -617,7 +619,10 @@ spf_status spf_pool_submit_scheme_switch_v(spf_pool *pool, const spf_value *glev
 spf_status spf_pool_submit_blind_rotation_v(spf_pool *pool, const spf_value *glwe, const spf_value *const *shift_ggsw /* n_bits */,
                                             size_t n_bits, size_t log_stride, spf_value **out, uint64_t *ticket);
 /* `exec_op`'s whole match in one entry (circuit_processor/mod.rs:255-540): the operation as a spf_graph_op, operands in the order
- * spf_graph_add_op takes them (CMUX: selector, low, high), `param` = SampleExtract index / MulXN amount */
+ * spf_graph_add_op takes them (CMUX: selector, low, high), `param` = SampleExtract index / MulXN amount.  SPF_OP_PBS_UNIVARIATE
+ * [lwe0, lut glwe1] and SPF_OP_PBS_BIVARIATE [left lwe0, right lwe0, lut glwe1] (`param` = plaintext_bits < 64) go the same
+ * way: `programmable_bootstrap_univariate` / `_bivariate` (programmable_bootstrapping.rs:291, 575-621) by handle, batched and paced
+ * like the circuit bootstraps, word-equal to spf_pbs_univariate_batch / spf_pbs_bivariate_batch of the same rows */
 spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value *const *inputs, size_t n_inputs, uint64_t param,
                                 spf_value **out, uint64_t *ticket);
 
@@ -635,6 +640,12 @@ spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value
  *   CMUX [sel ggsw1, low glwe1 (taken when sel = 0), high glwe1] -> glwe1   (FheEdge::Sel/Low/High)
  *   GLEV_CMUX [sel ggsw1, low glev1, high glev1] -> glev1
  *   MULTIPLY_GGSW_GLWE [ggsw1, glwe1] -> glwe1
+ *   PBS_UNIVARIATE [lwe0, lut glwe1] -> lwe1           PBS_BIVARIATE(param = plaintext_bits < 64) [left lwe0, right lwe0, lut glwe1] -> lwe1
+ * The two bootstraps by a caller's table stand for `programmable_bootstrap_univariate` / `programmable_bootstrap_bivariate`
+ * (ops/bootstrapping/programmable_bootstrapping.rs:291, 575-621), which the reference's `FheOp` does not have: a node is word-equal to
+ * spf_pbs_univariate_batch / spf_pbs_bivariate_batch of the same rows with lut_stride = one GLWE, whatever batch it lands in.
+ * The table is a glwe1 node like any other (an input, a trivial encryption, something the graph computed); the nodes of a level
+ * that name ONE table node read it in place.  PBS_BIVARIATE with plaintext_bits >= 64 is SPF_ERR_INVALID_ARGUMENT.
  * Wrong arity or operand type is reported by spf_graph_add_op, before anything runs (the
  * reference validates per task, task.rs:26-31).  Input and output host buffers are read /
  * written by every spf_graph_run and must stay valid until it returns; a graph can be run
@@ -678,6 +689,17 @@ spf_status spf_graph_add_pack(spf_graph *graph, const uint32_t *nodes, size_t n_
  * whose cbs radix is not 4 x 4 bits: SPF_ERR_UNSUPPORTED), nothing is recorded and the graph stays usable. */
 spf_status spf_graph_add_blind_rotation(spf_graph *graph, uint32_t glwe_node, const uint32_t *shift_nodes /* n_bits ggsw1 nodes, bit 0 first */,
                                         size_t n_bits, size_t log_stride, uint32_t *node_out);
+/* `public_functional_keyswitch` (ops/keyswitch/public_functional_keyswitch.rs:74-148) with the map "message j to coefficient j"
+ * as a node constructor — no FheOp there, no spf_graph_op here: lwe_nodes[0 .. lwe_count) are all lwe0 or all lwe1 nodes of any
+ * origin and level (sample extracts, bootstrap results, keyswitch results, inputs; repeats allowed), 0 < lwe_count <=
+ * polynomial_degree; creates ONE glwe1 node, one level above its highest operand, word-equal to
+ * spf_public_functional_keyswitch_batch of those rows in that order.  All such nodes of one level with one (lwe_count, operand
+ * kind) are one main launch that reads the rows where they lie.  The new node is an ordinary glwe1 node.  A wrong argument
+ * (lwe_count out of range, lwe0 and lwe1 mixed, a node that does not exist or is no LWE, a null pointer) is
+ * SPF_ERR_INVALID_ARGUMENT from the call, nothing is recorded and the graph stays usable.  spf_graph_run reports SPF_ERR_NO_KEY
+ * while no public functional keyswitch key is loaded, and SPF_ERR_INVALID_ARGUMENT when the key's from_dimension is not the
+ * dimension of the operands (lwe_dimension for lwe0, glwe_size * polynomial_degree for lwe1). */
+spf_status spf_graph_add_public_functional_keyswitch(spf_graph *graph, const uint32_t *lwe_nodes, size_t lwe_count, uint32_t *node_out);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */
@@ -700,10 +722,11 @@ spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t w
  * context since timing was enabled (or since the last query, which clears the record), measured
  * with hipEvents recorded on the launch stream around each launch: "pbs" (blind rotation),
  * "keyswitch" (digits + GEMM), "trace" (cbs_trace_kernel), "scheme_switch", "cmux" (contiguous
- * batched CMUX family).  A host-pointer bootstrap of more than one chip round is launched in slices
+ * batched CMUX family), "pufks_prepass" (the transposing pre-pass of a public functional keyswitch at the hand-written radices,
+ * with the gather in front of it where there is one).  A host-pointer bootstrap of more than one chip round is launched in slices
  * of 1024 ciphertexts: it records one "pbs" entry per slice.  Enable with spf_set_timing(ctx, 1). */
 spf_status spf_set_timing(spf_ctx *ctx, int enabled);
-spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" */,
+spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" */,
                               double *avg_ms, int *launches);
 /* `generate_lut` (sunscreen_tfhe ops/bootstrapping/programmable_bootstrapping.rs:129-185) for
  * `programmable_bootstrap_univariate`: map_tables[f * 2^bits + x] = f(x) for n_maps functions over a

@@ -24,6 +24,19 @@
 // read of the low one — composed from MulXN(2N - r) + CMux nodes the same words cost two levels and two launches per bit.  All such
 // nodes of one level and one rotation are ONE launch over a pointer table (launch_cmux_rot_scattered), each writing its own row.
 //
+// The bootstraps by a caller's table (SPF_OP_PBS_UNIVARIATE / SPF_OP_PBS_BIVARIATE: `programmable_bootstrap_univariate` / `_bivariate`,
+// programmable_bootstrapping.rs:291, 575-621) are rows of the operation table whose LAST operand is the table, a GLWE1 node.  A group
+// whose members all name one table node launches with lut_stride = 0 and copies nothing; otherwise the tables are gathered like any
+// operand.  Bivariate inputs that do not lie consecutively are packed straight from where they lie (lwe_pack_rows_kernel: one launch
+// where two gathers and lwe_pack_kernel were three).  The slack rule below batches each of the two kinds as it batches the circuit
+// bootstraps.
+//
+// A public functional keyswitch (`public_functional_keyswitch`, public_functional_keyswitch.rs:74-148, message j to coefficient j)
+// is a fourth constructor: spf_graph_add_public_functional_keyswitch packs lwe_count LWE nodes of one kind, from anywhere, into ONE
+// GLWE1 node — what brings the LWEs out of a bootstrap or a sample extract back into a packed integer or into CMUX-land.  All
+// such nodes of one level with one (lwe_count, kind) are one main launch (launch_pufks_rows; rows that lie consecutively take the
+// contiguous entry point).
+//
 // Included at the end of spf_hip.hip: uses its `fail` / HIPCHK helpers and the `_dev` entry points.
 #pragma once
 
@@ -60,23 +73,25 @@ struct spf_pinned_buf {
 };
 
 struct spf_graph {
-    // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation)
-    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66 };
+    // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation /
+    // spf_graph_add_public_functional_keyswitch)
+    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67 };
+    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks; } // operands in pack_in, not in Node::in
     struct Node {
         int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack / kNodeRotCmux, or -1 input, -2 trivial constant
         int32_t kind;      // spf_value_kind of the value the node produces
         uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node
         uint32_t in[3];    // (rotate-CMUX nodes: {selector, accumulator})
         uint32_t n_in;
-        uint32_t n_bits;   // unpack and pack nodes: width of the integer
-        uint32_t ext;      // pack nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
+        uint32_t n_bits;   // unpack and pack nodes: width of the integer; public functional keyswitch nodes: lwe_count
+        uint32_t ext;      // pack and public functional keyswitch nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
         uint32_t level;
         size_t off;        // byte offset of the value in the arena
         const void* host;  // inputs: caller's buffer, read at every run
     };
     struct Group {
         int32_t op;
-        uint64_t param;    // (unpack and pack groups: n_bits)
+        uint64_t param;    // (unpack and pack groups: n_bits; public functional keyswitch groups: lwe_count | operand kind << 32)
         std::vector<uint32_t> members;
         size_t out_off = 0;
         // per operand slot: offset of the first operand when the members' operands are contiguous
@@ -84,18 +99,19 @@ struct spf_graph {
         bool contiguous[3] = {false, false, false};
         size_t first_off[3] = {0, 0, 0};
         size_t ptr_index[3] = {0, 0, 0};
+        bool one_lut = false; // the bootstraps by table: every member names the same table node (read in place, lut_stride = 0)
     };
     spf_ctx* ctx = nullptr;
     spf_params prm{};
     struct spf_group* grp = nullptr; // a graph of a device group (spf_group_graph_create): placed on a member when it is run
     int member = -1;                 // ... the member its most recent run took place on
     std::vector<Node> nodes;
-    std::vector<uint32_t> pack_in; // operand lists of the pack nodes
+    std::vector<uint32_t> pack_in; // operand lists of the pack and the public functional keyswitch nodes
     // f(operand id) for every operand of a node
     template <class F> void for_operands(const Node& n, F f) const
     {
         for (uint32_t i = 0; i < n.n_in; i++) f(n.in[i]);
-        if (n.op == kNodePack)
+        if (has_list(n.op))
             for (uint32_t i = 0; i < n.n_bits; i++) f(pack_in[n.ext + i]);
     }
     std::vector<std::pair<uint32_t, void*>> outputs;
@@ -121,6 +137,7 @@ struct spf_graph {
         outputs_planned = (size_t)-1;
     }
     size_t inputs_bytes = 0, arena_bytes = 0, stage_bytes = 0;
+    bool has_pufks = false, pufks_stage = false; // public functional keyswitch nodes: any; planned with room to gather their rows
     char* d_arena = nullptr;
     char* d_stage[2] = {nullptr, nullptr};
     void** d_ptrs = nullptr;
@@ -200,17 +217,20 @@ inline spf_status plan(spf_graph* g)
                 if (g->nodes[in].op >= 0) alap[in] = std::min(alap[in], alap[id] - 1);
             });
         }
-        std::vector<uint32_t> cbs;
-        for (uint32_t id = 0; id < nn; id++)
-            if (g->nodes[id].op == SPF_OP_CIRCUIT_BOOTSTRAP) cbs.push_back(id);
-        std::sort(cbs.begin(), cbs.end(), [&](uint32_t a, uint32_t b) { return alap[a] != alap[b] ? alap[a] < alap[b] : a < b; });
+        // (the bootstraps by table cost the same blind rotation: each of the three kinds is batched among its own)
         std::vector<uint32_t> fixed(nn, 0);
         std::vector<bool> done(nn, false);
-        for (uint32_t lead : cbs) {
-            if (done[lead]) continue;
-            const uint32_t t = alap[lead];
-            for (uint32_t id : cbs)
-                if (!done[id] && g->nodes[id].level <= t) { done[id] = true; fixed[id] = t; }
+        for (const int32_t kind : {(int32_t)SPF_OP_CIRCUIT_BOOTSTRAP, (int32_t)SPF_OP_PBS_UNIVARIATE, (int32_t)SPF_OP_PBS_BIVARIATE}) {
+            std::vector<uint32_t> cbs;
+            for (uint32_t id = 0; id < nn; id++)
+                if (g->nodes[id].op == kind) cbs.push_back(id);
+            std::sort(cbs.begin(), cbs.end(), [&](uint32_t a, uint32_t b) { return alap[a] != alap[b] ? alap[a] < alap[b] : a < b; });
+            for (uint32_t lead : cbs) {
+                if (done[lead]) continue;
+                const uint32_t t = alap[lead];
+                for (uint32_t id : cbs)
+                    if (!done[id] && g->nodes[id].level <= t) { done[id] = true; fixed[id] = t; }
+            }
         }
         // forward again with the chosen bootstrap levels as lower bounds (t <= latest level: depth unchanged)
         for (size_t id = 0; id < nn; id++) {
@@ -238,7 +258,8 @@ inline spf_status plan(spf_graph* g)
     for (uint32_t id = 0; id < g->nodes.size(); id++) {
         const auto& n = g->nodes[id];
         if (n.op < 0) continue;
-        const uint64_t key_param = n.op == spf_graph::kNodeUnpack || n.op == spf_graph::kNodePack ? n.n_bits : n.param;
+        const uint64_t key_param = n.op == spf_graph::kNodeUnpack || n.op == spf_graph::kNodePack ? n.n_bits
+                                   : n.op == spf_graph::kNodePufks ? n.n_bits | (uint64_t)g->nodes[g->pack_in[n.ext]].kind << 32 : n.param;
         auto key = std::make_tuple(n.level, n.op, key_param);
         auto it = index.find(key);
         if (it == index.end()) {
@@ -268,8 +289,29 @@ inline spf_status plan(spf_graph* g)
     HIPCHK(c, hipMalloc((void**)&g->d_arena, std::max<size_t>(g->arena_bytes, 256)));
     // operand access per group
     std::vector<void*> table;
+    g->has_pufks = false;
+    g->pufks_stage = !pufks_tuned(c) || pufks_rows_gather(); // (also while no key is loaded: the key that comes may be of any radix)
     for (auto& gr : g->groups) {
         const size_t B = gr.members.size();
+        if (gr.op == spf_graph::kNodePufks) {
+            // the rows of every output, output-major: in place when they lie consecutively; else read through the table by the
+            // pre-pass of the hand-written radices, or gathered for generic_pufks_kernel
+            g->has_pufks = true;
+            const size_t rb = value_bytes(g->prm, (int)(gr.param >> 32));
+            std::vector<size_t> offs;
+            for (uint32_t id : gr.members)
+                g->for_operands(g->nodes[id], [&](uint32_t in) { offs.push_back(g->nodes[in].off); });
+            bool contig = true;
+            for (size_t i = 1; i < offs.size() && contig; i++) contig = offs[i] == offs[0] + i * rb;
+            gr.contiguous[0] = contig;
+            gr.first_off[0] = offs[0];
+            if (!contig) {
+                gr.ptr_index[0] = table.size();
+                for (size_t o : offs) table.push_back(g->d_arena + o);
+                if (g->pufks_stage) stage = std::max(stage, offs.size() * rb);
+            }
+            continue;
+        }
         if (gr.op == spf_graph::kNodePack) {
             // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table
             gr.ptr_index[0] = table.size();
@@ -341,6 +383,7 @@ inline spf_status plan(spf_graph* g)
             for (const Unit& u : units) for (void* q : u.p) table.push_back(q);
             continue;
         }
+        const bool by_table = gr.op == SPF_OP_PBS_UNIVARIATE || gr.op == SPF_OP_PBS_BIVARIATE;
         for (int s = 0; s < info.arity; s++) {
             const size_t ib = value_bytes(g->prm, info.in_kind[s]);
             bool contig = true;
@@ -349,7 +392,19 @@ inline spf_status plan(spf_graph* g)
                 contig = g->nodes[g->nodes[gr.members[i]].in[s]].off == first + i * ib;
             gr.contiguous[s] = contig;
             gr.first_off[s] = first;
-            if (!contig) {
+        }
+        if (by_table) { // one table node for the whole group: read in place with lut_stride = 0 (B = 1 included)
+            const int s = info.arity - 1;
+            gr.one_lut = true;
+            for (size_t i = 1; i < B && gr.one_lut; i++) gr.one_lut = g->nodes[gr.members[i]].in[s] == g->nodes[gr.members[0]].in[s];
+            if (gr.one_lut) gr.contiguous[s] = true;
+        }
+        // bivariate inputs: one of them scattered -> both are read through their pointer rows by lwe_pack_rows_kernel, which
+        // writes the packed rows into the stage buffer
+        if (gr.op == SPF_OP_PBS_BIVARIATE && !(gr.contiguous[0] && gr.contiguous[1])) gr.contiguous[0] = gr.contiguous[1] = false;
+        for (int s = 0; s < info.arity; s++) {
+            const size_t ib = value_bytes(g->prm, info.in_kind[s]);
+            if (!gr.contiguous[s]) {
                 gr.ptr_index[s] = table.size();
                 for (size_t i = 0; i < B; i++) table.push_back(g->d_arena + g->nodes[g->nodes[gr.members[i]].in[s]].off);
                 stage = std::max(stage, B * ib);
@@ -388,9 +443,33 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                                      hipMemcpyDeviceToDevice, s));
         }
     g->n_launches = 0;
+    // the public functional keyswitch key comes with its own shape: checked against the nodes before anything is enqueued
+    for (const auto& gr : g->groups)
+        if (gr.op == spf_graph::kNodePufks) {
+            if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "graph: public functional keyswitch key not loaded");
+            const int kind = (int)(gr.param >> 32);
+            const size_t dim = value_bytes(g->prm, kind) / 8 - 1;
+            if (c->pufks_n != dim)
+                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: the public functional keyswitch key's from_dimension " + std::to_string(c->pufks_n) +
+                                                             " is not the dimension " + std::to_string(dim) + " of its " +
+                                                             (kind == SPF_VAL_LWE0 ? "lwe0" : "lwe1") + " operands");
+        }
     for (const auto& gr : g->groups) {
         const size_t B = gr.members.size();
         char* out = g->d_arena + gr.out_off;
+        if (gr.op == spf_graph::kNodePufks) {
+            const size_t p = (size_t)(gr.param & 0xffffffffu);
+            spf_status st;
+            if (gr.contiguous[0]) {
+                st = spf_public_functional_keyswitch_enqueue(c, s, B, p, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
+                g->n_launches += pufks_tuned(c) ? 2 : 1;
+            } else {
+                st = launch_pufks_rows(c, s, B, p, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]),
+                                       g->pufks_stage ? (uint64_t*)g->d_stage[0] : nullptr, (uint64_t*)out, &g->n_launches);
+            }
+            if (st != SPF_OK) return st;
+            continue;
+        }
         if (gr.op == spf_graph::kNodePack) {
             spf_status st = launch_glwe_pack_rows(c, s, B, gr.param, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
             if (st != SPF_OK) return st;
@@ -427,21 +506,44 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
             continue;
         }
         const void* in[3] = {nullptr, nullptr, nullptr};
+        // (stage buffers: the table of a bootstrap by table goes to the second one, its LWE rows — gathered, or packed from where
+        // they lie — to the first)
+        const bool pack_rows = gr.op == SPF_OP_PBS_BIVARIATE && !gr.contiguous[0];
+        if (pack_rows) {
+            spf_status st = launch_lwe_pack_rows(c, s, B, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]),
+                                                 (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[1]), (uint32_t)gr.param, (uint64_t*)g->d_stage[0]);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            const void* lut = g->d_arena + gr.first_off[2];
+            if (!gr.contiguous[2]) {
+                st = spf_gather_rows_dev(c, s, B, value_bytes(g->prm, SPF_VAL_GLWE1) / 8, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[2]),
+                                         (uint64_t*)g->d_stage[1]);
+                if (st != SPF_OK) return st;
+                g->n_launches++;
+                lut = g->d_stage[1];
+            }
+            st = spf_pbs_univariate_dev(c, s, B, (const uint64_t*)g->d_stage[0], (const uint64_t*)lut, gr.one_lut ? 0 : value_bytes(g->prm, SPF_VAL_GLWE1) / 8,
+                                        (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
         for (int sl = 0; sl < info.arity; sl++) {
+            char* stage_sl = g->d_stage[sl == info.arity - 1 && sl > 0 ? 1 : sl];
             if (gr.contiguous[sl]) {
                 in[sl] = g->d_arena + gr.first_off[sl];
             } else {
                 spf_status st = spf_gather_rows_dev(c, s, B, value_bytes(g->prm, info.in_kind[sl]) / 8,
                                                     (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[sl]),
-                                                    (uint64_t*)g->d_stage[sl]);
+                                                    (uint64_t*)stage_sl);
                 if (st != SPF_OK) return st;
                 g->n_launches++;
-                in[sl] = g->d_stage[sl];
+                in[sl] = stage_sl;
             }
         }
-        const spf_status st = spf_ops::launch_op(c, s, info.op, B, in, out, gr.param, nullptr, 0, nullptr);
+        const spf_status st = spf_ops::launch_op(c, s, info.op, B, in, out, gr.param, nullptr, 0, nullptr, gr.one_lut);
         if (st != SPF_OK) return st;
-        g->n_launches++;
+        g->n_launches += gr.op == SPF_OP_PBS_BIVARIATE ? 2 : 1; // (contiguous bivariate inputs: lwe_pack_kernel, then the bootstrap)
     }
     return SPF_OK;
 }
@@ -486,6 +588,8 @@ inline spf_status run(spf_graph* g)
     // one graph at a time per context: the _dev calls below share the context's scratch buffers and
     // stream, and a run must not interleave its launches with another run's
     std::lock_guard<std::recursive_mutex> whole(c->mu);
+    // (planned under a key of a hand-written radix, run under one that goes to generic_pufks_kernel: that one gathers its rows)
+    if (g->planned && g->has_pufks && !g->pufks_stage && (!pufks_tuned(c) || pufks_rows_gather())) g->planned = false;
     if (!g->planned) {
         spf_status st = plan(g);
         if (st != SPF_OK) return st;
@@ -691,6 +795,37 @@ spf_status spf_graph_add_pack(spf_graph* g, const uint32_t* nodes, size_t n_bits
     n.op = spf_graph::kNodePack; n.kind = SPF_VAL_GLWE1; n.n_bits = (uint32_t)n_bits; n.ext = (uint32_t)g->pack_in.size();
     try {
         g->pack_in.insert(g->pack_in.end(), nodes, nodes + n_bits);
+        g->nodes.push_back(n);
+    } catch (const std::exception&) {
+        g->pack_in.resize(n.ext);
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    *node_out = (uint32_t)g->nodes.size() - 1;
+    g->planned = false;
+    return SPF_OK;
+}
+
+// `public_functional_keyswitch` (public_functional_keyswitch.rs:74-148) as a node constructor: one GLWE1 node whose coefficient j
+// carries the message of lwe_nodes[j]; the operands in the side list, as a pack node's
+spf_status spf_graph_add_public_functional_keyswitch(spf_graph* g, const uint32_t* lwe_nodes, size_t lwe_count, uint32_t* node_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!lwe_nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: null pointer");
+    if (lwe_count == 0 || lwe_count > g->prm.polynomial_degree)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: lwe_count must be in 1 ..= polynomial_degree");
+    for (size_t i = 0; i < lwe_count; i++) {
+        if (lwe_nodes[i] >= g->nodes.size())
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: operand is not a node of this graph");
+        const int kind = g->nodes[lwe_nodes[i]].kind;
+        if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1)
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: operand is not an LWE");
+        if (kind != g->nodes[lwe_nodes[0]].kind)
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: lwe0 and lwe1 operands mixed");
+    }
+    spf_graph::Node n{};
+    n.op = spf_graph::kNodePufks; n.kind = SPF_VAL_GLWE1; n.n_bits = (uint32_t)lwe_count; n.ext = (uint32_t)g->pack_in.size();
+    try {
+        g->pack_in.insert(g->pack_in.end(), lwe_nodes, lwe_nodes + lwe_count);
         g->nodes.push_back(n);
     } catch (const std::exception&) {
         g->pack_in.resize(n.ext);

@@ -915,7 +915,7 @@ double graph_cost(const spf_graph* g)
 {
     double c = 0;
     for (const auto& n : g->nodes)
-        c += n.op == SPF_OP_CIRCUIT_BOOTSTRAP ? 50.0 : (n.op >= 0 ? 1.0 : 0.0);
+        c += n.op == SPF_OP_CIRCUIT_BOOTSTRAP ? 50.0 : (n.op == SPF_OP_PBS_UNIVARIATE || n.op == SPF_OP_PBS_BIVARIATE ? 40.0 : (n.op >= 0 ? 1.0 : 0.0));
     return c;
 }
 
@@ -930,7 +930,7 @@ spf_status merge_jobs(spf_ctx* c, const std::vector<spf_graph*>& jobs, spf_graph
             const uint32_t base = (uint32_t)m->nodes.size(), ext_base = (uint32_t)m->pack_in.size();
             for (spf_graph::Node n : j->nodes) {
                 for (uint32_t i = 0; i < n.n_in; i++) n.in[i] += base;
-                if (n.op == spf_graph::kNodePack) n.ext += ext_base; // (their operand lists move with them)
+                if (spf_graph::has_list(n.op)) n.ext += ext_base; // (the operand lists of pack and public functional keyswitch nodes move with them)
                 m->nodes.push_back(n);
             }
             for (uint32_t in : j->pack_in) m->pack_in.push_back(in + base);

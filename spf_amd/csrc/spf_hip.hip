@@ -62,8 +62,8 @@ struct Scratch {
 };
 
 // kernels whose launches spf_set_timing brackets with hipEvents on the launch stream (spf_last_kernel_ms)
-enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_COUNT };
-const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux"};
+enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_COUNT };
+const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass"};
 
 } // namespace
 
@@ -1067,6 +1067,20 @@ static spf_status launch_lwe_pack(spf_ctx* c, hipStream_t s, size_t B, const uin
     const size_t words = B * lwe0_words(c->prm);
     const unsigned blocks = (unsigned)std::min<size_t>((words + 255) / 256, 4 * (size_t)c->n_cu);
     hipLaunchKernelGGL(lwe_pack_kernel, dim3(blocks), dim3(256), 0, s, d_left, d_right, d_out, words, (uint64_t)1 << plaintext_bits);
+    HIPCHK(c, hipGetLastError());
+    return SPF_OK;
+}
+
+// the same with row b of either operand at d_left[b] / d_right[b] (device tables of device pointers; lwe_pack_rows_kernel).  At most
+// one workgroup per CU: a level of a graph is a few hundred rows of a few KiB
+static spf_status launch_lwe_pack_rows(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* const* d_left, const uint64_t* const* d_right,
+                                       uint32_t plaintext_bits, uint64_t* d_out)
+{
+    const size_t words = lwe0_words(c->prm), items = B * ((words + 255) / 256);
+    if (items == 0) return SPF_OK;
+    const unsigned blocks = (unsigned)std::min<size_t>(items, (size_t)c->n_cu);
+    hipLaunchKernelGGL(lwe_pack_rows_kernel, dim3(blocks), dim3(256), 0, s, d_left, d_right, d_out, B, (uint32_t)words,
+                       (uint64_t)1 << plaintext_bits);
     HIPCHK(c, hipGetLastError());
     return SPF_OK;
 }
@@ -2137,7 +2151,7 @@ spf_status spf_last_kernel_ms(spf_ctx* c, const char* kernel, double* avg_ms, in
     std::vector<TimedLaunch>* v = nullptr;
     for (int k = 0; k < T_COUNT; k++)
         if (!strcmp(kernel, kTimedNames[k])) v = &c->timed[k];
-    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\" or \"cmux\"");
+    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\" or \"pufks_prepass\"");
     double total = 0.0;
     int n = 0;
     for (auto& t : *v) {
@@ -2426,9 +2440,17 @@ static spf_status pufks_args(spf_ctx* c, size_t B, size_t lwe_count, const void*
     return SPF_OK;
 }
 
+// d_rows == null: the B * p rows are contiguous at d_in.  Otherwise row b * p + j is d_rows[b * p + j] (a device table of device
+// pointers, d_in unused): the pre-pass reads the rows where they lie and leaves their bodies behind the digits of the launch —
+// or, given d_gather, a buffer of B * p rows (the diagnostic SPF_PUFKS_ROWS_GATHER=1: the form the scattered pre-pass was
+// measured against, tools/pbs_graph_bench.py), the rows are gathered there and the contiguous pre-pass runs on the copy.  The
+// pre-pass of a launch, with its gather, is one "pufks_prepass" entry of spf_last_kernel_ms.
 extern "C++" template <int LOGB, int L>
-static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32_t p, const uint64_t* d_in, uint64_t* d_out)
+static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32_t p, const uint64_t* d_in, uint64_t* d_out,
+                                     const uint64_t* const* d_rows = nullptr, uint64_t* d_gather = nullptr)
 {
+    const uint64_t* const* d_gather_from = nullptr;
+    if (d_rows && d_gather) { d_gather_from = d_rows; d_rows = nullptr; d_in = d_gather; }
     const uint32_t n = c->pufks_n, pstride = (p + 31u) & ~31u;
     const size_t per_output = (size_t)n * pstride * sizeof(uint32_t), row_words = (size_t)n + 1, gw = glwe_words(c->prm);
     // outputs per launch: what keeps the digits of a launch within 8 GiB of scratch (half the bytes of the inputs they come from;
@@ -2436,8 +2458,9 @@ static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32
     // CUs idle, 311 ms per 1024 outputs), a multiple of the outputs per workgroup
     size_t chunk = std::max<size_t>(4, std::min<size_t>(4096, (((size_t)8 << 30) / per_output) & ~(size_t)3));
     chunk = std::min(chunk, (B + 3) & ~(size_t)3);
-    spf_status st = ensure(c, c->pufks_dig, chunk * per_output);
+    spf_status st = ensure(c, c->pufks_dig, chunk * per_output + (d_rows ? chunk * pstride * sizeof(uint64_t) : 0));
     if (st != SPF_OK) return st;
+    uint64_t* d_bodies = (uint64_t*)((char*)c->pufks_dig.p + chunk * per_output); // (per_output is a multiple of 128 bytes)
     // at most one output per CU: the four-waves-per-output latency shape.  Beyond, two outputs per workgroup while the call fills at
     // most two workgroups per CU (more CUs at work on a small batch), then four: each key row then serves four outputs from one
     // trip to memory.  One shape per call, whatever its launches hold.
@@ -2445,9 +2468,25 @@ static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32
     for (size_t at = 0; at < B; at += chunk) {
         const size_t nb = std::min(chunk, B - at);
         const uint64_t* in = d_in + at * p * row_words;
-        hipLaunchKernelGGL((pufks_digits_kernel<L, LOGB>), dim3((n + 31) / 32, pstride / 32, (unsigned)nb), dim3(256), 0, s, in,
-                           (uint32_t*)c->pufks_dig.p, n, p, pstride);
-        PufksArgs a{c->d_pufks, (const uint32_t*)c->pufks_dig.p, in, d_out + at * gw, c->d_tables, (uint32_t)nb, n, p, pstride};
+        {
+            TimedScope ts(c, s, T_PUFKS_PRE);
+            st = ts.begin();
+            if (st != SPF_OK) return st;
+            if (d_gather_from) {
+                st = spf_gather_rows_dev(c, s, nb * p, row_words, d_gather_from + at * p, d_gather + at * p * row_words);
+                if (st != SPF_OK) return st;
+            }
+            if (d_rows)
+                hipLaunchKernelGGL((pufks_digits_rows_kernel<L, LOGB>), dim3((n + 31) / 32, pstride / 32, (unsigned)nb), dim3(256), 0, s,
+                                   d_rows + at * p, (uint32_t*)c->pufks_dig.p, d_bodies, n, p, pstride);
+            else
+                hipLaunchKernelGGL((pufks_digits_kernel<L, LOGB>), dim3((n + 31) / 32, pstride / 32, (unsigned)nb), dim3(256), 0, s, in,
+                                   (uint32_t*)c->pufks_dig.p, n, p, pstride);
+            st = ts.end();
+            if (st != SPF_OK) return st;
+        }
+        PufksArgs a{c->d_pufks, (const uint32_t*)c->pufks_dig.p, d_rows ? d_bodies : in + n, d_rows ? (size_t)pstride : p * row_words,
+                    d_rows ? (size_t)1 : row_words, d_out + at * gw, c->d_tables, (uint32_t)nb, n, p, pstride};
         if (latency) {
             c->last_pufks_kernel = L == 8 ? "pufks4_kernel<4,8>" : "pufks4_kernel<4,4>";
             hipLaunchKernelGGL((pufks4_kernel<LOGB, L>), dim3((unsigned)nb), dim3(256), kPufks4Lds, s, a);
@@ -2493,6 +2532,41 @@ spf_status spf_public_functional_keyswitch_enqueue(spf_ctx* c, void* stream, siz
     }
     HIPCHK(c, hipGetLastError());
     return SPF_OK;
+}
+
+// diagnostic, read at every call: the hand-written radices gather scattered rows and run the contiguous pre-pass (a graph planned
+// without it is planned again)
+static bool pufks_rows_gather()
+{
+    const char* e = getenv("SPF_PUFKS_ROWS_GATHER");
+    return e && e[0] == '1';
+}
+
+// A gate graph's level of spf_graph_add_public_functional_keyswitch nodes: output b = the keyswitch of the rows
+// d_rows[b * p .. b * p + p) (a device table of device pointers), read where they lie.  The hand-written radices run the pointer-table
+// pre-pass and the main kernel over its digits and bodies; every other key gathers the rows into d_gather (B * p rows; the graph's
+// stage buffer) and runs generic_pufks_kernel on them.  *launches counts what went on the stream.
+static spf_status launch_pufks_rows(spf_ctx* c, hipStream_t s, size_t B, size_t p, const uint64_t* const* d_rows, uint64_t* d_gather,
+                                    uint64_t* d_out, uint32_t* launches)
+{
+    if (const char* why = pufks_shape_error(c->prm, B, p)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (pufks_tuned(c)) {
+        const uint32_t pstride = ((uint32_t)p + 31u) & ~31u;
+        const size_t per_output = (size_t)c->pufks_n * pstride * sizeof(uint32_t);
+        const size_t chunk = std::max<size_t>(4, std::min<size_t>(4096, (((size_t)8 << 30) / per_output) & ~(size_t)3));
+        uint64_t* gather_into = pufks_rows_gather() ? d_gather : nullptr;
+        *launches += (gather_into ? 3 : 2) * (uint32_t)((B + chunk - 1) / chunk);
+        return c->pufks_count == 8 ? launch_pufks_tuned<4, 8>(c, s, B, (uint32_t)p, nullptr, d_out, d_rows, gather_into)
+                                   : launch_pufks_tuned<4, 4>(c, s, B, (uint32_t)p, nullptr, d_out, d_rows, gather_into);
+    }
+    if (!d_gather) return fail(c, SPF_ERR_INVALID_ARGUMENT, "public functional keyswitch over scattered rows: no gather buffer");
+    spf_status st = spf_gather_rows_dev(c, s, B * p, (size_t)c->pufks_n + 1, d_rows, d_gather);
+    if (st != SPF_OK) return st;
+    *launches += 1 + (uint32_t)((B + kMaxGridRows - 1) / kMaxGridRows);
+    return spf_public_functional_keyswitch_enqueue(c, s, B, p, d_gather, d_out);
 }
 
 spf_status spf_public_functional_keyswitch_batch(spf_ctx* c, size_t B, size_t lwe_count, const uint64_t* lwe_in, uint64_t* glwe_out)

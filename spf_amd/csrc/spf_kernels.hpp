@@ -1734,6 +1734,24 @@ __global__ void lwe_pack_kernel(const uint64_t* left, const uint64_t* right, uin
         out[i] = left[i] * shift + right[i];
 }
 
+// The same over rows that lie anywhere (a gate graph's level): out[b] = left[b] * shift + right[b] wrapping, row b of either operand
+// read through a device pointer table, as glwe_pack_rows_kernel reads its rows.  Integer only.  One item = 256 words of one row, a
+// block-level grid-stride loop over the B * ceil(words / 256) items: the two row pointers of an iteration are the same for the whole
+// workgroup (scalar loads), the words of a row go to consecutive lanes.
+__global__ void lwe_pack_rows_kernel(const uint64_t* const* __restrict__ left, const uint64_t* const* __restrict__ right,
+                                     uint64_t* __restrict__ out, size_t B, uint32_t words, uint64_t shift)
+{
+    const uint32_t pieces = (words + blockDim.x - 1) / blockDim.x;
+    for (size_t item = blockIdx.x; item < B * pieces; item += gridDim.x) {
+        const size_t b = item / pieces;
+        const uint32_t j = (uint32_t)(item - b * pieces) * blockDim.x + threadIdx.x;
+        if (j >= words) continue;
+        const uint64_t* l = left[b];
+        const uint64_t* r = right[b];
+        out[b * words + j] = l[j] * shift + r[j];
+    }
+}
+
 // `DynamicGenericIntGraphNodes::pack` (parasol_runtime fluent/dynamic_generic_int_graph_nodes.rs:139-200): bit i of a
 // packed integer is the GLWE `in[b * n_bits + i]` times X^i (`MulXN(i)`), and the n_bits products are summed (a tree of
 // `GlweAdd`s).  Written out: out[b][p*N + j] = sum_{i < n_bits} s * in[b*n_bits + i][p*N + (j - i mod N)], s = -1 when

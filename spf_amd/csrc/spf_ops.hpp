@@ -47,10 +47,12 @@ enum Op {
     OP_KEYSWITCH = 0, OP_CBS = 1, OP_CMUX = 2, OP_GATE_CBS = 3,
     OP_SAMPLE_EXTRACT = 4, OP_NOT = 5, OP_GLWE_ADD = 6, OP_MUL_XN = 7, OP_MULTIPLY_GGSW_GLWE = 8, OP_GLEV_CMUX = 9, OP_SCHEME_SWITCH = 10,
     OP_ROT_CMUX = 11,
-    N_OPS = 12
+    // the bootstraps by a caller's lookup table (programmable_bootstrap_univariate / _bivariate), the table an operand
+    OP_PBS_UNIVARIATE = 12, OP_PBS_BIVARIATE = 13,
+    N_OPS = 14
 };
 
-enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N, PARAM_ROTATION_BELOW_N };
+enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N, PARAM_ROTATION_BELOW_N, PARAM_PLAINTEXT_BITS_BELOW_64 };
 constexpr int kNone = -1; // no spf_graph_op / no operand in this slot
 
 struct OpRow {
@@ -78,6 +80,9 @@ constexpr OpRow kOps[N_OPS] = {
     {OP_SCHEME_SWITCH, SPF_OP_SCHEME_SWITCH, 1, {SPF_VAL_GLEV1, kNone, kNone}, SPF_VAL_GGSW1, false, false, PARAM_NONE},
     // out = cmux(selector, acc, X^-param * acc): the high operand is a rotated read of the low one (launch_cmux_rot_scattered)
     {OP_ROT_CMUX, kNone, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, kNone}, SPF_VAL_GLWE1, true, false, PARAM_ROTATION_BELOW_N},
+    // out = sample_extract(blind rotation of the table by the LWE), the table the LAST operand; bivariate: by left * 2^param + right
+    {OP_PBS_UNIVARIATE, SPF_OP_PBS_UNIVARIATE, 2, {SPF_VAL_LWE0, SPF_VAL_GLWE1, kNone}, SPF_VAL_LWE1, false, true, PARAM_NONE},
+    {OP_PBS_BIVARIATE, SPF_OP_PBS_BIVARIATE, 3, {SPF_VAL_LWE0, SPF_VAL_LWE0, SPF_VAL_GLWE1}, SPF_VAL_LWE1, false, true, PARAM_PLAINTEXT_BITS_BELOW_64},
 };
 
 constexpr const OpRow& row(int op) { return kOps[op]; } // op: a valid pool operation
@@ -98,7 +103,8 @@ inline void in_out_bytes(const spf_params& p, int op, size_t (&in)[3], size_t& o
 }
 
 // The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN
-// amount is reduced mod 2N, a rotate-CMUX rotation lies in 1 .. N - 1, every other operation's parameter is 0 whatever the caller passed.
+// amount is reduced mod 2N, a rotate-CMUX rotation lies in 1 .. N - 1,
+// a bivariate bootstrap's plaintext_bits are below 64, every other operation's parameter is 0 whatever the caller passed.
 inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const char** why)
 {
     switch (kOps[op].param) {
@@ -110,6 +116,10 @@ inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const c
     case PARAM_ROTATION_BELOW_N:
         if (*param > 0 && *param < p.polynomial_degree) return SPF_OK;
         *why = "rotation must be in 1 .. polynomial_degree - 1";
+        return SPF_ERR_INVALID_ARGUMENT;
+    case PARAM_PLAINTEXT_BITS_BELOW_64:
+        if (*param < 64) return SPF_OK;
+        *why = "plaintext_bits must be below 64";
         return SPF_ERR_INVALID_ARGUMENT;
     default: *param = 0; return SPF_OK;
     }
@@ -130,13 +140,13 @@ constexpr bool rows_ok()
         if (!row_ok(kOps[op], op)) return false;
     return true;
 }
-constexpr bool graph_ops_ok() // the ten public values name ten rows (distinct: each row names its value back), OP_GATE_CBS and OP_ROT_CMUX have none
+constexpr bool graph_ops_ok() // the twelve public values name twelve rows (distinct: each row names its value back), OP_GATE_CBS and OP_ROT_CMUX have none
 {
-    for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_MUL_XN; g++)
+    for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_PBS_BIVARIATE; g++)
         if (pool_op_of(g) == kNone) return false;
     for (int op = 0; op < N_OPS; op++) {
         const int g = kOps[op].graph_op;
-        if (op == OP_GATE_CBS || op == OP_ROT_CMUX ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_MUL_XN || pool_op_of(g) != op)) return false;
+        if (op == OP_GATE_CBS || op == OP_ROT_CMUX ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_PBS_BIVARIATE || pool_op_of(g) != op)) return false;
     }
     return true;
 }
@@ -151,17 +161,27 @@ static_assert(graph_ops_ok(), "every spf_graph_op needs exactly one row, and onl
 static spf_status pool_keyswitch(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_in, uint64_t* d_out, Scratch* sc);
 static spf_status pool_circuit_bootstrap(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_lwe, double* d_ggsw, Scratch* sc,
                                          int per_wg_hint);
+static spf_status launch_lwe_pack(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_left, const uint64_t* d_right,
+                                  uint32_t plaintext_bits, uint64_t* d_out);
+namespace {
+spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_lwe, const uint64_t* d_lut, size_t lut_stride,
+                               uint32_t log_chi, uint32_t log_v, uint64_t body_rotate, uint64_t* d_out, size_t out_stride, bool extract,
+                               int per_wg_hint);
+}
 
 namespace spf_ops {
 
 // The kernels of B operations of one kind: operands in[0 .. arity) and `out` are contiguous device rows.  (The CMUX family over
 // SCATTERED operands — by handle on the tuned parameter sets, and in gate graphs — goes to spf_cmux_scattered_dev instead.)
 //   scr != null: a pool's batch — the staging set's intermediates, the population's workgroup shape (per_wg, launch_blind_rotate),
-//                no batch-limit check (a set never holds that many); d_mid = the set's level-0 row for OP_GATE_CBS;
+//                no batch-limit check (a set never holds that many); d_mid = the set's level-0 rows: the keyswitched LWE of
+//                OP_GATE_CBS, the packed input of OP_PBS_BIVARIATE (not the context's `packed`: several sets run side by side);
 //   scr == null: a gate graph's level — the public `_dev` entry points on the context's own intermediates, with their checks.
+// The two bootstraps by table read table row b at in[arity - 1] + b GLWEs, or ONE table for all rows with `one_lut`.
 inline spf_status launch_op(spf_ctx* c, hipStream_t s, int op, size_t B, const void* const in[3], void* out, uint64_t param,
-                            Scratch* scr, int per_wg, void* d_mid)
+                            Scratch* scr, int per_wg, void* d_mid, bool one_lut = false)
 {
+    const size_t lut_stride = one_lut ? 0 : glwe_words(c->prm);
     const auto u64 = [](const void* p) { return static_cast<const uint64_t*>(p); };
     const auto f64 = [](const void* p) { return static_cast<const double*>(p); };
     const auto keyswitch = [&](const void* lwe1, void* lwe0) {
@@ -185,6 +205,15 @@ inline spf_status launch_op(spf_ctx* c, hipStream_t s, int op, size_t B, const v
     case OP_MULTIPLY_GGSW_GLWE: return spf_multiply_glwe_ggsw_dev(c, s, B, u64(in[1]), f64(in[0]), (uint64_t*)out);
     case OP_GLEV_CMUX: return spf_glev_cmux_dev(c, s, B, f64(in[0]), u64(in[1]), u64(in[2]), (uint64_t*)out);
     case OP_SCHEME_SWITCH: return spf_scheme_switch_dev(c, s, B, u64(in[0]), (double*)out);
+    case OP_PBS_UNIVARIATE:
+        if (!scr) return spf_pbs_univariate_dev(c, s, B, u64(in[0]), u64(in[1]), lut_stride, (uint64_t*)out);
+        return launch_blind_rotate(c, s, B, u64(in[0]), u64(in[1]), lut_stride, 0, 0, 0, (uint64_t*)out, lwe1_words(c->prm), true, per_wg);
+    case OP_PBS_BIVARIATE: {
+        if (!scr) return spf_pbs_bivariate_dev(c, s, B, u64(in[0]), u64(in[1]), u64(in[2]), lut_stride, (uint32_t)param, (uint64_t*)out);
+        const spf_status st = launch_lwe_pack(c, s, B, u64(in[0]), u64(in[1]), (uint32_t)param, (uint64_t*)d_mid);
+        if (st != SPF_OK) return st;
+        return launch_blind_rotate(c, s, B, (const uint64_t*)d_mid, u64(in[2]), lut_stride, 0, 0, 0, (uint64_t*)out, lwe1_words(c->prm), true, per_wg);
+    }
     case OP_ROT_CMUX: return fail(c, SPF_ERR_INVALID_ARGUMENT, "a rotate-CMUX step reads its operands through a pointer table only");
     default: return fail(c, SPF_ERR_INVALID_ARGUMENT, "unknown graph operation");
     }

@@ -378,7 +378,7 @@ struct spf_pool {
             if (!grow_dev(s.d_out, s.dcap_out, cap * out)) return false;
             if (!grow_host(s.h_out, s.cap_out, cap * out)) return false;
         }
-        if (op == spf_pool_impl::OP_GATE_CBS && !grow_dev(s.d_mid, s.cap_mid, cap * value_bytes(prm, SPF_VAL_LWE0))) return false;
+        if ((op == spf_pool_impl::OP_GATE_CBS || op == spf_pool_impl::OP_PBS_BIVARIATE) && !grow_dev(s.d_mid, s.cap_mid, cap * value_bytes(prm, SPF_VAL_LWE0))) return false;
         if ((op == spf_pool_impl::OP_KEYSWITCH || op == spf_pool_impl::OP_CBS || op == spf_pool_impl::OP_GATE_CBS) && s.scr_cap < cap) {
             // (both: a staging set serves any kind later; a table set only ever sees the keyswitch — no 160 KB of circuit-bootstrap
             // intermediates per slot for it)

@@ -16,6 +16,8 @@
 //   through LDS, LWE rows read along their words, the packed gadget digits (one uint32 per coefficient: L * LOGB <= 32) written
 //   along the coefficients, [output][key row][pstride] with pstride = p rounded up to 32.  The main kernel reads one row of packed
 //   digits per key row, one row ahead; coefficients >= p are zeros and touch no line of their own.  Half the bytes of the words themselves.
+//   pufks_digits_rows_kernel is the same pre-pass over rows that lie anywhere (a gate graph's node): row b * p + c comes from a
+//   device pointer table, and the p bodies of an output are copied into a compact array, which the main kernels then read (PufksArgs::body).
 //   Key sharing.  G outputs (G = 2 up to two workgroups per CU, G = 4 beyond) share a workgroup whose waves meet at the same
 //   barriers every round, so the G wave pairs ask for the same key row within one round of each other: the first request brings
 //   the line into L2, the others hit there; workgroups launched together stay within a few rounds of each other and meet in the
@@ -89,10 +91,38 @@ __global__ __launch_bounds__(256) void pufks_digits_kernel(const uint64_t* __res
     }
 }
 
+// The same with row b * p + c read where it lies, through a device pointer table (a gate graph's level: the LWEs of a
+// spf_graph_add_public_functional_keyswitch node come from any node of any level).  The main kernels need the p bodies per output
+// as well: the blocks of the first tile column copy them into a compact [output][pstride] array, so no row is gathered whole.
+template <int L, int LOGB>
+__global__ __launch_bounds__(256) void pufks_digits_rows_kernel(const uint64_t* const* __restrict__ rows, uint32_t* __restrict__ dig,
+                                                                uint64_t* __restrict__ bodies, uint32_t n, uint32_t p, uint32_t pstride)
+{
+    __shared__ uint32_t tile[32][33];
+    const uint32_t tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const uint32_t i0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const uint64_t* const* row = rows + (size_t)blockIdx.z * p;
+    uint32_t* o = dig + (size_t)blockIdx.z * n * pstride;
+    for (uint32_t r = ty; r < 32; r += 8) {
+        const uint32_t c = c0 + r, i = i0 + tx;
+        if (c < p && i < n) tile[r][tx] = gadget_digits_packed<L, LOGB>(row[c][i]);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 32 && c0 + threadIdx.x < p)
+        bodies[(size_t)blockIdx.z * pstride + c0 + threadIdx.x] = row[c0 + threadIdx.x][n];
+    __syncthreads();
+    for (uint32_t r = ty; r < 32; r += 8) {
+        const uint32_t i = i0 + r, c = c0 + tx;
+        if (i < n && c < p) o[(size_t)i * pstride + c] = tile[tx][r];
+    }
+}
+
 struct PufksArgs {
     const c64* key;         // [n][L][2][1024]
-    const uint32_t* dig;    // [B][n][pstride] (pufks_digits_kernel)
-    const uint64_t* lwe_in; // B * p rows of n + 1 words: the bodies are read from here
+    const uint32_t* dig;    // [B][n][pstride] (pufks_digits_kernel / pufks_digits_rows_kernel)
+    // body of input c of output b = body[b * body_out_stride + c * body_stride]: word n of the contiguous rows (lwe_in + n, strides
+    // p * (n + 1) and n + 1), or the compact array of pufks_digits_rows_kernel (strides pstride and 1)
+    const uint64_t* body;
+    size_t body_out_stride, body_stride;
     uint64_t* out;          // B x 4096
     const c64* tables;
     uint32_t B, n, p, pstride;
@@ -223,11 +253,11 @@ __device__ __forceinline__ void pufks_body(const PufksArgs& a, char* smem)
     // the bodies b_j of this wave's coefficients j < p (word n of LWE row j): they land under the first polynomial's conversion
     uint64_t body[16];
     {
-        const uint64_t* rows = a.lwe_in + (size_t)ct * p * ((size_t)n + 1) + n;
+        const uint64_t* rows = a.body + (size_t)ct * a.body_out_stride;
 #pragma unroll
         for (int e = 0; e < 16; e++) {
             const uint32_t c = (uint32_t)coef2(e, lane_late, w);
-            body[e] = rows[(size_t)min(c, p - 1) * ((size_t)n + 1)]; // (coefficients >= p: masked where the body is added)
+            body[e] = rows[(size_t)min(c, p - 1) * a.body_stride]; // (coefficients >= p: masked where the body is added)
         }
     }
 #pragma unroll
@@ -387,9 +417,9 @@ __device__ __forceinline__ void pufks4_body(const PufksArgs& a, char* smem)
     wg_sync(); // cross reads retired before the image is overwritten
     uint64_t body[16];
     {
-        const uint64_t* rows = a.lwe_in + (size_t)ct * p * ((size_t)n + 1) + n;
+        const uint64_t* rows = a.body + (size_t)ct * a.body_out_stride;
 #pragma unroll
-        for (int e = 0; e < 16; e++) body[e] = rows[(size_t)min((uint32_t)coef2(e, lane, w), p - 1) * ((size_t)n + 1)];
+        for (int e = 0; e < 16; e++) body[e] = rows[(size_t)min((uint32_t)coef2(e, lane, w), p - 1) * a.body_stride];
     }
     fft512_single<-1, 7>(WW, mine, tab, lane);
     uint64_t tw[16];

@@ -40,11 +40,40 @@ class FheOp(enum.IntEnum):
     MulXN = 9
 
 
+class TableOp(enum.IntEnum):
+    """The `spf_graph_op` values that are no `FheOp` of the reference: `programmable_bootstrap_univariate` / `_bivariate`
+    (programmable_bootstrapping.rs:291, 575-621) with the lookup table as the last operand, a GLWE1 node; PBS_BIVARIATE's param
+    is plaintext_bits (< 64).  Taken wherever an FheOp is (`add_op`, `Pool.submit_v` / `push_v` / `run_v`) and reachable as
+    `FheOp.PBS_UNIVARIATE` / `FheOp.PBS_BIVARIATE`; iterating `FheOp` still gives the reference's ten."""
+    PBS_UNIVARIATE = 10
+    PBS_BIVARIATE = 11
+
+
+FheOp.PBS_UNIVARIATE = TableOp.PBS_UNIVARIATE
+FheOp.PBS_BIVARIATE = TableOp.PBS_BIVARIATE
+
+
+def graph_op(op):
+    """the member of FheOp or TableOp that a `spf_graph_op` value names"""
+    return TableOp(op) if int(op) in TableOp._value2member_map_ else FheOp(op)
+
+
 # RecordedCircuit's codes of the node constructors that are no FheOp (spf_graph_add_unpack / spf_graph_add_pack /
-# spf_graph_add_blind_rotation: one NODE_ROT_CMUX per bit, inputs (selector, accumulator), param = the rotation)
+# spf_graph_add_blind_rotation: one NODE_ROT_CMUX per bit, inputs (selector, accumulator), param = the rotation /
+# spf_graph_add_public_functional_keyswitch: inputs = all lwe_count operands, param = lwe_count)
 NODE_UNPACK = 64
 NODE_PACK = 65
 NODE_ROT_CMUX = 66
+NODE_PUFKS = 67
+
+# operand kinds of the operations whose arguments RecordedCircuit checks itself, as the library's table does (spf_ops.hpp)
+_PBS_IN_KINDS = {int(TableOp.PBS_UNIVARIATE): (0, 2), int(TableOp.PBS_BIVARIATE): (0, 0, 2)}
+
+
+def _check_lwe_count(what: str, lwe_count: int, degree: int) -> int:
+    if not 0 < lwe_count <= degree:
+        raise SpfError(1, f"{what}: lwe_count must be in 1 ..= {degree}, got {lwe_count!r}")
+    return int(lwe_count)
 
 
 def _check_n_bits(what: str, n_bits: int, degree: int) -> int:
@@ -155,6 +184,18 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_blind_rotation(self._g, int(glwe_node), arr, len(nodes), log_stride, C.byref(node)))
         return node.value
 
+    # public_functional_keyswitch (public_functional_keyswitch.rs:74-148), message j to coefficient j: the LWE0 (or LWE1) nodes
+    # -> one GLWE1 node
+    def add_public_functional_keyswitch(self, nodes: Sequence[int]) -> int:
+        nodes = list(nodes)
+        lwe_count = _check_lwe_count("add_public_functional_keyswitch", len(nodes), self._eng.params.polynomial_degree)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 1 << 32 for x in nodes):
+            raise SpfError(1, "add_public_functional_keyswitch: the operands must be node ids")
+        arr = (C.c_uint32 * lwe_count)(*[int(x) for x in nodes])
+        node = C.c_uint32()
+        self._eng._ck(self._lib.spf_graph_add_public_functional_keyswitch(self._g, arr, lwe_count, C.byref(node)))
+        return node.value
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -185,14 +226,15 @@ class RecordedCircuit:
     _OUT_KIND = {FheOp.SampleExtract: ValueKind.LWE1, FheOp.KeyswitchL1toL0: ValueKind.LWE0, FheOp.Not: ValueKind.GLWE1,
                  FheOp.GlweAdd: ValueKind.GLWE1, FheOp.CMux: ValueKind.GLWE1, FheOp.GlevCMux: ValueKind.GLEV1,
                  FheOp.MultiplyGgswGlwe: ValueKind.GLWE1, FheOp.CircuitBootstrap: ValueKind.GGSW1,
-                 FheOp.SchemeSwitch: ValueKind.GGSW1, FheOp.MulXN: ValueKind.GLWE1}
+                 FheOp.SchemeSwitch: ValueKind.GGSW1, FheOp.MulXN: ValueKind.GLWE1,
+                 TableOp.PBS_UNIVARIATE: ValueKind.LWE1, TableOp.PBS_BIVARIATE: ValueKind.LWE1}
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS, -1 input, -2 trivial constant
         self.kind: List[int] = []
         self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
-        self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands)
+        self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands; public functional keyswitch nodes: all lwe_count)
         self.host: List = []           # inputs: the caller's array
         self.outputs: List[int] = []   # nodes, in add_output order
         self._unpack_width: dict = {}  # unpack node -> n_bits of its add_unpack call
@@ -211,7 +253,18 @@ class RecordedCircuit:
     def add_op(self, op: FheOp, inputs: Sequence[int], param: int = 0) -> int:
         if any(i >= len(self.op) for i in inputs):
             raise SpfError(1, "operand is not a node of this circuit")
-        return self._add(FheOp(op), self._OUT_KIND[FheOp(op)], param, inputs)
+        want = _PBS_IN_KINDS.get(int(op))
+        if want is not None:   # the bootstraps by table: refused here as spf_graph_add_op refuses them
+            if len(inputs) != len(want):
+                raise SpfError(1, "graph op: wrong number of operands")
+            inputs = [_check_node(graph_op(op).name, x, len(self.op)) for x in inputs]
+            if any(self.kind[x] != k for x, k in zip(inputs, want)):
+                raise SpfError(1, "graph op: operand has the wrong ciphertext type")
+            if graph_op(op) == TableOp.PBS_UNIVARIATE:
+                param = 0
+            elif isinstance(param, bool) or not isinstance(param, (int, np.integer)) or not 0 <= param < 64:
+                raise SpfError(1, "graph op: plaintext_bits must be below 64")
+        return self._add(graph_op(op), self._OUT_KIND[graph_op(op)], param, inputs)
 
     def add_unpack(self, glwe_node: int, n_bits: int) -> List[int]:
         n_bits = _check_n_bits("add_unpack", n_bits, self.polynomial_degree)
@@ -244,6 +297,16 @@ class RecordedCircuit:
             acc = self._add(NODE_ROT_CMUX, ValueKind.GLWE1, 1 << (i + log_stride), (sel, acc))
         return acc
 
+    def add_public_functional_keyswitch(self, nodes: Sequence[int]) -> int:
+        nodes = list(nodes)
+        _check_lwe_count("add_public_functional_keyswitch", len(nodes), self.polynomial_degree)
+        nodes = [_check_node("add_public_functional_keyswitch", x, len(self.op)) for x in nodes]
+        if any(self.kind[x] not in (int(ValueKind.LWE0), int(ValueKind.LWE1)) for x in nodes):
+            raise SpfError(1, "add_public_functional_keyswitch: an operand is not an LWE")
+        if any(self.kind[x] != self.kind[nodes[0]] for x in nodes):
+            raise SpfError(1, "add_public_functional_keyswitch: lwe0 and lwe1 operands mixed")
+        return self._add(NODE_PUFKS, ValueKind.GLWE1, len(nodes), nodes)
+
     def add_output(self, node: int, kind: ValueKind) -> int:
         if self.kind[node] != int(kind):
             raise SpfError(1, "output kind does not match the node")
@@ -263,6 +326,8 @@ class RecordedCircuit:
                 continue
             if self.op[i] == NODE_PACK:
                 n = g.add_pack(self.inputs[i])
+            elif self.op[i] == NODE_PUFKS:
+                n = g.add_public_functional_keyswitch(self.inputs[i])
             elif self.op[i] == NODE_ROT_CMUX:  # one step = a one-bit rotation whose stride is the step's rotation
                 n = g.add_blind_rotation(self.inputs[i][1], [self.inputs[i][0]], self.param[i].bit_length() - 1)
             elif self.op[i] == -1:
@@ -270,7 +335,7 @@ class RecordedCircuit:
             elif self.op[i] == -2:
                 n = g.add_trivial(ValueKind(self.kind[i]), self.param[i])
             else:
-                n = g.add_op(FheOp(self.op[i]), self.inputs[i], self.param[i])
+                n = g.add_op(graph_op(self.op[i]), self.inputs[i], self.param[i])
             assert n == i
             i += 1
         return g, [g.add_output(n, ValueKind(self.kind[n])) for n in self.outputs]
@@ -287,7 +352,8 @@ class RecordedCircuit:
     def _build_arrays(self) -> dict:
         n = len(self.op)
         # a pack node's operands do not fit the three columns: they are ext[ext_at[i] : ext_at[i] + n_bits[i]] and its n_in is 0
-        # (the executor's own layout, spf_graph.hpp).  n_bits is the integer's width on unpack and pack nodes, 0 elsewhere;
+        # (the executor's own layout, spf_graph.hpp); a public functional keyswitch node's lwe_count operands lie the same way.
+        # n_bits is the integer's width on unpack and pack nodes, lwe_count on those, 0 elsewhere;
         # an unpack node's param is its bit index.
         ins = np.zeros((n, 3), dtype=np.uint32)
         n_in = np.zeros(n, dtype=np.uint32)
@@ -295,7 +361,7 @@ class RecordedCircuit:
         ext_at = np.zeros(n, dtype=np.uint32)
         ext: List[int] = []
         for i, t in enumerate(self.inputs):
-            if self.op[i] == NODE_PACK:
+            if self.op[i] in (NODE_PACK, NODE_PUFKS):
                 n_bits[i], ext_at[i] = len(t), len(ext)
                 ext.extend(t)
                 continue
@@ -326,6 +392,9 @@ class RecordedCircuit:
             if op == NODE_PACK:
                 at = int(a["ext_at"][i])
                 g.add_pack([int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]])
+            elif op == NODE_PUFKS:
+                at = int(a["ext_at"][i])
+                g.add_public_functional_keyswitch([int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]])
             elif op == NODE_ROT_CMUX:
                 g.add_blind_rotation(int(a["in"][i, 1]), [int(a["in"][i, 0])], int(a["param"][i]).bit_length() - 1)
             elif op == -1 and host[i] is not None:
@@ -333,7 +402,7 @@ class RecordedCircuit:
             elif op == -1:
                 g.add_trivial(ValueKind(kind[i]), int(a["param"][i]))
             else:
-                g.add_op(FheOp(op), [int(x) for x in a["in"][i, :int(a["n_in"][i])]], int(a["param"][i]))
+                g.add_op(graph_op(op), [int(x) for x in a["in"][i, :int(a["n_in"][i])]], int(a["param"][i]))
             i += 1
         for node in np.flatnonzero(a["keep"]):
             g.add_output(int(node), ValueKind(g.kind[int(node)]))

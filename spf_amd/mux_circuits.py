@@ -456,6 +456,9 @@ class GraphBuilder:
     def add_blind_rotation(self, glwe_node, shift_nodes, log_stride: int = 0) -> int:
         return self.graph.add_blind_rotation(glwe_node, shift_nodes, log_stride)
 
+    def add_public_functional_keyswitch(self, lwe_nodes) -> int:
+        return self.graph.add_public_functional_keyswitch(lwe_nodes)
+
 
 def append_uint_multiply(builder, a: Sequence, b: Sequence, blocks: Callable[[int, int], MuxCircuit]) -> list:
     """`mul_impl` (parasol_runtime/src/circuits/mul.rs:90-200): recursive gradeschool multiplication of two unsigned

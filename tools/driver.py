@@ -74,10 +74,13 @@ def upload_circuit_inputs(pool, rec, member=-1):
 
 def _fhe_ops_only(rec):
     """the native drivers hand every node to spf_pool_submit_op_v as an FheOp: a node of add_blind_rotation is none"""
-    from spf_amd.graph import NODE_ROT_CMUX
+    from spf_amd.graph import NODE_PUFKS, NODE_ROT_CMUX
     if NODE_ROT_CMUX in rec.op:
         raise RuntimeError("the circuit holds add_blind_rotation nodes, which are no FheOp: the per-operation drivers cannot walk it "
                            "(lower() it into a gate graph, or push the rotation with Pool.push_blind_rotation_v)")
+    if NODE_PUFKS in rec.op:
+        raise RuntimeError("the circuit holds add_public_functional_keyswitch nodes, which are no FheOp and have no submit by handle: "
+                           "the per-operation drivers cannot walk it (lower() it into a gate graph)")
 
 
 def run_circuit_by_handles(pool, rec, threads=64, member=-1, vals=None):

@@ -140,11 +140,11 @@ bool batch_forms_refuse_bad_arguments(spf_ctx* c)
     return ok;
 }
 
-// The ten computing `FheOp` arms as include/spf_hip.h documents them ("Operand order per operation", the gate graphs' comment):
+// The ten computing `FheOp` arms and the two bootstraps by table as include/spf_hip.h documents them ("Operand order per operation", the gate graphs' comment):
 // operation, operand kinds in order, result kind.  Written out here on purpose — NOT read from the library's table (spf_ops.hpp),
 // which is what it checks.
 struct HeaderOp { spf_graph_op op; int arity; spf_value_kind in[3]; spf_value_kind out; };
-const HeaderOp kHeaderOps[10] = {
+const HeaderOp kHeaderOps[12] = {
     {SPF_OP_SAMPLE_EXTRACT, 1, {SPF_VAL_GLWE1}, SPF_VAL_LWE1},
     {SPF_OP_KEYSWITCH_L1_TO_L0, 1, {SPF_VAL_LWE1}, SPF_VAL_LWE0},
     {SPF_OP_CIRCUIT_BOOTSTRAP, 1, {SPF_VAL_LWE0}, SPF_VAL_GGSW1},
@@ -155,6 +155,8 @@ const HeaderOp kHeaderOps[10] = {
     {SPF_OP_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLWE1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
     {SPF_OP_GLEV_CMUX, 3, {SPF_VAL_GGSW1, SPF_VAL_GLEV1, SPF_VAL_GLEV1}, SPF_VAL_GLEV1},
     {SPF_OP_MULTIPLY_GGSW_GLWE, 2, {SPF_VAL_GGSW1, SPF_VAL_GLWE1}, SPF_VAL_GLWE1},
+    {SPF_OP_PBS_UNIVARIATE, 2, {SPF_VAL_LWE0, SPF_VAL_GLWE1}, SPF_VAL_LWE1},
+    {SPF_OP_PBS_BIVARIATE, 3, {SPF_VAL_LWE0, SPF_VAL_LWE0, SPF_VAL_GLWE1}, SPF_VAL_LWE1},
 };
 const HeaderOp* header_op(int op)
 {
@@ -166,7 +168,7 @@ const HeaderOp* header_op(int op)
 // spf_graph_add_op against kHeaderOps, for every operation: the right operand kinds are accepted and give a node of the stated
 // result kind (which spf_graph_add_output takes); a wrong kind in any one slot, one operand too few and one too many are refused
 // with the builder's messages; the parameter follows the rule of the header (SampleExtract index below N, MulXN amount mod 2N,
-// ignored elsewhere).  Nothing is run: the context has no device.
+// a bivariate bootstrap's plaintext_bits below 64, ignored elsewhere).  Nothing is run: the context has no device.
 bool graph_ops_match_the_header(spf_ctx* c)
 {
     const uint64_t N = c->prm.polynomial_degree;
@@ -207,10 +209,13 @@ bool graph_ops_match_the_header(spf_ctx* c)
         if (h.op == SPF_OP_SAMPLE_EXTRACT)
             expect("index N", h.op, spf_graph_add_op(g, h.op, in, h.arity, N, &node), SPF_ERR_INVALID_ARGUMENT,
                    "graph op: sample_extract index >= polynomial_degree");
+        if (h.op == SPF_OP_PBS_BIVARIATE)
+            expect("plaintext_bits 64", h.op, spf_graph_add_op(g, h.op, in, h.arity, 64, &node), SPF_ERR_INVALID_ARGUMENT,
+                   "graph op: plaintext_bits must be below 64");
         if (g->nodes.size() != n_nodes) { fprintf(stderr, "spf_graph_add_op, operation %d: a refused call left a node\n", h.op); ok = false; }
         // the parameter the node keeps
-        const uint64_t given = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : 2 * N + 3;
-        const uint64_t kept = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : (h.op == SPF_OP_MUL_XN ? 3 : 0);
+        const uint64_t given = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : (h.op == SPF_OP_PBS_BIVARIATE ? 63 : 2 * N + 3);
+        const uint64_t kept = h.op == SPF_OP_SAMPLE_EXTRACT ? N - 1 : (h.op == SPF_OP_MUL_XN ? 3 : (h.op == SPF_OP_PBS_BIVARIATE ? 63 : 0));
         expect("with a parameter", h.op, spf_graph_add_op(g, h.op, in, h.arity, given, &node), SPF_OK, nullptr);
         if (ok && g->nodes[node].param != kept) {
             fprintf(stderr, "spf_graph_add_op, operation %d: parameter %" PRIu64 " kept as %" PRIu64 ", expected %" PRIu64 "\n", h.op, given, g->nodes[node].param, kept);
@@ -218,7 +223,7 @@ bool graph_ops_match_the_header(spf_ctx* c)
         }
     }
     uint32_t node = 0;
-    expect("no such operation", 10, spf_graph_add_op(g, (spf_graph_op)10, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    expect("no such operation", 12, spf_graph_add_op(g, (spf_graph_op)12, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
     // the two node constructors of packed integers: n_bits nodes of kind LWE1 with the bit index as parameter / one GLWE1 node
     // whose operand list is kept whole; every refusal of the header, and a refused call leaves nothing behind
     {
@@ -430,7 +435,7 @@ int main(int argc, char** argv)
                 case 2: {
                     uint32_t in[4];
                     for (auto& x : in) x = r.below(4) ? (uint32_t)r.below(have + 2) : (uint32_t)r();
-                    st = spf_graph_add_op(g, (spf_graph_op)r.below(12), r.below(10) ? in : nullptr, r.below(5), r.below(2) ? r() : r.below(5000), &node);
+                    st = spf_graph_add_op(g, (spf_graph_op)r.below(14), r.below(10) ? in : nullptr, r.below(5), r.below(2) ? r() : r.below(5000), &node);
                     break;
                 }
                 default: st = spf_graph_add_output(g, r.below(4) ? (uint32_t)r.below(have + 2) : (uint32_t)r(), r.below(8) ? host_buf : nullptr); break;
