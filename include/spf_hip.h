@@ -78,6 +78,28 @@ typedef struct spf_ctx spf_ctx;
  * per-GPU engine (twiddle tables, scratch).  device_id is the HIP ordinal. */
 spf_status spf_create(const spf_params *params, int device_id, spf_ctx **out);
 void spf_destroy(spf_ctx *ctx);
+/* Lifetimes.  A child keeps its parent alive, and the destroy functions may be called in ANY order, each exactly once per
+ * handle.  spf_graph_create and spf_pool_create retain their context; spf_graph_destroy and spf_pool_destroy release it.
+ * spf_destroy drops the caller's reference: the context's streams and device memory go with the last one, and graphs and
+ * pools made from the context stay fully usable (run, submit, wait, download) until they are destroyed themselves.
+ * spf_group_graph_create and spf_pool_create_group retain the group; the group holds one reference on each member context and
+ * a merged graph one on its member's.  spf_group_destroy drops the caller's reference: the communicators, the member threads,
+ * the merged graphs and the group's references on its members go with the last one, so after it a job can still be read
+ * (spf_graph_member, spf_graph_stats), run and destroyed, and a group pool — or a pool or graph made on a context borrowed
+ * through spf_group_ctx — goes on working.  Values keep their own rule (below: they may outlive their pool, and are refused,
+ * never trusted, by any other pool).
+ * The caller's duty, NOT detected by the library: no use of a handle after its own destroy (that includes passing the
+ * spf_ctx* to any call after spf_destroy, and the spf_group* after spf_group_destroy); no second destroy of a handle; no
+ * destroy while another thread is inside a call on that handle; no spf_destroy on a context borrowed through spf_group_ctx;
+ * no spf_device_free after the context's last reference is gone. */
+
+/* Process-wide counts of the handles that exist: made and not yet freed (a context or group that its children keep alive
+ * still counts; a group pool counts itself and one pool per member; a group's merged graphs count as graphs).  Atomic
+ * counters moved in the constructors and at the final frees: how a host without a leak checker sees a lost reference. */
+typedef struct spf_live_counts {
+    uint64_t contexts, groups, graphs, pools, values;
+} spf_live_counts;
+spf_status spf_live_objects(spf_live_counts *out);
 /* Message of the last failing call on this context (or, with ctx == NULL, of the last failing
  * spf_create on the calling thread).  The returned pointer is storage of the calling thread: it
  * stays valid until that thread calls spf_last_error again, whatever other threads do. */
@@ -463,6 +485,7 @@ typedef enum spf_graph_op {
  *   The library asks the HIP runtime for more hardware queues when it is loaded (GPU_MAX_HW_QUEUES=24 unless set): streams that
  *   share a hardware queue run their kernels one after the other. */
 typedef struct spf_pool spf_pool;
+/* (the pool retains `ctx` until spf_pool_destroy: see Lifetimes at spf_create) */
 spf_status spf_pool_create(spf_ctx *ctx, size_t max_batch, uint32_t max_wait_us, spf_pool **out);
 void spf_pool_destroy(spf_pool *pool); /* drains pending work first */
 /* `Evaluation::keyswitch_lwe_l1_lwe_l0` for one ciphertext */
@@ -652,6 +675,7 @@ spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value
  * repeatedly with new input contents.  A graph is not thread-safe; distinct graphs on one
  * context may run from different threads (their launches serialise on the context's stream). */
 typedef struct spf_graph spf_graph;
+/* (the graph retains `ctx` until spf_graph_destroy: see Lifetimes at spf_create) */
 spf_status spf_graph_create(spf_ctx *ctx, spf_graph **out);
 void spf_graph_destroy(spf_graph *graph);
 /* FheOp::Input{Lwe0,Lwe1,Glwe1,Ggsw1,Glev1} */
@@ -841,7 +865,8 @@ typedef struct spf_group spf_group;
 spf_status spf_group_create(const spf_params *params, const int *device_ids, int n_devices, spf_group **out);
 void spf_group_destroy(spf_group *grp);
 int spf_group_size(const spf_group *grp);
-/* member i's context: for the `_dev` entry points, gate graphs and measurement hooks on that device.  Owned by the group. */
+/* member i's context: for the `_dev` entry points, gate graphs and measurement hooks on that device.  Owned by the group:
+ * never spf_destroy it; a pool or graph made on it keeps it alive past spf_group_destroy (Lifetimes, at spf_create). */
 spf_ctx *spf_group_ctx(spf_group *grp, int member);
 /* message of the last failing group call (storage of the calling thread, as spf_last_error) */
 const char *spf_group_last_error(const spf_group *grp);
@@ -941,7 +966,8 @@ spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_o
  *       rotation and its jobs are dealt again over the others.  Results are word-identical to spf_graph_run of each job on one
  *       context.  spf_graph_run / spf_graph_stats / spf_graph_destroy work on such a graph (run = a pool of one; stats = of
  *       the job as built: levels and launches are those of the merged graph it last ran in).
- *   spf_graph_member:       the member a group's graph last ran on (-1 before its first run; 0 for an ordinary graph). */
+ *   spf_graph_member:       the member a group's graph last ran on (-1 before its first run; 0 for an ordinary graph).
+ * A job retains its group until spf_graph_destroy (Lifetimes, at spf_create). */
 spf_status spf_group_graph_create(spf_group *grp, spf_graph **out);
 spf_status spf_group_run_graphs(spf_group *grp, spf_graph *const *graphs, size_t n);
 int spf_graph_member(const spf_graph *graph);
@@ -949,7 +975,7 @@ int spf_graph_member(const spf_graph *graph);
 /* Call coalescing over the group: one pool per member; a calling thread is dealt to a member on its first submit
  * (round-robin over the members in rotation) and stays there, so that the callers of one device keep coming back to the
  * same batch.  The handle is used with the spf_pool_submit_*, spf_pool_wait, spf_pool_stats (sums), spf_pool_set_max_inflight
- * (per member) and spf_pool_destroy entry points above. */
+ * (per member) and spf_pool_destroy entry points above.  The pool retains the group until spf_pool_destroy (Lifetimes, at spf_create). */
 spf_status spf_pool_create_group(spf_group *grp, size_t max_batch, uint32_t max_wait_us, spf_pool **out);
 
 /* Library / kernel build information: version, target, the compile-time options of the blind rotation. */

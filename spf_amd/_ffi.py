@@ -154,6 +154,7 @@ SYMBOLS = [
     ("spf_ciphertext_from_bincode", _I, [C.POINTER(_CParams), _I, _P, _SZ, _P]),
     ("spf_ciphertext_to_bincode", _I, [C.POINTER(_CParams), _I, _P, _P, _SZ, C.POINTER(_SZ)]),
     ("spf_version", C.c_char_p, []),
+    ("spf_live_objects", _I, [C.POINTER(_U64 * 5)]),
     # device groups (one host process, every GPU of the node)
     ("spf_group_create", _I, [C.POINTER(_CParams), C.POINTER(_I), _I, C.POINTER(_P)]),
     ("spf_group_destroy", None, [_P]),
@@ -362,6 +363,15 @@ def ciphertext_to_bincode(kind: int, words, params: Params = DEFAULT_128) -> byt
     if st != 0:
         raise SpfError(st, (lib.spf_last_error(None) or b"").decode())
     return out[:written.value].tobytes()
+
+
+def live_objects() -> dict:
+    """`spf_live_objects`: how many contexts, groups, graphs, pools and values exist in this process (made, not yet freed)"""
+    a = (_U64 * 5)()
+    st = load_library().spf_live_objects(C.byref(a))
+    if st != 0:
+        raise SpfError(st, "spf_live_objects failed")
+    return dict(zip(("contexts", "groups", "graphs", "pools", "values"), (int(x) for x in a)))
 
 
 class Engine:

@@ -101,6 +101,7 @@ struct spf_graph {
         size_t ptr_index[3] = {0, 0, 0};
         bool one_lut = false; // the bootstraps by table: every member names the same table node (read in place, lut_stride = 0)
     };
+    spf_live::Tick<spf_live::GRAPH> live;
     spf_ctx* ctx = nullptr;
     spf_params prm{};
     struct spf_group* grp = nullptr; // a graph of a device group (spf_group_graph_create): placed on a member when it is run
@@ -680,6 +681,7 @@ inline spf_status run(spf_graph* g)
 
 static spf_status group_run_graphs(struct spf_group* grp, spf_graph* const* graphs, size_t n); // spf_group.hpp
 static void group_forget_graph(struct spf_group* grp, spf_graph* graph);
+static void group_release(struct spf_group* grp);
 
 spf_status spf_graph_create(spf_ctx* c, spf_graph** out)
 {
@@ -688,6 +690,7 @@ spf_status spf_graph_create(spf_ctx* c, spf_graph** out)
     if (!g) return fail(c, SPF_ERR_HIP, "out of host memory");
     g->ctx = c;
     g->prm = c->prm;
+    ctx_retain(c); // (the graph's device memory is the context's device's, its launches the context's stream's)
     *out = g;
     return SPF_OK;
 }
@@ -695,11 +698,15 @@ spf_status spf_graph_create(spf_ctx* c, spf_graph** out)
 void spf_graph_destroy(spf_graph* g)
 {
     if (!g) return;
-    if (g->grp) group_forget_graph(g->grp, g); // (a merged graph of the group may still read this job's buffers)
-    (void)hipSetDevice(g->ctx->device);
+    spf_ctx* c = g->ctx;
+    struct spf_group* grp = g->grp;
+    if (grp) group_forget_graph(grp, g); // (a merged graph of the group may still read this job's buffers)
+    (void)hipSetDevice(c->device);
     g->release();
     g->h_inputs.free_buf();
     delete g;
+    ctx_release(c);
+    if (grp) group_release(grp); // (a job holds its group: the last one out, after spf_group_destroy, takes the group down)
 }
 
 spf_status spf_graph_add_input(spf_graph* g, spf_value_kind kind, const void* host, uint32_t* node)

@@ -144,6 +144,8 @@ struct Rccl {
 
 struct spf_group {
     using Member = spf_group_impl::Member;
+    spf_live::Tick<spf_live::GROUP> live;
+    std::atomic<int> refs{1}; // the caller's (spf_group_destroy drops it), one per job (spf_group_graph_create) and per group pool
     spf_params prm{};
     std::vector<std::unique_ptr<Member>> m;
     std::mutex key_mu; // key loading and replication: one at a time
@@ -492,19 +494,27 @@ spf_status spf_group_create(const spf_params* params, const int* device_ids, int
     return SPF_OK;
 }
 
-void spf_group_destroy(spf_group* g)
+void spf_group_destroy(spf_group* g) { group_release(g); }
+
+} // extern "C"
+
+// the communicators, the member threads, the merged graphs and the group's references on its members go with the last reference
+static void group_retain(spf_group* g) { g->refs.fetch_add(1, std::memory_order_relaxed); }
+static void group_release(spf_group* g)
 {
-    if (!g) return;
+    if (!g || g->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
     for (auto& mem : g->m) mem->worker.finish();
     for (auto& mg : g->merged)
         if (mg.graph) spf_graph_destroy(mg.graph);
     if (g->rccl.handle)
         for (ncclComm_t c : g->rccl.comms)
             if (c) (void)g->rccl.CommDestroy(c);
-    for (auto& mem : g->m) spf_destroy(mem->ctx);
+    for (auto& mem : g->m) ctx_release(mem->ctx); // (a pool or graph made on a borrowed member context keeps that context)
     // (librccl.so stays loaded: unloading a library that owns device state at process teardown is not worth the risk)
     delete g;
 }
+
+extern "C" {
 
 int spf_group_size(const spf_group* g) { return g ? (int)g->m.size() : 0; }
 
@@ -1051,6 +1061,7 @@ spf_status spf_group_graph_create(spf_group* g, spf_graph** out)
     spf_status s = spf_graph_create(g->m[0]->ctx, out); // (member 0's context: parameters and build-time validation only)
     if (s != SPF_OK) return gfail(g, s, std::string("member 0: ") + spf_last_error(g->m[0]->ctx));
     (*out)->grp = g;
+    group_retain(g);
     return SPF_OK;
 }
 
@@ -1077,6 +1088,7 @@ spf_status spf_pool_create_group(spf_group* g, size_t max_batch, uint32_t max_wa
         }
         top->members.push_back(p);
     }
+    group_retain(g); // (pool_deal reads the members' rotation flags: the group stays until spf_pool_destroy)
     *out = top;
     return SPF_OK;
 }

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,7 +68,22 @@ const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_s
 
 } // namespace
 
+// Process-wide counts of the live handles (spf_live_objects).  Every handle struct has a Tick member: the counts move in the
+// constructors and at the final frees and nowhere else — never on a submit, run or wait path.
+namespace spf_live {
+enum Kind { CTX = 0, GROUP, GRAPH, POOL, VALUE, KINDS };
+inline std::atomic<uint64_t> g_count[KINDS];
+template <Kind K> struct Tick {
+    Tick() { g_count[K].fetch_add(1, std::memory_order_relaxed); }
+    ~Tick() { g_count[K].fetch_sub(1, std::memory_order_relaxed); }
+    Tick(const Tick&) = delete;
+    Tick& operator=(const Tick&) = delete;
+};
+} // namespace spf_live
+
 struct spf_ctx {
+    spf_live::Tick<spf_live::CTX> live;
+    std::atomic<int> refs{1}; // the caller's (spf_destroy drops it), one per graph and pool made on the context, a group's on its members
     spf_params prm{};
     int device = 0;
     std::recursive_mutex mu; // recursive: the host-pointer entry points hold it across the _dev calls they make
@@ -721,9 +737,24 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
     return SPF_OK;
 }
 
-void spf_destroy(spf_ctx* c)
+spf_status spf_live_objects(spf_live_counts* out)
 {
-    if (!c) return;
+    if (!out) return SPF_ERR_INVALID_ARGUMENT;
+    auto n = [](spf_live::Kind k) { return spf_live::g_count[k].load(std::memory_order_relaxed); };
+    out->contexts = n(spf_live::CTX);
+    out->groups = n(spf_live::GROUP);
+    out->graphs = n(spf_live::GRAPH);
+    out->pools = n(spf_live::POOL);
+    out->values = n(spf_live::VALUE);
+    return SPF_OK;
+}
+
+// Lifetimes (include/spf_hip.h): a child keeps its parent alive.  A graph and a pool retain their context, a group its members'
+// contexts; the streams and the device memory go with the last reference, whoever drops it.
+static void ctx_retain(spf_ctx* c) { c->refs.fetch_add(1, std::memory_order_relaxed); }
+static void ctx_release(spf_ctx* c)
+{
+    if (!c || c->refs.fetch_sub(1, std::memory_order_acq_rel) != 1) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& v : c->timed)
@@ -740,6 +771,8 @@ void spf_destroy(spf_ctx* c)
     for (hipEvent_t e : c->slice_ev) (void)hipEventDestroy(e);
     delete c;
 }
+
+void spf_destroy(spf_ctx* c) { ctx_release(c); }
 
 // The blind-rotation kernels read a copy of the bootstrap key scaled by 2^-10 (the 1/N of the inverse transform travels with
 // the key through the multiply-accumulate: exact, and 32 multiplications per polynomial and step are not executed).  Built
@@ -2999,6 +3032,7 @@ spf_status spf_pool_create(spf_ctx* c, size_t max_batch, uint32_t max_wait_us, s
         delete p;
         return fail(c, SPF_ERR_HIP, std::string("spf_pool_create: cannot start the pool threads: ") + e.what());
     }
+    ctx_retain(c); // (the pool's threads use the context's stream, mutex and scratch: it stays until spf_pool_destroy)
     *out = p;
     return SPF_OK;
 }
@@ -3016,14 +3050,19 @@ spf_status spf_pool_set_max_inflight(spf_pool* p, size_t max_inflight)
     return SPF_OK;
 }
 
+static void group_release(struct spf_group* g); // spf_group.hpp
+
 void spf_pool_destroy(spf_pool* p)
 {
     if (!p) return;
     if (!p->members.empty()) { // a group pool owns one pool per member and no threads of its own
         for (spf_pool* q : p->members) spf_pool_destroy(q);
+        spf_group* grp = p->grp;
         delete p;
+        group_release(grp);
         return;
     }
+    spf_ctx* ctx = p->ctx;
     {
         std::lock_guard<spf_pool::Mutex> lk(p->mu);
         p->stop = true;
@@ -3051,6 +3090,7 @@ void spf_pool_destroy(spf_pool* p)
     p->destroy_def_streams();
     if (p->arena) p->arena->close(); // cached blocks go back to the driver; values still alive free theirs when they are released
     delete p;
+    ctx_release(ctx);
 }
 
 } // extern "C"
@@ -3176,6 +3216,16 @@ spf_pool* value_pool(spf_pool* top, int member, int* which)
     return top->members[member];
 }
 
+// The pool of `top` that value `v` lives on, or null when the value is not this pool's.  Decided by the arena the value holds — which
+// it keeps alive, so no later pool can come to own the same one — and by its member index: v->home is the address of a pool that
+// may be gone (values may outlive their pool) and of whatever was allocated there since; nobody reads it before this has answered.
+spf_pool* value_home(spf_pool* top, const spf_value* v)
+{
+    spf_pool* leaf = top;
+    if (!top->members.empty()) leaf = (v->member >= 0 && v->member < (int)top->members.size()) ? top->members[(size_t)v->member] : nullptr;
+    return (leaf && leaf->arena && leaf->arena == v->arena) ? leaf : nullptr;
+}
+
 // a submit by handle: the checks of every `_v` wrapper below.  `explain`: a refused parameter leaves its reason in the context's
 // last error (spf_pool_submit_op_v) instead of a bare status (the named wrappers).
 spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, size_t n_vals, uint64_t param, spf_value** out,
@@ -3194,13 +3244,12 @@ spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, si
         if (v[k]->kind != info.in_kind[k]) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand has the wrong ciphertext type");
         if (v[k]->state.load(std::memory_order_acquire) == spf_value_impl::FAILED)
             return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: the operation that was to produce this operand failed");
-        if (v[k]->home != v[0]->home)
+        if (v[k]->arena != v[0]->arena)
             return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operands live on different members of the group (spf_value_copy_to_member moves one)");
     }
-    spf_pool* leaf = v[0]->home;
+    spf_pool* leaf = value_home(top, v[0]);
     const int member = v[0]->member;
-    const bool mine = top->members.empty() ? leaf == top : (member >= 0 && member < (int)top->members.size() && top->members[member] == leaf);
-    if (!mine) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
+    if (!leaf) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
     spf_value* res = spf_value::make(leaf->arena, leaf, member, info.out_kind, value_bytes(leaf->prm, info.out_kind));
     if (!res) return fail(leaf->ctx, SPF_ERR_HIP, "out of host memory");
     const spf_status st = leaf->submit_impl(op, true, nullptr, nullptr, v, res, ticket, param);
@@ -3576,13 +3625,14 @@ spf_status spf_pool_submit_blind_rotation_v(spf_pool* p, const spf_value* glwe, 
     for (size_t i = 0; i < n_bits; i++) {
         if (!shift_ggsw[i]) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: null selector");
         if (shift_ggsw[i]->kind != SPF_VAL_GGSW1) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: selector is not an L1 GGSW");
-        if (shift_ggsw[i]->home != glwe->home)
+        if (shift_ggsw[i]->arena != glwe->arena)
             return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: operands live on different members of the group (spf_value_copy_to_member moves one)");
         if (shift_ggsw[i]->state.load(std::memory_order_acquire) == spf_value_impl::FAILED)
             return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool blind rotation: the operation that was to produce a selector failed");
     }
-    const spf_pool* leaf = glwe->home;
-    if (leaf && !leaf->ctx->generic && (leaf->prm.cbs_radix_log != 4 || leaf->prm.cbs_radix_count != 4))
+    const spf_pool* leaf = value_home(p, glwe);
+    if (!leaf) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
+    if (!leaf->ctx->generic && (leaf->prm.cbs_radix_log != 4 || leaf->prm.cbs_radix_count != 4))
         return fail(p->ctx, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
     const spf_value* acc = glwe;
     for (size_t i = 0; i < n_bits; i++) {

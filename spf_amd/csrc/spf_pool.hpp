@@ -218,6 +218,7 @@ struct spf_group;
 
 struct spf_pool {
     using Batch = spf_pool_impl::Batch;
+    spf_live::Tick<spf_live::POOL> live;
     // A pool over a device group (spf_pool_create_group) is only a dealer: one ordinary pool per member, the calling thread's
     // home member decided on its first submit; tickets carry the member in their top byte.  Nothing below `members` is used then.
     static constexpr int kMemberShift = 56;

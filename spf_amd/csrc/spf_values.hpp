@@ -167,11 +167,13 @@ enum State : int { PENDING = 0, READY = 1, FAILED = 2 };
 struct spf_pool;
 
 struct spf_value {
+    spf_live::Tick<spf_live::VALUE> live;
     std::atomic<int> refs{1};
     int kind = 0;
     size_t bytes = 0;
     int member = 0;                 // member of a group pool the value lives on (0 for a plain pool)
-    spf_pool* home = nullptr;       // the (member) pool whose context owns the memory: operands of one operation share it
+    spf_pool* home = nullptr;       // the (member) pool the value was made on.  Dangles once that pool is destroyed (values may outlive
+                                    // it): whether a value belongs to a pool is decided by `arena`, never by this address (value_home)
     std::shared_ptr<spf_value_impl::Arena> arena;
     std::shared_ptr<spf_value_impl::Block> blk; // set at upload, or when the producing batch is enqueued
     size_t off = 0;

@@ -2,6 +2,7 @@
 # Build and run the host-side sanitizer fuzz (tools/fuzz_host.cpp): the library's translation unit with AddressSanitizer +
 # UndefinedBehaviorSanitizer on the HOST code only (GPU ASan / XNACK are not available on this pool), no GPU needed.
 # usage: bash tools/asan_host.sh [cases (default 1000000)] [seed]
+# (the same binary has the destroy-order modes --lifetimes, --lifetimes-random <cases> <seed>, --selftest-lifetime: tests/test_lifetimes_host.py)
 set -e
 cd "$(dirname "$0")/.."
 mkdir -p tools/bin

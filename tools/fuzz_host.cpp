@@ -14,9 +14,11 @@
 // Seeds: the reference's own malformed vector (parasol_runtime/src/safe_bincode.rs:58-66, :105-117) and valid serializations.
 //
 // usage: fuzz_host <cases> [seed]
+//        fuzz_host --lifetimes [scenario] | --lifetimes-random <cases> <seed> | --selftest-lifetime   (destroy orders, below)
 #include "../spf_amd/csrc/spf_hip.hip"
 
 #include <cinttypes>
+#include <functional>
 #include <random>
 
 namespace {
@@ -286,10 +288,323 @@ bool wire_sizes_match_the_header(const spf_params& p)
     return ok;
 }
 
+
+// ---- lifetimes: every destroy order of the handles (contexts, groups, graphs, jobs), on hand-made parents, no device ----------
+//
+// The rule of include/spf_hip.h ("Lifetimes"): a child keeps its parent alive, destroy functions may come in any order.  A forest
+// of hand-made contexts and groups (as fake_ctx: device -1, every HIP call fails and is ignored by the destroy paths) with graphs,
+// jobs, jobs filed under a hand-filled merged entry and graphs on borrowed member contexts is taken apart in a given or a random
+// order; after every step spf_live_objects must equal the model below, which knows the rule and nothing of the library's
+// counting.  The sanitizers see a parent freed under a child, LeakSanitizer one that nobody freed.
+struct Forest {
+    enum Type { CTX = 0, GROUP = 1, GRAPH = 2 };
+    struct Handle { Type type; int idx; };
+    struct MCtx { spf_ctx* h; bool held; int kids; };                       // held: by the caller, or by its group; kids: graphs on it
+    struct MSlot { std::vector<int> jobs; bool graph = false; };          // one merged[member] entry: the jobs filed there
+    struct MGroup { spf_group* h; bool held; int jobs; std::vector<int> ctx; std::vector<MSlot> slots; bool freed; };
+    struct MGraph { spf_graph* h; int ctx; int grp; bool alive; };
+    spf_params prm;
+    std::vector<MCtx> ctxs;
+    std::vector<MGroup> groups;
+    std::vector<MGraph> graphs;
+    std::vector<Handle> handles; // what the caller owns and has to destroy, in creation order
+    uint64_t merged_alive = 0;
+    bool ok = true;
+    const char* step = "";
+
+    explicit Forest(const spf_params& p) : prm(p) {}
+
+    void check()
+    {
+        uint64_t want_ctx = 0, want_grp = 0, want_graph = merged_alive;
+        for (const MCtx& c : ctxs) want_ctx += (c.held || c.kids > 0) ? 1 : 0;
+        for (const MGroup& g : groups) want_grp += g.freed ? 0 : 1;
+        for (const MGraph& g : graphs) want_graph += g.alive ? 1 : 0;
+        spf_live_counts got;
+        if (spf_live_objects(&got) != SPF_OK) { fprintf(stderr, "spf_live_objects failed\n"); ok = false; return; }
+        if (got.contexts != want_ctx || got.groups != want_grp || got.graphs != want_graph || got.pools != 0 || got.values != 0) {
+            fprintf(stderr, "lifetimes, after %s: live contexts/groups/graphs/pools/values %" PRIu64 "/%" PRIu64 "/%" PRIu64 "/%" PRIu64 "/%" PRIu64
+                            ", the model says %" PRIu64 "/%" PRIu64 "/%" PRIu64 "/0/0\n",
+                    step, got.contexts, got.groups, got.graphs, got.pools, got.values, want_ctx, want_grp, want_graph);
+            ok = false;
+        }
+    }
+    int new_ctx()
+    {
+        spf_ctx* c = new spf_ctx();
+        fake_ctx(*c, prm, true);
+        ctxs.push_back({c, true, 0});
+        return (int)ctxs.size() - 1;
+    }
+    int add_ctx()
+    {
+        const int i = new_ctx();
+        handles.push_back({CTX, i});
+        step = "a context made";
+        check();
+        return i;
+    }
+    int add_group(int members)
+    {
+        spf_group* g = new spf_group();
+        g->prm = prm;
+        MGroup m{g, true, 0, {}, {}, false};
+        for (int i = 0; i < members; i++) {
+            const int c = new_ctx();
+            g->m.emplace_back(new spf_group::Member());
+            g->m.back()->ctx = ctxs[(size_t)c].h;
+            g->m.back()->device = -1;
+            m.ctx.push_back(c);
+        }
+        g->merged.resize((size_t)members);
+        m.slots.resize((size_t)members);
+        groups.push_back(m);
+        handles.push_back({GROUP, (int)groups.size() - 1});
+        step = "a group made";
+        check();
+        return (int)groups.size() - 1;
+    }
+    // nodes through the builder, so that the graph owns host memory of its own
+    void fill(spf_graph* g, size_t n_ops)
+    {
+        static uint64_t host_buf[4];
+        uint32_t at = 0, node = 0;
+        if (spf_graph_add_input(g, SPF_VAL_GLWE1, host_buf, &at) != SPF_OK) ok = false;
+        for (size_t k = 0; k < n_ops; k++) {
+            if (spf_graph_add_op(g, SPF_OP_NOT, &at, 1, 0, &node) != SPF_OK) ok = false;
+            at = node;
+        }
+        if (spf_graph_add_output(g, at, host_buf) != SPF_OK) ok = false;
+    }
+    // a graph on context `c` (a caller's, or one borrowed from a group: spf_group_ctx)
+    int add_graph(int c, size_t n_ops = 2)
+    {
+        spf_graph* g = nullptr;
+        if (spf_graph_create(ctxs[(size_t)c].h, &g) != SPF_OK) { ok = false; return -1; }
+        fill(g, n_ops);
+        ctxs[(size_t)c].kids++;
+        graphs.push_back({g, c, -1, true});
+        handles.push_back({GRAPH, (int)graphs.size() - 1});
+        step = "a graph made";
+        check();
+        return (int)graphs.size() - 1;
+    }
+    int add_borrowed_graph(int grp, int member, size_t n_ops = 2)
+    {
+        if (spf_group_ctx(groups[(size_t)grp].h, member) != ctxs[(size_t)groups[(size_t)grp].ctx[(size_t)member]].h) ok = false;
+        return add_graph(groups[(size_t)grp].ctx[(size_t)member], n_ops);
+    }
+    // a job of group `grp`; slot >= 0: to be filed under merged[slot] by file_merged()
+    int add_job(int grp, int slot = -1, size_t n_ops = 2)
+    {
+        MGroup& m = groups[(size_t)grp];
+        spf_graph* g = nullptr;
+        if (spf_group_graph_create(m.h, &g) != SPF_OK) { ok = false; return -1; }
+        fill(g, n_ops);
+        ctxs[(size_t)m.ctx[0]].kids++; // (a job is built on member 0's context)
+        m.jobs++;
+        graphs.push_back({g, m.ctx[0], grp, true});
+        const int k = (int)graphs.size() - 1;
+        if (slot >= 0) m.slots[(size_t)slot].jobs.push_back(k);
+        handles.push_back({GRAPH, k});
+        step = "a job made";
+        check();
+        return k;
+    }
+    // what a run of the group leaves behind, filled in by hand: per member with filed jobs one merged graph on that member's
+    // context (spf_graph_create) and the list of its jobs
+    void file_merged()
+    {
+        for (MGroup& m : groups)
+            for (size_t s = 0; s < m.slots.size(); s++) {
+                if (m.slots[s].jobs.empty()) continue;
+                spf_group::Merged& mg = m.h->merged[s];
+                if (spf_graph_create(ctxs[(size_t)m.ctx[s]].h, &mg.graph) != SPF_OK) { ok = false; continue; }
+                for (int k : m.slots[s].jobs) {
+                    mg.jobs.push_back(graphs[(size_t)k].h);
+                    mg.shape.emplace_back(graphs[(size_t)k].h->nodes.size(), graphs[(size_t)k].h->outputs.size());
+                }
+                m.slots[s].graph = true;
+                ctxs[(size_t)m.ctx[s]].kids++;
+                merged_alive++;
+                step = "a merged graph filed";
+                check();
+            }
+    }
+    void drop_merged(MGroup& m, size_t s)
+    {
+        if (!m.slots[s].graph) return;
+        m.slots[s].graph = false;
+        m.slots[s].jobs.clear();
+        ctxs[(size_t)m.ctx[s]].kids--;
+        merged_alive--;
+    }
+    void maybe_free(MGroup& m)
+    {
+        if (m.held || m.jobs > 0 || m.freed) return;
+        m.freed = true;
+        for (size_t s = 0; s < m.slots.size(); s++) drop_merged(m, s);
+        for (int c : m.ctx) ctxs[(size_t)c].held = false;
+    }
+    void destroy(const Handle& h)
+    {
+        if (h.type == CTX) {
+            spf_destroy(ctxs[(size_t)h.idx].h);
+            ctxs[(size_t)h.idx].held = false;
+            step = "spf_destroy";
+        } else if (h.type == GROUP) {
+            MGroup& m = groups[(size_t)h.idx];
+            spf_group_destroy(m.h);
+            m.held = false;
+            maybe_free(m);
+            step = "spf_group_destroy";
+        } else {
+            MGraph& g = graphs[(size_t)h.idx];
+            spf_graph_destroy(g.h);
+            g.alive = false;
+            ctxs[(size_t)g.ctx].kids--;
+            if (g.grp >= 0) {
+                MGroup& m = groups[(size_t)g.grp];
+                for (size_t s = 0; s < m.slots.size(); s++) // the merged graph that held this job goes with it
+                    if (std::find(m.slots[s].jobs.begin(), m.slots[s].jobs.end(), h.idx) != m.slots[s].jobs.end()) drop_merged(m, s);
+                m.jobs--;
+                maybe_free(m);
+            }
+            step = "spf_graph_destroy";
+        }
+        check();
+    }
+    // the handles in the order given (indices into `handles`), then: nothing may be left
+    bool take_apart(const std::vector<size_t>& order)
+    {
+        for (size_t k : order) destroy(handles[k]); // (to the end after a mismatch too: the order is what is under test)
+        spf_live_counts got;
+        if (ok && (spf_live_objects(&got) != SPF_OK || got.contexts || got.groups || got.graphs || got.pools || got.values)) {
+            fprintf(stderr, "lifetimes: handles are left after the last destroy\n");
+            ok = false;
+        }
+        return ok;
+    }
+};
+
+struct LifetimeScenario {
+    const char* name;
+    std::function<bool(const spf_params&)> run;
+};
+
+std::vector<LifetimeScenario> lifetime_scenarios()
+{
+    std::vector<LifetimeScenario> v;
+    v.push_back({"context, graph: graph first", [](const spf_params& p) { Forest f(p); f.add_graph(f.add_ctx()); return f.take_apart({1, 0}); }});
+    v.push_back({"context, graph: context first", [](const spf_params& p) { Forest f(p); f.add_graph(f.add_ctx()); return f.take_apart({0, 1}); }});
+    v.push_back({"group, job: job first", [](const spf_params& p) { Forest f(p); f.add_job(f.add_group(1)); return f.take_apart({1, 0}); }});
+    v.push_back({"group, job: group first", [](const spf_params& p) { Forest f(p); f.add_job(f.add_group(1)); return f.take_apart({0, 1}); }});
+    static const size_t perms[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+    static const char* const perm_names[6] = {"group, two jobs: group, job 0, job 1", "group, two jobs: group, job 1, job 0", "group, two jobs: job 0, group, job 1",
+                                              "group, two jobs: job 0, job 1, group", "group, two jobs: job 1, group, job 0", "group, two jobs: job 1, job 0, group"};
+    for (int k = 0; k < 6; k++)
+        v.push_back({perm_names[k], [k](const spf_params& p) {
+                         Forest f(p);
+                         const int g = f.add_group(2);
+                         f.add_job(g);
+                         f.add_job(g);
+                         return f.take_apart({perms[k][0], perms[k][1], perms[k][2]});
+                     }});
+    // two jobs filed under merged[1], whose merged graph was made by spf_graph_create on member 1's context
+    auto merged = [](const spf_params& p, std::vector<size_t> order) {
+        Forest f(p);
+        const int g = f.add_group(2);
+        f.add_job(g, 1);
+        f.add_job(g, 1);
+        f.file_merged();
+        return f.take_apart(order);
+    };
+    v.push_back({"merged entry: its job first", [merged](const spf_params& p) { return merged(p, {1, 2, 0}); }});
+    v.push_back({"merged entry: the group first", [merged](const spf_params& p) { return merged(p, {0, 1, 2}); }});
+    v.push_back({"merged entry: the other job of the entry first", [merged](const spf_params& p) { return merged(p, {2, 0, 1}); }});
+    v.push_back({"borrowed member context: graph, then group, then graph", [](const spf_params& p) {
+                     Forest f(p);
+                     const int g = f.add_group(2);
+                     f.add_borrowed_graph(g, 1);
+                     f.add_borrowed_graph(g, 1);
+                     return f.take_apart({1, 0, 2});
+                 }});
+    return v;
+}
+
+// a seeded random forest, taken apart in a uniformly random order
+bool random_forest(const spf_params& p, Rng& r)
+{
+    Forest f(p);
+    const int n_ctx = 1 + (int)r.below(3), n_grp = (int)r.below(3);
+    for (int i = 0; i < n_ctx; i++) f.add_ctx();
+    for (int i = 0; i < n_grp; i++) f.add_group(1 + (int)r.below(3));
+    for (int i = 0; i < n_ctx; i++)
+        for (size_t k = r.below(7); k > 0; k--) f.add_graph(i, r.below(12));
+    for (int i = 0; i < n_grp; i++) {
+        const int members = (int)f.groups[(size_t)i].ctx.size();
+        for (size_t k = r.below(7); k > 0; k--) switch (r.below(3)) {
+            case 0: f.add_job(i, -1, r.below(12)); break;
+            case 1: f.add_job(i, (int)r.below((size_t)members), r.below(12)); break; // filed under a merged entry
+            default: f.add_borrowed_graph(i, (int)r.below((size_t)members), r.below(12)); break;
+            }
+    }
+    f.file_merged();
+    std::vector<size_t> order(f.handles.size());
+    for (size_t k = 0; k < order.size(); k++) order[k] = k;
+    for (size_t k = order.size(); k > 1; k--) std::swap(order[k - 1], order[r.below(k)]); // Fisher-Yates
+    return f.take_apart(order);
+}
+
 } // namespace
 
 int main(int argc, char** argv)
 {
+    if (argc > 1 && (!strncmp(argv[1], "--lifetimes", 11) || !strcmp(argv[1], "--selftest-lifetime"))) {
+        spf_params tiny;
+        spf_default_params(&tiny);
+        tiny.lwe_dimension = 2; tiny.polynomial_degree = 16; tiny.ks_radix_count = 2; tiny.tr_radix_count = 2; tiny.ss_radix_count = 2;
+        tiny.pbs_radix_log = 4; tiny.cbs_radix_count = 2;
+        if (!strcmp(argv[1], "--selftest-lifetime")) {
+            // the sanitizer sees this class of error: a group freed with a bare `delete`, past its reference count, and then its job
+            // destroyed — the run must die with a heap-use-after-free report in group_forget_graph (tests/test_lifetimes_host.py)
+            Forest f(tiny);
+            const int g = f.add_group(1);
+            const int job = f.add_job(g);
+            delete f.groups[(size_t)g].h;
+            spf_graph_destroy(f.graphs[(size_t)job].h);
+            printf("selftest: no report?!\n");
+            return 0;
+        }
+        if (!strcmp(argv[1], "--lifetimes")) { // --lifetimes [scenario index]: every scenario, or the one named
+            const std::vector<LifetimeScenario> all = lifetime_scenarios();
+            const long only = argc > 2 ? strtol(argv[2], nullptr, 10) : -1;
+            size_t done = 0;
+            for (size_t k = 0; k < all.size(); k++) {
+                if (only >= 0 && (size_t)only != k) continue;
+                const bool good = all[k].run(tiny);
+                printf("lifetimes %2zu: %s: %s\n", k, all[k].name, good ? "ok" : "MISMATCH");
+                fflush(stdout);
+                if (!good) return 1;
+                done++;
+            }
+            printf("lifetimes: %zu scenarios, live counts as the model after every step, nothing left, no sanitizer report\n", done);
+            return done ? 0 : 2;
+        }
+        if (!strcmp(argv[1], "--lifetimes-random")) { // --lifetimes-random <cases> <seed>
+            const uint64_t cases = argc > 2 ? strtoull(argv[2], nullptr, 10) : 1000;
+            Rng r(argc > 3 ? strtoull(argv[3], nullptr, 10) : 0x11FE71E5);
+            uint64_t destroyed = 0;
+            for (uint64_t it = 0; it < cases; it++) {
+                if (!random_forest(tiny, r)) { fprintf(stderr, "lifetimes-random: case %" PRIu64 " failed\n", it); return 1; }
+                destroyed++;
+            }
+            printf("lifetimes-random: %" PRIu64 " forests taken apart in random order, live counts as the model after every step, no sanitizer report\n", destroyed);
+            return 0;
+        }
+        fprintf(stderr, "unknown mode %s\n", argv[1]);
+        return 2;
+    }
     if (argc > 1 && !strcmp(argv[1], "--selftest-overflow")) {
         // the sanitizer really watches the library's host code: a caller that lies about `len` makes the parser read past the
         // allocation, and the run must die with a heap-buffer-overflow report (tests/test_asan_host.py expects exactly that)

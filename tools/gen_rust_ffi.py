@@ -5,7 +5,7 @@ cannot drift from the header: every struct, enum constant and function of the he
     python3 tools/gen_rust_ffi.py include/spf_hip.h > include/spf_hip.rs
     python3 tools/gen_rust_ffi.py --check-library spf_amd/lib/libspf_hip.so include/spf_hip.h     (nm -D == the header's functions)
 
-The parser handles exactly the C subset the header uses (opaque structs, two plain structs, enums, function prototypes with
+The parser handles exactly the C subset the header uses (opaque structs, plain structs, enums, function prototypes with
 pointer / integer / double arguments); anything else is an error, not a guess."""
 import re
 import subprocess
