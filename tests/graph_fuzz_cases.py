@@ -1,0 +1,462 @@
+"""The generator of the random differential tests of gate graphs (tests/test_graph_fuzz_host.py, tests/test_gpu_graph_fuzz.py):
+`draw_circuit(seed, P, profile) -> (RecordedCircuit, facts)`, deterministic in its arguments, numpy only.
+
+A circuit is a typed DAG over the five value kinds with every node kind of the executor in it: every operation of the table
+(spf_ops.hpp) that has a `spf_graph_op` and the four constructors (unpack, pack, blind rotation, public functional keyswitch).
+The generator BUILDS the layouts in which the executor's plan takes another branch (PATTERNS below) and, for each, records the
+claim that makes it one: which nodes have to share a group, lie in consecutive rows, or stand on different levels.  The claims
+are checked against `circuit_model.planned_levels`, the executor's own level passes, so `facts` names a pattern only if the
+circuit really holds it once the planner has moved the bootstraps and the conversion heads."""
+import numpy as np
+
+from spf_amd import FheOp, RecordedCircuit, TableOp, ValueKind
+from spf_amd.graph import NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from tests.blind_rotation_graph_cases import random_selectors
+from tests.circuit_model import kind_name, planned_levels
+
+PROFILES = ("full", "pushable", "small")
+CMUX_WIDTHS = (1, 2, 3, 5, 40, 70, 260, 300)           # test_gpu_fuzz.py's list: both CMUX kernels of the tuned context
+_WIDTH_SETS = ((260, 2, 5), (40, 70, 3), (300, 1))      # by seed % 3: three consecutive seeds draw every width
+MAX_NODES = 450                                         # "about 400": the 300-wide level and every pattern in one circuit
+MAX_NODES_SMALL = 60
+MAX_BOOTSTRAPS = 16                                     # of each of the three kinds
+
+DEFAULT_CASES, DEFAULT_SEED = 3, 20260701               # of tests/test_gpu_graph_fuzz.py (SPF_FUZZ_CASES / SPF_FUZZ_SEED)
+PUFKS_RADICES = ((4, 8), (4, 4), (5, 3))                # (log, count) on the tuned context: two hand-written, one generic
+
+
+def case_seed(seed, test, case) -> int:
+    """the circuit seed of case `case` of test number `test` of the GPU file (0 lowered, 1 pushed, 2 group jobs, 3 parameter sets)"""
+    return seed + 1000 * test + case
+
+
+def tuned_pufks_kind(case):
+    """the tuned context's operand kind: LWE0 in all cases but one in nine (an LWE1 key is 268 MB, a second per node on the oracle)"""
+    return ValueKind.LWE1 if case % 9 == 1 else ValueKind.LWE0
+
+
+L0, L1, GL, GG, GV = ValueKind.LWE0, ValueKind.LWE1, ValueKind.GLWE1, ValueKind.GGSW1, ValueKind.GLEV1
+
+PUFKS_PATTERNS = (
+    "pufks_rows_consecutive", "pufks_rows_scattered_with_repeats", "pufks_count_1", "pufks_count_2", "pufks_count_large",
+    "pufks_two_of_one_count_on_one_level", "pufks_result_as_table", "pufks_result_as_cmux_operand",
+    "pufks_result_as_unpack_source", "unpack_source_is_a_keyswitch_node")
+PATTERNS = tuple(f"cmux_width_{w}" for w in CMUX_WIDTHS) + (
+    "pbs_group_one_table", "pbs_group_tables_out_of_order", "pbs_table_computed_later_than_its_lwes",
+    "pbs_univariate_and_bivariate_on_one_level", "bivariate_both_inputs_consecutive", "bivariate_one_input_scattered",
+    "bivariate_same_node_twice", "bivariate_plaintext_bits_0", "bivariate_plaintext_bits_middle", "bivariate_plaintext_bits_63",
+    "slack_circuit_bootstrap_early_next_to_late", "slack_univariate_early_next_to_late", "slack_bivariate_early_next_to_late",
+    "sample_extract_users_on_two_levels", "keyswitch_users_on_two_levels", "sample_extract_is_also_an_output",
+    "keyswitch_is_also_an_output",
+    "unpack_two_calls_consecutive_sources", "unpack_two_calls_scattered_sources", "unpack_two_widths_on_one_level",
+    "unpack_source_is_a_pack",
+    "pack_operands_from_two_levels", "pack_operand_repeated", "pack_two_of_one_width_on_one_level", "pack_width_1",
+    "pack_width_2", "pack_width_above_8",
+    "rotation_bits_1", "rotation_bits_2", "rotation_bits_3", "rotation_bits_4", "rotation_log_stride_0",
+    "rotation_log_stride_larger", "rotation_chains_share_selectors", "rotation_chains_distinct_selectors",
+    "rotation_two_rotations_on_one_level", "rotation_selector_input", "rotation_selector_trivial",
+    "rotation_selector_circuit_bootstrap", "rotation_selector_scheme_switch_of_glev_cmux", "rotation_middle_step_used_elsewhere",
+    "cmux_glev_cmux_and_multiply_share_a_selector_on_one_level",
+    "output_of_every_kind", "output_given_twice", "outputs_every_node_of_the_last_level",
+    "trivial_of_every_kind_both_bits") + PUFKS_PATTERNS
+
+
+def words_of(P, kind) -> int:
+    return {L0: P.lwe_n + 1, L1: P.k * P.N + 1, GL: P.glwe_len, GG: 2 * P.cbs_ggsw_fft_len, GV: P.cbs_count * P.glwe_len}[ValueKind(kind)]
+
+
+def random_value(rng, P, kind) -> np.ndarray:
+    """uniform 64-bit words; GGSW: complex values at 2^58 (blind_rotation_graph_cases.random_selectors)"""
+    if ValueKind(kind) == GG:
+        return random_selectors(int(rng.integers(1 << 62)), 1, P)[0]
+    return rng.integers(0, 1 << 64, size=words_of(P, kind), dtype=np.uint64)
+
+
+def refill_inputs(rec, P, seed):
+    """new random contents in the input arrays of `rec`, in place: the same graph on new data"""
+    rng = np.random.default_rng([0x6A6, seed])
+    for i, op in enumerate(rec.op):
+        if op == -1:
+            new = random_value(rng, P, rec.kind[i])
+            rec.host[i].view(np.uint64).reshape(-1)[...] = new.view(np.uint64).reshape(-1)
+
+
+def group_key(rec, levels, i):
+    """(level, kind, parameter) as plan() keys its groups"""
+    op = rec.op[i]
+    if op == NODE_UNPACK:
+        return levels[i], op, rec._unpack_width[i]
+    if op == NODE_PACK:
+        return levels[i], op, len(rec.inputs[i])
+    if op == NODE_PUFKS:
+        return levels[i], op, len(rec.inputs[i]) | rec.kind[rec.inputs[i][0]] << 32
+    return levels[i], op, rec.param[i]
+
+
+def groups_of(rec, levels) -> dict:
+    """{group key: members in node order}: a group's results are consecutive rows in that order"""
+    out = {}
+    for i, op in enumerate(rec.op):
+        if op >= 0:
+            out.setdefault(group_key(rec, levels, i), []).append(i)
+    return out
+
+
+class _Builder:
+    def __init__(self, seed, P, profile):
+        self.P, self.profile = P, profile
+        self.rng = np.random.default_rng([0x6A5, seed, P.N, P.k, P.lwe_n, PROFILES.index(profile)])
+        self.rec = RecordedCircuit(P.N)
+        self.pool = {k: [] for k in ValueKind}
+        self.claims = []        # (name, f(view) -> bool)
+        self.keep = []          # nodes that are outputs whatever the sample draws
+        self.lvl = []
+
+    # ---- nodes
+    def _note(self, node):
+        self.pool[ValueKind(self.rec.kind[node])].append(node)
+        while len(self.lvl) <= node:    # as soon as possible: what plan() starts from
+            i = len(self.lvl)
+            self.lvl.append(1 + max((self.lvl[j] for j in self.rec.inputs[i]), default=0) if self.rec.op[i] >= 0 else 0)
+        return node
+
+    def older(self, kind, level):
+        """the nodes of a kind that are ready by `level`"""
+        return [i for i in self.pool[ValueKind(kind)] if self.lvl[i] <= level]
+
+    def inp(self, kind):
+        return self._note(self.rec.add_input(kind, random_value(self.rng, self.P, kind)))
+
+    def triv(self, kind, bit):
+        return self._note(self.rec.add_trivial(kind, bit))
+
+    def op(self, op, ins, param=0):
+        return self._note(self.rec.add_op(op, ins, param))
+
+    def unpack(self, src, w):
+        bits = self.rec.add_unpack(src, w)
+        for b in bits:
+            self._note(b)
+        return bits
+
+    def pack(self, nodes):
+        return self._note(self.rec.add_pack(nodes))
+
+    def pufks(self, nodes):
+        return self._note(self.rec.add_public_functional_keyswitch(nodes))
+
+    def rotation(self, acc, sels, log_stride=0):
+        first = len(self.rec.op)
+        last = self.rec.add_blind_rotation(acc, sels, log_stride)
+        self._note(last)        # (the steps before it are drawn as operands only on purpose: most chains stay whole)
+        return list(range(first, last + 1))
+
+    def pick(self, kind, count=None, among=None):
+        src = self.pool[ValueKind(kind)] if among is None else among
+        at = self.rng.integers(0, len(src), size=1 if count is None else count)
+        return src[int(at[0])] if count is None else [src[int(a)] for a in at]
+
+    def index(self):
+        return int(self.rng.integers(0, self.P.N))
+
+    def claim(self, name, fn=None):
+        self.claims.append((name, fn if fn is not None else (lambda v: True)))
+
+
+class _View:
+    """the finished circuit as the planner sees it: what the claims are checked against"""
+
+    def __init__(self, rec):
+        self.rec = rec
+        self.level = planned_levels(rec)
+        self.asap = [0] * len(rec.op)
+        for i, op in enumerate(rec.op):
+            if op >= 0:
+                self.asap[i] = 1 + max((self.asap[j] for j in rec.inputs[i]), default=0)
+        self.groups = groups_of(rec, self.level)
+        self.users = [[] for _ in rec.op]
+        for i, ins in enumerate(rec.inputs):
+            for j in set(ins):
+                self.users[j].append(i)
+
+    def key(self, i):
+        return group_key(self.rec, self.level, i)
+
+    def one_group(self, nodes):
+        return len({self.key(i) for i in nodes}) == 1
+
+    def whole_group(self, nodes):
+        """the nodes are a group, all of it"""
+        return self.one_group(nodes) and sorted(self.groups[self.key(nodes[0])]) == sorted(nodes)
+
+    def rows(self, nodes):
+        """the rows lie consecutively in this order: successive members of one group"""
+        if not self.one_group(nodes):
+            return False
+        members = self.groups[self.key(nodes[0])]
+        at = [members.index(i) for i in nodes]
+        return all(b == a + 1 for a, b in zip(at, at[1:]))
+
+    def user_levels(self, i):
+        return {self.level[u] for u in self.users[i]}
+
+    def moved_next_to_late(self, early, late):
+        """ready early and not needed for at least two levels, run on the level of one that is ready late"""
+        return self.asap[early] + 2 <= self.level[early] == self.level[late] and self.asap[late] >= self.asap[early] + 2
+
+
+def _sources(b, n_glwe, n_l1, n_l0, n_ggsw, n_glev, trivials=True):
+    s = {GL: [b.inp(GL) for _ in range(n_glwe)], L1: [b.inp(L1) for _ in range(n_l1)], L0: [b.inp(L0) for _ in range(n_l0)],
+         GG: [b.inp(GG) for _ in range(n_ggsw)], GV: [b.inp(GV) for _ in range(n_glev)]}
+    t = {(k, bit): b.triv(k, bit) for k in (ValueKind if trivials else ()) for bit in (0, 1)}
+    if trivials:
+        b.claim("trivial_of_every_kind_both_bits", lambda v: {(b.rec.kind[i], b.rec.param[i]) for i, op in enumerate(b.rec.op) if op == -2}
+                == {(int(k), bit) for k in ValueKind for bit in (0, 1)})
+    return s, t
+
+
+def _outputs(b, sample):
+    """the kept nodes (one of them twice), every node of the last level, every node nobody uses, a random sample of the rest"""
+    rec = b.rec
+    v = _View(rec)
+    top = max(v.level)
+    last = [i for i, op in enumerate(rec.op) if op >= 0 and v.level[i] == top]
+    unused = [i for i, op in enumerate(rec.op) if op >= 0 and not v.users[i]]
+    rest = [i for i, op in enumerate(rec.op) if op >= 0]
+    drawn = [rest[int(a)] for a in b.rng.integers(0, len(rest), size=min(sample, len(rest)))]
+    order, seen = [], set()
+    for i in b.keep + last + unused + drawn:
+        if i not in seen:
+            seen.add(i)
+            order.append(i)
+    order.insert(len(order) // 2, order[0])                 # one node given as an output twice
+    for i in order:
+        rec.add_output(i, ValueKind(rec.kind[i]))
+    b.claim("output_given_twice", lambda w: len(rec.outputs) > len(set(rec.outputs)))
+    b.claim("output_of_every_kind", lambda w: {rec.kind[i] for i in rec.outputs} == {int(k) for k in ValueKind})
+    b.claim("outputs_every_node_of_the_last_level", lambda w: set(last) <= set(rec.outputs))
+
+
+def _draw_full(b, with_pufks, pufks_kind, width_set):
+    P, rng, rec = b.P, b.rng, b.rec
+    log_n = P.N.bit_length() - 1
+    s, t = _sources(b, 6, 3, 4, 2, 2)
+    G, S, V = s[GL], s[GG], s[GV]
+
+    # ---- conversions: SampleExtract / KeyswitchL1toL0 heads and the selectors of every origin
+    # (cbs_a and cbs_b head the longest path of the circuit, below: the planner cannot move them, and every circuit bootstrap
+    # that is ready by their level runs with them)
+    se0 = b.op(FheOp.SampleExtract, [G[0]], b.index())
+    cbs_a = b.op(FheOp.CircuitBootstrap, [b.op(FheOp.KeyswitchL1toL0, [se0])])
+    uni_one = [b.op(TableOp.PBS_UNIVARIATE, [x, G[2]]) for x in s[L0]]       # ONE table, ready at once, uni_one[3] needed at once
+    cbs_b = b.op(FheOp.CircuitBootstrap, [b.op(FheOp.KeyswitchL1toL0, [uni_one[3]])])
+    ks_out = b.op(FheOp.KeyswitchL1toL0, [s[L1][0]])        # also an output; two users: a bootstrap now, table bootstraps late
+    se_out = b.op(FheOp.SampleExtract, [G[1]], b.index())   # also an output
+    cbs_c = [b.op(FheOp.CircuitBootstrap, [ks_out]), b.op(FheOp.CircuitBootstrap, [b.op(FheOp.KeyswitchL1toL0, [se_out])])]
+    glev_sel = b.op(FheOp.GlevCMux, [S[0], V[0], V[1]])
+    sel_ss = b.op(FheOp.SchemeSwitch, [glev_sel])
+    b.keep += [ks_out, se_out, glev_sel, sel_ss, cbs_a]
+    b.claim("sample_extract_is_also_an_output", lambda v: se_out in rec.outputs and v.users[se_out])
+    b.claim("keyswitch_is_also_an_output", lambda v: ks_out in rec.outputs and v.users[ks_out])
+    selectors = S + [t[GG, 0], t[GG, 1], cbs_a, cbs_b, sel_ss] + cbs_c
+
+    # ---- blind rotation: accumulators of level 0, so every chain starts on level 1
+    stride = min(2, log_n - 3)                             # 3 bits + stride within log2 N at N = 16
+    x_chain = b.rotation(G[2], [S[0], t[GG, 1]])
+    y_chain = b.rotation(G[3], [S[0], t[GG, 1]])
+    w_chain = b.rotation(G[4], [S[1], t[GG, 0]])
+    one_bit = b.rotation(G[5], [t[GG, 1]], stride)
+    three = b.rotation(G[2], [cbs_a, sel_ss, S[1]], stride)
+    four = b.rotation(G[3], [S[0], cbs_b, t[GG, 0], sel_ss])
+    mid_user = b.op(FheOp.Not, [three[1]])
+    b.keep += [x_chain[-1], y_chain[-1], w_chain[-1], one_bit[-1], three[-1], four[-1], mid_user]
+    for chain in (one_bit, x_chain, three, four):
+        b.claim(f"rotation_bits_{len(chain)}", lambda v, chain=chain: all(rec.inputs[m][1] == m - 1 for m in chain[1:]))
+    b.claim("rotation_log_stride_0", lambda v: rec.param[four[0]] == 1)
+    b.claim("rotation_log_stride_larger", lambda v: stride > 0)
+    b.claim("rotation_chains_share_selectors", lambda v: all(v.one_group([x_chain[i], y_chain[i]]) for i in range(2)))
+    b.claim("rotation_chains_distinct_selectors", lambda v: all(v.one_group([x_chain[i], w_chain[i]]) for i in range(2)))
+    b.claim("rotation_two_rotations_on_one_level", lambda v: v.level[one_bit[0]] == v.level[x_chain[0]] and rec.param[one_bit[0]] != rec.param[x_chain[0]])
+    origin = {"input": -1, "trivial": -2, "circuit_bootstrap": int(FheOp.CircuitBootstrap), "scheme_switch_of_glev_cmux": int(FheOp.SchemeSwitch)}
+    for name, op in origin.items():
+        b.claim(f"rotation_selector_{name}", lambda v, op=op: any(rec.op[rec.inputs[m][0]] == op for m in three + four))
+    b.claim("rotation_middle_step_used_elsewhere", lambda v: rec.op[three[1]] == NODE_ROT_CMUX and len(v.users[three[1]]) >= 2)
+
+    # ---- unpack and pack
+    w_a, w_b = 2, 3
+    n_a, n_b = b.op(FheOp.Not, [G[0]]), b.op(FheOp.Not, [G[1]])          # two rows of one group: consecutive sources
+    un_c = [b.unpack(n_a, w_a), b.unpack(n_b, w_a)]
+    un_other = b.unpack(n_a, w_b)
+    un_s = [b.unpack(G[4], w_a), b.unpack(G[1], w_a)]                      # inputs in descending order: scattered sources
+    pack_1 = b.pack([G[5]])
+    pack_2 = [b.pack([G[0], n_a]), b.pack([n_b, n_b])]
+    pack_9 = b.pack([G[2], n_a] + b.pick(GL, 7 + int(rng.integers(0, 4))))
+    un_p = b.unpack(pack_2[0], w_a)
+    b.keep += [pack_1, pack_9, pack_2[1]] + un_c[1] + un_other + un_s[0] + un_p
+    b.claim("unpack_two_calls_consecutive_sources", lambda v: v.whole_group(un_c[0] + un_c[1]) and v.rows([n_a, n_b]))
+    b.claim("unpack_two_calls_scattered_sources", lambda v: v.whole_group(un_s[0] + un_s[1]))
+    b.claim("unpack_two_widths_on_one_level", lambda v: v.level[un_other[0]] == v.level[un_c[0][0]])
+    b.claim("unpack_source_is_a_pack", lambda v: rec.op[rec.inputs[un_p[0]][0]] == NODE_PACK)
+    b.claim("pack_operands_from_two_levels", lambda v: v.level[G[0]] != v.level[n_a])
+    b.claim("pack_operand_repeated", lambda v: len(set(rec.inputs[pack_2[1]])) == 1)
+    b.claim("pack_two_of_one_width_on_one_level", lambda v: v.one_group(pack_2))
+    b.claim("pack_width_1", lambda v: len(rec.inputs[pack_1]) == 1)
+    b.claim("pack_width_2", lambda v: len(rec.inputs[pack_2[0]]) == 2)
+    b.claim("pack_width_above_8", lambda v: len(rec.inputs[pack_9]) > 8)
+
+    # ---- the CMUX family: a base on one level, then levels of the drawn widths, each reading the level before it
+    base = [b.op(FheOp.Not, [b.op(FheOp.MulXN, [b.op(FheOp.GlweAdd, [G[i], G[i + 1]])], int(rng.integers(0, 2 * P.N)))]) for i in (0, 2)]
+    base += [b.op(FheOp.GlweAdd, [x_chain[-1], n_a]), b.op(FheOp.MulXN, [w_chain[-1]], int(rng.integers(0, 2 * P.N)))]
+    assert {b.lvl[i] for i in base} == {3} and all(b.lvl[q] <= 3 for q in selectors)
+    # a circuit bootstrap that is ready after cbs_a's level and first needed in the last level
+    cbs_early = b.op(FheOp.CircuitBootstrap, [b.op(FheOp.KeyswitchL1toL0, [b.op(FheOp.SampleExtract, [y_chain[-1]], b.index())])])
+    widths = list(width_set) + [2, 3, 1][len(width_set) - 2:]
+    prev, glev_prev, levels = base, V[0], []
+    for depth, width in enumerate(widths):
+        last_level = depth == len(widths) - 1
+        older = b.older(GL, b.lvl[prev[0]])
+        # the longest path runs through the first node of every level; at its head both early circuit bootstraps
+        sel = cbs_a if depth == 0 else b.pick(GG, among=selectors)
+        trio = [b.op(FheOp.CMux, [sel, prev[0], prev[1]]), b.op(FheOp.GlevCMux, [sel, glev_prev, t[GV, depth % 2]]),
+                b.op(FheOp.MultiplyGgswGlwe, [sel, prev[0]])]
+        if depth == 0:
+            b.claim("cmux_glev_cmux_and_multiply_share_a_selector_on_one_level", lambda v, trio=trio: len({v.level[i] for i in trio}) == 1)
+        glev_prev = trio[1]
+        new = [trio[0]]
+        if depth == 0:
+            new.append(b.op(FheOp.CMux, [cbs_b, prev[1], G[5]]))
+        if last_level:                                      # the two late selectors select something
+            new += [b.op(FheOp.CMux, [q, b.pick(GL, among=prev), b.pick(GL, among=older)]) for q in (cbs_early, cbs_late)]
+        while len(new) < width:
+            new.append(b.op(FheOp.CMux, [b.pick(GG, among=selectors), b.pick(GL, among=prev), b.pick(GL, among=older)]))
+        others = [b.op(FheOp.Not, [b.pick(GL, among=prev)])]
+        if depth in (0, 2):
+            others += [b.op(FheOp.GlweAdd, [b.pick(GL, among=prev), b.pick(GL, among=older)]),
+                       b.op(FheOp.MulXN, [b.pick(GL, among=prev)], int(rng.integers(0, 2 * P.N)))]
+        levels.append(new)
+        b.claim(f"cmux_width_{len(new)}", lambda v, new=new: v.whole_group(new))
+        if depth == 0:      # conversions in the middle of the graph: ready late, used next to the early one in the last level
+            se_mid = b.op(FheOp.SampleExtract, [new[-1]], b.index())   # two users, which the planner pulls to different levels
+            cbs_late = b.op(FheOp.CircuitBootstrap, [b.op(FheOp.KeyswitchL1toL0, [se_mid])])
+            uni_lwe_late = b.op(FheOp.KeyswitchL1toL0, [se_mid])
+        prev = new + [trio[2]] + others
+    b.keep += [glev_prev]
+    b.claim("slack_circuit_bootstrap_early_next_to_late", lambda v: v.moved_next_to_late(cbs_early, cbs_late))
+
+    # ---- table bootstraps.  tables: inputs, and values computed in the last level (later than every LWE operand)
+    deep = levels[-1]
+    t_late = [b.op(FheOp.MulXN, [deep[0]], int(rng.integers(1, 2 * P.N))), deep[-1]]    # a MulXN and a CMux result
+    uni_late = b.op(TableOp.PBS_UNIVARIATE, [uni_lwe_late, G[2]])    # ready in the middle, not needed: run with the last ones
+    ks_rows = [b.op(FheOp.KeyswitchL1toL0, [u]) for u in uni_one[:3]]                   # one keyswitch group: consecutive rows
+    p_mid = int(rng.integers(1, 63))
+    biv_c = [b.op(TableOp.PBS_BIVARIATE, [ks_rows[i], ks_rows[i + 1], G[3]], p_mid) for i in (0, 1)]
+    biv_s = [b.op(TableOp.PBS_BIVARIATE, [ks_rows[i], x, G[2]], 0) for i, x in ((0, s[L0][3]), (1, t[L0, 1]))]
+    biv_same = [b.op(TableOp.PBS_BIVARIATE, [x, x, t_late[0]], 63) for x in (ks_out, s[L0][0])]
+    uni_each = [b.op(TableOp.PBS_UNIVARIATE, [x, tab]) for x, tab in zip((s[L0][1], t[L0, 0], ks_out), (t_late[0], t_late[1], t_late[0]))]
+    b.keep += uni_one + [uni_late] + ks_rows + biv_c + biv_s + biv_same + uni_each
+    b.claim("pbs_group_one_table", lambda v: v.whole_group(uni_one))
+    b.claim("pbs_group_tables_out_of_order", lambda v: v.one_group(uni_each) and rec.inputs[uni_each[0]][1] > rec.inputs[uni_each[1]][1])
+    b.claim("pbs_table_computed_later_than_its_lwes", lambda v: all(v.level[rec.inputs[u][1]] > v.level[rec.inputs[u][0]] for u in uni_each)
+            and rec.op[t_late[0]] == int(FheOp.MulXN) and rec.op[t_late[1]] == int(FheOp.CMux))
+    b.claim("pbs_univariate_and_bivariate_on_one_level", lambda v: v.level[uni_each[0]] == v.level[biv_same[0]])
+    b.claim("bivariate_both_inputs_consecutive", lambda v: v.whole_group(biv_c) and v.rows(ks_rows))
+    b.claim("bivariate_one_input_scattered", lambda v: v.whole_group(biv_s) and v.rows(ks_rows[:2]) and not v.one_group([s[L0][3], t[L0, 1]]))
+    b.claim("bivariate_same_node_twice", lambda v: v.whole_group(biv_same))
+    b.claim("bivariate_plaintext_bits_0", lambda v: rec.param[biv_s[0]] == 0)
+    b.claim("bivariate_plaintext_bits_middle", lambda v: 0 < p_mid < 63)
+    b.claim("bivariate_plaintext_bits_63", lambda v: rec.param[biv_same[0]] == 63)
+    b.claim("slack_univariate_early_next_to_late", lambda v: v.moved_next_to_late(uni_late, uni_each[0]))
+    b.claim("slack_bivariate_early_next_to_late", lambda v: v.moved_next_to_late(biv_c[0], biv_same[0]))
+    b.claim("sample_extract_users_on_two_levels", lambda v: len(v.user_levels(se_mid)) > 1)
+    b.claim("keyswitch_users_on_two_levels", lambda v: len(v.user_levels(ks_out)) > 1)
+
+    # ---- public functional keyswitch: ONE operand kind in a circuit (a context holds one such key)
+    if with_pufks:
+        kind = ValueKind(pufks_kind)
+        if kind == L0:
+            pair = [b.op(FheOp.KeyswitchL1toL0, [s[L1][i]]) for i in (1, 2)]            # one keyswitch group's outputs
+            rows = s[L0] + [t[L0, 0], t[L0, 1], ks_out] + pair       # (not ks_rows: a user down here would hold one of them back)
+        else:
+            pair = b.unpack(G[3], w_b)[:2]                           # the first bits of one unpack call
+            rows = s[L1] + [t[L1, 0], t[L1, 1], se0, se_out] + un_s[1] + uni_one + pair   # (level 1 at most: the CMux below
+            #                                                                               stays under the levels above)
+        large = min(P.N, 33 + int(rng.integers(0, 8)))
+        k_pair = b.pufks(pair)
+        k_one = b.pufks([b.pick(kind, among=rows)])
+        drawn = b.pick(kind, large - 1, among=rows)
+        drawn.insert(int(rng.integers(1, large)), drawn[0])
+        k_large = [b.pufks(drawn), b.pufks([drawn[int(i)] for i in rng.permutation(large)])]
+        as_table = b.op(TableOp.PBS_UNIVARIATE, [s[L0][2], k_pair])
+        as_operand = b.op(FheOp.CMux, [S[1], k_one, k_large[0]])
+        as_source = b.unpack(k_large[1], w_b)
+        b.keep += [k_pair, k_one, as_table, as_operand] + k_large + as_source
+        b.claim("pufks_rows_consecutive", lambda v: v.whole_group([k_pair]) and v.rows(pair))
+        b.claim("pufks_rows_scattered_with_repeats", lambda v: len(set(drawn)) < len(drawn) and len({v.level[i] for i in drawn}) > 1)
+        b.claim("pufks_count_1", lambda v: len(rec.inputs[k_one]) == 1)
+        b.claim("pufks_count_2", lambda v: len(rec.inputs[k_pair]) == 2)
+        b.claim("pufks_count_large", lambda v: len(rec.inputs[k_large[0]]) >= min(P.N, 33))
+        b.claim("pufks_two_of_one_count_on_one_level", lambda v: v.whole_group(k_large))
+        b.claim("pufks_result_as_table", lambda v: rec.op[rec.inputs[as_table][1]] == NODE_PUFKS)
+        b.claim("pufks_result_as_cmux_operand", lambda v: all(rec.op[j] == NODE_PUFKS for j in rec.inputs[as_operand][1:]))
+        b.claim("pufks_result_as_unpack_source", lambda v: rec.op[rec.inputs[as_source[0]][0]] == NODE_PUFKS)
+        b.claim("unpack_source_is_a_keyswitch_node", lambda v: rec.op[rec.inputs[as_source[0]][0]] == NODE_PUFKS)
+
+
+def _draw_small(b, with_pufks, pufks_kind):
+    """every node kind once or twice, nothing wider than 3, for random parameter sets"""
+    P, rng = b.P, b.rng
+    s, t = _sources(b, 3, 1, 2, 1, 1)
+    G, S, V = s[GL], s[GG], s[GV]
+    se = b.op(FheOp.SampleExtract, [G[0]], b.index())
+    l0 = [b.op(FheOp.KeyswitchL1toL0, [se]), b.op(FheOp.KeyswitchL1toL0, [s[L1][0]])]
+    cbs = [b.op(FheOp.CircuitBootstrap, [x]) for x in l0]
+    glev = b.op(FheOp.GlevCMux, [cbs[0], V[0], t[GV, 1]])
+    sel_ss = b.op(FheOp.SchemeSwitch, [glev])
+    sels = S + cbs + [sel_ss, t[GG, 0], t[GG, 1]]
+    vals = list(G) + [t[GL, 1]]
+    for _ in range(2):
+        vals += [b.op(FheOp.CMux, [b.pick(GG, among=sels)] + b.pick(GL, 2, among=vals)) for _ in range(int(rng.integers(1, 4)))]
+        vals += [b.op(FheOp.Not, [b.pick(GL, among=vals)]), b.op(FheOp.GlweAdd, b.pick(GL, 2, among=vals)),
+                 b.op(FheOp.MulXN, [b.pick(GL, among=vals)], int(rng.integers(0, 2 * P.N))),
+                 b.op(FheOp.MultiplyGgswGlwe, [b.pick(GG, among=sels), b.pick(GL, among=vals)])]
+    n_bits = int(rng.integers(1, 4))
+    rot = b.rotation(b.pick(GL, among=vals), b.pick(GG, n_bits, among=sels), int(rng.integers(0, P.N.bit_length() - n_bits)))
+    bits = b.unpack(rot[-1], int(rng.integers(1, 4)))
+    packed = b.pack(b.pick(GL, int(rng.integers(1, 4)), among=vals))
+    l0 += [b.op(FheOp.KeyswitchL1toL0, [x]) for x in bits[:2]]
+    uni = b.op(TableOp.PBS_UNIVARIATE, [b.pick(L0, among=l0 + s[L0]), packed])
+    biv = b.op(TableOp.PBS_BIVARIATE, [b.pick(L0, among=l0), b.pick(L0, among=s[L0] + [t[L0, 1]]), b.pick(GL, among=vals)],
+               int(rng.choice((0, 63, int(rng.integers(1, 63))))))
+    b.keep += [uni, biv, rot[-1], packed, glev, sel_ss, l0[-1]]
+    if with_pufks:
+        rows = l0 + s[L0] + [t[L0, 0]] if ValueKind(pufks_kind) == L0 else bits + s[L1] + [uni, biv, se, t[L1, 1]]
+        k = b.pufks(b.pick(pufks_kind, int(rng.integers(1, 4)), among=rows))
+        b.keep += [k, b.op(FheOp.CMux, [b.pick(GG, among=sels), k, b.pick(GL, among=vals)])]
+
+
+def draw_circuit(seed, P, profile, pufks_kind=None):
+    """-> (RecordedCircuit, facts).  facts: "patterns": the names of PATTERNS the circuit holds (claimed by the construction and
+    confirmed on the planned levels); "refused": claimed but not confirmed; "pufks_kind": the operand kind of its public
+    functional keyswitch nodes (drawn unless given; None without such nodes); "nodes" / "groups": counts by kind name."""
+    assert profile in PROFILES
+    b = _Builder(seed, P, profile)
+    with_pufks = profile != "pushable"
+    if with_pufks and pufks_kind is None:
+        pufks_kind = L0 if b.rng.random() < 0.7 else L1
+    pufks_kind = ValueKind(pufks_kind) if with_pufks else None
+    if profile == "small":
+        _draw_small(b, with_pufks, pufks_kind)
+    else:
+        _draw_full(b, with_pufks, pufks_kind, _WIDTH_SETS[seed % 3])
+    _outputs(b, 8 if profile == "small" else 30)
+    v = _View(b.rec)
+    held = [name for name, fn in b.claims if fn(v)]
+    nodes, groups = {}, {}
+    for i in range(len(b.rec.op)):
+        name = kind_name(b.rec, i).split("(")[0]
+        nodes[name] = nodes.get(name, 0) + 1
+    for key, members in v.groups.items():
+        name = kind_name(b.rec, members[0])
+        groups[name] = groups.get(name, 0) + 1
+    return b.rec, {"patterns": sorted(set(held)), "refused": sorted({n for n, _ in b.claims} - set(held)), "pufks_kind": pufks_kind,
+                   "nodes": nodes, "groups": groups, "levels": max(v.level), "seed": seed, "profile": profile}

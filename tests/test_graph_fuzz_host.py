@@ -1,0 +1,234 @@
+"""The host side of the random differential tests of gate graphs (tests/test_gpu_graph_fuzz.py): the generator
+(tests/graph_fuzz_cases.py) draws what it says it draws, and the model that is the GPU tests' only expectation
+(tests/circuit_model.py) equals the compositions somebody wrote by hand for the kinds' own tests.  No device."""
+import time
+
+import numpy as np
+import pytest
+
+import oracle as O
+import spf_amd
+from spf_amd import FheOp, TableOp, ValueKind
+from spf_amd import graph as G
+from tests import blind_rotation_graph_cases as BR
+from tests import circuit_model as M
+from tests import graph_fuzz_cases as F
+from tests import pbs_graph_cases as K
+from tests import pufks_cases as PC
+from tests.polyref_cases import key_fft
+from tests.util import random_glwe, random_lwe_batch
+
+NODE_CONSTANTS = {name: getattr(G, name) for name in dir(G) if name.startswith("NODE_")}
+
+
+def default_circuits(which, profile):
+    """the circuits the GPU file draws on a context at the default count and seed"""
+    P = K.keys_of(which)[0]
+    test = {"full": 0, "pushable": 1}[profile]
+    for case in range(F.DEFAULT_CASES):
+        kind = F.tuned_pufks_kind(case) if which == "tuned" and profile == "full" else None
+        yield F.draw_circuit(F.case_seed(F.DEFAULT_SEED, test, case), P, profile, kind)
+
+
+def test_the_generator_is_deterministic():
+    P = K.TEST1
+    for profile in F.PROFILES:
+        a, fa = F.draw_circuit(77, P, profile)
+        b, fb = F.draw_circuit(77, P, profile)
+        assert (a.op, a.kind, a.param, a.inputs, a.outputs) == (b.op, b.kind, b.param, b.inputs, b.outputs) and fa == fb
+        assert all(x is None and y is None or np.array_equal(x, y) for x, y in zip(a.host, b.host))
+        c, _ = F.draw_circuit(78, P, profile)
+        assert (a.op, a.param, a.inputs) != (c.op, c.param, c.inputs)
+
+
+@pytest.mark.parametrize("profile", F.PROFILES)
+@pytest.mark.parametrize("which", K.CONTEXTS)
+def test_every_circuit_is_one_recorded_circuit_accepts(which, profile):
+    """replayed through RecordedCircuit's own checks (from_arrays calls every builder again); operands precede their users;
+    the node and bootstrap budgets hold; a circuit has public functional keyswitch nodes of ONE operand kind, or none"""
+    P = K.keys_of(which)[0]
+    for seed in range(5):
+        rec, facts = F.draw_circuit(seed, P, profile)
+        assert all(j < i for i, ins in enumerate(rec.inputs) for j in ins)
+        again = spf_amd.RecordedCircuit.from_arrays(rec.arrays(), rec.kind, rec.host, P.N)
+        assert (again.op, again.kind, again.param, again.inputs) == (rec.op, rec.kind, rec.param, rec.inputs)
+        assert sorted(set(rec.outputs)) == again.outputs
+        assert len(rec.op) <= (F.MAX_NODES_SMALL if profile == "small" else F.MAX_NODES), len(rec.op)
+        for kind in ("CircuitBootstrap", "PBS_UNIVARIATE", "PBS_BIVARIATE"):
+            assert 0 < facts["nodes"][kind] <= F.MAX_BOOTSTRAPS
+        rows = {rec.kind[rec.inputs[i][0]] for i, op in enumerate(rec.op) if op == G.NODE_PUFKS}
+        assert rows == (set() if profile == "pushable" else {int(facts["pufks_kind"])})
+        assert all(rec.param[i] < P.N for i, op in enumerate(rec.op) if op in (int(FheOp.SampleExtract), G.NODE_UNPACK))
+        if profile == "small":
+            widths = [len(rec.inputs[i]) for i, op in enumerate(rec.op) if op in (G.NODE_PACK, G.NODE_PUFKS)]
+            assert max(widths + list(rec._unpack_width.values())) <= 3
+
+
+@pytest.mark.parametrize("which", K.CONTEXTS)
+def test_the_default_seeds_reach_every_pattern_and_every_node_kind(which):
+    """every name of PATTERNS is held (claimed by the construction AND confirmed on the planned levels) by a default circuit of
+    each context, lowered and pushed; every FheOp, TableOp and NODE_* constant of spf_amd.graph is a node of every one"""
+    assert len(NODE_CONSTANTS) >= 4 and len(list(FheOp)) + len(list(TableOp)) >= 12
+    kinds = {int(op) for op in FheOp} | {int(op) for op in TableOp} | set(NODE_CONSTANTS.values())
+    for profile, left_out in (("full", set()), ("pushable", set(F.PUFKS_PATTERNS))):
+        reached = set()
+        for rec, facts in default_circuits(which, profile):
+            reached |= set(facts["patterns"])
+            missing = kinds - set(rec.op) - ({G.NODE_PUFKS} if profile == "pushable" else set())
+            assert not missing, (profile, facts["seed"], missing)
+            assert {-1, -2} <= set(rec.op)
+        assert set(F.PATTERNS) - left_out <= reached, (profile, sorted(set(F.PATTERNS) - left_out - reached))
+        assert reached <= set(F.PATTERNS)
+    P = K.keys_of(which)[0]
+    for seed in range(3):                   # the small profile: every kind, on any parameter set
+        rec, _ = F.draw_circuit(seed, P, "small")
+        assert kinds <= set(rec.op), kinds - set(rec.op)
+
+
+def test_planned_levels_on_a_graph_whose_levels_are_known():
+    """the level passes of plan() on the shapes its comments name: a bootstrap with slack joins the one that must run soonest, a
+    keyswitch head is pulled up against its first user"""
+    rec = spf_amd.RecordedCircuit(16)
+    x, l1, sel = rec.add_input(ValueKind.GLWE1, np.zeros(1)), rec.add_input(ValueKind.LWE1, np.zeros(1)), rec.add_input(ValueKind.GGSW1, np.zeros(1))
+    ks = rec.add_op(FheOp.KeyswitchL1toL0, [l1])                        # ready at 1, first user at 4: pulled to 3
+    a = rec.add_op(FheOp.Not, [rec.add_op(FheOp.Not, [rec.add_op(FheOp.CMux, [sel, x, x])])])     # levels 1, 2, 3
+    late = rec.add_op(FheOp.CircuitBootstrap, [rec.add_op(FheOp.KeyswitchL1toL0, [rec.add_op(FheOp.SampleExtract, [a], 0)])])   # 4, 5, 6
+    early = rec.add_op(FheOp.CircuitBootstrap, [ks])                    # ready at 2, needed at 7: runs with `late` at 6
+    rec.add_op(FheOp.CMux, [early, rec.add_op(FheOp.CMux, [late, a, x]), x])
+    assert M.planned_levels(rec) == [0, 0, 0, 5, 1, 2, 3, 4, 5, 6, 6, 7, 8]
+
+
+# ---- the model against compositions written by hand ---------------------------------------------------------------------------
+
+@pytest.mark.parametrize("which", ["n128k2", "n16k1"])
+def test_the_model_equals_oracle_shift_right(which):
+    P, ks, ak, ssk = K.keys_of(which)
+    s_bits, x_bits = 2, 3
+    x, s = random_glwe(0xF00, 2, P.glwe_len)
+    rec = spf_amd.RecordedCircuit(P.N)
+    BR.shift_right_graph(rec, rec.add_input(ValueKind.GLWE1, x), rec.add_input(ValueKind.GLWE1, s), s_bits, x_bits)
+    vals = M.evaluate(rec, P, M.keys_of(which))
+    rotated, lwes = BR.oracle_shift_right(P, ks, ak, ssk, x, s, s_bits, x_bits)
+    assert K.same_words(vals[rec.outputs[0]], rotated)
+    for node, want in zip(rec.outputs[1:], lwes):
+        assert K.same_words(vals[node], want)
+
+
+def test_the_model_equals_oracle_loop_on_a_rotation_graph():
+    P = K.TEST1
+    glwes, sels = random_glwe(0xF10, 2, P.glwe_len), BR.random_selectors(0xF11, 3, P)
+
+    class Eng:                      # rotation_graph reads the degree off its engine; the circuit it fills is given
+        params = K.engine_params(P)
+
+    rec, _ = BR.rotation_graph(Eng, glwes, sels, 2, circuit=spf_amd.RecordedCircuit(P.N))
+    vals = M.evaluate(rec, P, M.keys_of("n128k2"))
+    for node, x in zip(rec.outputs, glwes):
+        assert K.same_words(vals[node], BR.oracle_loop(x, sels, 2, P))
+
+
+def test_the_model_equals_pufks_oracle_on_a_keyswitch_node():
+    P = K.TEST1
+    log, count = 4, 3
+    key = K.pufks_key(P.N, P.k, P.lwe_n, count)
+    rows = random_lwe_batch(0xF20, 4, P.lwe_n)
+    rec = spf_amd.RecordedCircuit(P.N)
+    ids = [rec.add_input(ValueKind.LWE0, r) for r in rows]
+    node = rec.add_public_functional_keyswitch([ids[i] for i in (2, 0, 3, 3, 1)])
+    vals = M.evaluate(rec, P, M.keys_of("n128k2", (key, log, count)))
+    assert K.same_words(vals[node], PC.pufks_oracle(rows[[2, 0, 3, 3, 1]], key_fft(key), P.N, P.k, log, count).reshape(-1))
+
+
+@pytest.mark.parametrize("which", K.CONTEXTS)
+def test_the_model_equals_the_expressions_of_the_computed_table_test(which):
+    """test_gpu_pbs_graph.py::test_a_computed_table_and_operands_from_two_levels: the same graph, recorded"""
+    P, ks, ak, ssk = K.keys_of(which)
+    x0, l1, lut = random_lwe_batch(0xE10, 1, P.lwe_n)[0], random_lwe_batch(0xE11, 1, P.k * P.N)[0], random_glwe(0xE12, 1, P.glwe_len)[0]
+    g = spf_amd.RecordedCircuit(P.N)
+    t = g.add_op(FheOp.MulXN, [g.add_input(ValueKind.GLWE1, lut)], 5)
+    a = g.add_input(ValueKind.LWE0, x0)
+    b = g.add_op(FheOp.KeyswitchL1toL0, [g.add_input(ValueKind.LWE1, l1)])
+    uni = [g.add_op(FheOp.PBS_UNIVARIATE, [n, t]) for n in (b, a)]
+    biv = g.add_op(FheOp.PBS_BIVARIATE, [b, a, t], 1)
+    vals = M.evaluate(g, P, M.keys_of(which))
+    t_want = O.glwe_mul_xn(lut, 5, P.N, P.k)
+    b_want = O.keyswitch_lwe(l1, ks.ksk, P.k * P.N, P.lwe_n, P.ks_radix_log, P.ks_count)
+    assert K.same_words(vals[uni[0]], O.pbs_univariate(b_want, t_want, ks.bsk_fft, P))
+    assert K.same_words(vals[uni[1]], O.pbs_univariate(x0, t_want, ks.bsk_fft, P))
+    assert K.same_words(vals[biv], O.pbs_univariate(K.pack(b_want, x0, 1), t_want, ks.bsk_fft, P))
+
+
+def test_the_model_states_the_constants_and_the_keyless_kinds_as_their_tests_do():
+    """test_gpu_graph.py::test_graph_ggsw_and_glev_constants and test_gpu_values.py:98-108, at (N, k) = (128, 2)"""
+    P, ks, ak, ssk = K.keys_of("n128k2")
+    a, b = random_glwe(0xF30, 2, P.glwe_len)
+    ga, gb = random_glwe(0xF31, 2, P.cbs_count * P.glwe_len)
+    ggsw = BR.random_selectors(0xF32, 1, P)[0]
+    rec = spf_amd.RecordedCircuit(P.N)
+    na, nb = rec.add_input(ValueKind.GLWE1, a), rec.add_input(ValueKind.GLWE1, b)
+    nga, ngb, ng = rec.add_input(ValueKind.GLEV1, ga), rec.add_input(ValueKind.GLEV1, gb), rec.add_input(ValueKind.GGSW1, ggsw)
+    one = rec.add_trivial(ValueKind.GGSW1, 1)
+    nodes = {"mul": rec.add_op(FheOp.MultiplyGgswGlwe, [ng, na]), "gc": rec.add_op(FheOp.GlevCMux, [ng, nga, ngb]),
+             "ss": rec.add_op(FheOp.SchemeSwitch, [rec.add_trivial(ValueKind.GLEV1, 1)]), "cmux": rec.add_op(FheOp.CMux, [ng, na, nb]),
+             "pack": rec.add_pack([na, nb, na]), "xn": rec.add_op(FheOp.MulXN, [na], 2 * P.N + 77)}
+    vals = M.evaluate(rec, P, M.keys_of("n128k2"))
+    cb = (P.N, P.k, P.cbs_radix_log, P.cbs_count)
+    triv = np.zeros(P.lwe_n + 1, dtype=np.uint64)
+    triv[-1] = np.uint64(1 << 63)
+    assert K.same_words(vals[one], O.circuit_bootstrap(triv, ks.bsk_fft, ak, ssk, P))
+    glev = np.zeros((P.cbs_count, P.k + 1, P.N), dtype=np.uint64)
+    for j in range(P.cbs_count):
+        glev[j, P.k, 0] = np.uint64(1 << (64 - P.cbs_radix_log * (j + 1)))
+    assert K.same_words(vals[nodes["ss"]], O.scheme_switch_fft(glev.reshape(-1), ssk, P))
+    h = P.N // 2
+    fft = O.glwe_ggsw_mad(np.zeros((P.k + 1) * h, dtype=np.complex128), a, ggsw, *cb)
+    assert K.same_words(vals[nodes["mul"]], np.concatenate([O.poly_ifft(fft[q * h:(q + 1) * h]) for q in range(P.k + 1)]))
+    for j in range(P.cbs_count):
+        want = O.cmux(ga.reshape(P.cbs_count, -1)[j], gb.reshape(P.cbs_count, -1)[j], ggsw, *cb)
+        assert K.same_words(vals[nodes["gc"]].reshape(P.cbs_count, -1)[j], want)
+    assert K.same_words(vals[nodes["cmux"]], O.cmux(a, b, ggsw, *cb))
+    assert K.same_words(vals[nodes["xn"]], O.glwe_mul_xn(a, 77, P.N, P.k))
+    want = a + O.glwe_mul_xn(b, 1, P.N, P.k) + O.glwe_mul_xn(a, 2, P.N, P.k)
+    assert K.same_words(vals[nodes["pack"]], want)
+
+
+# ---- the comparison -------------------------------------------------------------------------------------------------------------
+
+def test_the_comparison_bites():
+    """one word of one input changed: every output the model computes from that input differs under `same_words`, the others do
+    not, and `first_difference` names the lowest of them"""
+    which = "n16k1"
+    P = K.keys_of(which)[0]
+    rec, facts = F.draw_circuit(5, P, "full", ValueKind.LWE0)
+    keys = M.keys_of(which, (K.pufks_key(P.N, P.k, P.lwe_n, 3), 4, 3))
+    want = M.evaluate(rec, P, keys)
+    assert M.first_difference(rec, [want[n] for n in rec.outputs], want) is None
+    depends = [set() for _ in rec.op]
+    for i, ins in enumerate(rec.inputs):
+        depends[i] = {i}.union(*[depends[j] for j in ins])
+    flipped = 0
+    for node in [i for i, op in enumerate(rec.op) if op == -1]:
+        if not any(node in depends[o] for o in rec.outputs):
+            continue
+        host = rec.host[node].view(np.uint64).reshape(-1).copy()
+        host[host.size // 2] ^= np.uint64(1 << 63)
+        got = M.evaluate(rec, P, keys, hosts={node: host})
+        hit = [o for o in rec.outputs if node in depends[o] and not K.same_words(got[o], want[o])]
+        assert hit, node                                    # (a CMUX rounds: not every dependent word has to move, some must)
+        assert all(K.same_words(got[o], want[o]) for o in rec.outputs if node not in depends[o])
+        message = M.first_difference(rec, [got[n] for n in rec.outputs], want)
+        assert message is not None and f"lowest node {min(hit)} " in message, message
+        flipped += 1
+    assert flipped >= 10
+
+
+def test_time_of_the_model_on_a_full_circuit_of_the_tuned_set():
+    """sizes the GPU tests' node budget (profiles/r23_graph_fuzz.md): the oracle walks a default circuit in seconds"""
+    P = K.keys_of("tuned")[0]
+    rec, facts = F.draw_circuit(F.case_seed(F.DEFAULT_SEED, 0, 0), P, "full", ValueKind.LWE0)
+    keys = M.keys_of("tuned", (K.pufks_key(P.N, P.k, P.lwe_n, 8, seed=4), 4, 8))
+    t0 = time.perf_counter()
+    vals = M.evaluate(rec, P, keys)
+    seconds = time.perf_counter() - t0
+    print(f"model: {len(rec.op)} nodes of the tuned set in {seconds:.2f} s")
+    assert len(vals) == len(rec.op) and seconds < 20
