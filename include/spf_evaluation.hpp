@@ -188,6 +188,18 @@ class Evaluation {
     {
         check(spf_group_circuit_bootstrap_via_pfks_batch(grp_, B, input_lwe0, output_ggsw_fft));
     }
+    // plaintext linear maps, `scalar_mul_ciphertext_mad` + `add_lwe_inplace` (sunscreen_tfhe ops/ciphertext/lwe_ciphertext_ops.rs
+    // :48-66, :4-18) for an M x K matrix of int64 weights and an optional bias of M words, kept in slot `slot` <
+    // SPF_LWE_LINEAR_SLOTS: output[b][m] = sum_k weights[m][k] * input[b][k], + bias[m] on the body, every word mod 2^64.
+    // B x K LWEs of one kind (SPF_VAL_LWE0 or SPF_VAL_LWE1) -> B x M LWEs of that kind
+    void load_lwe_linear_weights(uint32_t slot, size_t M, size_t K, const int64_t* weights, const uint64_t* bias = nullptr)
+    {
+        check(spf_group_load_lwe_linear_weights(grp_, slot, M, K, weights, bias));
+    }
+    void lwe_linear(uint64_t* output_lwes, const uint64_t* input_lwes, uint32_t slot, spf_value_kind kind = SPF_VAL_LWE0, size_t B = 1)
+    {
+        check(spf_group_lwe_linear_batch(grp_, slot, kind, B, input_lwes, output_lwes));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

@@ -464,6 +464,34 @@ typedef enum spf_graph_op {
     SPF_OP_PBS_BIVARIATE = 11   /* no FheOp: `programmable_bootstrap_bivariate`, param = plaintext_bits */
 } spf_graph_op;
 
+/* ---- plaintext linear maps over LWE ciphertexts ---------------------------------------------
+ * `scalar_mul_ciphertext_mad` then `add_lwe_inplace` (sunscreen_tfhe/src/ops/ciphertext/lwe_ciphertext_ops.rs:48-66, :4-18) — the
+ * two calls `programmable_bootstrap_bivariate` makes for left * 2^bits + right — for any M x K matrix w of int64 weights and an
+ * optional bias of M words:
+ *   out[b][m][c] = sum_k (uint64_t)w[m][k] * in[b][k][c]   for every word c, mod 2^64;   out[b][m][W-1] += bias[m]
+ * in [B][K][W], out [B][M][W]; the K ciphertexts are all SPF_VAL_LWE0 (W = n+1) or all SPF_VAL_LWE1 (W = k*N+1), the body is word
+ * W-1.  No floating point: the words are the integers' words.  Weights live in the context like keys, in SPF_LWE_LINEAR_SLOTS
+ * numbered slots; loading a slot again replaces its weights.  A load is synchronous and must not race work that uses the slot
+ * (the rule of the key loads); spf_destroy frees the images.  A slot holds at most 2^27 weights (M * K): a larger matrix is
+ * SPF_ERR_INVALID_ARGUMENT, with both numbers in the message.  Weights in [-8 355 711, 8 421 504] are also kept as up to three
+ * balanced int8 limbs of -w for the matrix cores; any int64 is served.
+ *   SPF_ERR_NO_KEY: the slot is empty.  SPF_ERR_INVALID_ARGUMENT: slot >= SPF_LWE_LINEAR_SLOTS, M or K = 0, a kind that is not
+ *   an LWE kind, a null pointer, an output range that overlaps the input range.
+ * spf_lwe_linear_enqueue is the form on device pointers, under the contract of the `_dev` entry points above: it only enqueues on
+ * `stream`; the byte planes of the inputs live in a buffer of the context (one stream per context), which grows by the same rule.
+ * "lwe_linear_planes" and "lwe_linear" of spf_last_kernel_ms time the planes pass and the product; spf_last_lwe_linear_kernel
+ * names the product kernel of the last call ("pfks_gemm_kernel<U>" or "lwe_linear_valu_kernel"; the environment variable
+ * SPF_LWE_LINEAR_PATH=valu|mfma, a diagnostic, forces either where both are legal).
+ * The group forms: the load goes to every member, straight from the host pointer; B is dealt in contiguous shards. */
+typedef enum spf_lwe_linear_limits { SPF_LWE_LINEAR_SLOTS = 64 } spf_lwe_linear_limits;
+spf_status spf_load_lwe_linear_weights(spf_ctx *ctx, uint32_t slot, size_t M, size_t K, const int64_t *weights /* [M][K] */,
+                                       const uint64_t *bias /* [M] or NULL */);
+spf_status spf_lwe_linear_batch(spf_ctx *ctx, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t *lwe_in,
+                                uint64_t *lwe_out);
+spf_status spf_lwe_linear_enqueue(spf_ctx *ctx, void *stream, uint32_t slot, spf_value_kind kind, size_t B,
+                                  const uint64_t *d_lwe_in, uint64_t *d_lwe_out);
+const char *spf_last_lwe_linear_kernel(spf_ctx *ctx);
+
 /* ---- call coalescing: many threads, one ciphertext each -> one batch per launch ----------
  * The reference calls `Evaluation` from many rayon workers with a single ciphertext per call
  * (circuit_processor/mod.rs:192-253).  A pool keeps that calling convention — submit, then wait like the synchronous call it
@@ -747,10 +775,11 @@ spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t w
  * with hipEvents recorded on the launch stream around each launch: "pbs" (blind rotation),
  * "keyswitch" (digits + GEMM), "trace" (cbs_trace_kernel), "scheme_switch", "cmux" (contiguous
  * batched CMUX family), "pufks_prepass" (the transposing pre-pass of a public functional keyswitch at the hand-written radices,
- * with the gather in front of it where there is one).  A host-pointer bootstrap of more than one chip round is launched in slices
+ * with the gather in front of it where there is one), "lwe_linear_planes" and "lwe_linear" (the per-call byte planes and the product,
+ * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only).  A host-pointer bootstrap of more than one chip round is launched in slices
  * of 1024 ciphertexts: it records one "pbs" entry per slice.  Enable with spf_set_timing(ctx, 1). */
 spf_status spf_set_timing(spf_ctx *ctx, int enabled);
-spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" */,
+spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" */,
                               double *avg_ms, int *launches);
 /* `generate_lut` (sunscreen_tfhe ops/bootstrapping/programmable_bootstrapping.rs:129-185) for
  * `programmable_bootstrap_univariate`: map_tables[f * 2^bits + x] = f(x) for n_maps functions over a
@@ -950,6 +979,13 @@ spf_status spf_group_public_functional_keyswitch_batch(spf_group *grp, size_t B,
 spf_status spf_group_private_functional_keyswitch_batch(spf_group *grp, size_t key_index, size_t B, const uint64_t *lwe_in,
                                                         uint64_t *glwe_out);
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group *grp, size_t B, const uint64_t *lwe0_in, double *ggsw_fft_out);
+/* the plaintext linear maps (`scalar_mul_ciphertext_mad` + `add_lwe_inplace`, ops/ciphertext/lwe_ciphertext_ops.rs:48-66, :4-18;
+ * spf_load_lwe_linear_weights, spf_lwe_linear_batch): the weights go to every member, straight from the host pointer; a batch is
+ * sharded by input vector (a member's K ciphertexts are at * K onwards) */
+spf_status spf_group_load_lwe_linear_weights(spf_group *grp, uint32_t slot, size_t M, size_t K, const int64_t *weights,
+                                             const uint64_t *bias);
+spf_status spf_group_lwe_linear_batch(spf_group *grp, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t *lwe_in,
+                                      uint64_t *lwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

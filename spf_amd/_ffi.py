@@ -31,6 +31,11 @@ class _CParams(C.Structure):
         "tr_radix_count", "ss_radix_log", "ss_radix_count")]
 
 
+# spf_value_kind of the LWE ciphertexts, and the number of weight slots of a context (include/spf_hip.h)
+VAL_LWE0, VAL_LWE1 = 0, 1
+LWE_LINEAR_SLOTS = 64
+
+
 def lib_path() -> str:
     # SPF_HIP_LIBRARY lets experiments (e.g. A/B builds of the kept knobs, tools/ab_build.sh) swap the library
     return os.environ.get("SPF_HIP_LIBRARY") or os.path.join(_HERE, "lib", "libspf_hip.so")
@@ -94,6 +99,10 @@ SYMBOLS = [
     ("spf_apply_pfks_on_ggsw_components_enqueue", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_circuit_bootstrap_via_pfks_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_circuit_bootstrap_via_pfks_enqueue", _I, [_P, _P, _SZ, _P, _P]),
+    ("spf_load_lwe_linear_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P]),
+    ("spf_lwe_linear_batch", _I, [_P, _U32, _I, _SZ, _P, _P]),
+    ("spf_lwe_linear_enqueue", _I, [_P, _P, _U32, _I, _SZ, _P, _P]),
+    ("spf_last_lwe_linear_kernel", C.c_char_p, [_P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -202,6 +211,8 @@ SYMBOLS = [
     ("spf_group_public_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_private_functional_keyswitch_batch", _I, [_P, _SZ, _SZ, _P, _P]),
     ("spf_group_circuit_bootstrap_via_pfks_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_group_load_lwe_linear_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P]),
+    ("spf_group_lwe_linear_batch", _I, [_P, _U32, _I, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -732,6 +743,45 @@ class Engine:
         self._ck(self._lib.spf_circuit_bootstrap_via_pfks_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    def load_lwe_linear_weights(self, slot: int, weights, bias=None):
+        """weights of a plaintext linear map (`scalar_mul_ciphertext_mad` + `add_lwe_inplace`, sunscreen_tfhe
+        ops/ciphertext/lwe_ciphertext_ops.rs:48-66, :4-18) into slot `slot` < LWE_LINEAR_SLOTS: an (M, K) int64 matrix and an
+        optional bias of M uint64 words.  Replaces what the slot held; synchronous."""
+        w = np.asarray(weights)
+        if w.ndim != 2 or w.dtype.kind not in "iu" or (w.dtype.kind == "u" and w.size and int(w.max()) > 2**63 - 1):
+            raise SpfError(-2, f"load_lwe_linear_weights: the weights are a 2-D array of int64 values, got {w.dtype} {w.shape}")
+        w = np.ascontiguousarray(w, dtype=np.int64)
+        b = None
+        if bias is not None:
+            b = _u64(bias)
+            if b.shape != (w.shape[0],):
+                raise SpfError(-2, f"load_lwe_linear_weights: the bias has shape {b.shape}, expected ({w.shape[0]},)")
+        shapes = self.__dict__.setdefault("_lin_shapes", {})
+        shapes.pop(int(slot), None)
+        self._ck(self._lib.spf_load_lwe_linear_weights(self._h, int(slot), w.shape[0], w.shape[1], _ptr(w), _ptr(b) if b is not None else None))
+        shapes[int(slot)] = (int(w.shape[0]), int(w.shape[1]))
+
+    def _lin(self, slot: int, kind: int):
+        """(M, K, W) of a loaded slot for ciphertexts of `kind`; whatever the library refuses is refused by the library"""
+        shape = self.__dict__.get("_lin_shapes", {}).get(int(slot)) if 0 <= int(slot) < 2**32 else None
+        if shape is None or int(kind) not in (VAL_LWE0, VAL_LWE1):
+            one = np.zeros(1, dtype=np.uint64)
+            two = np.zeros(1, dtype=np.uint64)
+            self._ck(self._lib.spf_lwe_linear_batch(self._h, int(slot) & 0xFFFFFFFF, int(kind), 0, _ptr(one), _ptr(two)))
+            raise SpfError(3, f"lwe_linear: no weights loaded in slot {slot} through this handle")
+        return shape + (self.params.lwe0_words if int(kind) == VAL_LWE0 else self.params.lwe1_words,)
+
+    def lwe_linear(self, slot: int, lwes, kind: int = 0) -> np.ndarray:
+        """out[b][m] = sum_k w[m][k] * lwes[b][k] (+ bias[m] on the body), every word mod 2^64: (B, K, W) LWEs of one kind
+        (VAL_LWE0: W = n+1, VAL_LWE1: W = k*N+1) -> (B, M, W), under the weights of slot `slot`"""
+        M, K, W = self._lin(slot, kind)
+        x = _u64(lwes)
+        if x.ndim != 3 or x.shape[1:] != (K, W):
+            raise SpfError(-2, f"lwe_linear: operand must have shape (B, {K}, {W}), got {x.shape}")
+        out = np.empty((x.shape[0], M, W), dtype=np.uint64)
+        self._ck(self._lib.spf_lwe_linear_batch(self._h, int(slot), int(kind), x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -849,6 +899,12 @@ class Engine:
 
     def last_cmux_kernel(self) -> str:
         return (self._lib.spf_last_cmux_kernel(self._h) or b"").decode()
+
+    def lwe_linear_enqueue(self, stream, slot, kind, B, d_lwe_in, d_lwe_out):
+        self._ck(self._lib.spf_lwe_linear_enqueue(self._h, stream, int(slot), int(kind), B, d_lwe_in, d_lwe_out))
+
+    def last_lwe_linear_kernel(self) -> str:
+        return (self._lib.spf_last_lwe_linear_kernel(self._h) or b"").decode()
 
     def last_public_functional_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()

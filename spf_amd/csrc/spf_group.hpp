@@ -828,6 +828,40 @@ spf_status spf_group_private_functional_keyswitch_batch(spf_group* g, size_t key
     });
 }
 
+// plaintext weights of the linear maps: every member, straight from the host pointer (no blob to replicate: each member derives
+// its own limb image)
+spf_status spf_group_load_lwe_linear_weights(spf_group* g, uint32_t slot, size_t M, size_t K, const int64_t* weights, const uint64_t* bias)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    std::lock_guard<std::mutex> lk(g->key_mu);
+    for (size_t i = 0; i < g->m.size(); i++) {
+        spf_status s = spf_load_lwe_linear_weights(g->m[i]->ctx, slot, M, K, weights, bias);
+        if (s != SPF_OK) return gfail(g, s, "member " + std::to_string(i) + ": " + spf_last_error(g->m[i]->ctx));
+    }
+    return SPF_OK;
+}
+
+// linear maps: sharded by input vector, a vector's K ciphertexts go with it
+spf_status spf_group_lwe_linear_batch(spf_group* g, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* in, uint64_t* out)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t wi, wo;
+    {
+        spf_ctx* c0 = g->m[0]->ctx;
+        std::lock_guard<std::recursive_mutex> lk(c0->mu);
+        const LweLinearSlot* l;
+        size_t W;
+        spf_status s = lwe_linear_shape(c0, slot, kind, B, &l, &W);
+        if (s != SPF_OK) return gfail(g, s, spf_last_error(c0));
+        wi = l->K * W; wo = l->M * W;
+    }
+    if (ranges_overlap(out, B * wo * 8, in, B * wi * 8)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
+        return spf_lwe_linear_batch(c, slot, kind, cnt, in + at * wi, out + at * wo);
+    });
+}
+
 // circuit bootstrap via PFKS: sharded by item
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {

@@ -11,6 +11,7 @@
 #include "spf_poly_fft.hpp"
 #include "spf_pufks.hpp"
 #include "spf_pfks.hpp"
+#include "spf_lwe_linear.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -63,8 +64,21 @@ struct Scratch {
 };
 
 // kernels whose launches spf_set_timing brackets with hipEvents on the launch stream (spf_last_kernel_ms)
-enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_COUNT };
-const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass"};
+enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_COUNT };
+const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass", "lwe_linear_planes",
+                                          "lwe_linear"};
+
+// one slot of plaintext weights for spf_lwe_linear_* (spf_lwe_linear.hpp): the int64 matrix as loaded, always; the int8 limbs of
+// -w and their sums where the matrix-core path takes the matrix (U > 0)
+struct LweLinearSlot {
+    bool ready = false;
+    size_t M = 0, K = 0, Mpad = 0, Kpad = 0;
+    uint32_t U = 0, nseg = 0;
+    long long* d_w = nullptr; // [M][K]
+    uint64_t* d_bias = nullptr; // [M], or null
+    int8_t* d_A = nullptr;    // [U][Mpad][Kpad]
+    int* d_rs = nullptr;      // [nseg][U][Mpad]
+};
 
 } // namespace
 
@@ -149,6 +163,10 @@ struct spf_ctx {
     DevBuf pfks_dig, pfks_rowsum; // limbs [U][Mpad][Kpad] and limb sums [nseg][U][Mpad] of one launch
     DevBuf pfks_glwe, pfks_lwe;   // circuit bootstrap via PFKS: the lo-noise GLWEs and the extracted, rotated LWE rows
     const char* last_pfks_kernel = "";
+    // plaintext linear maps over LWE ciphertexts (spf_lwe_linear.hpp): the weight slots and the byte planes of one launch
+    LweLinearSlot lin[SPF_LWE_LINEAR_SLOTS];
+    DevBuf lin_planes;
+    const char* last_lin_kernel = "";
 };
 
 namespace {
@@ -763,8 +781,11 @@ static void ctx_release(spf_ctx* c)
                     c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
                     c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables,
                     (void*)c->d_pufks, c->pufks_dig.p, (void*)c->d_pfks, (void*)c->d_pfks_planes, c->pfks_dig.p, c->pfks_rowsum.p, c->pfks_glwe.p,
-                    c->pfks_lwe.p})
+                    c->pfks_lwe.p, c->lin_planes.p})
         if (p) (void)hipFree(p);
+    for (LweLinearSlot& l : c->lin)
+        for (void* p : {(void*)l.d_w, (void*)l.d_bias, (void*)l.d_A, (void*)l.d_rs})
+            if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -2184,7 +2205,7 @@ spf_status spf_last_kernel_ms(spf_ctx* c, const char* kernel, double* avg_ms, in
     std::vector<TimedLaunch>* v = nullptr;
     for (int k = 0; k < T_COUNT; k++)
         if (!strcmp(kernel, kTimedNames[k])) v = &c->timed[k];
-    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\" or \"pufks_prepass\"");
+    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\" or \"lwe_linear\"");
     double total = 0.0;
     int n = 0;
     for (auto& t : *v) {
@@ -2856,6 +2877,212 @@ const char* spf_last_private_functional_keyswitch_kernel(spf_ctx* c)
     if (!c) return "";
     std::lock_guard<std::recursive_mutex> g(c->mu);
     return c->last_pfks_kernel;
+}
+
+// ---------------------------------------------------------------- plaintext linear maps over LWE ciphertexts
+// `scalar_mul_ciphertext_mad` + `add_lwe_inplace` (sunscreen_tfhe/src/ops/ciphertext/lwe_ciphertext_ops.rs:48-66, :4-18) for an
+// integer matrix; kernels and arithmetic: spf_lwe_linear.hpp.
+
+constexpr size_t kLweLinearWeightCap = (size_t)1 << 27; // weights of one slot (1 GiB of int64 on the device)
+constexpr size_t kLweLinearImageCap = (size_t)1 << 30;  // bytes of a slot's limb image, and of the byte planes of one launch
+// Whether the matrix-core path is taken where both are legal.  Measured (profiles/r24_lwe_linear.md), no constant M0 separates the
+// two: at K = 256 the VALU kernel wins at every M up to 1024, at K = 4096 the matrix cores win from M = 64.  The two estimates
+// below, in ms per 102 450 output words per row, are fitted to the 81 measured cells of that table (K 256 .. 4096, M 1 .. 1024,
+// one to three limbs) and decide 79 of them as the measurement does; the other two are within 10 % and go to the VALU kernel.
+//   VALU:         K times the larger of its memory floor and its 64-bit multiplies over the rows, in groups of LWE_LINEAR_VT
+//   matrix cores: the planes pass, written and read again (per input column); per 128-row tile the folds and the epilogue, and
+//                 the MFMA passes (per limb and column); the output stores (per row)
+// The matrix cores are taken where their estimate is below the VALU kernel's by a tenth.
+static bool lwe_linear_matrix_cores_pay(size_t M, size_t K, size_t Kpad, uint32_t U)
+{
+    const double valu = (double)K * std::max(2.4e-4, 1.55e-5 * (double)((M + LWE_LINEAR_VT - 1) / LWE_LINEAR_VT * LWE_LINEAR_VT));
+    const double tiles = (double)((M + PFKS_TILE - 1) / PFKS_TILE);
+    const double mfma = 6.6e-4 * (double)Kpad + tiles * (0.27 + 2.6e-4 * U * (double)Kpad) + 0.0022 * (double)M;
+    return 1.1 * mfma < valu;
+}
+
+static void lwe_linear_drop(LweLinearSlot& l)
+{
+    for (void* p : {(void*)l.d_w, (void*)l.d_bias, (void*)l.d_A, (void*)l.d_rs})
+        if (p) (void)hipFree(p);
+    l = LweLinearSlot{};
+}
+
+// Synchronous, like a key load: the slot is empty from the first check that passes until the end, and after any failure.
+spf_status spf_load_lwe_linear_weights(spf_ctx* c, uint32_t slot, size_t M, size_t K, const int64_t* weights, const uint64_t* bias)
+{
+    if (!c) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null context");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (slot >= SPF_LWE_LINEAR_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_LWE_LINEAR_SLOTS = " + std::to_string(SPF_LWE_LINEAR_SLOTS));
+    if (!weights) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (M == 0 || K == 0) return fail(c, SPF_ERR_INVALID_ARGUMENT, "a weight matrix needs M >= 1 and K >= 1");
+    if (M > kLweLinearWeightCap / K)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "weight matrix of " + std::to_string(M) + " x " + std::to_string(K) + " weights > the cap of " +
+                                                     std::to_string(kLweLinearWeightCap) + " weights per slot");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    LweLinearSlot& l = c->lin[slot];
+    lwe_linear_drop(l);
+    long long lo = weights[0], hi = weights[0];
+    for (size_t i = 1; i < M * K; i++) { lo = std::min<long long>(lo, weights[i]); hi = std::max<long long>(hi, weights[i]); }
+    LweLinearSlot n;
+    n.M = M; n.K = K;
+    n.Mpad = (M + PFKS_TILE - 1) / PFKS_TILE * PFKS_TILE;
+    n.Kpad = (K + 127) & ~(size_t)127;
+    n.nseg = (uint32_t)((n.Kpad / 128 + kPfksSegRounds - 1) / kPfksSegRounds);
+    n.U = lwe_linear_limbs(lo, hi);
+    // (grid.y of the GEMM; a matrix the first path declines is served by the VALU kernel)
+    if (n.U && (n.Mpad / PFKS_TILE > 65535 || n.Mpad * n.Kpad > kLweLinearImageCap / n.U)) n.U = 0;
+    auto build = [&]() -> spf_status {
+        HIPCHK(c, hipMalloc((void**)&n.d_w, M * K * 8));
+        HIPCHK(c, hipMemcpy(n.d_w, weights, M * K * 8, hipMemcpyHostToDevice));
+        if (bias) {
+            HIPCHK(c, hipMalloc((void**)&n.d_bias, M * 8));
+            HIPCHK(c, hipMemcpy(n.d_bias, bias, M * 8, hipMemcpyHostToDevice));
+        }
+        if (!n.U) return SPF_OK;
+        HIPCHK(c, hipMalloc((void**)&n.d_A, (size_t)n.U * n.Mpad * n.Kpad));
+        HIPCHK(c, hipMalloc((void**)&n.d_rs, (size_t)n.nseg * n.U * n.Mpad * sizeof(int)));
+        hipLaunchKernelGGL(lwe_linear_limbs_kernel, dim3((unsigned)n.Mpad), dim3(256), 0, c->stream, n.d_w, n.d_A, (uint32_t)M, (uint32_t)n.Mpad,
+                           (uint32_t)K, (uint32_t)n.Kpad, n.U);
+        hipLaunchKernelGGL(pfks_rowsum_kernel, dim3((unsigned)n.Mpad, n.nseg * n.U), dim3(256), 0, c->stream, (const int8_t*)n.d_A, n.d_rs,
+                           (uint32_t)n.Mpad, n.U, (uint32_t)n.Kpad, kPfksSegRounds * 128u);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SPF_OK;
+    };
+    const spf_status st = build();
+    if (st != SPF_OK) {
+        lwe_linear_drop(n);
+        return st;
+    }
+    n.ready = true;
+    l = n;
+    return SPF_OK;
+}
+
+// what a call needs of the slot and the kind, or why not; under c->mu
+static spf_status lwe_linear_shape(spf_ctx* c, uint32_t slot, spf_value_kind kind, size_t B, const LweLinearSlot** l, size_t* W)
+{
+    if (slot >= SPF_LWE_LINEAR_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_LWE_LINEAR_SLOTS = " + std::to_string(SPF_LWE_LINEAR_SLOTS));
+    if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kind must be SPF_VAL_LWE0 or SPF_VAL_LWE1");
+    if (!c->lin[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no weights loaded in slot " + std::to_string(slot));
+    *l = &c->lin[slot];
+    *W = kind == SPF_VAL_LWE0 ? lwe0_words(c->prm) : lwe1_words(c->prm);
+    if (B > 0x0fffffffu / std::max((*l)->M, (*l)->K)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    return SPF_OK;
+}
+
+// Which product kernel serves a call where both are legal: SPF_LWE_LINEAR_PATH=valu | mfma (diagnostic; read at every call)
+static int lwe_linear_forced_path()
+{
+    const char* e = getenv("SPF_LWE_LINEAR_PATH");
+    return !e ? 0 : !strcmp(e, "valu") ? 1 : !strcmp(e, "mfma") ? 2 : 0;
+}
+
+spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* d_lwe_in,
+                                  uint64_t* d_lwe_out)
+{
+    if (!c || !d_lwe_in || !d_lwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const LweLinearSlot* lp;
+    size_t W;
+    spf_status st = lwe_linear_shape(c, slot, kind, B, &lp, &W);
+    if (st != SPF_OK) return st;
+    if (B == 0) return SPF_OK;
+    const LweLinearSlot& l = *lp;
+    const size_t M = l.M, K = l.K;
+    if (ranges_overlap(d_lwe_out, B * M * W * 8, d_lwe_in, B * K * W * 8)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t item_planes = 8 * W * l.Kpad; // bytes of one item's byte planes
+    const bool mfma_legal = l.U != 0 && item_planes <= kLweLinearImageCap;
+    const int forced = lwe_linear_forced_path();
+    const bool mfma = mfma_legal && (forced == 2 || (forced == 0 && lwe_linear_matrix_cores_pay(M, K, l.Kpad, l.U)));
+    if (!mfma) {
+        c->last_lin_kernel = "lwe_linear_valu_kernel";
+        TimedScope ts(c, s, T_LIN);
+        st = ts.begin();
+        if (st != SPF_OK) return st;
+        const size_t rows_step = (size_t)65535 * LWE_LINEAR_VT;
+        for (size_t at = 0; at < B; at += 65535) {
+            const size_t nb = std::min<size_t>(B - at, 65535);
+            for (size_t m0 = 0; m0 < M; m0 += rows_step) {
+                const size_t nm = std::min(M - m0, rows_step);
+                LweLinearValuArgs a{d_lwe_in + at * K * W, l.d_w + m0 * K, l.d_bias ? l.d_bias + m0 : nullptr, d_lwe_out + (at * M + m0) * W,
+                                    (uint32_t)nm, (uint32_t)M, (uint32_t)K, (uint32_t)W};
+                hipLaunchKernelGGL(lwe_linear_valu_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)((nm + LWE_LINEAR_VT - 1) / LWE_LINEAR_VT), (unsigned)nb),
+                                   dim3(256), 0, s, a);
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+        return ts.end();
+    }
+    // items per launch: what keeps the planes of a launch within kLweLinearImageCap, the plane rows within 32 bits and grid.z
+    // of the planes pass within its limit (at least one: an item whose planes exceed the cap is served above)
+    size_t per = std::max<size_t>(1, kLweLinearImageCap / item_planes);
+    per = std::min({per, B, (size_t)65535, std::max<size_t>(1, ((size_t)1 << 28) / W)});
+    st = ensure(c, c->lin_planes, ((8 * per * W + PFKS_TILE - 1) / PFKS_TILE * PFKS_TILE) * l.Kpad);
+    if (st != SPF_OK) return st;
+    c->last_lin_kernel = l.U == 1 ? "pfks_gemm_kernel<1>" : l.U == 2 ? "pfks_gemm_kernel<2>" : "pfks_gemm_kernel<3>";
+    for (size_t at = 0; at < B; at += per) {
+        const size_t nb = std::min(per, B - at);
+        {
+            TimedScope ts(c, s, T_LIN_PLANES);
+            st = ts.begin();
+            if (st != SPF_OK) return st;
+            hipLaunchKernelGGL(lwe_linear_planes_kernel, dim3((unsigned)(l.Kpad / 64), (unsigned)((W + 31) / 32), (unsigned)nb), dim3(256), 0, s,
+                               d_lwe_in + at * K * W, (int8_t*)c->lin_planes.p, (uint32_t)W, (uint32_t)K, (uint32_t)l.Kpad);
+            HIPCHK(c, hipGetLastError());
+            st = ts.end();
+            if (st != SPF_OK) return st;
+        }
+        TimedScope ts(c, s, T_LIN);
+        st = ts.begin();
+        if (st != SPF_OK) return st;
+        // output row m of item q, word col, at out[q][m][col]
+        uint64_t* o = d_lwe_out + at * M * W;
+        PfksGemmArgs a{l.d_A, (const int8_t*)c->lin_planes.p, l.d_rs, PfksDest{o, 1, W, 0, M * W},
+                       (uint32_t)M, (uint32_t)l.Mpad, (uint32_t)l.Kpad, (uint32_t)W, (uint32_t)(nb * W)};
+        const dim3 grid((unsigned)((8 * nb * W + PFKS_TILE - 1) / PFKS_TILE), (unsigned)(l.Mpad / PFKS_TILE));
+        if (l.U == 1) hipLaunchKernelGGL(pfks_gemm_kernel<1>, grid, dim3(256), 0, s, a);
+        else if (l.U == 2) hipLaunchKernelGGL(pfks_gemm_kernel<2>, grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(pfks_gemm_kernel<3>, grid, dim3(256), 0, s, a);
+        if (l.d_bias)
+            hipLaunchKernelGGL(lwe_linear_bias_kernel, dim3((unsigned)((nb * M + 255) / 256)), dim3(256), 0, s, o, (const uint64_t*)l.d_bias,
+                               (uint32_t)M, (uint32_t)W, nb * M);
+        HIPCHK(c, hipGetLastError());
+        st = ts.end();
+        if (st != SPF_OK) return st;
+    }
+    return SPF_OK;
+}
+
+spf_status spf_lwe_linear_batch(spf_ctx* c, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* lwe_in, uint64_t* lwe_out)
+{
+    if (!c || !lwe_in || !lwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    size_t M, K, W;
+    {
+        std::lock_guard<std::recursive_mutex> g(c->mu);
+        const LweLinearSlot* l;
+        spf_status st = lwe_linear_shape(c, slot, kind, B, &l, &W);
+        if (st != SPF_OK) return st;
+        M = l->M; K = l->K;
+    }
+    if (B == 0) return SPF_OK;
+    if (ranges_overlap(lwe_out, B * M * W * 8, lwe_in, B * K * W * 8)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    return host_call(c, {{c->in, lwe_in, B * K * W * 8}}, B * M * W * 8, lwe_out, [&] {
+        return spf_lwe_linear_enqueue(c, c->stream, slot, kind, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    });
+}
+
+const char* spf_last_lwe_linear_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_lin_kernel;
 }
 
 const char* spf_last_blind_rotate_kernel(spf_ctx* c)

@@ -101,6 +101,15 @@ class Evaluation:
                                          plaintext_bits: int):
         self._store(output, self.engine.pbs_bivariate(left, right, lut, plaintext_bits))
 
+    # plaintext linear maps: scalar_mul_ciphertext_mad + add_lwe_inplace (sunscreen_tfhe ops/ciphertext/
+    # lwe_ciphertext_ops.rs:48-66, :4-18) for an (M, K) int64 matrix and an optional bias, kept in a slot of the engine:
+    # (B, K, W) LWEs of one kind -> (B, M, W)
+    def load_lwe_linear_weights(self, slot: int, weights: np.ndarray, bias=None):
+        self.engine.load_lwe_linear_weights(slot, weights, bias)
+
+    def lwe_linear(self, output: np.ndarray, input: np.ndarray, slot: int, kind: int = 0):
+        self._store(output, self.engine.lwe_linear(slot, input, kind))
+
     # generalized_programmable_bootstrap (programmable_bootstrapping.rs:342-410)
     def generalized_programmable_bootstrap(self, output, input, lut, log_chi: int, log_v: int):
         self._store(output, self.engine.generalized_pbs(input, lut, log_chi, log_v, 0))

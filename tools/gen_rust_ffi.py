@@ -11,7 +11,7 @@ import re
 import subprocess
 import sys
 
-INT_TYPES = {"int": "c_int", "size_t": "usize", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32",
+INT_TYPES = {"int": "c_int", "size_t": "usize", "uint8_t": "u8", "uint32_t": "u32", "uint64_t": "u64", "int32_t": "i32", "int64_t": "i64",
              "double": "f64", "char": "c_char", "void": "c_void", "spf_status": "spf_status"}
 
 
