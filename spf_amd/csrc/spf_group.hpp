@@ -279,6 +279,29 @@ spf_status group_split(spf_group* g, size_t B, const std::function<spf_status(sp
     return SPF_OK;
 }
 
+// what every batch form refuses first: a null group, and (`null_argument`) a null pointer where the form does not take one
+spf_status group_args(spf_group* g, bool null_argument)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    return null_argument ? gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument") : SPF_OK;
+}
+
+// group_split() for B items of `sh`: the range that starts at item `at` has its operand k at ins[k] + at * sh.in_words[k] words and
+// its result at out + at * sh.out_words; `call(ctx, count, operands..., out)` is the member's own host-pointer form.
+template <class Call>
+spf_status group_batch(spf_group* g, const BatchShape& sh, size_t B, std::initializer_list<const void*> ins, void* out, Call call)
+{
+    const void* in[3] = {};
+    std::copy(ins.begin(), ins.end(), in);
+    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) -> spf_status {
+        const auto rows = [&](int k) { return Rows{(uint64_t*)in[k] + at * sh.in_words[k]}; };
+        const Rows o{(uint64_t*)out + at * sh.out_words};
+        if constexpr (std::is_invocable_v<Call, spf_ctx*, size_t, Rows, Rows>) return call(c, n, rows(0), o);
+        else if constexpr (std::is_invocable_v<Call, spf_ctx*, size_t, Rows, Rows, Rows>) return call(c, n, rows(0), rows(1), o);
+        else return call(c, n, rows(0), rows(1), rows(2), o);
+    });
+}
+
 bool blob_ready(spf_ctx* c, int which)
 {
     std::lock_guard<std::recursive_mutex> lk(c->mu);
@@ -667,165 +690,136 @@ spf_status spf_group_debug_fail_next(spf_group* g, int member, int count)
 
 // ---- the batch forms: the member's own host-pointer entry point on its range
 
-#define SPF_GROUP_NULL(cond)                                                                       \
-    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");                         \
-    if (B && (cond)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument")
-
 spf_status spf_group_keyswitch_lwe_l1_lwe_l0_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = lwe1_words(g->prm), wo = lwe0_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_keyswitch_lwe_l1_lwe_l0_batch(c, n, in + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_KEYSWITCH), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_keyswitch_lwe_l1_lwe_l0_batch(c, n, in, out); });
 }
 
 spf_status spf_group_generalized_pbs_batch(spf_group* g, size_t B, const uint64_t* lwe, const uint64_t* lut, size_t lut_stride,
                                            uint32_t log_chi, uint32_t log_v, uint64_t body_rotate, uint64_t* out)
 {
-    SPF_GROUP_NULL(!lwe || !lut || !out);
-    const size_t wi = lwe0_words(g->prm), wo = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_generalized_pbs_batch(c, n, lwe + at * wi, lut + at * lut_stride, lut_stride, log_chi, log_v, body_rotate, out + at * wo);
+    if (spf_status s = group_args(g, B && (!lwe || !lut || !out))) return s;
+    return group_batch(g, pbs_shape(g->prm, false, false, lut_stride), B, {lwe, lut}, out, [=](spf_ctx* c, size_t n, Rows lwe, Rows lut, Rows out) {
+        return spf_generalized_pbs_batch(c, n, lwe, lut, lut_stride, log_chi, log_v, body_rotate, out);
     });
 }
 
 spf_status spf_group_pbs_univariate_batch(spf_group* g, size_t B, const uint64_t* lwe, const uint64_t* lut, size_t lut_stride,
                                           uint64_t* out)
 {
-    SPF_GROUP_NULL(!lwe || !lut || !out);
-    const size_t wi = lwe0_words(g->prm), wo = lwe1_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_pbs_univariate_batch(c, n, lwe + at * wi, lut + at * lut_stride, lut_stride, out + at * wo);
+    if (spf_status s = group_args(g, B && (!lwe || !lut || !out))) return s;
+    return group_batch(g, pbs_shape(g->prm, true, false, lut_stride), B, {lwe, lut}, out, [=](spf_ctx* c, size_t n, Rows lwe, Rows lut, Rows out) {
+        return spf_pbs_univariate_batch(c, n, lwe, lut, lut_stride, out);
     });
 }
 
 spf_status spf_group_pbs_bivariate_batch(spf_group* g, size_t B, const uint64_t* left, const uint64_t* right, const uint64_t* lut,
                                          size_t lut_stride, uint32_t plaintext_bits, uint64_t* out)
 {
-    SPF_GROUP_NULL(!left || !right || !lut || !out);
+    if (spf_status s = group_args(g, B && (!left || !right || !lut || !out))) return s;
     if (plaintext_bits >= 64) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "plaintext_bits must be below 64");
-    const size_t wi = lwe0_words(g->prm), wo = lwe1_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_pbs_bivariate_batch(c, n, left + at * wi, right + at * wi, lut + at * lut_stride, lut_stride, plaintext_bits,
-                                       out + at * wo);
-    });
+    return group_batch(g, pbs_shape(g->prm, true, true, lut_stride), B, {left, right, lut}, out,
+                       [=](spf_ctx* c, size_t n, Rows left, Rows right, Rows lut, Rows out) {
+                           return spf_pbs_bivariate_batch(c, n, left, right, lut, lut_stride, plaintext_bits, out);
+                       });
 }
 
 spf_status spf_group_circuit_bootstrap_pbs_batch(spf_group* g, size_t B, const uint64_t* lwe, uint64_t* out)
 {
-    SPF_GROUP_NULL(!lwe || !out);
-    const size_t wi = lwe0_words(g->prm), wo = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_circuit_bootstrap_pbs_batch(c, n, lwe + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!lwe || !out))) return s;
+    return group_batch(g, pbs_shape(g->prm, false), B, {lwe}, out,
+                       [](spf_ctx* c, size_t n, Rows lwe, Rows out) { return spf_circuit_bootstrap_pbs_batch(c, n, lwe, out); });
 }
 
 spf_status spf_group_circuit_bootstrap_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {
-    SPF_GROUP_NULL(!lwe || !out);
-    const size_t wi = lwe0_words(g->prm), wo = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_circuit_bootstrap_batch(c, n, lwe + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!lwe || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_CBS), B, {lwe}, out,
+                       [](spf_ctx* c, size_t n, Rows lwe, Rows out) { return spf_circuit_bootstrap_batch(c, n, lwe, out); });
 }
 
 spf_status spf_group_mod_switch_trace_and_rotate_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = glwe_words(g->prm), wo = wi * g->prm.cbs_radix_count;
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_mod_switch_trace_and_rotate_batch(c, n, in + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, trace_shape(g->prm), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_mod_switch_trace_and_rotate_batch(c, n, in, out); });
 }
 
 spf_status spf_group_scheme_switch_batch(spf_group* g, size_t B, const uint64_t* in, double* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = glwe_words(g->prm) * g->prm.cbs_radix_count, wo = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_scheme_switch_batch(c, n, in + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_SCHEME_SWITCH), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_scheme_switch_batch(c, n, in, out); });
 }
 
 spf_status spf_group_sample_extract_l1_batch(spf_group* g, size_t B, const uint64_t* in, size_t idx, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = glwe_words(g->prm), wo = lwe1_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_sample_extract_l1_batch(c, n, in + at * wi, idx, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_SAMPLE_EXTRACT), B, {in}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_sample_extract_l1_batch(c, n, in, idx, out); });
 }
 
 // packed integers: sharded by packed ciphertext, so the member that takes ciphertexts [at, at + n) takes rows at * n_bits ..
-#define SPF_GROUP_PACKED(in, out)                                                                  \
-    SPF_GROUP_NULL(!(in) || !(out));                                                               \
-    if (const char* why = packed_shape_error(g->prm, B, n_bits)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why)
-
 spf_status spf_group_glwe_pack_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* bits, uint64_t* out)
 {
-    SPF_GROUP_PACKED(bits, out);
-    const size_t w = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_glwe_pack_batch(c, n, n_bits, bits + at * n_bits * w, out + at * w);
-    });
+    if (spf_status s = group_args(g, B && (!bits || !out))) return s;
+    if (const char* why = packed_shape_error(g->prm, B, n_bits)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
+    return group_batch(g, packed_shape(g->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_GLWE1, true), B, {bits}, out,
+                       [=](spf_ctx* c, size_t n, Rows bits, Rows out) { return spf_glwe_pack_batch(c, n, n_bits, bits, out); });
 }
 
 spf_status spf_group_glwe_unpack_l1_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* glwe, uint64_t* lwe1_out)
 {
-    SPF_GROUP_PACKED(glwe, lwe1_out);
-    const size_t wi = glwe_words(g->prm), wo = lwe1_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_glwe_unpack_l1_batch(c, n, n_bits, glwe + at * wi, lwe1_out + at * n_bits * wo);
-    });
+    if (spf_status s = group_args(g, B && (!glwe || !lwe1_out))) return s;
+    if (const char* why = packed_shape_error(g->prm, B, n_bits)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
+    return group_batch(g, packed_shape(g->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_LWE1, false), B, {glwe}, lwe1_out,
+                       [=](spf_ctx* c, size_t n, Rows glwe, Rows out) { return spf_glwe_unpack_l1_batch(c, n, n_bits, glwe, out); });
 }
 
 spf_status spf_group_unpack_circuit_bootstrap_batch(spf_group* g, size_t B, size_t n_bits, const uint64_t* glwe, double* ggsw_out)
 {
-    SPF_GROUP_PACKED(glwe, ggsw_out);
-    const size_t wi = glwe_words(g->prm), wo = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_unpack_circuit_bootstrap_batch(c, n, n_bits, glwe + at * wi, ggsw_out + at * n_bits * wo);
-    });
+    if (spf_status s = group_args(g, B && (!glwe || !ggsw_out))) return s;
+    if (const char* why = packed_shape_error(g->prm, B, n_bits)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
+    return group_batch(g, packed_shape(g->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_GGSW1, false), B, {glwe}, ggsw_out,
+                       [=](spf_ctx* c, size_t n, Rows glwe, Rows out) { return spf_unpack_circuit_bootstrap_batch(c, n, n_bits, glwe, out); });
 }
 
 // blind rotation by an encrypted shift: sharded by item, an item's n_bits selectors go with it
 spf_status spf_group_blind_rotation_batch(spf_group* g, size_t B, size_t n_bits, size_t log_stride, const double* shift,
                                           const uint64_t* in, uint64_t* out)
 {
-    SPF_GROUP_NULL(!shift || !in || !out);
+    if (spf_status s = group_args(g, B && (!shift || !in || !out))) return s;
     if (const char* why = blind_rotation_shape_error(g->prm, B, n_bits, log_stride)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
-    const size_t w = glwe_words(g->prm), sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) {
-        return spf_blind_rotation_batch(c, n, n_bits, log_stride, shift + at * n_bits * sw, in + at * w, out + at * w);
+    return group_batch(g, blind_rotation_shape(g->prm, n_bits), B, {shift, in}, out, [=](spf_ctx* c, size_t n, Rows shift, Rows in, Rows out) {
+        return spf_blind_rotation_batch(c, n, n_bits, log_stride, shift, in, out);
     });
 }
+
+// The forms whose shape comes with a key or with weights: member 0's context makes the checks of its own form (every member holds
+// the same keys) and its status and text are passed on.
 
 // public functional keyswitch: sharded by output, an output's lwe_count input rows go with it
 spf_status spf_group_public_functional_keyswitch_batch(spf_group* g, size_t B, size_t lwe_count, const uint64_t* in, uint64_t* out)
 {
-    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
-    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (const char* why = pufks_shape_error(g->prm, B, lwe_count)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, why);
-    size_t n;
-    {
-        spf_ctx* c0 = g->m[0]->ctx;
-        std::lock_guard<std::recursive_mutex> lk(c0->mu);
-        if (!c0->pufks_ready) return gfail(g, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
-        n = c0->pufks_n;
-    }
-    const size_t wi = lwe_count * (n + 1), wo = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
-        return spf_public_functional_keyswitch_batch(c, cnt, lwe_count, in + at * wi, out + at * wo);
-    });
+    if (spf_status s = group_args(g, false)) return s;
+    BatchShape sh;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = pufks_args(c0, B, lwe_count, in, out, &sh)) return gfail(g, s, spf_last_error(c0));
+    return group_batch(g, sh, B, {in}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_public_functional_keyswitch_batch(c, n, lwe_count, in, out); });
 }
 
 // private functional keyswitch: sharded by output, an output's lwe_count input rows go with it
 spf_status spf_group_private_functional_keyswitch_batch(spf_group* g, size_t key_index, size_t B, const uint64_t* in, uint64_t* out)
 {
-    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
-    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    size_t wi;
-    {
-        spf_ctx* c0 = g->m[0]->ctx;
-        std::lock_guard<std::recursive_mutex> lk(c0->mu);
-        if (!c0->pfks_ready) return gfail(g, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
-        if (key_index >= c0->pfks_keys) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
-        wi = pfks_row_words(c0);
-    }
-    if (B > 0x0fffffffu) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    const size_t wo = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
-        return spf_private_functional_keyswitch_batch(c, key_index, cnt, in + at * wi, out + at * wo);
-    });
+    if (spf_status s = group_args(g, false)) return s;
+    BatchShape sh;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = pfks_args(c0, key_index, B, in, out, &sh)) return gfail(g, s, spf_last_error(c0));
+    return group_batch(g, sh, B, {in}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_private_functional_keyswitch_batch(c, key_index, n, in, out); });
 }
 
 // plaintext weights of the linear maps: every member, straight from the host pointer (no blob to replicate: each member derives
@@ -841,93 +835,81 @@ spf_status spf_group_load_lwe_linear_weights(spf_group* g, uint32_t slot, size_t
     return SPF_OK;
 }
 
-// linear maps: sharded by input vector, a vector's K ciphertexts go with it
+// linear maps: sharded by input vector, a vector's K ciphertexts go with it.  (The overlap is checked on the whole batch: two
+// ranges that overlap as a whole can be cut into shards that do not.)
 spf_status spf_group_lwe_linear_batch(spf_group* g, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* in, uint64_t* out)
 {
-    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
-    if (!in || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    size_t wi, wo;
-    {
-        spf_ctx* c0 = g->m[0]->ctx;
-        std::lock_guard<std::recursive_mutex> lk(c0->mu);
-        const LweLinearSlot* l;
-        size_t W;
-        spf_status s = lwe_linear_shape(c0, slot, kind, B, &l, &W);
-        if (s != SPF_OK) return gfail(g, s, spf_last_error(c0));
-        wi = l->K * W; wo = l->M * W;
-    }
-    if (ranges_overlap(out, B * wo * 8, in, B * wi * 8)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
-        return spf_lwe_linear_batch(c, slot, kind, cnt, in + at * wi, out + at * wo);
-    });
+    if (spf_status s = group_args(g, false)) return s;
+    BatchShape sh;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = lwe_linear_args(c0, slot, kind, B, in, out, &sh)) return gfail(g, s, spf_last_error(c0));
+    if (batch_overlaps(sh, B, out, in)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    return group_batch(g, sh, B, {in}, out, [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_lwe_linear_batch(c, slot, kind, n, in, out); });
 }
 
 // circuit bootstrap via PFKS: sharded by item
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {
-    SPF_GROUP_NULL(!lwe || !out);
-    const size_t wi = lwe0_words(g->prm), wo = ggsw_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t cnt) {
-        return spf_circuit_bootstrap_via_pfks_batch(c, cnt, lwe + at * wi, out + at * wo);
-    });
+    if (spf_status s = group_args(g, B && (!lwe || !out))) return s;
+    return group_batch(g, cbs_via_pfks_shape(g->prm), B, {lwe}, out,
+                       [](spf_ctx* c, size_t n, Rows lwe, Rows out) { return spf_circuit_bootstrap_via_pfks_batch(c, n, lwe, out); });
 }
 
 spf_status spf_group_glwe_not_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t w = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_glwe_not_batch(c, n, in + at * w, out + at * w); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_NOT), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_glwe_not_batch(c, n, in, out); });
 }
 
 spf_status spf_group_glwe_xor_batch(spf_group* g, size_t B, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
-    SPF_GROUP_NULL(!a || !b || !out);
-    const size_t w = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_glwe_xor_batch(c, n, a + at * w, b + at * w, out + at * w); });
+    if (spf_status s = group_args(g, B && (!a || !b || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_GLWE_ADD), B, {a, b}, out,
+                       [](spf_ctx* c, size_t n, Rows a, Rows b, Rows out) { return spf_glwe_xor_batch(c, n, a, b, out); });
 }
 
 spf_status spf_group_glwe_mul_xn_batch(spf_group* g, size_t B, const uint64_t* in, size_t amount, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t w = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_glwe_mul_xn_batch(c, n, in + at * w, amount, out + at * w); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_MUL_XN), B, {in}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_glwe_mul_xn_batch(c, n, in, amount, out); });
 }
 
 spf_status spf_group_cmux_batch(spf_group* g, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
-    SPF_GROUP_NULL(!sel || !a || !b || !out);
-    const size_t w = glwe_words(g->prm), sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_cmux_batch(c, n, sel + at * sw, a + at * w, b + at * w, out + at * w); });
+    if (spf_status s = group_args(g, B && (!sel || !a || !b || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_CMUX), B, {sel, a, b}, out,
+                       [](spf_ctx* c, size_t n, Rows sel, Rows a, Rows b, Rows out) { return spf_cmux_batch(c, n, sel, a, b, out); });
 }
 
 spf_status spf_group_glev_cmux_batch(spf_group* g, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
-    SPF_GROUP_NULL(!sel || !a || !b || !out);
-    const size_t w = glwe_words(g->prm) * g->prm.cbs_radix_count, sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_glev_cmux_batch(c, n, sel + at * sw, a + at * w, b + at * w, out + at * w); });
+    if (spf_status s = group_args(g, B && (!sel || !a || !b || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_GLEV_CMUX), B, {sel, a, b}, out,
+                       [](spf_ctx* c, size_t n, Rows sel, Rows a, Rows b, Rows out) { return spf_glev_cmux_batch(c, n, sel, a, b, out); });
 }
 
 spf_status spf_group_multiply_glwe_ggsw_batch(spf_group* g, size_t B, const uint64_t* glwe, const double* ggsw, uint64_t* out)
 {
-    SPF_GROUP_NULL(!glwe || !ggsw || !out);
-    const size_t w = glwe_words(g->prm), sw = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_multiply_glwe_ggsw_batch(c, n, glwe + at * w, ggsw + at * sw, out + at * w); });
+    if (spf_status s = group_args(g, B && (!glwe || !ggsw || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_MULTIPLY_GGSW_GLWE), B, {ggsw, glwe}, out,
+                       [](spf_ctx* c, size_t n, Rows ggsw, Rows glwe, Rows out) { return spf_multiply_glwe_ggsw_batch(c, n, glwe, ggsw, out); });
 }
 
 spf_status spf_group_gate_bootstrap_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = lwe1_words(g->prm), wo = glwe_words(g->prm);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_gate_bootstrap_batch(c, n, in + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, gate_bootstrap_shape(g->prm), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_gate_bootstrap_batch(c, n, in, out); });
 }
 
 spf_status spf_group_keyswitch_circuit_bootstrap_batch(spf_group* g, size_t B, const uint64_t* in, double* out)
 {
-    SPF_GROUP_NULL(!in || !out);
-    const size_t wi = lwe1_words(g->prm), wo = 2 * ggsw_fft_complex(g->prm, g->prm.cbs_radix_count);
-    return group_split(g, B, [=](spf_ctx* c, size_t at, size_t n) { return spf_keyswitch_circuit_bootstrap_batch(c, n, in + at * wi, out + at * wo); });
+    if (spf_status s = group_args(g, B && (!in || !out))) return s;
+    return group_batch(g, spf_ops::shape(g->prm, spf_ops::OP_GATE_CBS), B, {in}, out,
+                       [](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_keyswitch_circuit_bootstrap_batch(c, n, in, out); });
 }
-#undef SPF_GROUP_NULL
 
 spf_status spf_group_l1ggsw_constant(spf_group* g, int bit, double* out)
 {

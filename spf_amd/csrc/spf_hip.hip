@@ -369,7 +369,7 @@ GenericShape generic_shape(const spf_ctx* c)
 
 spf_status blind_rotate_args(spf_ctx* c, size_t B, uint32_t log_chi, uint32_t log_v)
 {
-    if (B > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    if (B > kBatchMax) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
     // modulus switch needs log_modulus - log_v >= 1 and shifts below 64
     if (log_v >= c->log_n + 1 || log_chi >= 52) return fail(c, SPF_ERR_INVALID_ARGUMENT, "log_v / log_chi out of range");
     return SPF_OK;
@@ -596,6 +596,50 @@ spf_status host_call(spf_ctx* c, std::initializer_list<HostIn> ins, size_t out_b
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return SPF_OK;
     });
+}
+
+// an operand of host_batch(): the caller's rows and the staging buffer they go to
+struct HostRows {
+    DevBuf& buf;
+    const void* host;
+};
+// the rows of one operand or of the result as host_batch() and group_batch() hand them to their lambda, whose parameter names
+// the element type (uint64_t words, or the doubles of a spectrum)
+struct Rows {
+    void* p;
+    template <class T> operator T*() const { return static_cast<T*>(p); }
+};
+
+// host_call() for B items of `sh`: operand k of `ins` is B * sh.in_words[k] words, the result B * sh.out_words; `enqueue` gets
+// the device pointers of the operands, in the order of `ins`, then that of the result.  B = 0 is SPF_OK and touches nothing.
+template <class Enqueue>
+spf_status host_batch(spf_ctx* c, const BatchShape& sh, size_t B, std::initializer_list<HostRows> ins, void* host_out, Enqueue&& enqueue)
+{
+    if (B == 0) return SPF_OK;
+    const HostRows* o = ins.begin();
+    const auto in = [&](size_t k) { return k < ins.size() ? HostIn{o[k].buf, o[k].host, B * sh.in_words[k] * 8} : HostIn{c->in, nullptr, 0}; };
+    return host_call(c, {in(0), in(1), in(2)}, B * sh.out_words * 8, host_out, [&]() -> spf_status {
+        const Rows out{c->out.p};
+        if constexpr (std::is_invocable_v<Enqueue, Rows, Rows>) return enqueue(Rows{o[0].buf.p}, out);
+        else if constexpr (std::is_invocable_v<Enqueue, Rows, Rows, Rows>) return enqueue(Rows{o[0].buf.p}, Rows{o[1].buf.p}, out);
+        else return enqueue(Rows{o[0].buf.p}, Rows{o[1].buf.p}, Rows{o[2].buf.p}, out);
+    });
+}
+
+spf_status batch_limit(spf_ctx* c, const BatchShape& sh, size_t B)
+{
+    return B > sh.max_batch ? fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large") : SPF_OK;
+}
+
+bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+// whether the result of B items of `sh` at `out` overlaps their operand k at `in`
+bool batch_overlaps(const BatchShape& sh, size_t B, const void* out, const void* in, int k = 0)
+{
+    return ranges_overlap(out, B * sh.out_words * 8, in, B * sh.in_words[k] * 8);
 }
 
 } // namespace
@@ -1172,8 +1216,7 @@ spf_status spf_circuit_bootstrap_pbs_dev(spf_ctx* c, void* stream, size_t B, con
 // the circuit-bootstrap tail launches cbs_radix_count units per ciphertext
 static spf_status tail_batch_args(spf_ctx* c, size_t B)
 {
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    return SPF_OK;
+    return B > kBatchMaxRows ? fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large") : SPF_OK;
 }
 
 static spf_status tail_supported(spf_ctx* c)
@@ -1386,7 +1429,7 @@ spf_status spf_glwe_mul_xn_dev(spf_ctx* c, void* stream, size_t B, const uint64_
 static const char* packed_shape_error(const spf_params& p, size_t B, size_t n_bits)
 {
     if (n_bits == 0 || n_bits > p.polynomial_degree) return "n_bits must be in 1 ..= polynomial_degree";
-    if (B > 0x0fffffffu / n_bits) return "B * n_bits above 0x0fffffff";
+    if (B > packed_shape(p, n_bits, SPF_VAL_GLWE1, SPF_VAL_GLWE1, true).max_batch) return "B * n_bits above 0x0fffffff";
     return nullptr;
 }
 
@@ -1439,9 +1482,8 @@ spf_status spf_glwe_pack_dev(spf_ctx* c, void* stream, size_t B, size_t n_bits, 
 {
     spf_status st = packed_args(c, B, n_bits, d_bits, d_out);
     if (st != SPF_OK || B == 0) return st;
-    const uintptr_t in0 = (uintptr_t)d_bits, in1 = in0 + B * n_bits * glwe_words(c->prm) * 8;
-    const uintptr_t out0 = (uintptr_t)d_out, out1 = out0 + B * glwe_words(c->prm) * 8;
-    if (out0 < in1 && in0 < out1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the packed output overlaps the bit GLWEs");
+    if (batch_overlaps(packed_shape(c->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_GLWE1, true), B, d_out, d_bits))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the packed output overlaps the bit GLWEs");
     std::lock_guard<std::recursive_mutex> g(c->mu);
     HIPCHK(c, hipSetDevice(c->device));
     return launch_glwe_pack(c, (hipStream_t)stream, B, n_bits, d_bits, d_out);
@@ -1710,7 +1752,7 @@ static const char* blind_rotation_shape_error(const spf_params& p, size_t B, siz
     while ((1u << log_n) < p.polynomial_degree) log_n++;
     if (n_bits == 0) return "n_bits must be at least 1";
     if (n_bits > log_n || log_stride > log_n - n_bits) return "n_bits + log_stride above log2(polynomial_degree)";
-    if (B > 0x0fffffffu / n_bits) return "B * n_bits above 0x0fffffff";
+    if (B > blind_rotation_shape(p, n_bits).max_batch) return "B * n_bits above 0x0fffffff";
     return nullptr;
 }
 
@@ -1734,10 +1776,9 @@ spf_status spf_blind_rotation_dev(spf_ctx* c, void* stream, size_t B, size_t n_b
     if (!c->generic && (c->prm.cbs_radix_log != 4 || c->prm.cbs_radix_count != 4))
         return fail(c, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
     if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm), sel = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count);
-    const uintptr_t out0 = (uintptr_t)d_out, out1 = out0 + B * gw * 8;
-    const uintptr_t in0 = (uintptr_t)d_in, sh0 = (uintptr_t)d_shift;
-    if ((out0 < in0 + B * gw * 8 && in0 < out1) || (out0 < sh0 + B * n_bits * sel * sizeof(c64) && sh0 < out1))
+    const BatchShape sh = blind_rotation_shape(c->prm, n_bits);
+    const size_t gw = sh.out_words, sel = ggsw_fft_complex(c->prm, c->prm.cbs_radix_count);
+    if (batch_overlaps(sh, B, d_out, d_in, 1) || batch_overlaps(sh, B, d_out, d_shift, 0))
         return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps an input");
     hipStream_t s = (hipStream_t)stream;
     std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -1778,14 +1819,14 @@ spf_status spf_blind_rotation_dev(spf_ctx* c, void* stream, size_t B, size_t n_b
 
 // ---------------------------------------------------------------- host-pointer forms
 //
-// Each form checks every argument it can see, then reaches the device through staged() / host_call() only.
+// Each form checks every argument it can see, then reaches the device through host_batch() on its batch shape (spf_ops.hpp), or,
+// where it has staging of its own, through staged() / host_call().
 
 spf_status spf_keyswitch_lwe_l1_lwe_l0_batch(spf_ctx* c, size_t B, const uint64_t* in, uint64_t* out)
 {
     if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    return host_call(c, {{c->in, in, B * lwe1_words(c->prm) * 8}}, B * lwe0_words(c->prm) * 8, out,
-                     [&] { return launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p); });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_KEYSWITCH), B, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, uint64_t* d_out) { return launch_keyswitch(c, c->stream, B, d_in, d_out); });
 }
 
 // Bootstrap a device-resident batch and bring the outputs to the caller's host buffer, in SLICES of one
@@ -1795,10 +1836,10 @@ spf_status spf_keyswitch_lwe_l1_lwe_l0_batch(spf_ctx* c, size_t B, const uint64_
 // added 10-15 % to a call, sliced only the last slice's copy is exposed.  (A pageable destination makes
 // hipMemcpyAsync block the host until that copy is done — which is why every kernel is enqueued first.)
 static spf_status bootstrap_sliced_to_host(spf_ctx* c, size_t B, const uint64_t* d_lwe, const uint64_t* d_lut,
-                                           size_t lut_stride, uint32_t log_chi, uint32_t log_v, uint64_t rot, size_t ow,
+                                           size_t lut_stride, uint32_t log_chi, uint32_t log_v, uint64_t rot, const BatchShape& sh,
                                            bool extract, uint64_t* host_out)
 {
-    const size_t lw = lwe0_words(c->prm);
+    const size_t lw = sh.in_words[0], ow = sh.out_words;
     const size_t round = 4 * (size_t)c->n_cu;
     const size_t slice = B > round ? round : B;
     const size_t n_slices = (B + slice - 1) / slice;
@@ -1843,16 +1884,17 @@ static spf_status pbs_host(spf_ctx* c, size_t B, const uint64_t* lwe, const uint
     if (lut_stride && lut_stride < glwe_words(c->prm)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "lut_stride smaller than a GLWE");
     spf_status s = blind_rotate_args(c, B, log_chi, log_v);
     if (s != SPF_OK) return s;
-    const size_t lw = B * lwe0_words(c->prm) * 8, ow = extract ? lwe1_words(c->prm) : glwe_words(c->prm);
+    const BatchShape sh = pbs_shape(c->prm, extract);
+    const size_t lw = B * sh.in_words[0] * 8;
     const size_t lut_words = lut_stride ? (B - 1) * lut_stride + glwe_words(c->prm) : glwe_words(c->prm);
-    return staged(c, {{c->in, lwe, lw}, {c->mid, rhs, lw}, {c->aux, lut, lut_words * 8}}, B * ow * 8, [&]() -> spf_status {
+    return staged(c, {{c->in, lwe, lw}, {c->mid, rhs, lw}, {c->aux, lut, lut_words * 8}}, B * sh.out_words * 8, [&]() -> spf_status {
         if (rhs) {
             spf_status st = launch_lwe_pack(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, shift_bits,
                                             (uint64_t*)c->in.p);
             if (st != SPF_OK) return st;
         }
         return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->in.p, lut ? (const uint64_t*)c->aux.p : c->d_cbs_lut,
-                                        lut ? lut_stride : 0, log_chi, log_v, rot, ow, extract, out);
+                                        lut ? lut_stride : 0, log_chi, log_v, rot, sh, extract, out);
     });
 }
 
@@ -1888,102 +1930,83 @@ spf_status spf_sample_extract_l1_batch(spf_ctx* c, size_t B, const uint64_t* glw
 {
     if (!c || (B && (!glwe || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (idx >= c->prm.polynomial_degree) return fail(c, SPF_ERR_INVALID_ARGUMENT, "sample_extract index >= polynomial_degree");
-    if (B == 0) return SPF_OK;
-    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, B * lwe1_words(c->prm) * 8, out, [&] {
-        return spf_sample_extract_l1_dev(c, c->stream, B, (const uint64_t*)c->in.p, idx, (uint64_t*)c->out.p);
-    });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_SAMPLE_EXTRACT), B, {{c->in, glwe}}, out,
+                      [&](const uint64_t* d_glwe, uint64_t* d_out) { return spf_sample_extract_l1_dev(c, c->stream, B, d_glwe, idx, d_out); });
 }
 
 spf_status spf_glwe_not_batch(spf_ctx* c, size_t B, const uint64_t* in, uint64_t* out)
 {
     if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, in, gw}}, gw, out,
-                     [&] { return spf_glwe_not_dev(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p); });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_NOT), B, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, uint64_t* d_out) { return spf_glwe_not_dev(c, c->stream, B, d_in, d_out); });
 }
 
 spf_status spf_glwe_xor_batch(spf_ctx* c, size_t B, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, a, gw}, {c->mid, b, gw}}, gw, out, [&] {
-        return spf_glwe_xor_dev(c, c->stream, B, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p, (uint64_t*)c->out.p);
-    });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_GLWE_ADD), B, {{c->in, a}, {c->mid, b}}, out,
+                      [&](const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out) { return spf_glwe_xor_dev(c, c->stream, B, d_a, d_b, d_out); });
 }
 
 spf_status spf_glwe_mul_xn_batch(spf_ctx* c, size_t B, const uint64_t* in, size_t n, uint64_t* out)
 {
     if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, in, gw}}, gw, out,
-                     [&] { return spf_glwe_mul_xn_dev(c, c->stream, B, (const uint64_t*)c->in.p, n, (uint64_t*)c->out.p); });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_MUL_XN), B, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, uint64_t* d_out) { return spf_glwe_mul_xn_dev(c, c->stream, B, d_in, n, d_out); });
 }
 
 spf_status spf_glwe_pack_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* bits, uint64_t* out)
 {
     spf_status s = packed_args(c, B, n_bits, bits, out);
-    if (s != SPF_OK || B == 0) return s;
-    const size_t gw = glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, bits, B * n_bits * gw}}, B * gw, out, [&] {
-        return spf_glwe_pack_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    });
+    if (s != SPF_OK) return s;
+    return host_batch(c, packed_shape(c->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_GLWE1, true), B, {{c->in, bits}}, out,
+                      [&](const uint64_t* d_bits, uint64_t* d_out) { return spf_glwe_pack_dev(c, c->stream, B, n_bits, d_bits, d_out); });
 }
 
 spf_status spf_glwe_unpack_l1_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, uint64_t* lwe1_out)
 {
     spf_status s = packed_args(c, B, n_bits, glwe, lwe1_out);
-    if (s != SPF_OK || B == 0) return s;
-    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, B * n_bits * lwe1_words(c->prm) * 8, lwe1_out, [&] {
-        return spf_glwe_unpack_l1_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    });
+    if (s != SPF_OK) return s;
+    return host_batch(c, packed_shape(c->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_LWE1, false), B, {{c->in, glwe}}, lwe1_out,
+                      [&](const uint64_t* d_glwe, uint64_t* d_out) { return spf_glwe_unpack_l1_dev(c, c->stream, B, n_bits, d_glwe, d_out); });
 }
 
 spf_status spf_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!sel || !a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->aux, sel, sw}, {c->in, a, gw}, {c->mid, b, gw}}, gw, out, [&] {
-        return spf_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p,
-                            (uint64_t*)c->out.p);
-    });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_CMUX), B,
+                      {{c->aux, sel}, {c->in, a}, {c->mid, b}}, out, [&](const double* d_sel, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out) {
+                          return spf_cmux_dev(c, c->stream, B, d_sel, d_a, d_b, d_out);
+                      });
 }
 
 spf_status spf_blind_rotation_batch(spf_ctx* c, size_t B, size_t n_bits, size_t log_stride, const double* shift, const uint64_t* in,
                                     uint64_t* out)
 {
     spf_status s = blind_rotation_args(c, B, n_bits, log_stride, shift, in, out);
-    if (s != SPF_OK || B == 0) return s;
-    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * n_bits * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->aux, shift, sw}, {c->in, in, gw}}, gw, out, [&] {
-        return spf_blind_rotation_dev(c, c->stream, B, n_bits, log_stride, (const double*)c->aux.p, (const uint64_t*)c->in.p,
-                                      (uint64_t*)c->out.p);
-    });
+    if (s != SPF_OK) return s;
+    return host_batch(c, blind_rotation_shape(c->prm, n_bits), B, {{c->aux, shift}, {c->in, in}}, out,
+                      [&](const double* d_shift, const uint64_t* d_in, uint64_t* d_out) {
+                          return spf_blind_rotation_dev(c, c->stream, B, n_bits, log_stride, d_shift, d_in, d_out);
+                      });
 }
 
 spf_status spf_glev_cmux_batch(spf_ctx* c, size_t B, const double* sel, const uint64_t* a, const uint64_t* b, uint64_t* out)
 {
     if (!c || (B && (!sel || !a || !b || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t ev = B * glwe_words(c->prm) * 8 * c->prm.cbs_radix_count;
-    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->aux, sel, sw}, {c->in, a, ev}, {c->mid, b, ev}}, ev, out, [&] {
-        return spf_glev_cmux_dev(c, c->stream, B, (const double*)c->aux.p, (const uint64_t*)c->in.p, (const uint64_t*)c->mid.p,
-                                 (uint64_t*)c->out.p);
-    });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_GLEV_CMUX), B,
+                      {{c->aux, sel}, {c->in, a}, {c->mid, b}}, out, [&](const double* d_sel, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out) {
+                          return spf_glev_cmux_dev(c, c->stream, B, d_sel, d_a, d_b, d_out);
+                      });
 }
 
 spf_status spf_multiply_glwe_ggsw_batch(spf_ctx* c, size_t B, const uint64_t* glwe, const double* ggsw, uint64_t* out)
 {
     if (!c || (B && (!glwe || !ggsw || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    const size_t gw = B * glwe_words(c->prm) * 8, sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->aux, ggsw, sw}, {c->in, glwe, gw}}, gw, out, [&] {
-        return spf_multiply_glwe_ggsw_dev(c, c->stream, B, (const uint64_t*)c->in.p, (const double*)c->aux.p, (uint64_t*)c->out.p);
-    });
+    return host_batch(c, spf_ops::shape(c->prm, spf_ops::OP_MULTIPLY_GGSW_GLWE), B, {{c->aux, ggsw}, {c->in, glwe}}, out,
+                      [&](const double* d_ggsw, const uint64_t* d_glwe, uint64_t* d_out) {
+                          return spf_multiply_glwe_ggsw_dev(c, c->stream, B, d_glwe, d_ggsw, d_out);
+                      });
 }
 
 static spf_status load_fft_key(spf_ctx* c, int which, const double* src, size_t n_complex, size_t want, bool* ready)
@@ -2054,11 +2077,10 @@ spf_status spf_poly_fft_dev(spf_ctx* c, void* stream, size_t n_polys, const uint
 spf_status spf_poly_fft_batch(spf_ctx* c, size_t n_polys, const uint64_t* in, double* out)
 {
     if (!c || (n_polys && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (n_polys == 0) return SPF_OK;
-    if (n_polys > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    const size_t bytes = n_polys * c->prm.polynomial_degree * 8;
-    return host_call(c, {{c->in, in, bytes}}, bytes, out,
-                     [&] { return spf_poly_fft_dev(c, c->stream, n_polys, (const uint64_t*)c->in.p, (double*)c->out.p); });
+    const BatchShape sh = poly_fft_shape(c->prm);
+    if (spf_status s = batch_limit(c, sh, n_polys)) return s;
+    return host_batch(c, sh, n_polys, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, double* d_out) { return spf_poly_fft_dev(c, c->stream, n_polys, d_in, d_out); });
 }
 
 // A key in standard form: the words go into the key blob as they are (same bytes as its spectra) and are transformed there;
@@ -2114,49 +2136,39 @@ spf_status spf_load_scheme_switch_key_std(spf_ctx* c, const uint64_t* ssk, size_
 spf_status spf_mod_switch_trace_and_rotate_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, uint64_t* glev_out)
 {
     if (!c || (B && (!glwe_in || !glev_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    spf_status s = tail_batch_args(c, B);
-    if (s != SPF_OK) return s;
-    const size_t gw = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, glwe_in, gw}}, gw * c->prm.cbs_radix_count, glev_out, [&] {
-        return spf_mod_switch_trace_and_rotate_dev(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
-    });
+    const BatchShape sh = trace_shape(c->prm);
+    if (spf_status s = batch_limit(c, sh, B)) return s;
+    return host_batch(c, sh, B, {{c->in, glwe_in}}, glev_out,
+                      [&](const uint64_t* d_glwe, uint64_t* d_glev) { return spf_mod_switch_trace_and_rotate_dev(c, c->stream, B, d_glwe, d_glev); });
 }
 
 spf_status spf_scheme_switch_batch(spf_ctx* c, size_t B, const uint64_t* glev_in, double* ggsw_out)
 {
     if (!c || (B && (!glev_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    spf_status s = tail_batch_args(c, B);
-    if (s != SPF_OK) return s;
-    const size_t ev = B * glwe_words(c->prm) * 8 * c->prm.cbs_radix_count;
-    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->in, glev_in, ev}}, sw, ggsw_out,
-                     [&] { return spf_scheme_switch_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p); });
+    const BatchShape sh = spf_ops::shape(c->prm, spf_ops::OP_SCHEME_SWITCH);
+    if (spf_status s = batch_limit(c, sh, B)) return s;
+    return host_batch(c, sh, B, {{c->in, glev_in}}, ggsw_out,
+                      [&](const uint64_t* d_glev, double* d_ggsw) { return spf_scheme_switch_dev(c, c->stream, B, d_glev, d_ggsw); });
 }
 
 spf_status spf_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe0_in, double* ggsw_out)
 {
     if (!c || (B && (!lwe0_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    spf_status s = tail_batch_args(c, B);
-    if (s != SPF_OK) return s;
-    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->in, lwe0_in, B * lwe0_words(c->prm) * 8}}, sw, ggsw_out,
-                     [&] { return spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p); });
+    const BatchShape sh = spf_ops::shape(c->prm, spf_ops::OP_CBS);
+    if (spf_status s = batch_limit(c, sh, B)) return s;
+    return host_batch(c, sh, B, {{c->in, lwe0_in}}, ggsw_out,
+                      [&](const uint64_t* d_lwe, double* d_ggsw) { return spf_circuit_bootstrap_dev(c, c->stream, B, d_lwe, d_ggsw); });
 }
 
 spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe1_in, double* ggsw_out)
 {
     if (!c || (B && (!lwe1_in || !ggsw_out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    if (B == 0) return SPF_OK;
-    spf_status s = tail_batch_args(c, B);
-    if (s != SPF_OK) return s;
-    const size_t sw = B * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->in, lwe1_in, B * lwe1_words(c->prm) * 8}}, sw, ggsw_out, [&] {
+    const BatchShape sh = spf_ops::shape(c->prm, spf_ops::OP_GATE_CBS);
+    if (spf_status s = batch_limit(c, sh, B)) return s;
+    return host_batch(c, sh, B, {{c->in, lwe1_in}}, ggsw_out, [&](const uint64_t* d_lwe1, double* d_ggsw) {
         spf_status st = ensure(c, c->mid, B * lwe0_words(c->prm) * 8); // the level-0 LWE never leaves the device
-        if (st == SPF_OK) st = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
-        if (st == SPF_OK) st = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->mid.p, (double*)c->out.p);
+        if (st == SPF_OK) st = launch_keyswitch(c, c->stream, B, d_lwe1, (uint64_t*)c->mid.p);
+        if (st == SPF_OK) st = spf_circuit_bootstrap_dev(c, c->stream, B, (const uint64_t*)c->mid.p, d_ggsw);
         return st;
     });
 }
@@ -2164,11 +2176,9 @@ spf_status spf_keyswitch_circuit_bootstrap_batch(spf_ctx* c, size_t B, const uin
 spf_status spf_unpack_circuit_bootstrap_batch(spf_ctx* c, size_t B, size_t n_bits, const uint64_t* glwe, double* ggsw_out)
 {
     spf_status s = packed_args(c, B, n_bits, glwe, ggsw_out);
-    if (s != SPF_OK || B == 0) return s;
-    const size_t sw = B * n_bits * ggsw_fft_complex(c->prm, c->prm.cbs_radix_count) * 16;
-    return host_call(c, {{c->in, glwe, B * glwe_words(c->prm) * 8}}, sw, ggsw_out, [&] {
-        return spf_unpack_circuit_bootstrap_dev(c, c->stream, B, n_bits, (const uint64_t*)c->in.p, (double*)c->out.p);
-    });
+    if (s != SPF_OK) return s;
+    return host_batch(c, packed_shape(c->prm, n_bits, SPF_VAL_GLWE1, SPF_VAL_GGSW1, false), B, {{c->in, glwe}}, ggsw_out,
+                      [&](const uint64_t* d_glwe, double* d_ggsw) { return spf_unpack_circuit_bootstrap_dev(c, c->stream, B, n_bits, d_glwe, d_ggsw); });
 }
 
 spf_status spf_gate_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe1, uint64_t* glwe_out)
@@ -2178,12 +2188,12 @@ spf_status spf_gate_bootstrap_batch(spf_ctx* c, size_t B, const uint64_t* lwe1, 
     const uint32_t log_v = ceil_log2(c->prm.cbs_radix_count);
     spf_status s = blind_rotate_args(c, B, 0, log_v);
     if (s != SPF_OK) return s;
-    return staged(c, {{c->in, lwe1, B * lwe1_words(c->prm) * 8}}, B * glwe_words(c->prm) * 8, [&] {
-        spf_status st = ensure(c, c->mid, B * lwe0_words(c->prm) * 8); // the level-0 LWE never leaves the device
+    const BatchShape sh = gate_bootstrap_shape(c->prm), pbs = pbs_shape(c->prm, false); // (pbs: the second stage)
+    return staged(c, {{c->in, lwe1, B * sh.in_words[0] * 8}}, B * sh.out_words * 8, [&] {
+        spf_status st = ensure(c, c->mid, B * pbs.in_words[0] * 8); // the level-0 LWE never leaves the device
         if (st == SPF_OK) st = launch_keyswitch(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->mid.p);
         if (st != SPF_OK) return st;
-        return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->mid.p, c->d_cbs_lut, 0, 0, log_v, (uint64_t)1 << 62,
-                                        glwe_words(c->prm), false, glwe_out);
+        return bootstrap_sliced_to_host(c, B, (const uint64_t*)c->mid.p, c->d_cbs_lut, 0, 0, log_v, (uint64_t)1 << 62, pbs, false, glwe_out);
     });
 }
 
@@ -2483,14 +2493,19 @@ static const char* pufks_shape_error(const spf_params& p, size_t B, size_t lwe_c
 {
     if (lwe_count == 0) return "lwe_count must be at least 1";
     if (lwe_count > p.polynomial_degree) return "lwe_count above polynomial_degree";
-    if (B > 0x0fffffffu / lwe_count) return "B * lwe_count above 0x0fffffff";
+    if (B > pufks_shape(p, lwe_count, 0).max_batch) return "B * lwe_count above 0x0fffffff";
     return nullptr;
 }
 
-static spf_status pufks_args(spf_ctx* c, size_t B, size_t lwe_count, const void* in, const void* out)
+// What every form of the public functional keyswitch checks before the batch is touched, on `c` with its texts: the pointers (never
+// null, whatever B), the shape of the call, the key; *sh: the batch shape for the loaded key's from_dimension.
+static spf_status pufks_args(spf_ctx* c, size_t B, size_t lwe_count, const void* in, const void* out, BatchShape* sh)
 {
     if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
     if (const char* why = pufks_shape_error(c->prm, B, lwe_count)) return fail(c, SPF_ERR_INVALID_ARGUMENT, why);
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
+    *sh = pufks_shape(c->prm, lwe_count, c->pufks_n);
     return SPF_OK;
 }
 
@@ -2559,16 +2574,13 @@ static spf_status launch_pufks_tuned(spf_ctx* c, hipStream_t s, size_t B, uint32
 spf_status spf_public_functional_keyswitch_enqueue(spf_ctx* c, void* stream, size_t B, size_t lwe_count, const uint64_t* d_lwe_in,
                                                    uint64_t* d_glwe_out)
 {
-    spf_status st = pufks_args(c, B, lwe_count, d_lwe_in, d_glwe_out);
+    BatchShape sh;
+    spf_status st = pufks_args(c, B, lwe_count, d_lwe_in, d_glwe_out, &sh);
     if (st != SPF_OK) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
     if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm), in_bytes = B * lwe_count * ((size_t)c->pufks_n + 1) * 8;
-    {
-        const uintptr_t o0 = (uintptr_t)d_glwe_out, o1 = o0 + B * gw * 8, i0 = (uintptr_t)d_lwe_in;
-        if (o0 < i0 + in_bytes && i0 < o1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
-    }
+    if (batch_overlaps(sh, B, d_glwe_out, d_lwe_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    const size_t gw = sh.out_words;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     if (pufks_tuned(c))
@@ -2625,18 +2637,11 @@ static spf_status launch_pufks_rows(spf_ctx* c, hipStream_t s, size_t B, size_t 
 
 spf_status spf_public_functional_keyswitch_batch(spf_ctx* c, size_t B, size_t lwe_count, const uint64_t* lwe_in, uint64_t* glwe_out)
 {
-    spf_status s = pufks_args(c, B, lwe_count, lwe_in, glwe_out);
+    BatchShape sh;
+    spf_status s = pufks_args(c, B, lwe_count, lwe_in, glwe_out, &sh);
     if (s != SPF_OK) return s;
-    size_t n;
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "public functional keyswitch key not loaded");
-        n = c->pufks_n;
-    }
-    if (B == 0) return SPF_OK;
-    const size_t in_bytes = B * lwe_count * (n + 1) * 8, out_bytes = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, lwe_in, in_bytes}}, out_bytes, glwe_out, [&] {
-        return spf_public_functional_keyswitch_enqueue(c, c->stream, B, lwe_count, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    return host_batch(c, sh, B, {{c->in, lwe_in}}, glwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
+        return spf_public_functional_keyswitch_enqueue(c, c->stream, B, lwe_count, d_in, d_out);
     });
 }
 
@@ -2730,48 +2735,42 @@ static spf_status launch_pfks(spf_ctx* c, hipStream_t s, size_t M, const uint64_
     return SPF_OK;
 }
 
-static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+// What every form of the private functional keyswitch checks before the batch is touched, on `c` with its texts: the pointers (never
+// null, whatever B), the keys, the key index, the batch limit; *sh: the batch shape for the loaded keys' row.
+static spf_status pfks_args(spf_ctx* c, size_t key_index, size_t B, const void* in, const void* out, BatchShape* sh)
 {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
+    if (key_index >= c->pfks_keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
+    *sh = pfks_shape(c->prm, pfks_row_words(c));
+    return batch_limit(c, *sh, B);
 }
 
 spf_status spf_private_functional_keyswitch_enqueue(spf_ctx* c, void* stream, size_t key_index, size_t B, const uint64_t* d_lwe_in,
                                                     uint64_t* d_glwe_out)
 {
-    if (!c || !d_lwe_in || !d_glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    BatchShape sh;
+    spf_status st = pfks_args(c, key_index, B, d_lwe_in, d_glwe_out, &sh);
+    if (st != SPF_OK || B == 0) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
-    if (key_index >= c->pfks_keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm);
-    if (ranges_overlap(d_glwe_out, B * gw * 8, d_lwe_in, B * pfks_row_words(c) * 8))
-        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    if (batch_overlaps(sh, B, d_glwe_out, d_lwe_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
     HIPCHK(c, hipSetDevice(c->device));
-    return launch_pfks(c, (hipStream_t)stream, B, d_lwe_in, (uint32_t)key_index, 1, PfksDest{d_glwe_out, 1, gw, 0, 0});
+    return launch_pfks(c, (hipStream_t)stream, B, d_lwe_in, (uint32_t)key_index, 1, PfksDest{d_glwe_out, 1, sh.out_words, 0, 0});
 }
 
 spf_status spf_private_functional_keyswitch_batch(spf_ctx* c, size_t key_index, size_t B, const uint64_t* lwe_in, uint64_t* glwe_out)
 {
-    if (!c || !lwe_in || !glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    size_t rw;
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
-        if (key_index >= c->pfks_keys) return fail(c, SPF_ERR_INVALID_ARGUMENT, "key_index >= n_keys");
-        rw = pfks_row_words(c);
-    }
-    if (B > 0x0fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    const size_t out_bytes = B * glwe_words(c->prm) * 8;
-    return host_call(c, {{c->in, lwe_in, B * rw * 8}}, out_bytes, glwe_out, [&] {
-        return spf_private_functional_keyswitch_enqueue(c, c->stream, key_index, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    BatchShape sh;
+    spf_status st = pfks_args(c, key_index, B, lwe_in, glwe_out, &sh);
+    if (st != SPF_OK) return st;
+    return host_batch(c, sh, B, {{c->in, lwe_in}}, glwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
+        return spf_private_functional_keyswitch_enqueue(c, c->stream, key_index, B, d_in, d_out);
     });
 }
 
-// what `apply_pfks_on_ggsw_components` needs of the loaded keys, or why not
-static spf_status pfks_components_shape(spf_ctx* c)
+// what `apply_pfks_on_ggsw_components` needs of the loaded keys, or why not; under c->mu
+static spf_status pfks_components_keys(spf_ctx* c)
 {
     if (!c->pfks_ready) return fail(c, SPF_ERR_NO_KEY, "private functional keyswitch keys not loaded");
     if (c->pfks_keys != c->prm.glwe_size + 1 || c->pfks_p != 1 || c->pfks_n != c->prm.glwe_size * c->prm.polynomial_degree)
@@ -2779,60 +2778,70 @@ static spf_status pfks_components_shape(spf_ctx* c)
     return SPF_OK;
 }
 
-static size_t ggsw_words(const spf_params& p) { return (size_t)(p.glwe_size + 1) * p.cbs_radix_count * glwe_words(p); }
+// ... and what both of its forms check before the batch is touched: the pointers (never null), the keys, the batch limit
+static spf_status pfks_components_args(spf_ctx* c, size_t B, const void* in, const void* out, BatchShape* sh)
+{
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    spf_status st = pfks_components_keys(c);
+    if (st != SPF_OK) return st;
+    *sh = pfks_components_shape(c->prm, pfks_row_words(c));
+    return batch_limit(c, *sh, B);
+}
+
+// where launch_pfks places row (r, level) of item b of B * cbs_radix_count rows: the reference's [k+1][l_cbs][k+1][N]
+static PfksDest ggsw_components_dest(const spf_params& p, uint64_t* d_ggsw)
+{
+    return PfksDest{d_ggsw, p.cbs_radix_count, value_words(p, SPF_VAL_GGSW1), glwe_words(p), (size_t)p.cbs_radix_count * glwe_words(p)};
+}
 
 // `apply_pfks_on_ggsw_components` (circuit_bootstrapping.rs:485-514): GGSW row (r, level) = PFKS of LWE `level` under key r.  One
 // launch sequence: a row's digits are computed once and meet all k+1 keys.
 spf_status spf_apply_pfks_on_ggsw_components_enqueue(spf_ctx* c, void* stream, size_t B, const uint64_t* d_lwe_in, uint64_t* d_ggsw_out)
 {
-    if (!c || !d_lwe_in || !d_ggsw_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    BatchShape sh;
+    spf_status st = pfks_components_args(c, B, d_lwe_in, d_ggsw_out, &sh);
+    if (st != SPF_OK || B == 0) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    spf_status st = pfks_components_shape(c);
-    if (st != SPF_OK) return st;
-    const uint32_t L = c->prm.cbs_radix_count;
-    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    const size_t gw = glwe_words(c->prm);
-    if (ranges_overlap(d_ggsw_out, B * ggsw_words(c->prm) * 8, d_lwe_in, B * L * pfks_row_words(c) * 8))
-        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    if (batch_overlaps(sh, B, d_ggsw_out, d_lwe_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
     HIPCHK(c, hipSetDevice(c->device));
-    return launch_pfks(c, (hipStream_t)stream, B * L, d_lwe_in, 0, c->pfks_keys, PfksDest{d_ggsw_out, L, ggsw_words(c->prm), gw, (size_t)L * gw});
+    return launch_pfks(c, (hipStream_t)stream, B * c->prm.cbs_radix_count, d_lwe_in, 0, c->pfks_keys, ggsw_components_dest(c->prm, d_ggsw_out));
 }
 
 spf_status spf_apply_pfks_on_ggsw_components_batch(spf_ctx* c, size_t B, const uint64_t* lwe_in, uint64_t* ggsw_out)
 {
-    if (!c || !lwe_in || !ggsw_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    size_t rw;
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        spf_status st = pfks_components_shape(c);
-        if (st != SPF_OK) return st;
-        rw = pfks_row_words(c);
-    }
-    const uint32_t L = c->prm.cbs_radix_count;
-    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    const size_t out_bytes = B * ggsw_words(c->prm) * 8;
-    return host_call(c, {{c->in, lwe_in, B * L * rw * 8}}, out_bytes, ggsw_out, [&] {
-        return spf_apply_pfks_on_ggsw_components_enqueue(c, c->stream, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    BatchShape sh;
+    spf_status st = pfks_components_args(c, B, lwe_in, ggsw_out, &sh);
+    if (st != SPF_OK) return st;
+    return host_batch(c, sh, B, {{c->in, lwe_in}}, ggsw_out, [&](const uint64_t* d_in, uint64_t* d_out) {
+        return spf_apply_pfks_on_ggsw_components_enqueue(c, c->stream, B, d_in, d_out);
     });
+}
+
+// what both context forms check before the batch is touched: the pointers (never null), the keys of both stages, the radix, the limit
+static spf_status cbs_via_pfks_args(spf_ctx* c, size_t B, const void* in, const void* out, BatchShape* sh)
+{
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    spf_status st = pfks_components_keys(c);
+    if (st != SPF_OK) return st;
+    if (!c->bsk_ready) return fail(c, SPF_ERR_NO_KEY, "bootstrap key not loaded");
+    if ((uint64_t)c->prm.cbs_radix_log * c->prm.cbs_radix_count + 1 > 64)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "cbs_radix_log * cbs_radix_count above 63");
+    *sh = cbs_via_pfks_shape(c->prm);
+    return batch_limit(c, *sh, B);
 }
 
 // `circuit_bootstrap_via_pfks` (circuit_bootstrapping.rs:162-219): hi_noise_lwe_to_lo_noise_glwe, extract_and_rotate_lo_noise_glwe,
 // apply_pfks_on_ggsw_components, then every polynomial of the integer GGSW through the library's forward transform, in place
 spf_status spf_circuit_bootstrap_via_pfks_enqueue(spf_ctx* c, void* stream, size_t B, const uint64_t* d_lwe0_in, double* d_ggsw_fft_out)
 {
-    if (!c || !d_lwe0_in || !d_ggsw_fft_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    BatchShape sh;
+    spf_status st = cbs_via_pfks_args(c, B, d_lwe0_in, d_ggsw_fft_out, &sh);
+    if (st != SPF_OK || B == 0) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    spf_status st = pfks_components_shape(c);
-    if (st != SPF_OK) return st;
-    if (!c->bsk_ready) return fail(c, SPF_ERR_NO_KEY, "bootstrap key not loaded");
+    if (batch_overlaps(sh, B, d_ggsw_fft_out, d_lwe0_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
     const uint32_t L = c->prm.cbs_radix_count, N = c->prm.polynomial_degree, k = c->prm.glwe_size;
-    if ((uint64_t)c->prm.cbs_radix_log * L + 1 > 64) return fail(c, SPF_ERR_INVALID_ARGUMENT, "cbs_radix_log * cbs_radix_count above 63");
-    if (B > 0x0fffffffu / L) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    if (ranges_overlap(d_ggsw_fft_out, B * ggsw_words(c->prm) * 8, d_lwe0_in, B * lwe0_words(c->prm) * 8))
-        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t gw = glwe_words(c->prm), rw = (size_t)k * N + 1;
@@ -2851,24 +2860,18 @@ spf_status spf_circuit_bootstrap_via_pfks_enqueue(spf_ctx* c, void* stream, size
     }
     HIPCHK(c, hipGetLastError());
     uint64_t* d_ggsw = reinterpret_cast<uint64_t*>(d_ggsw_fft_out);
-    st = launch_pfks(c, s, B * L, d_rows, 0, c->pfks_keys, PfksDest{d_ggsw, L, ggsw_words(c->prm), gw, (size_t)L * gw});
+    st = launch_pfks(c, s, B * L, d_rows, 0, c->pfks_keys, ggsw_components_dest(c->prm, d_ggsw));
     if (st != SPF_OK) return st;
     return launch_poly_fft(c, s, B * (k + 1) * L * (k + 1), d_ggsw, reinterpret_cast<c64*>(d_ggsw));
 }
 
 spf_status spf_circuit_bootstrap_via_pfks_batch(spf_ctx* c, size_t B, const uint64_t* lwe0_in, double* ggsw_fft_out)
 {
-    if (!c || !lwe0_in || !ggsw_fft_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        spf_status st = pfks_components_shape(c);
-        if (st != SPF_OK) return st;
-    }
-    if (B > 0x0fffffffu / c->prm.cbs_radix_count) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    if (B == 0) return SPF_OK;
-    const size_t out_bytes = B * ggsw_words(c->prm) * 8;
-    return host_call(c, {{c->in, lwe0_in, B * lwe0_words(c->prm) * 8}}, out_bytes, ggsw_fft_out, [&] {
-        return spf_circuit_bootstrap_via_pfks_enqueue(c, c->stream, B, (const uint64_t*)c->in.p, (double*)c->out.p);
+    BatchShape sh;
+    spf_status st = cbs_via_pfks_args(c, B, lwe0_in, ggsw_fft_out, &sh);
+    if (st != SPF_OK) return st;
+    return host_batch(c, sh, B, {{c->in, lwe0_in}}, ggsw_fft_out, [&](const uint64_t* d_in, double* d_out) {
+        return spf_circuit_bootstrap_via_pfks_enqueue(c, c->stream, B, d_in, d_out);
     });
 }
 
@@ -2962,17 +2965,18 @@ spf_status spf_load_lwe_linear_weights(spf_ctx* c, uint32_t slot, size_t M, size
     return SPF_OK;
 }
 
-// what a call needs of the slot and the kind, or why not; under c->mu
-static spf_status lwe_linear_shape(spf_ctx* c, uint32_t slot, spf_value_kind kind, size_t B, const LweLinearSlot** l, size_t* W)
+// What every form of the linear maps checks before the batch is touched, on `c` with its texts: the pointers (never null, whatever
+// B), the slot, the kind, the weights, the batch limit; *sh: the batch shape for the slot's M and K.
+static spf_status lwe_linear_args(spf_ctx* c, uint32_t slot, spf_value_kind kind, size_t B, const void* in, const void* out, BatchShape* sh)
 {
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
     if (slot >= SPF_LWE_LINEAR_SLOTS)
         return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_LWE_LINEAR_SLOTS = " + std::to_string(SPF_LWE_LINEAR_SLOTS));
     if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kind must be SPF_VAL_LWE0 or SPF_VAL_LWE1");
     if (!c->lin[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no weights loaded in slot " + std::to_string(slot));
-    *l = &c->lin[slot];
-    *W = kind == SPF_VAL_LWE0 ? lwe0_words(c->prm) : lwe1_words(c->prm);
-    if (B > 0x0fffffffu / std::max((*l)->M, (*l)->K)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
-    return SPF_OK;
+    *sh = lwe_linear_batch_shape(c->prm, c->lin[slot].M, c->lin[slot].K, kind);
+    return batch_limit(c, *sh, B);
 }
 
 // Which product kernel serves a call where both are legal: SPF_LWE_LINEAR_PATH=valu | mfma (diagnostic; read at every call)
@@ -2985,16 +2989,13 @@ static int lwe_linear_forced_path()
 spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* d_lwe_in,
                                   uint64_t* d_lwe_out)
 {
-    if (!c || !d_lwe_in || !d_lwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    BatchShape sh;
+    spf_status st = lwe_linear_args(c, slot, kind, B, d_lwe_in, d_lwe_out, &sh);
+    if (st != SPF_OK || B == 0) return st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
-    const LweLinearSlot* lp;
-    size_t W;
-    spf_status st = lwe_linear_shape(c, slot, kind, B, &lp, &W);
-    if (st != SPF_OK) return st;
-    if (B == 0) return SPF_OK;
-    const LweLinearSlot& l = *lp;
-    const size_t M = l.M, K = l.K;
-    if (ranges_overlap(d_lwe_out, B * M * W * 8, d_lwe_in, B * K * W * 8)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    if (batch_overlaps(sh, B, d_lwe_out, d_lwe_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    const LweLinearSlot& l = c->lin[slot];
+    const size_t M = l.M, K = l.K, W = value_words(c->prm, kind);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     const size_t item_planes = 8 * W * l.Kpad; // bytes of one item's byte planes
@@ -3062,19 +3063,12 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
 
 spf_status spf_lwe_linear_batch(spf_ctx* c, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t* lwe_in, uint64_t* lwe_out)
 {
-    if (!c || !lwe_in || !lwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
-    size_t M, K, W;
-    {
-        std::lock_guard<std::recursive_mutex> g(c->mu);
-        const LweLinearSlot* l;
-        spf_status st = lwe_linear_shape(c, slot, kind, B, &l, &W);
-        if (st != SPF_OK) return st;
-        M = l->M; K = l->K;
-    }
-    if (B == 0) return SPF_OK;
-    if (ranges_overlap(lwe_out, B * M * W * 8, lwe_in, B * K * W * 8)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
-    return host_call(c, {{c->in, lwe_in, B * K * W * 8}}, B * M * W * 8, lwe_out, [&] {
-        return spf_lwe_linear_enqueue(c, c->stream, slot, kind, B, (const uint64_t*)c->in.p, (uint64_t*)c->out.p);
+    BatchShape sh;
+    spf_status st = lwe_linear_args(c, slot, kind, B, lwe_in, lwe_out, &sh);
+    if (st != SPF_OK) return st;
+    if (batch_overlaps(sh, B, lwe_out, lwe_in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    return host_batch(c, sh, B, {{c->in, lwe_in}}, lwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
+        return spf_lwe_linear_enqueue(c, c->stream, slot, kind, B, d_in, d_out);
     });
 }
 

@@ -3,6 +3,8 @@
 // The library runs the ten `FheOp` kinds of `CircuitProcessor::exec_op` (circuit_processor/mod.rs:255-540) through the gate graph,
 // the pool by host pointer, the pool by handle and the device group.  Everything those routes have to agree on lives here:
 //   * the size of a ciphertext of each spf_value_kind (value_words / value_bytes over the four word helpers);
+//   * the shape of a batch — words per item of each operand and of the result, the batch limit — that the device-pointer, the
+//     host-pointer and the group form of an entry point share (BatchShape: one function per family; spf_ops::shape for the table);
 //   * ONE table row per operation: the spf_graph_op it answers to, arity, operand kinds, result kind, the scheduling flags and
 //     the rule for its parameter — an operation is DECLARED by adding its row (and its arm in launch_op);
 //   * the parameter rule as a function (op_param);
@@ -36,6 +38,70 @@ inline size_t value_words(const spf_params& p, int kind)
     }
 }
 inline size_t value_bytes(const spf_params& p, int kind) { return 8 * value_words(p, kind); }
+
+// ---------------------------------------------------------------- batch shapes
+// What the three forms of a batched entry point (device pointers, host pointers, group) have to agree on: the 64-bit words ONE item
+// of each operand and of the result occupies, and the largest batch.  One function per family of entry points, from spf_params and
+// the plain numbers the family depends on (no spf_ctx: the context-level checks in spf_hip.hip read those numbers under its lock).
+struct BatchShape {
+    int n_in;
+    size_t in_words[3];
+    size_t out_words;
+    size_t max_batch;
+};
+constexpr size_t kBatchMax = 0x7fffffff;     // one launch of a kernel that takes one unit per item
+constexpr size_t kBatchMaxRows = 0x0fffffff; // ... that takes several units or rows per item: the limit is on items * rows
+
+// every operand and the result one ciphertext of a spf_value_kind per item
+inline BatchShape kinds_shape(const spf_params& p, size_t max_batch, int out, int in0, int in1 = -1, int in2 = -1)
+{
+    return {in2 >= 0 ? 3 : in1 >= 0 ? 2 : 1, {value_words(p, in0), value_words(p, in1), value_words(p, in2)}, value_words(p, out), max_batch};
+}
+// the forward transform: one polynomial of N words into its N/2 complex bins
+inline BatchShape poly_fft_shape(const spf_params& p) { return {1, {p.polynomial_degree, 0, 0}, p.polynomial_degree, kBatchMax}; }
+// the bootstraps by a lookup table: one or two level-0 LWEs in, a GLWE or its sample extract out; the table is the last operand and
+// advances by the caller's lut_stride (0: one table for the batch — what it occupies in all is the host form's to work out)
+inline BatchShape pbs_shape(const spf_params& p, bool extract, bool bivariate = false, size_t lut_stride = 0)
+{
+    BatchShape sh = kinds_shape(p, kBatchMax, extract ? SPF_VAL_LWE1 : SPF_VAL_GLWE1, SPF_VAL_LWE0, bivariate ? SPF_VAL_LWE0 : -1);
+    sh.in_words[sh.n_in++] = lut_stride;
+    return sh;
+}
+// (an operation of the table below: spf_ops::shape)
+// the two stages of a circuit bootstrap that are no operation of the table: lo-noise GLWE -> GLEV, and the fused gate LWE1 -> GLWE
+inline BatchShape trace_shape(const spf_params& p) { return kinds_shape(p, kBatchMaxRows, SPF_VAL_GLEV1, SPF_VAL_GLWE1); }
+inline BatchShape gate_bootstrap_shape(const spf_params& p) { return kinds_shape(p, kBatchMax, SPF_VAL_GLWE1, SPF_VAL_LWE1); }
+// packed integers: n_bits ciphertexts of `in` per item into one of `out` (pack), or one of `in` into n_bits of `out` (the unpacks)
+inline BatchShape packed_shape(const spf_params& p, size_t n_bits, int in, int out, bool pack)
+{
+    return {1, {value_words(p, in) * (pack ? n_bits : 1), 0, 0}, value_words(p, out) * (pack ? 1 : n_bits), n_bits ? kBatchMaxRows / n_bits : 0};
+}
+// blind rotation by an encrypted shift: an item's n_bits selectors, then its GLWE
+inline BatchShape blind_rotation_shape(const spf_params& p, size_t n_bits)
+{
+    return {2, {n_bits * value_words(p, SPF_VAL_GGSW1), glwe_words(p), 0}, glwe_words(p), n_bits ? kBatchMaxRows / n_bits : 0};
+}
+// public functional keyswitch: lwe_count rows of the key's from_dimension + 1 words into one GLWE
+inline BatchShape pufks_shape(const spf_params& p, size_t lwe_count, size_t from_dimension)
+{
+    return {1, {lwe_count * (from_dimension + 1), 0, 0}, glwe_words(p), lwe_count ? kBatchMaxRows / lwe_count : 0};
+}
+// private functional keyswitch: one row of the keys' lwe_count * (from_dimension + 1) words into one GLWE; the GGSW components:
+// cbs_radix_count such rows into one integer-form GGSW (as many words as its spectrum)
+inline BatchShape pfks_shape(const spf_params& p, size_t row_words) { return {1, {row_words, 0, 0}, glwe_words(p), kBatchMaxRows}; }
+inline BatchShape pfks_components_shape(const spf_params& p, size_t row_words)
+{
+    return {1, {p.cbs_radix_count * row_words, 0, 0}, value_words(p, SPF_VAL_GGSW1), p.cbs_radix_count ? kBatchMaxRows / p.cbs_radix_count : 0};
+}
+inline BatchShape cbs_via_pfks_shape(const spf_params& p)
+{
+    return kinds_shape(p, p.cbs_radix_count ? kBatchMaxRows / p.cbs_radix_count : 0, SPF_VAL_GGSW1, SPF_VAL_LWE0);
+}
+// plaintext linear maps: K ciphertexts of `kind` (a level-0 or level-1 LWE) into M
+inline BatchShape lwe_linear_batch_shape(const spf_params& p, size_t M, size_t K, int kind)
+{
+    return {1, {K * value_words(p, kind), 0, 0}, M * value_words(p, kind), kBatchMaxRows / (M > K ? M : K ? K : 1)};
+}
 
 // ---------------------------------------------------------------- the operation table
 namespace spf_ops {
@@ -100,6 +166,14 @@ inline void in_out_bytes(const spf_params& p, int op, size_t (&in)[3], size_t& o
 {
     for (int k = 0; k < 3; k++) in[k] = value_bytes(p, kOps[op].in_kind[k]); // (kNone: 0 bytes)
     out = value_bytes(p, kOps[op].out_kind);
+}
+
+// the batch shape of the entry points that run operation `op`: its row's kinds, operands in the row's order; an operation that
+// ends in the circuit-bootstrap tail (a GGSW out) launches cbs_radix_count units per item
+inline BatchShape shape(const spf_params& p, int op)
+{
+    const OpRow& r = kOps[op];
+    return kinds_shape(p, r.out_kind == SPF_VAL_GGSW1 ? kBatchMaxRows : kBatchMax, r.out_kind, r.in_kind[0], r.in_kind[1], r.in_kind[2]);
 }
 
 // The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN

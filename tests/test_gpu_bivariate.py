@@ -238,6 +238,19 @@ def test_bivariate_group_and_errors(full):
         grp.pbs_bivariate(left, right, lut, 64)
     assert e.value.status == 1
     grp.close()
+    # a ragged split (2 + 1) with a table per ciphertext: both inputs and the table's stride follow the range
+    Q = TEST1
+    qs = O.gen_keyset(0xB1CAFE, Q, with_ksk=False)
+    small, grp = spf_amd.Engine(to_engine_params(Q)), spf_amd.Group(to_engine_params(Q), devices=[0, 0])
+    try:
+        for member in (small, grp):
+            member.load_bootstrap_key(qs.bsk_fft)
+        left3, right3 = random_lwe_batch(0xB602, 3, Q.lwe_n), random_lwe_batch(0xB603, 3, Q.lwe_n)
+        luts = np.stack([spf_amd.generate_bivariate_lut(f, 1, 1, small.params) for f in (lambda l, r: l ^ r, lambda l, r: l & r, lambda l, r: l | r)])
+        assert np.array_equal(grp.pbs_bivariate(left3, right3, luts, 1), small.pbs_bivariate(left3, right3, luts, 1))
+    finally:
+        grp.close()
+        small.close()
 
     # the device-pointer checks get one real buffer, large enough for every operand of B = 4 (nothing may launch)
     keyless = spf_amd.Engine(P)

@@ -8,9 +8,10 @@
 // spf_load_compute_key_bincode's and spf_load_compute_key_nonfft_bincode's size walks (ComputeKey, ComputeKeyNonFft), spf_generate_lut, params_supported / params_generic, and
 // spf_graph_add_{input,trivial,op,output} (the reference validates per task, task.rs:26-31) — every call must return a status,
 // never crash, never touch memory outside its buffers (every destination is an exact-size heap allocation).  Before the random
-// cases, a fixed table calls every spf_*_batch entry point with one bad argument each (batch_forms_refuse_bad_arguments) and
-// holds spf_graph_add_op and spf_ciphertext_words to the header's own statement of the ten operations and the four wire
-// sizes (graph_ops_match_the_header, wire_sizes_match_the_header).
+// cases, a fixed table calls every spf_*_batch entry point with one bad argument each and holds its status and message
+// (batch_forms_refuse_bad_arguments), and three more hold spf_graph_add_op, spf_ciphertext_words and the batch shapes to the
+// header's own statement of the ten operations, the four wire sizes and every batch entry point's operand widths
+// (graph_ops_match_the_header, wire_sizes_match_the_header, batch_shapes_match_the_header).
 // Seeds: the reference's own malformed vector (parasol_runtime/src/safe_bincode.rs:58-66, :105-117) and valid serializations.
 //
 // usage: fuzz_host <cases> [seed]
@@ -70,9 +71,14 @@ void fake_ctx(spf_ctx& c, const spf_params& p, bool generic)
     while ((1u << c.log_n) < p.polynomial_degree) c.log_n++;
 }
 
-// Every spf_*_batch entry point with exactly one bad argument: each must be refused as SPF_ERR_INVALID_ARGUMENT before its first
-// HIP call (the context's device is -1, so a call that reaches HIP returns SPF_ERR_HIP instead).  The buffers are exact-size heap
-// allocations for B ciphertexts; the batch-limit cases hand the same buffers with a larger B and must not read them.
+// Every spf_*_batch entry point with exactly one bad argument: each must be refused with the stated status AND the stated text of
+// spf_last_error before its first HIP call (the context's device is -1, so a call that reaches HIP returns SPF_ERR_HIP instead:
+// "reaches the device" below, its text is the runtime's and is not compared).  The buffers are exact-size heap allocations for B
+// ciphertexts; the batch-limit cases hand the same buffers with a larger B and must not read them.  The newer forms (blind rotation,
+// the functional keyswitches, circuit bootstrap via PFKS, the linear maps) run on a second hand-made context whose readiness flags
+// and key shapes are set by hand, each in its `_batch` and its device-pointer form, with null pointers at B == 0, a batch one past
+// the limit and an output that overlaps the input; the group forms are held to the checks they make before the batch is split.
+// The expected values were recorded from the library as it was before the batch shapes were stated once (spf_ops.hpp).
 bool batch_forms_refuse_bad_arguments(spf_ctx* c)
 {
     const spf_params& p = c->prm;
@@ -83,62 +89,362 @@ bool batch_forms_refuse_bad_arguments(spf_ctx* c)
         bits(B * nb * gw), o_lwe0(B * l0), o_lwe1(B * l1), o_glwe(B * gw), o_glev(B * l * gw), o_bits(B * nb * l1);
     std::vector<double> ggsw(B * sw), o_ggsw(B * sw), o_ggsw_bits(B * nb * sw);
     bool ok = true;
-    auto expect = [&](const char* call, spf_status st) {
-        if (st == SPF_ERR_INVALID_ARGUMENT) return;
-        fprintf(stderr, "spf_*_batch bad argument: %s returned %d, not SPF_ERR_INVALID_ARGUMENT (%s)\n", call, st, c->err.c_str());
-        ok = false;
+    const spf_status BAD = SPF_ERR_INVALID_ARGUMENT;
+    const char* const null_arg = "null argument";
+    const char* const too_large = "batch too large";
+    const char* const device = nullptr; // SPF_ERR_HIP: every check passed and the call went on to the device
+    spf_ctx* on = c;
+    // (`msg` null: the text is not compared)
+    auto expect = [&](const char* call, spf_status st, spf_status want, const char* msg) {
+        if (st != want || (msg && on->err != msg)) {
+            fprintf(stderr, "spf_*_batch bad argument: %s returned %d (%s), not %d (%s)\n", call, st, on->err.c_str(), want, msg ? msg : "any text");
+            ok = false;
+        }
+        on->err.clear();
     };
-    expect("keyswitch_lwe_l1_lwe_l0 null in", spf_keyswitch_lwe_l1_lwe_l0_batch(c, B, nullptr, o_lwe0.data()));
-    expect("generalized_pbs null lut", spf_generalized_pbs_batch(c, B, lwe0.data(), nullptr, 0, 0, 0, 0, o_glwe.data()));
-    expect("generalized_pbs lut_stride 1", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 1, 0, 0, 0, o_glwe.data()));
-    expect("generalized_pbs log_v 12", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 0, 12, 0, o_glwe.data()));
-    expect("generalized_pbs log_chi 52", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 52, 0, 0, o_glwe.data()));
+    expect("keyswitch_lwe_l1_lwe_l0 null in", spf_keyswitch_lwe_l1_lwe_l0_batch(c, B, nullptr, o_lwe0.data()), BAD, null_arg);
+    expect("generalized_pbs null lut", spf_generalized_pbs_batch(c, B, lwe0.data(), nullptr, 0, 0, 0, 0, o_glwe.data()), BAD, "null lut");
+    expect("generalized_pbs lut_stride 1", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 1, 0, 0, 0, o_glwe.data()), BAD,
+           "lut_stride smaller than a GLWE");
+    expect("generalized_pbs log_v 12", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 0, 12, 0, o_glwe.data()), BAD,
+           "log_v / log_chi out of range");
+    expect("generalized_pbs log_chi 52", spf_generalized_pbs_batch(c, B, lwe0.data(), lut.data(), 0, 52, 0, 0, o_glwe.data()), BAD,
+           "log_v / log_chi out of range");
     expect("generalized_pbs B 0x80000000",
-           spf_generalized_pbs_batch(c, over_br, lwe0.data(), lut.data(), 0, 0, 0, 0, o_glwe.data()));
-    expect("pbs_univariate lut_stride 1", spf_pbs_univariate_batch(c, B, lwe0.data(), lut.data(), 1, o_lwe1.data()));
-    expect("pbs_univariate null in", spf_pbs_univariate_batch(c, B, nullptr, lut.data(), 0, o_lwe1.data()));
-    expect("pbs_bivariate null right", spf_pbs_bivariate_batch(c, B, lwe0.data(), nullptr, lut.data(), 0, 2, o_lwe1.data()));
+           spf_generalized_pbs_batch(c, over_br, lwe0.data(), lut.data(), 0, 0, 0, 0, o_glwe.data()), BAD, too_large);
+    expect("pbs_univariate lut_stride 1", spf_pbs_univariate_batch(c, B, lwe0.data(), lut.data(), 1, o_lwe1.data()), BAD,
+           "lut_stride smaller than a GLWE");
+    expect("pbs_univariate null in", spf_pbs_univariate_batch(c, B, nullptr, lut.data(), 0, o_lwe1.data()), BAD, null_arg);
+    expect("pbs_bivariate null right", spf_pbs_bivariate_batch(c, B, lwe0.data(), nullptr, lut.data(), 0, 2, o_lwe1.data()), BAD, null_arg);
     expect("pbs_bivariate plaintext_bits 64",
-           spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 0, 64, o_lwe1.data()));
-    expect("pbs_bivariate lut_stride 1", spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 1, 2, o_lwe1.data()));
-    expect("circuit_bootstrap_pbs null out", spf_circuit_bootstrap_pbs_batch(c, B, lwe0.data(), nullptr));
-    expect("circuit_bootstrap_pbs B 0x80000000", spf_circuit_bootstrap_pbs_batch(c, over_br, lwe0.data(), o_glwe.data()));
-    expect("circuit_bootstrap null in", spf_circuit_bootstrap_batch(c, B, nullptr, o_ggsw.data()));
-    expect("circuit_bootstrap B 0x10000000", spf_circuit_bootstrap_batch(c, over_tail, lwe0.data(), o_ggsw.data()));
-    expect("mod_switch_trace_and_rotate null out", spf_mod_switch_trace_and_rotate_batch(c, B, glwe.data(), nullptr));
+           spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 0, 64, o_lwe1.data()), BAD, "plaintext_bits must be below 64");
+    expect("pbs_bivariate lut_stride 1", spf_pbs_bivariate_batch(c, B, lwe0.data(), rhs.data(), lut.data(), 1, 2, o_lwe1.data()), BAD,
+           "lut_stride smaller than a GLWE");
+    expect("circuit_bootstrap_pbs null out", spf_circuit_bootstrap_pbs_batch(c, B, lwe0.data(), nullptr), BAD, null_arg);
+    expect("circuit_bootstrap_pbs B 0x80000000", spf_circuit_bootstrap_pbs_batch(c, over_br, lwe0.data(), o_glwe.data()), BAD, too_large);
+    expect("circuit_bootstrap null in", spf_circuit_bootstrap_batch(c, B, nullptr, o_ggsw.data()), BAD, null_arg);
+    expect("circuit_bootstrap B 0x10000000", spf_circuit_bootstrap_batch(c, over_tail, lwe0.data(), o_ggsw.data()), BAD, too_large);
+    expect("mod_switch_trace_and_rotate null out", spf_mod_switch_trace_and_rotate_batch(c, B, glwe.data(), nullptr), BAD, null_arg);
     expect("mod_switch_trace_and_rotate B 0x10000000",
-           spf_mod_switch_trace_and_rotate_batch(c, over_tail, glwe.data(), o_glev.data()));
-    expect("scheme_switch null in", spf_scheme_switch_batch(c, B, nullptr, o_ggsw.data()));
-    expect("scheme_switch B 0x10000000", spf_scheme_switch_batch(c, over_tail, glev.data(), o_ggsw.data()));
-    expect("sample_extract_l1 idx N", spf_sample_extract_l1_batch(c, B, glwe.data(), N, o_lwe1.data()));
-    expect("sample_extract_l1 null out", spf_sample_extract_l1_batch(c, B, glwe.data(), 0, nullptr));
-    expect("glwe_not null in", spf_glwe_not_batch(c, B, nullptr, o_glwe.data()));
-    expect("glwe_xor null b", spf_glwe_xor_batch(c, B, glwe.data(), nullptr, o_glwe.data()));
-    expect("glwe_mul_xn null out", spf_glwe_mul_xn_batch(c, B, glwe.data(), 3, nullptr));
-    expect("glwe_pack n_bits 0", spf_glwe_pack_batch(c, B, 0, bits.data(), o_glwe.data()));
-    expect("glwe_pack null out", spf_glwe_pack_batch(c, B, nb, bits.data(), nullptr));
-    expect("glwe_unpack_l1 n_bits N + 1", spf_glwe_unpack_l1_batch(c, B, N + 1, glwe.data(), o_bits.data()));
-    expect("cmux null sel", spf_cmux_batch(c, B, nullptr, glwe.data(), glwe_b.data(), o_glwe.data()));
-    expect("glev_cmux null b", spf_glev_cmux_batch(c, B, ggsw.data(), glev.data(), nullptr, o_glev.data()));
-    expect("multiply_glwe_ggsw null ggsw", spf_multiply_glwe_ggsw_batch(c, B, glwe.data(), nullptr, o_glwe.data()));
-    expect("gate_bootstrap null in", spf_gate_bootstrap_batch(c, B, nullptr, o_glwe.data()));
-    expect("gate_bootstrap B 0x80000000", spf_gate_bootstrap_batch(c, over_br, lwe1.data(), o_glwe.data()));
-    expect("keyswitch_circuit_bootstrap null out", spf_keyswitch_circuit_bootstrap_batch(c, B, lwe1.data(), nullptr));
+           spf_mod_switch_trace_and_rotate_batch(c, over_tail, glwe.data(), o_glev.data()), BAD, too_large);
+    expect("scheme_switch null in", spf_scheme_switch_batch(c, B, nullptr, o_ggsw.data()), BAD, null_arg);
+    expect("scheme_switch B 0x10000000", spf_scheme_switch_batch(c, over_tail, glev.data(), o_ggsw.data()), BAD, too_large);
+    expect("sample_extract_l1 idx N", spf_sample_extract_l1_batch(c, B, glwe.data(), N, o_lwe1.data()), BAD,
+           "sample_extract index >= polynomial_degree");
+    expect("sample_extract_l1 null out", spf_sample_extract_l1_batch(c, B, glwe.data(), 0, nullptr), BAD, null_arg);
+    expect("glwe_not null in", spf_glwe_not_batch(c, B, nullptr, o_glwe.data()), BAD, null_arg);
+    expect("glwe_xor null b", spf_glwe_xor_batch(c, B, glwe.data(), nullptr, o_glwe.data()), BAD, null_arg);
+    expect("glwe_mul_xn null out", spf_glwe_mul_xn_batch(c, B, glwe.data(), 3, nullptr), BAD, null_arg);
+    const char* const n_bits_range = "n_bits must be in 1 ..= polynomial_degree";
+    const char* const rows_above = "B * n_bits above 0x0fffffff";
+    expect("glwe_pack n_bits 0", spf_glwe_pack_batch(c, B, 0, bits.data(), o_glwe.data()), BAD, n_bits_range);
+    expect("glwe_pack null out", spf_glwe_pack_batch(c, B, nb, bits.data(), nullptr), BAD, null_arg);
+    expect("glwe_unpack_l1 n_bits N + 1", spf_glwe_unpack_l1_batch(c, B, N + 1, glwe.data(), o_bits.data()), BAD, n_bits_range);
+    expect("cmux null sel", spf_cmux_batch(c, B, nullptr, glwe.data(), glwe_b.data(), o_glwe.data()), BAD, null_arg);
+    expect("glev_cmux null b", spf_glev_cmux_batch(c, B, ggsw.data(), glev.data(), nullptr, o_glev.data()), BAD, null_arg);
+    expect("multiply_glwe_ggsw null ggsw", spf_multiply_glwe_ggsw_batch(c, B, glwe.data(), nullptr, o_glwe.data()), BAD, null_arg);
+    expect("gate_bootstrap null in", spf_gate_bootstrap_batch(c, B, nullptr, o_glwe.data()), BAD, null_arg);
+    expect("gate_bootstrap B 0x80000000", spf_gate_bootstrap_batch(c, over_br, lwe1.data(), o_glwe.data()), BAD, too_large);
+    expect("keyswitch_circuit_bootstrap null out", spf_keyswitch_circuit_bootstrap_batch(c, B, lwe1.data(), nullptr), BAD, null_arg);
     expect("keyswitch_circuit_bootstrap B 0x10000000",
-           spf_keyswitch_circuit_bootstrap_batch(c, over_tail, lwe1.data(), o_ggsw.data()));
+           spf_keyswitch_circuit_bootstrap_batch(c, over_tail, lwe1.data(), o_ggsw.data()), BAD, too_large);
     expect("unpack_circuit_bootstrap B * n_bits 0x10000002",
-           spf_unpack_circuit_bootstrap_batch(c, over_tail / 2 + 1, 2, glwe.data(), o_ggsw_bits.data()));
-    expect("unpack_circuit_bootstrap null in", spf_unpack_circuit_bootstrap_batch(c, B, nb, nullptr, o_ggsw_bits.data()));
+           spf_unpack_circuit_bootstrap_batch(c, over_tail / 2 + 1, 2, glwe.data(), o_ggsw_bits.data()), BAD, rows_above);
+    expect("unpack_circuit_bootstrap null in", spf_unpack_circuit_bootstrap_batch(c, B, nb, nullptr, o_ggsw_bits.data()), BAD, null_arg);
     // the standard-form entry points: polynomials and keys as integer words
     std::vector<double> o_spec(B * N);
-    expect("poly_fft null in", spf_poly_fft_batch(c, B, nullptr, o_spec.data()));
-    expect("poly_fft null out", spf_poly_fft_batch(c, B, glwe.data(), nullptr));
-    expect("poly_fft n_polys 0x80000000", spf_poly_fft_batch(c, over_br, glwe.data(), o_spec.data()));
-    expect("poly_fft_dev partial overlap", spf_poly_fft_dev(c, nullptr, B, glwe.data(), reinterpret_cast<double*>(glwe.data() + N)));
-    expect("load_bootstrap_key_std null", spf_load_bootstrap_key_std(c, nullptr, 2 * (size_t)p.lwe_dimension * ggsw_fft_complex(p, p.pbs_radix_count)));
-    expect("load_bootstrap_key_std length in complex", spf_load_bootstrap_key_std(c, glwe.data(), (size_t)p.lwe_dimension * ggsw_fft_complex(p, p.pbs_radix_count)));
-    expect("load_automorphism_key_std one word short", spf_load_automorphism_key_std(c, glwe.data(), 2 * ak_complex(p) - 1));
-    expect("load_scheme_switch_key_std one word long", spf_load_scheme_switch_key_std(c, glwe.data(), 2 * ssk_complex(p) + 1));
+    expect("poly_fft null in", spf_poly_fft_batch(c, B, nullptr, o_spec.data()), BAD, null_arg);
+    expect("poly_fft null out", spf_poly_fft_batch(c, B, glwe.data(), nullptr), BAD, null_arg);
+    expect("poly_fft n_polys 0x80000000", spf_poly_fft_batch(c, over_br, glwe.data(), o_spec.data()), BAD, too_large);
+    expect("poly_fft_dev partial overlap", spf_poly_fft_dev(c, nullptr, B, glwe.data(), reinterpret_cast<double*>(glwe.data() + N)), BAD,
+           "spf_poly_fft_dev: d_out must be d_in itself or must not overlap it");
+    const size_t bsk_complex = (size_t)p.lwe_dimension * ggsw_fft_complex(p, p.pbs_radix_count);
+    auto key_length = [](const char* name, size_t got, size_t want_complex) {
+        return std::string(name) + " key length " + std::to_string(got) + " words != " + std::to_string(2 * want_complex);
+    };
+    expect("load_bootstrap_key_std null", spf_load_bootstrap_key_std(c, nullptr, 2 * bsk_complex), BAD, null_arg);
+    expect("load_bootstrap_key_std length in complex", spf_load_bootstrap_key_std(c, glwe.data(), bsk_complex), BAD,
+           key_length("bootstrap", bsk_complex, bsk_complex).c_str());
+    expect("load_automorphism_key_std one word short", spf_load_automorphism_key_std(c, glwe.data(), 2 * ak_complex(p) - 1), BAD,
+           key_length("automorphism", 2 * ak_complex(p) - 1, ak_complex(p)).c_str());
+    expect("load_scheme_switch_key_std one word long", spf_load_scheme_switch_key_std(c, glwe.data(), 2 * ssk_complex(p) + 1), BAD,
+           key_length("scheme-switch", 2 * ssk_complex(p) + 1, ssk_complex(p)).c_str());
+
+    // ---- a representative older operation in both forms: nulls at B == 0 are accepted, the limit, the overlap (device-pointer form only)
+    expect("cmux nulls at B 0", spf_cmux_batch(c, 0, nullptr, nullptr, nullptr, nullptr), SPF_OK, "");
+    expect("glwe_pack nulls at B 0", spf_glwe_pack_batch(c, 0, nb, nullptr, nullptr), SPF_OK, "");
+    expect("glwe_pack_dev nulls at B 0", spf_glwe_pack_dev(c, nullptr, 0, nb, nullptr, nullptr), SPF_OK, "");
+    expect("glwe_pack B * n_bits one past", spf_glwe_pack_batch(c, 0x0fffffff / nb + 1, nb, bits.data(), o_glwe.data()), BAD, rows_above);
+    expect("glwe_pack_dev B * n_bits one past", spf_glwe_pack_dev(c, nullptr, 0x0fffffff / nb + 1, nb, bits.data(), o_glwe.data()), BAD, rows_above);
+    expect("glwe_pack_dev out inside in", spf_glwe_pack_dev(c, nullptr, B, nb, bits.data(), bits.data() + gw), BAD,
+           "the packed output overlaps the bit GLWEs");
+    expect("glwe_pack out inside in reaches the device", spf_glwe_pack_batch(c, B, nb, bits.data(), bits.data() + gw), SPF_ERR_HIP, device);
+
+    // ---- the newer forms, on a context with keys and weights "loaded" by hand
+    const size_t k = p.glwe_size, pu_n = 8, pu_p = 2, lin_M = 2, lin_K = 3;
+    spf_ctx keyed;
+    fake_ctx(keyed, p, c->generic);
+    keyed.bsk_ready = true;
+    keyed.pufks_ready = true; keyed.pufks_n = (uint32_t)pu_n; keyed.pufks_log = 4; keyed.pufks_count = 4;
+    keyed.pfks_ready = true; keyed.pfks_keys = (uint32_t)k + 1; keyed.pfks_n = (uint32_t)(k * N); keyed.pfks_p = 1; keyed.pfks_log = 4; keyed.pfks_count = 4;
+    keyed.lin[0].ready = true; keyed.lin[0].M = lin_M; keyed.lin[0].K = lin_K;
+    spf_ctx* q = &keyed;
+    on = q;
+    const size_t ggsw_int = (k + 1) * l * gw; // an integer-form GGSW: as many words as its spectrum
+    std::vector<uint64_t> pu_rows(B * pu_p * (pu_n + 1) + B * gw), pf_rows(B * l * l1 + B * ggsw_int), lin_rows(B * (lin_K + lin_M) * l0),
+        lwe0_ggsw(B * l0 + B * ggsw_int), rot(B * gw);
+    const char* const overlap = "the output overlaps the input";
+
+    expect("blind_rotation nulls at B 0", spf_blind_rotation_batch(q, 0, nb, 0, nullptr, nullptr, nullptr), SPF_OK, "");
+    expect("blind_rotation_dev nulls at B 0", spf_blind_rotation_dev(q, nullptr, 0, nb, 0, nullptr, nullptr, nullptr), SPF_OK, "");
+    expect("blind_rotation null shift", spf_blind_rotation_batch(q, B, nb, 0, nullptr, glwe.data(), o_glwe.data()), BAD, null_arg);
+    expect("blind_rotation n_bits 0", spf_blind_rotation_batch(q, B, 0, 0, ggsw.data(), glwe.data(), o_glwe.data()), BAD, "n_bits must be at least 1");
+    expect("blind_rotation n_bits + log_stride 12", spf_blind_rotation_batch(q, B, nb, 9, ggsw.data(), glwe.data(), o_glwe.data()), BAD,
+           "n_bits + log_stride above log2(polynomial_degree)");
+    expect("blind_rotation B * n_bits one past", spf_blind_rotation_batch(q, 0x0fffffff / nb + 1, nb, 0, ggsw.data(), glwe.data(), o_glwe.data()), BAD, rows_above);
+    expect("blind_rotation_dev B * n_bits one past", spf_blind_rotation_dev(q, nullptr, 0x0fffffff / nb + 1, nb, 0, ggsw.data(), glwe.data(), o_glwe.data()), BAD,
+           rows_above);
+    expect("blind_rotation_dev out == in", spf_blind_rotation_dev(q, nullptr, 1, nb, 0, o_ggsw_bits.data(), rot.data(), rot.data()), BAD,
+           "the output overlaps an input");
+    expect("blind_rotation_dev out inside shift",
+           spf_blind_rotation_dev(q, nullptr, 1, nb, 0, o_ggsw_bits.data(), rot.data(), reinterpret_cast<uint64_t*>(o_ggsw_bits.data() + (nb - 1) * sw)), BAD,
+           "the output overlaps an input");
+    expect("blind_rotation out == in reaches the device", spf_blind_rotation_batch(q, 1, nb, 0, o_ggsw_bits.data(), rot.data(), rot.data()), SPF_ERR_HIP, device);
+
+    uint64_t* const pu_out = pu_rows.data() + B * pu_p * (pu_n + 1);
+    const char* const pu_above = "B * lwe_count above 0x0fffffff";
+    expect("public_functional_keyswitch nulls at B 0", spf_public_functional_keyswitch_batch(q, 0, pu_p, nullptr, nullptr), BAD, null_arg);
+    expect("public_functional_keyswitch_enqueue nulls at B 0", spf_public_functional_keyswitch_enqueue(q, nullptr, 0, pu_p, nullptr, nullptr), BAD, null_arg);
+    expect("public_functional_keyswitch B 0", spf_public_functional_keyswitch_batch(q, 0, pu_p, pu_rows.data(), pu_out), SPF_OK, "");
+    expect("public_functional_keyswitch_enqueue B 0", spf_public_functional_keyswitch_enqueue(q, nullptr, 0, pu_p, pu_rows.data(), pu_out), SPF_OK, "");
+    expect("public_functional_keyswitch lwe_count 0", spf_public_functional_keyswitch_batch(q, B, 0, pu_rows.data(), pu_out), BAD, "lwe_count must be at least 1");
+    expect("public_functional_keyswitch_enqueue lwe_count N + 1", spf_public_functional_keyswitch_enqueue(q, nullptr, B, N + 1, pu_rows.data(), pu_out), BAD,
+           "lwe_count above polynomial_degree");
+    expect("public_functional_keyswitch B * lwe_count one past", spf_public_functional_keyswitch_batch(q, 0x0fffffff / pu_p + 1, pu_p, pu_rows.data(), pu_out), BAD, pu_above);
+    expect("public_functional_keyswitch_enqueue B * lwe_count one past",
+           spf_public_functional_keyswitch_enqueue(q, nullptr, 0x0fffffff / pu_p + 1, pu_p, pu_rows.data(), pu_out), BAD, pu_above);
+    expect("public_functional_keyswitch_enqueue out on the last input word",
+           spf_public_functional_keyswitch_enqueue(q, nullptr, B, pu_p, pu_rows.data(), pu_out - 1), BAD, overlap);
+    expect("public_functional_keyswitch_enqueue in on the last output word",
+           spf_public_functional_keyswitch_enqueue(q, nullptr, B, pu_p, pu_out + B * gw - 1, pu_out), BAD, overlap);
+    expect("public_functional_keyswitch_enqueue out behind in reaches the device",
+           spf_public_functional_keyswitch_enqueue(q, nullptr, B, pu_p, pu_rows.data(), pu_out), SPF_ERR_HIP, device);
+    expect("public_functional_keyswitch out on the last input word reaches the device",
+           spf_public_functional_keyswitch_batch(q, B, pu_p, pu_rows.data(), pu_out - 1), SPF_ERR_HIP, device);
+    q->pufks_ready = false;
+    expect("public_functional_keyswitch no key", spf_public_functional_keyswitch_batch(q, B, pu_p, pu_rows.data(), pu_out), SPF_ERR_NO_KEY,
+           "public functional keyswitch key not loaded");
+    expect("public_functional_keyswitch_enqueue no key", spf_public_functional_keyswitch_enqueue(q, nullptr, 0, pu_p, pu_rows.data(), pu_out), SPF_ERR_NO_KEY,
+           "public functional keyswitch key not loaded");
+    expect("public_functional_keyswitch no key, lwe_count 0", spf_public_functional_keyswitch_batch(q, B, 0, pu_rows.data(), pu_out), BAD, "lwe_count must be at least 1");
+    q->pufks_ready = true;
+
+    uint64_t* const pf_out = pf_rows.data() + B * l * l1; // behind B * l rows: room for B GLWEs and for B integer GGSWs
+    const char* const pf_none = "private functional keyswitch keys not loaded";
+    expect("private_functional_keyswitch nulls at B 0", spf_private_functional_keyswitch_batch(q, 0, 0, nullptr, nullptr), BAD, null_arg);
+    expect("private_functional_keyswitch_enqueue nulls at B 0", spf_private_functional_keyswitch_enqueue(q, nullptr, 0, 0, nullptr, nullptr), BAD, null_arg);
+    expect("private_functional_keyswitch B 0", spf_private_functional_keyswitch_batch(q, k, 0, pf_rows.data(), pf_out), SPF_OK, "");
+    expect("private_functional_keyswitch key_index k + 1", spf_private_functional_keyswitch_batch(q, k + 1, over_tail, pf_rows.data(), pf_out), BAD, "key_index >= n_keys");
+    expect("private_functional_keyswitch_enqueue key_index k + 1", spf_private_functional_keyswitch_enqueue(q, nullptr, k + 1, B, pf_rows.data(), pf_out), BAD,
+           "key_index >= n_keys");
+    expect("private_functional_keyswitch B 0x10000000", spf_private_functional_keyswitch_batch(q, 0, over_tail, pf_rows.data(), pf_out), BAD, too_large);
+    expect("private_functional_keyswitch_enqueue B 0x10000000", spf_private_functional_keyswitch_enqueue(q, nullptr, 0, over_tail, pf_rows.data(), pf_out), BAD, too_large);
+    expect("private_functional_keyswitch_enqueue out on the last input word",
+           spf_private_functional_keyswitch_enqueue(q, nullptr, 0, B, pf_rows.data(), pf_rows.data() + B * l1 - 1), BAD, overlap);
+    expect("private_functional_keyswitch_enqueue out behind in reaches the device",
+           spf_private_functional_keyswitch_enqueue(q, nullptr, 0, B, pf_rows.data(), pf_rows.data() + B * l1), SPF_ERR_HIP, device);
+    expect("private_functional_keyswitch out on the last input word reaches the device",
+           spf_private_functional_keyswitch_batch(q, 0, B, pf_rows.data(), pf_rows.data() + B * l1 - 1), SPF_ERR_HIP, device);
+
+    const char* const components = "the GGSW components need n_keys = k+1, lwe_count = 1 and from_dimension = k * N";
+    expect("apply_pfks_on_ggsw_components nulls at B 0", spf_apply_pfks_on_ggsw_components_batch(q, 0, nullptr, nullptr), BAD, null_arg);
+    expect("apply_pfks_on_ggsw_components_enqueue nulls at B 0", spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, 0, nullptr, nullptr), BAD, null_arg);
+    expect("apply_pfks_on_ggsw_components B 0", spf_apply_pfks_on_ggsw_components_batch(q, 0, pf_rows.data(), pf_out), SPF_OK, "");
+    expect("apply_pfks_on_ggsw_components B * l one past", spf_apply_pfks_on_ggsw_components_batch(q, 0x0fffffff / l + 1, pf_rows.data(), pf_out), BAD, too_large);
+    expect("apply_pfks_on_ggsw_components_enqueue B * l one past",
+           spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, 0x0fffffff / l + 1, pf_rows.data(), pf_out), BAD, too_large);
+    expect("apply_pfks_on_ggsw_components_enqueue out on the last input word",
+           spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, B, pf_rows.data(), pf_out - 1), BAD, overlap);
+    expect("apply_pfks_on_ggsw_components_enqueue in on the last output word",
+           spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, 1, pf_out + ggsw_int - 1, pf_out), BAD, overlap);
+    expect("apply_pfks_on_ggsw_components_enqueue out behind in reaches the device",
+           spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, B, pf_rows.data(), pf_out), SPF_ERR_HIP, device);
+    expect("apply_pfks_on_ggsw_components out on the last input word reaches the device",
+           spf_apply_pfks_on_ggsw_components_batch(q, B, pf_rows.data(), pf_out - 1), SPF_ERR_HIP, device);
+
+    uint64_t* const cb_out = lwe0_ggsw.data() + B * l0;
+    expect("circuit_bootstrap_via_pfks nulls at B 0", spf_circuit_bootstrap_via_pfks_batch(q, 0, nullptr, nullptr), BAD, null_arg);
+    expect("circuit_bootstrap_via_pfks_enqueue nulls at B 0", spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, 0, nullptr, nullptr), BAD, null_arg);
+    expect("circuit_bootstrap_via_pfks B 0", spf_circuit_bootstrap_via_pfks_batch(q, 0, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), SPF_OK, "");
+    expect("circuit_bootstrap_via_pfks B * l one past",
+           spf_circuit_bootstrap_via_pfks_batch(q, 0x0fffffff / l + 1, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), BAD, too_large);
+    expect("circuit_bootstrap_via_pfks_enqueue B * l one past",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, 0x0fffffff / l + 1, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), BAD, too_large);
+    expect("circuit_bootstrap_via_pfks_enqueue out on the last input word",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out - 1)), BAD, overlap);
+    expect("circuit_bootstrap_via_pfks_enqueue out behind in reaches the device",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), SPF_ERR_HIP, device);
+    expect("circuit_bootstrap_via_pfks out on the last input word reaches the device",
+           spf_circuit_bootstrap_via_pfks_batch(q, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out - 1)), SPF_ERR_HIP, device);
+    q->bsk_ready = false;
+    expect("circuit_bootstrap_via_pfks_enqueue no bootstrap key",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), SPF_ERR_NO_KEY, "bootstrap key not loaded");
+    q->bsk_ready = true;
+    q->pfks_p = 2; // keys of another shape: the single operation takes them, the GGSW components do not
+    expect("private_functional_keyswitch lwe_count 2: out on the last input word",
+           spf_private_functional_keyswitch_enqueue(q, nullptr, 0, 1, pf_rows.data(), pf_rows.data() + 2 * l1 - 1), BAD, overlap);
+    expect("apply_pfks_on_ggsw_components lwe_count 2", spf_apply_pfks_on_ggsw_components_batch(q, B, pf_rows.data(), pf_out), BAD, components);
+    expect("apply_pfks_on_ggsw_components_enqueue lwe_count 2", spf_apply_pfks_on_ggsw_components_enqueue(q, nullptr, B, pf_rows.data(), pf_out), BAD, components);
+    expect("circuit_bootstrap_via_pfks lwe_count 2", spf_circuit_bootstrap_via_pfks_batch(q, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), BAD, components);
+    expect("circuit_bootstrap_via_pfks_enqueue lwe_count 2",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), BAD, components);
+    q->pfks_p = 1;
+    q->pfks_ready = false;
+    expect("private_functional_keyswitch no keys", spf_private_functional_keyswitch_batch(q, k + 1, over_tail, pf_rows.data(), pf_out), SPF_ERR_NO_KEY, pf_none);
+    expect("private_functional_keyswitch_enqueue no keys", spf_private_functional_keyswitch_enqueue(q, nullptr, 0, B, pf_rows.data(), pf_out), SPF_ERR_NO_KEY, pf_none);
+    expect("apply_pfks_on_ggsw_components no keys", spf_apply_pfks_on_ggsw_components_batch(q, B, pf_rows.data(), pf_out), SPF_ERR_NO_KEY, pf_none);
+    expect("circuit_bootstrap_via_pfks_enqueue no keys",
+           spf_circuit_bootstrap_via_pfks_enqueue(q, nullptr, B, lwe0_ggsw.data(), reinterpret_cast<double*>(cb_out)), SPF_ERR_NO_KEY, pf_none);
+    q->pfks_ready = true;
+
+    uint64_t* const lin_out = lin_rows.data() + B * lin_K * l0;
+    expect("lwe_linear nulls at B 0", spf_lwe_linear_batch(q, 0, SPF_VAL_LWE0, 0, nullptr, nullptr), BAD, null_arg);
+    expect("lwe_linear_enqueue nulls at B 0", spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE0, 0, nullptr, nullptr), BAD, null_arg);
+    expect("lwe_linear B 0", spf_lwe_linear_batch(q, 0, SPF_VAL_LWE0, 0, lin_rows.data(), lin_out), SPF_OK, "");
+    expect("lwe_linear_enqueue B 0", spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE1, 0, lin_rows.data(), lin_out), SPF_OK, "");
+    expect("lwe_linear slot 64", spf_lwe_linear_batch(q, 64, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), BAD, "slot 64 >= SPF_LWE_LINEAR_SLOTS = 64");
+    expect("lwe_linear_enqueue kind GLWE1", spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_GLWE1, B, lin_rows.data(), lin_out), BAD,
+           "kind must be SPF_VAL_LWE0 or SPF_VAL_LWE1");
+    expect("lwe_linear empty slot", spf_lwe_linear_batch(q, 1, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), SPF_ERR_NO_KEY, "no weights loaded in slot 1");
+    expect("lwe_linear B * max(M, K) one past", spf_lwe_linear_batch(q, 0, SPF_VAL_LWE0, 0x0fffffff / lin_K + 1, lin_rows.data(), lin_out), BAD, too_large);
+    expect("lwe_linear_enqueue B * max(M, K) one past",
+           spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE0, 0x0fffffff / lin_K + 1, lin_rows.data(), lin_out), BAD, too_large);
+    expect("lwe_linear out on the last input word", spf_lwe_linear_batch(q, 0, SPF_VAL_LWE0, B, lin_rows.data(), lin_out - 1), BAD, overlap);
+    expect("lwe_linear_enqueue out on the last input word", spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE0, B, lin_rows.data(), lin_out - 1), BAD, overlap);
+    expect("lwe_linear_enqueue in on the last output word",
+           spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE0, 1, lin_out + lin_M * l0 - 1, lin_out), BAD, overlap);
+    expect("lwe_linear out behind in reaches the device", spf_lwe_linear_batch(q, 0, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), SPF_ERR_HIP, device);
+    expect("lwe_linear_enqueue out behind in reaches the device", spf_lwe_linear_enqueue(q, nullptr, 0, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), SPF_ERR_HIP, device);
+
+    // ---- the group forms, up to the point where the batch would be split: one hand-made member (its thread is never started, so
+    // every call here must return before group_split posts a range); the text is spf_group_last_error's
+    spf_group* grp = new spf_group();
+    grp->prm = p;
+    grp->m.emplace_back(new spf_group::Member());
+    spf_ctx* m0 = new spf_ctx();
+    fake_ctx(*m0, p, c->generic);
+    m0->pufks_ready = true; m0->pufks_n = (uint32_t)pu_n; m0->pufks_log = 4; m0->pufks_count = 4;
+    m0->pfks_ready = true; m0->pfks_keys = (uint32_t)k + 1; m0->pfks_n = (uint32_t)(k * N); m0->pfks_p = 1; m0->pfks_log = 4; m0->pfks_count = 4;
+    m0->lin[0].ready = true; m0->lin[0].M = lin_M; m0->lin[0].K = lin_K;
+    grp->m.back()->ctx = m0;
+    grp->m.back()->device = -1;
+    auto gexpect = [&](const char* call, spf_status st, spf_status want, const char* msg, spf_group* of) {
+        const std::string got = spf_group_last_error(of);
+        if (st != want || got != msg) {
+            fprintf(stderr, "spf_group_*_batch bad argument: %s returned %d (%s), not %d (%s)\n", call, st, got.c_str(), want, msg);
+            ok = false;
+        }
+        gfail(of, SPF_OK, "");
+    };
+    gexpect("group glwe_not null group", spf_group_glwe_not_batch(nullptr, B, glwe.data(), o_glwe.data()), BAD, "null group", nullptr);
+    gexpect("group glwe_not null in", spf_group_glwe_not_batch(grp, B, nullptr, o_glwe.data()), BAD, null_arg, grp);
+    gexpect("group glwe_not nulls at B 0", spf_group_glwe_not_batch(grp, 0, nullptr, nullptr), SPF_OK, "", grp);
+    gexpect("group cmux null b", spf_group_cmux_batch(grp, B, ggsw.data(), glwe.data(), nullptr, o_glwe.data()), BAD, null_arg, grp);
+    gexpect("group pbs_bivariate plaintext_bits 64", spf_group_pbs_bivariate_batch(grp, 0, nullptr, nullptr, nullptr, 0, 64, nullptr), BAD,
+            "plaintext_bits must be below 64", grp);
+    gexpect("group glwe_pack n_bits 0", spf_group_glwe_pack_batch(grp, 0, 0, nullptr, nullptr), BAD, n_bits_range, grp);
+    gexpect("group glwe_unpack_l1 null out", spf_group_glwe_unpack_l1_batch(grp, B, 0, glwe.data(), nullptr), BAD, null_arg, grp);
+    gexpect("group unpack_circuit_bootstrap B * n_bits one past",
+            spf_group_unpack_circuit_bootstrap_batch(grp, 0x0fffffff / nb + 1, nb, glwe.data(), o_ggsw_bits.data()), BAD, rows_above, grp);
+    gexpect("group blind_rotation nulls at B 0", spf_group_blind_rotation_batch(grp, 0, nb, 0, nullptr, nullptr, nullptr), SPF_OK, "", grp);
+    gexpect("group blind_rotation n_bits 0", spf_group_blind_rotation_batch(grp, 0, 0, 0, nullptr, nullptr, nullptr), BAD, "n_bits must be at least 1", grp);
+    gexpect("group blind_rotation B * n_bits one past",
+            spf_group_blind_rotation_batch(grp, 0x0fffffff / nb + 1, nb, 0, ggsw.data(), glwe.data(), o_glwe.data()), BAD, rows_above, grp);
+    gexpect("group public_functional_keyswitch null group", spf_group_public_functional_keyswitch_batch(nullptr, 0, pu_p, pu_rows.data(), pu_out), BAD, "null group", nullptr);
+    gexpect("group public_functional_keyswitch nulls at B 0", spf_group_public_functional_keyswitch_batch(grp, 0, pu_p, nullptr, nullptr), BAD, null_arg, grp);
+    gexpect("group public_functional_keyswitch B 0", spf_group_public_functional_keyswitch_batch(grp, 0, pu_p, pu_rows.data(), pu_out), SPF_OK, "", grp);
+    gexpect("group public_functional_keyswitch lwe_count 0", spf_group_public_functional_keyswitch_batch(grp, B, 0, pu_rows.data(), pu_out), BAD,
+            "lwe_count must be at least 1", grp);
+    gexpect("group public_functional_keyswitch B * lwe_count one past",
+            spf_group_public_functional_keyswitch_batch(grp, 0x0fffffff / pu_p + 1, pu_p, pu_rows.data(), pu_out), BAD, pu_above, grp);
+    m0->pufks_ready = false;
+    gexpect("group public_functional_keyswitch no key", spf_group_public_functional_keyswitch_batch(grp, 0, pu_p, pu_rows.data(), pu_out), SPF_ERR_NO_KEY,
+            "public functional keyswitch key not loaded", grp);
+    gexpect("group public_functional_keyswitch no key, lwe_count 0", spf_group_public_functional_keyswitch_batch(grp, B, 0, pu_rows.data(), pu_out), BAD,
+            "lwe_count must be at least 1", grp);
+    gexpect("group private_functional_keyswitch nulls at B 0", spf_group_private_functional_keyswitch_batch(grp, 0, 0, nullptr, nullptr), BAD, null_arg, grp);
+    gexpect("group private_functional_keyswitch B 0", spf_group_private_functional_keyswitch_batch(grp, k, 0, pf_rows.data(), pf_out), SPF_OK, "", grp);
+    gexpect("group private_functional_keyswitch key_index k + 1", spf_group_private_functional_keyswitch_batch(grp, k + 1, over_tail, pf_rows.data(), pf_out), BAD,
+            "key_index >= n_keys", grp);
+    gexpect("group private_functional_keyswitch B 0x10000000", spf_group_private_functional_keyswitch_batch(grp, 0, over_tail, pf_rows.data(), pf_out), BAD, too_large, grp);
+    m0->pfks_ready = false;
+    gexpect("group private_functional_keyswitch no keys", spf_group_private_functional_keyswitch_batch(grp, k + 1, over_tail, pf_rows.data(), pf_out), SPF_ERR_NO_KEY,
+            pf_none, grp);
+    gexpect("group circuit_bootstrap_via_pfks nulls at B 0, no keys", spf_group_circuit_bootstrap_via_pfks_batch(grp, 0, nullptr, nullptr), SPF_OK, "", grp);
+    gexpect("group circuit_bootstrap_via_pfks null out", spf_group_circuit_bootstrap_via_pfks_batch(grp, B, lwe0_ggsw.data(), nullptr), BAD, null_arg, grp);
+    gexpect("group lwe_linear nulls at B 0", spf_group_lwe_linear_batch(grp, 0, SPF_VAL_LWE0, 0, nullptr, nullptr), BAD, null_arg, grp);
+    gexpect("group lwe_linear B 0", spf_group_lwe_linear_batch(grp, 0, SPF_VAL_LWE0, 0, lin_rows.data(), lin_out), SPF_OK, "", grp);
+    gexpect("group lwe_linear slot 64", spf_group_lwe_linear_batch(grp, 64, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), BAD, "slot 64 >= SPF_LWE_LINEAR_SLOTS = 64", grp);
+    gexpect("group lwe_linear kind GGSW1", spf_group_lwe_linear_batch(grp, 0, SPF_VAL_GGSW1, B, lin_rows.data(), lin_out), BAD,
+            "kind must be SPF_VAL_LWE0 or SPF_VAL_LWE1", grp);
+    gexpect("group lwe_linear empty slot", spf_group_lwe_linear_batch(grp, 1, SPF_VAL_LWE0, B, lin_rows.data(), lin_out), SPF_ERR_NO_KEY, "no weights loaded in slot 1", grp);
+    gexpect("group lwe_linear B * max(M, K) one past", spf_group_lwe_linear_batch(grp, 0, SPF_VAL_LWE0, 0x0fffffff / lin_K + 1, lin_rows.data(), lin_out), BAD,
+            too_large, grp);
+    gexpect("group lwe_linear out on the last input word", spf_group_lwe_linear_batch(grp, 0, SPF_VAL_LWE0, B, lin_rows.data(), lin_out - 1), BAD, overlap, grp);
+    spf_group_destroy(grp);
+    return ok;
+}
+
+// The operand and result widths of every spf_*_batch entry point, in 64-bit words per item, as the sentences of include/spf_hip.h
+// state them (a complex bin is two words) — written out here on purpose, NOT computed with the library's size helpers — against
+// the batch shapes of spf_ops.hpp that the three forms of each entry point share.  Operands in the order the shape lists them
+// (the order they are staged in: a selector or spectrum first); `max`: the batch limit where the header states one, else 0.
+bool batch_shapes_match_the_header(const spf_params& p)
+{
+    const size_t n = p.lwe_dimension, k = p.glwe_size, N = p.polynomial_degree, l = p.cbs_radix_count;
+    const size_t lwe0 = n + 1, lwe1 = k * N + 1, glwe = (k + 1) * N, glev = l * (k + 1) * N, ggsw = 2 * ((k + 1) * l * (k + 1) * N / 2);
+    const size_t n_bits = 3, stride = glwe + 5, lwe_count = 2, from = 9, M = 5, K = 7;
+    const int L0 = SPF_VAL_LWE0, L1 = SPF_VAL_LWE1, GL = SPF_VAL_GLWE1, GG = SPF_VAL_GGSW1;
+    const struct { const char* entry; BatchShape got; int n_in; size_t in[3]; size_t out; size_t max; } rows[] = {
+        {"poly_fft", poly_fft_shape(p), 1, {N}, 2 * (N / 2), 0},
+        {"keyswitch_lwe_l1_lwe_l0", spf_ops::shape(p, spf_ops::OP_KEYSWITCH), 1, {lwe1}, lwe0, 0},
+        {"generalized_pbs", pbs_shape(p, false, false, stride), 2, {lwe0, stride}, glwe, 0},
+                {"pbs_univariate", pbs_shape(p, true, false, stride), 2, {lwe0, stride}, lwe1, 0},
+        {"pbs_bivariate", pbs_shape(p, true, true, stride), 3, {lwe0, lwe0, stride}, lwe1, 0},
+        {"circuit_bootstrap_pbs", pbs_shape(p, false), 2, {lwe0, 0}, glwe, 0},
+        {"circuit_bootstrap", spf_ops::shape(p, spf_ops::OP_CBS), 1, {lwe0}, ggsw, 0},
+        {"mod_switch_trace_and_rotate", trace_shape(p), 1, {glwe}, glev, 0},
+        {"scheme_switch", spf_ops::shape(p, spf_ops::OP_SCHEME_SWITCH), 1, {glev}, ggsw, 0},
+        {"sample_extract_l1", spf_ops::shape(p, spf_ops::OP_SAMPLE_EXTRACT), 1, {glwe}, lwe1, 0},
+        {"glwe_not", spf_ops::shape(p, spf_ops::OP_NOT), 1, {glwe}, glwe, 0},
+        {"glwe_mul_xn", spf_ops::shape(p, spf_ops::OP_MUL_XN), 1, {glwe}, glwe, 0},
+        {"glwe_xor", spf_ops::shape(p, spf_ops::OP_GLWE_ADD), 2, {glwe, glwe}, glwe, 0},
+        {"cmux", spf_ops::shape(p, spf_ops::OP_CMUX), 3, {ggsw, glwe, glwe}, glwe, 0},
+        {"glev_cmux", spf_ops::shape(p, spf_ops::OP_GLEV_CMUX), 3, {ggsw, glev, glev}, glev, 0},
+        {"multiply_glwe_ggsw", spf_ops::shape(p, spf_ops::OP_MULTIPLY_GGSW_GLWE), 2, {ggsw, glwe}, glwe, 0},
+        {"gate_bootstrap", gate_bootstrap_shape(p), 1, {lwe1}, glwe, 0},
+        {"keyswitch_circuit_bootstrap", spf_ops::shape(p, spf_ops::OP_GATE_CBS), 1, {lwe1}, ggsw, 0},
+        {"glwe_pack", packed_shape(p, n_bits, GL, GL, true), 1, {n_bits * glwe}, glwe, 0x0fffffff / n_bits},
+        {"glwe_unpack_l1", packed_shape(p, n_bits, GL, L1, false), 1, {glwe}, n_bits * lwe1, 0x0fffffff / n_bits},
+        {"unpack_circuit_bootstrap", packed_shape(p, n_bits, GL, GG, false), 1, {glwe}, n_bits * ggsw, 0x0fffffff / n_bits},
+        {"blind_rotation", blind_rotation_shape(p, n_bits), 2, {n_bits * ggsw, glwe}, glwe, 0x0fffffff / n_bits},
+        {"public_functional_keyswitch", pufks_shape(p, lwe_count, from), 1, {lwe_count * (from + 1)}, glwe, 0x0fffffff / lwe_count},
+        {"private_functional_keyswitch", pfks_shape(p, lwe_count * (from + 1)), 1, {lwe_count * (from + 1)}, glwe, 0x0fffffff},
+        {"apply_pfks_on_ggsw_components", pfks_components_shape(p, lwe1), 1, {l * lwe1}, (k + 1) * l * (k + 1) * N, 0},
+        {"circuit_bootstrap_via_pfks", cbs_via_pfks_shape(p), 1, {lwe0}, ggsw, 0},
+        {"lwe_linear, level 0", lwe_linear_batch_shape(p, M, K, L0), 1, {K * lwe0}, M * lwe0, 0},
+        {"lwe_linear, level 1", lwe_linear_batch_shape(p, M, K, L1), 1, {K * lwe1}, M * lwe1, 0},
+    };
+    bool ok = true;
+    for (const auto& r : rows) {
+        bool same = r.got.n_in == r.n_in && r.got.out_words == r.out && (!r.max || r.got.max_batch == r.max);
+        for (int i = 0; i < 3; i++) same = same && r.got.in_words[i] == r.in[i];
+        if (same) continue;
+        fprintf(stderr, "batch shape of %s: %d operands of %zu / %zu / %zu words, result %zu, limit %zu; the header says %d of %zu / %zu / %zu, result %zu, limit %zu\n",
+                r.entry, r.got.n_in, r.got.in_words[0], r.got.in_words[1], r.got.in_words[2], r.got.out_words, r.got.max_batch, r.n_in, r.in[0], r.in[1],
+                r.in[2], r.out, r.max);
+        ok = false;
+    }
     return ok;
 }
 
@@ -648,6 +954,9 @@ int main(int argc, char** argv)
     if (!batch_forms_refuse_bad_arguments(&dflt_ctx)) return 1;
     if (!graph_ops_match_the_header(&dflt_ctx) || !graph_ops_match_the_header(&tiny_ctx)) return 1;
     if (!wire_sizes_match_the_header(dflt) || !wire_sizes_match_the_header(tiny)) return 1;
+    spf_params k2 = tiny; // a generic set with glwe_size 2 (and a cbs count that is no power of two)
+    k2.glwe_size = 2; k2.polynomial_degree = 64; k2.cbs_radix_count = 3;
+    if (!batch_shapes_match_the_header(dflt) || !batch_shapes_match_the_header(k2) || !batch_shapes_match_the_header(tiny)) return 1;
     std::vector<uint8_t> key_seed;
     {
         const size_t want[4] = {(size_t)tiny.lwe_dimension * ggsw_fft_complex(tiny, tiny.pbs_radix_count),
