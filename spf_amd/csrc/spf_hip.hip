@@ -507,6 +507,8 @@ spf_status launch_keyswitch(spf_ctx* c, hipStream_t s, size_t B, const uint64_t*
         hipLaunchKernelGGL(ks_gemm_lds_kernel, grid, dim3(256), kKsLdsBytes, s, g); // operand tiles staged through LDS by LDS-DMA
         c->last_ks_kernel = "ks_gemm_lds_kernel";
     } else {
+        // (the whole batch in one grid: grid.y = 65536 launches and computes on gfx950, tests/test_gpu_launch_slices.py; larger
+        // values are not held by a test)
         dim3 grid((a.n_out + 1 + 255) / 256, (unsigned)((B + KS_CT - 1) / KS_CT)), block(256);
         hipLaunchKernelGGL(keyswitch_kernel, grid, block, 0, s, a);
         c->last_ks_kernel = "keyswitch_kernel";
@@ -3022,7 +3024,8 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
         return ts.end();
     }
     // items per launch: what keeps the planes of a launch within kLweLinearImageCap, the plane rows within 32 bits and grid.z
-    // of the planes pass within its limit (at least one: an item whose planes exceed the cap is served above)
+    // of the planes pass within its limit (at least one: an item whose planes exceed the cap is served above).  The 2^28 / W term
+    // is a guard, not a live limit: item_planes >= 1024 W, so the cap term is at most 2^20 / W for every W.
     size_t per = std::max<size_t>(1, kLweLinearImageCap / item_planes);
     per = std::min({per, B, (size_t)65535, std::max<size_t>(1, ((size_t)1 << 28) / W)});
     st = ensure(c, c->lin_planes, ((8 * per * W + PFKS_TILE - 1) / PFKS_TILE * PFKS_TILE) * l.Kpad);

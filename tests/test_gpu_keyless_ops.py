@@ -106,3 +106,15 @@ def test_batches_beyond_one_grid_slice():
     del got, exp
     n1 = eng.glwe_not(glwe)
     assert np.array_equal(n1[:, N], glwe[:, N] + np.uint64(1 << 63)) and np.array_equal(n1[:, :N], glwe[:, :N])
+    assert np.array_equal(n1[:, N + 1:], glwe[:, N + 1:])
+    del n1
+    # glwe_linear_kernel<XOR> and <MUL_XN> past the same slice (tests/launch_slice_cases.py lists this test for the three)
+    x = eng.glwe_xor(glwe, glwe)
+    assert np.array_equal(x, glwe + glwe)
+    assert np.array_equal(x[B - 1], O.glwe_xor(glwe[B - 1], glwe[B - 1], P.N, P.k))
+    del x
+    n = N + 5                                                        # X^(N + 5) = -X^5: every coefficient moves, every sign is used
+    got = eng.glwe_mul_xn(glwe, n).reshape(B, 2, N)
+    src = glwe.reshape(B, 2, N)
+    assert np.array_equal(got[:, :, 5:], np.uint64(0) - src[:, :, :N - 5]) and np.array_equal(got[:, :, :5], src[:, :, N - 5:])
+    assert np.array_equal(got[B - 1].reshape(-1), O.glwe_mul_xn(glwe[B - 1], n, P.N, P.k))
