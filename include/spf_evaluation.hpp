@@ -370,6 +370,16 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_public_functional_keyswitch(g_, lwes.data(), lwes.size(), &n), ctx_);
         return n;
     }
+    // The plaintext linear map of weight slot `slot` (Evaluation::load_lwe_linear_weights) as nodes — no FheOp in the reference:
+    // M nodes of the operands' kind, node m = sum over k of weights[m][k] * lwes[k] (+ bias[m] on the body), the L0 (or L1) LWE
+    // nodes `lwes` from anywhere in the graph.  What stands between two bootstraps by table: a layer, then its activation.  The
+    // slot is read by run(); M and the operand count are checked against it there
+    std::vector<Node> lwe_linear(uint32_t slot, const std::vector<Node>& lwes, size_t M)
+    {
+        std::vector<Node> rows(M ? M : 1); // (M = 0 is refused by the library: a place for it to leave untouched)
+        Evaluation::check(spf_graph_add_lwe_linear(g_, slot, lwes.data(), lwes.size(), M, rows.data()), ctx_);
+        return rows;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }

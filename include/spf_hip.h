@@ -752,6 +752,26 @@ spf_status spf_graph_add_blind_rotation(spf_graph *graph, uint32_t glwe_node, co
  * while no public functional keyswitch key is loaded, and SPF_ERR_INVALID_ARGUMENT when the key's from_dimension is not the
  * dimension of the operands (lwe_dimension for lwe0, glwe_size * polynomial_degree for lwe1). */
 spf_status spf_graph_add_public_functional_keyswitch(spf_graph *graph, const uint32_t *lwe_nodes, size_t lwe_count, uint32_t *node_out);
+/* The plaintext linear map of weight slot `slot` (spf_load_lwe_linear_weights above) as a node constructor — no FheOp there, no
+ * spf_graph_op here: what stands between two SPF_OP_PBS_* nodes (a layer, then its activation table).  lwe_nodes[0 .. K) are all
+ * lwe0 or all lwe1 nodes of any origin and level (inputs, trivials, sample extracts, unpack bits, keyswitch results, bootstrap
+ * results, results of another linear node; repeats allowed); creates M nodes of the operands' kind, all one level above the highest
+ * operand, nodes_out[m] word-equal to row m of spf_lwe_linear_batch(slot, kind, B = 1) over those K rows in that order, bias
+ * included.  The new nodes are ordinary: operands of any operation, outputs, counted by spf_graph_stats.  All layers of one level
+ * with one (slot, M, K, operand kind) are one group: operand rows that lie consecutively in the graph's memory (the K results of
+ * one bootstrap or keyswitch group, or of another layer) go to the dispatcher of spf_lwe_linear_enqueue in place, anything else is
+ * ONE launch of lwe_linear_rows_kernel that reads the rows where they lie (the name spf_last_lwe_linear_kernel then gives; timed
+ * as "lwe_linear").  A wrong argument (slot >= SPF_LWE_LINEAR_SLOTS, K = 0, M = 0 or M > SPF_GRAPH_LWE_LINEAR_MAX_ROWS, a null
+ * pointer, a node that does not exist or is no LWE, lwe0 and lwe1 mixed) is SPF_ERR_INVALID_ARGUMENT from the call, nothing is
+ * recorded and the graph stays usable.  The slot is read by spf_graph_run — it may be loaded after the graph is built, and loaded
+ * again between runs under the rule of the key loads (the next run uses the new weights; a graph of a group reads the slot of the
+ * member it runs on): before anything is enqueued, an empty slot is SPF_ERR_NO_KEY and a slot whose (M, K) is not the nodes' is
+ * SPF_ERR_INVALID_ARGUMENT with both shapes in the message.
+ * spf_lwe_linear_slot_shape: M, K and whether a bias is loaded in `slot`; SPF_ERR_NO_KEY while the slot is empty. */
+typedef enum spf_graph_lwe_linear_limits { SPF_GRAPH_LWE_LINEAR_MAX_ROWS = 4096 } spf_graph_lwe_linear_limits;
+spf_status spf_lwe_linear_slot_shape(spf_ctx *ctx, uint32_t slot, size_t *M, size_t *K, int *has_bias);
+spf_status spf_graph_add_lwe_linear(spf_graph *graph, uint32_t slot, const uint32_t *lwe_nodes /* K */, size_t K,
+                                    size_t M, uint32_t *nodes_out /* M */);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */

@@ -103,6 +103,7 @@ SYMBOLS = [
     ("spf_lwe_linear_batch", _I, [_P, _U32, _I, _SZ, _P, _P]),
     ("spf_lwe_linear_enqueue", _I, [_P, _P, _U32, _I, _SZ, _P, _P]),
     ("spf_last_lwe_linear_kernel", C.c_char_p, [_P]),
+    ("spf_lwe_linear_slot_shape", _I, [_P, _U32, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -138,6 +139,7 @@ SYMBOLS = [
     ("spf_graph_add_pack", _I, [_P, C.POINTER(_U32), _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_blind_rotation", _I, [_P, _U32, C.POINTER(_U32), _SZ, _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_public_functional_keyswitch", _I, [_P, C.POINTER(_U32), _SZ, C.POINTER(_U32)]),
+    ("spf_graph_add_lwe_linear", _I, [_P, _U32, C.POINTER(_U32), _SZ, _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_output", _I, [_P, _U32, _P]),
     ("spf_graph_run", _I, [_P]),
     ("spf_graph_stats", _I, [_P, C.POINTER(_U32), C.POINTER(_U32), C.POINTER(_U32)]),
@@ -761,14 +763,22 @@ class Engine:
         self._ck(self._lib.spf_load_lwe_linear_weights(self._h, int(slot), w.shape[0], w.shape[1], _ptr(w), _ptr(b) if b is not None else None))
         shapes[int(slot)] = (int(w.shape[0]), int(w.shape[1]))
 
+    def lwe_linear_slot_shape(self, slot: int):
+        """`spf_lwe_linear_slot_shape`: (M, K, has_bias) of the weights in `slot`; an empty slot is SPF_ERR_NO_KEY"""
+        M, K, has_bias = _SZ(), _SZ(), C.c_int()
+        self._ck(self._lib.spf_lwe_linear_slot_shape(self._h, int(slot) & 0xFFFFFFFF, C.byref(M), C.byref(K), C.byref(has_bias)))
+        return int(M.value), int(K.value), bool(has_bias.value)
+
     def _lin(self, slot: int, kind: int):
         """(M, K, W) of a loaded slot for ciphertexts of `kind`; whatever the library refuses is refused by the library"""
         shape = self.__dict__.get("_lin_shapes", {}).get(int(slot)) if 0 <= int(slot) < 2**32 else None
-        if shape is None or int(kind) not in (VAL_LWE0, VAL_LWE1):
+        if int(kind) not in (VAL_LWE0, VAL_LWE1):   # (the slot first, then the kind: the order of the batch call's own checks)
             one = np.zeros(1, dtype=np.uint64)
             two = np.zeros(1, dtype=np.uint64)
             self._ck(self._lib.spf_lwe_linear_batch(self._h, int(slot) & 0xFFFFFFFF, int(kind), 0, _ptr(one), _ptr(two)))
-            raise SpfError(3, f"lwe_linear: no weights loaded in slot {slot} through this handle")
+            raise SpfError(1, f"lwe_linear: kind {kind} is not an LWE kind")
+        if shape is None:   # not loaded through this handle: the library knows
+            shape = self.lwe_linear_slot_shape(slot)[:2]
         return shape + (self.params.lwe0_words if int(kind) == VAL_LWE0 else self.params.lwe1_words,)
 
     def lwe_linear(self, slot: int, lwes, kind: int = 0) -> np.ndarray:
@@ -1006,6 +1016,10 @@ class Group(Engine):
 
     def debug_fail_next(self, member: int, count: int = 1):
         self._ck(self._raw.spf_group_debug_fail_next(self._h, member, count))
+
+    def lwe_linear_slot_shape(self, slot: int):
+        """of member 0: `spf_group_load_lwe_linear_weights` loads every member alike"""
+        return self.member(0).lwe_linear_slot_shape(slot)
 
     def run_graphs(self, graphs):
         """`spf_group_run_graphs`: graphs are `spf_amd.FheCircuit`s made over this group; dealt to the members by cost,

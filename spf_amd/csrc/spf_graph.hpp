@@ -37,6 +37,13 @@
 // such nodes of one level with one (lwe_count, kind) are one main launch (launch_pufks_rows; rows that lie consecutively take the
 // contiguous entry point).
 //
+// A plaintext linear map over LWE ciphertexts (spf_lwe_linear.hpp) is a fifth constructor: spf_graph_add_lwe_linear makes the M
+// rows of weight slot `slot` times K LWE nodes of one kind, from anywhere — what stands between two bootstraps by table (a layer,
+// then its activation).  All layers of one level with one (slot, M, K, kind) are one group whose output is [layers][M][W]; operand
+// rows that lie consecutively (the results of one bootstrap or keyswitch group, or of another layer) go to the batch dispatcher
+// in place, matrix cores included, anything else is ONE launch of lwe_linear_rows_kernel over a pointer table.  The slot is read
+// when the graph runs: it may be loaded, and loaded again, after the graph is built.
+//
 // Included at the end of spf_hip.hip: uses its `fail` / HIPCHK helpers and the `_dev` entry points.
 #pragma once
 
@@ -74,24 +81,27 @@ struct spf_pinned_buf {
 
 struct spf_graph {
     // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation /
-    // spf_graph_add_public_functional_keyswitch)
-    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67 };
-    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks; } // operands in pack_in, not in Node::in
+    // spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear)
+    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68 };
+    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks || op == kNodeLweLinear; } // operands in pack_in, not in Node::in
     struct Node {
         int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack / kNodeRotCmux, or -1 input, -2 trivial constant
         int32_t kind;      // spf_value_kind of the value the node produces
-        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node
+        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node /
+                           // row index m of a linear node
         uint32_t in[3];    // (rotate-CMUX nodes: {selector, accumulator})
         uint32_t n_in;
-        uint32_t n_bits;   // unpack and pack nodes: width of the integer; public functional keyswitch nodes: lwe_count
-        uint32_t ext;      // pack and public functional keyswitch nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
+        uint32_t n_bits;   // unpack and pack nodes: width of the integer; public functional keyswitch nodes: lwe_count; linear nodes: K
+        uint32_t ext;      // pack, public functional keyswitch and linear nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
+        uint32_t lin_slot, lin_rows; // linear nodes: the weight slot and M (the M nodes of one call share one operand list)
         uint32_t level;
         size_t off;        // byte offset of the value in the arena
         const void* host;  // inputs: caller's buffer, read at every run
     };
     struct Group {
         int32_t op;
-        uint64_t param;    // (unpack and pack groups: n_bits; public functional keyswitch groups: lwe_count | operand kind << 32)
+        uint64_t param;    // (unpack and pack groups: n_bits; public functional keyswitch groups: lwe_count | operand kind << 32;
+                           // linear groups: K | M << 32 | slot << 48 | operand kind << 56)
         std::vector<uint32_t> members;
         size_t out_off = 0;
         // per operand slot: offset of the first operand when the members' operands are contiguous
@@ -107,7 +117,7 @@ struct spf_graph {
     struct spf_group* grp = nullptr; // a graph of a device group (spf_group_graph_create): placed on a member when it is run
     int member = -1;                 // ... the member its most recent run took place on
     std::vector<Node> nodes;
-    std::vector<uint32_t> pack_in; // operand lists of the pack and the public functional keyswitch nodes
+    std::vector<uint32_t> pack_in; // operand lists of the pack, the public functional keyswitch and the linear nodes
     // f(operand id) for every operand of a node
     template <class F> void for_operands(const Node& n, F f) const
     {
@@ -139,6 +149,7 @@ struct spf_graph {
     }
     size_t inputs_bytes = 0, arena_bytes = 0, stage_bytes = 0;
     bool has_pufks = false, pufks_stage = false; // public functional keyswitch nodes: any; planned with room to gather their rows
+    bool has_linear = false;                     // linear nodes: any (their weight slots are checked at every run)
     char* d_arena = nullptr;
     char* d_stage[2] = {nullptr, nullptr};
     void** d_ptrs = nullptr;
@@ -147,7 +158,7 @@ struct spf_graph {
     // SPF_GRAPH_CAPTURE=1): captured on the second run after planning (the first one sizes the context's scratch buffers),
     // replayed afterwards; dropped when the graph is re-planned or a captured scratch buffer moved
     hipGraphExec_t exec = nullptr;
-    uint64_t exec_epoch = 0;
+    uint64_t exec_epoch = 0, exec_lin_epoch = 0; // (the second: the context's count of weight loads, for a graph with linear nodes)
     uint32_t runs_since_plan = 0, captured_launches = 0;
 
     void drop_exec()
@@ -254,13 +265,18 @@ inline spf_status plan(spf_graph* g)
     g->n_levels = max_level;
     // one group per (level, kind, parameter), members in node order.  Unpack and pack nodes group by their width: the bit
     // nodes of one spf_graph_add_unpack call have consecutive ids and one level (their source's + 1; nothing below moves
-    // them), so a group's members are whole integers, int-major
+    // them), so a group's members are whole integers, int-major.  Linear nodes group by (slot, M, K, operand kind): the M nodes of
+    // one spf_graph_add_lwe_linear call have consecutive ids, one operand list and so one level, and nothing above moves them (they
+    // are no bootstrap and no head of a conversion chain), so a group's members are whole layers, layer-major
     std::map<std::tuple<uint32_t, int32_t, uint64_t>, size_t> index;
     for (uint32_t id = 0; id < g->nodes.size(); id++) {
         const auto& n = g->nodes[id];
         if (n.op < 0) continue;
         const uint64_t key_param = n.op == spf_graph::kNodeUnpack || n.op == spf_graph::kNodePack ? n.n_bits
-                                   : n.op == spf_graph::kNodePufks ? n.n_bits | (uint64_t)g->nodes[g->pack_in[n.ext]].kind << 32 : n.param;
+                                   : n.op == spf_graph::kNodePufks ? n.n_bits | (uint64_t)g->nodes[g->pack_in[n.ext]].kind << 32
+                                   : n.op == spf_graph::kNodeLweLinear
+                                       ? n.n_bits | (uint64_t)n.lin_rows << 32 | (uint64_t)n.lin_slot << 48 | (uint64_t)n.kind << 56
+                                       : n.param;
         auto key = std::make_tuple(n.level, n.op, key_param);
         auto it = index.find(key);
         if (it == index.end()) {
@@ -291,6 +307,7 @@ inline spf_status plan(spf_graph* g)
     // operand access per group
     std::vector<void*> table;
     g->has_pufks = false;
+    g->has_linear = false;
     g->pufks_stage = !pufks_tuned(c) || pufks_rows_gather(); // (also while no key is loaded: the key that comes may be of any radix)
     for (auto& gr : g->groups) {
         const size_t B = gr.members.size();
@@ -310,6 +327,24 @@ inline spf_status plan(spf_graph* g)
                 gr.ptr_index[0] = table.size();
                 for (size_t o : offs) table.push_back(g->d_arena + o);
                 if (g->pufks_stage) stage = std::max(stage, offs.size() * rb);
+            }
+            continue;
+        }
+        if (gr.op == spf_graph::kNodeLweLinear) {
+            // the K rows of every layer, layer-major (every M-th member starts a layer): in place when all of them lie consecutively
+            // (the batch dispatcher, matrix cores included), else read through the table by lwe_linear_rows_kernel
+            g->has_linear = true;
+            const size_t M = (size_t)(gr.param >> 32 & 0xffff), rb = value_bytes(g->prm, (int)(gr.param >> 56));
+            std::vector<size_t> offs;
+            for (size_t i = 0; i < B; i += M)
+                g->for_operands(g->nodes[gr.members[i]], [&](uint32_t in) { offs.push_back(g->nodes[in].off); });
+            bool contig = true;
+            for (size_t i = 1; i < offs.size() && contig; i++) contig = offs[i] == offs[0] + i * rb;
+            gr.contiguous[0] = contig;
+            gr.first_off[0] = offs[0];
+            if (!contig) {
+                gr.ptr_index[0] = table.size();
+                for (size_t o : offs) table.push_back(g->d_arena + o);
             }
             continue;
         }
@@ -471,6 +506,21 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
             if (st != SPF_OK) return st;
             continue;
         }
+        if (gr.op == spf_graph::kNodeLweLinear) {
+            const size_t M = (size_t)(gr.param >> 32 & 0xffff);
+            const uint32_t slot = (uint32_t)(gr.param >> 48 & 0xff);
+            const spf_value_kind kind = (spf_value_kind)(gr.param >> 56);
+            spf_status st;
+            if (gr.contiguous[0]) {
+                st = spf_lwe_linear_enqueue(c, s, slot, kind, B / M, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
+                g->n_launches += c->last_lin_launches;
+            } else {
+                st = launch_lwe_linear_rows(c, s, slot, kind, B / M, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
+                g->n_launches++;
+            }
+            if (st != SPF_OK) return st;
+            continue;
+        }
         if (gr.op == spf_graph::kNodePack) {
             spf_status st = launch_glwe_pack_rows(c, s, B, gr.param, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
             if (st != SPF_OK) return st;
@@ -549,6 +599,25 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
     return SPF_OK;
 }
 
+// The weight slots of the linear groups against their nodes: a slot comes with its own shape and may be loaded after the graph is
+// built.  Run before anything is enqueued, on the replay of a captured graph as well.
+inline spf_status check_linear_slots(spf_graph* g)
+{
+    spf_ctx* c = g->ctx;
+    for (const auto& gr : g->groups)
+        if (gr.op == spf_graph::kNodeLweLinear) {
+            const size_t K = (size_t)(gr.param & 0xffffffffu), M = (size_t)(gr.param >> 32 & 0xffff);
+            const uint32_t slot = (uint32_t)(gr.param >> 48 & 0xff);
+            const LweLinearSlot& l = c->lin[slot];
+            if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no weights loaded in slot " + std::to_string(slot));
+            if (l.M != M || l.K != K)
+                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: slot " + std::to_string(slot) + " holds " + std::to_string(l.M) + " x " +
+                                                             std::to_string(l.K) + " weights, its linear nodes were built for " +
+                                                             std::to_string(M) + " x " + std::to_string(K));
+        }
+    return SPF_OK;
+}
+
 // Output staging (after plan(): needs the arena offsets): outputs grouped by value size, one pointer row per group
 inline spf_status plan_outputs(spf_graph* g)
 {
@@ -595,6 +664,10 @@ inline spf_status run(spf_graph* g)
         spf_status st = plan(g);
         if (st != SPF_OK) return st;
     }
+    if (g->has_linear) {
+        spf_status st = check_linear_slots(g);
+        if (st != SPF_OK) return st;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t k = g->prm.glwe_size, N = g->prm.polynomial_degree;
@@ -632,6 +705,7 @@ inline spf_status run(spf_graph* g)
     static const bool capture_on = [] { const char* e = getenv("SPF_GRAPH_CAPTURE"); return e && e[0] == '1'; }();
     g->runs_since_plan++;
     if (g->exec && g->exec_epoch != c->buf_epoch) g->drop_exec(); // a scratch buffer moved since the capture
+    if (g->exec && g->has_linear && g->exec_lin_epoch != c->lin_epoch) g->drop_exec(); // a weight slot was loaded: its old image is freed
     if (g->exec) {
         HIPCHK(c, hipGraphLaunch(g->exec, s));
         g->n_launches = g->captured_launches;
@@ -646,6 +720,7 @@ inline spf_status run(spf_graph* g)
             if (st == SPF_OK && e == hipSuccess && graph && epoch0 == c->buf_epoch &&
                 hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                 g->exec_epoch = c->buf_epoch;
+                g->exec_lin_epoch = c->lin_epoch;
                 g->captured_launches = g->n_launches;
             } else {
                 g->exec = nullptr;
@@ -839,6 +914,46 @@ spf_status spf_graph_add_public_functional_keyswitch(spf_graph* g, const uint32_
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
     *node_out = (uint32_t)g->nodes.size() - 1;
+    g->planned = false;
+    return SPF_OK;
+}
+
+// The linear map of weight slot `slot` (spf_lwe_linear.hpp) as a node constructor: M nodes of the operands' kind, node m = row m of
+// the slot's matrix times lwe_nodes[0 .. K) (+ bias[m]); one operand list in the side list for all M.  The slot itself is looked at
+// by spf_graph_run, not here
+spf_status spf_graph_add_lwe_linear(spf_graph* g, uint32_t slot, const uint32_t* lwe_nodes, size_t K, size_t M, uint32_t* nodes_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!lwe_nodes || !nodes_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: null pointer");
+    if (slot >= SPF_LWE_LINEAR_SLOTS)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: slot " + std::to_string(slot) + " >= SPF_LWE_LINEAR_SLOTS = " +
+                                                          std::to_string(SPF_LWE_LINEAR_SLOTS));
+    if (K == 0 || K > 0xffffffffu) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: K must be in 1 ..= 2^32 - 1");
+    if (M == 0 || M > SPF_GRAPH_LWE_LINEAR_MAX_ROWS)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: M must be in 1 ..= SPF_GRAPH_LWE_LINEAR_MAX_ROWS = " +
+                                                          std::to_string(SPF_GRAPH_LWE_LINEAR_MAX_ROWS));
+    for (size_t i = 0; i < K; i++) {
+        if (lwe_nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: operand is not a node of this graph");
+        const int kind = g->nodes[lwe_nodes[i]].kind;
+        if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: operand is not an LWE");
+        if (kind != g->nodes[lwe_nodes[0]].kind) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: lwe0 and lwe1 operands mixed");
+    }
+    spf_graph::Node n{};
+    n.op = spf_graph::kNodeLweLinear; n.kind = g->nodes[lwe_nodes[0]].kind; n.n_bits = (uint32_t)K; n.ext = (uint32_t)g->pack_in.size();
+    n.lin_slot = slot; n.lin_rows = (uint32_t)M;
+    const uint32_t first = (uint32_t)g->nodes.size();
+    try {
+        g->nodes.reserve(g->nodes.size() + M); // all of the layer's nodes or none
+        g->pack_in.insert(g->pack_in.end(), lwe_nodes, lwe_nodes + K);
+    } catch (const std::exception&) {
+        g->pack_in.resize(n.ext);
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    for (size_t m = 0; m < M; m++) {
+        n.param = m;
+        g->nodes.push_back(n);
+        nodes_out[m] = first + (uint32_t)m;
+    }
     g->planned = false;
     return SPF_OK;
 }

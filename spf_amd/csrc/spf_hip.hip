@@ -167,6 +167,8 @@ struct spf_ctx {
     LweLinearSlot lin[SPF_LWE_LINEAR_SLOTS];
     DevBuf lin_planes;
     const char* last_lin_kernel = "";
+    uint64_t lin_epoch = 0;         // bumped by every spf_load_lwe_linear_weights (captured gate graphs hold a slot's pointers)
+    uint32_t last_lin_launches = 0; // kernel launches the last spf_lwe_linear_enqueue made (spf_graph_stats)
 };
 
 namespace {
@@ -2929,6 +2931,7 @@ spf_status spf_load_lwe_linear_weights(spf_ctx* c, uint32_t slot, size_t M, size
     HIPCHK(c, hipStreamSynchronize(c->stream));
     LweLinearSlot& l = c->lin[slot];
     lwe_linear_drop(l);
+    c->lin_epoch++;
     long long lo = weights[0], hi = weights[0];
     for (size_t i = 1; i < M * K; i++) { lo = std::min<long long>(lo, weights[i]); hi = std::max<long long>(hi, weights[i]); }
     LweLinearSlot n;
@@ -3000,6 +3003,7 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
     const size_t M = l.M, K = l.K, W = value_words(c->prm, kind);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
+    c->last_lin_launches = 0;
     const size_t item_planes = 8 * W * l.Kpad; // bytes of one item's byte planes
     const bool mfma_legal = l.U != 0 && item_planes <= kLweLinearImageCap;
     const int forced = lwe_linear_forced_path();
@@ -3018,6 +3022,7 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
                                     (uint32_t)nm, (uint32_t)M, (uint32_t)K, (uint32_t)W};
                 hipLaunchKernelGGL(lwe_linear_valu_kernel, dim3((unsigned)((W + 255) / 256), (unsigned)((nm + LWE_LINEAR_VT - 1) / LWE_LINEAR_VT), (unsigned)nb),
                                    dim3(256), 0, s, a);
+                c->last_lin_launches++;
             }
         }
         HIPCHK(c, hipGetLastError());
@@ -3039,6 +3044,7 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
             if (st != SPF_OK) return st;
             hipLaunchKernelGGL(lwe_linear_planes_kernel, dim3((unsigned)(l.Kpad / 64), (unsigned)((W + 31) / 32), (unsigned)nb), dim3(256), 0, s,
                                d_lwe_in + at * K * W, (int8_t*)c->lin_planes.p, (uint32_t)W, (uint32_t)K, (uint32_t)l.Kpad);
+            c->last_lin_launches++;
             HIPCHK(c, hipGetLastError());
             st = ts.end();
             if (st != SPF_OK) return st;
@@ -3057,6 +3063,7 @@ spf_status spf_lwe_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, spf_v
         if (l.d_bias)
             hipLaunchKernelGGL(lwe_linear_bias_kernel, dim3((unsigned)((nb * M + 255) / 256)), dim3(256), 0, s, o, (const uint64_t*)l.d_bias,
                                (uint32_t)M, (uint32_t)W, nb * M);
+        c->last_lin_launches += l.d_bias ? 2 : 1;
         HIPCHK(c, hipGetLastError());
         st = ts.end();
         if (st != SPF_OK) return st;
@@ -3073,6 +3080,40 @@ spf_status spf_lwe_linear_batch(spf_ctx* c, uint32_t slot, spf_value_kind kind, 
     return host_batch(c, sh, B, {{c->in, lwe_in}}, lwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
         return spf_lwe_linear_enqueue(c, c->stream, slot, kind, B, d_in, d_out);
     });
+}
+
+// The product over rows that are not contiguous (a level of a gate graph, spf_graph.hpp): d_rows is a device table of
+// layers * K device pointers, layer-major, d_out layers * M contiguous rows that overlap none of them.  The caller has checked
+// the slot against its nodes (M, K) and M <= SPF_GRAPH_LWE_LINEAR_MAX_ROWS: ONE launch of lwe_linear_rows_kernel whatever the
+// shape (layers in grid.x), the VALU product whatever the size.
+static spf_status launch_lwe_linear_rows(spf_ctx* c, hipStream_t s, uint32_t slot, spf_value_kind kind, size_t layers,
+                                         const uint64_t* const* d_rows, uint64_t* d_out)
+{
+    const LweLinearSlot& l = c->lin[slot];
+    const size_t W = value_words(c->prm, kind);
+    if (layers > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: more than 2^31 - 1 linear layers on one level");
+    c->last_lin_kernel = "lwe_linear_rows_kernel";
+    TimedScope ts(c, s, T_LIN);
+    spf_status st = ts.begin();
+    if (st != SPF_OK) return st;
+    LweLinearRowsArgs a{d_rows, l.d_w, l.d_bias, d_out, (uint32_t)l.M, (uint32_t)l.K, (uint32_t)W};
+    hipLaunchKernelGGL(lwe_linear_rows_kernel, dim3((unsigned)layers, (unsigned)((l.M + LWE_LINEAR_VT - 1) / LWE_LINEAR_VT), (unsigned)((W + 255) / 256)),
+                       dim3(256), 0, s, a);
+    HIPCHK(c, hipGetLastError());
+    return ts.end();
+}
+
+spf_status spf_lwe_linear_slot_shape(spf_ctx* c, uint32_t slot, size_t* M, size_t* K, int* has_bias)
+{
+    if (!c || !M || !K || !has_bias) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (slot >= SPF_LWE_LINEAR_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_LWE_LINEAR_SLOTS = " + std::to_string(SPF_LWE_LINEAR_SLOTS));
+    if (!c->lin[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no weights loaded in slot " + std::to_string(slot));
+    *M = c->lin[slot].M;
+    *K = c->lin[slot].K;
+    *has_bias = c->lin[slot].d_bias != nullptr;
+    return SPF_OK;
 }
 
 const char* spf_last_lwe_linear_kernel(spf_ctx* c)

@@ -25,7 +25,8 @@
 // The bias is one word per output row: lwe_linear_bias_kernel adds it after the GEMM (B M words against the GEMM's B M W), which
 // leaves pfks_gemm_kernel without a second instantiation and the PFKS code objects what they were.
 //
-// VALU path (weights beyond three limbs, small M, and whatever the first path declines): lwe_linear_valu_kernel.
+// VALU path (weights beyond three limbs, small M, and whatever the first path declines): lwe_linear_valu_kernel; the same product
+// over operands that do not lie consecutively (a level of a gate graph, through a pointer table): lwe_linear_rows_kernel.
 #pragma once
 
 #include "spf_pfks.hpp"
@@ -150,6 +151,48 @@ __global__ __launch_bounds__(256) void lwe_linear_valu_kernel(LweLinearValuArgs 
         if (m0 + t < a.M) {
             if (a.bias && col == a.W - 1) sum[t] += a.bias[m0 + t];
             a.out[((size_t)b * a.M_total + m0 + t) * a.W + col] = sum[t];
+        }
+}
+
+// ---- the same product over operands where they lie (a level of a gate graph, spf_graph.hpp): layer q reads its K rows through
+// row q of a pointer table and writes its M rows contiguously.  The row pointer of step k is workgroup-uniform like the weights
+// (a scalar load); the k loop is unrolled as above, so the pointer of step k + 1 is fetched before the row load of step k returns.
+// Layers in grid.x (2^31 - 1 of them), M <= SPF_GRAPH_LWE_LINEAR_MAX_ROWS in grid.y: any group is one launch.
+// grid (layers, ceil(M / LWE_LINEAR_VT), ceil(W / 256))
+struct LweLinearRowsArgs {
+    const uint64_t* const* in_ptrs; // [layers][K] device pointers to rows of W words
+    const long long* w;             // [M][K]
+    const uint64_t* bias;           // [M], or null
+    uint64_t* out;                  // [layers][M][W]
+    uint32_t M, K, W;
+};
+
+__global__ __launch_bounds__(256) void lwe_linear_rows_kernel(LweLinearRowsArgs a)
+{
+    const uint32_t col = blockIdx.z * 256 + threadIdx.x, m0 = blockIdx.y * LWE_LINEAR_VT;
+    const size_t q = blockIdx.x;
+    const bool live = col < a.W;
+    const uint32_t c = live ? col : 0;
+    const uint64_t* const* rows = a.in_ptrs + q * a.K;
+    const long long* wr[LWE_LINEAR_VT];
+    uint64_t sum[LWE_LINEAR_VT];
+#pragma unroll
+    for (int t = 0; t < LWE_LINEAR_VT; t++) {
+        wr[t] = a.w + (size_t)(m0 + t < a.M ? m0 + t : a.M - 1) * a.K;
+        sum[t] = 0;
+    }
+#pragma unroll 4
+    for (uint32_t k = 0; k < a.K; k++) {
+        const uint64_t xv = rows[k][c];
+#pragma unroll
+        for (int t = 0; t < LWE_LINEAR_VT; t++) sum[t] += xv * (uint64_t)wr[t][k];
+    }
+    if (!live) return;
+#pragma unroll
+    for (int t = 0; t < LWE_LINEAR_VT; t++)
+        if (m0 + t < a.M) {
+            if (a.bias && col == a.W - 1) sum[t] += a.bias[m0 + t];
+            a.out[(q * a.M + m0 + t) * a.W + col] = sum[t];
         }
 }
 

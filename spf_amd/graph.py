@@ -65,6 +65,12 @@ NODE_UNPACK = 64
 NODE_PACK = 65
 NODE_ROT_CMUX = 66
 NODE_PUFKS = 67
+# spf_graph_add_lwe_linear: one node per output row m, inputs = all K operands (one list shared by the M nodes of a call), param = m.
+# Not a NODE_* name yet: the random graph generator of the differential tests draws every NODE_* of this module, and it cannot draw
+# weights.  This becomes NODE_LWE_LINEAR in the change that teaches the generator to draw them.
+LWE_LINEAR_NODE = 68
+LWE_LINEAR_SLOTS = 64            # SPF_LWE_LINEAR_SLOTS
+LWE_LINEAR_GRAPH_MAX_ROWS = 4096  # SPF_GRAPH_LWE_LINEAR_MAX_ROWS
 
 # operand kinds of the operations whose arguments RecordedCircuit checks itself, as the library's table does (spf_ops.hpp)
 _PBS_IN_KINDS = {int(TableOp.PBS_UNIVARIATE): (0, 2), int(TableOp.PBS_BIVARIATE): (0, 0, 2)}
@@ -91,6 +97,16 @@ def _check_blind_rotation(what: str, n_bits: int, log_stride, degree: int) -> in
     if n_bits + log_stride > log_n:
         raise SpfError(1, f"{what}: n_bits + log_stride above log2(polynomial_degree) = {log_n}")
     return int(log_stride)
+
+
+def _check_lwe_linear(what: str, slot, n_operands: int, M) -> tuple:
+    if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < LWE_LINEAR_SLOTS:
+        raise SpfError(1, f"{what}: slot must be in 0 .. {LWE_LINEAR_SLOTS - 1}, got {slot!r}")
+    if n_operands < 1:
+        raise SpfError(1, f"{what}: K = 0 operands")
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 0 < M <= LWE_LINEAR_GRAPH_MAX_ROWS:
+        raise SpfError(1, f"{what}: M must be in 1 ..= {LWE_LINEAR_GRAPH_MAX_ROWS}, got {M!r}")
+    return int(slot), int(M)
 
 
 def _check_node(what: str, node, n_nodes: int) -> int:
@@ -196,6 +212,21 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_public_functional_keyswitch(self._g, arr, lwe_count, C.byref(node)))
         return node.value
 
+    # the plaintext linear map of weight slot `slot` (Engine.load_lwe_linear_weights) over K LWE0 (or LWE1) nodes: M nodes of the
+    # same kind, node m = sum over k of w[m][k] * nodes[k] (+ bias[m] on the body).  M=None asks the engine for the slot's shape;
+    # the slot may also be loaded, and loaded again, after the graph is built (run() checks it)
+    def add_lwe_linear(self, slot: int, nodes: Sequence[int], M=None) -> List[int]:
+        nodes = list(nodes)
+        if M is None:
+            M = self._eng.lwe_linear_slot_shape(slot)[0]
+        slot, M = _check_lwe_linear("add_lwe_linear", slot, len(nodes), M)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 1 << 32 for x in nodes):
+            raise SpfError(1, "add_lwe_linear: the operands must be node ids")
+        arr = (C.c_uint32 * len(nodes))(*[int(x) for x in nodes])
+        out = (C.c_uint32 * M)()
+        self._eng._ck(self._lib.spf_graph_add_lwe_linear(self._g, slot, arr, len(nodes), M, out))
+        return list(out)
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -231,13 +262,14 @@ class RecordedCircuit:
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / LWE_LINEAR_NODE, -1 input, -2 trivial constant
         self.kind: List[int] = []
         self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
         self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands; public functional keyswitch nodes: all lwe_count)
         self.host: List = []           # inputs: the caller's array
         self.outputs: List[int] = []   # nodes, in add_output order
         self._unpack_width: dict = {}  # unpack node -> n_bits of its add_unpack call
+        self._linear: dict = {}        # linear node -> (slot, M) of its add_lwe_linear call
 
     def _add(self, op, kind, param, inputs, host=None) -> int:
         self.op.append(int(op)); self.kind.append(int(kind)); self.param.append(int(param))
@@ -307,6 +339,20 @@ class RecordedCircuit:
             raise SpfError(1, "add_public_functional_keyswitch: lwe0 and lwe1 operands mixed")
         return self._add(NODE_PUFKS, ValueKind.GLWE1, len(nodes), nodes)
 
+    def add_lwe_linear(self, slot: int, nodes: Sequence[int], M: int) -> List[int]:
+        """M is required here: a recording is bound to no engine that could be asked for the slot's shape"""
+        nodes = list(nodes)
+        slot, M = _check_lwe_linear("add_lwe_linear", slot, len(nodes), M)
+        nodes = [_check_node("add_lwe_linear", x, len(self.op)) for x in nodes]
+        if any(self.kind[x] not in (int(ValueKind.LWE0), int(ValueKind.LWE1)) for x in nodes):
+            raise SpfError(1, "add_lwe_linear: an operand is not an LWE")
+        if any(self.kind[x] != self.kind[nodes[0]] for x in nodes):
+            raise SpfError(1, "add_lwe_linear: lwe0 and lwe1 operands mixed")
+        out = [self._add(LWE_LINEAR_NODE, self.kind[nodes[0]], m, nodes) for m in range(M)]
+        for n in out:
+            self._linear[n] = (slot, M)
+        return out
+
     def add_output(self, node: int, kind: ValueKind) -> int:
         if self.kind[node] != int(kind):
             raise SpfError(1, "output kind does not match the node")
@@ -323,6 +369,12 @@ class RecordedCircuit:
                 bits = g.add_unpack(self.inputs[i][0], n_bits)
                 assert bits == list(range(i, i + n_bits))
                 i += n_bits
+                continue
+            if self.op[i] == LWE_LINEAR_NODE:   # the row nodes of one add_lwe_linear call are consecutive
+                slot, M = self._linear[i]
+                rows = g.add_lwe_linear(slot, self.inputs[i], M)
+                assert rows == list(range(i, i + M))
+                i += M
                 continue
             if self.op[i] == NODE_PACK:
                 n = g.add_pack(self.inputs[i])
@@ -354,13 +406,25 @@ class RecordedCircuit:
         # a pack node's operands do not fit the three columns: they are ext[ext_at[i] : ext_at[i] + n_bits[i]] and its n_in is 0
         # (the executor's own layout, spf_graph.hpp); a public functional keyswitch node's lwe_count operands lie the same way.
         # n_bits is the integer's width on unpack and pack nodes, lwe_count on those, 0 elsewhere;
-        # an unpack node's param is its bit index.
+        # an unpack node's param is its bit index.  The M nodes of one add_lwe_linear call share ONE list of K operands
+        # (n_bits = K, the same ext_at, param = the row index m); their weight slot and M are lin_slot / lin_rows, 0 elsewhere.
         ins = np.zeros((n, 3), dtype=np.uint32)
         n_in = np.zeros(n, dtype=np.uint32)
         n_bits = np.zeros(n, dtype=np.uint32)
         ext_at = np.zeros(n, dtype=np.uint32)
+        lin_slot = np.zeros(n, dtype=np.uint32)
+        lin_rows = np.zeros(n, dtype=np.uint32)
         ext: List[int] = []
         for i, t in enumerate(self.inputs):
+            if self.op[i] == LWE_LINEAR_NODE:
+                lin_slot[i], lin_rows[i] = self._linear[i]
+                n_bits[i] = len(t)
+                if self.param[i] == 0:
+                    ext_at[i] = len(ext)
+                    ext.extend(t)
+                else:
+                    ext_at[i] = ext_at[i - 1]
+                continue
             if self.op[i] in (NODE_PACK, NODE_PUFKS):
                 n_bits[i], ext_at[i] = len(t), len(ext)
                 ext.extend(t)
@@ -373,7 +437,8 @@ class RecordedCircuit:
         keep[self.outputs] = 1
         return {"op": np.array([o if o >= 0 else -1 for o in self.op], dtype=np.int32), "in": ins, "n_in": n_in,
                 "param": np.array(self.param, dtype=np.uint64), "keep": keep,
-                "n_bits": n_bits, "ext_at": ext_at, "ext": np.array(ext, dtype=np.uint32)}
+                "n_bits": n_bits, "ext_at": ext_at, "ext": np.array(ext, dtype=np.uint32),
+                "lin_slot": lin_slot, "lin_rows": lin_rows}
 
     @classmethod
     def from_arrays(cls, a: dict, kind: Sequence[int], host: Sequence, polynomial_degree: int = 2048) -> "RecordedCircuit":
@@ -388,6 +453,11 @@ class RecordedCircuit:
                 w = int(a["n_bits"][i])
                 g.add_unpack(int(a["in"][i, 0]), w)
                 i += w
+                continue
+            if op == LWE_LINEAR_NODE:
+                at, rows = int(a["ext_at"][i]), int(a["lin_rows"][i])
+                g.add_lwe_linear(int(a["lin_slot"][i]), [int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]], rows)
+                i += rows
                 continue
             if op == NODE_PACK:
                 at = int(a["ext_at"][i])

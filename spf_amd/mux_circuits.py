@@ -459,6 +459,11 @@ class GraphBuilder:
     def add_public_functional_keyswitch(self, lwe_nodes) -> int:
         return self.graph.add_public_functional_keyswitch(lwe_nodes)
 
+    # the plaintext linear map of weight slot `slot` over K LWE nodes: M nodes (a RecordedCircuit records op 68 with the operand
+    # list, n_bits = K and param = m like the pack nodes, plus slot and M, and lowers it; it needs M, an FheCircuit may ask its engine)
+    def add_lwe_linear(self, slot: int, lwe_nodes, M=None) -> list:
+        return self.graph.add_lwe_linear(slot, lwe_nodes, M)
+
 
 def append_uint_multiply(builder, a: Sequence, b: Sequence, blocks: Callable[[int, int], MuxCircuit]) -> list:
     """`mul_impl` (parasol_runtime/src/circuits/mul.rs:90-200): recursive gradeschool multiplication of two unsigned
