@@ -200,6 +200,20 @@ class Evaluation {
     {
         check(spf_group_lwe_linear_batch(grp_, slot, kind, B, input_lwes, output_lwes));
     }
+    // plaintext polynomial linear maps over GLWE ciphertexts: `glwe_polynomial_mad`, `glwe_scalar_mad`, `sub_glwe_ciphertexts`,
+    // `glwe_negate_inplace` and `glwe_rotate` (sunscreen_tfhe ops/ciphertext/glwe_ciphertext_ops.rs:164-183, :189-202, :121-141,
+    // :147-156, :285-305) as one M x K matrix of sparse plaintext polynomials in CSR form (polynomial (m, k) = sum of
+    // coefficients[t] * X^exponents[t], t in [offsets[m K + k], offsets[m K + k + 1])) and an optional bias of M plaintext
+    // polynomials on the body, kept in slot `slot` < SPF_GLWE_POLY_SLOTS: B x K GLWEs -> B x M GLWEs, every word mod 2^64
+    void load_glwe_poly_weights(uint32_t slot, size_t M, size_t K, const uint32_t* offsets, const uint32_t* exponents,
+                                const int64_t* coefficients, const uint64_t* bias = nullptr)
+    {
+        check(spf_group_load_glwe_poly_weights(grp_, slot, M, K, offsets, exponents, coefficients, bias));
+    }
+    void glwe_poly_linear(uint64_t* output_glwes, const uint64_t* input_glwes, uint32_t slot, size_t B = 1)
+    {
+        check(spf_group_glwe_poly_linear_batch(grp_, slot, B, input_glwes, output_glwes));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

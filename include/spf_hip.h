@@ -492,6 +492,46 @@ spf_status spf_lwe_linear_enqueue(spf_ctx *ctx, void *stream, uint32_t slot, spf
                                   const uint64_t *d_lwe_in, uint64_t *d_lwe_out);
 const char *spf_last_lwe_linear_kernel(spf_ctx *ctx);
 
+/* ---- plaintext polynomial linear maps over GLWE ciphertexts ----------------------------------
+ * `glwe_polynomial_mad` (sunscreen_tfhe/src/ops/ciphertext/glwe_ciphertext_ops.rs:164-183, over `polynomial_external_mad`,
+ * math/polynomial.rs:114-197), `glwe_scalar_mad` (:189-202), `sub_glwe_ciphertexts` (:121-141), `glwe_negate_inplace` (:147-156)
+ * and `glwe_rotate` (:285-305) — and the keyless NOT, addition and multiplication by X^n above — as ONE operation, for any M x K
+ * matrix w of plaintext polynomials and an optional bias of M plaintext polynomials, in R = Z_2^64[X]/(X^N + 1):
+ *   out[b][m][p] = sum_k w[m][k] * in[b][k][p]   for p = 0 .. glwe_size (the mask polynomials, then the body), every word mod 2^64
+ *   out[b][m][glwe_size] += bias[m]
+ * in [B][K][(k+1)*N], out [B][M][(k+1)*N], all SPF_VAL_GLWE1 rows.  No floating point, no key, no tolerance: the words are the
+ * integers' words.  The matrix is given sparse, in CSR form over its M*K polynomials: polynomial (m, k) is the sum of
+ * coefficients[t] * X^exponents[t] over t in [offsets[m*K + k], offsets[m*K + k + 1]).  Duplicate exponents inside a polynomial are
+ * legal and add; a polynomial without terms is zero; any int64 coefficient is served, INT64_MIN included; exponents and
+ * coefficients may be null where the matrix has no term at all (the bias alone).  Weights live in the context like keys, in
+ * SPF_GLWE_POLY_SLOTS numbered slots; a load is synchronous, replaces the slot and must not race work that uses it (the rule of
+ * the key loads); spf_destroy frees the images.
+ *   SPF_ERR_NO_KEY: the slot is empty.  SPF_ERR_INVALID_ARGUMENT, with the offending numbers in the message: slot >=
+ *   SPF_GLWE_POLY_SLOTS, M or K = 0, M > SPF_GLWE_POLY_MAX_ROWS, M * K > 2^22, offsets that do not start at 0 or that decrease,
+ *   more than SPF_GLWE_POLY_MAX_TERMS terms (read from the last offset alone, before any other offset or any term is read), an
+ *   exponent >= N, a null pointer, an output range that overlaps the input range.
+ * spf_glwe_poly_linear_enqueue is the form on device pointers, under the contract of the `_dev` entry points above: it only
+ * enqueues on `stream`, one launch whatever B, and uses no buffer of the context.  "glwe_poly_linear" of spf_last_kernel_ms times
+ * it.  A slot whose every exponent is 0 (scalar weights: weighted sums, subtraction, negation, `glwe_rotate` through a constant
+ * bias) is served by "glwe_poly_stream_kernel", any other by "glwe_poly_lds_kernel"; spf_last_glwe_poly_kernel names the kernel
+ * of the last call (the environment variable SPF_GLWE_POLY_PATH=lds|stream, a diagnostic read at every call, forces the LDS kernel
+ * on a constants-only slot; `stream` on any other slot is ignored).  spf_glwe_poly_slot_shape: M, K, the number of terms and
+ * whether a bias is loaded.  The group forms: the load goes to every member, straight from the host pointers; B is dealt in
+ * contiguous shards. */
+typedef enum spf_glwe_poly_limits {
+    SPF_GLWE_POLY_SLOTS = 64,
+    SPF_GLWE_POLY_MAX_ROWS = 4096,
+    SPF_GLWE_POLY_MAX_TERMS = 16777216 /* 2^24 */
+} spf_glwe_poly_limits;
+spf_status spf_load_glwe_poly_weights(spf_ctx *ctx, uint32_t slot, size_t M, size_t K, const uint32_t *offsets /* [M*K+1] */,
+                                      const uint32_t *exponents /* [T] */, const int64_t *coefficients /* [T] */,
+                                      const uint64_t *bias /* [M][N] or NULL */);
+spf_status spf_glwe_poly_linear_batch(spf_ctx *ctx, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_glwe_poly_linear_enqueue(spf_ctx *ctx, void *stream, uint32_t slot, size_t B, const uint64_t *d_glwe_in,
+                                        uint64_t *d_glwe_out);
+spf_status spf_glwe_poly_slot_shape(spf_ctx *ctx, uint32_t slot, size_t *M, size_t *K, size_t *terms, int *has_bias);
+const char *spf_last_glwe_poly_kernel(spf_ctx *ctx);
+
 /* ---- call coalescing: many threads, one ciphertext each -> one batch per launch ----------
  * The reference calls `Evaluation` from many rayon workers with a single ciphertext per call
  * (circuit_processor/mod.rs:192-253).  A pool keeps that calling convention — submit, then wait like the synchronous call it
@@ -796,10 +836,10 @@ spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t w
  * "keyswitch" (digits + GEMM), "trace" (cbs_trace_kernel), "scheme_switch", "cmux" (contiguous
  * batched CMUX family), "pufks_prepass" (the transposing pre-pass of a public functional keyswitch at the hand-written radices,
  * with the gather in front of it where there is one), "lwe_linear_planes" and "lwe_linear" (the per-call byte planes and the product,
- * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only).  A host-pointer bootstrap of more than one chip round is launched in slices
+ * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only), "glwe_poly_linear" (the one launch of spf_glwe_poly_linear_enqueue).  A host-pointer bootstrap of more than one chip round is launched in slices
  * of 1024 ciphertexts: it records one "pbs" entry per slice.  Enable with spf_set_timing(ctx, 1). */
 spf_status spf_set_timing(spf_ctx *ctx, int enabled);
-spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" */,
+spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" | "glwe_poly_linear" */,
                               double *avg_ms, int *launches);
 /* `generate_lut` (sunscreen_tfhe ops/bootstrapping/programmable_bootstrapping.rs:129-185) for
  * `programmable_bootstrap_univariate`: map_tables[f * 2^bits + x] = f(x) for n_maps functions over a
@@ -1006,6 +1046,12 @@ spf_status spf_group_load_lwe_linear_weights(spf_group *grp, uint32_t slot, size
                                              const uint64_t *bias);
 spf_status spf_group_lwe_linear_batch(spf_group *grp, uint32_t slot, spf_value_kind kind, size_t B, const uint64_t *lwe_in,
                                       uint64_t *lwe_out);
+/* the plaintext polynomial linear maps over GLWE ciphertexts (`glwe_polynomial_mad` and its kin, ops/ciphertext/
+ * glwe_ciphertext_ops.rs:164-183; spf_load_glwe_poly_weights, spf_glwe_poly_linear_batch): the weights go to every member,
+ * straight from the host pointers; a batch is sharded by item (a member's K GLWEs are at * K onwards) */
+spf_status spf_group_load_glwe_poly_weights(spf_group *grp, uint32_t slot, size_t M, size_t K, const uint32_t *offsets,
+                                            const uint32_t *exponents, const int64_t *coefficients, const uint64_t *bias);
+spf_status spf_group_glwe_poly_linear_batch(spf_group *grp, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

@@ -34,6 +34,8 @@ class _CParams(C.Structure):
 # spf_value_kind of the LWE ciphertexts, and the number of weight slots of a context (include/spf_hip.h)
 VAL_LWE0, VAL_LWE1 = 0, 1
 LWE_LINEAR_SLOTS = 64
+# the limits of the plaintext polynomial weights over GLWE ciphertexts (spf_glwe_poly_limits)
+GLWE_POLY_SLOTS, GLWE_POLY_MAX_ROWS, GLWE_POLY_MAX_TERMS = 64, 4096, 1 << 24
 
 
 def lib_path() -> str:
@@ -104,6 +106,11 @@ SYMBOLS = [
     ("spf_lwe_linear_enqueue", _I, [_P, _P, _U32, _I, _SZ, _P, _P]),
     ("spf_last_lwe_linear_kernel", C.c_char_p, [_P]),
     ("spf_lwe_linear_slot_shape", _I, [_P, _U32, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)]),
+    ("spf_load_glwe_poly_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P, _P, _P]),
+    ("spf_glwe_poly_linear_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_poly_linear_enqueue", _I, [_P, _P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_poly_slot_shape", _I, [_P, _U32, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)]),
+    ("spf_last_glwe_poly_kernel", C.c_char_p, [_P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -215,6 +222,8 @@ SYMBOLS = [
     ("spf_group_circuit_bootstrap_via_pfks_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_load_lwe_linear_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P]),
     ("spf_group_lwe_linear_batch", _I, [_P, _U32, _I, _SZ, _P, _P]),
+    ("spf_group_load_glwe_poly_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P, _P, _P]),
+    ("spf_group_glwe_poly_linear_batch", _I, [_P, _U32, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -792,6 +801,69 @@ class Engine:
         self._ck(self._lib.spf_lwe_linear_batch(self._h, int(slot), int(kind), x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    def load_glwe_poly_weights(self, slot: int, w, bias=None, shape=None):
+        """weights of a plaintext polynomial linear map over GLWE ciphertexts (`glwe_polynomial_mad`, `glwe_scalar_mad`,
+        `sub_glwe_ciphertexts`, `glwe_negate_inplace`, `glwe_rotate`; sunscreen_tfhe ops/ciphertext/glwe_ciphertext_ops.rs:164-183,
+        :189-202, :121-141, :147-156, :285-305) into slot `slot` < GLWE_POLY_SLOTS.  `w` is a dense (M, K, N) array of int64
+        coefficients, of which the non-zeros are kept, or the CSR triple (offsets, exponents, coefficients) over the M * K
+        polynomials with `shape` = (M, K).  `bias`: M plaintext polynomials, (M, N) uint64 words, added to the body.
+        Replaces what the slot held; synchronous."""
+        N = self.params.polynomial_degree
+        if isinstance(w, tuple):
+            if len(w) != 3 or shape is None or len(shape) != 2:
+                raise SpfError(-2, "load_glwe_poly_weights: the sparse form is (offsets, exponents, coefficients) with shape=(M, K)")
+            M, K = int(shape[0]), int(shape[1])
+            off, exp = (np.asarray(a) for a in w[:2])
+            coef = np.asarray(w[2])
+            for name, a in (("offsets", off), ("exponents", exp)):
+                if a.ndim != 1 or (a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) >= 2**32)):
+                    raise SpfError(-2, f"load_glwe_poly_weights: the {name} are a 1-D array of uint32 values")
+            if coef.ndim != 1 or (coef.size and coef.dtype.kind not in "iu") or (coef.dtype.kind == "u" and coef.size and int(coef.max()) > 2**63 - 1):
+                raise SpfError(-2, "load_glwe_poly_weights: the coefficients are a 1-D array of int64 values")
+            if M < 0 or K < 0 or off.size != M * K + 1 or exp.size != coef.size or (off.size and int(off[-1]) > exp.size):
+                raise SpfError(-2, f"load_glwe_poly_weights: {off.size} offsets, {exp.size} exponents and {coef.size} coefficients "
+                                   f"do not describe {M} x {K} polynomials")
+            off, exp = np.ascontiguousarray(off, dtype=np.uint32), np.ascontiguousarray(exp, dtype=np.uint32)
+            coef = np.ascontiguousarray(coef, dtype=np.int64)
+        else:
+            d = np.asarray(w)
+            if d.ndim != 3 or d.shape[2] != N or d.dtype.kind not in "iu" or (d.dtype.kind == "u" and d.size and int(d.max()) > 2**63 - 1):
+                raise SpfError(-2, f"load_glwe_poly_weights: the dense form is an (M, K, {N}) array of int64 values, got {d.dtype} {d.shape}")
+            d = np.ascontiguousarray(d, dtype=np.int64)
+            M, K = d.shape[:2]
+            nz = d != 0
+            off = np.concatenate([[0], np.cumsum(nz.reshape(M * K, N).sum(axis=1))]).astype(np.uint32)
+            exp = np.nonzero(nz)[2].astype(np.uint32)
+            coef = np.ascontiguousarray(d[nz])
+        b = None
+        if bias is not None:
+            b = _u64(bias)
+            if b.shape != (M, N):
+                raise SpfError(-2, f"load_glwe_poly_weights: the bias has shape {b.shape}, expected ({M}, {N})")
+        keep = np.zeros(1, dtype=np.uint64)   # (an empty array has no address worth passing)
+        self._ck(self._lib.spf_load_glwe_poly_weights(self._h, int(slot) & 0xFFFFFFFF, M, K, _ptr(off), _ptr(exp if exp.size else keep),
+                                                      _ptr(coef if coef.size else keep), _ptr(b) if b is not None else None))
+
+    def glwe_poly_slot_shape(self, slot: int):
+        """`spf_glwe_poly_slot_shape`: (M, K, terms, has_bias) of the weights in `slot`; an empty slot is SPF_ERR_NO_KEY"""
+        M, K, T, has_bias = _SZ(), _SZ(), _SZ(), C.c_int()
+        self._ck(self._lib.spf_glwe_poly_slot_shape(self._h, int(slot) & 0xFFFFFFFF, C.byref(M), C.byref(K), C.byref(T), C.byref(has_bias)))
+        return int(M.value), int(K.value), int(T.value), bool(has_bias.value)
+
+    def glwe_poly_linear(self, slot: int, glwes) -> np.ndarray:
+        """out[b][m] = sum_k w[m][k] * glwes[b][k] (+ bias[m] on the body) in Z_2^64[X]/(X^N + 1), word for word: (B, K, k+1, N)
+        GLWEs -> (B, M, k+1, N), under the polynomial weights of slot `slot`"""
+        M, K = self.glwe_poly_slot_shape(slot)[:2]
+        k1, N = self.params.glwe_size + 1, self.params.polynomial_degree
+        x = _u64(glwes)
+        if x.ndim == 3 and x.shape[1:] == (K, k1 * N):
+            x = x.reshape(-1, K, k1, N)
+        if x.ndim != 4 or x.shape[1:] != (K, k1, N):
+            raise SpfError(-2, f"glwe_poly_linear: operand must have shape (B, {K}, {k1}, {N}), got {x.shape}")
+        out = np.empty((x.shape[0], M, k1, N), dtype=np.uint64)
+        self._ck(self._lib.spf_glwe_poly_linear_batch(self._h, int(slot), x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -916,6 +988,12 @@ class Engine:
     def last_lwe_linear_kernel(self) -> str:
         return (self._lib.spf_last_lwe_linear_kernel(self._h) or b"").decode()
 
+    def glwe_poly_linear_enqueue(self, stream, slot, B, d_glwe_in, d_glwe_out):
+        self._ck(self._lib.spf_glwe_poly_linear_enqueue(self._h, stream, int(slot), B, d_glwe_in, d_glwe_out))
+
+    def last_glwe_poly_kernel(self) -> str:
+        return (self._lib.spf_last_glwe_poly_kernel(self._h) or b"").decode()
+
     def last_public_functional_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()
 
@@ -1020,6 +1098,13 @@ class Group(Engine):
     def lwe_linear_slot_shape(self, slot: int):
         """of member 0: `spf_group_load_lwe_linear_weights` loads every member alike"""
         return self.member(0).lwe_linear_slot_shape(slot)
+
+    def glwe_poly_slot_shape(self, slot: int):
+        """of member 0: `spf_group_load_glwe_poly_weights` loads every member alike"""
+        return self.member(0).glwe_poly_slot_shape(slot)
+
+    def last_glwe_poly_kernel(self) -> str:
+        return self.member(0).last_glwe_poly_kernel()
 
     def run_graphs(self, graphs):
         """`spf_group_run_graphs`: graphs are `spf_amd.FheCircuit`s made over this group; dealt to the members by cost,

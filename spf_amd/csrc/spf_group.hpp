@@ -847,6 +847,29 @@ spf_status spf_group_lwe_linear_batch(spf_group* g, uint32_t slot, spf_value_kin
     return group_batch(g, sh, B, {in}, out, [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_lwe_linear_batch(c, slot, kind, n, in, out); });
 }
 
+// plaintext polynomial weights: every member, straight from the host pointers
+spf_status spf_group_load_glwe_poly_weights(spf_group* g, uint32_t slot, size_t M, size_t K, const uint32_t* offsets, const uint32_t* exponents,
+                                            const int64_t* coefficients, const uint64_t* bias)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    std::lock_guard<std::mutex> lk(g->key_mu);
+    for (size_t i = 0; i < g->m.size(); i++) {
+        spf_status s = spf_load_glwe_poly_weights(g->m[i]->ctx, slot, M, K, offsets, exponents, coefficients, bias);
+        if (s != SPF_OK) return gfail(g, s, "member " + std::to_string(i) + ": " + spf_last_error(g->m[i]->ctx));
+    }
+    return SPF_OK;
+}
+
+// polynomial linear maps: sharded by item, an item's K GLWEs go with it (the overlap is checked on the whole batch)
+spf_status spf_group_glwe_poly_linear_batch(spf_group* g, uint32_t slot, size_t B, const uint64_t* in, uint64_t* out)
+{
+    if (spf_status s = group_args(g, false)) return s;
+    BatchShape sh;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = glwe_poly_args(c0, slot, B, in, out, &sh)) return gfail(g, s, spf_last_error(c0));
+    return group_batch(g, sh, B, {in}, out, [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_glwe_poly_linear_batch(c, slot, n, in, out); });
+}
+
 // circuit bootstrap via PFKS: sharded by item
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {

@@ -12,6 +12,7 @@
 #include "spf_pufks.hpp"
 #include "spf_pfks.hpp"
 #include "spf_lwe_linear.hpp"
+#include "spf_glwe_poly.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -64,9 +65,9 @@ struct Scratch {
 };
 
 // kernels whose launches spf_set_timing brackets with hipEvents on the launch stream (spf_last_kernel_ms)
-enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_COUNT };
+enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_GLWE_POLY, T_COUNT };
 const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass", "lwe_linear_planes",
-                                          "lwe_linear"};
+                                          "lwe_linear", "glwe_poly_linear"};
 
 // one slot of plaintext weights for spf_lwe_linear_* (spf_lwe_linear.hpp): the int64 matrix as loaded, always; the int8 limbs of
 // -w and their sums where the matrix-core path takes the matrix (U > 0)
@@ -78,6 +79,17 @@ struct LweLinearSlot {
     uint64_t* d_bias = nullptr; // [M], or null
     int8_t* d_A = nullptr;    // [U][Mpad][Kpad]
     int* d_rs = nullptr;      // [nseg][U][Mpad]
+};
+
+// one slot of plaintext polynomial weights for spf_glwe_poly_linear_* (spf_glwe_poly.hpp): the image spf_glwe_poly::pack makes
+struct GlwePolySlot {
+    bool ready = false;
+    bool constants_only = false;
+    size_t M = 0, K = 0, terms = 0;
+    uint32_t* d_offsets = nullptr;           // [M K + 1]
+    spf_glwe_poly::Term* d_terms = nullptr;  // [terms], or null where there are none
+    uint64_t* d_scalars = nullptr;           // [M][K], constants-only slots
+    uint64_t* d_bias = nullptr;              // [M][N], or null
 };
 
 } // namespace
@@ -169,6 +181,9 @@ struct spf_ctx {
     const char* last_lin_kernel = "";
     uint64_t lin_epoch = 0;         // bumped by every spf_load_lwe_linear_weights (captured gate graphs hold a slot's pointers)
     uint32_t last_lin_launches = 0; // kernel launches the last spf_lwe_linear_enqueue made (spf_graph_stats)
+    // plaintext polynomial linear maps over GLWE ciphertexts (spf_glwe_poly.hpp): the weight slots
+    GlwePolySlot gpoly[SPF_GLWE_POLY_SLOTS];
+    const char* last_gpoly_kernel = "";
 };
 
 namespace {
@@ -833,6 +848,9 @@ static void ctx_release(spf_ctx* c)
         if (p) (void)hipFree(p);
     for (LweLinearSlot& l : c->lin)
         for (void* p : {(void*)l.d_w, (void*)l.d_bias, (void*)l.d_A, (void*)l.d_rs})
+            if (p) (void)hipFree(p);
+    for (GlwePolySlot& l : c->gpoly)
+        for (void* p : {(void*)l.d_offsets, (void*)l.d_terms, (void*)l.d_scalars, (void*)l.d_bias})
             if (p) (void)hipFree(p);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
@@ -2219,7 +2237,7 @@ spf_status spf_last_kernel_ms(spf_ctx* c, const char* kernel, double* avg_ms, in
     std::vector<TimedLaunch>* v = nullptr;
     for (int k = 0; k < T_COUNT; k++)
         if (!strcmp(kernel, kTimedNames[k])) v = &c->timed[k];
-    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\" or \"lwe_linear\"");
+    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\", \"lwe_linear\" or \"glwe_poly_linear\"");
     double total = 0.0;
     int n = 0;
     for (auto& t : *v) {
@@ -3121,6 +3139,134 @@ const char* spf_last_lwe_linear_kernel(spf_ctx* c)
     if (!c) return "";
     std::lock_guard<std::recursive_mutex> g(c->mu);
     return c->last_lin_kernel;
+}
+
+// ---------------------------------------------------------------- plaintext polynomial linear maps over GLWE ciphertexts
+// `glwe_polynomial_mad`, `glwe_scalar_mad`, `sub_glwe_ciphertexts`, `glwe_negate_inplace`, `glwe_rotate`
+// (sunscreen_tfhe/src/ops/ciphertext/glwe_ciphertext_ops.rs:164-183, :189-202, :121-141, :147-156, :285-305) for a matrix of sparse
+// plaintext polynomials; checks and image: spf_glwe_poly_plan.hpp, kernels and arithmetic: spf_glwe_poly.hpp.
+
+static void glwe_poly_drop(GlwePolySlot& l)
+{
+    for (void* p : {(void*)l.d_offsets, (void*)l.d_terms, (void*)l.d_scalars, (void*)l.d_bias})
+        if (p) (void)hipFree(p);
+    l = GlwePolySlot{};
+}
+
+// Synchronous, like a key load: the slot is empty from the first device call on until the end, and after any failure there.
+spf_status spf_load_glwe_poly_weights(spf_ctx* c, uint32_t slot, size_t M, size_t K, const uint32_t* offsets, const uint32_t* exponents,
+                                      const int64_t* coefficients, const uint64_t* bias)
+{
+    if (!c) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null context");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const size_t N = c->prm.polynomial_degree;
+    const spf_glwe_poly::Verdict v = spf_glwe_poly::validate(slot, M, K, N, offsets, exponents, coefficients);
+    if (v.status != SPF_OK) return fail(c, v.status, v.message);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    GlwePolySlot& l = c->gpoly[slot];
+    glwe_poly_drop(l);
+    const spf_glwe_poly::Image im = spf_glwe_poly::pack(M, K, offsets, exponents, coefficients);
+    GlwePolySlot n;
+    n.M = M; n.K = K; n.terms = im.terms.size();
+    n.constants_only = im.cls == spf_glwe_poly::kConstantsOnly;
+    auto upload = [&](auto** dst, const void* src, size_t bytes) -> spf_status {
+        if (!bytes) return SPF_OK;
+        HIPCHK(c, hipMalloc((void**)dst, bytes));
+        HIPCHK(c, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+        return SPF_OK;
+    };
+    spf_status st = upload(&n.d_offsets, im.offsets.data(), im.offsets.size() * sizeof(uint32_t));
+    if (st == SPF_OK) st = upload(&n.d_terms, im.terms.data(), im.terms.size() * sizeof(spf_glwe_poly::Term));
+    if (st == SPF_OK) st = upload(&n.d_scalars, im.scalars.data(), im.scalars.size() * 8);
+    if (st == SPF_OK && bias) st = upload(&n.d_bias, bias, M * N * 8);
+    if (st != SPF_OK) {
+        glwe_poly_drop(n);
+        return st;
+    }
+    n.ready = true;
+    l = n;
+    return SPF_OK;
+}
+
+// What every form checks before the batch is touched, on `c` with its texts: the pointers (never null, whatever B), the slot, the
+// weights, the batch limit; *sh: the batch shape for the slot's M and K.
+static spf_status glwe_poly_args(spf_ctx* c, uint32_t slot, size_t B, const void* in, const void* out, BatchShape* sh)
+{
+    if (!c || !in || !out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (slot >= SPF_GLWE_POLY_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_GLWE_POLY_SLOTS = " + std::to_string(SPF_GLWE_POLY_SLOTS));
+    if (!c->gpoly[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no polynomial weights loaded in slot " + std::to_string(slot));
+    *sh = glwe_poly_batch_shape(c->prm, c->gpoly[slot].M, c->gpoly[slot].K);
+    if (batch_limit(c, *sh, B) != SPF_OK) return SPF_ERR_INVALID_ARGUMENT;
+    if (batch_overlaps(*sh, B, out, in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the input");
+    return SPF_OK;
+}
+
+// Which kernel serves a constants-only slot: SPF_GLWE_POLY_PATH=lds | stream (diagnostic; read at every call).  A general slot
+// has the LDS kernel only.
+static int glwe_poly_forced_path()
+{
+    const char* e = getenv("SPF_GLWE_POLY_PATH");
+    return !e ? 0 : !strcmp(e, "lds") ? 1 : !strcmp(e, "stream") ? 2 : 0;
+}
+
+// ONE launch whatever B and M: the items ride grid.x (B <= 2^28 by the batch shape), M <= SPF_GLWE_POLY_MAX_ROWS keeps grid.y in
+// range, and grid.z is the polynomials of a GLWE or its words in groups of 256.
+spf_status spf_glwe_poly_linear_enqueue(spf_ctx* c, void* stream, uint32_t slot, size_t B, const uint64_t* d_glwe_in, uint64_t* d_glwe_out)
+{
+    BatchShape sh;
+    spf_status st = glwe_poly_args(c, slot, B, d_glwe_in, d_glwe_out, &sh);
+    if (st != SPF_OK || B == 0) return st;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const GlwePolySlot& l = c->gpoly[slot];
+    const uint32_t N = c->prm.polynomial_degree, k1 = c->prm.glwe_size + 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    // the default for a constants-only slot: the stream kernel (profiles/r28_glwe_poly_linear.md)
+    const bool stream_kernel = l.constants_only && glwe_poly_forced_path() != 1;
+    c->last_gpoly_kernel = stream_kernel ? "glwe_poly_stream_kernel" : "glwe_poly_lds_kernel";
+    TimedScope ts(c, s, T_GLWE_POLY);
+    st = ts.begin();
+    if (st != SPF_OK) return st;
+    GlwePolyArgs a{d_glwe_in, l.d_offsets, l.d_terms, l.d_scalars, l.d_bias, d_glwe_out, (uint32_t)l.M, (uint32_t)l.K, N, k1 - 1};
+    const unsigned tiles = (unsigned)((l.M + GLWE_POLY_VT - 1) / GLWE_POLY_VT);
+    if (stream_kernel) hipLaunchKernelGGL(glwe_poly_stream_kernel, dim3((unsigned)B, tiles, (k1 * N + 255) / 256), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(glwe_poly_lds_kernel, dim3((unsigned)B, tiles, k1), dim3(256), 0, s, a);
+    HIPCHK(c, hipGetLastError());
+    return ts.end();
+}
+
+spf_status spf_glwe_poly_linear_batch(spf_ctx* c, uint32_t slot, size_t B, const uint64_t* glwe_in, uint64_t* glwe_out)
+{
+    BatchShape sh;
+    spf_status st = glwe_poly_args(c, slot, B, glwe_in, glwe_out, &sh);
+    if (st != SPF_OK) return st;
+    return host_batch(c, sh, B, {{c->in, glwe_in}}, glwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
+        return spf_glwe_poly_linear_enqueue(c, c->stream, slot, B, d_in, d_out);
+    });
+}
+
+spf_status spf_glwe_poly_slot_shape(spf_ctx* c, uint32_t slot, size_t* M, size_t* K, size_t* terms, int* has_bias)
+{
+    if (!c || !M || !K || !terms || !has_bias) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (slot >= SPF_GLWE_POLY_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_GLWE_POLY_SLOTS = " + std::to_string(SPF_GLWE_POLY_SLOTS));
+    if (!c->gpoly[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no polynomial weights loaded in slot " + std::to_string(slot));
+    *M = c->gpoly[slot].M;
+    *K = c->gpoly[slot].K;
+    *terms = c->gpoly[slot].terms;
+    *has_bias = c->gpoly[slot].d_bias != nullptr;
+    return SPF_OK;
+}
+
+const char* spf_last_glwe_poly_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_gpoly_kernel;
 }
 
 const char* spf_last_blind_rotate_kernel(spf_ctx* c)

@@ -102,6 +102,11 @@ inline BatchShape lwe_linear_batch_shape(const spf_params& p, size_t M, size_t K
 {
     return {1, {K * value_words(p, kind), 0, 0}, M * value_words(p, kind), kBatchMaxRows / (M > K ? M : K ? K : 1)};
 }
+// plaintext polynomial linear maps: K GLWEs into M
+inline BatchShape glwe_poly_batch_shape(const spf_params& p, size_t M, size_t K)
+{
+    return {1, {K * glwe_words(p), 0, 0}, M * glwe_words(p), kBatchMaxRows / (M > K ? M : K ? K : 1)};
+}
 
 // ---------------------------------------------------------------- the operation table
 namespace spf_ops {

@@ -110,6 +110,14 @@ class Evaluation:
     def lwe_linear(self, output: np.ndarray, input: np.ndarray, slot: int, kind: int = 0):
         self._store(output, self.engine.lwe_linear(slot, input, kind))
 
+    # `glwe_polynomial_mad`, `glwe_scalar_mad`, `sub_glwe_ciphertexts`, `glwe_negate_inplace`, `glwe_rotate`
+    # (ops/ciphertext/glwe_ciphertext_ops.rs:164-183, :189-202, :121-141, :147-156, :285-305) as one plaintext polynomial matrix
+    def load_glwe_poly_weights(self, slot: int, w, bias=None, shape=None):
+        self.engine.load_glwe_poly_weights(slot, w, bias, shape)
+
+    def glwe_poly_linear(self, output: np.ndarray, input: np.ndarray, slot: int):
+        self._store(output, self.engine.glwe_poly_linear(slot, input))
+
     # generalized_programmable_bootstrap (programmable_bootstrapping.rs:342-410)
     def generalized_programmable_bootstrap(self, output, input, lut, log_chi: int, log_v: int):
         self._store(output, self.engine.generalized_pbs(input, lut, log_chi, log_v, 0))
