@@ -65,10 +65,9 @@ NODE_UNPACK = 64
 NODE_PACK = 65
 NODE_ROT_CMUX = 66
 NODE_PUFKS = 67
-# spf_graph_add_lwe_linear: one node per output row m, inputs = all K operands (one list shared by the M nodes of a call), param = m.
-# Not a NODE_* name yet: the random graph generator of the differential tests draws every NODE_* of this module, and it cannot draw
-# weights.  This becomes NODE_LWE_LINEAR in the change that teaches the generator to draw them.
-LWE_LINEAR_NODE = 68
+# spf_graph_add_lwe_linear: one node per output row m, inputs = all K operands (one list shared by the M nodes of a call), param = m
+NODE_LWE_LINEAR = 68
+LWE_LINEAR_NODE = NODE_LWE_LINEAR  # its name in the revision before: that revision's test modules import it and must still load
 LWE_LINEAR_SLOTS = 64            # SPF_LWE_LINEAR_SLOTS
 LWE_LINEAR_GRAPH_MAX_ROWS = 4096  # SPF_GRAPH_LWE_LINEAR_MAX_ROWS
 
@@ -262,7 +261,7 @@ class RecordedCircuit:
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / LWE_LINEAR_NODE, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / NODE_LWE_LINEAR, -1 input, -2 trivial constant
         self.kind: List[int] = []
         self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
         self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands; public functional keyswitch nodes: all lwe_count)
@@ -348,10 +347,14 @@ class RecordedCircuit:
             raise SpfError(1, "add_lwe_linear: an operand is not an LWE")
         if any(self.kind[x] != self.kind[nodes[0]] for x in nodes):
             raise SpfError(1, "add_lwe_linear: lwe0 and lwe1 operands mixed")
-        out = [self._add(LWE_LINEAR_NODE, self.kind[nodes[0]], m, nodes) for m in range(M)]
+        out = [self._add(NODE_LWE_LINEAR, self.kind[nodes[0]], m, nodes) for m in range(M)]
         for n in out:
             self._linear[n] = (slot, M)
         return out
+
+    def linear_of(self, node: int) -> tuple:
+        """(slot, M) of the add_lwe_linear call that made this linear node (its row index is `param[node]`)"""
+        return self._linear[node]
 
     def add_output(self, node: int, kind: ValueKind) -> int:
         if self.kind[node] != int(kind):
@@ -370,7 +373,7 @@ class RecordedCircuit:
                 assert bits == list(range(i, i + n_bits))
                 i += n_bits
                 continue
-            if self.op[i] == LWE_LINEAR_NODE:   # the row nodes of one add_lwe_linear call are consecutive
+            if self.op[i] == NODE_LWE_LINEAR:   # the row nodes of one add_lwe_linear call are consecutive
                 slot, M = self._linear[i]
                 rows = g.add_lwe_linear(slot, self.inputs[i], M)
                 assert rows == list(range(i, i + M))
@@ -416,7 +419,7 @@ class RecordedCircuit:
         lin_rows = np.zeros(n, dtype=np.uint32)
         ext: List[int] = []
         for i, t in enumerate(self.inputs):
-            if self.op[i] == LWE_LINEAR_NODE:
+            if self.op[i] == NODE_LWE_LINEAR:
                 lin_slot[i], lin_rows[i] = self._linear[i]
                 n_bits[i] = len(t)
                 if self.param[i] == 0:
@@ -454,7 +457,7 @@ class RecordedCircuit:
                 g.add_unpack(int(a["in"][i, 0]), w)
                 i += w
                 continue
-            if op == LWE_LINEAR_NODE:
+            if op == NODE_LWE_LINEAR:
                 at, rows = int(a["ext_at"][i]), int(a["lin_rows"][i])
                 g.add_lwe_linear(int(a["lin_slot"][i]), [int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]], rows)
                 i += rows

@@ -9,21 +9,24 @@ import numpy as np
 
 import oracle as O
 from spf_amd import FheOp, TableOp, ValueKind
-from spf_amd.graph import NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from spf_amd.graph import NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from tests import lwe_linear_cases as LC
 from tests import pbs_graph_cases as K
 from tests import pufks_cases as PC
 from tests.polyref_cases import key_fft
 
-# ks: oracle KeySet; ak / ssk: automorphism and scheme-switch keys; pufks: None or (key as loaded (n, count, k+1, N), log, count)
-Keys = namedtuple("Keys", "ks ak ssk pufks", defaults=(None,))
+# ks: oracle KeySet; ak / ssk: automorphism and scheme-switch keys; pufks: None or (key as loaded (n, count, k+1, N), log, count);
+# linear: None or the weight slots as loaded, {slot: (weights int64 (M, K), bias uint64 (M,) or None)}
+Keys = namedtuple("Keys", "ks ak ssk pufks linear", defaults=(None, None))
 
 _BOOTSTRAPS = (int(FheOp.CircuitBootstrap), int(TableOp.PBS_UNIVARIATE), int(TableOp.PBS_BIVARIATE))
 
 
-def keys_of(which, pufks=None) -> Keys:
-    """the keys of a context of pbs_graph_cases.CONTEXTS, with the public-functional-keyswitch key if one is loaded"""
+def keys_of(which, pufks=None, linear=None) -> Keys:
+    """the keys of a context of pbs_graph_cases.CONTEXTS, with the public-functional-keyswitch key and the weight slots of the
+    linear maps if they are loaded"""
     _, ks, ak, ssk = K.keys_of(which)
-    return Keys(ks, ak, ssk, pufks)
+    return Keys(ks, ak, ssk, pufks, linear)
 
 
 def kind_name(rec, i) -> str:
@@ -32,7 +35,8 @@ def kind_name(rec, i) -> str:
         return f"Input{ValueKind(rec.kind[i]).name}"
     if op == -2:
         return f"Trivial{ValueKind(rec.kind[i]).name}({rec.param[i]})"
-    names = {NODE_UNPACK: "Unpack", NODE_PACK: "Pack", NODE_ROT_CMUX: "RotCMux", NODE_PUFKS: "PublicFunctionalKeyswitch"}
+    names = {NODE_UNPACK: "Unpack", NODE_PACK: "Pack", NODE_ROT_CMUX: "RotCMux", NODE_PUFKS: "PublicFunctionalKeyswitch",
+             NODE_LWE_LINEAR: "LweLinear"}
     return names[op] if op in names else (TableOp(op).name if op in TableOp._value2member_map_ else FheOp(op).name)
 
 
@@ -122,6 +126,11 @@ def evaluate(rec, P, keys: Keys, hosts=None):
             key, log, count = keys.pufks
             assert key.shape[0] == x[0].size - 1, "the key's dimension is not the operands'"
             v = PC.pufks_oracle(np.stack(x), pufks_fft, N, k, log, count).reshape(-1)
+        elif op == NODE_LWE_LINEAR:     # row par of the layer: the M nodes of one call share the operand list and the slot
+            slot, rows = rec.linear_of(i)
+            w, bias = keys.linear[slot]
+            assert np.shape(w) == (rows, len(x)), f"node {i}: slot {slot} holds {np.shape(w)} weights, the layer is {(rows, len(x))}"
+            v = LC.linear_ref(np.stack(x), w, bias)[par]
         else:
             raise ValueError(f"node {i}: unknown operation {op}")
         vals.append(np.asarray(v).reshape(-1))

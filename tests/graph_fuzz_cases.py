@@ -2,7 +2,9 @@
 `draw_circuit(seed, P, profile) -> (RecordedCircuit, facts)`, deterministic in its arguments, numpy only.
 
 A circuit is a typed DAG over the five value kinds with every node kind of the executor in it: every operation of the table
-(spf_ops.hpp) that has a `spf_graph_op` and the four constructors (unpack, pack, blind rotation, public functional keyswitch).
+(spf_ops.hpp) that has a `spf_graph_op` and the five constructors (unpack, pack, blind rotation, public functional keyswitch,
+plaintext linear map).  The weights of the linear maps are no part of a circuit: `draw_linear_slots(linear_seed)` draws them for a
+fixed table of slot shapes, so that one engine (or one group) loads them once for every circuit it runs.
 The generator BUILDS the layouts in which the executor's plan takes another branch (PATTERNS below) and, for each, records the
 claim that makes it one: which nodes have to share a group, lie in consecutive rows, or stand on different levels.  The claims
 are checked against `circuit_model.planned_levels`, the executor's own level passes, so `facts` names a pattern only if the
@@ -10,15 +12,16 @@ circuit really holds it once the planner has moved the bootstraps and the conver
 import numpy as np
 
 from spf_amd import FheOp, RecordedCircuit, TableOp, ValueKind
-from spf_amd.graph import NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from spf_amd.graph import NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
 from tests.blind_rotation_graph_cases import random_selectors
 from tests.circuit_model import kind_name, planned_levels
+from tests.lwe_linear_cases import class_weights
 
 PROFILES = ("full", "pushable", "small")
 CMUX_WIDTHS = (1, 2, 3, 5, 40, 70, 260, 300)           # test_gpu_fuzz.py's list: both CMUX kernels of the tuned context
 _WIDTH_SETS = ((260, 2, 5), (40, 70, 3), (300, 1))      # by seed % 3: three consecutive seeds draw every width
-MAX_NODES = 450                                         # "about 400": the 300-wide level and every pattern in one circuit
-MAX_NODES_SMALL = 60
+MAX_NODES = 620                                         # "about 400" and the ~165 nodes of LINEAR_PATTERNS (rows are nodes)
+MAX_NODES_SMALL = 66                                    # ... and a 9-row and a 2-row layer with their user
 MAX_BOOTSTRAPS = 16                                     # of each of the three kinds
 
 DEFAULT_CASES, DEFAULT_SEED = 3, 20260701               # of tests/test_gpu_graph_fuzz.py (SPF_FUZZ_CASES / SPF_FUZZ_SEED)
@@ -60,6 +63,44 @@ PATTERNS = tuple(f"cmux_width_{w}" for w in CMUX_WIDTHS) + (
     "output_of_every_kind", "output_given_twice", "outputs_every_node_of_the_last_level",
     "trivial_of_every_kind_both_bits") + PUFKS_PATTERNS
 
+# the layouts of the plaintext linear map (spf_graph_add_lwe_linear).  "in place": ALL operand rows of the layer's group are
+# successive members of one group, in the group's layer-major order; "scattered": the claim rests on a repeated operand or on a
+# pair of neighbours that lie in descending order in the arena, which no arena layout makes consecutive (`_View.scattered`)
+LINEAR_PATTERNS = (
+    "linear_in_place_over_a_keyswitch_group", "linear_in_place_over_a_univariate_group", "linear_in_place_over_unpack_bits",
+    "linear_in_place_over_a_previous_layer", "linear_two_layers_in_place",
+    "linear_scattered_previous_layer_permuted", "linear_scattered_operand_repeated", "linear_scattered_three_levels_inputs_and_constants",
+    "linear_two_layers_one_consecutive_one_scattered", "linear_two_layers_over_one_operand_list",
+    "linear_two_slots_of_one_shape_on_one_level", "linear_both_operand_kinds_on_one_level_with_one_slot", "linear_shape_1_1",
+    "linear_pulls_a_keyswitch_up", "linear_pulls_a_sample_extract_up", "linear_follows_a_moved_table_bootstrap",
+    "linear_row_into_a_circuit_bootstrap", "linear_row_into_a_univariate_bootstrap", "linear_rows_into_a_bivariate_consecutive",
+    "linear_row_into_a_bivariate_scattered", "linear_rows_into_a_keyswitch", "linear_rows_into_a_functional_keyswitch_in_order",
+    "linear_rows_into_a_functional_keyswitch_with_a_repeat", "linear_row_is_an_output_and_has_users", "linear_layer_partly_used",
+    "linear_last_group_in_place_with_one_limb_weights")
+PATTERNS += LINEAR_PATTERNS
+
+# ---- the weight slots: (slot, M, K, class of lwe_linear_cases.class_weights, bias).  M below, at and above LWE_LINEAR_VT = 8
+# (1, 2 .. 5, 8, 9, 17), K = 1 and off and on the unroll factor 4; slots 0 and 1 have one shape; every class; bias and none; the
+# slot ids run to the last one (SPF_LWE_LINEAR_SLOTS - 1)
+S_A, S_B, S_WIDE, S_PERM, S_REPEAT, S_MIXED, S_PAIR, S_ONE, S_SMALL, S_BITS, S_LAST, S_TWICE = 0, 1, 2, 3, 7, 12, 21, 33, 40, 47, 62, 63
+LINEAR_SLOTS = (
+    (S_A, 8, 4, 2, True), (S_B, 8, 4, "beyond", False), (S_WIDE, 17, 3, 2, True), (S_PERM, 3, 8, "int64", True),
+    (S_REPEAT, 9, 5, 3, False), (S_MIXED, 1, 7, "beyond", True), (S_PAIR, 3, 2, "int64", False), (S_ONE, 1, 1, 1, True),
+    (S_SMALL, 2, 9, 2, False), (S_BITS, 5, 3, 3, False), (S_LAST, 9, 5, 1, True), (S_TWICE, 2, 2, 1, False))
+LINEAR_SHAPE = {slot: (M, K) for slot, M, K, _, _ in LINEAR_SLOTS}
+LINEAR_CLASS = {slot: cls for slot, _, _, cls, _ in LINEAR_SLOTS}
+
+
+def draw_linear_slots(linear_seed) -> dict:
+    """{slot: (weights int64 (M, K), bias uint64 (M,) or None)} for the table LINEAR_SLOTS: the shapes, the classes and which slots
+    have a bias are fixed, the contents are drawn from `linear_seed`"""
+    out = {}
+    for slot, M, K, cls, bias in LINEAR_SLOTS:
+        w = class_weights(64 * int(linear_seed) + slot, M, K, cls)
+        b = np.random.default_rng([0x6A7, int(linear_seed), slot]).integers(0, 1 << 64, M, dtype=np.uint64) if bias else None
+        out[slot] = (w, b)
+    return out
+
 
 def words_of(P, kind) -> int:
     return {L0: P.lwe_n + 1, L1: P.k * P.N + 1, GL: P.glwe_len, GG: 2 * P.cbs_ggsw_fft_len, GV: P.cbs_count * P.glwe_len}[ValueKind(kind)]
@@ -90,6 +131,9 @@ def group_key(rec, levels, i):
         return levels[i], op, len(rec.inputs[i])
     if op == NODE_PUFKS:
         return levels[i], op, len(rec.inputs[i]) | rec.kind[rec.inputs[i][0]] << 32
+    if op == NODE_LWE_LINEAR:       # K | M << 32 | slot << 48 | kind << 56
+        slot, rows = rec.linear_of(i)
+        return levels[i], op, len(rec.inputs[i]) | rows << 32 | slot << 48 | rec.kind[i] << 56
     return levels[i], op, rec.param[i]
 
 
@@ -110,6 +154,7 @@ class _Builder:
         self.pool = {k: [] for k in ValueKind}
         self.claims = []        # (name, f(view) -> bool)
         self.keep = []          # nodes that are outputs whatever the sample draws
+        self.dead = set()       # nodes that nobody uses and that are no outputs either
         self.lvl = []
 
     # ---- nodes
@@ -144,6 +189,12 @@ class _Builder:
 
     def pufks(self, nodes):
         return self._note(self.rec.add_public_functional_keyswitch(nodes))
+
+    def linear(self, slot, nodes):
+        """one layer of weight slot `slot` -> its M row nodes"""
+        M, K = LINEAR_SHAPE[slot]
+        assert len(nodes) == K, (slot, K, len(nodes))
+        return [self._note(r) for r in self.rec.add_lwe_linear(slot, nodes, M)]
 
     def rotation(self, acc, sels, log_stride=0):
         first = len(self.rec.op)
@@ -197,6 +248,28 @@ class _View:
         at = [members.index(i) for i in nodes]
         return all(b == a + 1 for a, b in zip(at, at[1:]))
 
+    def position(self, i):
+        """orders the nodes as plan() lays them out in the arena: inputs and constants in node order, then the groups by (level,
+        kind, parameter), a group's members in node order"""
+        if self.rec.op[i] < 0:
+            return 0, -3, 0, i
+        return self.key(i) + (self.groups[self.key(i)].index(i),)
+
+    def scattered(self, nodes):
+        """a repeat, or two neighbours of which the second lies no later than the first: consecutive under no layout"""
+        return any(self.position(b) <= self.position(a) for a, b in zip(nodes, nodes[1:]))
+
+    def linear_operands(self, node):
+        """the operand rows of the whole group of a linear node, layer-major as plan() collects them"""
+        members = self.groups[self.key(node)]
+        M = self.rec.linear_of(node)[1]
+        return [j for q in range(0, len(members), M) for j in self.rec.inputs[members[q]]]
+
+    def in_place(self, node):
+        """the linear node's group reads its operands where they lie"""
+        ops = self.linear_operands(node)
+        return all(self.rec.op[j] >= 0 for j in ops) and self.rows(ops)
+
     def user_levels(self, i):
         return {self.level[u] for u in self.users[i]}
 
@@ -221,8 +294,9 @@ def _outputs(b, sample):
     v = _View(rec)
     top = max(v.level)
     last = [i for i, op in enumerate(rec.op) if op >= 0 and v.level[i] == top]
-    unused = [i for i, op in enumerate(rec.op) if op >= 0 and not v.users[i]]
-    rest = [i for i, op in enumerate(rec.op) if op >= 0]
+    assert not any(v.users[i] or v.level[i] == top for i in b.dead)
+    unused = [i for i, op in enumerate(rec.op) if op >= 0 and not v.users[i] and i not in b.dead]
+    rest = [i for i, op in enumerate(rec.op) if op >= 0 and i not in b.dead]
     drawn = [rest[int(a)] for a in b.rng.integers(0, len(rest), size=min(sample, len(rest)))]
     order, seen = [], set()
     for i in b.keep + last + unused + drawn:
@@ -400,10 +474,113 @@ def _draw_full(b, with_pufks, pufks_kind, width_set):
         b.claim("pufks_result_as_cmux_operand", lambda v: all(rec.op[j] == NODE_PUFKS for j in rec.inputs[as_operand][1:]))
         b.claim("pufks_result_as_unpack_source", lambda v: rec.op[rec.inputs[as_source[0]][0]] == NODE_PUFKS)
         b.claim("unpack_source_is_a_keyswitch_node", lambda v: rec.op[rec.inputs[as_source[0]][0]] == NODE_PUFKS)
+        # ---- plaintext linear maps: like the keyswitch above they have no submit by handle, so `pushable` draws none
+        _draw_linear(b, s, t, G, uni_one, base, levels, p_mid, ValueKind(pufks_kind))
+
+
+def _draw_linear(b, s, t, G, uni_one, base, cmux_levels, p_mid, pufks_kind):
+    """every name of LINEAR_PATTERNS, drawn last: nothing here lengthens the graph (the deepest node stands on its last level)
+    and nothing takes slack from a bootstrap above (the deep sources are nodes of the longest path, which have none)"""
+    rec, rng = b.rec, b.rng
+    KS, SE, UNI, BIV = FheOp.KeyswitchL1toL0, FheOp.SampleExtract, TableOp.PBS_UNIVARIATE, TableOp.PBS_BIVARIATE
+    top = max(b.lvl)
+    slot_of = lambda layer: rec.linear_of(layer[0])[0]
+
+    # ---- level 2: layers over ONE keyswitch group (level 0 rows) and over the one-table bootstrap group (level 1 rows)
+    ks = [b.op(KS, [b.inp(L1)]) for _ in range(10)]           # users: layers of level 2 first, so the rows stay on level 1
+    a_ks, b_ks, a_pbs = b.linear(S_A, ks[:4]), b.linear(S_B, ks[:4]), b.linear(S_A, uni_one)
+    wide = [b.linear(S_WIDE, ks[4:7]), b.linear(S_WIDE, ks[7:10])]
+    mixed = [b.linear(S_BITS, uni_one[:3]), b.linear(S_BITS, [uni_one[3], uni_one[1], uni_one[0]])]
+    twice = [b.linear(S_TWICE, ks[8:10]) for _ in range(2)]
+    b.claim("linear_in_place_over_a_keyswitch_group", lambda v: v.whole_group(a_ks) and v.in_place(a_ks[0]) and rec.inputs[a_ks[0]] == tuple(ks[:4]))
+    b.claim("linear_in_place_over_a_univariate_group", lambda v: v.whole_group(a_pbs) and v.in_place(a_pbs[0]) and v.whole_group(uni_one))
+    b.claim("linear_two_layers_in_place", lambda v: v.whole_group(wide[0] + wide[1]) and v.in_place(wide[0][0]) and v.rows(ks[4:10]))
+    b.claim("linear_two_layers_one_consecutive_one_scattered", lambda v: v.whole_group(mixed[0] + mixed[1]) and v.rows(list(rec.inputs[mixed[0][0]]))
+            and v.scattered(rec.inputs[mixed[1][0]]) and not v.in_place(mixed[0][0]))
+    b.claim("linear_two_layers_over_one_operand_list", lambda v: v.whole_group(twice[0] + twice[1]) and rec.inputs[twice[0][0]] == rec.inputs[twice[1][0]]
+            and v.scattered(v.linear_operands(twice[0][0])))
+    b.claim("linear_two_slots_of_one_shape_on_one_level", lambda v: v.level[a_ks[0]] == v.level[b_ks[0]] and v.whole_group(a_ks) and v.whole_group(b_ks)
+            and LINEAR_SHAPE[S_A] == LINEAR_SHAPE[S_B] and rec.kind[a_ks[0]] == rec.kind[b_ks[0]] and v.in_place(b_ks[0]))
+    b.claim("linear_both_operand_kinds_on_one_level_with_one_slot", lambda v: v.level[a_ks[0]] == v.level[a_pbs[0]] and slot_of(a_ks) == slot_of(a_pbs)
+            and {rec.kind[a_ks[0]], rec.kind[a_pbs[0]]} == {int(L0), int(L1)})
+
+    # ---- the planner: conversion heads that are ready early and first used by a layer far above, next to a late one of their
+    # own group and created right after it: the layer's two rows are consecutive only because the head was pulled up
+    index = b.index()
+    deep_l0, ks_early = b.op(KS, [b.op(SE, [base[1]], b.index())]), b.op(KS, [b.inp(L1)])
+    pl_ks = b.linear(S_PAIR, [deep_l0, ks_early])
+    deep_l1, se_early = b.op(SE, [cmux_levels[0][0]], index), b.op(SE, [G[3]], index)
+    pl_se = b.linear(S_PAIR, [deep_l1, se_early])
+    for name, head, layer in (("keyswitch", ks_early, pl_ks), ("sample_extract", se_early, pl_se)):
+        b.claim(f"linear_pulls_a_{name}_up", lambda v, head=head, layer=layer: v.asap[head] + 2 <= v.level[layer[0]] and v.level[head] == v.level[layer[0]] - 1
+                and v.level[layer[0]] == min(v.user_levels(head)) and v.whole_group(layer) and v.in_place(layer[0]))
+    # a table bootstrap that is ready on level 2 and has slack, next to one that is ready on level 4 and has none (a public
+    # functional keyswitch and a chain of Not up to the last level hang on it): the slack pass runs both on level 4, and a layer
+    # whose other operand is an input follows the early one
+    ks_lin = [b.op(KS, [x]) for x in a_pbs[:2]]
+    uni_e, uni_l = b.op(UNI, [ks[6], G[2]]), b.op(UNI, [ks_lin[0], G[2]])
+    x = b.pufks([uni_l] if pufks_kind == L1 else [b.op(KS, [uni_l])])
+    while b.lvl[x] < top:
+        x = b.op(FheOp.Not, [x])
+    pl_uni = b.linear(S_PAIR, [uni_e, s[L1][0]])
+    b.keep += [x]
+    b.claim("linear_follows_a_moved_table_bootstrap", lambda v: v.moved_next_to_late(uni_e, uni_l) and v.level[pl_uni[0]] == v.level[uni_e] + 1 > v.asap[pl_uni[0]])
+    b.claim("linear_rows_into_a_keyswitch", lambda v: all(rec.op[rec.inputs[k][0]] == NODE_LWE_LINEAR and rec.kind[rec.inputs[k][0]] == int(L1) for k in ks_lin))
+
+    # ---- scattered
+    perm = [a_ks[int(i)] for i in rng.permutation(len(a_ks))]
+    if perm == a_ks:
+        perm = perm[::-1]
+    only_linear = b.inp(L0)                                   # an input that reaches the outputs through a linear layer only
+    lists = {"previous_layer_permuted": (S_PERM, perm),
+             "operand_repeated": (S_REPEAT, [ks[1], ks[3], ks[1], wide[1][2], b_ks[7]]),
+             "three_levels_inputs_and_constants": (S_MIXED, [deep_l0, a_ks[2], ks[5], only_linear, t[L0, 1], t[L0, 0], s[L0][2]])}
+    sc = {name: b.linear(slot, ops) for name, (slot, ops) in lists.items()}
+    also = {"previous_layer_permuted": lambda v, ops: sorted(ops) == a_ks and ops != a_ks,
+            "operand_repeated": lambda v, ops: len(set(ops)) == len(ops) - 1,
+            "three_levels_inputs_and_constants": lambda v, ops: len({v.level[j] for j in ops}) >= 4 and {-1, -2} <= {rec.op[j] for j in ops}}
+    for name, layer in sc.items():
+        b.claim(f"linear_scattered_{name}", lambda v, name=name, layer=layer: v.whole_group(layer) and v.scattered(rec.inputs[layer[0]])
+                and also[name](v, list(rec.inputs[layer[0]])))
+
+    # ---- consumers of linear rows
+    one = b.linear(S_ONE, [deep_l0])
+    cbs = b.op(FheOp.CircuitBootstrap, [one[0]])
+    uni_lin = b.op(UNI, [b_ks[0], G[2]])
+    # plaintext bits no other bivariate group has, so that each pair is a group of its own: _draw_full's bivariates take 0, 63 and
+    # p_mid and nothing else, and a bivariate node is drawn nowhere else (both whole_group claims below would refuse a collision)
+    p_c, p_s = [p for p in (1, 2, 3) if p != p_mid][:2]
+    biv_c = [b.op(BIV, [a_ks[i], a_ks[i + 1], G[3]], p_c) for i in (0, 1)]
+    biv_s = [b.op(BIV, [a_ks[4 + i], x, G[2]], p_s) for i, x in enumerate((t[L0, 1], s[L0][3]))]
+    rows = pl_ks if pufks_kind == L0 else pl_se
+    k_rows, k_repeat = b.pufks(rows), b.pufks([rows[0], rows[1], rows[1], rows[2]])
+    b.dead |= set(wide[1]) - {wide[1][2], wide[1][16]}
+    b.keep += a_ks + [wide[1][16], cbs, uni_lin, k_rows, k_repeat] + biv_c + biv_s + sc["three_levels_inputs_and_constants"]
+    b.claim("linear_shape_1_1", lambda v: LINEAR_SHAPE[slot_of(one)] == (1, 1) and v.in_place(one[0]))
+    b.claim("linear_row_into_a_circuit_bootstrap", lambda v: rec.inputs[cbs] == (one[0],) and rec.kind[one[0]] == int(L0))
+    b.claim("linear_row_into_a_univariate_bootstrap", lambda v: rec.inputs[uni_lin][0] == b_ks[0] and rec.kind[b_ks[0]] == int(L0))
+    b.claim("linear_rows_into_a_bivariate_consecutive", lambda v: v.whole_group(biv_c) and v.rows(a_ks[:3]))
+    b.claim("linear_row_into_a_bivariate_scattered", lambda v: v.whole_group(biv_s) and v.rows(a_ks[4:6]) and v.scattered([rec.inputs[n][1] for n in biv_s]))
+    b.claim("linear_rows_into_a_functional_keyswitch_in_order", lambda v: v.whole_group([k_rows]) and v.rows(rows) and rec.inputs[k_rows] == tuple(rows))
+    b.claim("linear_rows_into_a_functional_keyswitch_with_a_repeat", lambda v: v.whole_group([k_repeat]) and len(set(rec.inputs[k_repeat])) < len(rec.inputs[k_repeat])
+            and all(rec.op[j] == NODE_LWE_LINEAR for j in rec.inputs[k_repeat]))
+    b.claim("linear_row_is_an_output_and_has_users", lambda v: all(n in rec.outputs and v.users[n] for n in a_ks[:6]))
+    b.claim("linear_layer_partly_used", lambda v: {bool(v.users[n]) or n in rec.outputs for n in wide[1]} == {True, False}
+            and v.users[wide[1][2]] and wide[1][16] in rec.outputs)
+
+    # ---- the last linear launch: unpack bits of a deep node, a layer over the first of them, a layer with one-limb weights over
+    # all of its rows, alone on the deepest level that has linear nodes (with the matrix cores forced, their kernel is the last)
+    bits = b.unpack(cmux_levels[2][0], 5)
+    over_bits = b.linear(S_BITS, bits[:3])
+    last = b.linear(S_LAST, over_bits)
+    b.claim("linear_in_place_over_unpack_bits", lambda v: v.whole_group(over_bits) and v.in_place(over_bits[0]) and rec.param[bits[0]] == 0)
+    b.claim("linear_in_place_over_a_previous_layer", lambda v: v.whole_group(last) and v.in_place(last[0]) and rec.inputs[last[0]] == tuple(over_bits))
+    b.claim("linear_last_group_in_place_with_one_limb_weights", lambda v: LINEAR_CLASS[slot_of(last)] == 1 and v.whole_group(last) and v.in_place(last[0])
+            and v.level[last[0]] > max(v.level[i] for i, op in enumerate(rec.op) if op == NODE_LWE_LINEAR and i not in last))
 
 
 def _draw_small(b, with_pufks, pufks_kind):
-    """every node kind once or twice, nothing wider than 3, for random parameter sets"""
+    """every node kind once or twice, nothing wider than 3 but the two linear layers, for random parameter sets"""
     P, rng = b.P, b.rng
     s, t = _sources(b, 3, 1, 2, 1, 1)
     G, S, V = s[GL], s[GG], s[GV]
@@ -432,13 +609,26 @@ def _draw_small(b, with_pufks, pufks_kind):
         rows = l0 + s[L0] + [t[L0, 0]] if ValueKind(pufks_kind) == L0 else bits + s[L1] + [uni, biv, se, t[L1, 1]]
         k = b.pufks(b.pick(pufks_kind, int(rng.integers(1, 4)), among=rows))
         b.keep += [k, b.op(FheOp.CMux, [b.pick(GG, among=sels), k, b.pick(GL, among=vals)])]
+    # two linear layers of either kind (W from 2 words to kN + 1 over the parameter sets): nine rows (above LWE_LINEAR_VT) over
+    # five scattered operands, the first of them twice, then two rows over those nine in place
+    kind = L0 if rng.random() < 0.5 else L1
+    among = l0 + s[L0] + [t[L0, 0], t[L0, 1]] if kind == L0 else bits + s[L1] + [uni, biv, se, t[L1, 1]]
+    ops = b.pick(kind, 4, among=among)
+    first = b.linear(S_REPEAT, ops + [ops[0]])
+    second = b.linear(S_SMALL, first)
+    b.keep += [first[0], second[1]] + ([b.op(FheOp.KeyswitchL1toL0, [second[0]])] if kind == L1 else [])
+    b.claim("linear_scattered_operand_repeated", lambda v: v.whole_group(first) and v.scattered(b.rec.inputs[first[0]]))
+    b.claim("linear_in_place_over_a_previous_layer", lambda v: v.whole_group(second) and v.in_place(second[0]))
 
 
-def draw_circuit(seed, P, profile, pufks_kind=None):
+def draw_circuit(seed, P, profile, pufks_kind=None, linear_seed=None):
     """-> (RecordedCircuit, facts).  facts: "patterns": the names of PATTERNS the circuit holds (claimed by the construction and
-    confirmed on the planned levels); "refused": claimed but not confirmed; "pufks_kind": the operand kind of its public
-    functional keyswitch nodes (drawn unless given; None without such nodes); "nodes" / "groups": counts by kind name."""
+    confirmed on the planned levels); "refused": claimed but not confirmed; "pufks_kind": the operand kind
+    of its public functional keyswitch nodes (drawn unless given; None without such nodes); "nodes" / "groups": counts by kind
+    name; "linear_slots": the weight slots its linear nodes name, `draw_linear_slots(linear_seed)` (derived from `seed` unless
+    given: circuits that share an engine or a group are drawn with one `linear_seed`), None for `pushable`."""
     assert profile in PROFILES
+    linear_seed = 0x11EA0000 + seed if linear_seed is None else linear_seed
     b = _Builder(seed, P, profile)
     with_pufks = profile != "pushable"
     if with_pufks and pufks_kind is None:
@@ -450,7 +640,7 @@ def draw_circuit(seed, P, profile, pufks_kind=None):
         _draw_full(b, with_pufks, pufks_kind, _WIDTH_SETS[seed % 3])
     _outputs(b, 8 if profile == "small" else 30)
     v = _View(b.rec)
-    held = [name for name, fn in b.claims if fn(v)]
+    held = {name for name, fn in b.claims if fn(v)}
     nodes, groups = {}, {}
     for i in range(len(b.rec.op)):
         name = kind_name(b.rec, i).split("(")[0]
@@ -458,5 +648,6 @@ def draw_circuit(seed, P, profile, pufks_kind=None):
     for key, members in v.groups.items():
         name = kind_name(b.rec, members[0])
         groups[name] = groups.get(name, 0) + 1
-    return b.rec, {"patterns": sorted(set(held)), "refused": sorted({n for n, _ in b.claims} - set(held)), "pufks_kind": pufks_kind,
-                   "nodes": nodes, "groups": groups, "levels": max(v.level), "seed": seed, "profile": profile}
+    return b.rec, {"patterns": sorted(held), "refused": sorted({n for n, _ in b.claims} - held), "pufks_kind": pufks_kind,
+                   "nodes": nodes, "groups": groups, "levels": max(v.level), "seed": seed, "profile": profile,
+                   "linear_seed": linear_seed if with_pufks else None, "linear_slots": draw_linear_slots(linear_seed) if with_pufks else None}

@@ -1,8 +1,11 @@
 """Randomised differential tests of gate graphs with every node kind mixed (r23): circuits of tests/graph_fuzz_cases.py, lowered
 into a gate graph, pushed node by node through the pool by handle, run as jobs of a device group, and drawn on random parameter
-sets.  The only expectation is `circuit_model.evaluate`, the oracle walking the same circuit on the CPU; the only comparison is
-`same_words`.  The default suite runs a few circuits per context; `SPF_FUZZ_CASES=N` (and `SPF_FUZZ_SEED`) turn it into a soak
-and `SPF_FUZZ_REPORT=path` collects one JSON line per circuit — profiles/r23_graph_fuzz.md records the r23 run."""
+sets.  Since r29 the plaintext linear maps are among the node kinds: their weight slots (`graph_fuzz_cases.draw_linear_slots`)
+are loaded before a circuit is lowered and handed to the model with the keys.  The only expectation is
+`circuit_model.evaluate`, the oracle walking the same circuit on the CPU; the only comparison is `same_words`.  The default
+suite runs a few circuits per context; `SPF_FUZZ_CASES=N` (and `SPF_FUZZ_SEED`) turn it into a soak and `SPF_FUZZ_REPORT=path`
+collects one JSON line per circuit — profiles/r23_graph_fuzz.md records the r23 run, profiles/r29_graph_fuzz_linear.md the one
+with linear nodes."""
 import gc
 import json
 import os
@@ -13,9 +16,10 @@ import pytest
 import oracle as O
 import spf_amd
 from spf_amd import FheOp, ValueKind
-from spf_amd.graph import NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from spf_amd.graph import NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
 from tests import circuit_model as M
 from tests import graph_fuzz_cases as F
+from tests import lwe_linear_cases as LC
 from tests import pbs_graph_cases as K
 from tests.util import to_engine_params
 
@@ -44,7 +48,8 @@ def report(test, which, facts, **more):
     path = os.environ.get("SPF_FUZZ_REPORT")
     if path:
         line = {"test": test, "context": which, "seed": facts["seed"], "profile": facts["profile"], "nodes": facts["nodes"],
-                "groups": facts["groups"], "levels": facts["levels"], "pufks_kind": None if facts["pufks_kind"] is None else facts["pufks_kind"].name}
+                "groups": facts["groups"], "levels": facts["levels"], "pufks_kind": None if facts["pufks_kind"] is None else facts["pufks_kind"].name,
+                "linear_nodes": facts["nodes"].get("LweLinear", 0), "linear_groups": facts["groups"].get("LweLinear", 0)}
         line.update(more)
         with open(path, "a") as f:
             f.write(json.dumps(line) + "\n")
@@ -54,6 +59,13 @@ def check(rec, got, want, tag):
     """every output against the model; the message names the seed, the case and the lowest differing output node"""
     message = M.first_difference(rec, got, want)
     assert message is None, f"{tag}: {message}"
+
+
+def load_linear_slots(eng, slots):
+    """every weight slot of the table into an engine or a group: before lower() (a graph may also be built first; run() checks)"""
+    for slot, (w, b) in slots.items():
+        eng.load_lwe_linear_weights(slot, w, b)
+    return slots
 
 
 def pufks_key_of(which, case, P, kind):
@@ -68,10 +80,14 @@ def pufks_key_of(which, case, P, kind):
 
 
 @pytest.mark.parametrize("which", K.CONTEXTS)
-def test_random_graphs_of_every_node_kind_equal_the_oracle(rigs, which):
+def test_random_graphs_of_every_node_kind_equal_the_oracle(rigs, which, monkeypatch):
     """profile `full` lowered into one gate graph; run, the inputs refilled and run again; on the tuned context every third case
-    then loads a key of the other radix family and runs a third time (the keyswitch nodes' rows are planned again)"""
+    then loads a key of the other radix family and runs a third time (the keyswitch nodes' rows are planned again).  One case in
+    three loads other weights of the same shapes into every slot between its first and second run.  Case 0 is then lowered a
+    second time with the matrix cores forced on every in-place linear group they can serve: the same words, and the last linear
+    launch (in place, one-limb weights: `linear_last_group_in_place_with_one_limb_weights`) is theirs"""
     P, eng = rigs(which)
+    monkeypatch.delenv("SPF_LWE_LINEAR_PATH", raising=False)
     for case in range(CASES):
         seed = F.case_seed(SEED, 0, case)
         rec, facts = F.draw_circuit(seed, P, "full", F.tuned_pufks_kind(case) if which == "tuned" else None)
@@ -80,6 +96,7 @@ def test_random_graphs_of_every_node_kind_equal_the_oracle(rigs, which):
         if which == "tuned" and case % 3 == 0:
             log, count = (5, 3) if key[1:] != (5, 3) else (4, 4)
             runs.append((K.pufks_key(P.N, P.k, key[0].shape[0], count, seed=log), log, count))
+        slots = load_linear_slots(eng, facts["linear_slots"])
         g, outs = rec.lower(eng)
         launches = []
         try:
@@ -89,11 +106,28 @@ def test_random_graphs_of_every_node_kind_equal_the_oracle(rigs, which):
                     eng.load_public_functional_keyswitch_key_std(*loaded)
                 if run:
                     F.refill_inputs(rec, P, seed + run)
+                if run == 1 and case % 3 == 1:
+                    slots = load_linear_slots(eng, F.draw_linear_slots(facts["linear_seed"] + 1))
                 g.run()
                 launches.append(g.stats()["launches"])
-                check(rec, outs, M.evaluate(rec, P, M.keys_of(which, loaded)), tag)
+                want = M.evaluate(rec, P, M.keys_of(which, loaded, slots))
+                check(rec, outs, want, tag)
             assert g.stats()["nodes"] == len(rec.op)
-            report("lowered", which, facts, launches=launches, outputs=len(outs),
+            kernels = [eng.last_lwe_linear_kernel()]
+            if case == 0:
+                assert kernels[0] == LC.VALU, tag      # (the cost rule takes the matrix cores from K = 512 on; in place, so not the rows kernel)
+                monkeypatch.setenv("SPF_LWE_LINEAR_PATH", "mfma")
+                forced, forced_outs = rec.lower(eng)
+                try:
+                    forced.run()
+                    kernels.append(eng.last_lwe_linear_kernel())
+                finally:
+                    forced.close()
+                    monkeypatch.delenv("SPF_LWE_LINEAR_PATH")
+                check(rec, forced_outs, want, tag + " lowered again with SPF_LWE_LINEAR_PATH=mfma")
+                assert all(K.same_words(a, b) for a, b in zip(forced_outs, outs)), tag
+                assert kernels[1] == "pfks_gemm_kernel<1>", (tag, kernels)
+            report("lowered", which, facts, launches=launches, outputs=len(outs), linear_kernels=kernels, linear_reloaded=case % 3 == 1,
                    radix=[list(r[1:]) for r in runs], kernel=eng.last_public_functional_keyswitch_kernel())
         finally:
             g.close()
@@ -181,7 +215,7 @@ def push_circuit(pool, rec, order):
                         continue
                 vals[i] = pool.push_blind_rotation_v(vals[ins[1]], [vals[ins[0]]], par.bit_length() - 1)
             else:
-                assert op != NODE_PUFKS, "a public functional keyswitch node has no submit by handle"
+                assert op not in (NODE_PUFKS, NODE_LWE_LINEAR), "public functional keyswitch and linear nodes have no submit by handle"
                 vals[i] = pool.push_v(op, [vals[j] for j in ins], par)
         return [vals[node].wait().download() for node in rec.outputs]
     finally:
@@ -218,27 +252,40 @@ def test_random_graphs_pushed_by_handle_equal_the_oracle(rigs, which):
 
 # ---- jobs of a device group ---------------------------------------------------------------------------------------------------
 
+def linear_group_keys(rec):
+    """plan()'s keys (level, kind, K | M << 32 | slot << 48 | operand kind << 56) of the linear groups of a circuit run alone"""
+    levels = M.planned_levels(rec)
+    return {F.group_key(rec, levels, i) for i, op in enumerate(rec.op) if op == NODE_LWE_LINEAR}
+
+
 def test_random_graphs_as_group_jobs_equal_the_oracle():
     """four circuits of the (128, 2) context and two of the tuned one as jobs of Group(devices=[0, 0]): a member that is dealt two
-    jobs runs them merged into one graph (nodes and pack / keyswitch operand lists renumbered)"""
+    jobs runs them merged into one graph (nodes and pack / keyswitch / linear operand lists renumbered).  All jobs of a group are
+    drawn with ONE linear_seed and the group holds one table of weight slots, so layers of two jobs that share a slot and a level
+    become one group of the merged graph"""
     for round_ in range(max(1, CASES // 3)):
         for which, n_jobs in (("n128k2", 4), ("tuned", 2)):
             P = K.keys_of(which)[0]
             key, log, count = pufks_key_of(which, 1 + round_, P, ValueKind.LWE0)
             seeds = [F.case_seed(SEED, 2, 100 * round_ + 10 * K.CONTEXTS.index(which) + j) for j in range(n_jobs)]
-            recs = [F.draw_circuit(s, P, "full", ValueKind.LWE0) for s in seeds]
+            recs = [F.draw_circuit(s, P, "full", ValueKind.LWE0, linear_seed=seeds[0]) for s in seeds]
+            slots = recs[0][1]["linear_slots"]
             grp = spf_amd.Group(K.engine_params(P), devices=[0, 0])
             jobs = []
             try:
                 K.load_keys(grp, which)
                 grp.load_public_functional_keyswitch_key_std(key, log, count)
+                load_linear_slots(grp, slots)
                 jobs = [rec.lower(grp) for rec, _ in recs]
                 grp.run_graphs([g for g, _ in jobs])
                 members = [g.member() for g, _ in jobs]
                 if n_jobs > 2:
                     assert max(members.count(m) for m in set(members)) >= 2, members       # at least one merge of two
+                for m in set(members):      # two circuits dealt to one member: layers of one slot, shape, kind and level in both
+                    dealt = [recs[j][0] for j in range(n_jobs) if members[j] == m]
+                    assert all(linear_group_keys(a) & linear_group_keys(b) for a, b in zip(dealt, dealt[1:])), (m, members)
                 for j, ((rec, facts), (g, outs)) in enumerate(zip(recs, jobs)):
-                    want = M.evaluate(rec, P, M.keys_of(which, (key, log, count)))
+                    want = M.evaluate(rec, P, M.keys_of(which, (key, log, count), slots))
                     check(rec, outs, want, f"seed {seeds[j]} job {j} of {n_jobs} ({which}) on member {members[j]} of {members}")
                     report("group", which, facts, member=members[j], members=members)
             finally:
@@ -251,7 +298,8 @@ def test_random_graphs_as_group_jobs_equal_the_oracle():
 
 def test_random_parameter_sets_with_random_graphs():
     """parameter sets drawn as test_gpu_fuzz.py::test_random_parameter_sets_through_the_generic_family draws them (the same
-    bounds), a random radix of the public-functional-keyswitch key, one `small` circuit per set"""
+    bounds), a random radix of the public-functional-keyswitch key, one `small` circuit per set: its two linear layers (nine rows
+    over scattered operands, two rows in place) work on rows of 2 words up to kN + 1"""
     rng = np.random.default_rng(SEED + 3)
     for case in range(max(4, CASES)):
         if rng.random() < 0.2:
@@ -295,10 +343,11 @@ def test_random_parameter_sets_with_random_graphs():
             eng.load_automorphism_key(ak)
             eng.load_scheme_switch_key(ssk)
             eng.load_public_functional_keyswitch_key_std(key, fl, fc)
+            slots = load_linear_slots(eng, facts["linear_slots"])
             g, outs = rec.lower(eng)
             try:
                 g.run()
-                check(rec, outs, M.evaluate(rec, P, M.Keys(ks, ak, ssk, (key, fl, fc))), tag)
+                check(rec, outs, M.evaluate(rec, P, M.Keys(ks, ak, ssk, (key, fl, fc), slots)), tag)
                 report("parameter sets", f"N{N}k{k}", facts, launches=[g.stats()["launches"]], tag=tag)
             finally:
                 g.close()

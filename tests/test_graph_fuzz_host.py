@@ -13,6 +13,8 @@ from spf_amd import graph as G
 from tests import blind_rotation_graph_cases as BR
 from tests import circuit_model as M
 from tests import graph_fuzz_cases as F
+from tests import lwe_linear_cases as LC
+from tests import lwe_linear_graph_cases as LG
 from tests import pbs_graph_cases as K
 from tests import pufks_cases as PC
 from tests.polyref_cases import key_fft
@@ -30,12 +32,22 @@ def default_circuits(which, profile):
         yield F.draw_circuit(F.case_seed(F.DEFAULT_SEED, test, case), P, profile, kind)
 
 
+def same_slots(a, b):
+    """two weight-slot tables (or None twice) hold the same slots, weights and bias words"""
+    if a is None or b is None:
+        return a is None and b is None
+    return a.keys() == b.keys() and all(np.array_equal(a[q][0], b[q][0]) and (a[q][1] is None) == (b[q][1] is None)
+                                        and (a[q][1] is None or np.array_equal(a[q][1], b[q][1])) for q in a)
+
+
 def test_the_generator_is_deterministic():
     P = K.TEST1
     for profile in F.PROFILES:
         a, fa = F.draw_circuit(77, P, profile)
         b, fb = F.draw_circuit(77, P, profile)
+        assert same_slots(fa.pop("linear_slots"), fb.pop("linear_slots"))     # (arrays: compared apart from the rest)
         assert (a.op, a.kind, a.param, a.inputs, a.outputs) == (b.op, b.kind, b.param, b.inputs, b.outputs) and fa == fb
+        assert a._linear == b._linear
         assert all(x is None and y is None or np.array_equal(x, y) for x, y in zip(a.host, b.host))
         c, _ = F.draw_circuit(78, P, profile)
         assert (a.op, a.param, a.inputs) != (c.op, c.param, c.inputs)
@@ -52,6 +64,10 @@ def test_every_circuit_is_one_recorded_circuit_accepts(which, profile):
         assert all(j < i for i, ins in enumerate(rec.inputs) for j in ins)
         again = spf_amd.RecordedCircuit.from_arrays(rec.arrays(), rec.kind, rec.host, P.N)
         assert (again.op, again.kind, again.param, again.inputs) == (rec.op, rec.kind, rec.param, rec.inputs)
+        assert again._linear == rec._linear and (profile == "pushable") == (not rec._linear)
+        for i in rec._linear:                                  # every layer is of its slot's shape, and the slot is in the table
+            assert rec.linear_of(i) == (rec.linear_of(i)[0], facts["linear_slots"][rec.linear_of(i)[0]][0].shape[0])
+            assert len(rec.inputs[i]) == facts["linear_slots"][rec.linear_of(i)[0]][0].shape[1]
         assert sorted(set(rec.outputs)) == again.outputs
         assert len(rec.op) <= (F.MAX_NODES_SMALL if profile == "small" else F.MAX_NODES), len(rec.op)
         for kind in ("CircuitBootstrap", "PBS_UNIVARIATE", "PBS_BIVARIATE"):
@@ -70,19 +86,26 @@ def test_the_default_seeds_reach_every_pattern_and_every_node_kind(which):
     each context, lowered and pushed; every FheOp, TableOp and NODE_* constant of spf_amd.graph is a node of every one"""
     assert len(NODE_CONSTANTS) >= 4 and len(list(FheOp)) + len(list(TableOp)) >= 12
     kinds = {int(op) for op in FheOp} | {int(op) for op in TableOp} | set(NODE_CONSTANTS.values())
-    for profile, left_out in (("full", set()), ("pushable", set(F.PUFKS_PATTERNS))):
+    assert G.NODE_LWE_LINEAR == 68 and NODE_CONSTANTS["NODE_LWE_LINEAR"] == 68 and set(F.LINEAR_PATTERNS) <= set(F.PATTERNS)
+    for profile, left_out in (("full", set()), ("pushable", set(F.PUFKS_PATTERNS) | set(F.LINEAR_PATTERNS))):
         reached = set()
         for rec, facts in default_circuits(which, profile):
             reached |= set(facts["patterns"])
-            missing = kinds - set(rec.op) - ({G.NODE_PUFKS} if profile == "pushable" else set())
+            missing = kinds - set(rec.op) - ({G.NODE_PUFKS, G.NODE_LWE_LINEAR} if profile == "pushable" else set())
             assert not missing, (profile, facts["seed"], missing)
+            assert not set(F.LINEAR_PATTERNS) & set(facts["refused"]), (profile, facts["seed"], facts["refused"])
+            if profile == "full":                           # EVERY full circuit holds every linear layout, not one of the three
+                assert set(F.LINEAR_PATTERNS) <= set(facts["patterns"]), (facts["seed"], sorted(set(F.LINEAR_PATTERNS) - set(facts["patterns"])))
             assert {-1, -2} <= set(rec.op)
         assert set(F.PATTERNS) - left_out <= reached, (profile, sorted(set(F.PATTERNS) - left_out - reached))
         assert reached <= set(F.PATTERNS)
     P = K.keys_of(which)[0]
     for seed in range(3):                   # the small profile: every kind, on any parameter set
-        rec, _ = F.draw_circuit(seed, P, "small")
+        rec, facts = F.draw_circuit(seed, P, "small")
         assert kinds <= set(rec.op), kinds - set(rec.op)
+        # its two layers: one above LWE_LINEAR_VT rows over scattered operands, one in place
+        assert {"linear_scattered_operand_repeated", "linear_in_place_over_a_previous_layer"} <= set(facts["patterns"]), facts["refused"]
+        assert max(rec.linear_of(i)[1] for i in rec._linear) > 8
 
 
 def test_planned_levels_on_a_graph_whose_levels_are_known():
@@ -137,6 +160,75 @@ def test_the_model_equals_pufks_oracle_on_a_keyswitch_node():
     node = rec.add_public_functional_keyswitch([ids[i] for i in (2, 0, 3, 3, 1)])
     vals = M.evaluate(rec, P, M.keys_of("n128k2", (key, log, count)))
     assert K.same_words(vals[node], PC.pufks_oracle(rows[[2, 0, 3, 3, 1]], key_fft(key), P.N, P.k, log, count).reshape(-1))
+
+
+def test_draw_linear_slots_is_deterministic_and_holds_every_class_shape_and_bias_state():
+    slots, again, other = F.draw_linear_slots(11), F.draw_linear_slots(11), F.draw_linear_slots(12)
+    assert same_slots(slots, again) and set(slots) == {q for q, *_ in F.LINEAR_SLOTS} == set(other)
+    assert all(0 <= q < G.LWE_LINEAR_SLOTS for q in slots) and G.LWE_LINEAR_SLOTS - 1 in slots
+    shapes = {q: w.shape for q, (w, _) in slots.items()}
+    assert shapes == F.LINEAR_SHAPE == {q: other[q][0].shape for q in other}          # a fixed table: only the contents are drawn
+    assert all(not np.array_equal(slots[q][0], other[q][0]) for q in slots if slots[q][0].size > 4)
+    assert {M for M, _ in shapes.values()} >= {1, 8, 9, 17} and any(1 < M < 8 for M, _ in shapes.values())      # around LWE_LINEAR_VT
+    assert {Kk for _, Kk in shapes.values()} >= {1, 4, 8} and any(Kk % 4 for _, Kk in shapes.values() if Kk > 1)  # the unroll
+    assert shapes[F.S_A] == shapes[F.S_B] and not np.array_equal(slots[F.S_A][0], slots[F.S_B][0])
+    assert {b is None for _, b in slots.values()} == {True, False}
+    classes = {q: LC.limbs_of(int(w.min()), int(w.max())) for q, (w, _) in slots.items()}
+    assert {1, 2, 3, 0} <= set(classes.values())
+    for q, M, Kk, cls, bias in F.LINEAR_SLOTS:
+        w, b = slots[q]
+        assert w.dtype == np.int64 and (b is None) == (not bias) and (b is None or (b.dtype == np.uint64 and b.shape == (M,)))
+        assert classes[q] == (cls if cls in (1, 2, 3) else 0), q
+        if cls == "beyond":
+            assert (w == LC.FIRST_BEYOND[1]).any()
+        if cls == "int64":
+            assert all((w == v).any() for v in (LC.INT64_MIN, -1, 0, LC.INT64_MAX)), q
+    given, derived, next_ = (F.draw_circuit(seed, K.TEST1, "full", linear_seed=ls)[1] for seed, ls in ((3, 11), (3, None), (4, None)))
+    assert given["linear_seed"] == 11 and same_slots(given["linear_slots"], slots)
+    assert len({11, derived["linear_seed"], next_["linear_seed"]}) == 3           # derived from the circuit seed unless given
+    assert same_slots(derived["linear_slots"], F.draw_linear_slots(derived["linear_seed"]))
+
+
+@pytest.mark.parametrize("slot", [q for q, *_ in F.LINEAR_SLOTS])
+def test_the_model_equals_linear_literal_on_a_linear_node(slot):
+    """the reference's loop on Python integers (independent of `linear_ref`), for a slot of each weight class, shape and bias
+    state; operands of both kinds with a repeat among them"""
+    P = K.TEST1
+    w, b = F.draw_linear_slots(0xF40)[slot]
+    rows_out, Kk = w.shape
+    for kind, dim in ((ValueKind.LWE0, P.lwe_n), (ValueKind.LWE1, P.k * P.N)):
+        rows = random_lwe_batch(0xF41 + slot, Kk, dim)
+        rec = spf_amd.RecordedCircuit(P.N)
+        ids = [rec.add_input(kind, r) for r in rows]
+        order = [(3 * j + 1) % Kk for j in range(Kk - 1)] + [0]               # a permutation for odd K, repeats elsewhere
+        nodes = rec.add_lwe_linear(slot, [ids[j] for j in order], rows_out)
+        vals = M.evaluate(rec, P, M.Keys(None, None, None, None, {slot: (w, b)}))      # (no key but the weight slots)
+        want = LC.linear_literal(rows[order], w, b)
+        for m, node in enumerate(nodes):
+            assert K.same_words(vals[node], np.array(want[m], dtype=np.uint64)), (slot, kind, m)
+
+
+@pytest.mark.parametrize("kind", [ValueKind.LWE0, ValueKind.LWE1], ids=["lwe0", "lwe1"])
+def test_the_model_equals_chain_by_oracle_on_the_recorded_chain(kind):
+    """tests/lwe_linear_graph_cases.py's "layer -> table -> layer -> table", recorded: the walk its own GPU test compares with"""
+    which = "n16k1"
+    P, ks = K.keys_of(which)[:2]
+    Kk, M1, M2 = 4, 3, 2
+    (wa, ba), (wb, bb) = LG.weights(0xF50, M1, Kk, True), LG.weights(0xF51, M2, M1, False)
+    luts = random_glwe(0xF52, 2, P.glwe_len)
+    x = LC.uniform_inputs(0xF53, 1, Kk, LG.words(P, kind))[0]
+
+    class Rec(spf_amd.RecordedCircuit):     # chain() keeps what add_output returns: here the node, not an array to be filled
+        def add_output(self, node, kind):
+            super().add_output(node, kind)
+            return node
+
+    rec = Rec(P.N)
+    outs = LG.chain(rec, kind, 20, 21, x, luts[0], luts[1], M1, M2)
+    vals = M.evaluate(rec, P, M.keys_of(which, None, {20: (wa, ba), 21: (wb, bb)}))
+    want = LG.chain_by_oracle(P, ks, kind, x, wa, ba, wb, bb, luts[0], luts[1])
+    for name in ("a", "h", "b", "y"):
+        assert K.same_words(np.stack([vals[n] for n in outs[name]]), want[name]), name
 
 
 @pytest.mark.parametrize("which", K.CONTEXTS)
@@ -196,11 +288,14 @@ def test_the_model_states_the_constants_and_the_keyless_kinds_as_their_tests_do(
 
 def test_the_comparison_bites():
     """one word of one input changed: every output the model computes from that input differs under `same_words`, the others do
-    not, and `first_difference` names the lowest of them"""
+    not, and `first_difference` names the lowest of them.  One of the inputs reaches the outputs through linear layers only"""
     which = "n16k1"
     P = K.keys_of(which)[0]
     rec, facts = F.draw_circuit(5, P, "full", ValueKind.LWE0)
-    keys = M.keys_of(which, (K.pufks_key(P.N, P.k, P.lwe_n, 3), 4, 3))
+    keys = M.keys_of(which, (K.pufks_key(P.N, P.k, P.lwe_n, 3), 4, 3), facts["linear_slots"])
+    users = [[i for i, ins in enumerate(rec.inputs) if node in ins] for node in range(len(rec.op))]
+    only_linear = [node for node, op in enumerate(rec.op) if op == -1 and users[node] and all(rec.op[u] == G.NODE_LWE_LINEAR for u in users[node])]
+    assert only_linear
     want = M.evaluate(rec, P, keys)
     assert M.first_difference(rec, [want[n] for n in rec.outputs], want) is None
     depends = [set() for _ in rec.op]
@@ -219,14 +314,17 @@ def test_the_comparison_bites():
         message = M.first_difference(rec, [got[n] for n in rec.outputs], want)
         assert message is not None and f"lowest node {min(hit)} " in message, message
         flipped += 1
-    assert flipped >= 10
+        if node in only_linear:
+            only_linear.remove(node)
+    assert flipped >= 10 and not only_linear
 
 
 def test_time_of_the_model_on_a_full_circuit_of_the_tuned_set():
-    """sizes the GPU tests' node budget (profiles/r23_graph_fuzz.md): the oracle walks a default circuit in seconds"""
+    """sizes the GPU tests' node budget (profiles/r23_graph_fuzz.md, r29_graph_fuzz_linear.md): the oracle walks a default
+    circuit in seconds"""
     P = K.keys_of("tuned")[0]
     rec, facts = F.draw_circuit(F.case_seed(F.DEFAULT_SEED, 0, 0), P, "full", ValueKind.LWE0)
-    keys = M.keys_of("tuned", (K.pufks_key(P.N, P.k, P.lwe_n, 8, seed=4), 4, 8))
+    keys = M.keys_of("tuned", (K.pufks_key(P.N, P.k, P.lwe_n, 8, seed=4), 4, 8), facts["linear_slots"])
     t0 = time.perf_counter()
     vals = M.evaluate(rec, P, keys)
     seconds = time.perf_counter() - t0

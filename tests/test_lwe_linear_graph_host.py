@@ -12,7 +12,7 @@ import pytest
 
 import spf_amd
 from spf_amd import FheOp, ValueKind, _ffi
-from spf_amd.graph import LWE_LINEAR_NODE
+from spf_amd.graph import NODE_LWE_LINEAR
 from tests import lwe_linear_cases as LC
 from tests import lwe_linear_graph_cases as G
 
@@ -28,10 +28,11 @@ def circuit():
             rec.add_input(ValueKind.GGSW1, np.zeros(1)))
 
 
-def test_the_node_kind_is_68_and_is_no_NODE_name():
+def test_the_node_kind_is_68_and_is_a_NODE_name():
+    """a NODE_* name: the random differential tests of gate graphs draw every one of them (tests/test_graph_fuzz_host.py)"""
     import spf_amd.graph as graph
-    assert LWE_LINEAR_NODE == 68
-    assert not [n for n in dir(graph) if n.startswith("NODE_") and getattr(graph, n) == 68]
+    assert NODE_LWE_LINEAR == 68
+    assert [n for n in dir(graph) if n.startswith("NODE_") and getattr(graph, n) == 68] == ["NODE_LWE_LINEAR"]
     assert graph.LWE_LINEAR_SLOTS == G.SLOTS and graph.LWE_LINEAR_GRAPH_MAX_ROWS == G.MAX_ROWS
 
 
@@ -64,7 +65,7 @@ def test_recorded_circuit_records_a_layer_as_m_nodes_over_one_operand_list():
     bits = rec.add_unpack(glwe, 2)                                   # lwe1 nodes one level up
     rows = rec.add_lwe_linear(5, [l1, bits[1], l1], 4)               # lwe1 nodes of any origin; repeats allowed
     assert rows == list(range(bits[-1] + 1, bits[-1] + 5))
-    assert rec.op[rows[0]:] == [LWE_LINEAR_NODE] * 4 and rec.kind[rows[0]:] == [int(ValueKind.LWE1)] * 4
+    assert rec.op[rows[0]:] == [NODE_LWE_LINEAR] * 4 and rec.kind[rows[0]:] == [int(ValueKind.LWE1)] * 4
     assert rec.param[rows[0]:] == [0, 1, 2, 3] and rec.inputs[rows[0]:] == [(l1, bits[1], l1)] * 4
     low = rec.add_lwe_linear(63, [a], 1)                             # one operand, one row, the last slot; lwe0 in, lwe0 out
     assert rec.kind[low[0]] == int(ValueKind.LWE0)
@@ -86,7 +87,7 @@ def test_arrays_carry_the_layer_and_round_trip():
     rec.add_output(rows[0], ValueKind.LWE0)
     arr = rec.arrays()
     at = rows[0]
-    assert list(arr["op"][at:at + 5]) == [LWE_LINEAR_NODE] * 5 and list(arr["n_in"][at:at + 5]) == [0] * 5
+    assert list(arr["op"][at:at + 5]) == [NODE_LWE_LINEAR] * 5 and list(arr["n_in"][at:at + 5]) == [0] * 5
     assert list(arr["n_bits"][at:at + 5]) == [3, 3, 2, 2, 2] and list(arr["param"][at:at + 5]) == [0, 1, 0, 1, 2]
     assert list(arr["lin_slot"][at:at + 5]) == [9, 9, 10, 10, 10] and list(arr["lin_rows"][at:at + 5]) == [2, 2, 3, 3, 3]
     # the operand lists in node order, ONE per layer: [pufks | layer 9 | layer 10 | pack]
@@ -129,7 +130,7 @@ def test_the_builder_of_mux_circuits_passes_the_layer_on():
     from spf_amd.mux_circuits import GraphBuilder
     rec, a, b, l1, _, _ = circuit()
     rows = GraphBuilder(rec).add_lwe_linear(3, [a, b], 2)
-    assert rec.op[rows[0]:] == [LWE_LINEAR_NODE] * 2 and rec._linear[rows[1]] == (3, 2)
+    assert rec.op[rows[0]:] == [NODE_LWE_LINEAR] * 2 and rec._linear[rows[1]] == (3, 2)
 
 
 def test_native_per_operation_drivers_say_that_they_cannot_walk_a_linear_node():
