@@ -28,7 +28,7 @@
 // programmable_bootstrapping.rs:291, 575-621) are rows of the operation table whose LAST operand is the table, a GLWE1 node.  A group
 // whose members all name one table node launches with lut_stride = 0 and copies nothing; otherwise the tables are gathered like any
 // operand.  Bivariate inputs that do not lie consecutively are packed straight from where they lie (lwe_pack_rows_kernel: one launch
-// where two gathers and lwe_pack_kernel were three).  The slack rule below batches each of the two kinds as it batches the circuit
+// where two gathers and lwe_pack_kernel were three).  The slack rule (spf_graph_plan.hpp) batches each of the two kinds as it batches the circuit
 // bootstraps.
 //
 // A public functional keyswitch (`public_functional_keyswitch`, public_functional_keyswitch.rs:74-148, message j to coefficient j)
@@ -44,13 +44,18 @@
 // in place, matrix cores included, anything else is ONE launch of lwe_linear_rows_kernel over a pointer table.  The slot is read
 // when the graph runs: it may be loaded, and loaded again, after the graph is built.
 //
+// What is decided before a device is touched — levels, groups and their order, arena offsets, in place or through a pointer row,
+// the order of the CMUX units, the size of the stage buffers — is spf_graph_plan.hpp's, free of HIP and checked on the CPU; here
+// are the handle, the node constructors with their checks, the device memory of a plan and the launches.
+//
 // Included at the end of spf_hip.hip: uses its `fail` / HIPCHK helpers and the `_dev` entry points.
 #pragma once
+
+#include "spf_graph_plan.hpp"
 
 #include <algorithm>
 #include <cstring>
 #include <map>
-#include <tuple>
 #include <vector>
 
 // host memory the copy engines can reach directly (hipHostMalloc): a copy to or from pageable memory is staged by the runtime
@@ -79,55 +84,15 @@ struct spf_pinned_buf {
     void free_buf() { (void)resize(0); }
 };
 
-struct spf_graph {
-    // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation /
-    // spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear)
-    enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68 };
-    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks || op == kNodeLweLinear; } // operands in pack_in, not in Node::in
-    struct Node {
-        int32_t op;        // spf_graph_op, kNodeUnpack / kNodePack / kNodeRotCmux, or -1 input, -2 trivial constant
-        int32_t kind;      // spf_value_kind of the value the node produces
-        uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node /
-                           // row index m of a linear node
-        uint32_t in[3];    // (rotate-CMUX nodes: {selector, accumulator})
-        uint32_t n_in;
-        uint32_t n_bits;   // unpack and pack nodes: width of the integer; public functional keyswitch nodes: lwe_count; linear nodes: K
-        uint32_t ext;      // pack, public functional keyswitch and linear nodes: their n_bits operands are pack_in[ext ...] (n_in = 0)
-        uint32_t lin_slot, lin_rows; // linear nodes: the weight slot and M (the M nodes of one call share one operand list)
-        uint32_t level;
-        size_t off;        // byte offset of the value in the arena
-        const void* host;  // inputs: caller's buffer, read at every run
-    };
-    struct Group {
-        int32_t op;
-        uint64_t param;    // (unpack and pack groups: n_bits; public functional keyswitch groups: lwe_count | operand kind << 32;
-                           // linear groups: K | M << 32 | slot << 48 | operand kind << 56)
-        std::vector<uint32_t> members;
-        size_t out_off = 0;
-        // per operand slot: offset of the first operand when the members' operands are contiguous
-        // in member order, else index of the slot's pointer row in the table
-        bool contiguous[3] = {false, false, false};
-        size_t first_off[3] = {0, 0, 0};
-        size_t ptr_index[3] = {0, 0, 0};
-        bool one_lut = false; // the bootstraps by table: every member names the same table node (read in place, lut_stride = 0)
-    };
+// the nodes (spf_graph_plan::Graph) and, once planned, their plan (spf_graph_plan::Plan) with its device memory
+struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
     spf_live::Tick<spf_live::GRAPH> live;
     spf_ctx* ctx = nullptr;
     spf_params prm{};
     struct spf_group* grp = nullptr; // a graph of a device group (spf_group_graph_create): placed on a member when it is run
     int member = -1;                 // ... the member its most recent run took place on
-    std::vector<Node> nodes;
-    std::vector<uint32_t> pack_in; // operand lists of the pack, the public functional keyswitch and the linear nodes
-    // f(operand id) for every operand of a node
-    template <class F> void for_operands(const Node& n, F f) const
-    {
-        for (uint32_t i = 0; i < n.n_in; i++) f(n.in[i]);
-        if (has_list(n.op))
-            for (uint32_t i = 0; i < n.n_bits; i++) f(pack_in[n.ext + i]);
-    }
     std::vector<std::pair<uint32_t, void*>> outputs;
     bool planned = false;
-    std::vector<Group> groups;
     spf_pinned_buf h_inputs;
     // outputs leave in ONE device-to-host copy: gathered on the device (one gather_rows launch per value size) into d_out_stage,
     // copied into pinned h_out_stage, handed to the callers' buffers from there
@@ -147,13 +112,11 @@ struct spf_graph {
         out_classes.clear();
         outputs_planned = (size_t)-1;
     }
-    size_t inputs_bytes = 0, arena_bytes = 0, stage_bytes = 0;
-    bool has_pufks = false, pufks_stage = false; // public functional keyswitch nodes: any; planned with room to gather their rows
-    bool has_linear = false;                     // linear nodes: any (their weight slots are checked at every run)
+    bool pufks_stage = false; // planned with room to gather the rows of the public functional keyswitch nodes
     char* d_arena = nullptr;
     char* d_stage[2] = {nullptr, nullptr};
-    void** d_ptrs = nullptr;
-    uint32_t n_levels = 0, n_launches = 0;
+    void** d_ptrs = nullptr; // the plan's table, the arena's base added
+    uint32_t n_launches = 0;
     // hipGraph of the planned launch sequence (everything between the input copy and the output copies; opt-in,
     // SPF_GRAPH_CAPTURE=1): captured on the second run after planning (the first one sizes the context's scratch buffers),
     // replayed afterwards; dropped when the graph is re-planned or a captured scratch buffer moved
@@ -183,283 +146,33 @@ struct spf_graph {
 
 namespace spf_graph_impl {
 
-// the table row (spf_ops.hpp) of a node's operation: a spf_graph_op that spf_graph_add_op has accepted
-inline const spf_ops::OpRow& op_row(int graph_op) { return spf_ops::row(spf_ops::pool_op_of(graph_op)); }
+using namespace spf_graph_plan; // (the node kinds, op_row, align_up, units_per_node)
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Levels, groups, arena layout, pointer table.  Called by the first run after the graph changed.
+// The plan of spf_graph_plan.hpp and its device memory.  Called by the first run after the graph changed.
 inline spf_status plan(spf_graph* g)
 {
     spf_ctx* c = g->ctx;
     g->release();
-    g->groups.clear();
     HIPCHK(c, hipSetDevice(c->device));
-    // inputs and constants first, packed, so one copy brings them up
-    size_t off = 0;
-    for (auto& n : g->nodes)
-        if (n.op < 0) {
-            n.level = 0;
-            n.off = off;
-            off = align_up(off + value_bytes(g->prm, n.kind), 256);
-        }
-    g->inputs_bytes = off;
-    uint32_t max_level = 0;
-    for (auto& n : g->nodes)
-        if (n.op >= 0) {
-            uint32_t lv = 0;
-            g->for_operands(n, [&](uint32_t in) { lv = std::max(lv, g->nodes[in].level); });
-            n.level = lv + 1;
-            max_level = std::max(max_level, n.level);
-        }
-    // A circuit bootstrap launch costs as much as ~150 CMUX levels whatever its width (up to one ciphertext per CU),
-    // and conversions in the middle of a circuit become ready one by one (the 128 partial-product bits of a 32 x 32
-    // multiplication at 32 different depths): batch them.  Within the slack that does not lengthen the graph
-    // (latest level = min over consumers of their latest level - 1), bootstraps are moved to common levels —
-    // repeatedly take the bootstrap that must run soonest and run every bootstrap that is ready by then with it —
-    // and the SampleExtract / KeyswitchL1toL0 nodes feeding them follow.  (Nodes are in topological order: operands
-    // precede their users.)
-    {
-        const size_t nn = g->nodes.size();
-        std::vector<uint32_t> alap(nn, max_level);
-        for (size_t id = nn; id-- > 0;) {
-            const auto& n = g->nodes[id];
-            if (n.op < 0) continue;
-            g->for_operands(n, [&](uint32_t in) {
-                if (g->nodes[in].op >= 0) alap[in] = std::min(alap[in], alap[id] - 1);
-            });
-        }
-        // (the bootstraps by table cost the same blind rotation: each of the three kinds is batched among its own)
-        std::vector<uint32_t> fixed(nn, 0);
-        std::vector<bool> done(nn, false);
-        for (const int32_t kind : {(int32_t)SPF_OP_CIRCUIT_BOOTSTRAP, (int32_t)SPF_OP_PBS_UNIVARIATE, (int32_t)SPF_OP_PBS_BIVARIATE}) {
-            std::vector<uint32_t> cbs;
-            for (uint32_t id = 0; id < nn; id++)
-                if (g->nodes[id].op == kind) cbs.push_back(id);
-            std::sort(cbs.begin(), cbs.end(), [&](uint32_t a, uint32_t b) { return alap[a] != alap[b] ? alap[a] < alap[b] : a < b; });
-            for (uint32_t lead : cbs) {
-                if (done[lead]) continue;
-                const uint32_t t = alap[lead];
-                for (uint32_t id : cbs)
-                    if (!done[id] && g->nodes[id].level <= t) { done[id] = true; fixed[id] = t; }
-            }
-        }
-        // forward again with the chosen bootstrap levels as lower bounds (t <= latest level: depth unchanged)
-        for (size_t id = 0; id < nn; id++) {
-            auto& n = g->nodes[id];
-            if (n.op < 0) continue;
-            uint32_t lv = 0;
-            g->for_operands(n, [&](uint32_t in) { lv = std::max(lv, g->nodes[in].level); });
-            n.level = std::max(lv + 1, fixed[id]);
-        }
-        // pull the conversion chain's head (SampleExtract -> KeyswitchL1toL0) up against its bootstrap
-        std::vector<uint32_t> min_user(nn, 0xffffffffu);
-        for (size_t id = nn; id-- > 0;) {
-            auto& n = g->nodes[id];
-            if (n.op < 0) continue;
-            if ((n.op == SPF_OP_KEYSWITCH_L1_TO_L0 || n.op == SPF_OP_SAMPLE_EXTRACT) && min_user[id] != 0xffffffffu)
-                n.level = std::max(n.level, min_user[id] - 1);
-            g->for_operands(n, [&](uint32_t in) { min_user[in] = std::min(min_user[in], n.level); });
-        }
-    }
-    g->n_levels = max_level;
-    // one group per (level, kind, parameter), members in node order.  Unpack and pack nodes group by their width: the bit
-    // nodes of one spf_graph_add_unpack call have consecutive ids and one level (their source's + 1; nothing below moves
-    // them), so a group's members are whole integers, int-major.  Linear nodes group by (slot, M, K, operand kind): the M nodes of
-    // one spf_graph_add_lwe_linear call have consecutive ids, one operand list and so one level, and nothing above moves them (they
-    // are no bootstrap and no head of a conversion chain), so a group's members are whole layers, layer-major
-    std::map<std::tuple<uint32_t, int32_t, uint64_t>, size_t> index;
-    for (uint32_t id = 0; id < g->nodes.size(); id++) {
-        const auto& n = g->nodes[id];
-        if (n.op < 0) continue;
-        const uint64_t key_param = n.op == spf_graph::kNodeUnpack || n.op == spf_graph::kNodePack ? n.n_bits
-                                   : n.op == spf_graph::kNodePufks ? n.n_bits | (uint64_t)g->nodes[g->pack_in[n.ext]].kind << 32
-                                   : n.op == spf_graph::kNodeLweLinear
-                                       ? n.n_bits | (uint64_t)n.lin_rows << 32 | (uint64_t)n.lin_slot << 48 | (uint64_t)n.kind << 56
-                                       : n.param;
-        auto key = std::make_tuple(n.level, n.op, key_param);
-        auto it = index.find(key);
-        if (it == index.end()) {
-            it = index.emplace(key, g->groups.size()).first;
-            g->groups.emplace_back();
-            g->groups.back().op = n.op;
-            g->groups.back().param = key_param;
-        }
-        g->groups[it->second].members.push_back(id);
-    }
-    // std::map iterates by level first: order the groups the same way
-    {
-        std::vector<spf_graph::Group> ordered;
-        ordered.reserve(g->groups.size());
-        for (auto& kv : index) ordered.push_back(std::move(g->groups[kv.second]));
-        g->groups.swap(ordered);
-    }
-    // outputs of a group are consecutive rows
-    size_t stage = 0;
-    for (auto& gr : g->groups) {
-        const size_t ob = value_bytes(g->prm, g->nodes[gr.members[0]].kind);
-        gr.out_off = off;
-        for (size_t i = 0; i < gr.members.size(); i++) g->nodes[gr.members[i]].off = off + i * ob;
-        off = align_up(off + gr.members.size() * ob, 256);
-    }
-    g->arena_bytes = off;
-    HIPCHK(c, hipMalloc((void**)&g->d_arena, std::max<size_t>(g->arena_bytes, 256)));
-    // operand access per group
-    std::vector<void*> table;
-    g->has_pufks = false;
-    g->has_linear = false;
     g->pufks_stage = !pufks_tuned(c) || pufks_rows_gather(); // (also while no key is loaded: the key that comes may be of any radix)
-    for (auto& gr : g->groups) {
-        const size_t B = gr.members.size();
-        if (gr.op == spf_graph::kNodePufks) {
-            // the rows of every output, output-major: in place when they lie consecutively; else read through the table by the
-            // pre-pass of the hand-written radices, or gathered for generic_pufks_kernel
-            g->has_pufks = true;
-            const size_t rb = value_bytes(g->prm, (int)(gr.param >> 32));
-            std::vector<size_t> offs;
-            for (uint32_t id : gr.members)
-                g->for_operands(g->nodes[id], [&](uint32_t in) { offs.push_back(g->nodes[in].off); });
-            bool contig = true;
-            for (size_t i = 1; i < offs.size() && contig; i++) contig = offs[i] == offs[0] + i * rb;
-            gr.contiguous[0] = contig;
-            gr.first_off[0] = offs[0];
-            if (!contig) {
-                gr.ptr_index[0] = table.size();
-                for (size_t o : offs) table.push_back(g->d_arena + o);
-                if (g->pufks_stage) stage = std::max(stage, offs.size() * rb);
-            }
-            continue;
-        }
-        if (gr.op == spf_graph::kNodeLweLinear) {
-            // the K rows of every layer, layer-major (every M-th member starts a layer): in place when all of them lie consecutively
-            // (the batch dispatcher, matrix cores included), else read through the table by lwe_linear_rows_kernel
-            g->has_linear = true;
-            const size_t M = (size_t)(gr.param >> 32 & 0xffff), rb = value_bytes(g->prm, (int)(gr.param >> 56));
-            std::vector<size_t> offs;
-            for (size_t i = 0; i < B; i += M)
-                g->for_operands(g->nodes[gr.members[i]], [&](uint32_t in) { offs.push_back(g->nodes[in].off); });
-            bool contig = true;
-            for (size_t i = 1; i < offs.size() && contig; i++) contig = offs[i] == offs[0] + i * rb;
-            gr.contiguous[0] = contig;
-            gr.first_off[0] = offs[0];
-            if (!contig) {
-                gr.ptr_index[0] = table.size();
-                for (size_t o : offs) table.push_back(g->d_arena + o);
-            }
-            continue;
-        }
-        if (gr.op == spf_graph::kNodePack) {
-            // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table
-            gr.ptr_index[0] = table.size();
-            for (uint32_t id : gr.members)
-                g->for_operands(g->nodes[id], [&](uint32_t in) { table.push_back(g->d_arena + g->nodes[in].off); });
-            continue;
-        }
-        if (gr.op == spf_graph::kNodeUnpack) {
-            // one source GLWE per integer (every n_bits-th member): in place when they are consecutive, else gathered
-            const size_t ints = B / gr.param, ib = value_bytes(g->prm, SPF_VAL_GLWE1);
-            auto src = [&](size_t m) { return g->nodes[g->nodes[gr.members[m * gr.param]].in[0]].off; };
-            bool contig = true;
-            for (size_t m = 1; m < ints && contig; m++) contig = src(m) == src(0) + m * ib;
-            gr.contiguous[0] = contig;
-            gr.first_off[0] = src(0);
-            if (!contig) {
-                gr.ptr_index[0] = table.size();
-                for (size_t m = 0; m < ints; m++) table.push_back(g->d_arena + src(m));
-                stage = std::max(stage, ints * ib);
-            }
-            continue;
-        }
-        if (gr.op == spf_graph::kNodeRotCmux) {
-            // units {selector, accumulator, unused (the high operand is a rotated read of the accumulator), out}; units of one
-            // selector next to each other, as below
-            gr.ptr_index[0] = table.size();
-            struct Unit { void* p[4]; };
-            std::vector<Unit> units;
-            units.reserve(B);
-            for (uint32_t id : gr.members) {
-                const auto& n = g->nodes[id];
-                units.push_back(Unit{{g->d_arena + g->nodes[n.in[0]].off, g->d_arena + g->nodes[n.in[1]].off, nullptr, g->d_arena + n.off}});
-            }
-            std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.p[0] < y.p[0]; });
-            for (const Unit& u : units) for (void* q : u.p) table.push_back(q);
-            continue;
-        }
-        const spf_ops::OpRow& info = op_row(gr.op);
-        if (info.cmux_family) {
-            // units: one per GLWE pair; {selector, low (a), high (b), out}
-            const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
-            const size_t gw = value_bytes(g->prm, SPF_VAL_GLWE1);
-            gr.ptr_index[0] = table.size();
-            struct Unit { void* p[4]; };
-            std::vector<Unit> units;
-            units.reserve(B * per);
-            for (size_t i = 0; i < B; i++) {
-                const auto& n = g->nodes[gr.members[i]];
-                for (size_t j = 0; j < per; j++) {
-                    Unit u;
-                    u.p[0] = g->d_arena + g->nodes[n.in[0]].off;
-                    if (gr.op == SPF_OP_MULTIPLY_GGSW_GLWE) {
-                        u.p[1] = nullptr; // zero ciphertext
-                        u.p[2] = g->d_arena + g->nodes[n.in[1]].off;
-                    } else {
-                        u.p[1] = g->d_arena + g->nodes[n.in[1]].off + j * gw;
-                        u.p[2] = g->d_arena + g->nodes[n.in[2]].off + j * gw;
-                    }
-                    u.p[3] = g->d_arena + n.off + j * gw;
-                    units.push_back(u);
-                }
-            }
-            // Units that select on the same GGSW go next to each other: a level of a mux_circuits block tests ONE
-            // variable (MuxCircuit::from(&[Bdd]), lib.rs:358-445), so a wide level is a handful of selectors with
-            // dozens of gates each, and neighbouring workgroups then hit the same 256 KiB in L2 (the streaming kernel
-            // does 17.3 M gates/s on four units per selector against 12.9 M/s on distinct ones).  Order inside a
-            // level is free: every unit carries its own output pointer.
-            std::stable_sort(units.begin(), units.end(), [](const Unit& x, const Unit& y) { return x.p[0] < y.p[0]; });
-            for (const Unit& u : units) for (void* q : u.p) table.push_back(q);
-            continue;
-        }
-        const bool by_table = gr.op == SPF_OP_PBS_UNIVARIATE || gr.op == SPF_OP_PBS_BIVARIATE;
-        for (int s = 0; s < info.arity; s++) {
-            const size_t ib = value_bytes(g->prm, info.in_kind[s]);
-            bool contig = true;
-            const size_t first = g->nodes[g->nodes[gr.members[0]].in[s]].off;
-            for (size_t i = 1; i < B && contig; i++)
-                contig = g->nodes[g->nodes[gr.members[i]].in[s]].off == first + i * ib;
-            gr.contiguous[s] = contig;
-            gr.first_off[s] = first;
-        }
-        if (by_table) { // one table node for the whole group: read in place with lut_stride = 0 (B = 1 included)
-            const int s = info.arity - 1;
-            gr.one_lut = true;
-            for (size_t i = 1; i < B && gr.one_lut; i++) gr.one_lut = g->nodes[gr.members[i]].in[s] == g->nodes[gr.members[0]].in[s];
-            if (gr.one_lut) gr.contiguous[s] = true;
-        }
-        // bivariate inputs: one of them scattered -> both are read through their pointer rows by lwe_pack_rows_kernel, which
-        // writes the packed rows into the stage buffer
-        if (gr.op == SPF_OP_PBS_BIVARIATE && !(gr.contiguous[0] && gr.contiguous[1])) gr.contiguous[0] = gr.contiguous[1] = false;
-        for (int s = 0; s < info.arity; s++) {
-            const size_t ib = value_bytes(g->prm, info.in_kind[s]);
-            if (!gr.contiguous[s]) {
-                gr.ptr_index[s] = table.size();
-                for (size_t i = 0; i < B; i++) table.push_back(g->d_arena + g->nodes[g->nodes[gr.members[i]].in[s]].off);
-                stage = std::max(stage, B * ib);
-            }
-        }
+    static_cast<Plan&>(*g) = spf_graph_plan::plan(*g, sizes_of(g->prm, g->pufks_stage));
+    HIPCHK(c, hipMalloc((void**)&g->d_arena, std::max<size_t>(g->arena_bytes, 256)));
+    if (g->stage_bytes) {
+        HIPCHK(c, hipMalloc((void**)&g->d_stage[0], g->stage_bytes));
+        HIPCHK(c, hipMalloc((void**)&g->d_stage[1], g->stage_bytes));
     }
-    g->stage_bytes = stage;
-    if (stage) {
-        HIPCHK(c, hipMalloc((void**)&g->d_stage[0], stage));
-        HIPCHK(c, hipMalloc((void**)&g->d_stage[1], stage));
-    }
-    if (!table.empty()) {
-        HIPCHK(c, hipMalloc((void**)&g->d_ptrs, table.size() * sizeof(void*)));
-        HIPCHK(c, hipMemcpy(g->d_ptrs, table.data(), table.size() * sizeof(void*), hipMemcpyHostToDevice));
+    if (!g->table.empty()) {
+        // offsets become addresses where they stand (a table of the four-multiplication graph is 16 MB: no second copy of it)
+        static_assert(sizeof(size_t) == sizeof(void*), "the table is converted in place");
+        for (size_t& t : g->table) t = t == kNull ? 0 : reinterpret_cast<size_t>(g->d_arena + t);
+        HIPCHK(c, hipMalloc((void**)&g->d_ptrs, g->table.size() * sizeof(void*)));
+        HIPCHK(c, hipMemcpy(g->d_ptrs, g->table.data(), g->table.size() * sizeof(void*), hipMemcpyHostToDevice));
+        std::vector<size_t>().swap(g->table); // (it lives on the device from here)
     }
     if (getenv("SPF_GRAPH_WIDTHS")) { // diagnostic: CMUX-family launch widths (units) of the plan
         std::map<size_t, size_t> hist;
         for (auto& gr : g->groups)
-            if (gr.op < spf_graph::kNodeUnpack && op_row(gr.op).cmux_family) hist[gr.members.size() * (gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1)]++;
+            if (gr.key.op < kNodeUnpack && op_row(gr.key.op).cmux_family) hist[gr.members.size() * units_per_node(gr.key.op, g->prm.cbs_radix_count)]++;
         for (auto& kv : hist) fprintf(stderr, "[graph widths] %zu units x %zu launches\n", kv.first, kv.second);
     }
     if (!g->h_inputs.resize(g->inputs_bytes)) return fail(c, SPF_ERR_HIP, "graph: out of host memory for the inputs");
@@ -481,9 +194,9 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
     g->n_launches = 0;
     // the public functional keyswitch key comes with its own shape: checked against the nodes before anything is enqueued
     for (const auto& gr : g->groups)
-        if (gr.op == spf_graph::kNodePufks) {
+        if (gr.key.op == spf_graph_plan::kNodePufks) {
             if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "graph: public functional keyswitch key not loaded");
-            const int kind = (int)(gr.param >> 32);
+            const int kind = gr.key.kind;
             const size_t dim = value_bytes(g->prm, kind) / 8 - 1;
             if (c->pufks_n != dim)
                 return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: the public functional keyswitch key's from_dimension " + std::to_string(c->pufks_n) +
@@ -493,8 +206,8 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
     for (const auto& gr : g->groups) {
         const size_t B = gr.members.size();
         char* out = g->d_arena + gr.out_off;
-        if (gr.op == spf_graph::kNodePufks) {
-            const size_t p = (size_t)(gr.param & 0xffffffffu);
+        if (gr.key.op == spf_graph_plan::kNodePufks) {
+            const size_t p = (size_t)gr.key.n;
             spf_status st;
             if (gr.contiguous[0]) {
                 st = spf_public_functional_keyswitch_enqueue(c, s, B, p, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
@@ -506,10 +219,10 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
             if (st != SPF_OK) return st;
             continue;
         }
-        if (gr.op == spf_graph::kNodeLweLinear) {
-            const size_t M = (size_t)(gr.param >> 32 & 0xffff);
-            const uint32_t slot = (uint32_t)(gr.param >> 48 & 0xff);
-            const spf_value_kind kind = (spf_value_kind)(gr.param >> 56);
+        if (gr.key.op == spf_graph_plan::kNodeLweLinear) {
+            const size_t M = gr.key.rows;
+            const uint32_t slot = gr.key.slot;
+            const spf_value_kind kind = (spf_value_kind)gr.key.kind;
             spf_status st;
             if (gr.contiguous[0]) {
                 st = spf_lwe_linear_enqueue(c, s, slot, kind, B / M, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
@@ -521,14 +234,14 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
             if (st != SPF_OK) return st;
             continue;
         }
-        if (gr.op == spf_graph::kNodePack) {
-            spf_status st = launch_glwe_pack_rows(c, s, B, gr.param, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
+        if (gr.key.op == spf_graph_plan::kNodePack) {
+            spf_status st = launch_glwe_pack_rows(c, s, B, gr.key.n, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
         }
-        if (gr.op == spf_graph::kNodeUnpack) {
-            const size_t ints = B / gr.param;
+        if (gr.key.op == spf_graph_plan::kNodeUnpack) {
+            const size_t ints = B / gr.key.n;
             const uint64_t* src = (const uint64_t*)(g->d_arena + gr.first_off[0]);
             if (!gr.contiguous[0]) {
                 spf_status st = spf_gather_rows_dev(c, s, ints, value_bytes(g->prm, SPF_VAL_GLWE1) / 8,
@@ -537,21 +250,20 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                 g->n_launches++;
                 src = (const uint64_t*)g->d_stage[0];
             }
-            spf_status st = launch_glwe_unpack(c, s, ints, gr.param, src, (uint64_t*)out);
+            spf_status st = launch_glwe_unpack(c, s, ints, gr.key.n, src, (uint64_t*)out);
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
         }
-        if (gr.op == spf_graph::kNodeRotCmux) {
-            spf_status st = launch_cmux_rot_scattered(c, s, B, (uint32_t)gr.param, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
+        if (gr.key.op == spf_graph_plan::kNodeRotCmux) {
+            spf_status st = launch_cmux_rot_scattered(c, s, B, (uint32_t)gr.key.n, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
         }
-        const spf_ops::OpRow& info = op_row(gr.op);
+        const spf_ops::OpRow& info = op_row(gr.key.op);
         if (info.cmux_family) {
-            const size_t per = gr.op == SPF_OP_GLEV_CMUX ? g->prm.cbs_radix_count : 1;
-            spf_status st = spf_cmux_scattered_dev(c, s, B * per, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
+            spf_status st = spf_cmux_scattered_dev(c, s, B * units_per_node(gr.key.op, g->prm.cbs_radix_count), (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
@@ -559,10 +271,10 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
         const void* in[3] = {nullptr, nullptr, nullptr};
         // (stage buffers: the table of a bootstrap by table goes to the second one, its LWE rows — gathered, or packed from where
         // they lie — to the first)
-        const bool pack_rows = gr.op == SPF_OP_PBS_BIVARIATE && !gr.contiguous[0];
+        const bool pack_rows = gr.key.op == SPF_OP_PBS_BIVARIATE && !gr.contiguous[0];
         if (pack_rows) {
             spf_status st = launch_lwe_pack_rows(c, s, B, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]),
-                                                 (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[1]), (uint32_t)gr.param, (uint64_t*)g->d_stage[0]);
+                                                 (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[1]), (uint32_t)gr.key.n, (uint64_t*)g->d_stage[0]);
             if (st != SPF_OK) return st;
             g->n_launches++;
             const void* lut = g->d_arena + gr.first_off[2];
@@ -592,9 +304,9 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                 in[sl] = stage_sl;
             }
         }
-        const spf_status st = spf_ops::launch_op(c, s, info.op, B, in, out, gr.param, nullptr, 0, nullptr, gr.one_lut);
+        const spf_status st = spf_ops::launch_op(c, s, info.op, B, in, out, gr.key.n, nullptr, 0, nullptr, gr.one_lut);
         if (st != SPF_OK) return st;
-        g->n_launches += gr.op == SPF_OP_PBS_BIVARIATE ? 2 : 1; // (contiguous bivariate inputs: lwe_pack_kernel, then the bootstrap)
+        g->n_launches += gr.key.op == SPF_OP_PBS_BIVARIATE ? 2 : 1; // (contiguous bivariate inputs: lwe_pack_kernel, then the bootstrap)
     }
     return SPF_OK;
 }
@@ -605,9 +317,9 @@ inline spf_status check_linear_slots(spf_graph* g)
 {
     spf_ctx* c = g->ctx;
     for (const auto& gr : g->groups)
-        if (gr.op == spf_graph::kNodeLweLinear) {
-            const size_t K = (size_t)(gr.param & 0xffffffffu), M = (size_t)(gr.param >> 32 & 0xffff);
-            const uint32_t slot = (uint32_t)(gr.param >> 48 & 0xff);
+        if (gr.key.op == spf_graph_plan::kNodeLweLinear) {
+            const size_t K = (size_t)gr.key.n, M = gr.key.rows;
+            const uint32_t slot = gr.key.slot;
             const LweLinearSlot& l = c->lin[slot];
             if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no weights loaded in slot " + std::to_string(slot));
             if (l.M != M || l.K != K)
@@ -788,10 +500,9 @@ spf_status spf_graph_add_input(spf_graph* g, spf_value_kind kind, const void* ho
 {
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
     if (!host || !node || value_bytes(g->prm, kind) == 0) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph input: bad kind or null pointer");
-    spf_graph::Node n{};
+    spf_graph_plan::Node n{};
     n.op = -1; n.kind = kind; n.host = host;
-    *node = (uint32_t)g->nodes.size();
-    g->nodes.push_back(n);
+    *node = g->add(n);
     g->planned = false;
     return SPF_OK;
 }
@@ -801,10 +512,9 @@ spf_status spf_graph_add_trivial(spf_graph* g, spf_value_kind kind, uint64_t bit
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
     if (!node || value_bytes(g->prm, kind) == 0 || bit > 1)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph constant: LWE0 / LWE1 / GLWE1 / GGSW1 / GLEV1 of bit 0 or 1");
-    spf_graph::Node n{};
+    spf_graph_plan::Node n{};
     n.op = -2; n.kind = kind; n.param = bit;
-    *node = (uint32_t)g->nodes.size();
-    g->nodes.push_back(n);
+    *node = g->add(n);
     g->planned = false;
     return SPF_OK;
 }
@@ -820,7 +530,7 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
     const spf_ops::OpRow& info = spf_ops::row(pop);
     if (n_inputs != (size_t)info.arity || (n_inputs && !inputs))
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: wrong number of operands");
-    spf_graph::Node n{};
+    spf_graph_plan::Node n{};
     n.op = op; n.kind = info.out_kind; n.n_in = (uint32_t)info.arity;
     for (int i = 0; i < info.arity; i++) {
         if (inputs[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: operand is not a node of this graph");
@@ -830,8 +540,7 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
     const char* why = nullptr;
     if (spf_ops::op_param(g->prm, pop, &param, &why) != SPF_OK) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph op: ") + why);
     n.param = param;
-    *node = (uint32_t)g->nodes.size();
-    g->nodes.push_back(n);
+    *node = g->add(n);
     g->planned = false;
     return SPF_OK;
 }
@@ -845,19 +554,15 @@ spf_status spf_graph_add_unpack(spf_graph* g, uint32_t glwe_node, size_t n_bits,
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: n_bits must be in 1 ..= polynomial_degree");
     if (glwe_node >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not a node of this graph");
     if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not an L1 GLWE");
-    spf_graph::Node n{};
-    n.op = spf_graph::kNodeUnpack; n.kind = SPF_VAL_LWE1; n.n_in = 1; n.in[0] = glwe_node; n.n_bits = (uint32_t)n_bits;
-    const uint32_t first = (uint32_t)g->nodes.size();
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodeUnpack; n.kind = SPF_VAL_LWE1; n.n_in = 1; n.in[0] = glwe_node; n.count = (uint32_t)n_bits;
+    uint32_t first;
     try {
-        g->nodes.reserve(g->nodes.size() + n_bits); // all of the integer's nodes or none
+        first = g->add_numbered(n, n_bits); // all of the integer's nodes or none
     } catch (const std::exception&) {
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
-    for (size_t i = 0; i < n_bits; i++) {
-        n.param = i;
-        g->nodes.push_back(n);
-        nodes_out[i] = first + (uint32_t)i;
-    }
+    for (size_t i = 0; i < n_bits; i++) nodes_out[i] = first + (uint32_t)i;
     g->planned = false;
     return SPF_OK;
 }
@@ -873,16 +578,13 @@ spf_status spf_graph_add_pack(spf_graph* g, const uint32_t* nodes, size_t n_bits
         if (nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not a node of this graph");
         if (g->nodes[nodes[i]].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not an L1 GLWE");
     }
-    spf_graph::Node n{};
-    n.op = spf_graph::kNodePack; n.kind = SPF_VAL_GLWE1; n.n_bits = (uint32_t)n_bits; n.ext = (uint32_t)g->pack_in.size();
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodePack; n.kind = SPF_VAL_GLWE1;
     try {
-        g->pack_in.insert(g->pack_in.end(), nodes, nodes + n_bits);
-        g->nodes.push_back(n);
+        *node_out = g->add_listed(n, nodes, n_bits);
     } catch (const std::exception&) {
-        g->pack_in.resize(n.ext);
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
-    *node_out = (uint32_t)g->nodes.size() - 1;
     g->planned = false;
     return SPF_OK;
 }
@@ -904,16 +606,13 @@ spf_status spf_graph_add_public_functional_keyswitch(spf_graph* g, const uint32_
         if (kind != g->nodes[lwe_nodes[0]].kind)
             return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: lwe0 and lwe1 operands mixed");
     }
-    spf_graph::Node n{};
-    n.op = spf_graph::kNodePufks; n.kind = SPF_VAL_GLWE1; n.n_bits = (uint32_t)lwe_count; n.ext = (uint32_t)g->pack_in.size();
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodePufks; n.kind = SPF_VAL_GLWE1;
     try {
-        g->pack_in.insert(g->pack_in.end(), lwe_nodes, lwe_nodes + lwe_count);
-        g->nodes.push_back(n);
+        *node_out = g->add_listed(n, lwe_nodes, lwe_count);
     } catch (const std::exception&) {
-        g->pack_in.resize(n.ext);
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
-    *node_out = (uint32_t)g->nodes.size() - 1;
     g->planned = false;
     return SPF_OK;
 }
@@ -938,22 +637,16 @@ spf_status spf_graph_add_lwe_linear(spf_graph* g, uint32_t slot, const uint32_t*
         if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: operand is not an LWE");
         if (kind != g->nodes[lwe_nodes[0]].kind) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: lwe0 and lwe1 operands mixed");
     }
-    spf_graph::Node n{};
-    n.op = spf_graph::kNodeLweLinear; n.kind = g->nodes[lwe_nodes[0]].kind; n.n_bits = (uint32_t)K; n.ext = (uint32_t)g->pack_in.size();
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodeLweLinear; n.kind = g->nodes[lwe_nodes[0]].kind;
     n.lin_slot = slot; n.lin_rows = (uint32_t)M;
-    const uint32_t first = (uint32_t)g->nodes.size();
+    uint32_t first;
     try {
-        g->nodes.reserve(g->nodes.size() + M); // all of the layer's nodes or none
-        g->pack_in.insert(g->pack_in.end(), lwe_nodes, lwe_nodes + K);
+        first = g->add_listed(n, lwe_nodes, K, M); // all of the layer's nodes or none
     } catch (const std::exception&) {
-        g->pack_in.resize(n.ext);
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
-    for (size_t m = 0; m < M; m++) {
-        n.param = m;
-        g->nodes.push_back(n);
-        nodes_out[m] = first + (uint32_t)m;
-    }
+    for (size_t m = 0; m < M; m++) nodes_out[m] = first + (uint32_t)m;
     g->planned = false;
     return SPF_OK;
 }
@@ -980,13 +673,12 @@ spf_status spf_graph_add_blind_rotation(spf_graph* g, uint32_t glwe_node, const 
     } catch (const std::exception&) {
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }
-    spf_graph::Node n{};
-    n.op = spf_graph::kNodeRotCmux; n.kind = SPF_VAL_GLWE1; n.n_in = 2;
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodeRotCmux; n.kind = SPF_VAL_GLWE1; n.n_in = 2;
     uint32_t acc = glwe_node;
     for (size_t i = 0; i < n_bits; i++) {
         n.in[0] = shift_nodes[i]; n.in[1] = acc; n.param = (uint64_t)1 << (i + log_stride);
-        acc = (uint32_t)g->nodes.size();
-        g->nodes.push_back(n);
+        acc = g->add(n);
     }
     *node_out = acc;
     g->planned = false;

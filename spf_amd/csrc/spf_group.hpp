@@ -976,13 +976,7 @@ spf_status merge_jobs(spf_ctx* c, const std::vector<spf_graph*>& jobs, spf_graph
     if (st != SPF_OK) return st;
     try {
         for (const spf_graph* j : jobs) {
-            const uint32_t base = (uint32_t)m->nodes.size(), ext_base = (uint32_t)m->pack_in.size();
-            for (spf_graph::Node n : j->nodes) {
-                for (uint32_t i = 0; i < n.n_in; i++) n.in[i] += base;
-                if (spf_graph::has_list(n.op)) n.ext += ext_base; // (the operand lists of pack and public functional keyswitch nodes move with them)
-                m->nodes.push_back(n);
-            }
-            for (uint32_t in : j->pack_in) m->pack_in.push_back(in + base);
+            const uint32_t base = m->append(*j);
             for (const auto& o : j->outputs) m->outputs.emplace_back(o.first + base, o.second);
         }
     } catch (const std::exception&) {

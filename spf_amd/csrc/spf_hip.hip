@@ -265,7 +265,8 @@ spf_status ensure(spf_ctx* c, DevBuf& b, size_t bytes)
 
 } // namespace
 
-#include "spf_ops.hpp" // ciphertext sizes, the operation table, the parameter rule, the dispatcher: where an operation is declared
+#include "spf_ops.hpp" // ciphertext sizes, the operation table, the parameter rule: where an operation is declared
+#include "spf_ops_launch.hpp" // ... and its dispatcher
 
 namespace {
 

@@ -138,7 +138,7 @@ def evaluate(rec, P, keys: Keys, hosts=None):
 
 
 def planned_levels(rec):
-    """the level of every node as plan() chooses it (spf_graph.hpp): as soon as possible; the three bootstrap kinds moved to common
+    """the level of every node as the planner chooses it (spf_graph_plan.hpp, assign_levels): as soon as possible; the three bootstrap kinds moved to common
     levels within their slack; SampleExtract and KeyswitchL1toL0 pulled up against their first user.  Inputs and constants: 0"""
     n = len(rec.op)
     level = [0] * n

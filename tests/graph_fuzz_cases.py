@@ -123,7 +123,8 @@ def refill_inputs(rec, P, seed):
 
 
 def group_key(rec, levels, i):
-    """(level, kind, parameter) as plan() keys its groups"""
+    """(level, kind, parameter) in the order the planner keys its groups (spf_graph_plan.hpp's GroupKey has named fields; this
+    packed number is the independent statement of their order: tests/test_graph_plan.py)"""
     op = rec.op[i]
     if op == NODE_UNPACK:
         return levels[i], op, rec._unpack_width[i]

@@ -545,8 +545,8 @@ bool graph_ops_match_the_header(spf_ctx* c)
                 ok = false;
             }
         expect("pack, N rows", -1, spf_graph_add_pack(g, rows.data(), N, &node), SPF_OK, nullptr);
-        if (ok && (node + 1 != g->nodes.size() || g->nodes[node].kind != SPF_VAL_GLWE1 || g->nodes[node].n_bits != N ||
-                   g->pack_in.size() != N || g->nodes[node].ext != 0)) {
+        if (ok && (node + 1 != g->nodes.size() || g->nodes[node].kind != SPF_VAL_GLWE1 || g->nodes[node].count != N ||
+                   g->listed_operands() != N || g->nodes[node].list_at != 0)) {
             fprintf(stderr, "spf_graph_add_pack: the node does not keep its %" PRIu64 " operands\n", N);
             ok = false;
         }
@@ -571,7 +571,7 @@ bool graph_ops_match_the_header(spf_ctx* c)
         expect("pack, null rows", -1, spf_graph_add_pack(g, nullptr, 1, &node), SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
         expect("pack, null out", -1, spf_graph_add_pack(g, rows.data(), 1, nullptr), SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
         expect("pack, null graph", -1, spf_graph_add_pack(nullptr, rows.data(), 1, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
-        if (g->nodes.size() != n_nodes || g->pack_in.size() != N) { fprintf(stderr, "a refused unpack or pack left a node\n"); ok = false; }
+        if (g->nodes.size() != n_nodes || g->listed_operands() != N) { fprintf(stderr, "a refused unpack or pack left a node\n"); ok = false; }
     }
     g->nodes.clear(); // (nothing was planned: no device memory to give back)
     delete g;
