@@ -394,6 +394,16 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_lwe_linear(g_, slot, lwes.data(), lwes.size(), M, rows.data()), ctx_);
         return rows;
     }
+    // The plaintext polynomial linear map of polynomial weight slot `slot` (Evaluation::load_glwe_poly_weights) as nodes — no FheOp
+    // in the reference: M GLWE1 nodes, node m = sum over k of w[m][k] * glwes[k] in Z_2^64[X]/(X^N + 1) (+ bias[m] on the body), the
+    // GLWE1 nodes `glwes` from anywhere in the graph.  A packed integer shifted and added to another before it is unpacked, a table
+    // that is a plaintext polynomial times an encrypted GLWE.  The slot is read by run(); M and the operand count are checked there
+    std::vector<Node> glwe_poly_linear(uint32_t slot, const std::vector<Node>& glwes, size_t M)
+    {
+        std::vector<Node> rows(M ? M : 1); // (M = 0 is refused by the library: a place for it to leave untouched)
+        Evaluation::check(spf_graph_add_glwe_poly_linear(g_, slot, glwes.data(), glwes.size(), M, rows.data()), ctx_);
+        return rows;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }

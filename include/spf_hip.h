@@ -812,6 +812,24 @@ typedef enum spf_graph_lwe_linear_limits { SPF_GRAPH_LWE_LINEAR_MAX_ROWS = 4096 
 spf_status spf_lwe_linear_slot_shape(spf_ctx *ctx, uint32_t slot, size_t *M, size_t *K, int *has_bias);
 spf_status spf_graph_add_lwe_linear(spf_graph *graph, uint32_t slot, const uint32_t *lwe_nodes /* K */, size_t K,
                                     size_t M, uint32_t *nodes_out /* M */);
+/* The plaintext polynomial linear map of polynomial weight slot `slot` (spf_load_glwe_poly_weights above) as a node constructor —
+ * no FheOp there, no spf_graph_op here: a packed integer out of spf_graph_add_public_functional_keyswitch shifted and added to
+ * another one before spf_graph_add_unpack, a lookup table that is a plaintext polynomial times an encrypted GLWE.
+ * glwe_nodes[0 .. K) are glwe1 nodes of any origin and level (inputs, trivials, packs, CMUX and blind rotation results, results
+ * of another such node; repeats allowed, within one list and across lists); creates M glwe1 nodes, all one level above the highest
+ * operand, nodes_out[m] word-equal to row m of spf_glwe_poly_linear_batch(slot, B = 1) over those K GLWEs in that order, bias
+ * included.  The new nodes are ordinary: operands of any operation, outputs, counted by spf_graph_stats.  All layers of one level
+ * with one (slot, M, K) are one group and ONE launch: operands that lie consecutively in the graph's memory go to the kernels of
+ * spf_glwe_poly_linear_enqueue in place, anything else to "glwe_poly_lds_rows_kernel" (or, on a constants-only slot,
+ * "glwe_poly_stream_rows_kernel"; SPF_GLWE_POLY_PATH=lds forces the former), which read the GLWEs where they lie — the names
+ * spf_last_glwe_poly_kernel then gives; timed as "glwe_poly_linear".  A wrong argument (a null pointer, slot >=
+ * SPF_GLWE_POLY_SLOTS, K = 0 or K > 2^32 - 1, M = 0 or M > SPF_GLWE_POLY_MAX_ROWS, a node that does not exist or is no glwe1) is
+ * SPF_ERR_INVALID_ARGUMENT from the call, nothing is recorded and the graph stays usable.  The slot is read by spf_graph_run — it
+ * may be loaded after the graph is built, and loaded again between runs under the rule of the key loads (the next run uses the
+ * new weights; a graph of a group reads the slot of the member it runs on): before anything is enqueued, an empty slot is
+ * SPF_ERR_NO_KEY and a slot whose (M, K) is not the nodes' is SPF_ERR_INVALID_ARGUMENT with both shapes in the message. */
+spf_status spf_graph_add_glwe_poly_linear(spf_graph *graph, uint32_t slot, const uint32_t *glwe_nodes /* K */, size_t K,
+                                          size_t M, uint32_t *nodes_out /* M */);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */

@@ -44,6 +44,13 @@
 // in place, matrix cores included, anything else is ONE launch of lwe_linear_rows_kernel over a pointer table.  The slot is read
 // when the graph runs: it may be loaded, and loaded again, after the graph is built.
 //
+// A plaintext polynomial linear map over GLWE ciphertexts (spf_glwe_poly.hpp) is a sixth constructor, the same way:
+// spf_graph_add_glwe_poly_linear makes the M rows of polynomial weight slot `slot` times K GLWE1 nodes from anywhere — a packed
+// integer shifted and added to another one before it is unpacked, a lookup table that is a plaintext polynomial times an
+// encrypted GLWE.  All layers of one level with one (slot, M, K) are one group whose output is [layers][M][(k+1) N]; operand GLWEs
+// that lie consecutively go to the batch kernels in place, anything else is ONE launch of glwe_poly_lds_rows_kernel or
+// glwe_poly_stream_rows_kernel over a pointer table.  The slot is read when the graph runs, as a linear node's.
+//
 // What is decided before a device is touched — levels, groups and their order, arena offsets, in place or through a pointer row,
 // the order of the CMUX units, the size of the stage buffers — is spf_graph_plan.hpp's, free of HIP and checked on the CPU; here
 // are the handle, the node constructors with their checks, the device memory of a plan and the launches.
@@ -122,6 +129,7 @@ struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
     // replayed afterwards; dropped when the graph is re-planned or a captured scratch buffer moved
     hipGraphExec_t exec = nullptr;
     uint64_t exec_epoch = 0, exec_lin_epoch = 0; // (the second: the context's count of weight loads, for a graph with linear nodes)
+    uint64_t exec_gpoly_epoch = 0;               // (its count of polynomial weight loads, for a graph with polynomial linear nodes)
     uint32_t runs_since_plan = 0, captured_launches = 0;
 
     void drop_exec()
@@ -234,6 +242,16 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
             if (st != SPF_OK) return st;
             continue;
         }
+        if (gr.key.op == spf_graph_plan::kNodeGlwePolyLinear) { // (one launch either way)
+            const size_t layers = B / gr.key.rows;
+            const spf_status st = gr.contiguous[0]
+                                      ? spf_glwe_poly_linear_enqueue(c, s, gr.key.slot, layers, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out)
+                                      : launch_glwe_poly_rows(c, s, gr.key.slot, layers, g->d_arena,
+                                                              (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
         if (gr.key.op == spf_graph_plan::kNodePack) {
             spf_status st = launch_glwe_pack_rows(c, s, B, gr.key.n, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
             if (st != SPF_OK) return st;
@@ -330,6 +348,24 @@ inline spf_status check_linear_slots(spf_graph* g)
     return SPF_OK;
 }
 
+// ... and the polynomial weight slots of the polynomial linear groups, the same way
+inline spf_status check_glwe_poly_slots(spf_graph* g)
+{
+    spf_ctx* c = g->ctx;
+    for (const auto& gr : g->groups)
+        if (gr.key.op == spf_graph_plan::kNodeGlwePolyLinear) {
+            const size_t K = (size_t)gr.key.n, M = gr.key.rows;
+            const uint32_t slot = gr.key.slot;
+            const GlwePolySlot& l = c->gpoly[slot];
+            if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no polynomial weights loaded in slot " + std::to_string(slot));
+            if (l.M != M || l.K != K)
+                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: slot " + std::to_string(slot) + " holds " + std::to_string(l.M) + " x " +
+                                                             std::to_string(l.K) + " polynomial weights, its polynomial linear nodes were built for " +
+                                                             std::to_string(M) + " x " + std::to_string(K));
+        }
+    return SPF_OK;
+}
+
 // Output staging (after plan(): needs the arena offsets): outputs grouped by value size, one pointer row per group
 inline spf_status plan_outputs(spf_graph* g)
 {
@@ -380,6 +416,10 @@ inline spf_status run(spf_graph* g)
         spf_status st = check_linear_slots(g);
         if (st != SPF_OK) return st;
     }
+    if (g->has_glwe_poly) {
+        spf_status st = check_glwe_poly_slots(g);
+        if (st != SPF_OK) return st;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t k = g->prm.glwe_size, N = g->prm.polynomial_degree;
@@ -418,6 +458,7 @@ inline spf_status run(spf_graph* g)
     g->runs_since_plan++;
     if (g->exec && g->exec_epoch != c->buf_epoch) g->drop_exec(); // a scratch buffer moved since the capture
     if (g->exec && g->has_linear && g->exec_lin_epoch != c->lin_epoch) g->drop_exec(); // a weight slot was loaded: its old image is freed
+    if (g->exec && g->has_glwe_poly && g->exec_gpoly_epoch != c->gpoly_epoch) g->drop_exec(); // ... a polynomial weight slot
     if (g->exec) {
         HIPCHK(c, hipGraphLaunch(g->exec, s));
         g->n_launches = g->captured_launches;
@@ -433,6 +474,7 @@ inline spf_status run(spf_graph* g)
                 hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                 g->exec_epoch = c->buf_epoch;
                 g->exec_lin_epoch = c->lin_epoch;
+                g->exec_gpoly_epoch = c->gpoly_epoch;
                 g->captured_launches = g->n_launches;
             } else {
                 g->exec = nullptr;
@@ -643,6 +685,40 @@ spf_status spf_graph_add_lwe_linear(spf_graph* g, uint32_t slot, const uint32_t*
     uint32_t first;
     try {
         first = g->add_listed(n, lwe_nodes, K, M); // all of the layer's nodes or none
+    } catch (const std::exception&) {
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    for (size_t m = 0; m < M; m++) nodes_out[m] = first + (uint32_t)m;
+    g->planned = false;
+    return SPF_OK;
+}
+
+// The polynomial linear map of polynomial weight slot `slot` (spf_glwe_poly.hpp) as a node constructor: M GLWE1 nodes, node m = row
+// m of the slot's polynomial matrix times glwe_nodes[0 .. K) (+ bias[m] on the body); one operand list in the side list for all M.
+// The slot itself is looked at by spf_graph_run, not here
+spf_status spf_graph_add_glwe_poly_linear(spf_graph* g, uint32_t slot, const uint32_t* glwe_nodes, size_t K, size_t M, uint32_t* nodes_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    if (!glwe_nodes || !nodes_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: null pointer");
+    if (slot >= SPF_GLWE_POLY_SLOTS)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: slot " + std::to_string(slot) + " >= SPF_GLWE_POLY_SLOTS = " +
+                                                          std::to_string(SPF_GLWE_POLY_SLOTS));
+    if (K == 0 || K > 0xffffffffu) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: K must be in 1 ..= 2^32 - 1");
+    if (M == 0 || M > SPF_GLWE_POLY_MAX_ROWS)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: M must be in 1 ..= SPF_GLWE_POLY_MAX_ROWS = " +
+                                                          std::to_string(SPF_GLWE_POLY_MAX_ROWS));
+    for (size_t i = 0; i < K; i++) {
+        if (glwe_nodes[i] >= g->nodes.size())
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: operand is not a node of this graph");
+        if (g->nodes[glwe_nodes[i]].kind != SPF_VAL_GLWE1)
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: operand is not an L1 GLWE");
+    }
+    spf_graph_plan::Node n{};
+    n.op = spf_graph_plan::kNodeGlwePolyLinear; n.kind = SPF_VAL_GLWE1;
+    n.lin_slot = slot; n.lin_rows = (uint32_t)M;
+    uint32_t first;
+    try {
+        first = g->add_listed(n, glwe_nodes, K, M); // all of the layer's nodes or none
     } catch (const std::exception&) {
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }

@@ -24,8 +24,8 @@
 namespace spf_graph_plan {
 
 // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation /
-// spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear)
-enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68 };
+// spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear / spf_graph_add_glwe_poly_linear)
+enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68, kNodeGlwePolyLinear = 69 };
 
 constexpr size_t kAlign = 256;        // inputs, constants and every group's block start on a multiple of this
 constexpr size_t kNull = (size_t)-1;  // a table entry that is no arena offset but a null pointer
@@ -40,7 +40,7 @@ struct Node {
     uint32_t n_in;
     uint32_t count;    // unpack nodes: the bit nodes of their call (the integer's width); nodes with an operand list: its length
     uint32_t list_at;  // ... where their list starts (n_in = 0)
-    uint32_t lin_slot, lin_rows; // linear nodes: the weight slot and M (the M nodes of one call share one operand list)
+    uint32_t lin_slot, lin_rows; // linear and polynomial linear nodes: the weight slot and M (the M nodes of one call share one operand list)
     uint32_t level;
     size_t off;        // byte offset of the value in the arena
     const void* host;  // inputs: caller's buffer, read at every run
@@ -103,8 +103,8 @@ struct Graph {
     }
 
 private:
-    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks || op == kNodeLweLinear; }
-    std::vector<uint32_t> lists; // operand lists of the pack, the public functional keyswitch and the linear nodes
+    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks || op == kNodeLweLinear || op == kNodeGlwePolyLinear; }
+    std::vector<uint32_t> lists; // operand lists of the pack, the public functional keyswitch, the linear and the polynomial linear nodes
 };
 
 // What the planner needs to know of the parameter set and the context
@@ -124,8 +124,8 @@ inline Sizes sizes_of(const spf_params& p, bool pufks_stage)
 }
 
 // What the nodes of one launch have in common.  Groups run, and lie in the arena, in the order of their keys: by level, then
-// operation, then — public functional keyswitch: (operand kind, lwe_count); linear map: (operand kind, slot, M, K); unpack and pack:
-// the width; every other operation: its parameter.
+// operation, then — public functional keyswitch: (operand kind, lwe_count); linear map and polynomial linear map: (operand kind,
+// slot, M, K); unpack and pack: the width; every other operation: its parameter.
 struct GroupKey {
     uint32_t level;
     int32_t op;
@@ -144,6 +144,8 @@ struct GroupKey {
 };
 static_assert(SPF_LWE_LINEAR_SLOTS - 1 <= 0xff, "a weight slot does not fit GroupKey::slot");
 static_assert(SPF_GRAPH_LWE_LINEAR_MAX_ROWS <= 0xffff, "the rows of a linear node do not fit GroupKey::rows");
+static_assert(SPF_GLWE_POLY_SLOTS - 1 <= 0xff, "a polynomial weight slot does not fit GroupKey::slot");
+static_assert(SPF_GLWE_POLY_MAX_ROWS <= 0xffff, "the rows of a polynomial linear node do not fit GroupKey::rows");
 static_assert(SPF_VAL_GLEV1 <= 0xff, "a value kind does not fit GroupKey::kind");
 
 struct Group {
@@ -165,6 +167,7 @@ struct Plan {
     uint32_t n_levels = 0;
     bool has_pufks = false;  // public functional keyswitch nodes: any
     bool has_linear = false; // linear nodes: any (their weight slots are checked at every run)
+    bool has_glwe_poly = false; // polynomial linear nodes: any (likewise)
 };
 
 // the table row (spf_ops.hpp) of a node's operation: a spf_graph_op that spf_graph_add_op has accepted
@@ -242,7 +245,7 @@ inline GroupKey key_of(const Graph& g, const Node& n)
         k.kind = (uint8_t)g.nodes[g.operand(n, 0)].kind;
         k.n = n.count;
     }
-    if (n.op == kNodeLweLinear) {
+    if (n.op == kNodeLweLinear || n.op == kNodeGlwePolyLinear) { // (polynomial linear nodes: the kind is SPF_VAL_GLWE1)
         k.kind = (uint8_t)n.kind;
         k.slot = (uint8_t)n.lin_slot;
         k.rows = (uint16_t)n.lin_rows;
@@ -255,7 +258,8 @@ inline GroupKey key_of(const Graph& g, const Node& n)
 // nodes of one spf_graph_add_unpack call have consecutive ids and one level (their source's + 1; nothing below moves
 // them), so a group's members are whole integers, int-major.  Linear nodes group by (operand kind, slot, M, K): the M nodes of
 // one spf_graph_add_lwe_linear call have consecutive ids, one operand list and so one level, and nothing above moves them (they
-// are no bootstrap and no head of a conversion chain), so a group's members are whole layers, layer-major
+// are no bootstrap and no head of a conversion chain), so a group's members are whole layers, layer-major.  Polynomial linear nodes
+// (spf_graph_add_glwe_poly_linear) likewise, by (slot, M, K)
 inline std::vector<Group> make_groups(const Graph& g)
 {
     std::map<GroupKey, std::vector<uint32_t>> by_key;
@@ -352,6 +356,12 @@ inline void plan_access(const Graph& g, const Sizes& sz, Plan& p)
             p.has_linear = true;
             const std::vector<size_t> offs = listed(gr.key.rows);
             read_rows(p, gr, 0, offs, sz.of(gr.key.kind), consecutive(offs, sz.of(gr.key.kind)), false);
+        } else if (op == kNodeGlwePolyLinear) {
+            // the K GLWEs of every layer, layer-major: in place when all of them lie consecutively (the batch kernels), else read
+            // through the table by the rows kernels; nothing is gathered
+            p.has_glwe_poly = true;
+            const std::vector<size_t> offs = listed(gr.key.rows);
+            read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), false);
         } else if (op == kNodePack) {
             // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table
             read_rows(p, gr, 0, listed(1), sz.of(SPF_VAL_GLWE1), false, false);

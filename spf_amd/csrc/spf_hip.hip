@@ -184,6 +184,7 @@ struct spf_ctx {
     // plaintext polynomial linear maps over GLWE ciphertexts (spf_glwe_poly.hpp): the weight slots
     GlwePolySlot gpoly[SPF_GLWE_POLY_SLOTS];
     const char* last_gpoly_kernel = "";
+    uint64_t gpoly_epoch = 0; // bumped by every spf_load_glwe_poly_weights (captured gate graphs hold a slot's pointers)
 };
 
 namespace {
@@ -3167,6 +3168,7 @@ spf_status spf_load_glwe_poly_weights(spf_ctx* c, uint32_t slot, size_t M, size_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     GlwePolySlot& l = c->gpoly[slot];
     glwe_poly_drop(l);
+    c->gpoly_epoch++;
     const spf_glwe_poly::Image im = spf_glwe_poly::pack(M, K, offsets, exponents, coefficients);
     GlwePolySlot n;
     n.M = M; n.K = K; n.terms = im.terms.size();
@@ -3247,6 +3249,31 @@ spf_status spf_glwe_poly_linear_batch(spf_ctx* c, uint32_t slot, size_t B, const
     return host_batch(c, sh, B, {{c->in, glwe_in}}, glwe_out, [&](const uint64_t* d_in, uint64_t* d_out) {
         return spf_glwe_poly_linear_enqueue(c, c->stream, slot, B, d_in, d_out);
     });
+}
+
+// The product over GLWEs that are not contiguous (a level of a gate graph, spf_graph.hpp): d_rows is a device table of layers * K
+// device pointers, layer-major, d_out layers * M contiguous GLWEs that overlap none of them.  The caller has checked the slot
+// against its nodes (M, K): ONE launch whatever layers and M (layers in grid.x, M <= SPF_GLWE_POLY_MAX_ROWS keeps grid.y <= 1024).
+// `arena` is the base the table's pointers were made from: the rows kernels stage 16 bytes at a time.
+static spf_status launch_glwe_poly_rows(spf_ctx* c, hipStream_t s, uint32_t slot, size_t layers, const void* arena,
+                                        const uint64_t* const* d_rows, uint64_t* d_out)
+{
+    const GlwePolySlot& l = c->gpoly[slot];
+    const uint32_t N = c->prm.polynomial_degree, k1 = c->prm.glwe_size + 1;
+    if (layers > 0x7fffffffu) return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: more than 2^31 - 1 polynomial linear layers on one level");
+    if (((uintptr_t)arena & 15) != 0 || N < 16 || N > (uint32_t)GLWE_POLY_MAX_N)
+        return fail(c, SPF_ERR_UNSUPPORTED, "graph: the polynomial linear rows kernels need GLWEs on 16 bytes and 16 <= N <= 2048");
+    const bool stream_kernel = l.constants_only && glwe_poly_forced_path() != 1;
+    c->last_gpoly_kernel = stream_kernel ? "glwe_poly_stream_rows_kernel" : "glwe_poly_lds_rows_kernel";
+    TimedScope ts(c, s, T_GLWE_POLY);
+    spf_status st = ts.begin();
+    if (st != SPF_OK) return st;
+    GlwePolyRowsArgs a{d_rows, l.d_offsets, l.d_terms, l.d_scalars, l.d_bias, d_out, (uint32_t)l.M, (uint32_t)l.K, N, k1 - 1};
+    const unsigned tiles = (unsigned)((l.M + GLWE_POLY_VT - 1) / GLWE_POLY_VT);
+    if (stream_kernel) hipLaunchKernelGGL(glwe_poly_stream_rows_kernel, dim3((unsigned)layers, tiles, (k1 * N + 255) / 256), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(glwe_poly_lds_rows_kernel, dim3((unsigned)layers, tiles, k1), dim3(256), 0, s, a);
+    HIPCHK(c, hipGetLastError());
+    return ts.end();
 }
 
 spf_status spf_glwe_poly_slot_shape(spf_ctx* c, uint32_t slot, size_t* M, size_t* K, size_t* terms, int* has_bias)

@@ -70,6 +70,13 @@ NODE_LWE_LINEAR = 68
 LWE_LINEAR_NODE = NODE_LWE_LINEAR  # its name in the revision before: that revision's test modules import it and must still load
 LWE_LINEAR_SLOTS = 64            # SPF_LWE_LINEAR_SLOTS
 LWE_LINEAR_GRAPH_MAX_ROWS = 4096  # SPF_GRAPH_LWE_LINEAR_MAX_ROWS
+# spf_graph_add_glwe_poly_linear: one GLWE1 node per output row m, inputs = all K operands (one list shared by the M nodes of a
+# call), param = m.  Not a NODE_* name yet: the random graph generator of the differential tests draws every NODE_* of this module,
+# and it cannot draw polynomial weights.  This becomes NODE_GLWE_POLY_LINEAR in the change that teaches the generator to draw them.
+GLWE_POLY_LINEAR_NODE = 69
+GLWE_POLY_SLOTS = 64       # SPF_GLWE_POLY_SLOTS
+GLWE_POLY_MAX_ROWS = 4096  # SPF_GLWE_POLY_MAX_ROWS
+_LINEAR_NODES = (NODE_LWE_LINEAR, GLWE_POLY_LINEAR_NODE)   # M nodes over one operand list, with a weight slot
 
 # operand kinds of the operations whose arguments RecordedCircuit checks itself, as the library's table does (spf_ops.hpp)
 _PBS_IN_KINDS = {int(TableOp.PBS_UNIVARIATE): (0, 2), int(TableOp.PBS_BIVARIATE): (0, 0, 2)}
@@ -98,13 +105,14 @@ def _check_blind_rotation(what: str, n_bits: int, log_stride, degree: int) -> in
     return int(log_stride)
 
 
-def _check_lwe_linear(what: str, slot, n_operands: int, M) -> tuple:
-    if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < LWE_LINEAR_SLOTS:
-        raise SpfError(1, f"{what}: slot must be in 0 .. {LWE_LINEAR_SLOTS - 1}, got {slot!r}")
+def _check_lwe_linear(what: str, slot, n_operands: int, M, slots: int = LWE_LINEAR_SLOTS, max_rows: int = LWE_LINEAR_GRAPH_MAX_ROWS) -> tuple:
+    """slot, K and M of a linear layer (add_lwe_linear; add_glwe_poly_linear with its own limits)"""
+    if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < slots:
+        raise SpfError(1, f"{what}: slot must be in 0 .. {slots - 1}, got {slot!r}")
     if n_operands < 1:
         raise SpfError(1, f"{what}: K = 0 operands")
-    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 0 < M <= LWE_LINEAR_GRAPH_MAX_ROWS:
-        raise SpfError(1, f"{what}: M must be in 1 ..= {LWE_LINEAR_GRAPH_MAX_ROWS}, got {M!r}")
+    if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 0 < M <= max_rows:
+        raise SpfError(1, f"{what}: M must be in 1 ..= {max_rows}, got {M!r}")
     return int(slot), int(M)
 
 
@@ -226,6 +234,21 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_lwe_linear(self._g, slot, arr, len(nodes), M, out))
         return list(out)
 
+    # the plaintext polynomial linear map of polynomial weight slot `slot` (Engine.load_glwe_poly_weights) over K GLWE1 nodes: M
+    # GLWE1 nodes, node m = sum over k of w[m][k] * nodes[k] in Z_2^64[X]/(X^N + 1) (+ bias[m] on the body).  M=None asks the
+    # engine for the slot's shape; the slot may also be loaded, and loaded again, after the graph is built (run() checks it)
+    def add_glwe_poly_linear(self, slot: int, nodes: Sequence[int], M=None) -> List[int]:
+        nodes = list(nodes)
+        if M is None:
+            M = self._eng.glwe_poly_slot_shape(slot)[0]
+        slot, M = _check_lwe_linear("add_glwe_poly_linear", slot, len(nodes), M, GLWE_POLY_SLOTS, GLWE_POLY_MAX_ROWS)
+        if any(isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not 0 <= x < 1 << 32 for x in nodes):
+            raise SpfError(1, "add_glwe_poly_linear: the operands must be node ids")
+        arr = (C.c_uint32 * len(nodes))(*[int(x) for x in nodes])
+        out = (C.c_uint32 * M)()
+        self._eng._ck(self._lib.spf_graph_add_glwe_poly_linear(self._g, slot, arr, len(nodes), M, out))
+        return list(out)
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -261,14 +284,14 @@ class RecordedCircuit:
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / NODE_LWE_LINEAR, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / NODE_LWE_LINEAR / GLWE_POLY_LINEAR_NODE, -1 input, -2 trivial constant
         self.kind: List[int] = []
         self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
         self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands; public functional keyswitch nodes: all lwe_count)
         self.host: List = []           # inputs: the caller's array
         self.outputs: List[int] = []   # nodes, in add_output order
         self._unpack_width: dict = {}  # unpack node -> n_bits of its add_unpack call
-        self._linear: dict = {}        # linear node -> (slot, M) of its add_lwe_linear call
+        self._linear: dict = {}        # linear node -> (slot, M) of its add_lwe_linear / add_glwe_poly_linear call
 
     def _add(self, op, kind, param, inputs, host=None) -> int:
         self.op.append(int(op)); self.kind.append(int(kind)); self.param.append(int(param))
@@ -352,8 +375,20 @@ class RecordedCircuit:
             self._linear[n] = (slot, M)
         return out
 
+    def add_glwe_poly_linear(self, slot: int, nodes: Sequence[int], M: int) -> List[int]:
+        """M is required here: a recording is bound to no engine that could be asked for the slot's shape"""
+        nodes = list(nodes)
+        slot, M = _check_lwe_linear("add_glwe_poly_linear", slot, len(nodes), M, GLWE_POLY_SLOTS, GLWE_POLY_MAX_ROWS)
+        nodes = [_check_node("add_glwe_poly_linear", x, len(self.op)) for x in nodes]
+        if any(self.kind[x] != int(ValueKind.GLWE1) for x in nodes):
+            raise SpfError(1, "add_glwe_poly_linear: an operand is not an L1 GLWE")
+        out = [self._add(GLWE_POLY_LINEAR_NODE, ValueKind.GLWE1, m, nodes) for m in range(M)]
+        for n in out:
+            self._linear[n] = (slot, M)
+        return out
+
     def linear_of(self, node: int) -> tuple:
-        """(slot, M) of the add_lwe_linear call that made this linear node (its row index is `param[node]`)"""
+        """(slot, M) of the add_lwe_linear or add_glwe_poly_linear call that made this linear node (its row index is `param[node]`)"""
         return self._linear[node]
 
     def add_output(self, node: int, kind: ValueKind) -> int:
@@ -373,9 +408,9 @@ class RecordedCircuit:
                 assert bits == list(range(i, i + n_bits))
                 i += n_bits
                 continue
-            if self.op[i] == NODE_LWE_LINEAR:   # the row nodes of one add_lwe_linear call are consecutive
+            if self.op[i] in _LINEAR_NODES:   # the row nodes of one add_lwe_linear / add_glwe_poly_linear call are consecutive
                 slot, M = self._linear[i]
-                rows = g.add_lwe_linear(slot, self.inputs[i], M)
+                rows = (g.add_lwe_linear if self.op[i] == NODE_LWE_LINEAR else g.add_glwe_poly_linear)(slot, self.inputs[i], M)
                 assert rows == list(range(i, i + M))
                 i += M
                 continue
@@ -410,7 +445,8 @@ class RecordedCircuit:
         # (the executor's own layout, spf_graph.hpp); a public functional keyswitch node's lwe_count operands lie the same way.
         # n_bits is the integer's width on unpack and pack nodes, lwe_count on those, 0 elsewhere;
         # an unpack node's param is its bit index.  The M nodes of one add_lwe_linear call share ONE list of K operands
-        # (n_bits = K, the same ext_at, param = the row index m); their weight slot and M are lin_slot / lin_rows, 0 elsewhere.
+        # (n_bits = K, the same ext_at, param = the row index m); their weight slot and M are lin_slot / lin_rows, 0 elsewhere;
+        # the M nodes of one add_glwe_poly_linear call lie the same way.
         ins = np.zeros((n, 3), dtype=np.uint32)
         n_in = np.zeros(n, dtype=np.uint32)
         n_bits = np.zeros(n, dtype=np.uint32)
@@ -419,7 +455,7 @@ class RecordedCircuit:
         lin_rows = np.zeros(n, dtype=np.uint32)
         ext: List[int] = []
         for i, t in enumerate(self.inputs):
-            if self.op[i] == NODE_LWE_LINEAR:
+            if self.op[i] in _LINEAR_NODES:
                 lin_slot[i], lin_rows[i] = self._linear[i]
                 n_bits[i] = len(t)
                 if self.param[i] == 0:
@@ -457,9 +493,9 @@ class RecordedCircuit:
                 g.add_unpack(int(a["in"][i, 0]), w)
                 i += w
                 continue
-            if op == NODE_LWE_LINEAR:
+            if op in _LINEAR_NODES:
                 at, rows = int(a["ext_at"][i]), int(a["lin_rows"][i])
-                g.add_lwe_linear(int(a["lin_slot"][i]), [int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]], rows)
+                (g.add_lwe_linear if op == NODE_LWE_LINEAR else g.add_glwe_poly_linear)(int(a["lin_slot"][i]), [int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]], rows)
                 i += rows
                 continue
             if op == NODE_PACK:

@@ -464,6 +464,11 @@ class GraphBuilder:
     def add_lwe_linear(self, slot: int, lwe_nodes, M=None) -> list:
         return self.graph.add_lwe_linear(slot, lwe_nodes, M)
 
+    # the plaintext polynomial linear map of polynomial weight slot `slot` over K GLWE1 nodes: M GLWE1 nodes (recorded as op 69,
+    # the same way)
+    def add_glwe_poly_linear(self, slot: int, glwe_nodes, M=None) -> list:
+        return self.graph.add_glwe_poly_linear(slot, glwe_nodes, M)
+
 
 def append_uint_multiply(builder, a: Sequence, b: Sequence, blocks: Callable[[int, int], MuxCircuit]) -> list:
     """`mul_impl` (parasol_runtime/src/circuits/mul.rs:90-200): recursive gradeschool multiplication of two unsigned

@@ -74,7 +74,10 @@ def upload_circuit_inputs(pool, rec, member=-1):
 
 def _fhe_ops_only(rec):
     """the native drivers hand every node to spf_pool_submit_op_v as an FheOp: a node of add_blind_rotation is none"""
-    from spf_amd.graph import NODE_LWE_LINEAR, NODE_PUFKS, NODE_ROT_CMUX
+    from spf_amd.graph import GLWE_POLY_LINEAR_NODE, NODE_LWE_LINEAR, NODE_PUFKS, NODE_ROT_CMUX
+    if GLWE_POLY_LINEAR_NODE in rec.op:
+        raise RuntimeError("the circuit holds add_glwe_poly_linear nodes, which are no FheOp and have no submit by handle (K operands, M "
+                           "results): the per-operation drivers cannot walk it (lower() it into a gate graph)")
     if NODE_LWE_LINEAR in rec.op:
         raise RuntimeError("the circuit holds add_lwe_linear nodes, which are no FheOp and have no submit by handle (K operands, M "
                            "results): the per-operation drivers cannot walk it (lower() it into a gate graph)")
