@@ -214,6 +214,26 @@ class Evaluation {
     {
         check(spf_group_glwe_poly_linear_batch(grp_, slot, B, input_glwes, output_glwes));
     }
+    // `keyswitch_glwe_to_glwe` (sunscreen_tfhe ops/fft_ops.rs:457-495) under a `GlweKeyswitchKey<u64>` in integer form, [row<k]
+    // [level<radix_count][poly<k+1][N] words, kept in slot `slot` < SPF_GLWE_KSK_SLOTS; one round of the trace's loop
+    // (ops/automorphisms/mod.rs:72-83; `round` in 1 .. log2 N) and `trace` (ops/automorphisms/mod.rs:53-85) under the automorphism
+    // key: B GLWEs -> B GLWEs, every word the reference's.  output == input (the same address) is allowed.
+    void load_glwe_keyswitch_key_std(uint32_t slot, const uint64_t* key, size_t n_words, uint32_t radix_log, uint32_t radix_count)
+    {
+        check(spf_group_load_glwe_keyswitch_key_std(grp_, slot, key, n_words, radix_log, radix_count));
+    }
+    void keyswitch_glwe_to_glwe(uint64_t* output_glwes, const uint64_t* input_glwes, uint32_t slot, size_t B = 1)
+    {
+        check(spf_group_glwe_keyswitch_batch(grp_, slot, B, input_glwes, output_glwes));
+    }
+    void glwe_automorphism(uint64_t* output_glwes, const uint64_t* input_glwes, uint32_t round, size_t B = 1)
+    {
+        check(spf_group_glwe_automorphism_batch(grp_, round, B, input_glwes, output_glwes));
+    }
+    void trace(uint64_t* output_glwes, const uint64_t* input_glwes, size_t B = 1)
+    {
+        check(spf_group_glwe_trace_batch(grp_, B, input_glwes, output_glwes));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {

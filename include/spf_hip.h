@@ -532,6 +532,50 @@ spf_status spf_glwe_poly_linear_enqueue(spf_ctx *ctx, void *stream, uint32_t slo
 spf_status spf_glwe_poly_slot_shape(spf_ctx *ctx, uint32_t slot, size_t *M, size_t *K, size_t *terms, int *has_bias);
 const char *spf_last_glwe_poly_kernel(spf_ctx *ctx);
 
+/* ---- GLWE keyswitch, one automorphism round, homomorphic trace ---------------------------------
+ * The three functions the circuit bootstrap's trace is built from, on B GLWEs of (k+1)*N words each (SPF_VAL_GLWE1 rows), B
+ * GLWEs out:
+ *   spf_glwe_keyswitch_*     `keyswitch_glwe_to_glwe` (sunscreen_tfhe/src/ops/fft_ops.rs:457-495; integer twin
+ *                            ops/keyswitch/glwe_keyswitch.rs:26-55) under the key in `slot`:
+ *                            out = (0, .., 0, b) - sum_i <decomp(a_i), KSK_i>
+ *   spf_glwe_automorphism_*  one round of the trace's loop (ops/automorphisms/mod.rs:72-83), `round` in 1 .. log2 N:
+ *                            out = keyswitch(in(X^t), ak[round-1]), t = N / 2^(round-1) + 1 (`polynomial_pow_k`,
+ *                            ops/polynomial/mod.rs:62-84), under the context's automorphism key and tr_radix
+ *   spf_glwe_trace_*         `trace` (ops/automorphisms/mod.rs:53-85): x <- x + automorphism_round(x) for rounds 1 .. log2 N in turn
+ * Every word equals the reference's: the kernels run its arithmetic in its order (spf_mod_switch_trace_and_rotate_* runs the same
+ * trace behind the circuit bootstrap's own prologue).
+ * Keys: SPF_GLWE_KSK_SLOTS numbered slots in the context.  spf_load_glwe_keyswitch_key_std takes a `GlweKeyswitchKey<u64>` in
+ * integer form, [row<k][level<radix_count][poly<k+1][N] words — n_words must be exactly k * radix_count * (k+1) * N — and transforms
+ * it on the device as spf_load_automorphism_key_std does; the radix comes with the key.  The load is synchronous, replaces what the
+ * slot held and must not race work that uses the slot (the rule of the key loads); spf_destroy frees the slots.
+ * SPF_ERR_INVALID_ARGUMENT, with the offending numbers in the message and nothing touched: slot >= SPF_GLWE_KSK_SLOTS, radix_log or
+ * radix_count = 0, radix_log * radix_count > 64 — and = 64, which the reference accepts and the kernels do not (they round to the
+ * top radix_log * radix_count bits by the bit below them) —, another n_words.  spf_glwe_keyswitch_slot_shape reads the radix back;
+ * an empty slot is SPF_ERR_NO_KEY.
+ * Statuses of the operations: B = 0 is SPF_OK; an empty slot, or no automorphism key, is SPF_ERR_NO_KEY; a round outside
+ * 1 .. log2 N or a slot >= SPF_GLWE_KSK_SLOTS is SPF_ERR_INVALID_ARGUMENT before anything is queued.
+ * Aliasing: glwe_out == glwe_in EXACTLY (the same address: the operation runs in place) is allowed; any other overlap of the two
+ * ranges is the caller's error and is refused with SPF_ERR_INVALID_ARGUMENT.
+ * The _enqueue forms take device pointers under the contract of the `_dev` entry points above: they only enqueue on `stream`, ONE
+ * launch whatever B (B <= 2^31 - 1), and use no buffer of the context.  "glwe_keyswitch" of spf_last_kernel_ms times all three.
+ * N = 2048, k = 1 with a radix of 6 levels x 7 bits (DEFAULT_128's automorphism key) runs the hand-written "glwe_ks_kernel",
+ * every other shape — a generic context, or another radix on a tuned one — "generic_glwe_ks_kernel";
+ * spf_last_glwe_keyswitch_kernel names the kernel of the last call.  The group forms: the key goes to every member, B is dealt in
+ * contiguous shards. */
+typedef enum spf_glwe_ksk_limits { SPF_GLWE_KSK_SLOTS = 16 } spf_glwe_ksk_limits;
+spf_status spf_load_glwe_keyswitch_key_std(spf_ctx *ctx, uint32_t slot, const uint64_t *key, size_t n_words, uint32_t radix_log,
+                                           uint32_t radix_count);
+spf_status spf_glwe_keyswitch_slot_shape(spf_ctx *ctx, uint32_t slot, uint32_t *radix_log, uint32_t *radix_count);
+spf_status spf_glwe_keyswitch_batch(spf_ctx *ctx, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_glwe_keyswitch_enqueue(spf_ctx *ctx, void *stream, uint32_t slot, size_t B, const uint64_t *d_glwe_in,
+                                      uint64_t *d_glwe_out);
+spf_status spf_glwe_automorphism_batch(spf_ctx *ctx, uint32_t round, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_glwe_automorphism_enqueue(spf_ctx *ctx, void *stream, uint32_t round, size_t B, const uint64_t *d_glwe_in,
+                                         uint64_t *d_glwe_out);
+spf_status spf_glwe_trace_batch(spf_ctx *ctx, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_glwe_trace_enqueue(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe_in, uint64_t *d_glwe_out);
+const char *spf_last_glwe_keyswitch_kernel(spf_ctx *ctx);
+
 /* ---- call coalescing: many threads, one ciphertext each -> one batch per launch ----------
  * The reference calls `Evaluation` from many rayon workers with a single ciphertext per call
  * (circuit_processor/mod.rs:192-253).  A pool keeps that calling convention — submit, then wait like the synchronous call it
@@ -854,10 +898,10 @@ spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t w
  * "keyswitch" (digits + GEMM), "trace" (cbs_trace_kernel), "scheme_switch", "cmux" (contiguous
  * batched CMUX family), "pufks_prepass" (the transposing pre-pass of a public functional keyswitch at the hand-written radices,
  * with the gather in front of it where there is one), "lwe_linear_planes" and "lwe_linear" (the per-call byte planes and the product,
- * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only), "glwe_poly_linear" (the one launch of spf_glwe_poly_linear_enqueue).  A host-pointer bootstrap of more than one chip round is launched in slices
+ * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only), "glwe_poly_linear" (the one launch of spf_glwe_poly_linear_enqueue), "glwe_keyswitch" (the one launch of spf_glwe_keyswitch_enqueue, spf_glwe_automorphism_enqueue or spf_glwe_trace_enqueue).  A host-pointer bootstrap of more than one chip round is launched in slices
  * of 1024 ciphertexts: it records one "pbs" entry per slice.  Enable with spf_set_timing(ctx, 1). */
 spf_status spf_set_timing(spf_ctx *ctx, int enabled);
-spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" | "glwe_poly_linear" */,
+spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" | "glwe_poly_linear" | "glwe_keyswitch" */,
                               double *avg_ms, int *launches);
 /* `generate_lut` (sunscreen_tfhe ops/bootstrapping/programmable_bootstrapping.rs:129-185) for
  * `programmable_bootstrap_univariate`: map_tables[f * 2^bits + x] = f(x) for n_maps functions over a
@@ -1070,6 +1114,14 @@ spf_status spf_group_lwe_linear_batch(spf_group *grp, uint32_t slot, spf_value_k
 spf_status spf_group_load_glwe_poly_weights(spf_group *grp, uint32_t slot, size_t M, size_t K, const uint32_t *offsets,
                                             const uint32_t *exponents, const int64_t *coefficients, const uint64_t *bias);
 spf_status spf_group_glwe_poly_linear_batch(spf_group *grp, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+/* GLWE keyswitch, one automorphism round and the trace (`keyswitch_glwe_to_glwe`, ops/fft_ops.rs:457-495; ops/automorphisms/
+ * mod.rs:53-85; spf_load_glwe_keyswitch_key_std, spf_glwe_keyswitch_batch, spf_glwe_automorphism_batch, spf_glwe_trace_batch): the
+ * key goes to every member, straight from the host pointer; a batch is sharded by item */
+spf_status spf_group_load_glwe_keyswitch_key_std(spf_group *grp, uint32_t slot, const uint64_t *key, size_t n_words,
+                                                 uint32_t radix_log, uint32_t radix_count);
+spf_status spf_group_glwe_keyswitch_batch(spf_group *grp, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_group_glwe_automorphism_batch(spf_group *grp, uint32_t round, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+spf_status spf_group_glwe_trace_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

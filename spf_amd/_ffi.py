@@ -36,6 +36,8 @@ VAL_LWE0, VAL_LWE1 = 0, 1
 LWE_LINEAR_SLOTS = 64
 # the limits of the plaintext polynomial weights over GLWE ciphertexts (spf_glwe_poly_limits)
 GLWE_POLY_SLOTS, GLWE_POLY_MAX_ROWS, GLWE_POLY_MAX_TERMS = 64, 4096, 1 << 24
+# the key slots of the GLWE keyswitch (spf_glwe_ksk_limits)
+GLWE_KSK_SLOTS = 16
 
 
 def lib_path() -> str:
@@ -111,6 +113,15 @@ SYMBOLS = [
     ("spf_glwe_poly_linear_enqueue", _I, [_P, _P, _U32, _SZ, _P, _P]),
     ("spf_glwe_poly_slot_shape", _I, [_P, _U32, C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(_SZ), C.POINTER(C.c_int)]),
     ("spf_last_glwe_poly_kernel", C.c_char_p, [_P]),
+    ("spf_load_glwe_keyswitch_key_std", _I, [_P, _U32, _P, _SZ, _U32, _U32]),
+    ("spf_glwe_keyswitch_slot_shape", _I, [_P, _U32, C.POINTER(_U32), C.POINTER(_U32)]),
+    ("spf_glwe_keyswitch_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_keyswitch_enqueue", _I, [_P, _P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_automorphism_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_automorphism_enqueue", _I, [_P, _P, _U32, _SZ, _P, _P]),
+    ("spf_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_glwe_trace_enqueue", _I, [_P, _P, _SZ, _P, _P]),
+    ("spf_last_glwe_keyswitch_kernel", C.c_char_p, [_P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -225,6 +236,10 @@ SYMBOLS = [
     ("spf_group_lwe_linear_batch", _I, [_P, _U32, _I, _SZ, _P, _P]),
     ("spf_group_load_glwe_poly_weights", _I, [_P, _U32, _SZ, _SZ, _P, _P, _P, _P]),
     ("spf_group_glwe_poly_linear_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_group_load_glwe_keyswitch_key_std", _I, [_P, _U32, _P, _SZ, _U32, _U32]),
+    ("spf_group_glwe_keyswitch_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_group_glwe_automorphism_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_group_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -865,6 +880,55 @@ class Engine:
         self._ck(self._lib.spf_glwe_poly_linear_batch(self._h, int(slot), x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    # GLWE keyswitch, one automorphism round, trace (`keyswitch_glwe_to_glwe`, sunscreen_tfhe ops/fft_ops.rs:457-495; ops/automorphisms/
+    # mod.rs:53-85)
+    def load_glwe_keyswitch_key_std(self, slot: int, key: np.ndarray, radix_log: int, radix_count: int):
+        """`GlweKeyswitchKey<u64>` words (k, radix_count, k+1, N) into slot `slot` < GLWE_KSK_SLOTS; transformed on the device.
+        The radix belongs to the key.  Replaces what the slot held; synchronous."""
+        N, k = self.params.polynomial_degree, self.params.glwe_size
+        if (not isinstance(key, np.ndarray) or key.dtype != np.uint64 or key.ndim != 4
+                or key.shape != (k, int(radix_count), k + 1, N)):
+            raise SpfError(-2, f"load_glwe_keyswitch_key_std: the key is a uint64 array of shape ({k}, {int(radix_count)}, {k + 1}, {N}), "
+                               f"got {getattr(key, 'dtype', type(key))} {getattr(key, 'shape', '')}")
+        a = np.ascontiguousarray(key)
+        self._ck(self._lib.spf_load_glwe_keyswitch_key_std(self._h, int(slot) & 0xFFFFFFFF, _ptr(a), a.size, int(radix_log), int(radix_count)))
+
+    def glwe_keyswitch_slot_shape(self, slot: int):
+        """`spf_glwe_keyswitch_slot_shape`: (radix_log, radix_count) of the key in `slot`; an empty slot is SPF_ERR_NO_KEY"""
+        lg, cnt = _U32(), _U32()
+        self._ck(self._lib.spf_glwe_keyswitch_slot_shape(self._h, int(slot) & 0xFFFFFFFF, C.byref(lg), C.byref(cnt)))
+        return int(lg.value), int(cnt.value)
+
+    def _glwes(self, name: str, glwes) -> np.ndarray:
+        k1, N = self.params.glwe_size + 1, self.params.polynomial_degree
+        x = _u64(glwes)
+        if x.ndim == 2 and x.shape[1] == k1 * N:
+            x = x.reshape(-1, k1, N)
+        if x.ndim != 3 or x.shape[1:] != (k1, N):
+            raise SpfError(-2, f"{name}: operand must have shape (B, {k1}, {N}), got {x.shape}")
+        return x
+
+    def glwe_keyswitch(self, slot: int, glwes) -> np.ndarray:
+        """`keyswitch_glwe_to_glwe` of (B, k+1, N) GLWEs under the key of slot `slot`, word for word"""
+        x = self._glwes("glwe_keyswitch", glwes)
+        out = np.empty_like(x)
+        self._ck(self._lib.spf_glwe_keyswitch_batch(self._h, int(slot) & 0xFFFFFFFF, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
+    def glwe_automorphism(self, round: int, glwes) -> np.ndarray:
+        """round `round` in 1 .. log2 N of the trace's loop: keyswitch(x(X^t), ak[round - 1]), t = N / 2^(round - 1) + 1"""
+        x = self._glwes("glwe_automorphism", glwes)
+        out = np.empty_like(x)
+        self._ck(self._lib.spf_glwe_automorphism_batch(self._h, int(round) & 0xFFFFFFFF, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
+    def glwe_trace(self, glwes) -> np.ndarray:
+        """`trace` (ops/automorphisms/mod.rs:53-85) of (B, k+1, N) GLWEs under the context's automorphism key"""
+        x = self._glwes("glwe_trace", glwes)
+        out = np.empty_like(x)
+        self._ck(self._lib.spf_glwe_trace_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
+        return out
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -995,6 +1059,19 @@ class Engine:
     def last_glwe_poly_kernel(self) -> str:
         return (self._lib.spf_last_glwe_poly_kernel(self._h) or b"").decode()
 
+    # the device-pointer forms of the GLWE keyswitch, automorphism round and trace; d_glwe_out may be d_glwe_in itself
+    def glwe_keyswitch_enqueue(self, stream, slot, B, d_glwe_in, d_glwe_out):
+        self._ck(self._lib.spf_glwe_keyswitch_enqueue(self._h, stream, int(slot) & 0xFFFFFFFF, B, d_glwe_in, d_glwe_out))
+
+    def glwe_automorphism_enqueue(self, stream, round, B, d_glwe_in, d_glwe_out):
+        self._ck(self._lib.spf_glwe_automorphism_enqueue(self._h, stream, int(round) & 0xFFFFFFFF, B, d_glwe_in, d_glwe_out))
+
+    def glwe_trace_enqueue(self, stream, B, d_glwe_in, d_glwe_out):
+        self._ck(self._lib.spf_glwe_trace_enqueue(self._h, stream, B, d_glwe_in, d_glwe_out))
+
+    def last_glwe_keyswitch_kernel(self) -> str:
+        return (self._lib.spf_last_glwe_keyswitch_kernel(self._h) or b"").decode()
+
     def last_public_functional_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()
 
@@ -1106,6 +1183,13 @@ class Group(Engine):
 
     def last_glwe_poly_kernel(self) -> str:
         return self.member(0).last_glwe_poly_kernel()
+
+    def glwe_keyswitch_slot_shape(self, slot: int):
+        """of member 0: `spf_group_load_glwe_keyswitch_key_std` loads every member alike"""
+        return self.member(0).glwe_keyswitch_slot_shape(slot)
+
+    def last_glwe_keyswitch_kernel(self) -> str:
+        return self.member(0).last_glwe_keyswitch_kernel()
 
     def run_graphs(self, graphs):
         """`spf_group_run_graphs`: graphs are `spf_amd.FheCircuit`s made over this group; dealt to the members by cost,

@@ -870,6 +870,41 @@ spf_status spf_group_glwe_poly_linear_batch(spf_group* g, uint32_t slot, size_t 
     return group_batch(g, sh, B, {in}, out, [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_glwe_poly_linear_batch(c, slot, n, in, out); });
 }
 
+// a GLWE keyswitch key: every member, straight from the host pointer
+spf_status spf_group_load_glwe_keyswitch_key_std(spf_group* g, uint32_t slot, const uint64_t* key, size_t n_words, uint32_t radix_log,
+                                                 uint32_t radix_count)
+{
+    if (!g) return gfail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null group");
+    std::lock_guard<std::mutex> lk(g->key_mu);
+    for (size_t i = 0; i < g->m.size(); i++) {
+        spf_status s = spf_load_glwe_keyswitch_key_std(g->m[i]->ctx, slot, key, n_words, radix_log, radix_count);
+        if (s != SPF_OK) return gfail(g, s, "member " + std::to_string(i) + ": " + spf_last_error(g->m[i]->ctx));
+    }
+    return SPF_OK;
+}
+
+// GLWE keyswitch, automorphism round, trace: sharded by item (the checks are made on the whole batch, on member 0)
+static spf_status group_glwe_ks(spf_group* g, int mode, uint32_t arg, size_t B, const uint64_t* in, uint64_t* out)
+{
+    if (spf_status s = group_args(g, false)) return s;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = glwe_ks_args(c0, mode, arg, B, in, out)) return gfail(g, s, spf_last_error(c0));
+    return group_batch(g, glwe_ks_shape(c0->prm), B, {in}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return glwe_ks_batch(c, mode, arg, n, in, out); });
+}
+spf_status spf_group_glwe_keyswitch_batch(spf_group* g, uint32_t slot, size_t B, const uint64_t* in, uint64_t* out)
+{
+    return group_glwe_ks(g, GLWE_KS_KEYSWITCH, slot, B, in, out);
+}
+spf_status spf_group_glwe_automorphism_batch(spf_group* g, uint32_t round, size_t B, const uint64_t* in, uint64_t* out)
+{
+    return group_glwe_ks(g, GLWE_KS_AUTOMORPHISM, round, B, in, out);
+}
+spf_status spf_group_glwe_trace_batch(spf_group* g, size_t B, const uint64_t* in, uint64_t* out)
+{
+    return group_glwe_ks(g, GLWE_KS_TRACE, 0, B, in, out);
+}
+
 // circuit bootstrap via PFKS: sharded by item
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {

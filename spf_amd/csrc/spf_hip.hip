@@ -13,6 +13,7 @@
 #include "spf_pfks.hpp"
 #include "spf_lwe_linear.hpp"
 #include "spf_glwe_poly.hpp"
+#include "spf_glwe_keyswitch.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -65,9 +66,9 @@ struct Scratch {
 };
 
 // kernels whose launches spf_set_timing brackets with hipEvents on the launch stream (spf_last_kernel_ms)
-enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_GLWE_POLY, T_COUNT };
+enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_GLWE_POLY, T_GLWE_KS, T_COUNT };
 const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass", "lwe_linear_planes",
-                                          "lwe_linear", "glwe_poly_linear"};
+                                          "lwe_linear", "glwe_poly_linear", "glwe_keyswitch"};
 
 // one slot of plaintext weights for spf_lwe_linear_* (spf_lwe_linear.hpp): the int64 matrix as loaded, always; the int8 limbs of
 // -w and their sums where the matrix-core path takes the matrix (U > 0)
@@ -90,6 +91,14 @@ struct GlwePolySlot {
     spf_glwe_poly::Term* d_terms = nullptr;  // [terms], or null where there are none
     uint64_t* d_scalars = nullptr;           // [M][K], constants-only slots
     uint64_t* d_bias = nullptr;              // [M][N], or null
+};
+
+// one slot of spf_load_glwe_keyswitch_key_std (spf_glwe_keyswitch.hpp): the key's spectra [row<k][level<count][poly<k+1][N/2] and
+// the radix that came with it
+struct GlweKskSlot {
+    bool ready = false;
+    c64* d_key = nullptr;
+    uint32_t radix_log = 0, radix_count = 0;
 };
 
 } // namespace
@@ -185,6 +194,11 @@ struct spf_ctx {
     GlwePolySlot gpoly[SPF_GLWE_POLY_SLOTS];
     const char* last_gpoly_kernel = "";
     uint64_t gpoly_epoch = 0; // bumped by every spf_load_glwe_poly_weights (captured gate graphs hold a slot's pointers)
+    // GLWE keyswitch, automorphism round and trace (spf_glwe_keyswitch.hpp): the keyswitch-key slots; whether the generic kernel
+    // has what it needs on this context (always on a generic one; on a tuned one from the first key or radix that needs it)
+    GlweKskSlot gksk[SPF_GLWE_KSK_SLOTS];
+    bool glwe_ks_generic_ready = false;
+    const char* last_glwe_ks_kernel = "";
 };
 
 namespace {
@@ -700,6 +714,42 @@ const char* spf_last_error(const spf_ctx* ctx)
     return copy.c_str();
 }
 
+// ---- GLWE keyswitch, automorphism round, trace (spf_glwe_keyswitch.hpp): which kernel a radix gets and what it needs
+
+// the hand-written kernel's shape: N = 2048, k = 1 (a tuned context) at 6 levels x 7 bits
+static bool glwe_ks_tuned(const spf_ctx* c, uint32_t radix_log, uint32_t radix_count) { return !c->generic && radix_log == 7 && radix_count == 6; }
+
+// why a radix is refused, with its numbers, or empty
+static std::string glwe_ks_radix_error(uint32_t radix_log, uint32_t radix_count)
+{
+    const std::string r = "radix_log " + std::to_string(radix_log) + ", radix_count " + std::to_string(radix_count);
+    if (radix_log == 0 || radix_count == 0) return r + ": a radix decomposition needs radix_log >= 1 and radix_count >= 1";
+    if ((uint64_t)radix_log * radix_count > 64) return r + ": radix_log * radix_count = " + std::to_string((uint64_t)radix_log * radix_count) + " > 64";
+    if ((uint64_t)radix_log * radix_count == 64)
+        return r + ": radix_log * radix_count = 64; the kernels round to the top radix_log * radix_count bits by the bit below them and need at most 63";
+    return "";
+}
+
+// what generic_glwe_ks_kernel needs on a tuned context: the generic twist table e^{+2 pi i j / (2N)} (shared with the public
+// functional keyswitch) and the launch attribute.  Synchronous (a table copy): called from spf_create and from a key load only.
+static spf_status glwe_ks_prepare_generic(spf_ctx* c)
+{
+    if (c->glwe_ks_generic_ready) return SPF_OK;
+    const uint32_t N = c->prm.polynomial_degree, h = N / 2;
+    if (generic_trace_lds_bytes(N, c->prm.glwe_size) > 160 * 1024)
+        return fail(c, SPF_ERR_UNSUPPORTED, "(k+1) polynomials of this degree do not fit the generic kernels' LDS");
+    if (!c->d_gen_tables) {
+        std::vector<c64> gt(h);
+        for (uint32_t j = 0; j < h; j++) gt[j] = root_of_unity(j, 2 * (uint64_t)N);
+        HIPCHK(c, hipMalloc((void**)&c->d_gen_tables, gt.size() * sizeof(c64)));
+        HIPCHK(c, hipMemcpy(c->d_gen_tables, gt.data(), gt.size() * sizeof(c64), hipMemcpyHostToDevice));
+    }
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
+    c->glwe_ks_generic_ready = true;
+    return SPF_OK;
+}
+
 spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
 {
     if (!params || !out) return fail(nullptr, SPF_ERR_INVALID_ARGUMENT, "null argument");
@@ -778,6 +828,9 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_scheme_switch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_lds_bytes(N, params->glwe_size, false)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)generic_trace_lds_bytes(N, params->glwe_size)));
+        c->glwe_ks_generic_ready = true;
         *out = c;
         return SPF_OK;
     }
@@ -815,7 +868,18 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&scheme_switch_kernel<15, 3>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_kernel<6, 7, GLWE_KS_TRACE>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_kernel<6, 7, GLWE_KS_AUTOMORPHISM>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_kernel<6, 7, GLWE_KS_KEYSWITCH>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
 #undef CK
+    // an automorphism key of another radix than the hand-written kernel's: spf_glwe_automorphism_* / spf_glwe_trace_* run the
+    // generic kernel (the *_enqueue forms only enqueue: its table is made here)
+    if (!glwe_ks_tuned(c, params->tr_radix_log, params->tr_radix_count) &&
+        glwe_ks_radix_error(params->tr_radix_log, params->tr_radix_count).empty() && glwe_ks_prepare_generic(c) != SPF_OK)
+        return bail(SPF_ERR_HIP);
     *out = c;
     return SPF_OK;
 }
@@ -854,6 +918,8 @@ static void ctx_release(spf_ctx* c)
     for (GlwePolySlot& l : c->gpoly)
         for (void* p : {(void*)l.d_offsets, (void*)l.d_terms, (void*)l.d_scalars, (void*)l.d_bias})
             if (p) (void)hipFree(p);
+    for (GlweKskSlot& l : c->gksk)
+        if (l.d_key) (void)hipFree(l.d_key);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->d_ggsw_const) (void)hipFree(c->d_ggsw_const);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
@@ -2239,7 +2305,7 @@ spf_status spf_last_kernel_ms(spf_ctx* c, const char* kernel, double* avg_ms, in
     std::vector<TimedLaunch>* v = nullptr;
     for (int k = 0; k < T_COUNT; k++)
         if (!strcmp(kernel, kTimedNames[k])) v = &c->timed[k];
-    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\", \"lwe_linear\" or \"glwe_poly_linear\"");
+    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\", \"lwe_linear\", \"glwe_poly_linear\" or \"glwe_keyswitch\"");
     double total = 0.0;
     int n = 0;
     for (auto& t : *v) {
@@ -3295,6 +3361,167 @@ const char* spf_last_glwe_poly_kernel(spf_ctx* c)
     if (!c) return "";
     std::lock_guard<std::recursive_mutex> g(c->mu);
     return c->last_gpoly_kernel;
+}
+
+// ---------------------------------------------------------------- GLWE keyswitch, automorphism round, homomorphic trace
+// `keyswitch_glwe_to_glwe` (sunscreen_tfhe/src/ops/fft_ops.rs:457-495; integer twin ops/keyswitch/glwe_keyswitch.rs:26-55), one
+// round of the trace's loop (`polynomial_pow_k`, ops/polynomial/mod.rs:62-84, then the keyswitch back: ops/automorphisms/mod.rs:72-83)
+// and `trace` (ops/automorphisms/mod.rs:53-85) on B GLWEs; kernels: spf_glwe_keyswitch.hpp.
+
+static spf_status glwe_ksk_slot_check(spf_ctx* c, uint32_t slot)
+{
+    if (slot >= SPF_GLWE_KSK_SLOTS)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "slot " + std::to_string(slot) + " >= SPF_GLWE_KSK_SLOTS = " + std::to_string(SPF_GLWE_KSK_SLOTS));
+    return SPF_OK;
+}
+
+// Synchronous, like every key load: the slot is empty from the first device call on until the end, and after any failure there.
+spf_status spf_load_glwe_keyswitch_key_std(spf_ctx* c, uint32_t slot, const uint64_t* key, size_t n_words, uint32_t radix_log, uint32_t radix_count)
+{
+    if (!c || !key) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (spf_status s = glwe_ksk_slot_check(c, slot)) return s;
+    const std::string why = glwe_ks_radix_error(radix_log, radix_count);
+    if (!why.empty()) return fail(c, SPF_ERR_INVALID_ARGUMENT, "GLWE keyswitch key: " + why);
+    const size_t k = c->prm.glwe_size, N = c->prm.polynomial_degree, want = k * radix_count * (k + 1) * N;
+    if (n_words != want)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "GLWE keyswitch key length " + std::to_string(n_words) + " words != glwe_size * radix_count * (glwe_size + 1) * N = " +
+                                                     std::to_string(want));
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!glwe_ks_tuned(c, radix_log, radix_count))
+        if (spf_status s = glwe_ks_prepare_generic(c)) return s;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    GlweKskSlot& l = c->gksk[slot];
+    if (l.d_key) (void)hipFree(l.d_key);
+    l = GlweKskSlot{};
+    c64* d = nullptr;
+    HIPCHK(c, hipMalloc((void**)&d, n_words * 8));
+    // the words go in as they are (same bytes as their spectra) and are transformed in place, as the other _std loaders do
+    spf_status st = SPF_OK;
+    {
+        const hipError_t e = hipMemcpyAsync(d, key, n_words * 8, hipMemcpyHostToDevice, c->stream);
+        if (e != hipSuccess) st = fail(c, SPF_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
+    }
+    if (st == SPF_OK) st = launch_poly_fft(c, c->stream, n_words / N, (const uint64_t*)d, d);
+    {
+        // (no return before the stream is idle: the copy reads the caller's buffer)
+        const hipError_t e = hipStreamSynchronize(c->stream);
+        if (st == SPF_OK && e != hipSuccess) st = fail(c, SPF_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    }
+    if (st != SPF_OK) {
+        (void)hipFree(d);
+        return st;
+    }
+    l.d_key = d; l.radix_log = radix_log; l.radix_count = radix_count; l.ready = true;
+    return SPF_OK;
+}
+
+spf_status spf_glwe_keyswitch_slot_shape(spf_ctx* c, uint32_t slot, uint32_t* radix_log, uint32_t* radix_count)
+{
+    if (!c || !radix_log || !radix_count) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (spf_status s = glwe_ksk_slot_check(c, slot)) return s;
+    if (!c->gksk[slot].ready) return fail(c, SPF_ERR_NO_KEY, "no GLWE keyswitch key loaded in slot " + std::to_string(slot));
+    *radix_log = c->gksk[slot].radix_log;
+    *radix_count = c->gksk[slot].radix_count;
+    return SPF_OK;
+}
+
+// What every form of the three operations checks before the batch is touched, on `c` with its texts.  mode: GlweKsMode; `arg` the
+// slot (keyswitch) or the round (automorphism).  B = 0 is SPF_OK once these hold.
+static spf_status glwe_ks_args(spf_ctx* c, int mode, uint32_t arg, size_t B, const void* in, const void* out)
+{
+    if (!c || (B && (!in || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    if (mode == GLWE_KS_KEYSWITCH) {
+        if (spf_status s = glwe_ksk_slot_check(c, arg)) return s;
+        if (!c->gksk[arg].ready) return fail(c, SPF_ERR_NO_KEY, "no GLWE keyswitch key loaded in slot " + std::to_string(arg));
+    } else {
+        if (mode == GLWE_KS_AUTOMORPHISM && (arg < 1 || arg > c->log_n))
+            return fail(c, SPF_ERR_INVALID_ARGUMENT, "round " + std::to_string(arg) + " outside 1 .. log2 N = " + std::to_string(c->log_n));
+        if (!c->ak_ready) return fail(c, SPF_ERR_NO_KEY, "automorphism key not loaded");
+        if (!glwe_ks_tuned(c, c->prm.tr_radix_log, c->prm.tr_radix_count) && !c->glwe_ks_generic_ready)
+            return fail(c, SPF_ERR_UNSUPPORTED, "the context's tr_radix is served by no GLWE keyswitch kernel: " +
+                                                    glwe_ks_radix_error(c->prm.tr_radix_log, c->prm.tr_radix_count));
+    }
+    const BatchShape sh = glwe_ks_shape(c->prm);
+    if (batch_limit(c, sh, B) != SPF_OK) return SPF_ERR_INVALID_ARGUMENT;
+    if (B && out != in && batch_overlaps(sh, B, out, in))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output must be the input itself or must not overlap it");
+    return SPF_OK;
+}
+
+// ONE launch whatever B <= kBatchMax: four items per workgroup (hand-written) or one (generic) on grid.x; no buffer of the context.
+static spf_status glwe_ks_enqueue(spf_ctx* c, void* stream, int mode, uint32_t arg, size_t B, const uint64_t* d_in, uint64_t* d_out)
+{
+    spf_status st = glwe_ks_args(c, mode, arg, B, d_in, d_out);
+    if (st != SPF_OK || B == 0) return st;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const bool ks = mode == GLWE_KS_KEYSWITCH;
+    const uint32_t radix_log = ks ? c->gksk[arg].radix_log : c->prm.tr_radix_log, count = ks ? c->gksk[arg].radix_count : c->prm.tr_radix_count;
+    const uint32_t N = c->prm.polynomial_degree, k = c->prm.glwe_size;
+    const size_t ksk_len = (size_t)k * count * (k + 1) * (N / 2); // complex values of one keyswitch key
+    const c64* key = ks ? c->gksk[arg].d_key : mode == GLWE_KS_AUTOMORPHISM ? c->d_ak + (size_t)(arg - 1) * ksk_len : c->d_ak;
+    const uint32_t kk = mode == GLWE_KS_AUTOMORPHISM ? (N >> (arg - 1)) + 1 : 1;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t s = (hipStream_t)stream;
+    TimedScope ts(c, s, T_GLWE_KS);
+    st = ts.begin();
+    if (st != SPF_OK) return st;
+    if (glwe_ks_tuned(c, radix_log, count)) {
+        GlweKsArgs a{d_in, d_out, key, c->d_tables, (uint32_t)B, kk};
+        const dim3 grid((unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock)), block(512);
+        if (mode == GLWE_KS_TRACE) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_TRACE>), grid, block, kTraceLds, s, a);
+        else if (mode == GLWE_KS_AUTOMORPHISM) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_AUTOMORPHISM>), grid, block, kTraceLds, s, a);
+        else hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_KEYSWITCH>), grid, block, kTraceLds, s, a);
+        c->last_glwe_ks_kernel = "glwe_ks_kernel";
+    } else {
+        GenericGlweKsArgs a{generic_shape(c), d_in, d_out, key, radix_log, count, (uint32_t)mode, kk};
+        hipLaunchKernelGGL(generic_glwe_ks_kernel, dim3((unsigned)B), dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a);
+        c->last_glwe_ks_kernel = "generic_glwe_ks_kernel";
+    }
+    HIPCHK(c, hipGetLastError());
+    return ts.end();
+}
+
+static spf_status glwe_ks_batch(spf_ctx* c, int mode, uint32_t arg, size_t B, const uint64_t* in, uint64_t* out)
+{
+    spf_status st = glwe_ks_args(c, mode, arg, B, in, out);
+    if (st != SPF_OK) return st;
+    return host_batch(c, glwe_ks_shape(c->prm), B, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, uint64_t* d_out) { return glwe_ks_enqueue(c, c->stream, mode, arg, B, d_in, d_out); });
+}
+
+spf_status spf_glwe_keyswitch_enqueue(spf_ctx* c, void* stream, uint32_t slot, size_t B, const uint64_t* d_glwe_in, uint64_t* d_glwe_out)
+{
+    return glwe_ks_enqueue(c, stream, GLWE_KS_KEYSWITCH, slot, B, d_glwe_in, d_glwe_out);
+}
+spf_status spf_glwe_automorphism_enqueue(spf_ctx* c, void* stream, uint32_t round, size_t B, const uint64_t* d_glwe_in, uint64_t* d_glwe_out)
+{
+    return glwe_ks_enqueue(c, stream, GLWE_KS_AUTOMORPHISM, round, B, d_glwe_in, d_glwe_out);
+}
+spf_status spf_glwe_trace_enqueue(spf_ctx* c, void* stream, size_t B, const uint64_t* d_glwe_in, uint64_t* d_glwe_out)
+{
+    return glwe_ks_enqueue(c, stream, GLWE_KS_TRACE, 0, B, d_glwe_in, d_glwe_out);
+}
+spf_status spf_glwe_keyswitch_batch(spf_ctx* c, uint32_t slot, size_t B, const uint64_t* glwe_in, uint64_t* glwe_out)
+{
+    return glwe_ks_batch(c, GLWE_KS_KEYSWITCH, slot, B, glwe_in, glwe_out);
+}
+spf_status spf_glwe_automorphism_batch(spf_ctx* c, uint32_t round, size_t B, const uint64_t* glwe_in, uint64_t* glwe_out)
+{
+    return glwe_ks_batch(c, GLWE_KS_AUTOMORPHISM, round, B, glwe_in, glwe_out);
+}
+spf_status spf_glwe_trace_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, uint64_t* glwe_out)
+{
+    return glwe_ks_batch(c, GLWE_KS_TRACE, 0, B, glwe_in, glwe_out);
+}
+
+const char* spf_last_glwe_keyswitch_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_glwe_ks_kernel;
 }
 
 const char* spf_last_blind_rotate_kernel(spf_ctx* c)

@@ -108,6 +108,8 @@ inline BatchShape glwe_poly_batch_shape(const spf_params& p, size_t M, size_t K)
 {
     return {1, {K * glwe_words(p), 0, 0}, M * glwe_words(p), kBatchMaxRows / (M > K ? M : K ? K : 1)};
 }
+// GLWE keyswitch, one automorphism round and the trace: one GLWE in, one GLWE out, one unit per item
+inline BatchShape glwe_ks_shape(const spf_params& p) { return kinds_shape(p, kBatchMax, SPF_VAL_GLWE1, SPF_VAL_GLWE1); }
 
 // ---------------------------------------------------------------- the operation table
 namespace spf_ops {

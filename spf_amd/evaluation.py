@@ -118,6 +118,17 @@ class Evaluation:
     def glwe_poly_linear(self, output: np.ndarray, input: np.ndarray, slot: int):
         self._store(output, self.engine.glwe_poly_linear(slot, input))
 
+    # `keyswitch_glwe_to_glwe` (ops/fft_ops.rs:457-495) under the key of slot `slot` (load_glwe_keyswitch_key_std) and `trace`
+    # (ops/automorphisms/mod.rs:53-85) under the automorphism key: (B, k+1, N) GLWEs -> (B, k+1, N)
+    def load_glwe_keyswitch_key_std(self, slot: int, key: np.ndarray, radix_log: int, radix_count: int):
+        self.engine.load_glwe_keyswitch_key_std(slot, key, radix_log, radix_count)
+
+    def keyswitch_glwe_to_glwe(self, output: np.ndarray, input: np.ndarray, slot: int):
+        self._store(output, self.engine.glwe_keyswitch(slot, input))
+
+    def trace(self, output: np.ndarray, input: np.ndarray):
+        self._store(output, self.engine.glwe_trace(input))
+
     # generalized_programmable_bootstrap (programmable_bootstrapping.rs:342-410)
     def generalized_programmable_bootstrap(self, output, input, lut, log_chi: int, log_v: int):
         self._store(output, self.engine.generalized_pbs(input, lut, log_chi, log_v, 0))
