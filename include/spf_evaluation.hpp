@@ -424,6 +424,28 @@ class FheCircuit {
         Evaluation::check(spf_graph_add_glwe_poly_linear(g_, slot, glwes.data(), glwes.size(), M, rows.data()), ctx_);
         return rows;
     }
+    // `keyswitch_glwe_to_glwe` (fft_ops.rs:457-495) under keyswitch-key slot `slot` (Evaluation::load_glwe_keyswitch_key), one
+    // round of the trace's loop (ops/automorphisms/mod.rs:72-83; `round` in 1 .. log2 N) and `trace` (ops/automorphisms/mod.rs:53-85)
+    // as nodes — no FheOps in the reference: one GLWE1 node over the GLWE1 node `glwe` from anywhere in the graph.  The keys are
+    // read by run(); a refused call throws and adds nothing
+    Node glwe_keyswitch(uint32_t slot, Node glwe)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_glwe_keyswitch(g_, slot, glwe, &n), ctx_);
+        return n;
+    }
+    Node glwe_automorphism(uint32_t round, Node glwe)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_glwe_automorphism(g_, round, glwe, &n), ctx_);
+        return n;
+    }
+    Node glwe_trace(Node glwe)
+    {
+        Node n = 0;
+        Evaluation::check(spf_graph_add_glwe_trace(g_, glwe, &n), ctx_);
+        return n;
+    }
     // FheOp::Output*: `host` is written by every run()
     void output(Node node, void* host) { Evaluation::check(spf_graph_add_output(g_, node, host), ctx_); }
     void run() { Evaluation::check(spf_graph_run(g_), ctx_); }

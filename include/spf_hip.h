@@ -560,7 +560,8 @@ const char *spf_last_glwe_poly_kernel(spf_ctx *ctx);
  * launch whatever B (B <= 2^31 - 1), and use no buffer of the context.  "glwe_keyswitch" of spf_last_kernel_ms times all three.
  * N = 2048, k = 1 with a radix of 6 levels x 7 bits (DEFAULT_128's automorphism key) runs the hand-written "glwe_ks_kernel",
  * every other shape — a generic context, or another radix on a tuned one — "generic_glwe_ks_kernel";
- * spf_last_glwe_keyswitch_kernel names the kernel of the last call.  The group forms: the key goes to every member, B is dealt in
+ * spf_last_glwe_keyswitch_kernel names the kernel of the last call (the nodes of a gate graph, spf_graph_add_glwe_keyswitch below,
+ * add "glwe_ks_rows_kernel" and "generic_glwe_ks_rows_kernel").  The group forms: the key goes to every member, B is dealt in
  * contiguous shards. */
 typedef enum spf_glwe_ksk_limits { SPF_GLWE_KSK_SLOTS = 16 } spf_glwe_ksk_limits;
 spf_status spf_load_glwe_keyswitch_key_std(spf_ctx *ctx, uint32_t slot, const uint64_t *key, size_t n_words, uint32_t radix_log,
@@ -874,6 +875,37 @@ spf_status spf_graph_add_lwe_linear(spf_graph *graph, uint32_t slot, const uint3
  * SPF_ERR_NO_KEY and a slot whose (M, K) is not the nodes' is SPF_ERR_INVALID_ARGUMENT with both shapes in the message. */
 spf_status spf_graph_add_glwe_poly_linear(spf_graph *graph, uint32_t slot, const uint32_t *glwe_nodes /* K */, size_t K,
                                           size_t M, uint32_t *nodes_out /* M */);
+/* The three operations of spf_glwe_keyswitch_* / spf_glwe_automorphism_* / spf_glwe_trace_* above as node constructors — no FheOp
+ * there, no spf_graph_op here:
+ *   spf_graph_add_glwe_keyswitch     `keyswitch_glwe_to_glwe` (sunscreen_tfhe/src/ops/fft_ops.rs:457-495; integer twin
+ *                                    ops/keyswitch/glwe_keyswitch.rs:26-55) under the key in `slot`
+ *   spf_graph_add_glwe_automorphism  one round of the trace's loop (`polynomial_pow_k`, ops/polynomial/mod.rs:62-84, then the
+ *                                    keyswitch back: ops/automorphisms/mod.rs:72-83), `round` in 1 .. log2 N
+ *   spf_graph_add_glwe_trace         `trace` (ops/automorphisms/mod.rs:53-85)
+ * glwe_node is ONE glwe1 node of any origin (an input, a trivial constant, a CMUX or blind rotation result, a pack, a public
+ * functional keyswitch, a row of a polynomial linear map, another of these nodes); each call creates one ordinary glwe1 node one
+ * level above it, word-equal to the batch entry point at B = 1 over that GLWE: an operand of any operation that takes a glwe1, an
+ * output, counted by spf_graph_stats.  A packed integer that changes its key, a GLWE traced behind an X^-j polynomial map to isolate
+ * one coefficient, stay inside one spf_graph_run.  All such nodes of one level with one operation and one slot (or round) are one
+ * group and ONE launch whatever their number: operands that lie consecutively in the graph's memory go to "glwe_ks_kernel" /
+ * "generic_glwe_ks_kernel" in place, anything else to "glwe_ks_rows_kernel" / "generic_glwe_ks_rows_kernel", which read the GLWEs
+ * where they lie through a pointer table (the same operand may stand in it several times) — the names
+ * spf_last_glwe_keyswitch_kernel then gives; timed as "glwe_keyswitch".
+ * SPF_ERR_INVALID_ARGUMENT from the call, with the offending numbers in the message, *node_out not written, nothing recorded and
+ * the graph still usable: a null graph or node_out, glwe_node that is no node of the graph or no glwe1, slot >=
+ * SPF_GLWE_KSK_SLOTS, round outside 1 .. log2 N.
+ * Keys are read by spf_graph_run, before anything is enqueued and on the replay of a captured graph as well.  The keyswitch-key
+ * slot may be loaded after the graph is built and loaded again between runs under the rule of the key loads: an empty slot is
+ * SPF_ERR_NO_KEY, the next run after a load uses the new key (and the kernel its radix asks for); a load counts on the context,
+ * and a captured graph (SPF_GRAPH_CAPTURE=1) that holds keyswitch nodes is dropped and captured anew when the count has moved.
+ * Automorphism and trace nodes read the context's automorphism key at tr_radix: no key is SPF_ERR_NO_KEY, a tr_radix that no kernel
+ * serves SPF_ERR_UNSUPPORTED with the text of the batch entry points.  spf_load_automorphism_key_* rewrites the key's one device
+ * buffer in place, so a captured graph is KEPT over a reload and its replay reads the new key — what the circuit bootstrap nodes
+ * of a captured graph do.  A graph of a group reads the keys of the member it runs on.
+ * Not there yet: a row of the operation table, a lane of the pool, a submit by handle. */
+spf_status spf_graph_add_glwe_keyswitch(spf_graph *graph, uint32_t slot, uint32_t glwe_node, uint32_t *node_out);
+spf_status spf_graph_add_glwe_automorphism(spf_graph *graph, uint32_t round, uint32_t glwe_node, uint32_t *node_out);
+spf_status spf_graph_add_glwe_trace(spf_graph *graph, uint32_t glwe_node, uint32_t *node_out);
 /* FheOp::Output*: copy the node's value to `host` at the end of every run.  Plain (pageable) buffers: the run gathers every
  * output on the device and brings them back in ONE copy through the graph's own pinned staging (inputs go up the same way);
  * per-output copies to pageable memory cost ~20 us each on this runtime — 0.68 ms of a 32-bit addition's 5.5. */

@@ -159,6 +159,9 @@ SYMBOLS = [
     ("spf_graph_add_public_functional_keyswitch", _I, [_P, C.POINTER(_U32), _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_lwe_linear", _I, [_P, _U32, C.POINTER(_U32), _SZ, _SZ, C.POINTER(_U32)]),
     ("spf_graph_add_glwe_poly_linear", _I, [_P, _U32, C.POINTER(_U32), _SZ, _SZ, C.POINTER(_U32)]),
+    ("spf_graph_add_glwe_keyswitch", _I, [_P, _U32, _U32, C.POINTER(_U32)]),
+    ("spf_graph_add_glwe_automorphism", _I, [_P, _U32, _U32, C.POINTER(_U32)]),
+    ("spf_graph_add_glwe_trace", _I, [_P, _U32, C.POINTER(_U32)]),
     ("spf_graph_add_output", _I, [_P, _U32, _P]),
     ("spf_graph_run", _I, [_P]),
     ("spf_graph_stats", _I, [_P, C.POINTER(_U32), C.POINTER(_U32), C.POINTER(_U32)]),

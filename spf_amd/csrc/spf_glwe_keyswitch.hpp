@@ -10,11 +10,15 @@
 // the two trace kernels, which is the oracle's: same words.
 //   glwe_ks_kernel<6, 7, MODE>  N = 2048, k = 1, radix 6 levels x 7 bits: the schedule of cbs_trace_kernel
 //   generic_glwe_ks_kernel      every other shape: one workgroup per GLWE over generic_glev_mad / generic_poly_ifft
+//   glwe_ks_rows_kernel<6, 7, MODE>, generic_glwe_ks_rows_kernel   their twins for operands where they lie, through a pointer
+//                               table (a level of a gate graph); the output must not overlap any operand there
 // One launch per call, items on grid.x.  `out == in` exactly is allowed in every mode (each work unit reads the whole of its own
 // item, and nothing else, before the first workgroup barrier, and stores to its own item only behind it).
 #pragma once
 #include "spf_cbs_tail.hpp"
 #include "spf_generic.hpp"
+
+#include <type_traits>
 
 namespace spf {
 
@@ -27,6 +31,20 @@ struct GlweKsArgs {
     const c64* tables;
     uint32_t units;      // B
     uint32_t kk;         // GLWE_KS_AUTOMORPHISM: the power of the round, N / 2^(round-1) + 1
+};
+
+// The same launch over operands where they lie (a level of a gate graph, spf_graph.hpp): item u is read through in_rows[u], the
+// output stays `units` consecutive GLWEs.  Aliasing contract of the rows form: the output rows of a launch are disjoint from
+// EVERY operand row of that launch — trace and automorphism park into a unit's output row before other workgroups have
+// necessarily read their inputs, so `out == in` of the in-place form has no counterpart here.  The same operand may stand in the
+// table several times (read-only).
+struct GlweKsRowsArgs {
+    const uint64_t* const* in_rows; // [B] device pointers to GLWEs of 4096 words
+    uint64_t* out;                  // B x 4096, disjoint from every row of in_rows
+    const c64* key;
+    const c64* tables;
+    uint32_t units;
+    uint32_t kk;
 };
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -42,9 +60,13 @@ struct GlweKsArgs {
 // keyswitch, without the gather, holds everything in registers.  The first store to an item is
 // behind the workgroup barrier that follows the loads of every unit of the workgroup, padding units included — a padding unit
 // of a ragged last workgroup is a duplicate of the last item, lives in that item's workgroup and stores nothing.
-template <int L, int LOGB, int W, int MODE>
-__device__ __forceinline__ void glwe_ks_body(const GlweKsArgs& a, char* smem)
+// `Args` is GlweKsArgs or GlweKsRowsArgs: only the entry loads differ.  The rows form loads the item's pointer once per wave (the
+// unit is wave-uniform: a scalar load) where the in-place form computes in + unit * 2N; park, padding units and the wait in front of
+// the first barrier are the same.
+template <int L, int LOGB, int W, int MODE, class Args>
+__device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
 {
+    constexpr bool kRows = std::is_same<Args, GlweKsRowsArgs>::value;
     static_assert(L == 6 && LOGB == 7, "three digit pairs; the state after the first pair fits 32 bits");
     constexpr int XP = 2;
     constexpr int NT = 512;
@@ -61,6 +83,15 @@ __device__ __forceinline__ void glwe_ks_body(const GlweKsArgs& a, char* smem)
     char* mine = tile + w * 8192;
     char* theirs = tile + (w ^ 1) * 8192;
     char* ring = smem + kTableBytes + kWavesPerBlock * kWaveBufBytes;
+    // rows form: the item's pointer first — wave-uniform index, ONE scalar load per wave (a padding unit takes the last item's, as
+    // below).  The table is read through the constant address space (nothing writes it while the kernel runs): as a plain global
+    // load hipcc made it scalar in the W = 0 body only, and a vector load of one address in all lanes in the other
+    [[maybe_unused]] gu64_cptr row_in = nullptr;
+    if constexpr (kRows) {
+        typedef const uint64_t* const __attribute__((address_space(4))) * table_ptr;
+        const uint32_t u = blockIdx.x * kWavesPerBlock + cslot;
+        row_in = global_view(((table_ptr)(uintptr_t)a.in_rows)[u < a.units ? u : a.units - 1]);
+    }
     {
         const double2* src = reinterpret_cast<const double2*>(a.tables);
         double2* dst = reinterpret_cast<double2*>(smem);
@@ -85,7 +116,15 @@ __device__ __forceinline__ void glwe_ks_body(const GlweKsArgs& a, char* smem)
     ring_dma(0);
 
     uint64_t accm[16], accb[16];
-    {
+    if constexpr (kRows) {
+        // (a pointer fetched from memory is generic to the compiler: the view pins it to global, loads that count on vmcnt alone)
+        gu64_cptr g = row_in;
+#pragma unroll
+        for (int e = 0; e < 16; e++) {
+            accm[e] = g[coef2(e, lane, w)];
+            accb[e] = g[kN + coef2(e, lane, w)];
+        }
+    } else {
         const uint64_t* g = a.in + (size_t)unit * 2 * kN;
 #pragma unroll
         for (int e = 0; e < 16; e++) {
@@ -350,6 +389,15 @@ __global__ __launch_bounds__(512, 2) void glwe_ks_kernel(GlweKsArgs a)
     else glwe_ks_body<L, LOGB, 0, MODE>(a, smem);
 }
 
+// The rows form (GlweKsRowsArgs above): same grid, same LDS, same body
+template <int L, int LOGB, int MODE>
+__global__ __launch_bounds__(512, 2) void glwe_ks_rows_kernel(GlweKsRowsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) glwe_ks_body<L, LOGB, 1, MODE>(a, smem);
+    else glwe_ks_body<L, LOGB, 0, MODE>(a, smem);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 struct GenericGlweKsArgs {
     GenericShape g;
@@ -376,6 +424,53 @@ __global__ __launch_bounds__(kGenericThreads) void generic_glwe_ks_kernel(Generi
     uint64_t* X = state + 2 * N;
     uint64_t* G = X + len;
     const uint64_t* in = a.in + (size_t)blockIdx.x * len;
+    for (uint32_t i = tid; i < len; i += kGenericThreads) X[i] = in[i];
+    __syncthreads();
+    const bool trace = a.mode == GLWE_KS_TRACE;
+    const uint32_t rounds = trace ? g.logN : 1;
+    const size_t glev_len = (size_t)a.count * (k + 1) * h, ksk_len = (size_t)k * glev_len;
+    for (uint32_t it = 0; it < rounds; it++) {
+        const uint32_t kk = trace ? (N >> it) + 1 : a.mode == GLWE_KS_AUTOMORPHISM ? a.kk : 1;
+        // polynomial_pow_k (ops/polynomial/mod.rs:62-84): p_k[(i kk) mod N] = +-p[i], minus when (i kk) / N is odd; kk = 1: a copy
+        for (uint32_t i = tid; i < len; i += kGenericThreads) {
+            const uint32_t p = i / N, c = i % N, prod = c * kk;
+            const uint64_t v = X[i];
+            G[p * N + (prod & (N - 1))] = ((prod >> g.logN) & 1) ? (uint64_t)0 - v : v;
+        }
+        for (uint32_t i = tid; i < (k + 1) * h; i += kGenericThreads) accf[i] = {0.0, 0.0};
+        __syncthreads();
+        const c64* ksk = a.key + (size_t)it * ksk_len;
+        for (uint32_t r = 0; r < k; r++)
+            generic_glev_mad(g, accf, buf, state, ksk + (size_t)r * glev_len, a.radix_log, a.count,
+                             [&](uint32_t i) { return G[r * N + i]; });
+        // trivial(b_k) - ks, on top of x in the trace
+        for (uint32_t q = 0; q <= k; q++)
+            generic_poly_ifft(g, accf + (size_t)q * h, buf, tmp, [&](uint32_t i, uint64_t t) {
+                const uint64_t ks = (q == k ? G[k * N + i] : (uint64_t)0) - t;
+                X[q * N + i] = trace ? X[q * N + i] + ks : ks;
+            });
+    }
+    uint64_t* out = a.out + (size_t)blockIdx.x * len;
+    for (uint32_t i = tid; i < len; i += kGenericThreads) out[i] = X[i];
+}
+
+// The rows form (a level of a gate graph): item b is in_rows[b] (a.in is not read), the output a.out's B consecutive GLWEs, disjoint
+// from every operand row (the contract of GlweKsRowsArgs; this kernel stores only at its end, but the contract is one for both).
+// A sibling, not a shared body: with the loop in a __forceinline__ function of both kernels hipcc gave generic_glwe_ks_kernel 156
+// VGPRs (arguments by reference) or 128 (by value) where it has 124 as written above; only the entry load differs — keep the two
+// in step.
+__global__ __launch_bounds__(kGenericThreads) void generic_glwe_ks_rows_kernel(GenericGlweKsArgs a, const uint64_t* const* in_rows)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const GenericShape& g = a.g;
+    const uint32_t tid = threadIdx.x, N = g.N, h = N / 2, k = g.k, len = (k + 1) * N;
+    c64* accf = reinterpret_cast<c64*>(smem);
+    c64* buf = accf + (size_t)(k + 1) * h;
+    uint64_t* state = reinterpret_cast<uint64_t*>(buf + h);
+    c64* tmp = reinterpret_cast<c64*>(state + N);
+    uint64_t* X = state + 2 * N;
+    uint64_t* G = X + len;
+    gu64_cptr in = global_view(in_rows[blockIdx.x]); // (a fetched pointer is generic to the compiler: pinned to global)
     for (uint32_t i = tid; i < len; i += kGenericThreads) X[i] = in[i];
     __syncthreads();
     const bool trace = a.mode == GLWE_KS_TRACE;

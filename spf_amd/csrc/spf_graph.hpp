@@ -51,6 +51,13 @@
 // that lie consecutively go to the batch kernels in place, anything else is ONE launch of glwe_poly_lds_rows_kernel or
 // glwe_poly_stream_rows_kernel over a pointer table.  The slot is read when the graph runs, as a linear node's.
 //
+// The GLWE keyswitch, one automorphism round and the homomorphic trace (spf_glwe_keyswitch.hpp) are three more constructors over ONE
+// GLWE1 node from anywhere: spf_graph_add_glwe_keyswitch / _automorphism / _trace — a packed integer that changes its key, a GLWE
+// traced behind an X^-j polynomial map to isolate one coefficient.  All nodes of one level with one mode and one slot (or round) are
+// one group and ONE launch: operands that lie consecutively go to glwe_ks_kernel / generic_glwe_ks_kernel in place, anything else
+// to their rows twins over a pointer table.  The keyswitch-key slot is read when the graph runs; the automorphism key is the
+// context's, rewritten in place by a load, so a captured graph is kept over its reload as with circuit bootstrap nodes.
+//
 // What is decided before a device is touched — levels, groups and their order, arena offsets, in place or through a pointer row,
 // the order of the CMUX units, the size of the stage buffers — is spf_graph_plan.hpp's, free of HIP and checked on the CPU; here
 // are the handle, the node constructors with their checks, the device memory of a plan and the launches.
@@ -130,6 +137,7 @@ struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
     hipGraphExec_t exec = nullptr;
     uint64_t exec_epoch = 0, exec_lin_epoch = 0; // (the second: the context's count of weight loads, for a graph with linear nodes)
     uint64_t exec_gpoly_epoch = 0;               // (its count of polynomial weight loads, for a graph with polynomial linear nodes)
+    uint64_t exec_gksk_epoch = 0;                // (its count of GLWE keyswitch-key loads, for a graph with GLWE keyswitch nodes)
     uint32_t runs_since_plan = 0, captured_launches = 0;
 
     void drop_exec()
@@ -155,6 +163,12 @@ struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
 namespace spf_graph_impl {
 
 using namespace spf_graph_plan; // (the node kinds, op_row, align_up, units_per_node)
+
+// GlweKsMode (spf_glwe_keyswitch.hpp) of a GLWE keyswitch, automorphism or trace node
+inline int glwe_ks_mode_of(int32_t op)
+{
+    return op == kNodeGlweKeyswitch ? GLWE_KS_KEYSWITCH : op == kNodeGlweAutomorphism ? GLWE_KS_AUTOMORPHISM : GLWE_KS_TRACE;
+}
 
 // The plan of spf_graph_plan.hpp and its device memory.  Called by the first run after the graph changed.
 inline spf_status plan(spf_graph* g)
@@ -248,6 +262,17 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                                       ? spf_glwe_poly_linear_enqueue(c, s, gr.key.slot, layers, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out)
                                       : launch_glwe_poly_rows(c, s, gr.key.slot, layers, g->d_arena,
                                                               (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
+            if (st != SPF_OK) return st;
+            g->n_launches++;
+            continue;
+        }
+        if (spf_graph_plan::is_glwe_ks_node(gr.key.op)) { // (one launch either way; the parameter is the slot or the round)
+            const int mode = glwe_ks_mode_of(gr.key.op);
+            // rows form: the output block overlaps no operand — operands are rows of earlier levels (or inputs), and a group's
+            // output is a fresh block of its own level (spf_graph_plan::lay_out), which is what the rows kernels' parking needs
+            const spf_status st = gr.contiguous[0]
+                                      ? glwe_ks_enqueue(c, s, mode, (uint32_t)gr.key.n, B, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out)
+                                      : launch_glwe_ks_rows(c, s, mode, (uint32_t)gr.key.n, B, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
             if (st != SPF_OK) return st;
             g->n_launches++;
             continue;
@@ -366,6 +391,18 @@ inline spf_status check_glwe_poly_slots(spf_graph* g)
     return SPF_OK;
 }
 
+// ... and the keys of the GLWE keyswitch, automorphism and trace groups: an empty keyswitch-key slot or a missing automorphism key
+// is SPF_ERR_NO_KEY, a tr_radix no kernel serves SPF_ERR_UNSUPPORTED, with the texts of the batch entry points (glwe_ks_args)
+inline spf_status check_glwe_ks_keys(spf_graph* g)
+{
+    for (const auto& gr : g->groups)
+        if (spf_graph_plan::is_glwe_ks_node(gr.key.op)) {
+            const spf_status st = glwe_ks_args(g->ctx, glwe_ks_mode_of(gr.key.op), (uint32_t)gr.key.n, 0, nullptr, nullptr);
+            if (st != SPF_OK) return st;
+        }
+    return SPF_OK;
+}
+
 // Output staging (after plan(): needs the arena offsets): outputs grouped by value size, one pointer row per group
 inline spf_status plan_outputs(spf_graph* g)
 {
@@ -420,6 +457,10 @@ inline spf_status run(spf_graph* g)
         spf_status st = check_glwe_poly_slots(g);
         if (st != SPF_OK) return st;
     }
+    if (g->has_glwe_ks) {
+        spf_status st = check_glwe_ks_keys(g);
+        if (st != SPF_OK) return st;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t k = g->prm.glwe_size, N = g->prm.polynomial_degree;
@@ -459,6 +500,7 @@ inline spf_status run(spf_graph* g)
     if (g->exec && g->exec_epoch != c->buf_epoch) g->drop_exec(); // a scratch buffer moved since the capture
     if (g->exec && g->has_linear && g->exec_lin_epoch != c->lin_epoch) g->drop_exec(); // a weight slot was loaded: its old image is freed
     if (g->exec && g->has_glwe_poly && g->exec_gpoly_epoch != c->gpoly_epoch) g->drop_exec(); // ... a polynomial weight slot
+    if (g->exec && g->has_glwe_ks && g->exec_gksk_epoch != c->gksk_epoch) g->drop_exec(); // ... a keyswitch-key slot (another buffer, maybe another kernel)
     if (g->exec) {
         HIPCHK(c, hipGraphLaunch(g->exec, s));
         g->n_launches = g->captured_launches;
@@ -475,6 +517,7 @@ inline spf_status run(spf_graph* g)
                 g->exec_epoch = c->buf_epoch;
                 g->exec_lin_epoch = c->lin_epoch;
                 g->exec_gpoly_epoch = c->gpoly_epoch;
+                g->exec_gksk_epoch = c->gksk_epoch;
                 g->captured_launches = g->n_launches;
             } else {
                 g->exec = nullptr;
@@ -725,6 +768,54 @@ spf_status spf_graph_add_glwe_poly_linear(spf_graph* g, uint32_t slot, const uin
     for (size_t m = 0; m < M; m++) nodes_out[m] = first + (uint32_t)m;
     g->planned = false;
     return SPF_OK;
+}
+
+// `keyswitch_glwe_to_glwe`, one round of the trace's loop and `trace` (spf_glwe_keyswitch.hpp) as node constructors: one GLWE1
+// operand in Node::in[0], one GLWE1 node, Node::param = the keyswitch-key slot / the round / 0.  The keys are looked at by
+// spf_graph_run, not here.  `what` names the call in the messages; nothing is written to *node_out before the node exists
+static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, uint32_t param, uint32_t glwe_node, uint32_t* node_out)
+{
+    if (!g) return SPF_ERR_INVALID_ARGUMENT;
+    const std::string w = std::string("graph ") + what;
+    if (!node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": null pointer");
+    if (op == spf_graph_plan::kNodeGlweKeyswitch && param >= SPF_GLWE_KSK_SLOTS)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": slot " + std::to_string(param) + " >= SPF_GLWE_KSK_SLOTS = " + std::to_string(SPF_GLWE_KSK_SLOTS));
+    if (op == spf_graph_plan::kNodeGlweAutomorphism) {
+        uint32_t log_n = 0;
+        while (((size_t)1 << (log_n + 1)) <= g->prm.polynomial_degree) log_n++;
+        if (param < 1 || param > log_n)
+            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": round " + std::to_string(param) + " outside 1 .. log2 N = " + std::to_string(log_n));
+    }
+    if (glwe_node >= g->nodes.size())
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": operand " + std::to_string(glwe_node) + " is not a node of this graph (" +
+                                                          std::to_string(g->nodes.size()) + " nodes)");
+    if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": operand " + std::to_string(glwe_node) + " is not an L1 GLWE (its kind is " +
+                                                          std::to_string(g->nodes[glwe_node].kind) + ")");
+    spf_graph_plan::Node n{};
+    n.op = op; n.kind = SPF_VAL_GLWE1; n.n_in = 1; n.in[0] = glwe_node; n.param = param;
+    uint32_t id;
+    try {
+        id = g->add(n);
+    } catch (const std::exception&) {
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    *node_out = id;
+    g->planned = false;
+    return SPF_OK;
+}
+
+spf_status spf_graph_add_glwe_keyswitch(spf_graph* g, uint32_t slot, uint32_t glwe_node, uint32_t* node_out)
+{
+    return graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweKeyswitch, "GLWE keyswitch", slot, glwe_node, node_out);
+}
+spf_status spf_graph_add_glwe_automorphism(spf_graph* g, uint32_t round, uint32_t glwe_node, uint32_t* node_out)
+{
+    return graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweAutomorphism, "GLWE automorphism", round, glwe_node, node_out);
+}
+spf_status spf_graph_add_glwe_trace(spf_graph* g, uint32_t glwe_node, uint32_t* node_out)
+{
+    return graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweTrace, "GLWE trace", 0, glwe_node, node_out);
 }
 
 // `blind_rotation` (blind_rotation.rs:202-223) as a node constructor: n_bits chained GLWE1 nodes,

@@ -24,8 +24,15 @@
 namespace spf_graph_plan {
 
 // the node constructors that are no spf_graph_op (spf_graph_add_unpack / spf_graph_add_pack / spf_graph_add_blind_rotation /
-// spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear / spf_graph_add_glwe_poly_linear)
-enum : int32_t { kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68, kNodeGlwePolyLinear = 69 };
+// spf_graph_add_public_functional_keyswitch / spf_graph_add_lwe_linear / spf_graph_add_glwe_poly_linear /
+// spf_graph_add_glwe_keyswitch / spf_graph_add_glwe_automorphism / spf_graph_add_glwe_trace)
+enum : int32_t {
+    kNodeUnpack = 64, kNodePack = 65, kNodeRotCmux = 66, kNodePufks = 67, kNodeLweLinear = 68, kNodeGlwePolyLinear = 69,
+    kNodeGlweKeyswitch = 70, kNodeGlweAutomorphism = 71, kNodeGlweTrace = 72
+};
+// the three nodes of spf_glwe_keyswitch.hpp: one GLWE1 operand in Node::in[0], one GLWE1 result; Node::param is the keyswitch-key
+// slot, the round, or 0
+inline bool is_glwe_ks_node(int32_t op) { return op >= kNodeGlweKeyswitch && op <= kNodeGlweTrace; }
 
 constexpr size_t kAlign = 256;        // inputs, constants and every group's block start on a multiple of this
 constexpr size_t kNull = (size_t)-1;  // a table entry that is no arena offset but a null pointer
@@ -35,7 +42,7 @@ struct Node {
     int32_t op;        // spf_graph_op, one of the kNode constructors, or -1 input, -2 trivial constant
     int32_t kind;      // spf_value_kind of the value the node produces
     uint64_t param;    // SampleExtract index / MulXN amount / trivial bit / bit index of an unpack node / rotation of a rotate-CMUX node /
-                       // row index m of a linear node
+                       // row index m of a linear node / keyswitch-key slot of a GLWE keyswitch node / round of an automorphism node
     uint32_t in[3];    // (rotate-CMUX nodes: {selector, accumulator})
     uint32_t n_in;
     uint32_t count;    // unpack nodes: the bit nodes of their call (the integer's width); nodes with an operand list: its length
@@ -125,7 +132,8 @@ inline Sizes sizes_of(const spf_params& p, bool pufks_stage)
 
 // What the nodes of one launch have in common.  Groups run, and lie in the arena, in the order of their keys: by level, then
 // operation, then — public functional keyswitch: (operand kind, lwe_count); linear map and polynomial linear map: (operand kind,
-// slot, M, K); unpack and pack: the width; every other operation: its parameter.
+// slot, M, K); unpack and pack: the width; every other operation: its parameter (GLWE keyswitch: the slot, automorphism: the round,
+// trace: 0 — the operation is the mode).
 struct GroupKey {
     uint32_t level;
     int32_t op;
@@ -168,6 +176,7 @@ struct Plan {
     bool has_pufks = false;  // public functional keyswitch nodes: any
     bool has_linear = false; // linear nodes: any (their weight slots are checked at every run)
     bool has_glwe_poly = false; // polynomial linear nodes: any (likewise)
+    bool has_glwe_ks = false;   // GLWE keyswitch, automorphism or trace nodes: any (their keys are checked at every run)
 };
 
 // the table row (spf_ops.hpp) of a node's operation: a spf_graph_op that spf_graph_add_op has accepted
@@ -361,6 +370,15 @@ inline void plan_access(const Graph& g, const Sizes& sz, Plan& p)
             // through the table by the rows kernels; nothing is gathered
             p.has_glwe_poly = true;
             const std::vector<size_t> offs = listed(gr.key.rows);
+            read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), false);
+        } else if (is_glwe_ks_node(op)) {
+            // one GLWE per member: in place when they lie consecutively (the batch kernels), else read through the table by the
+            // rows kernels, which park into the group's output rows while other workgroups still read: those rows are this group's
+            // own fresh block (lay_out), its operands rows of earlier levels — disjoint
+            p.has_glwe_ks = true;
+            std::vector<size_t> offs;
+            offs.reserve(B);
+            for (uint32_t id : gr.members) offs.push_back(off_of(g.nodes[id].in[0]));
             read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), false);
         } else if (op == kNodePack) {
             // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table

@@ -199,6 +199,7 @@ struct spf_ctx {
     GlweKskSlot gksk[SPF_GLWE_KSK_SLOTS];
     bool glwe_ks_generic_ready = false;
     const char* last_glwe_ks_kernel = "";
+    uint64_t gksk_epoch = 0; // bumped by every spf_load_glwe_keyswitch_key_std (captured gate graphs hold a slot's pointer and kernel)
 };
 
 namespace {
@@ -746,6 +747,8 @@ static spf_status glwe_ks_prepare_generic(spf_ctx* c)
     }
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
     c->glwe_ks_generic_ready = true;
     return SPF_OK;
 }
@@ -830,6 +833,8 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                                (int)generic_lds_bytes(N, params->glwe_size, false)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)generic_trace_lds_bytes(N, params->glwe_size)));
         c->glwe_ks_generic_ready = true;
         *out = c;
         return SPF_OK;
@@ -873,6 +878,12 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_kernel<6, 7, GLWE_KS_AUTOMORPHISM>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_kernel<6, 7, GLWE_KS_KEYSWITCH>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_rows_kernel<6, 7, GLWE_KS_TRACE>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_rows_kernel<6, 7, GLWE_KS_AUTOMORPHISM>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_rows_kernel<6, 7, GLWE_KS_KEYSWITCH>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
 #undef CK
     // an automorphism key of another radix than the hand-written kernel's: spf_glwe_automorphism_* / spf_glwe_trace_* run the
@@ -3394,6 +3405,7 @@ spf_status spf_load_glwe_keyswitch_key_std(spf_ctx* c, uint32_t slot, const uint
     GlweKskSlot& l = c->gksk[slot];
     if (l.d_key) (void)hipFree(l.d_key);
     l = GlweKskSlot{};
+    c->gksk_epoch++;
     c64* d = nullptr;
     HIPCHK(c, hipMalloc((void**)&d, n_words * 8));
     // the words go in as they are (same bytes as their spectra) and are transformed in place, as the other _std loaders do
@@ -3452,10 +3464,34 @@ static spf_status glwe_ks_args(spf_ctx* c, int mode, uint32_t arg, size_t B, con
 }
 
 // ONE launch whatever B <= kBatchMax: four items per workgroup (hand-written) or one (generic) on grid.x; no buffer of the context.
+// With `d_rows` (a level of a gate graph, spf_graph.hpp): item b is d_rows[b], a device table of B device pointers, d_in is unused and
+// d_out overlaps none of the items — the planner's guarantee: operands are rows of earlier levels, a level's outputs are fresh rows
+// (the rows kernels park into d_out while other workgroups still read).  Still one launch.
+static spf_status glwe_ks_launch(spf_ctx* c, void* stream, int mode, uint32_t arg, size_t B, const uint64_t* d_in,
+                                 const uint64_t* const* d_rows, uint64_t* d_out);
+
 static spf_status glwe_ks_enqueue(spf_ctx* c, void* stream, int mode, uint32_t arg, size_t B, const uint64_t* d_in, uint64_t* d_out)
 {
     spf_status st = glwe_ks_args(c, mode, arg, B, d_in, d_out);
     if (st != SPF_OK || B == 0) return st;
+    return glwe_ks_launch(c, stream, mode, arg, B, d_in, nullptr, d_out);
+}
+
+// The same over operands where they lie; the checks of glwe_ks_args that concern the key, none on the table's contents
+static spf_status launch_glwe_ks_rows(spf_ctx* c, hipStream_t s, int mode, uint32_t arg, size_t B, const uint64_t* const* d_rows, uint64_t* d_out)
+{
+    spf_status st = glwe_ks_args(c, mode, arg, 0, nullptr, nullptr);
+    if (st != SPF_OK) return st;
+    if (batch_limit(c, glwe_ks_shape(c->prm), B) != SPF_OK) return SPF_ERR_INVALID_ARGUMENT;
+    if (B == 0) return SPF_OK;
+    if (!d_rows || !d_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    return glwe_ks_launch(c, s, mode, arg, B, nullptr, d_rows, d_out);
+}
+
+static spf_status glwe_ks_launch(spf_ctx* c, void* stream, int mode, uint32_t arg, size_t B, const uint64_t* d_in,
+                                 const uint64_t* const* d_rows, uint64_t* d_out)
+{
+    spf_status st;
     std::lock_guard<std::recursive_mutex> g(c->mu);
     const bool ks = mode == GLWE_KS_KEYSWITCH;
     const uint32_t radix_log = ks ? c->gksk[arg].radix_log : c->prm.tr_radix_log, count = ks ? c->gksk[arg].radix_count : c->prm.tr_radix_count;
@@ -3469,16 +3505,25 @@ static spf_status glwe_ks_enqueue(spf_ctx* c, void* stream, int mode, uint32_t a
     st = ts.begin();
     if (st != SPF_OK) return st;
     if (glwe_ks_tuned(c, radix_log, count)) {
-        GlweKsArgs a{d_in, d_out, key, c->d_tables, (uint32_t)B, kk};
         const dim3 grid((unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock)), block(512);
-        if (mode == GLWE_KS_TRACE) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_TRACE>), grid, block, kTraceLds, s, a);
-        else if (mode == GLWE_KS_AUTOMORPHISM) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_AUTOMORPHISM>), grid, block, kTraceLds, s, a);
-        else hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_KEYSWITCH>), grid, block, kTraceLds, s, a);
-        c->last_glwe_ks_kernel = "glwe_ks_kernel";
+        if (d_rows) {
+            GlweKsRowsArgs a{d_rows, d_out, key, c->d_tables, (uint32_t)B, kk};
+            if (mode == GLWE_KS_TRACE) hipLaunchKernelGGL((glwe_ks_rows_kernel<6, 7, GLWE_KS_TRACE>), grid, block, kTraceLds, s, a);
+            else if (mode == GLWE_KS_AUTOMORPHISM) hipLaunchKernelGGL((glwe_ks_rows_kernel<6, 7, GLWE_KS_AUTOMORPHISM>), grid, block, kTraceLds, s, a);
+            else hipLaunchKernelGGL((glwe_ks_rows_kernel<6, 7, GLWE_KS_KEYSWITCH>), grid, block, kTraceLds, s, a);
+            c->last_glwe_ks_kernel = "glwe_ks_rows_kernel";
+        } else {
+            GlweKsArgs a{d_in, d_out, key, c->d_tables, (uint32_t)B, kk};
+            if (mode == GLWE_KS_TRACE) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_TRACE>), grid, block, kTraceLds, s, a);
+            else if (mode == GLWE_KS_AUTOMORPHISM) hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_AUTOMORPHISM>), grid, block, kTraceLds, s, a);
+            else hipLaunchKernelGGL((glwe_ks_kernel<6, 7, GLWE_KS_KEYSWITCH>), grid, block, kTraceLds, s, a);
+            c->last_glwe_ks_kernel = "glwe_ks_kernel";
+        }
     } else {
         GenericGlweKsArgs a{generic_shape(c), d_in, d_out, key, radix_log, count, (uint32_t)mode, kk};
-        hipLaunchKernelGGL(generic_glwe_ks_kernel, dim3((unsigned)B), dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a);
-        c->last_glwe_ks_kernel = "generic_glwe_ks_kernel";
+        if (d_rows) hipLaunchKernelGGL(generic_glwe_ks_rows_kernel, dim3((unsigned)B), dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a, d_rows);
+        else hipLaunchKernelGGL(generic_glwe_ks_kernel, dim3((unsigned)B), dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a);
+        c->last_glwe_ks_kernel = d_rows ? "generic_glwe_ks_rows_kernel" : "generic_glwe_ks_kernel";
     }
     HIPCHK(c, hipGetLastError());
     return ts.end();

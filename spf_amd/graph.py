@@ -77,6 +77,13 @@ GLWE_POLY_LINEAR_NODE = 69
 GLWE_POLY_SLOTS = 64       # SPF_GLWE_POLY_SLOTS
 GLWE_POLY_MAX_ROWS = 4096  # SPF_GLWE_POLY_MAX_ROWS
 _LINEAR_NODES = (NODE_LWE_LINEAR, GLWE_POLY_LINEAR_NODE)   # M nodes over one operand list, with a weight slot
+# spf_graph_add_glwe_keyswitch / _automorphism / _trace: one GLWE1 node over one GLWE1 operand, param = the keyswitch-key slot / the
+# round / 0.  No NODE_* names, for the reason above: the random generator cannot draw keyswitch keys.
+GLWE_KEYSWITCH_NODE = 70
+GLWE_AUTOMORPHISM_NODE = 71
+GLWE_TRACE_NODE = 72
+GLWE_KSK_SLOTS = 16   # SPF_GLWE_KSK_SLOTS
+_GLWE_KS_NODES = (GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE)
 
 # operand kinds of the operations whose arguments RecordedCircuit checks itself, as the library's table does (spf_ops.hpp)
 _PBS_IN_KINDS = {int(TableOp.PBS_UNIVARIATE): (0, 2), int(TableOp.PBS_BIVARIATE): (0, 0, 2)}
@@ -114,6 +121,20 @@ def _check_lwe_linear(what: str, slot, n_operands: int, M, slots: int = LWE_LINE
     if isinstance(M, bool) or not isinstance(M, (int, np.integer)) or not 0 < M <= max_rows:
         raise SpfError(1, f"{what}: M must be in 1 ..= {max_rows}, got {M!r}")
     return int(slot), int(M)
+
+
+def _check_glwe_ks(what: str, op: int, param, degree: int) -> int:
+    """the slot of add_glwe_keyswitch, the round of add_glwe_automorphism (add_glwe_trace has no parameter)"""
+    if op == GLWE_TRACE_NODE:
+        return 0
+    if isinstance(param, bool) or not isinstance(param, (int, np.integer)):
+        raise SpfError(1, f"{what}: {param!r} is not an integer")
+    if op == GLWE_KEYSWITCH_NODE and not 0 <= param < GLWE_KSK_SLOTS:
+        raise SpfError(1, f"{what}: slot must be in 0 .. {GLWE_KSK_SLOTS - 1}, got {param!r}")
+    log_n = degree.bit_length() - 1
+    if op == GLWE_AUTOMORPHISM_NODE and not 1 <= param <= log_n:
+        raise SpfError(1, f"{what}: round {param!r} outside 1 .. log2 N = {log_n}")
+    return int(param)
 
 
 def _check_node(what: str, node, n_nodes: int) -> int:
@@ -249,6 +270,33 @@ class FheCircuit:
         self._eng._ck(self._lib.spf_graph_add_glwe_poly_linear(self._g, slot, arr, len(nodes), M, out))
         return list(out)
 
+    def _add_glwe_ks(self, what: str, op: int, param, glwe_node) -> int:
+        param = _check_glwe_ks(what, op, param, self._eng.params.polynomial_degree)
+        if isinstance(glwe_node, bool) or not isinstance(glwe_node, (int, np.integer)) or not 0 <= glwe_node < 1 << 32:
+            raise SpfError(1, f"{what}: {glwe_node!r} is not a node id")
+        node = C.c_uint32()
+        if op == GLWE_KEYSWITCH_NODE:
+            st = self._lib.spf_graph_add_glwe_keyswitch(self._g, param, int(glwe_node), C.byref(node))
+        elif op == GLWE_AUTOMORPHISM_NODE:
+            st = self._lib.spf_graph_add_glwe_automorphism(self._g, param, int(glwe_node), C.byref(node))
+        else:
+            st = self._lib.spf_graph_add_glwe_trace(self._g, int(glwe_node), C.byref(node))
+        self._eng._ck(st)
+        return node.value
+
+    # keyswitch_glwe_to_glwe (fft_ops.rs:457-495) of one GLWE1 node under the key of slot `slot` (Engine.load_glwe_keyswitch_key):
+    # one GLWE1 node.  The slot may be loaded, and loaded again, after the graph is built (run() checks it)
+    def add_glwe_keyswitch(self, slot: int, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_keyswitch", GLWE_KEYSWITCH_NODE, slot, glwe_node)
+
+    # one round (1 .. log2 N) of the trace's loop (ops/automorphisms/mod.rs:72-83) under the context's automorphism key
+    def add_glwe_automorphism(self, round: int, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_automorphism", GLWE_AUTOMORPHISM_NODE, round, glwe_node)
+
+    # trace (ops/automorphisms/mod.rs:53-85) of one GLWE1 node
+    def add_glwe_trace(self, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_trace", GLWE_TRACE_NODE, 0, glwe_node)
+
     # FheOp::Output* — returns the array run() fills
     def add_output(self, node: int, kind: ValueKind) -> np.ndarray:
         dtype = np.complex128 if ValueKind(kind) == ValueKind.GGSW1 else np.uint64
@@ -284,9 +332,9 @@ class RecordedCircuit:
 
     def __init__(self, polynomial_degree: int = 2048):
         self.polynomial_degree = polynomial_degree   # bound of n_bits (add_unpack / add_pack); lower() checks the rest
-        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / NODE_LWE_LINEAR / GLWE_POLY_LINEAR_NODE, -1 input, -2 trivial constant
+        self.op: List[int] = []        # FheOp, NODE_UNPACK / NODE_PACK / NODE_ROT_CMUX / NODE_PUFKS / NODE_LWE_LINEAR / GLWE_POLY_LINEAR_NODE / GLWE_KEYSWITCH_NODE .. GLWE_TRACE_NODE, -1 input, -2 trivial constant
         self.kind: List[int] = []
-        self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits
+        self.param: List[int] = []     # SampleExtract index / MulXN amount / trivial bit / unpack: bit index / pack: n_bits / GLWE keyswitch: slot / automorphism: round
         self.inputs: List[tuple] = []  # (pack nodes: all n_bits operands; public functional keyswitch nodes: all lwe_count)
         self.host: List = []           # inputs: the caller's array
         self.outputs: List[int] = []   # nodes, in add_output order
@@ -387,6 +435,22 @@ class RecordedCircuit:
             self._linear[n] = (slot, M)
         return out
 
+    def _add_glwe_ks(self, what: str, op: int, param, glwe_node) -> int:
+        param = _check_glwe_ks(what, op, param, self.polynomial_degree)
+        glwe_node = _check_node(what, glwe_node, len(self.op))
+        if self.kind[glwe_node] != int(ValueKind.GLWE1):
+            raise SpfError(1, f"{what}: the operand is not an L1 GLWE")
+        return self._add(op, ValueKind.GLWE1, param, (glwe_node,))
+
+    def add_glwe_keyswitch(self, slot: int, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_keyswitch", GLWE_KEYSWITCH_NODE, slot, glwe_node)
+
+    def add_glwe_automorphism(self, round: int, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_automorphism", GLWE_AUTOMORPHISM_NODE, round, glwe_node)
+
+    def add_glwe_trace(self, glwe_node: int) -> int:
+        return self._add_glwe_ks("add_glwe_trace", GLWE_TRACE_NODE, 0, glwe_node)
+
     def linear_of(self, node: int) -> tuple:
         """(slot, M) of the add_lwe_linear or add_glwe_poly_linear call that made this linear node (its row index is `param[node]`)"""
         return self._linear[node]
@@ -418,6 +482,8 @@ class RecordedCircuit:
                 n = g.add_pack(self.inputs[i])
             elif self.op[i] == NODE_PUFKS:
                 n = g.add_public_functional_keyswitch(self.inputs[i])
+            elif self.op[i] in _GLWE_KS_NODES:
+                n = g._add_glwe_ks("lower", self.op[i], self.param[i], self.inputs[i][0])
             elif self.op[i] == NODE_ROT_CMUX:  # one step = a one-bit rotation whose stride is the step's rotation
                 n = g.add_blind_rotation(self.inputs[i][1], [self.inputs[i][0]], self.param[i].bit_length() - 1)
             elif self.op[i] == -1:
@@ -506,6 +572,8 @@ class RecordedCircuit:
                 g.add_public_functional_keyswitch([int(x) for x in a["ext"][at:at + int(a["n_bits"][i])]])
             elif op == NODE_ROT_CMUX:
                 g.add_blind_rotation(int(a["in"][i, 1]), [int(a["in"][i, 0])], int(a["param"][i]).bit_length() - 1)
+            elif op in _GLWE_KS_NODES:
+                g._add_glwe_ks("from_arrays", op, int(a["param"][i]), int(a["in"][i, 0]))
             elif op == -1 and host[i] is not None:
                 g.add_input(ValueKind(kind[i]), host[i])
             elif op == -1:

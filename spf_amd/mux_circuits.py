@@ -469,6 +469,17 @@ class GraphBuilder:
     def add_glwe_poly_linear(self, slot: int, glwe_nodes, M=None) -> list:
         return self.graph.add_glwe_poly_linear(slot, glwe_nodes, M)
 
+    # the GLWE keyswitch under keyswitch-key slot `slot`, one automorphism round and the trace of one GLWE1 node: one GLWE1 node
+    # (recorded as ops 70, 71, 72 with the slot / the round / 0 as the parameter)
+    def add_glwe_keyswitch(self, slot: int, glwe_node: int) -> int:
+        return self.graph.add_glwe_keyswitch(slot, glwe_node)
+
+    def add_glwe_automorphism(self, round: int, glwe_node: int) -> int:
+        return self.graph.add_glwe_automorphism(round, glwe_node)
+
+    def add_glwe_trace(self, glwe_node: int) -> int:
+        return self.graph.add_glwe_trace(glwe_node)
+
 
 def append_uint_multiply(builder, a: Sequence, b: Sequence, blocks: Callable[[int, int], MuxCircuit]) -> list:
     """`mul_impl` (parasol_runtime/src/circuits/mul.rs:90-200): recursive gradeschool multiplication of two unsigned

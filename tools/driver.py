@@ -74,7 +74,11 @@ def upload_circuit_inputs(pool, rec, member=-1):
 
 def _fhe_ops_only(rec):
     """the native drivers hand every node to spf_pool_submit_op_v as an FheOp: a node of add_blind_rotation is none"""
-    from spf_amd.graph import GLWE_POLY_LINEAR_NODE, NODE_LWE_LINEAR, NODE_PUFKS, NODE_ROT_CMUX
+    from spf_amd.graph import (GLWE_AUTOMORPHISM_NODE, GLWE_KEYSWITCH_NODE, GLWE_POLY_LINEAR_NODE, GLWE_TRACE_NODE, NODE_LWE_LINEAR,
+                               NODE_PUFKS, NODE_ROT_CMUX)
+    if any(op in rec.op for op in (GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE)):
+        raise RuntimeError("the circuit holds add_glwe_keyswitch / add_glwe_automorphism / add_glwe_trace nodes, which are no FheOp and "
+                           "have no submit by handle: the per-operation drivers cannot walk it (lower() it into a gate graph)")
     if GLWE_POLY_LINEAR_NODE in rec.op:
         raise RuntimeError("the circuit holds add_glwe_poly_linear nodes, which are no FheOp and have no submit by handle (K operands, M "
                            "results): the per-operation drivers cannot walk it (lower() it into a gate graph)")
