@@ -608,6 +608,20 @@ class PooledEvaluation {
         run(SPF_OP_PBS_BIVARIATE, output, {left.raw(), right.raw(), lut.raw()}, plaintext_bits);
     }
 
+    // `keyswitch_glwe_to_glwe` (fft_ops.rs:457-495) under keyswitch-key slot `slot`, one round of the trace's loop and `trace`
+    // (ops/automorphisms/mod.rs:53-85) by handle: Evaluation::keyswitch_glwe_to_glwe / trace on a ciphertext that stays in HBM (valid
+    // or, in pushed mode, still pending).  A slot >= SPF_GLWE_KSK_SLOTS or a round outside 1 .. log2 N throws
+    // SPF_ERR_INVALID_ARGUMENT, an empty slot or a missing automorphism key SPF_ERR_NO_KEY; `output` is then left as it was
+    void keyswitch_glwe_to_glwe(L1GlweCiphertext& output, const L1GlweCiphertext& input, uint32_t slot) const
+    {
+        run(SPF_OP_GLWE_KEYSWITCH, output, {input.raw()}, slot);
+    }
+    void glwe_automorphism(L1GlweCiphertext& output, const L1GlweCiphertext& input, uint32_t round) const
+    {
+        run(SPF_OP_GLWE_AUTOMORPHISM, output, {input.raw()}, round);
+    }
+    void trace(L1GlweCiphertext& output, const L1GlweCiphertext& input) const { run(SPF_OP_GLWE_TRACE, output, {input.raw()}); }
+
     // blind_rotation (blind_rotation.rs:202-223) by handle: output = input * X^-(s << log_stride), the shift as the span
     // shift_ggsw[0 .. n_bits) of the L1 GGSWs of its bits (bit 0 first; valid or, in pushed mode, still pending)
     void blind_rotation(L1GlweCiphertext& output, const L1GgswCiphertext* shift_ggsw, size_t n_bits, const L1GlweCiphertext& input,

@@ -461,7 +461,13 @@ typedef enum spf_graph_op {
     SPF_OP_SCHEME_SWITCH = 8,
     SPF_OP_MUL_XN = 9,
     SPF_OP_PBS_UNIVARIATE = 10, /* no FheOp: `programmable_bootstrap_univariate` with the table as an operand (below) */
-    SPF_OP_PBS_BIVARIATE = 11   /* no FheOp: `programmable_bootstrap_bivariate`, param = plaintext_bits */
+    SPF_OP_PBS_BIVARIATE = 11,  /* no FheOp: `programmable_bootstrap_bivariate`, param = plaintext_bits */
+    /* no FheOp either: `keyswitch_glwe_to_glwe`, one round of the trace's loop and `trace` (spf_glwe_keyswitch_batch and its
+     * neighbours below), one GLWE1 in, one GLWE1 out; param = the keyswitch-key slot (< SPF_GLWE_KSK_SLOTS) / the round
+     * (1 .. log2 N) / ignored */
+    SPF_OP_GLWE_KEYSWITCH = 12,
+    SPF_OP_GLWE_AUTOMORPHISM = 13,
+    SPF_OP_GLWE_TRACE = 14
 } spf_graph_op;
 
 /* ---- plaintext linear maps over LWE ciphertexts ---------------------------------------------
@@ -627,6 +633,17 @@ spf_status spf_pool_submit_multiply_ggsw_glwe(spf_pool *pool, const double *ggsw
 spf_status spf_pool_submit_glev_cmux(spf_pool *pool, const double *sel_ggsw_fft, const uint64_t *a, const uint64_t *b,
                                      uint64_t *glev_out, uint64_t *ticket);
 spf_status spf_pool_submit_scheme_switch(spf_pool *pool, const uint64_t *glev_in, double *ggsw_fft_out, uint64_t *ticket);
+/* `keyswitch_glwe_to_glwe` under the key of `slot`, one round of the trace's loop and `trace` (spf_glwe_keyswitch_batch /
+ * spf_glwe_automorphism_batch / spf_glwe_trace_batch above) for one GLWE; word-equal to those.  Calls with different slots or
+ * rounds run in different batches.  Checked at the submit: slot >= SPF_GLWE_KSK_SLOTS, round 0 or round > log2 N are
+ * SPF_ERR_INVALID_ARGUMENT; an empty slot, or no automorphism key, is SPF_ERR_NO_KEY; a refused call takes no ticket.
+ * The batch reads the slot again when it is launched.  Reloading a slot (spf_load_glwe_keyswitch_key_std, or the automorphism
+ * key) while submissions that use it are outstanding is the caller's error, as for every key loader: WAIT for every ticket and
+ * value submitted on the slot first, then load, then submit again.  The same holds by handle (below). */
+spf_status spf_pool_submit_glwe_keyswitch(spf_pool *pool, uint32_t slot, const uint64_t *glwe_in, uint64_t *glwe_out, uint64_t *ticket);
+spf_status spf_pool_submit_glwe_automorphism(spf_pool *pool, uint32_t round, const uint64_t *glwe_in, uint64_t *glwe_out,
+                                             uint64_t *ticket);
+spf_status spf_pool_submit_glwe_trace(spf_pool *pool, const uint64_t *glwe_in, uint64_t *glwe_out, uint64_t *ticket);
 /* Blocks until the operation has run; each ticket can be collected exactly once (an unknown or already
  * collected ticket is SPF_ERR_INVALID_ARGUMENT, never a hang). */
 spf_status spf_pool_wait(spf_pool *pool, uint64_t ticket);
@@ -745,6 +762,16 @@ spf_status spf_pool_submit_multiply_ggsw_glwe_v(spf_pool *pool, const spf_value 
 spf_status spf_pool_submit_glev_cmux_v(spf_pool *pool, const spf_value *sel_ggsw, const spf_value *a, const spf_value *b,
                                        spf_value **glev_out, uint64_t *ticket);
 spf_status spf_pool_submit_scheme_switch_v(spf_pool *pool, const spf_value *glev, spf_value **ggsw_out, uint64_t *ticket);
+/* GLWE keyswitch, one automorphism round and trace by handle (the statuses and the reload rule of spf_pool_submit_glwe_keyswitch
+ * above; a refused call creates no value: *out is not written).  The operand may be valid or still pending.  A batch whose
+ * operands lie consecutively in device memory runs the in-place kernel on them, any other ONE launch of the rows kernel over a
+ * table of their addresses — nothing is copied (spf_last_glwe_keyswitch_kernel tells which; the environment variable
+ * SPF_GLWE_KS_ROWS_GATHER=1, a diagnostic read by spf_pool_create, packs the operands first as the other kinds do).  The results of a
+ * batch are fresh memory: they overlap no operand, and one value may be the operand of several operations of a batch. */
+spf_status spf_pool_submit_glwe_keyswitch_v(spf_pool *pool, uint32_t slot, const spf_value *glwe, spf_value **out, uint64_t *ticket);
+spf_status spf_pool_submit_glwe_automorphism_v(spf_pool *pool, uint32_t round, const spf_value *glwe, spf_value **out,
+                                               uint64_t *ticket);
+spf_status spf_pool_submit_glwe_trace_v(spf_pool *pool, const spf_value *glwe, spf_value **out, uint64_t *ticket);
 /* `blind_rotation` (blind_rotation.rs:202-223) by handle: *out = glwe * X^-(s << log_stride), s given as the n_bits glwe-level
  * GGSW values of its bits (bit 0 first; valid or still pending, e.g. results of spf_pool_submit_keyswitch_circuit_bootstrap_v;
  * repeats allowed).  Word-equal to spf_blind_rotation_batch.  n_bits >= 1 and n_bits + log_stride <= log2(polynomial_degree);
@@ -758,7 +785,9 @@ spf_status spf_pool_submit_blind_rotation_v(spf_pool *pool, const spf_value *glw
  * spf_graph_add_op takes them (CMUX: selector, low, high), `param` = SampleExtract index / MulXN amount.  SPF_OP_PBS_UNIVARIATE
  * [lwe0, lut glwe1] and SPF_OP_PBS_BIVARIATE [left lwe0, right lwe0, lut glwe1] (`param` = plaintext_bits < 64) go the same
  * way: `programmable_bootstrap_univariate` / `_bivariate` (programmable_bootstrapping.rs:291, 575-621) by handle, batched and paced
- * like the circuit bootstraps, word-equal to spf_pbs_univariate_batch / spf_pbs_bivariate_batch of the same rows */
+ * like the circuit bootstraps, word-equal to spf_pbs_univariate_batch / spf_pbs_bivariate_batch of the same rows.
+ * SPF_OP_GLWE_KEYSWITCH (`param` = slot), SPF_OP_GLWE_AUTOMORPHISM (`param` = round) and SPF_OP_GLWE_TRACE [glwe1] are the three
+ * submits above. */
 spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value *const *inputs, size_t n_inputs, uint64_t param,
                                 spf_value **out, uint64_t *ticket);
 
@@ -782,6 +811,10 @@ spf_status spf_pool_submit_op_v(spf_pool *pool, spf_graph_op op, const spf_value
  * spf_pbs_univariate_batch / spf_pbs_bivariate_batch of the same rows with lut_stride = one GLWE, whatever batch it lands in.
  * The table is a glwe1 node like any other (an input, a trivial encryption, something the graph computed); the nodes of a level
  * that name ONE table node read it in place.  PBS_BIVARIATE with plaintext_bits >= 64 is SPF_ERR_INVALID_ARGUMENT.
+ *   GLWE_KEYSWITCH(param = slot) [glwe1]   GLWE_AUTOMORPHISM(param = round) [glwe1]   GLWE_TRACE [glwe1]   -> glwe1
+ * are the nodes of spf_graph_add_glwe_keyswitch / _automorphism / _trace below, built by the same code: same checks, same groups,
+ * same words.  These three values name an operation here over ONE operand only: with any other count the call is refused as
+ * "unknown operation" (with the value and the count), not as a wrong number of operands.
  * Wrong arity or operand type is reported by spf_graph_add_op, before anything runs (the
  * reference validates per task, task.rs:26-31).  Input and output host buffers are read /
  * written by every spf_graph_run and must stay valid until it returns; a graph can be run

@@ -17,7 +17,7 @@ from ._ffi import (Engine, Group, Pool, SpfError, Value, ciphertext_from_bincode
                    generate_bivariate_lut, generate_lut, lib_path, live_objects, load_library)
 from .evaluation import Evaluation, ComputeKey  # noqa: F401
 from .packed import packed_decode, packed_plaintext, table_plaintext, trivial_packed_glwe, trivial_table_glwe  # noqa: F401
-from .graph import FheCircuit, FheOp, RecordedCircuit, TableOp, ValueKind  # noqa: F401
+from .graph import FheCircuit, FheOp, KeyswitchOp, RecordedCircuit, TableOp, ValueKind  # noqa: F401
 from .build import build_library  # noqa: F401
 
 __all__ = ["Params", "DEFAULT_128", "Engine", "Group", "Pool", "Value", "SpfError", "Evaluation", "ComputeKey", "FheCircuit", "FheOp", "TableOp", "ValueKind", "RecordedCircuit",

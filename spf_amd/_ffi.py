@@ -145,6 +145,9 @@ SYMBOLS = [
     ("spf_pool_submit_multiply_ggsw_glwe", _I, [_P, _P, _P, _P, C.POINTER(_U64)]),
     ("spf_pool_submit_glev_cmux", _I, [_P, _P, _P, _P, _P, C.POINTER(_U64)]),
     ("spf_pool_submit_scheme_switch", _I, [_P, _P, _P, C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_keyswitch", _I, [_P, _U32, _P, _P, C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_automorphism", _I, [_P, _U32, _P, _P, C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_trace", _I, [_P, _P, _P, C.POINTER(_U64)]),
     ("spf_pool_wait", _I, [_P, _U64]),
     ("spf_pool_set_max_inflight", _I, [_P, _SZ]),
     ("spf_pool_stats", _I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
@@ -275,6 +278,9 @@ SYMBOLS = [
     ("spf_pool_submit_multiply_ggsw_glwe_v", _I, [_P, _P, _P, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_glev_cmux_v", _I, [_P, _P, _P, _P, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_scheme_switch_v", _I, [_P, _P, C.POINTER(_P), C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_keyswitch_v", _I, [_P, _U32, _P, C.POINTER(_P), C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_automorphism_v", _I, [_P, _U32, _P, C.POINTER(_P), C.POINTER(_U64)]),
+    ("spf_pool_submit_glwe_trace_v", _I, [_P, _P, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_op_v", _I, [_P, _I, C.POINTER(_P), _SZ, _U64, C.POINTER(_P), C.POINTER(_U64)]),
     ("spf_pool_submit_blind_rotation_v", _I, [_P, _P, C.POINTER(_P), _SZ, _SZ, C.POINTER(_P), C.POINTER(_U64)]),
 ]
@@ -1357,6 +1363,26 @@ class Pool:
         _out("pool scheme_switch", output, np.complex128, P.cbs_ggsw_complex)
         self._run("scheme_switch", self._lib.spf_pool_submit_scheme_switch, _ptr(x), _ptr(output))
 
+    # -- keyswitch_glwe_to_glwe under the key of `slot`, one round of the trace's loop, trace: one GLWE per call, word-equal to
+    # Engine.glwe_keyswitch / glwe_automorphism / glwe_trace.  Calls with different slots or rounds run in different batches; an
+    # empty slot or a missing automorphism key is refused at the submit (SPF_ERR_NO_KEY)
+    def _run_glwe_ks(self, what, fn, output, glwe, *param):
+        P = self.engine.params
+        x = _in(f"pool {what}", glwe, np.uint64, P.glwe_words)
+        _out(f"pool {what}", output, np.uint64, P.glwe_words)
+        t = C.c_uint64()
+        self._ck(fn(self._h, *param, _ptr(x), _ptr(output), C.byref(t)), f"pool {what}")
+        self._wait(t.value)
+
+    def glwe_keyswitch(self, output: np.ndarray, glwe: np.ndarray, slot: int):
+        self._run_glwe_ks("glwe_keyswitch", self._lib.spf_pool_submit_glwe_keyswitch, output, glwe, int(slot) & 0xFFFFFFFF)
+
+    def glwe_automorphism(self, output: np.ndarray, glwe: np.ndarray, round: int):
+        self._run_glwe_ks("glwe_automorphism", self._lib.spf_pool_submit_glwe_automorphism, output, glwe, int(round) & 0xFFFFFFFF)
+
+    def glwe_trace(self, output: np.ndarray, glwe: np.ndarray):
+        self._run_glwe_ks("glwe_trace", self._lib.spf_pool_submit_glwe_trace, output, glwe)
+
     def stats(self):
         ops, launches = C.c_uint64(), C.c_uint64()
         self._lib.spf_pool_stats(self._h, C.byref(ops), C.byref(launches))
@@ -1449,6 +1475,31 @@ class Pool:
             v.release()
             raise
         return v
+
+    # the three GLWE keyswitch operations by handle through their named entry points (run_v / push_v / submit_v with
+    # FheOp.GLWE_KEYSWITCH / GLWE_AUTOMORPHISM / GLWE_TRACE take the generic door): wait=False pushes without a ticket — the operand
+    # may then be pending, and Value.wait() on the result makes it run
+    def _glwe_ks_v(self, name, glwe: "Value", param, wait: bool) -> "Value":
+        h, t = C.c_void_p(), C.c_uint64()
+        fn = getattr(self._lib, name)
+        self._ck(fn(self._h, *param, glwe._h, C.byref(h), C.byref(t) if wait else None), name)
+        v = Value(self, h)
+        if wait:
+            try:
+                self._wait(t.value)
+            except SpfError:
+                v.release()
+                raise
+        return v
+
+    def glwe_keyswitch_v(self, slot: int, glwe: "Value", wait: bool = True) -> "Value":
+        return self._glwe_ks_v("spf_pool_submit_glwe_keyswitch_v", glwe, (int(slot) & 0xFFFFFFFF,), wait)
+
+    def glwe_automorphism_v(self, round: int, glwe: "Value", wait: bool = True) -> "Value":
+        return self._glwe_ks_v("spf_pool_submit_glwe_automorphism_v", glwe, (int(round) & 0xFFFFFFFF,), wait)
+
+    def glwe_trace_v(self, glwe: "Value", wait: bool = True) -> "Value":
+        return self._glwe_ks_v("spf_pool_submit_glwe_trace_v", glwe, (), wait)
 
     def keyswitch_circuit_bootstrap_v(self, lwe1: "Value") -> "Value":
         h, t = C.c_void_p(), C.c_uint64()

@@ -604,6 +604,8 @@ spf_status spf_graph_add_trivial(spf_graph* g, spf_value_kind kind, uint64_t bit
     return SPF_OK;
 }
 
+static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, uint32_t param, uint32_t glwe_node, uint32_t* node_out);
+
 // Validation happens here, before anything runs, as the reference's graph-level `RuntimeError`s do
 // (task.rs:26-31): wrong arity or operand type is an error of the call, not of the run.
 spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* inputs, size_t n_inputs, uint64_t param,
@@ -613,19 +615,32 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
     const int pop = spf_ops::pool_op_of(op);
     if (!node || pop == spf_ops::kNone) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
     const spf_ops::OpRow& info = spf_ops::row(pop);
+    const bool glwe_ks = pop == spf_ops::OP_GLWE_KEYSWITCH || pop == spf_ops::OP_GLWE_AUTOMORPHISM || pop == spf_ops::OP_GLWE_TRACE;
+    // The values 12 .. 14 stand for three node constructors, and this door knows them in the constructors' own form only, over ONE
+    // operand.  With any other count the call names no operation of this door: it is refused as it was while the values named
+    // nothing, "unknown operation" (tests/test_gpu_pbs_graph.py holds value 12 over two operands to that text), and the text says
+    // what the value takes.  The rows of the table that were there keep "wrong number of operands".
+    if (glwe_ks && n_inputs != 1)
+        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation: value " + std::to_string((int)op) + " over " + std::to_string(n_inputs) +
+                                                          " operands (the GLWE keyswitch, automorphism round and trace take one GLWE1)");
     if (n_inputs != (size_t)info.arity || (n_inputs && !inputs))
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: wrong number of operands");
-    spf_graph_plan::Node n{};
-    n.op = op; n.kind = info.out_kind; n.n_in = (uint32_t)info.arity;
+    // GLWE keyswitch, automorphism round, trace: the node of their named constructors (the planner's kinds 70 / 71 / 72), built by
+    // the builder they share; a parameter beyond 32 bits is refused as the table's rule refuses it, with its number
+    if (glwe_ks) {
+        const char* why = nullptr;
+        if (spf_ops::op_param(g->prm, pop, &param, &why) != SPF_OK) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph op: ") + why);
+        return pop == spf_ops::OP_GLWE_KEYSWITCH      ? graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweKeyswitch, "op (GLWE keyswitch)", (uint32_t)param, inputs[0], node)
+               : pop == spf_ops::OP_GLWE_AUTOMORPHISM ? graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweAutomorphism, "op (GLWE automorphism)", (uint32_t)param, inputs[0], node)
+                                                      : graph_add_glwe_ks(g, spf_graph_plan::kNodeGlweTrace, "op (GLWE trace)", 0, inputs[0], node);
+    }
     for (int i = 0; i < info.arity; i++) {
         if (inputs[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: operand is not a node of this graph");
         if (g->nodes[inputs[i]].kind != info.in_kind[i]) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph op: operand has the wrong ciphertext type");
-        n.in[i] = inputs[i];
     }
     const char* why = nullptr;
     if (spf_ops::op_param(g->prm, pop, &param, &why) != SPF_OK) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph op: ") + why);
-    n.param = param;
-    *node = g->add(n);
+    *node = g->add(spf_graph_plan::op_node(pop, inputs, param));
     g->planned = false;
     return SPF_OK;
 }
@@ -778,13 +793,12 @@ static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, 
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
     const std::string w = std::string("graph ") + what;
     if (!node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": null pointer");
-    if (op == spf_graph_plan::kNodeGlweKeyswitch && param >= SPF_GLWE_KSK_SLOTS)
-        return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": slot " + std::to_string(param) + " >= SPF_GLWE_KSK_SLOTS = " + std::to_string(SPF_GLWE_KSK_SLOTS));
-    if (op == spf_graph_plan::kNodeGlweAutomorphism) {
-        uint32_t log_n = 0;
-        while (((size_t)1 << (log_n + 1)) <= g->prm.polynomial_degree) log_n++;
-        if (param < 1 || param > log_n)
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": round " + std::to_string(param) + " outside 1 .. log2 N = " + std::to_string(log_n));
+    const int pop = op == spf_graph_plan::kNodeGlweKeyswitch ? spf_ops::OP_GLWE_KEYSWITCH
+                    : op == spf_graph_plan::kNodeGlweAutomorphism ? spf_ops::OP_GLWE_AUTOMORPHISM : spf_ops::OP_GLWE_TRACE;
+    uint64_t p64 = param;
+    { // the slot / the round by the operation table's rule (spf_ops::op_param), which states it once for graphs and the pool
+        const char* why = nullptr;
+        if (spf_ops::op_param(g->prm, pop, &p64, &why) != SPF_OK) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": " + why);
     }
     if (glwe_node >= g->nodes.size())
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": operand " + std::to_string(glwe_node) + " is not a node of this graph (" +
@@ -792,11 +806,9 @@ static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, 
     if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": operand " + std::to_string(glwe_node) + " is not an L1 GLWE (its kind is " +
                                                           std::to_string(g->nodes[glwe_node].kind) + ")");
-    spf_graph_plan::Node n{};
-    n.op = op; n.kind = SPF_VAL_GLWE1; n.n_in = 1; n.in[0] = glwe_node; n.param = param;
     uint32_t id;
     try {
-        id = g->add(n);
+        id = g->add(spf_graph_plan::op_node(pop, &glwe_node, p64)); // (the node spf_graph_add_op records for the same operation)
     } catch (const std::exception&) {
         return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
     }

@@ -53,6 +53,26 @@ struct Node {
     const void* host;  // inputs: caller's buffer, read at every run
 };
 
+// The node of an operation of the table (spf_ops.hpp) over `inputs[0 .. arity)`, as spf_graph_add_op records it and as the named
+// constructors of the three GLWE keyswitch operations do: Node::op is the row's spf_graph_op — except for those three, whose
+// nodes keep the kinds 70 / 71 / 72 of their constructors (the planner groups, places and keys them by that kind: the recorded
+// plans do not move).  `pool_op` is a row with a spf_graph_op; the parameter has been through spf_ops::op_param.
+inline int32_t node_op_of(int pool_op)
+{
+    return pool_op == spf_ops::OP_GLWE_KEYSWITCH      ? (int32_t)kNodeGlweKeyswitch
+           : pool_op == spf_ops::OP_GLWE_AUTOMORPHISM ? (int32_t)kNodeGlweAutomorphism
+           : pool_op == spf_ops::OP_GLWE_TRACE        ? (int32_t)kNodeGlweTrace
+                                                      : (int32_t)spf_ops::row(pool_op).graph_op;
+}
+inline Node op_node(int pool_op, const uint32_t* inputs, uint64_t param)
+{
+    const spf_ops::OpRow& r = spf_ops::row(pool_op);
+    Node n{};
+    n.op = node_op_of(pool_op); n.kind = r.out_kind; n.n_in = (uint32_t)r.arity; n.param = param;
+    for (int i = 0; i < r.arity; i++) n.in[i] = inputs[i];
+    return n;
+}
+
 struct Graph {
     std::vector<Node> nodes; // in topological order: operands precede their users
 

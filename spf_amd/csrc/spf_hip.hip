@@ -3665,6 +3665,7 @@ spf_status spf_pool_create(spf_ctx* c, size_t max_batch, uint32_t max_wait_us, s
     if (const char* e = getenv("SPF_POOL_DEF_HEAVY")) p->max_def_heavy = std::max(0, atoi(e));
     if (const char* e = getenv("SPF_POOL_TABLE_SETS")) p->n_table_sets = std::min(std::max(1, atoi(e)), (int)spf_pool::kTableSets);
     if (const char* e = getenv("SPF_POOL_HOT_US")) p->hot_us = std::max(0, atoi(e)); // (0: the launcher never polls; completers complete every batch)
+    if (const char* e = getenv("SPF_GLWE_KS_ROWS_GATHER")) p->glwe_ks_rows_gather = e[0] && e[0] != '0'; // (diagnostic: see enqueue_v)
     bool streams_ok = hipSetDevice(c->device) == hipSuccess && p->create_def_streams();
     for (auto& set : p->sets)
         streams_ok = streams_ok && hipStreamCreateWithFlags(&set.sk, hipStreamNonBlocking) == hipSuccess;
@@ -3810,6 +3811,17 @@ void spf_pool_destroy(spf_pool* p)
 // (defined with the group, spf_group.hpp)
 static spf_pool* pool_deal(spf_pool* top, int* member);
 
+// The keys of a GLWE keyswitch, automorphism round or trace, looked at when the operation is SUBMITTED to the pool of context `c`
+// (under the context's lock, let go again before the operation is queued): an empty slot or no automorphism key is
+// SPF_ERR_NO_KEY with the batch entry points' text, and nothing is queued.  The launch reads the slot again — at run time, as a
+// gate graph does; a caller that reloads a slot waits for its submissions on it first (spf_hip.h).  Any other operation: SPF_OK.
+static spf_status pool_glwe_ks_keys(spf_ctx* c, int op, uint64_t param)
+{
+    if (!spf_ops::rows_in_place(op)) return SPF_OK;
+    const int mode = op == spf_ops::OP_GLWE_KEYSWITCH ? GLWE_KS_KEYSWITCH : op == spf_ops::OP_GLWE_AUTOMORPHISM ? GLWE_KS_AUTOMORPHISM : GLWE_KS_TRACE;
+    return glwe_ks_args(c, mode, (uint32_t)param, 0, nullptr, nullptr);
+}
+
 // a host-pointer submit: the null and parameter checks of every wrapper below, then the operation goes to the pool the calling
 // thread is dealt to.  (Refusals are a bare status: no message is set.)
 static spf_status pool_submit(spf_pool* p, int op, std::initializer_list<const void*> in, void* out, uint64_t* ticket, uint64_t param = 0)
@@ -3826,6 +3838,7 @@ static spf_status pool_submit(spf_pool* p, int op, std::initializer_list<const v
     int member = 0;
     spf_pool* q = pool_deal(p, &member);
     if (!q) return SPF_ERR_HIP; // no member of the group is in rotation
+    if (spf_status ks = pool_glwe_ks_keys(q->ctx, op, param)) return ks;
     const spf_status st = q->submit_impl(op, false, src, out, nullptr, nullptr, ticket, param);
     if (st == SPF_OK && q != p) *ticket |= (uint64_t)member << spf_pool::kMemberShift;
     return st;
@@ -3880,6 +3893,19 @@ spf_status spf_pool_submit_glev_cmux(spf_pool* p, const double* sel_ggsw_fft, co
 spf_status spf_pool_submit_scheme_switch(spf_pool* p, const uint64_t* glev_in, double* ggsw_fft_out, uint64_t* ticket)
 {
     return pool_submit(p, spf_ops::OP_SCHEME_SWITCH, {glev_in}, ggsw_fft_out, ticket);
+}
+// (the slot / the round is part of the lane's key, as the SampleExtract index is: callers with different ones never share a launch)
+spf_status spf_pool_submit_glwe_keyswitch(spf_pool* p, uint32_t slot, const uint64_t* glwe_in, uint64_t* glwe_out, uint64_t* ticket)
+{
+    return pool_submit(p, spf_ops::OP_GLWE_KEYSWITCH, {glwe_in}, glwe_out, ticket, slot);
+}
+spf_status spf_pool_submit_glwe_automorphism(spf_pool* p, uint32_t round, const uint64_t* glwe_in, uint64_t* glwe_out, uint64_t* ticket)
+{
+    return pool_submit(p, spf_ops::OP_GLWE_AUTOMORPHISM, {glwe_in}, glwe_out, ticket, round);
+}
+spf_status spf_pool_submit_glwe_trace(spf_pool* p, const uint64_t* glwe_in, uint64_t* glwe_out, uint64_t* ticket)
+{
+    return pool_submit(p, spf_ops::OP_GLWE_TRACE, {glwe_in}, glwe_out, ticket);
 }
 
 spf_status spf_pool_wait(spf_pool* p, uint64_t ticket)
@@ -3961,6 +3987,7 @@ spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, si
     spf_pool* leaf = value_home(top, v[0]);
     const int member = v[0]->member;
     if (!leaf) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
+    if (spf_status ks = pool_glwe_ks_keys(leaf->ctx, op, param)) return ks; // (no value made, no ticket taken)
     spf_value* res = spf_value::make(leaf->arena, leaf, member, info.out_kind, value_bytes(leaf->prm, info.out_kind));
     if (!res) return fail(leaf->ctx, SPF_ERR_HIP, "out of host memory");
     const spf_status st = leaf->submit_impl(op, true, nullptr, nullptr, v, res, ticket, param);
@@ -4319,6 +4346,18 @@ spf_status spf_pool_submit_glev_cmux_v(spf_pool* p, const spf_value* sel, const 
 spf_status spf_pool_submit_scheme_switch_v(spf_pool* p, const spf_value* glev, spf_value** ggsw_out, uint64_t* ticket)
 {
     return pool_submit_v(p, spf_ops::OP_SCHEME_SWITCH, {glev}, 0, ggsw_out, ticket);
+}
+spf_status spf_pool_submit_glwe_keyswitch_v(spf_pool* p, uint32_t slot, const spf_value* glwe, spf_value** out, uint64_t* ticket)
+{
+    return pool_submit_v(p, spf_ops::OP_GLWE_KEYSWITCH, &glwe, 1, slot, out, ticket, true); // (a refused parameter leaves its number in the last error)
+}
+spf_status spf_pool_submit_glwe_automorphism_v(spf_pool* p, uint32_t round, const spf_value* glwe, spf_value** out, uint64_t* ticket)
+{
+    return pool_submit_v(p, spf_ops::OP_GLWE_AUTOMORPHISM, &glwe, 1, round, out, ticket, true); // (a refused parameter leaves its number in the last error)
+}
+spf_status spf_pool_submit_glwe_trace_v(spf_pool* p, const spf_value* glwe, spf_value** out, uint64_t* ticket)
+{
+    return pool_submit_v(p, spf_ops::OP_GLWE_TRACE, &glwe, 1, 0, out, ticket, true); // (a refused parameter leaves its number in the last error)
 }
 
 // `blind_rotation` (blind_rotation.rs:202-223) by handle: n_bits pushes of the rotate-CMUX kind, step i on the still-pending

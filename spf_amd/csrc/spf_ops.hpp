@@ -16,6 +16,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 
 // ---------------------------------------------------------------- sizes (the only formulas)
 inline size_t lwe0_words(const spf_params& p) { return (size_t)p.lwe_dimension + 1; }
@@ -123,10 +124,16 @@ enum Op {
     OP_ROT_CMUX = 11,
     // the bootstraps by a caller's lookup table (programmable_bootstrap_univariate / _bivariate), the table an operand
     OP_PBS_UNIVARIATE = 12, OP_PBS_BIVARIATE = 13,
-    N_OPS = 14
+    // `keyswitch_glwe_to_glwe`, one round of the trace's loop and `trace` (spf_glwe_keyswitch.hpp): the parameter is the
+    // keyswitch-key slot / the round / nothing
+    OP_GLWE_KEYSWITCH = 14, OP_GLWE_AUTOMORPHISM = 15, OP_GLWE_TRACE = 16,
+    N_OPS = 17
 };
 
-enum ParamRule { PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N, PARAM_ROTATION_BELOW_N, PARAM_PLAINTEXT_BITS_BELOW_64 };
+enum ParamRule {
+    PARAM_NONE, PARAM_INDEX_BELOW_N, PARAM_AMOUNT_MOD_2N, PARAM_ROTATION_BELOW_N, PARAM_PLAINTEXT_BITS_BELOW_64,
+    PARAM_GLWE_KSK_SLOT, PARAM_ROUND_1_TO_LOG_N
+};
 constexpr int kNone = -1; // no spf_graph_op / no operand in this slot
 
 struct OpRow {
@@ -138,6 +145,11 @@ struct OpRow {
     bool cmux_family; // read scattered operands in place through a pointer table (spf_cmux_scattered_dev)
     bool heavy;       // milliseconds on the GPU: caller groups, pacing and the "previous batch still out" rule apply (spf_pool.hpp)
     ParamRule param;
+    // By handle and in gate graphs the operands are read where they lie, through a table of ONE pointer per item, by
+    // launch_glwe_ks_rows; the output stays one block of consecutive rows that the launcher passes beside the table (and that
+    // overlaps no operand).  Not cmux_family: that table carries four pointers per unit — selector, low, high AND the output —
+    // so its units may be sorted and its outputs scattered; here item i of the table is row i of the output.
+    bool rows_in_place = false;
 };
 
 constexpr OpRow kOps[N_OPS] = {
@@ -157,12 +169,18 @@ constexpr OpRow kOps[N_OPS] = {
     // out = sample_extract(blind rotation of the table by the LWE), the table the LAST operand; bivariate: by left * 2^param + right
     {OP_PBS_UNIVARIATE, SPF_OP_PBS_UNIVARIATE, 2, {SPF_VAL_LWE0, SPF_VAL_GLWE1, kNone}, SPF_VAL_LWE1, false, true, PARAM_NONE},
     {OP_PBS_BIVARIATE, SPF_OP_PBS_BIVARIATE, 3, {SPF_VAL_LWE0, SPF_VAL_LWE0, SPF_VAL_GLWE1}, SPF_VAL_LWE1, false, true, PARAM_PLAINTEXT_BITS_BELOW_64},
+    // out = keyswitch(in, slot param) / keyswitch(in(X^t), automorphism key of round param) / trace(in): one launch per batch,
+    // microseconds (the trace: 0.024 ms a round at B = 256, profiles/r32_glwe_keyswitch.md; by handle: profiles/r34_glwe_keyswitch_pool.md)
+    {OP_GLWE_KEYSWITCH, SPF_OP_GLWE_KEYSWITCH, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_GLWE1, false, false, PARAM_GLWE_KSK_SLOT, true},
+    {OP_GLWE_AUTOMORPHISM, SPF_OP_GLWE_AUTOMORPHISM, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_GLWE1, false, false, PARAM_ROUND_1_TO_LOG_N, true},
+    {OP_GLWE_TRACE, SPF_OP_GLWE_TRACE, 1, {SPF_VAL_GLWE1, kNone, kNone}, SPF_VAL_GLWE1, false, false, PARAM_NONE, true},
 };
 
 constexpr const OpRow& row(int op) { return kOps[op]; } // op: a valid pool operation
 constexpr bool heavy(int op) { return kOps[op].heavy; }
 constexpr bool cmux_family(int op) { return kOps[op].cmux_family; }
-// the pool operation a spf_graph_op stands for; kNone for a value that is none of the ten
+constexpr bool rows_in_place(int op) { return kOps[op].rows_in_place; }
+// the pool operation a spf_graph_op stands for; kNone for a value that is none of the fifteen
 constexpr int pool_op_of(int graph_op)
 {
     for (int op = 0; op < N_OPS; op++)
@@ -186,10 +204,29 @@ inline BatchShape shape(const spf_params& p, int op)
 
 // The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN
 // amount is reduced mod 2N, a rotate-CMUX rotation lies in 1 .. N - 1,
-// a bivariate bootstrap's plaintext_bits are below 64, every other operation's parameter is 0 whatever the caller passed.
+// a bivariate bootstrap's plaintext_bits are below 64, a GLWE keyswitch's slot is below SPF_GLWE_KSK_SLOTS, an automorphism's round
+// lies in 1 .. log2 N (both texts carry the number, in a buffer of the calling thread: read `why` before the thread's next call),
+// every other operation's parameter — the trace's too — is 0 whatever the caller passed.
+inline uint32_t log2_degree(const spf_params& p)
+{
+    uint32_t log_n = 0;
+    while (((uint64_t)1 << (log_n + 1)) <= p.polynomial_degree) log_n++;
+    return log_n;
+}
 inline spf_status op_param(const spf_params& p, int op, uint64_t* param, const char** why)
 {
+    static thread_local char text[96];
     switch (kOps[op].param) {
+    case PARAM_GLWE_KSK_SLOT:
+        if (*param < SPF_GLWE_KSK_SLOTS) return SPF_OK;
+        std::snprintf(text, sizeof text, "slot %llu >= SPF_GLWE_KSK_SLOTS = %d", (unsigned long long)*param, (int)SPF_GLWE_KSK_SLOTS);
+        *why = text;
+        return SPF_ERR_INVALID_ARGUMENT;
+    case PARAM_ROUND_1_TO_LOG_N:
+        if (*param >= 1 && *param <= log2_degree(p)) return SPF_OK;
+        std::snprintf(text, sizeof text, "round %llu outside 1 .. log2 N = %u", (unsigned long long)*param, log2_degree(p));
+        *why = text;
+        return SPF_ERR_INVALID_ARGUMENT;
     case PARAM_INDEX_BELOW_N:
         if (*param < p.polynomial_degree) return SPF_OK;
         *why = "sample_extract index >= polynomial_degree";
@@ -216,24 +253,25 @@ constexpr bool row_ok(const OpRow& r, int index)
         if (k < r.arity ? !is_kind(r.in_kind[k]) : r.in_kind[k] != kNone) return false;
     return true;
 }
+// a row read through the one-pointer table has one operand, and is not of the CMUX family (whose table is another)
 constexpr bool rows_ok()
 {
     for (int op = 0; op < N_OPS; op++)
-        if (!row_ok(kOps[op], op)) return false;
+        if (!row_ok(kOps[op], op) || (kOps[op].rows_in_place && (kOps[op].arity != 1 || kOps[op].cmux_family))) return false;
     return true;
 }
-constexpr bool graph_ops_ok() // the twelve public values name twelve rows (distinct: each row names its value back), OP_GATE_CBS and OP_ROT_CMUX have none
+constexpr bool graph_ops_ok() // the fifteen public values name fifteen rows (distinct: each row names its value back), OP_GATE_CBS and OP_ROT_CMUX have none
 {
-    for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_PBS_BIVARIATE; g++)
+    for (int g = SPF_OP_SAMPLE_EXTRACT; g <= SPF_OP_GLWE_TRACE; g++)
         if (pool_op_of(g) == kNone) return false;
     for (int op = 0; op < N_OPS; op++) {
         const int g = kOps[op].graph_op;
-        if (op == OP_GATE_CBS || op == OP_ROT_CMUX ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_PBS_BIVARIATE || pool_op_of(g) != op)) return false;
+        if (op == OP_GATE_CBS || op == OP_ROT_CMUX ? g != kNone : (g < SPF_OP_SAMPLE_EXTRACT || g > SPF_OP_GLWE_TRACE || pool_op_of(g) != op)) return false;
     }
     return true;
 }
-static_assert(rows_ok(), "a row is out of the enum's order, or its arity and its operand kinds disagree, or a kind is no spf_value_kind");
-static_assert(graph_ops_ok(), "every spf_graph_op needs exactly one row, and only OP_GATE_CBS and OP_ROT_CMUX go without a spf_graph_op");
+static_assert(rows_ok(), "a row is out of the enum's order, or its arity and its operand kinds disagree, or a kind is no spf_value_kind, or a rows_in_place row has more than one operand or is of the CMUX family");
+static_assert(graph_ops_ok(), "every spf_graph_op, SPF_OP_SAMPLE_EXTRACT .. SPF_OP_GLWE_TRACE, needs exactly one row, and only OP_GATE_CBS and OP_ROT_CMUX go without a spf_graph_op");
 } // namespace check
 
 } // namespace spf_ops

@@ -12,6 +12,8 @@ static spf_status pool_circuit_bootstrap(spf_ctx* c, hipStream_t s, size_t B, co
                                          int per_wg_hint);
 static spf_status launch_lwe_pack(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_left, const uint64_t* d_right,
                                   uint32_t plaintext_bits, uint64_t* d_out);
+// (GLWE keyswitch, automorphism round, trace over consecutive rows: `mode` a GlweKsMode, `arg` the slot or the round)
+static spf_status glwe_ks_enqueue(spf_ctx* c, void* stream, int mode, uint32_t arg, size_t B, const uint64_t* d_in, uint64_t* d_out);
 namespace {
 spf_status launch_blind_rotate(spf_ctx* c, hipStream_t s, size_t B, const uint64_t* d_lwe, const uint64_t* d_lut, size_t lut_stride,
                                uint32_t log_chi, uint32_t log_v, uint64_t body_rotate, uint64_t* d_out, size_t out_stride, bool extract,
@@ -63,6 +65,11 @@ inline spf_status launch_op(spf_ctx* c, hipStream_t s, int op, size_t B, const v
         if (st != SPF_OK) return st;
         return launch_blind_rotate(c, s, B, (const uint64_t*)d_mid, u64(in[2]), lut_stride, 0, 0, 0, (uint64_t*)out, lwe1_words(c->prm), true, per_wg);
     }
+    // one launch, no intermediates: the same arm for a pool's batch and a graph's level.  (Scattered operands by handle and in gate
+    // graphs go to launch_glwe_ks_rows instead: the rows' `rows_in_place`.)
+    case OP_GLWE_KEYSWITCH: return glwe_ks_enqueue(c, s, spf::GLWE_KS_KEYSWITCH, (uint32_t)param, B, u64(in[0]), (uint64_t*)out);
+    case OP_GLWE_AUTOMORPHISM: return glwe_ks_enqueue(c, s, spf::GLWE_KS_AUTOMORPHISM, (uint32_t)param, B, u64(in[0]), (uint64_t*)out);
+    case OP_GLWE_TRACE: return glwe_ks_enqueue(c, s, spf::GLWE_KS_TRACE, 0, B, u64(in[0]), (uint64_t*)out);
     case OP_ROT_CMUX: return fail(c, SPF_ERR_INVALID_ARGUMENT, "a rotate-CMUX step reads its operands through a pointer table only");
     default: return fail(c, SPF_ERR_INVALID_ARGUMENT, "unknown graph operation");
     }

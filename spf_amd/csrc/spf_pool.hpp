@@ -353,7 +353,13 @@ struct spf_pool {
         have = bytes;
         return true;
     }
-    // pointers of a handle batch's table: one row of `cap` per operand, or four per CMUX unit
+    // A batch by handle of a `rows_in_place` operation (GLWE keyswitch, automorphism round, trace) whose operands do not lie
+    // consecutively is ONE launch_glwe_ks_rows over the pointer table: no gather pass, no device rows of the set.
+    // SPF_GLWE_KS_ROWS_GATHER=1, read when the pool is made, keeps the route of every other kind — gather_rows_kernel into the set's
+    // rows, then the kernel over consecutive rows — for the A/B (profiles/r34_glwe_keyswitch_pool.md).
+    bool glwe_ks_rows_gather = false;
+    bool rows_route(int op) const { return spf_pool_impl::rows_in_place(op) && !glwe_ks_rows_gather; }
+    // pointers of a handle batch's table: one row of `cap` per operand (a rows_in_place operation uses the first), or four per CMUX unit
     size_t table_pointers(int op, size_t cap) const
     {
         return spf_pool_impl::cmux_family(op) ? 4 * cap * (op == spf_pool_impl::OP_GLEV_CMUX ? prm.cbs_radix_count : 1) + 3 * cap : 3 * cap;
@@ -365,7 +371,7 @@ struct spf_pool {
         if (hipSetDevice(ctx->device) != hipSuccess) return false;
         for (int k = 0; k < 3; k++) {
             if (!in[k]) continue;
-            if (by_handle && scattered_cmux(op)) continue; // read in place through the pointer table
+            if (by_handle && (scattered_cmux(op) || rows_route(op))) continue; // read in place through the pointer table
             if (!grow_dev(s.d_in[k], s.dcap_in[k], cap * in[k])) return false;
             if (!by_handle && !grow_host(s.h_in[k], s.cap_in[k], cap * in[k])) return false;
         }
@@ -957,8 +963,9 @@ struct spf_pool {
         return spf_ops::launch_op(ctx, stream_of(b), b.op, B, d, d_out, b.param, const_cast<Scratch*>(&s.scr), b.per_wg, s.d_mid);
     }
 
-    // A batch by handle: no copies.  The outputs are one block of the arena; the operands are read where they are (CMUX family)
-    // or packed into the set's device rows by gather_rows_kernel — unless they already lie consecutively.
+    // A batch by handle: no copies.  The outputs are one block of the arena; the operands are read where they are (CMUX family:
+    // four pointers per unit; the `rows_in_place` operations: one pointer per item, rows_route) or packed into the set's device
+    // rows by gather_rows_kernel — unless they already lie consecutively.
     spf_status enqueue_v(Batch& b)
     {
         using namespace spf_pool_impl;
@@ -1007,6 +1014,7 @@ struct spf_pool {
                                      : spf_cmux_scattered_dev(ctx, sk, n_units, (const void* const*)s.h_ptrs);
         } else {
             void* d[3] = {nullptr, nullptr, nullptr};
+            bool in_rows = false; // the batch has run over the pointer table (a rows_in_place operation)
             for (int k = 0; k < 3 && st == SPF_OK; k++) {
                 if (!in[k]) continue;
                 char* first = static_cast<char*>(b.slots[0].vin[k]->ptr());
@@ -1015,10 +1023,18 @@ struct spf_pool {
                 if (contiguous) { d[k] = first; continue; }
                 void** row = s.h_ptrs + (size_t)k * b.cap;
                 for (size_t i = 0; i < B; i++) row[i] = b.slots[i].vin[k]->ptr();
+                if (rows_route(b.op)) {
+                    // the rows kernels read the table themselves (one operand: k = 0).  d_out is a fresh block of the arena: it
+                    // overlaps no operand, which they require; the same value may stand in the table several times
+                    const int mode = b.op == OP_GLWE_KEYSWITCH ? spf::GLWE_KS_KEYSWITCH : b.op == OP_GLWE_AUTOMORPHISM ? spf::GLWE_KS_AUTOMORPHISM : spf::GLWE_KS_TRACE;
+                    st = launch_glwe_ks_rows(ctx, sk, mode, (uint32_t)b.param, B, (const uint64_t* const*)row, (uint64_t*)d_out);
+                    in_rows = true;
+                    break;
+                }
                 st = spf_gather_rows_dev(ctx, sk, B, in[k] / 8, (const uint64_t* const*)row, (uint64_t*)s.d_in[k]);
                 d[k] = s.d_in[k];
             }
-            if (st == SPF_OK) st = run_kernels(b, s, B, d, d_out);
+            if (st == SPF_OK && !in_rows) st = run_kernels(b, s, B, d, d_out);
         }
         if (st != SPF_OK) return st;
         if (hipEventRecord(b.ev_k, sk) != hipSuccess) return SPF_ERR_HIP;

@@ -129,6 +129,12 @@ class Evaluation:
     def trace(self, output: np.ndarray, input: np.ndarray):
         self._store(output, self.engine.glwe_trace(input))
 
+    # one round (1 .. log2 N) of the trace's loop (ops/automorphisms/mod.rs:72-83).  The three as single-ciphertext operations of
+    # a pool, by host pointer or on device-resident values: Pool.glwe_keyswitch / glwe_automorphism / glwe_trace and their `_v`
+    # forms (FheOp.GLWE_KEYSWITCH / GLWE_AUTOMORPHISM / GLWE_TRACE through Pool.run_v / push_v)
+    def glwe_automorphism(self, output: np.ndarray, input: np.ndarray, round: int):
+        self._store(output, self.engine.glwe_automorphism(round, input))
+
     # generalized_programmable_bootstrap (programmable_bootstrapping.rs:342-410)
     def generalized_programmable_bootstrap(self, output, input, lut, log_chi: int, log_v: int):
         self._store(output, self.engine.generalized_pbs(input, lut, log_chi, log_v, 0))

@@ -53,9 +53,29 @@ FheOp.PBS_UNIVARIATE = TableOp.PBS_UNIVARIATE
 FheOp.PBS_BIVARIATE = TableOp.PBS_BIVARIATE
 
 
+class KeyswitchOp(enum.IntEnum):
+    """Three more `spf_graph_op` values that are no `FheOp` of the reference: `keyswitch_glwe_to_glwe` (fft_ops.rs:457-495) under
+    the key of slot `param`, round `param` (1 .. log2 N) of the trace's loop, and `trace` (ops/automorphisms/mod.rs:53-85); one GLWE1
+    operand, one GLWE1 result.  Taken wherever an FheOp is and reachable as `FheOp.GLWE_KEYSWITCH` / `GLWE_AUTOMORPHISM` /
+    `GLWE_TRACE`.  In a gate graph they are the nodes of `add_glwe_keyswitch` / `add_glwe_automorphism` / `add_glwe_trace`.  An
+    enum of its own, beside TableOp: the random graph generator of the differential tests draws every member of FheOp and TableOp,
+    and it cannot draw keyswitch keys."""
+    GLWE_KEYSWITCH = 12
+    GLWE_AUTOMORPHISM = 13
+    GLWE_TRACE = 14
+
+
+FheOp.GLWE_KEYSWITCH = KeyswitchOp.GLWE_KEYSWITCH
+FheOp.GLWE_AUTOMORPHISM = KeyswitchOp.GLWE_AUTOMORPHISM
+FheOp.GLWE_TRACE = KeyswitchOp.GLWE_TRACE
+
+
 def graph_op(op):
-    """the member of FheOp or TableOp that a `spf_graph_op` value names"""
-    return TableOp(op) if int(op) in TableOp._value2member_map_ else FheOp(op)
+    """the member of FheOp, TableOp or KeyswitchOp that a `spf_graph_op` value names"""
+    for extra in (TableOp, KeyswitchOp):
+        if int(op) in extra._value2member_map_:
+            return extra(op)
+    return FheOp(op)
 
 
 # RecordedCircuit's codes of the node constructors that are no FheOp (spf_graph_add_unpack / spf_graph_add_pack /
@@ -84,6 +104,10 @@ GLWE_AUTOMORPHISM_NODE = 71
 GLWE_TRACE_NODE = 72
 GLWE_KSK_SLOTS = 16   # SPF_GLWE_KSK_SLOTS
 _GLWE_KS_NODES = (GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE)
+# ... which spf_graph_add_op records for the three KeyswitchOp values as well (the same node, whichever door built it)
+_GLWE_KS_NODE_OF = {int(KeyswitchOp.GLWE_KEYSWITCH): GLWE_KEYSWITCH_NODE, int(KeyswitchOp.GLWE_AUTOMORPHISM): GLWE_AUTOMORPHISM_NODE,
+                    int(KeyswitchOp.GLWE_TRACE): GLWE_TRACE_NODE}
+_GLWE_KS_NAME = {GLWE_KEYSWITCH_NODE: "add_glwe_keyswitch", GLWE_AUTOMORPHISM_NODE: "add_glwe_automorphism", GLWE_TRACE_NODE: "add_glwe_trace"}
 
 # operand kinds of the operations whose arguments RecordedCircuit checks itself, as the library's table does (spf_ops.hpp)
 _PBS_IN_KINDS = {int(TableOp.PBS_UNIVARIATE): (0, 2), int(TableOp.PBS_BIVARIATE): (0, 0, 2)}
@@ -355,6 +379,12 @@ class RecordedCircuit:
     def add_op(self, op: FheOp, inputs: Sequence[int], param: int = 0) -> int:
         if any(i >= len(self.op) for i in inputs):
             raise SpfError(1, "operand is not a node of this circuit")
+        node = _GLWE_KS_NODE_OF.get(int(op))
+        if node is not None:   # recorded as the node of its named constructor, as spf_graph_add_op records it
+            if len(inputs) != 1:   # (the library's text: over another count the value names no operation of spf_graph_add_op)
+                raise SpfError(1, f"graph op: unknown operation: value {int(op)} over {len(inputs)} operands (the GLWE keyswitch, "
+                                  "automorphism round and trace take one GLWE1)")
+            return self._add_glwe_ks(_GLWE_KS_NAME[node], node, param, inputs[0])
         want = _PBS_IN_KINDS.get(int(op))
         if want is not None:   # the bootstraps by table: refused here as spf_graph_add_op refuses them
             if len(inputs) != len(want):

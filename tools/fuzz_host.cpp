@@ -531,7 +531,37 @@ bool graph_ops_match_the_header(spf_ctx* c)
         }
     }
     uint32_t node = 0;
-    expect("no such operation", 12, spf_graph_add_op(g, (spf_graph_op)12, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
+    // the GLWE keyswitch, automorphism round and trace (SPF_OP_GLWE_* = 12 .. 14): one GLWE1 in, one GLWE1 out, recorded as the
+    // nodes of their named constructors (kinds 70 .. 72); the slot below SPF_GLWE_KSK_SLOTS, the round in 1 .. log2 N, the trace's
+    // parameter ignored
+    {
+        uint32_t log_n = 0;
+        while (((uint64_t)1 << (log_n + 1)) <= N) log_n++;
+        const struct { spf_graph_op op; int32_t kind; uint64_t good, kept, bad; const char* why; } glwe_ops[3] = {
+            {SPF_OP_GLWE_KEYSWITCH, 70, SPF_GLWE_KSK_SLOTS - 1, SPF_GLWE_KSK_SLOTS - 1, SPF_GLWE_KSK_SLOTS, "graph op: slot 16 >= SPF_GLWE_KSK_SLOTS = 16"},
+            {SPF_OP_GLWE_AUTOMORPHISM, 71, log_n, log_n, 0, nullptr},
+            {SPF_OP_GLWE_TRACE, 72, 2 * N + 3, 0, 0, nullptr}};
+        for (const auto& h : glwe_ops) {
+            const uint32_t in[2] = {input_of[SPF_VAL_GLWE1], input_of[SPF_VAL_GLWE1]};
+            expect("right kind", h.op, spf_graph_add_op(g, h.op, in, 1, h.good, &node), SPF_OK, nullptr);
+            if (ok && (node + 1 != g->nodes.size() || g->nodes[node].kind != SPF_VAL_GLWE1 || g->nodes[node].op != h.kind || g->nodes[node].param != h.kept)) {
+                fprintf(stderr, "spf_graph_add_op, operation %d: not the node of its named constructor\n", h.op);
+                ok = false;
+            }
+            const size_t n_nodes = g->nodes.size();
+            for (int wrong = 0; wrong < 5; wrong++)
+                if (wrong != SPF_VAL_GLWE1) expect("a wrong kind", h.op, spf_graph_add_op(g, h.op, &input_of[wrong], 1, h.good, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
+            // (over another number of operands the value names no operation of this door: "unknown operation", with value and count)
+            expect("no operand", h.op, spf_graph_add_op(g, h.op, in, 0, h.good, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
+            if (c->err.find("graph op: unknown operation: value " + std::to_string((int)h.op) + " over 0 operands") != 0) { fprintf(stderr, "spf_graph_add_op, operation %d, no operand: %s\n", h.op, c->err.c_str()); ok = false; }
+            expect("one operand too many", h.op, spf_graph_add_op(g, h.op, in, 2, h.good, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
+            if (c->err.find("graph op: unknown operation: value " + std::to_string((int)h.op) + " over 2 operands") != 0) { fprintf(stderr, "spf_graph_add_op, operation %d, two operands: %s\n", h.op, c->err.c_str()); ok = false; }
+            if (h.op != SPF_OP_GLWE_TRACE) expect("a parameter out of range", h.op, spf_graph_add_op(g, h.op, in, 1, h.bad, &node), SPF_ERR_INVALID_ARGUMENT, h.why);
+            if (h.op == SPF_OP_GLWE_AUTOMORPHISM) expect("round log2 N + 1", h.op, spf_graph_add_op(g, h.op, in, 1, log_n + 1, &node), SPF_ERR_INVALID_ARGUMENT, nullptr);
+            if (g->nodes.size() != n_nodes) { fprintf(stderr, "spf_graph_add_op, operation %d: a refused call left a node\n", h.op); ok = false; }
+        }
+    }
+    expect("no such operation", 15, spf_graph_add_op(g, (spf_graph_op)15, &input_of[2], 1, 0, &node), SPF_ERR_INVALID_ARGUMENT, "graph op: unknown operation");
     // the two node constructors of packed integers: n_bits nodes of kind LWE1 with the bit index as parameter / one GLWE1 node
     // whose operand list is kept whole; every refusal of the header, and a refused call leaves nothing behind
     {
@@ -1059,7 +1089,7 @@ int main(int argc, char** argv)
                 case 2: {
                     uint32_t in[4];
                     for (auto& x : in) x = r.below(4) ? (uint32_t)r.below(have + 2) : (uint32_t)r();
-                    st = spf_graph_add_op(g, (spf_graph_op)r.below(14), r.below(10) ? in : nullptr, r.below(5), r.below(2) ? r() : r.below(5000), &node);
+                    st = spf_graph_add_op(g, (spf_graph_op)r.below(16), r.below(10) ? in : nullptr, r.below(5), r.below(2) ? r() : r.below(5000), &node);
                     break;
                 }
                 default: st = spf_graph_add_output(g, r.below(4) ? (uint32_t)r.below(have + 2) : (uint32_t)r(), r.below(8) ? host_buf : nullptr); break;
@@ -1070,6 +1100,12 @@ int main(int argc, char** argv)
             for (size_t i = 0; i < g->nodes.size(); i++) {
                 const auto& n = g->nodes[i];
                 if (n.op < 0) continue;
+                if (n.op >= 70 && n.op <= 72) { // SPF_OP_GLWE_KEYSWITCH / _AUTOMORPHISM / _TRACE: the nodes of their named constructors
+                    if (n.n_in != 1 || n.kind != SPF_VAL_GLWE1) { fprintf(stderr, "graph: bad node accepted\n"); return 1; }
+                    if (n.in[0] >= i || g->nodes[n.in[0]].kind != SPF_VAL_GLWE1) { fprintf(stderr, "graph: bad operand accepted\n"); return 1; }
+                    if (n.op == 70 ? n.param >= SPF_GLWE_KSK_SLOTS : n.op == 71 ? (n.param < 1 || n.param > 11) : n.param != 0) { fprintf(stderr, "graph: bad parameter accepted\n"); return 1; }
+                    continue;
+                }
                 const HeaderOp* info = header_op(n.op);
                 if (!info || n.n_in != (uint32_t)info->arity || n.kind != info->out) { fprintf(stderr, "graph: bad node accepted\n"); return 1; }
                 for (uint32_t j = 0; j < n.n_in; j++)
