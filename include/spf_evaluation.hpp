@@ -234,6 +234,24 @@ class Evaluation {
     {
         check(spf_group_glwe_trace_batch(grp_, B, input_glwes, output_glwes));
     }
+    // The parameter PER ITEM (spf_*_each_batch): item i under params[i], row i of the output its result, ONE launch where the
+    // single-parameter methods above take one call per distinct parameter.  The output must not overlap the input.
+    void sample_extract_l1_each(uint64_t* output, const uint64_t* input, const uint64_t* idx, size_t B)
+    {
+        check(spf_group_sample_extract_l1_each_batch(grp_, B, input, idx, output));
+    }
+    void mul_xn_each(uint64_t* output, const uint64_t* input, const uint64_t* amounts, size_t B)
+    {
+        check(spf_group_glwe_mul_xn_each_batch(grp_, B, input, amounts, output));
+    }
+    void keyswitch_glwe_to_glwe_each(uint64_t* output_glwes, const uint64_t* input_glwes, const uint64_t* slots, size_t B)
+    {
+        check(spf_group_glwe_keyswitch_each_batch(grp_, B, input_glwes, slots, output_glwes));
+    }
+    void glwe_automorphism_each(uint64_t* output_glwes, const uint64_t* input_glwes, const uint64_t* rounds, size_t B)
+    {
+        check(spf_group_glwe_automorphism_each_batch(grp_, B, input_glwes, rounds, output_glwes));
+    }
     // Evaluation::keyswitch_lwe_l1_lwe_l0(&mut L0LweCiphertext, &L1LweCiphertext) (:246)
     void keyswitch_lwe_l1_lwe_l0(uint64_t* output, const uint64_t* input, size_t B = 1)
     {
@@ -539,6 +557,9 @@ class PooledEvaluation {
     // pushed mode: what has been pushed so far is launched now (e.g. once the conversions at the head of a circuit are in: they
     // run under the rest of the push); nothing is waited for
     void flush() const { check(spf_pool_flush(pool_)); }
+    // sample_extract_l1 / mul_xn / keyswitch_glwe_to_glwe / glwe_automorphism calls whose parameters differ share a batch and run
+    // as one launch (spf_pool_set_mixed_parameters); only before the first operation, on every member of the group
+    void set_mixed_parameters(bool on = true) const { check(spf_pool_set_mixed_parameters(pool_, on ? 1 : 0)); }
 
     // `encrypt` / `trivial_*` land here: host words -> a device ciphertext on the calling thread's member
     template <class C> C upload(const void* host) const

@@ -538,6 +538,43 @@ spf_status spf_glwe_poly_linear_enqueue(spf_ctx *ctx, void *stream, uint32_t slo
 spf_status spf_glwe_poly_slot_shape(spf_ctx *ctx, uint32_t slot, size_t *M, size_t *K, size_t *terms, int *has_bias);
 const char *spf_last_glwe_poly_kernel(spf_ctx *ctx);
 
+/* ---- one launch over items with a parameter each ------------------------------------------------
+ * The four single-operand operations that take a parameter, with the parameter PER ITEM: item i of the batch runs under
+ * params[i], row i of the output is its result, every word equal to the single-parameter call's.
+ *   spf_sample_extract_l1_each_*   replaces one spf_sample_extract_l1_batch / _dev call per distinct index (the 32
+ *                                  `SampleExtract(i)` of a 32-bit unpack are ONE call); idx[i] < N
+ *   spf_glwe_mul_xn_each_*         replaces one spf_glwe_mul_xn_batch / _dev call per distinct amount; amounts[i] taken mod 2N
+ *   spf_glwe_keyswitch_each_*      replaces one spf_glwe_keyswitch_batch / _enqueue call per distinct slot; slots[i] < SPF_GLWE_KSK_SLOTS
+ *   spf_glwe_automorphism_each_*   replaces one spf_glwe_automorphism_batch / _enqueue call per distinct round; rounds[i] in 1 .. log2 N
+ * (the trace has no parameter).  The parameters are a HOST array of B values in every form, read during the call.
+ * Launches: SampleExtract, MulXN and the automorphism round make ONE launch; the keyswitch one launch per distinct
+ * (radix_log, radix_count) among the slots named — keys of different radix never share a launch.  The kernels read every operand
+ * once, where it lies, through a pointer table (no gather pass); the hand-written keyswitch kernel ("glwe_ks_each_kernel", 6 x 7
+ * bits at N = 2048, k = 1; elsewhere "generic_glwe_ks_each_kernel" — spf_last_glwe_keyswitch_kernel names them, "glwe_keyswitch"
+ * of spf_last_kernel_ms times them) runs four items per workgroup over one key, so the items are ordered by parameter and every
+ * parameter's run is padded to a whole workgroup; the results land in the caller's order all the same.
+ * Before anything is queued, and touching nothing: an index >= N, a slot >= SPF_GLWE_KSK_SLOTS or a round outside 1 .. log2 N is
+ * SPF_ERR_INVALID_ARGUMENT with the offending position and value in the message; an empty slot, or no automorphism key, is
+ * SPF_ERR_NO_KEY; B = 0 is SPF_OK; ANY overlap of output and input — out == in too: the kernels write row i while other items are
+ * still being read — is SPF_ERR_INVALID_ARGUMENT.
+ * The _devptr forms (not `_dev`: unlike every `_dev` entry point they also read a host array, during the call) take device
+ * pointers for the ciphertexts under the contract of the `_dev` entry points above and only enqueue on `stream`; the
+ * pointer and parameter tables of a call live in a buffer of the context, so use ONE stream per context with them (a call may
+ * wait until the previous call's table has left the host).  There is no _enqueue form: that contract allows no buffer of the
+ * context.  (SPF_GLWE_KSK_SLOTS, the key slots and spf_last_glwe_keyswitch_kernel: the next section.)  The group forms deal the parameter array in the same contiguous shards as the items. */
+spf_status spf_sample_extract_l1_each_batch(spf_ctx *ctx, size_t B, const uint64_t *glwe_in, const uint64_t *idx, uint64_t *lwe1_out);
+spf_status spf_sample_extract_l1_each_devptr(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe_in, const uint64_t *idx,
+                                          uint64_t *d_lwe1_out);
+spf_status spf_glwe_mul_xn_each_batch(spf_ctx *ctx, size_t B, const uint64_t *glwe_in, const uint64_t *amounts, uint64_t *glwe_out);
+spf_status spf_glwe_mul_xn_each_devptr(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe_in, const uint64_t *amounts,
+                                    uint64_t *d_glwe_out);
+spf_status spf_glwe_keyswitch_each_batch(spf_ctx *ctx, size_t B, const uint64_t *glwe_in, const uint64_t *slots, uint64_t *glwe_out);
+spf_status spf_glwe_keyswitch_each_devptr(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe_in, const uint64_t *slots,
+                                       uint64_t *d_glwe_out);
+spf_status spf_glwe_automorphism_each_batch(spf_ctx *ctx, size_t B, const uint64_t *glwe_in, const uint64_t *rounds, uint64_t *glwe_out);
+spf_status spf_glwe_automorphism_each_devptr(spf_ctx *ctx, void *stream, size_t B, const uint64_t *d_glwe_in, const uint64_t *rounds,
+                                          uint64_t *d_glwe_out);
+
 /* ---- GLWE keyswitch, one automorphism round, homomorphic trace ---------------------------------
  * The three functions the circuit bootstrap's trace is built from, on B GLWEs of (k+1)*N words each (SPF_VAL_GLWE1 rows), B
  * GLWEs out:
@@ -620,8 +657,10 @@ spf_status spf_pool_submit_cmux(spf_pool *pool, const double *sel_ggsw_fft, cons
                                 uint64_t *out, uint64_t *ticket);
 /* The other operations `CircuitProcessor::exec_op` issues per task (circuit_processor/mod.rs:341-540), one ciphertext per call:
  *   FheOp::SampleExtract(idx) -> `KeylessEvaluation::sample_extract_l1` (crypto/evaluation.rs:126-133); idx >= N is
- *                                SPF_ERR_INVALID_ARGUMENT.  Calls with different indices run in different batches.
- *   FheOp::Not / GlweAdd / MulXN(n) -> `not` / `xor` / `mul_xn` (crypto/evaluation.rs:47-66); n is taken mod 2N
+ *                                SPF_ERR_INVALID_ARGUMENT.  Calls with different indices run in different batches
+ *                                unless the pool mixes parameters (spf_pool_set_mixed_parameters below).
+ *   FheOp::Not / GlweAdd / MulXN(n) -> `not` / `xor` / `mul_xn` (crypto/evaluation.rs:47-66); n is taken mod 2N (calls with
+ *                                different amounts: as for the indices)
  *   FheOp::MultiplyGgswGlwe -> `multiply_glwe_ggsw` (:104-123)         FheOp::GlevCMux -> `glev_cmux` (:86-101), GLEVs of l_cbs GLWEs
  *   FheOp::SchemeSwitch -> `Evaluation::scheme_switch` (:231-240) */
 spf_status spf_pool_submit_sample_extract(spf_pool *pool, const uint64_t *glwe_in, size_t idx, uint64_t *lwe1_out, uint64_t *ticket);
@@ -635,7 +674,7 @@ spf_status spf_pool_submit_glev_cmux(spf_pool *pool, const double *sel_ggsw_fft,
 spf_status spf_pool_submit_scheme_switch(spf_pool *pool, const uint64_t *glev_in, double *ggsw_fft_out, uint64_t *ticket);
 /* `keyswitch_glwe_to_glwe` under the key of `slot`, one round of the trace's loop and `trace` (spf_glwe_keyswitch_batch /
  * spf_glwe_automorphism_batch / spf_glwe_trace_batch above) for one GLWE; word-equal to those.  Calls with different slots or
- * rounds run in different batches.  Checked at the submit: slot >= SPF_GLWE_KSK_SLOTS, round 0 or round > log2 N are
+ * rounds run in different batches unless the pool mixes parameters (spf_pool_set_mixed_parameters below).  Checked at the submit: slot >= SPF_GLWE_KSK_SLOTS, round 0 or round > log2 N are
  * SPF_ERR_INVALID_ARGUMENT; an empty slot, or no automorphism key, is SPF_ERR_NO_KEY; a refused call takes no ticket.
  * The batch reads the slot again when it is launched.  Reloading a slot (spf_load_glwe_keyswitch_key_std, or the automorphism
  * key) while submissions that use it are outstanding is the caller's error, as for every key loader: WAIT for every ticket and
@@ -651,6 +690,15 @@ spf_status spf_pool_wait(spf_pool *pool, uint64_t ticket);
  * circuit_processor/mod.rs:139): a submit blocks while `max_inflight` tickets are submitted and not yet
  * collected.  Default 4 x max_batch. */
 spf_status spf_pool_set_max_inflight(spf_pool *pool, size_t max_inflight);
+/* Mixed parameters, opt-in (`on` != 0; the default is off and changes nothing): SampleExtract, MulXN, GLWE keyswitch and
+ * automorphism calls with DIFFERENT indices, amounts, slots or rounds join the same batch — by host pointer and by handle, on
+ * valid and on pending operands — and the batch runs as ONE launch of the per-item kernels (spf_*_each_* above) over its members'
+ * parameters: the 32 `SampleExtract(i)` of a 32-bit unpack are one launch, not 32.  A keyswitch batch holds slots of ONE
+ * (radix_log, radix_count), as read at the submit: keys of different radix never share a launch.  Every other operation batches
+ * as before (a blind rotation's steps sit at different depths and never meet; a bivariate bootstrap's plaintext_bits are a
+ * constant of a workload).  Results are word-equal to the pool without it.  Legal only before the pool's first submit:
+ * afterwards SPF_ERR_INVALID_ARGUMENT.  A group pool applies it to every member.  The rule for reloading a key slot is unchanged. */
+spf_status spf_pool_set_mixed_parameters(spf_pool *pool, int on);
 /* operations completed and batches launched so far (ops / launches = achieved batch size) */
 spf_status spf_pool_stats(spf_pool *pool, uint64_t *ops, uint64_t *launches);
 
@@ -1187,6 +1235,17 @@ spf_status spf_group_load_glwe_keyswitch_key_std(spf_group *grp, uint32_t slot, 
 spf_status spf_group_glwe_keyswitch_batch(spf_group *grp, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 spf_status spf_group_glwe_automorphism_batch(spf_group *grp, uint32_t round, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 spf_status spf_group_glwe_trace_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+/* The per-item forms (spf_sample_extract_l1_each_batch, spf_glwe_mul_xn_each_batch, spf_glwe_keyswitch_each_batch,
+ * spf_glwe_automorphism_each_batch): a batch is sharded by item and the parameter array is dealt in the same contiguous shards;
+ * the checks are made on the whole batch before any member is touched */
+spf_status spf_group_sample_extract_l1_each_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, const uint64_t *idx,
+                                                  uint64_t *lwe1_out);
+spf_status spf_group_glwe_mul_xn_each_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, const uint64_t *amounts,
+                                            uint64_t *glwe_out);
+spf_status spf_group_glwe_keyswitch_each_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, const uint64_t *slots,
+                                               uint64_t *glwe_out);
+spf_status spf_group_glwe_automorphism_each_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, const uint64_t *rounds,
+                                                  uint64_t *glwe_out);
 /* `Evaluation::l1ggsw_zero` / `l1ggsw_one` (identical on every member: same keys, same kernels; taken from member 0) */
 spf_status spf_group_l1ggsw_constant(spf_group *grp, int bit, double *ggsw_fft_out);
 

@@ -122,6 +122,15 @@ SYMBOLS = [
     ("spf_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_glwe_trace_enqueue", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_last_glwe_keyswitch_kernel", C.c_char_p, [_P]),
+    # the per-item forms: (ctx, [stream,] B, in, HOST array of B parameters, out)
+    ("spf_sample_extract_l1_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_sample_extract_l1_each_devptr", _I, [_P, _P, _SZ, _P, _P, _P]),
+    ("spf_glwe_mul_xn_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_glwe_mul_xn_each_devptr", _I, [_P, _P, _SZ, _P, _P, _P]),
+    ("spf_glwe_keyswitch_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_glwe_keyswitch_each_devptr", _I, [_P, _P, _SZ, _P, _P, _P]),
+    ("spf_glwe_automorphism_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_glwe_automorphism_each_devptr", _I, [_P, _P, _SZ, _P, _P, _P]),
     ("spf_keyswitch_lwe_l1_lwe_l0_dev", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_generalized_pbs_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _U32, _U32, _U64, _P]),
     ("spf_pbs_univariate_dev", _I, [_P, _P, _SZ, _P, _P, _SZ, _P]),
@@ -150,6 +159,7 @@ SYMBOLS = [
     ("spf_pool_submit_glwe_trace", _I, [_P, _P, _P, C.POINTER(_U64)]),
     ("spf_pool_wait", _I, [_P, _U64]),
     ("spf_pool_set_max_inflight", _I, [_P, _SZ]),
+    ("spf_pool_set_mixed_parameters", _I, [_P, C.c_int]),
     ("spf_pool_stats", _I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
     ("spf_graph_create", _I, [_P, C.POINTER(_P)]),
     ("spf_graph_destroy", None, [_P]),
@@ -245,6 +255,10 @@ SYMBOLS = [
     ("spf_group_load_glwe_keyswitch_key_std", _I, [_P, _U32, _P, _SZ, _U32, _U32]),
     ("spf_group_glwe_keyswitch_batch", _I, [_P, _U32, _SZ, _P, _P]),
     ("spf_group_glwe_automorphism_batch", _I, [_P, _U32, _SZ, _P, _P]),
+    ("spf_group_sample_extract_l1_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_group_glwe_mul_xn_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_group_glwe_keyswitch_each_batch", _I, [_P, _SZ, _P, _P, _P]),
+    ("spf_group_glwe_automorphism_each_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_group_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
@@ -931,6 +945,39 @@ class Engine:
         self._ck(self._lib.spf_glwe_automorphism_batch(self._h, int(round) & 0xFFFFFFFF, x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    # ---- the parameter per item (spf_*_each_batch): ONE launch over B items under B parameters, row i the result of item i under
+    # params[i].  `out`: a caller's array to write into (the tests look at the rows around it), else a fresh one.
+    def _each(self, name: str, fn, glwes, params, out_words: int, out):
+        x = self._glwes(name, glwes)
+        try:
+            p = np.array([int(v) for v in (params.reshape(-1) if isinstance(params, np.ndarray) else params)], dtype=np.uint64).reshape(-1)
+        except (OverflowError, TypeError, ValueError):
+            raise SpfError(-2, f"{name}: the parameters must be non-negative integers below 2^64")
+        if p.shape[0] != x.shape[0]:
+            raise SpfError(-2, f"{name}: {x.shape[0]} items but {p.shape[0]} parameters")
+        if out is None:
+            out = np.empty((x.shape[0], out_words), dtype=np.uint64)
+        else:
+            _out(name, out, np.uint64, x.shape[0] * out_words)
+        self._ck(fn(self._h, x.shape[0], _ptr(x), _ptr(p), _ptr(out)))
+        return out
+
+    def sample_extract_l1_each(self, glwes, idx, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """`sample_extract(glwes[i], idx[i])`: replaces one sample_extract_l1 call per distinct index"""
+        return self._each("sample_extract_l1_each", self._lib.spf_sample_extract_l1_each_batch, glwes, idx, self.params.lwe1_words, out)
+
+    def glwe_mul_xn_each(self, glwes, amounts, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """`glwes[i] * X^amounts[i]`, amounts mod 2N: replaces one glwe_mul_xn call per distinct amount"""
+        return self._each("glwe_mul_xn_each", self._lib.spf_glwe_mul_xn_each_batch, glwes, amounts, self.params.glwe_words, out)
+
+    def glwe_keyswitch_each(self, slots, glwes, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """item i under the key of slot slots[i]: replaces one glwe_keyswitch call per distinct slot"""
+        return self._each("glwe_keyswitch_each", self._lib.spf_glwe_keyswitch_each_batch, glwes, slots, self.params.glwe_words, out)
+
+    def glwe_automorphism_each(self, rounds, glwes, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """item i through round rounds[i] of the trace's loop: replaces one glwe_automorphism call per distinct round"""
+        return self._each("glwe_automorphism_each", self._lib.spf_glwe_automorphism_each_batch, glwes, rounds, self.params.glwe_words, out)
+
     def glwe_trace(self, glwes) -> np.ndarray:
         """`trace` (ops/automorphisms/mod.rs:53-85) of (B, k+1, N) GLWEs under the context's automorphism key"""
         x = self._glwes("glwe_trace", glwes)
@@ -1074,6 +1121,25 @@ class Engine:
 
     def glwe_automorphism_enqueue(self, stream, round, B, d_glwe_in, d_glwe_out):
         self._ck(self._lib.spf_glwe_automorphism_enqueue(self._h, stream, int(round) & 0xFFFFFFFF, B, d_glwe_in, d_glwe_out))
+
+    # the per-item forms on device pointers: `params` a HOST array of B values (one stream per context)
+    def _each_dev(self, fn, stream, B, d_in, params, d_out):
+        p = np.ascontiguousarray(params, dtype=np.uint64).reshape(-1)
+        if p.shape[0] != int(B):
+            raise SpfError(-2, f"{int(B)} items but {p.shape[0]} parameters")
+        self._ck(fn(self._h, stream, B, d_in, _ptr(p), d_out))
+
+    def sample_extract_l1_each_dev(self, stream, B, d_glwe, idx, d_out):
+        self._each_dev(self._lib.spf_sample_extract_l1_each_devptr, stream, B, d_glwe, idx, d_out)
+
+    def glwe_mul_xn_each_dev(self, stream, B, d_in, amounts, d_out):
+        self._each_dev(self._lib.spf_glwe_mul_xn_each_devptr, stream, B, d_in, amounts, d_out)
+
+    def glwe_keyswitch_each_dev(self, stream, slots, B, d_glwe_in, d_glwe_out):
+        self._each_dev(self._lib.spf_glwe_keyswitch_each_devptr, stream, B, d_glwe_in, slots, d_glwe_out)
+
+    def glwe_automorphism_each_dev(self, stream, rounds, B, d_glwe_in, d_glwe_out):
+        self._each_dev(self._lib.spf_glwe_automorphism_each_devptr, stream, B, d_glwe_in, rounds, d_glwe_out)
 
     def glwe_trace_enqueue(self, stream, B, d_glwe_in, d_glwe_out):
         self._ck(self._lib.spf_glwe_trace_enqueue(self._h, stream, B, d_glwe_in, d_glwe_out))
@@ -1246,6 +1312,13 @@ class Pool:
         if st != 0:
             raise SpfError(st, "spf_pool_set_max_inflight failed")
 
+    def set_mixed_parameters(self, on: bool = True):
+        """`spf_pool_set_mixed_parameters`: SampleExtract / MulXN / GLWE keyswitch / automorphism calls whose parameters differ
+        share a batch, run as one launch of the per-item kernels.  Only before the pool's first submit."""
+        st = self._lib.spf_pool_set_mixed_parameters(self._h, 1 if on else 0)
+        if st != 0:
+            raise SpfError(st, "spf_pool_set_mixed_parameters: only before the pool's first submit")
+
     def submit_keyswitch(self, output: np.ndarray, input: np.ndarray) -> int:
         """asynchronous form: returns the ticket; buffers must stay alive until wait(ticket) returns"""
         t = C.c_uint64()
@@ -1364,7 +1437,7 @@ class Pool:
         self._run("scheme_switch", self._lib.spf_pool_submit_scheme_switch, _ptr(x), _ptr(output))
 
     # -- keyswitch_glwe_to_glwe under the key of `slot`, one round of the trace's loop, trace: one GLWE per call, word-equal to
-    # Engine.glwe_keyswitch / glwe_automorphism / glwe_trace.  Calls with different slots or rounds run in different batches; an
+    # Engine.glwe_keyswitch / glwe_automorphism / glwe_trace.  Calls with different slots or rounds run in different batches unless the pool mixes parameters (set_mixed_parameters); an
     # empty slot or a missing automorphism key is refused at the submit (SPF_ERR_NO_KEY)
     def _run_glwe_ks(self, what, fn, output, glwe, *param):
         P = self.engine.params

@@ -408,6 +408,41 @@ __global__ void generic_linear_kernel(const uint64_t* a, const uint64_t* b, uint
     }
 }
 
+// generic_sample_extract_kernel and generic_linear_kernel's MulXN with the parameter per item, operands where they lie (the
+// twins of sample_extract_each_kernel / glwe_mul_xn_each_kernel, spf_kernels.hpp, for any (N, k)): item blockIdx.y is rows[ct], its
+// index / amount (reduced mod 2N) param[ct] — workgroup-uniform, scalar loads —, row ct of the output block is written; the items
+// go over grid.y in a stride: one launch whatever B.
+__global__ void generic_sample_extract_each_kernel(const uint64_t* const* __restrict__ rows, const uint32_t* __restrict__ param,
+                                                   uint64_t* __restrict__ lwe, uint32_t B, uint32_t N, uint32_t k)
+{
+    for (uint32_t ct = blockIdx.y; ct < B; ct += gridDim.y) {
+        const uint64_t* a = rows[ct];
+        const uint32_t hidx = param[ct];
+        uint64_t* o = lwe + (size_t)ct * (k * N + 1);
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i <= k * N; i += gridDim.x * blockDim.x) {
+            if (i == k * N) { o[i] = a[k * N + hidx]; continue; }
+            const uint32_t p = i / N, j = i % N;
+            o[i] = j <= hidx ? a[p * N + hidx - j] : (uint64_t)0 - a[p * N + hidx + N - j];
+        }
+    }
+}
+
+__global__ void generic_mul_xn_each_kernel(const uint64_t* const* __restrict__ rows, const uint32_t* __restrict__ param,
+                                           uint64_t* __restrict__ out, uint32_t B, uint32_t N, uint32_t logN, uint32_t k)
+{
+    const uint32_t len = (k + 1) * N;
+    for (uint32_t ct = blockIdx.y; ct < B; ct += gridDim.y) {
+        const uint64_t* x = rows[ct];
+        const uint32_t n = param[ct];
+        uint64_t* o = out + (size_t)ct * len;
+        for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < len; i += gridDim.x * blockDim.x) {
+            const uint32_t p = i / N, c = i % N, idx = c + 2 * N - n; // out = in * X^n: out[c] = +-in[(c - n) mod N]
+            const uint64_t v = x[p * N + (idx & (N - 1))];
+            o[i] = ((idx >> logN) & 1) ? (uint64_t)0 - v : v;
+        }
+    }
+}
+
 struct GenericTraceArgs {
     GenericShape g;
     const uint64_t* glwe_in; // B x (k+1) N: lo-noise GLWE out of the bootstrap

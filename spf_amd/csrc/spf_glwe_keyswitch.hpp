@@ -47,6 +47,32 @@ struct GlweKsRowsArgs {
     uint32_t kk;
 };
 
+// The rows form with the parameter PER ITEM (spf_glwe_keyswitch_each_*, spf_glwe_automorphism_each_*): the keyswitch-key slot or
+// the automorphism round belongs to the item, not to the launch.  The four units of a workgroup share one LDS key ring, so they
+// share their key: the host orders the items by parameter and pads every parameter's run to whole workgroups (the segment plan,
+// spf_each_plan.hpp) and hands the kernel
+//   wg[w]     the key base and kk of workgroup w (workgroup-uniform: scalar loads)
+//   unit[u]   the operand pointer of unit u = 4 w + slot and the output row it owns, or spf_each::kNoRow — a padding unit: a
+//             duplicate of an item of its own workgroup that reads, takes part in every barrier and stores nothing
+// Both tables cover gridDim.x whole workgroups: no unit index is clamped.  The results land in the caller's order (unit u of item i
+// writes row i of `out`).  Aliasing contract: that of GlweKsRowsArgs.  Keyswitch and automorphism modes only (the trace has no
+// parameter).
+struct GlweKsEachUnit {
+    const uint64_t* in;
+    uint32_t out_row, reserved;
+};
+struct GlweKsEachWg {
+    const c64* key;
+    uint32_t kk, reserved;
+};
+struct GlweKsEachArgs {
+    const GlweKsEachUnit* unit; // [gridDim.x * kWavesPerBlock]
+    const GlweKsEachWg* wg;     // [gridDim.x]
+    uint64_t* out;              // the rows named by unit[].out_row, disjoint from every operand row
+    const c64* tables;
+};
+constexpr uint32_t kGlweKsNoRow = 0xFFFFFFFFu; // (= spf_each::kNoRow; the launcher asserts it)
+
 // ---------------------------------------------------------------------------------------------------------------
 // The body of cbs_trace_kernel (spf_cbs_tail.hpp, where the schedule is explained: three transform pairs for the six digits, one
 // inverse pair, the key rows through a 64 KiB LDS ring filled by LDS-DMA one digit pair ahead, bare workgroup barriers) in three
@@ -62,11 +88,14 @@ struct GlweKsRowsArgs {
 // of a ragged last workgroup is a duplicate of the last item, lives in that item's workgroup and stores nothing.
 // `Args` is GlweKsArgs or GlweKsRowsArgs: only the entry loads differ.  The rows form loads the item's pointer once per wave (the
 // unit is wave-uniform: a scalar load) where the in-place form computes in + unit * 2N; park, padding units and the wait in front of
-// the first barrier are the same.
+// the first barrier are the same.  GlweKsEachArgs (above): the unit's pointer and output row and the workgroup's key and kk come
+// from the two tables, four scalar loads per wave; everything behind the entry is the rows form's.
 template <int L, int LOGB, int W, int MODE, class Args>
 __device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
 {
-    constexpr bool kRows = std::is_same<Args, GlweKsRowsArgs>::value;
+    constexpr bool kEach = std::is_same<Args, GlweKsEachArgs>::value;
+    constexpr bool kRows = std::is_same<Args, GlweKsRowsArgs>::value || kEach;
+    static_assert(!kEach || MODE != GLWE_KS_TRACE, "the trace has no parameter");
     static_assert(L == 6 && LOGB == 7, "three digit pairs; the state after the first pair fits 32 bits");
     constexpr int XP = 2;
     constexpr int NT = 512;
@@ -87,19 +116,42 @@ __device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
     // below).  The table is read through the constant address space (nothing writes it while the kernel runs): as a plain global
     // load hipcc made it scalar in the W = 0 body only, and a vector load of one address in all lanes in the other
     [[maybe_unused]] gu64_cptr row_in = nullptr;
-    if constexpr (kRows) {
-        typedef const uint64_t* const __attribute__((address_space(4))) * table_ptr;
-        const uint32_t u = blockIdx.x * kWavesPerBlock + cslot;
-        row_in = global_view(((table_ptr)(uintptr_t)a.in_rows)[u < a.units ? u : a.units - 1]);
+    [[maybe_unused]] uint32_t each_row = 0;
+    const c64* key_base;
+    uint32_t kk_arg;
+    if constexpr (kEach) {
+        typedef const GlweKsEachUnit __attribute__((address_space(4))) * unit_ptr;
+        typedef const GlweKsEachWg __attribute__((address_space(4))) * wg_ptr;
+        const unit_ptr up = (unit_ptr)(uintptr_t)a.unit + (blockIdx.x * kWavesPerBlock + cslot);
+        const wg_ptr wp = (wg_ptr)(uintptr_t)a.wg + blockIdx.x;
+        row_in = global_view(up->in);
+        each_row = up->out_row;
+        key_base = wp->key;
+        kk_arg = wp->kk;
+    } else {
+        if constexpr (kRows) {
+            typedef const uint64_t* const __attribute__((address_space(4))) * table_ptr;
+            const uint32_t u = blockIdx.x * kWavesPerBlock + cslot;
+            row_in = global_view(((table_ptr)(uintptr_t)a.in_rows)[u < a.units ? u : a.units - 1]);
+        }
+        key_base = a.key;
+        kk_arg = a.kk;
     }
     {
         const double2* src = reinterpret_cast<const double2*>(a.tables);
         double2* dst = reinterpret_cast<double2*>(smem);
         for (int i = tid; i < kTableEntries; i += NT) dst[i] = src[i];
     }
-    const uint32_t unit_raw = blockIdx.x * kWavesPerBlock + cslot;
-    const bool owns_output = unit_raw < a.units;
-    const uint32_t unit = owns_output ? unit_raw : a.units - 1;
+    bool owns_output;
+    uint32_t unit;
+    if constexpr (kEach) {
+        owns_output = each_row != kGlweKsNoRow;
+        unit = owns_output ? each_row : 0u; // (a padding unit's row is never addressed)
+    } else {
+        const uint32_t unit_raw = blockIdx.x * kWavesPerBlock + cslot;
+        owns_output = unit_raw < a.units;
+        unit = owns_output ? unit_raw : a.units - 1;
+    }
 
     // key chunk c = 3 round + m: the 64 KiB [level L-2-2m | level L-1-2m] of that round, copied as it lies: the first digit of
     // the pair (j = 2m, level L-1-2m) is the ring's second half
@@ -107,7 +159,7 @@ __device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
     const uint32_t dma_dst = lds_address(ring) + wv * 1024;
     auto ring_dma = [&](uint32_t chunk) {
         const uint32_t rnd = chunk / 3, m = chunk % 3;
-        const char* src = reinterpret_cast<const char*>(a.key) +
+        const char* src = reinterpret_cast<const char*>(key_base) +
                           (size_t)__builtin_amdgcn_readfirstlane(rnd * L + (L - 2 - 2 * m)) * kBskSlotBytes;
 #pragma unroll
         for (int k = 0; k < 2 * kBskSlotBytes / (NT * 16); k++)
@@ -159,7 +211,7 @@ __device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
     for (uint32_t it = 0; it < kRounds; it++) {
         // automorphism X -> X^kk (ops/polynomial/mod.rs:62-84): out[d] = +-in[c], c kk = d mod 2N <=> c' = d kk^-1 mod 2N,
         // c = c' mod N, sign = c' >= N.  kk^-1 is odd: every source lies in this wave's own staging region.
-        const uint32_t kk = kTrace ? (uint32_t)(kN >> it) + 1 : a.kk;
+        const uint32_t kk = kTrace ? (uint32_t)(kN >> it) + 1 : kk_arg;
         uint32_t kinv = kk; // Newton iteration for the inverse of an odd number mod 2^12
         kinv *= 2 - kk * kinv; kinv *= 2 - kk * kinv; kinv *= 2 - kk * kinv; kinv *= 2 - kk * kinv;
         kinv &= 2 * kN - 1;
@@ -347,7 +399,7 @@ __device__ __forceinline__ void glwe_ks_body(const Args& a, char* smem)
         if constexpr (kTrace) {
             if (chunk < total_chunks) { // rows of the next round's first digit pair, this wave's share = the slot it just read
                 const uint32_t rnd = chunk / 3;
-                const char* src = reinterpret_cast<const char*>(a.key) +
+                const char* src = reinterpret_cast<const char*>(key_base) +
                                   (size_t)__builtin_amdgcn_readfirstlane(rnd * L + (L - 2)) * kBskSlotBytes + (wv ^ 1) * 8192;
                 const uint32_t lane16 = (uint32_t)lane * 16u;
                 const uint32_t dst = lds_address(ring) + (wv ^ 1) * 8192;
@@ -392,6 +444,15 @@ __global__ __launch_bounds__(512, 2) void glwe_ks_kernel(GlweKsArgs a)
 // The rows form (GlweKsRowsArgs above): same grid, same LDS, same body
 template <int L, int LOGB, int MODE>
 __global__ __launch_bounds__(512, 2) void glwe_ks_rows_kernel(GlweKsRowsArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) glwe_ks_body<L, LOGB, 1, MODE>(a, smem);
+    else glwe_ks_body<L, LOGB, 0, MODE>(a, smem);
+}
+
+// The per-item form (GlweKsEachArgs above): grid = the plan's workgroups, same LDS, same body
+template <int L, int LOGB, int MODE>
+__global__ __launch_bounds__(512, 2) void glwe_ks_each_kernel(GlweKsEachArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) glwe_ks_body<L, LOGB, 1, MODE>(a, smem);
@@ -498,6 +559,53 @@ __global__ __launch_bounds__(kGenericThreads) void generic_glwe_ks_rows_kernel(G
             });
     }
     uint64_t* out = a.out + (size_t)blockIdx.x * len;
+    for (uint32_t i = tid; i < len; i += kGenericThreads) out[i] = X[i];
+}
+
+// The per-item form: item b is unit[b].in under the key and kk of wg[b] (one unit per workgroup: the segment plan of
+// spf_each_plan.hpp at units_per_wg = 1, where both tables have one entry per item and no padding), its result row
+// unit[b].out_row of a.out.  a.in, a.key and a.kk are not read; a.mode is GLWE_KS_KEYSWITCH or GLWE_KS_AUTOMORPHISM (one round).
+// The third sibling of the two kernels above, for the reason given there — keep the three in step.
+__global__ __launch_bounds__(kGenericThreads) void generic_glwe_ks_each_kernel(GenericGlweKsArgs a, const GlweKsEachUnit* units,
+                                                                               const GlweKsEachWg* wgs)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const GenericShape& g = a.g;
+    const uint32_t tid = threadIdx.x, N = g.N, h = N / 2, k = g.k, len = (k + 1) * N;
+    c64* accf = reinterpret_cast<c64*>(smem);
+    c64* buf = accf + (size_t)(k + 1) * h;
+    uint64_t* state = reinterpret_cast<uint64_t*>(buf + h);
+    c64* tmp = reinterpret_cast<c64*>(state + N);
+    uint64_t* X = state + 2 * N;
+    uint64_t* G = X + len;
+    const GlweKsEachUnit unit = units[blockIdx.x]; // workgroup-uniform: scalar loads
+    const GlweKsEachWg wg = wgs[blockIdx.x];
+    gu64_cptr in = global_view(unit.in);
+    for (uint32_t i = tid; i < len; i += kGenericThreads) X[i] = in[i];
+    __syncthreads();
+    const size_t glev_len = (size_t)a.count * (k + 1) * h;
+    {
+        const uint32_t kk = a.mode == GLWE_KS_AUTOMORPHISM ? wg.kk : 1;
+        // polynomial_pow_k (ops/polynomial/mod.rs:62-84): p_k[(i kk) mod N] = +-p[i], minus when (i kk) / N is odd; kk = 1: a copy
+        for (uint32_t i = tid; i < len; i += kGenericThreads) {
+            const uint32_t p = i / N, c = i % N, prod = c * kk;
+            const uint64_t v = X[i];
+            G[p * N + (prod & (N - 1))] = ((prod >> g.logN) & 1) ? (uint64_t)0 - v : v;
+        }
+        for (uint32_t i = tid; i < (k + 1) * h; i += kGenericThreads) accf[i] = {0.0, 0.0};
+        __syncthreads();
+        const c64* ksk = wg.key;
+        for (uint32_t r = 0; r < k; r++)
+            generic_glev_mad(g, accf, buf, state, ksk + (size_t)r * glev_len, a.radix_log, a.count,
+                             [&](uint32_t i) { return G[r * N + i]; });
+        // trivial(b_k) - ks
+        for (uint32_t q = 0; q <= k; q++)
+            generic_poly_ifft(g, accf + (size_t)q * h, buf, tmp, [&](uint32_t i, uint64_t t) {
+                X[q * N + i] = (q == k ? G[k * N + i] : (uint64_t)0) - t;
+            });
+    }
+    if (unit.out_row == kGlweKsNoRow) return;
+    uint64_t* out = a.out + (size_t)unit.out_row * len;
     for (uint32_t i = tid; i < len; i += kGenericThreads) out[i] = X[i];
 }
 

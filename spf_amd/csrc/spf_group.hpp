@@ -905,6 +905,33 @@ spf_status spf_group_glwe_trace_batch(spf_group* g, size_t B, const uint64_t* in
     return group_glwe_ks(g, GLWE_KS_TRACE, 0, B, in, out);
 }
 
+// The per-item forms (spf_*_each_batch): sharded by item, the parameter array — the second operand of each_shape, one word per
+// item — dealt in the same contiguous shards; the checks are made on the whole batch, on member 0
+static spf_status group_each(spf_group* g, int op, size_t B, const uint64_t* in, const uint64_t* params, uint64_t* out)
+{
+    if (spf_status s = group_args(g, false)) return s;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = each_args(c0, op, B, in, params, out)) return gfail(g, s, spf_last_error(c0));
+    return group_batch(g, spf_ops::each_shape(c0->prm, op), B, {in, params}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows params, Rows out) { return each_batch(c, op, n, in, params, out); });
+}
+spf_status spf_group_sample_extract_l1_each_batch(spf_group* g, size_t B, const uint64_t* glwe_in, const uint64_t* idx, uint64_t* lwe1_out)
+{
+    return group_each(g, spf_ops::OP_SAMPLE_EXTRACT, B, glwe_in, idx, lwe1_out);
+}
+spf_status spf_group_glwe_mul_xn_each_batch(spf_group* g, size_t B, const uint64_t* glwe_in, const uint64_t* amounts, uint64_t* glwe_out)
+{
+    return group_each(g, spf_ops::OP_MUL_XN, B, glwe_in, amounts, glwe_out);
+}
+spf_status spf_group_glwe_keyswitch_each_batch(spf_group* g, size_t B, const uint64_t* glwe_in, const uint64_t* slots, uint64_t* glwe_out)
+{
+    return group_each(g, spf_ops::OP_GLWE_KEYSWITCH, B, glwe_in, slots, glwe_out);
+}
+spf_status spf_group_glwe_automorphism_each_batch(spf_group* g, size_t B, const uint64_t* glwe_in, const uint64_t* rounds, uint64_t* glwe_out)
+{
+    return group_each(g, spf_ops::OP_GLWE_AUTOMORPHISM, B, glwe_in, rounds, glwe_out);
+}
+
 // circuit bootstrap via PFKS: sharded by item
 spf_status spf_group_circuit_bootstrap_via_pfks_batch(spf_group* g, size_t B, const uint64_t* lwe, double* out)
 {

@@ -14,6 +14,7 @@
 #include "spf_lwe_linear.hpp"
 #include "spf_glwe_poly.hpp"
 #include "spf_glwe_keyswitch.hpp"
+#include "spf_each_plan.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -200,6 +201,13 @@ struct spf_ctx {
     bool glwe_ks_generic_ready = false;
     const char* last_glwe_ks_kernel = "";
     uint64_t gksk_epoch = 0; // bumped by every spf_load_glwe_keyswitch_key_std (captured gate graphs hold a slot's pointer and kernel)
+    // the per-item entry points (spf_*_each_*): the pointer, parameter, workgroup and unit tables of ONE call, built on the host in
+    // `each_host` (pinned), copied to `each_tab` on the call's stream; `each_ev` says when that copy has read the host image
+    DevBuf each_tab;
+    void* each_host = nullptr;
+    size_t each_host_cap = 0;
+    hipEvent_t each_ev = nullptr;
+    bool each_ev_recorded = false;
 };
 
 namespace {
@@ -749,6 +757,8 @@ static spf_status glwe_ks_prepare_generic(spf_ctx* c)
                                   (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_each_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
     c->glwe_ks_generic_ready = true;
     return SPF_OK;
 }
@@ -835,6 +845,8 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_each_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)generic_trace_lds_bytes(N, params->glwe_size)));
         c->glwe_ks_generic_ready = true;
         *out = c;
         return SPF_OK;
@@ -885,6 +897,10 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_rows_kernel<6, 7, GLWE_KS_KEYSWITCH>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_each_kernel<6, 7, GLWE_KS_AUTOMORPHISM>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_each_kernel<6, 7, GLWE_KS_KEYSWITCH>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
 #undef CK
     // an automorphism key of another radix than the hand-written kernel's: spf_glwe_automorphism_* / spf_glwe_trace_* run the
     // generic kernel (the *_enqueue forms only enqueue: its table is made here)
@@ -921,8 +937,10 @@ static void ctx_release(spf_ctx* c)
                     c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
                     c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables,
                     (void*)c->d_pufks, c->pufks_dig.p, (void*)c->d_pfks, (void*)c->d_pfks_planes, c->pfks_dig.p, c->pfks_rowsum.p, c->pfks_glwe.p,
-                    c->pfks_lwe.p, c->lin_planes.p})
+                    c->pfks_lwe.p, c->lin_planes.p, c->each_tab.p})
         if (p) (void)hipFree(p);
+    if (c->each_ev) { (void)hipEventSynchronize(c->each_ev); (void)hipEventDestroy(c->each_ev); }
+    if (c->each_host) (void)hipHostFree(c->each_host);
     for (LweLinearSlot& l : c->lin)
         for (void* p : {(void*)l.d_w, (void*)l.d_bias, (void*)l.d_A, (void*)l.d_rs})
             if (p) (void)hipFree(p);
@@ -3562,6 +3580,255 @@ spf_status spf_glwe_trace_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, u
     return glwe_ks_batch(c, GLWE_KS_TRACE, 0, B, glwe_in, glwe_out);
 }
 
+// ---------------------------------------------------------------- one launch over items with a parameter each (spf_*_each_*)
+// SampleExtract (the index), MulXN (the amount), the GLWE keyswitch (the key slot) and one automorphism round (the round) with the
+// parameter PER ITEM: `params` is a HOST array of B values, read during the call.  The kernels read item i through a pointer table
+// and its parameter from a table beside it (spf_kernels.hpp, spf_generic.hpp), or, for the keyswitch kernels, through the segment
+// plan of spf_each_plan.hpp (spf_glwe_keyswitch.hpp); the tables of a call are built in c->each_host and travel to c->each_tab on
+// the call's stream: a buffer of the context, so one stream per context, and no _enqueue form.
+static_assert(spf_each::kNoRow == kGlweKsNoRow, "the plan's padding mark is the kernels'");
+static_assert(sizeof(GlweKsEachUnit) == 16 && sizeof(GlweKsEachWg) == 16, "the tables lie back to back, every entry aligned");
+
+// What every per-item form checks before anything is queued, touching nothing: every parameter under the rule of op_param (the
+// text carries position and value), then the keys, the batch limit and the ranges.  B = 0 is SPF_OK.
+static spf_status each_args(spf_ctx* c, int op, size_t B, const void* in, const uint64_t* params, const void* out)
+{
+    if (!c || !spf_ops::has_each_form(op) || (B && (!in || !params || !out))) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    if (B == 0) return SPF_OK;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const BatchShape sh = spf_ops::each_shape(c->prm, op);
+    if (batch_limit(c, sh, B) != SPF_OK) return SPF_ERR_INVALID_ARGUMENT;
+    for (size_t i = 0; i < B; i++) {
+        uint64_t v = params[i];
+        const char* why = "";
+        if (spf_ops::op_param(c->prm, op, &v, &why) != SPF_OK)
+            return fail(c, SPF_ERR_INVALID_ARGUMENT, "parameter " + std::to_string(i) + " of " + std::to_string(B) + " is " + std::to_string(params[i]) + ": " + why);
+    }
+    if (op == spf_ops::OP_GLWE_KEYSWITCH) {
+        for (size_t i = 0; i < B; i++)
+            if (!c->gksk[params[i]].ready)
+                return fail(c, SPF_ERR_NO_KEY, "no GLWE keyswitch key loaded in slot " + std::to_string(params[i]) + " (parameter " + std::to_string(i) + " of " + std::to_string(B) + ")");
+    } else if (op == spf_ops::OP_GLWE_AUTOMORPHISM) {
+        if (!c->ak_ready) return fail(c, SPF_ERR_NO_KEY, "automorphism key not loaded");
+        if (!glwe_ks_tuned(c, c->prm.tr_radix_log, c->prm.tr_radix_count) && !c->glwe_ks_generic_ready)
+            return fail(c, SPF_ERR_UNSUPPORTED, "the context's tr_radix is served by no GLWE keyswitch kernel: " +
+                                                    glwe_ks_radix_error(c->prm.tr_radix_log, c->prm.tr_radix_count));
+    }
+    if (batch_overlaps(sh, B, out, in)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output must not overlap the input");
+    return SPF_OK;
+}
+
+// `image` -> c->each_tab on `s`, through the pinned c->each_host.  The previous call's copy has read the pinned image before it is
+// overwritten (its event; that copy stands at the head of the previous call's work); the device table is overwritten behind the
+// previous call's kernels: same stream.  Under c->mu.
+static spf_status each_upload(spf_ctx* c, hipStream_t s, const std::vector<char>& image)
+{
+    if (!c->each_ev) HIPCHK(c, hipEventCreateWithFlags(&c->each_ev, hipEventDisableTiming));
+    if (c->each_ev_recorded) HIPCHK(c, hipEventSynchronize(c->each_ev));
+    c->each_ev_recorded = false;
+    if (c->each_host_cap < image.size()) {
+        if (c->each_host) HIPCHK(c, hipHostFree(c->each_host));
+        c->each_host = nullptr; c->each_host_cap = 0;
+        const size_t cap = std::max<size_t>(2 * image.size(), 4096);
+        HIPCHK(c, hipHostMalloc(&c->each_host, cap, hipHostMallocDefault));
+        c->each_host_cap = cap;
+    }
+    if (spf_status st = ensure(c, c->each_tab, c->each_host_cap)) return st;
+    std::memcpy(c->each_host, image.data(), image.size());
+    HIPCHK(c, hipMemcpyAsync(c->each_tab.p, c->each_host, image.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->each_ev, s));
+    c->each_ev_recorded = true;
+    return SPF_OK;
+}
+
+// The tables of one per-item call and what its launches need to know about them.  SampleExtract and MulXN: [B] operand pointers,
+// then [B] parameters of 32 bits (a MulXN amount reduced mod 2N).  Keyswitch and automorphism: per launch — one per distinct
+// (radix_log, radix_count) among the slots named; the automorphism has one — the unit table, then the workgroup table of its
+// segment plan (spf_each_plan.hpp: four units per workgroup for the hand-written kernel, one for the generic one).
+struct EachLaunch {
+    uint32_t radix_log, count;
+    std::vector<uint32_t> items;
+    spf_each::Plan plan;
+    size_t unit_at = 0, wg_at = 0; // byte offsets of its tables in the image
+};
+struct EachTables {
+    std::vector<char> image;
+    std::vector<EachLaunch> launches;
+};
+
+// Item i is rows[i] (a HOST array of device pointers), or d_in + i * words where `rows` is null; the parameters have been checked
+// (each_args, or the pool's submit).  Under c->mu: the keys' pointers and shapes are read here.
+static spf_status each_build(spf_ctx* c, int op, size_t B, const uint64_t* d_in, const uint64_t* const* rows, const uint64_t* params, EachTables& t)
+{
+    const size_t words = spf_ops::each_shape(c->prm, op).in_words[0];
+    const uint32_t N = c->prm.polynomial_degree, k = c->prm.glwe_size;
+    const auto row_of = [&](size_t i) { return rows ? rows[i] : d_in + i * words; };
+    std::vector<char>& image = t.image;
+    std::vector<EachLaunch>& launches = t.launches;
+    using Launch = EachLaunch;
+    try {
+        if (op == spf_ops::OP_SAMPLE_EXTRACT || op == spf_ops::OP_MUL_XN) {
+            image.resize(B * 12); // [B] pointers, then [B] parameters of 32 bits
+            const uint64_t** rows_out = reinterpret_cast<const uint64_t**>(image.data());
+            uint32_t* par = reinterpret_cast<uint32_t*>(image.data() + B * 8);
+            for (size_t i = 0; i < B; i++) {
+                uint64_t v = params[i];
+                const char* why = "";
+                (void)spf_ops::op_param(c->prm, op, &v, &why); // (checked above; reduces a MulXN amount mod 2N)
+                rows_out[i] = row_of(i);
+                par[i] = (uint32_t)v;
+            }
+        } else {
+            const bool ks = op == spf_ops::OP_GLWE_KEYSWITCH;
+            for (size_t i = 0; i < B; i++) {
+                const uint32_t rl = ks ? c->gksk[params[i]].radix_log : c->prm.tr_radix_log, rc = ks ? c->gksk[params[i]].radix_count : c->prm.tr_radix_count;
+                auto l = std::find_if(launches.begin(), launches.end(), [&](const Launch& x) { return x.radix_log == rl && x.count == rc; });
+                if (l == launches.end()) l = launches.insert(l, Launch{rl, rc, {}, {}});
+                l->items.push_back((uint32_t)i);
+            }
+            for (Launch& l : launches) {
+                const size_t ksk_len = (size_t)k * l.count * (k + 1) * (N / 2); // complex values of one keyswitch key
+                l.plan = spf_each::plan(params, l.items, B, glwe_ks_tuned(c, l.radix_log, l.count) ? (uint32_t)kWavesPerBlock : 1u);
+                l.unit_at = image.size();
+                l.wg_at = l.unit_at + l.plan.units() * sizeof(GlweKsEachUnit);
+                image.resize(l.wg_at + l.plan.workgroups() * sizeof(GlweKsEachWg));
+                GlweKsEachUnit* unit = reinterpret_cast<GlweKsEachUnit*>(image.data() + l.unit_at);
+                GlweKsEachWg* wg = reinterpret_cast<GlweKsEachWg*>(image.data() + l.wg_at);
+                for (size_t u = 0; u < l.plan.units(); u++) unit[u] = {row_of(l.plan.unit_item[u]), l.plan.unit_out[u], 0};
+                for (size_t w = 0; w < l.plan.workgroups(); w++) {
+                    const uint64_t p = l.plan.wg_param[w];
+                    if (ks) wg[w] = {c->gksk[p].d_key, 1u, 0};
+                    else wg[w] = {c->d_ak + (size_t)(p - 1) * ksk_len, (N >> (p - 1)) + 1, 0};
+                }
+            }
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(c, SPF_ERR_HIP, "out of host memory for the tables of a per-item launch");
+    }
+    return SPF_OK;
+}
+
+// The launches of a call over its tables at `base` (device-visible: c->each_tab, or a pool's pinned table).  SampleExtract and
+// MulXN: one launch whatever B.  Keyswitch: one launch per distinct radix shape, the
+// hand-written kernel at 6 x 7 bits on a tuned context, the generic one elsewhere; automorphism: one launch.  Under c->mu.
+static spf_status each_run(spf_ctx* c, hipStream_t s, int op, size_t B, const char* base, const EachTables& t, uint64_t* d_out)
+{
+    spf_status st;
+    const uint32_t N = c->prm.polynomial_degree, k = c->prm.glwe_size;
+    const std::vector<EachLaunch>& launches = t.launches;
+    using Launch = EachLaunch;
+    if (op == spf_ops::OP_SAMPLE_EXTRACT || op == spf_ops::OP_MUL_XN) {
+        const uint64_t* const* d_rows = reinterpret_cast<const uint64_t* const*>(base);
+        const uint32_t* d_par = reinterpret_cast<const uint32_t*>(base + B * 8);
+        const unsigned gy = (unsigned)std::min(B, kMaxGridRows); // (the kernels stride over the items: one launch whatever B)
+        if (op == spf_ops::OP_SAMPLE_EXTRACT) {
+            if (c->generic) hipLaunchKernelGGL(generic_sample_extract_each_kernel, dim3((k * N + 1 + 255) / 256, gy), dim3(256), 0, s, d_rows, d_par, d_out, (uint32_t)B, N, k);
+            else hipLaunchKernelGGL(sample_extract_each_kernel, dim3((kN + 1 + 255) / 256, gy), dim3(256), 0, s, d_rows, d_par, d_out, (uint32_t)B);
+        } else {
+            if (c->generic) hipLaunchKernelGGL(generic_mul_xn_each_kernel, dim3(((k + 1) * N + 255) / 256, gy), dim3(256), 0, s, d_rows, d_par, d_out, (uint32_t)B, N, c->log_n, k);
+            else hipLaunchKernelGGL(glwe_mul_xn_each_kernel, dim3(2 * kN / 256, gy), dim3(256), 0, s, d_rows, d_par, d_out, (uint32_t)B);
+        }
+        HIPCHK(c, hipGetLastError());
+        return SPF_OK;
+    }
+    const int mode = op == spf_ops::OP_GLWE_KEYSWITCH ? GLWE_KS_KEYSWITCH : GLWE_KS_AUTOMORPHISM;
+    for (const Launch& l : launches) {
+        const GlweKsEachUnit* d_unit = reinterpret_cast<const GlweKsEachUnit*>(base + l.unit_at);
+        const GlweKsEachWg* d_wg = reinterpret_cast<const GlweKsEachWg*>(base + l.wg_at);
+        const dim3 grid((unsigned)l.plan.workgroups());
+        TimedScope ts(c, s, T_GLWE_KS);
+        st = ts.begin();
+        if (st != SPF_OK) return st;
+        if (glwe_ks_tuned(c, l.radix_log, l.count)) {
+            GlweKsEachArgs a{d_unit, d_wg, d_out, c->d_tables};
+            if (mode == GLWE_KS_AUTOMORPHISM) hipLaunchKernelGGL((glwe_ks_each_kernel<6, 7, GLWE_KS_AUTOMORPHISM>), grid, dim3(512), kTraceLds, s, a);
+            else hipLaunchKernelGGL((glwe_ks_each_kernel<6, 7, GLWE_KS_KEYSWITCH>), grid, dim3(512), kTraceLds, s, a);
+            c->last_glwe_ks_kernel = "glwe_ks_each_kernel";
+        } else {
+            GenericGlweKsArgs a{generic_shape(c), nullptr, d_out, nullptr, l.radix_log, l.count, (uint32_t)mode, 0};
+            hipLaunchKernelGGL(generic_glwe_ks_each_kernel, grid, dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a, d_unit, d_wg);
+            c->last_glwe_ks_kernel = "generic_glwe_ks_each_kernel";
+        }
+        HIPCHK(c, hipGetLastError());
+        st = ts.end();
+        if (st != SPF_OK) return st;
+    }
+    return SPF_OK;
+}
+
+// The checks, the tables, the launches: B consecutive items at d_in, row i of d_out the result of item i under params[i]
+static spf_status each_enqueue(spf_ctx* c, void* stream, int op, size_t B, const uint64_t* d_in, const uint64_t* params, uint64_t* d_out)
+{
+    spf_status st = each_args(c, op, B, d_in, params, d_out);
+    if (st != SPF_OK || B == 0) return st;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    EachTables t;
+    st = each_build(c, op, B, d_in, nullptr, params, t);
+    if (st != SPF_OK) return st;
+    st = each_upload(c, (hipStream_t)stream, t.image);
+    if (st != SPF_OK) return st;
+    return each_run(c, (hipStream_t)stream, op, B, static_cast<const char*>(c->each_tab.p), t, d_out);
+}
+
+// The same for a batch of a pool with mixed parameters (spf_pool_set_mixed_parameters): item i is rows[i], wherever it lies (by
+// handle), or row i of the staged block d_in (by host pointer); the tables go to `table`, pinned memory of the batch's set that the
+// kernels read in place (no buffer of the context: the pool's batches run on their sets' streams side by side).  The parameters
+// and the keys were checked at the submits.
+static spf_status each_launch_pool(spf_ctx* c, hipStream_t s, int op, size_t B, const uint64_t* d_in, const uint64_t* const* rows,
+                                   const uint64_t* params, void* table, size_t table_bytes, uint64_t* d_out)
+{
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    EachTables t;
+    spf_status st = each_build(c, op, B, d_in, rows, params, t);
+    if (st != SPF_OK) return st;
+    if (t.image.size() > table_bytes) return fail(c, SPF_ERR_HIP, "the tables of a mixed-parameter batch outgrow the set's pinned table");
+    std::memcpy(table, t.image.data(), t.image.size());
+    return each_run(c, s, op, B, static_cast<const char*>(table), t, d_out);
+}
+
+static spf_status each_batch(spf_ctx* c, int op, size_t B, const uint64_t* in, const uint64_t* params, uint64_t* out)
+{
+    spf_status st = each_args(c, op, B, in, params, out);
+    if (st != SPF_OK) return st;
+    return host_batch(c, spf_ops::each_shape(c->prm, op), B, {{c->in, in}}, out,
+                      [&](const uint64_t* d_in, uint64_t* d_out) { return each_enqueue(c, c->stream, op, B, d_in, params, d_out); });
+}
+
+spf_status spf_sample_extract_l1_each_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, const uint64_t* idx, uint64_t* lwe1_out)
+{
+    return each_batch(c, spf_ops::OP_SAMPLE_EXTRACT, B, glwe_in, idx, lwe1_out);
+}
+spf_status spf_sample_extract_l1_each_devptr(spf_ctx* c, void* stream, size_t B, const uint64_t* d_glwe_in, const uint64_t* idx, uint64_t* d_lwe1_out)
+{
+    return each_enqueue(c, stream, spf_ops::OP_SAMPLE_EXTRACT, B, d_glwe_in, idx, d_lwe1_out);
+}
+spf_status spf_glwe_mul_xn_each_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, const uint64_t* amounts, uint64_t* glwe_out)
+{
+    return each_batch(c, spf_ops::OP_MUL_XN, B, glwe_in, amounts, glwe_out);
+}
+spf_status spf_glwe_mul_xn_each_devptr(spf_ctx* c, void* stream, size_t B, const uint64_t* d_glwe_in, const uint64_t* amounts, uint64_t* d_glwe_out)
+{
+    return each_enqueue(c, stream, spf_ops::OP_MUL_XN, B, d_glwe_in, amounts, d_glwe_out);
+}
+spf_status spf_glwe_keyswitch_each_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, const uint64_t* slots, uint64_t* glwe_out)
+{
+    return each_batch(c, spf_ops::OP_GLWE_KEYSWITCH, B, glwe_in, slots, glwe_out);
+}
+spf_status spf_glwe_keyswitch_each_devptr(spf_ctx* c, void* stream, size_t B, const uint64_t* d_glwe_in, const uint64_t* slots, uint64_t* d_glwe_out)
+{
+    return each_enqueue(c, stream, spf_ops::OP_GLWE_KEYSWITCH, B, d_glwe_in, slots, d_glwe_out);
+}
+spf_status spf_glwe_automorphism_each_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, const uint64_t* rounds, uint64_t* glwe_out)
+{
+    return each_batch(c, spf_ops::OP_GLWE_AUTOMORPHISM, B, glwe_in, rounds, glwe_out);
+}
+spf_status spf_glwe_automorphism_each_devptr(spf_ctx* c, void* stream, size_t B, const uint64_t* d_glwe_in, const uint64_t* rounds, uint64_t* d_glwe_out)
+{
+    return each_enqueue(c, stream, spf_ops::OP_GLWE_AUTOMORPHISM, B, d_glwe_in, rounds, d_glwe_out);
+}
+
 const char* spf_last_glwe_keyswitch_kernel(spf_ctx* c)
 {
     if (!c) return "";
@@ -3762,6 +4029,23 @@ spf_status spf_pool_set_max_inflight(spf_pool* p, size_t max_inflight)
     return SPF_OK;
 }
 
+spf_status spf_pool_set_mixed_parameters(spf_pool* p, int on)
+{
+    if (!p) return SPF_ERR_INVALID_ARGUMENT;
+    if (!p->members.empty()) { // a group pool: every member, or none — refused as soon as one member has seen a submit
+        for (spf_pool* q : p->members) {
+            std::lock_guard<spf_pool::Mutex> lk(q->mu);
+            if (q->submitted) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "spf_pool_set_mixed_parameters: only before the pool's first submit");
+        }
+        for (spf_pool* q : p->members) (void)spf_pool_set_mixed_parameters(q, on);
+        return SPF_OK;
+    }
+    std::lock_guard<spf_pool::Mutex> lk(p->mu);
+    if (p->submitted) return fail(p->ctx, SPF_ERR_INVALID_ARGUMENT, "spf_pool_set_mixed_parameters: only before the pool's first submit");
+    p->mixed_parameters = on != 0;
+    return SPF_OK;
+}
+
 static void group_release(struct spf_group* g); // spf_group.hpp
 
 void spf_pool_destroy(spf_pool* p)
@@ -3815,11 +4099,17 @@ static spf_pool* pool_deal(spf_pool* top, int* member);
 // (under the context's lock, let go again before the operation is queued): an empty slot or no automorphism key is
 // SPF_ERR_NO_KEY with the batch entry points' text, and nothing is queued.  The launch reads the slot again — at run time, as a
 // gate graph does; a caller that reloads a slot waits for its submissions on it first (spf_hip.h).  Any other operation: SPF_OK.
-static spf_status pool_glwe_ks_keys(spf_ctx* c, int op, uint64_t param)
+// `ks_shape`: the radix shape of a keyswitch's slot as it is now, (radix_log << 32) | radix_count — what a pool with mixed parameters
+// keys its keyswitch batches by.
+static spf_status pool_glwe_ks_keys(spf_ctx* c, int op, uint64_t param, uint64_t* ks_shape)
 {
+    *ks_shape = 0;
     if (!spf_ops::rows_in_place(op)) return SPF_OK;
     const int mode = op == spf_ops::OP_GLWE_KEYSWITCH ? GLWE_KS_KEYSWITCH : op == spf_ops::OP_GLWE_AUTOMORPHISM ? GLWE_KS_AUTOMORPHISM : GLWE_KS_TRACE;
-    return glwe_ks_args(c, mode, (uint32_t)param, 0, nullptr, nullptr);
+    std::lock_guard<std::recursive_mutex> g(c->mu); // (the lock glwe_ks_args takes: the shape is read under the hold that checked the key)
+    const spf_status st = glwe_ks_args(c, mode, (uint32_t)param, 0, nullptr, nullptr);
+    if (st == SPF_OK && mode == GLWE_KS_KEYSWITCH) *ks_shape = (uint64_t)c->gksk[param].radix_log << 32 | c->gksk[param].radix_count;
+    return st;
 }
 
 // a host-pointer submit: the null and parameter checks of every wrapper below, then the operation goes to the pool the calling
@@ -3838,8 +4128,9 @@ static spf_status pool_submit(spf_pool* p, int op, std::initializer_list<const v
     int member = 0;
     spf_pool* q = pool_deal(p, &member);
     if (!q) return SPF_ERR_HIP; // no member of the group is in rotation
-    if (spf_status ks = pool_glwe_ks_keys(q->ctx, op, param)) return ks;
-    const spf_status st = q->submit_impl(op, false, src, out, nullptr, nullptr, ticket, param);
+    uint64_t ks_shape;
+    if (spf_status ks = pool_glwe_ks_keys(q->ctx, op, param, &ks_shape)) return ks;
+    const spf_status st = q->submit_impl(op, false, src, out, nullptr, nullptr, ticket, param, ks_shape);
     if (st == SPF_OK && q != p) *ticket |= (uint64_t)member << spf_pool::kMemberShift;
     return st;
 }
@@ -3987,10 +4278,11 @@ spf_status pool_submit_v(spf_pool* top, int op, const spf_value* const* vals, si
     spf_pool* leaf = value_home(top, v[0]);
     const int member = v[0]->member;
     if (!leaf) return fail(top->ctx, SPF_ERR_INVALID_ARGUMENT, "pool operation by handle: operand belongs to another pool");
-    if (spf_status ks = pool_glwe_ks_keys(leaf->ctx, op, param)) return ks; // (no value made, no ticket taken)
+    uint64_t ks_shape;
+    if (spf_status ks = pool_glwe_ks_keys(leaf->ctx, op, param, &ks_shape)) return ks; // (no value made, no ticket taken)
     spf_value* res = spf_value::make(leaf->arena, leaf, member, info.out_kind, value_bytes(leaf->prm, info.out_kind));
     if (!res) return fail(leaf->ctx, SPF_ERR_HIP, "out of host memory");
-    const spf_status st = leaf->submit_impl(op, true, nullptr, nullptr, v, res, ticket, param);
+    const spf_status st = leaf->submit_impl(op, true, nullptr, nullptr, v, res, ticket, param, ks_shape);
     if (st != SPF_OK) {
         res->release();
         return st == SPF_ERR_INVALID_ARGUMENT ? fail(top->ctx, st, "pool operation by handle: refused (pool closing, or an operand's producing operation failed)") : st;

@@ -1858,6 +1858,42 @@ __global__ void gather_rows_kernel(const uint64_t* const* src, uint64_t* dst, ui
     dst[(size_t)r * words + j] = src[r][j];
 }
 
+// sample_extract_kernel and glwe_linear_kernel<GLWE_MUL_XN> with the parameter PER ITEM, operands where they lie
+// (spf_sample_extract_l1_each_*, spf_glwe_mul_xn_each_*): item ct is read through rows[ct], its index / amount (already reduced
+// mod 2N) is param[ct], row ct of the output block is written.  ONE launch and one read of each operand, no gather pass in front.
+// The items go over grid.y in a stride (ONE launch whatever B: grid.y stays within its limit), so both table reads are
+// workgroup-uniform: scalar loads (the tables are not written while the kernel
+// runs and the output overlaps no operand and neither table: __restrict__).  The same operand may stand in the table several times.
+__global__ void sample_extract_each_kernel(const uint64_t* const* __restrict__ rows, const uint32_t* __restrict__ param,
+                                           uint64_t* __restrict__ lwe, uint32_t B)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j > kN) return;
+    for (uint32_t ct = blockIdx.y; ct < B; ct += gridDim.y) {
+        const uint64_t* g = rows[ct];
+        const uint32_t h = param[ct];
+        uint64_t* o = lwe + (size_t)ct * (kN + 1);
+        if (j == kN) o[kN] = g[kN + h];
+        else if (j <= h) o[j] = g[h - j];
+        else o[j] = (uint64_t)0 - g[h + kN - j];
+    }
+}
+
+__global__ void glwe_mul_xn_each_kernel(const uint64_t* const* __restrict__ rows, const uint32_t* __restrict__ param,
+                                        uint64_t* __restrict__ out, uint32_t B)
+{
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; // 0 .. 2N-1: polynomial j / N, coefficient j % N
+    if (j >= 2 * kN) return;
+    const uint32_t poly = j & ~(uint32_t)(kN - 1), i = j & (kN - 1);
+    for (uint32_t ct = blockIdx.y; ct < B; ct += gridDim.y) {
+        const uint64_t* x = rows[ct];
+        const uint32_t n = param[ct];
+        const uint32_t idx = (i + 2 * kN - n) & (2 * kN - 1); // exponent of the source term, mod 2N
+        const uint64_t v = x[poly + (idx & (kN - 1))];
+        out[(size_t)ct * 2 * kN + j] = (idx & kN) ? (uint64_t)0 - v : v;
+    }
+}
+
 // lwe_rotate (ops/homomorphisms/lwe.rs:9-20) is folded into the blind-rotation kernels' body_rotate.
 
 } // namespace spf

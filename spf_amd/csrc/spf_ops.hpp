@@ -202,6 +202,18 @@ inline BatchShape shape(const spf_params& p, int op)
     return kinds_shape(p, r.out_kind == SPF_VAL_GGSW1 ? kBatchMaxRows : kBatchMax, r.out_kind, r.in_kind[0], r.in_kind[1], r.in_kind[2]);
 }
 
+// the per-item forms of a parameterised single-operand operation (spf_*_each_*: OP_SAMPLE_EXTRACT, OP_MUL_XN, OP_GLWE_KEYSWITCH,
+// OP_GLWE_AUTOMORPHISM): the operation's own shape with the parameters as a second operand of ONE word per item.  That operand is
+// a HOST array in every form (it is read during the call and never staged: host_batch gets the first operand alone); it stands in
+// the shape so that the group form deals it in the same contiguous shards as the items.
+inline BatchShape each_shape(const spf_params& p, int op)
+{
+    BatchShape sh = shape(p, op);
+    sh.in_words[sh.n_in++] = 1;
+    return sh;
+}
+constexpr bool has_each_form(int op) { return op == OP_SAMPLE_EXTRACT || op == OP_MUL_XN || op == OP_GLWE_KEYSWITCH || op == OP_GLWE_AUTOMORPHISM; }
+
 // The parameter of an operation, as every entry point takes it: a SampleExtract index must be below N (`why` says so), a MulXN
 // amount is reduced mod 2N, a rotate-CMUX rotation lies in 1 .. N - 1,
 // a bivariate bootstrap's plaintext_bits are below 64, a GLWE keyswitch's slot is below SPF_GLWE_KSK_SLOTS, an automorphism's round

@@ -93,6 +93,7 @@ struct Slot {
                     // batches change it under the pool's mutex (reclaim() reads it there); by handle it is a lock-free CAS
     spf_value* vin[3]; // by handle: the operands (retained until the batch has run) ...
     spf_value* vout;   // ... and the result (the batch's own reference; the caller holds another)
+    uint64_t param = 0; // the operation's parameter: what a batch of mixed parameters (Batch::mixed) runs this item under
 };
 
 struct Staging {
@@ -156,6 +157,12 @@ struct Batch {
     size_t n_returning = 0;       // members submitted by a thread that was in the previous batch of this kind
     int per_wg = 0;               // workgroup shape of its bootstrap (the population's, decided when it is enqueued)
     uint64_t param = 0;           // SampleExtract index / MulXN amount: one value per batch (a different one opens a new batch)
+    // What an arrival must share with the batch to join it: the parameter — or, in a pool with mixed parameters
+    // (spf_pool_set_mixed_parameters) for the operations with a per-item kernel, 0 and for the GLWE keyswitch the slot's radix
+    // shape as read at the submit (keys of different radix never share a launch); `mixed`: the batch runs the per-item kernels
+    // over its slots' parameters and `param` means nothing
+    uint64_t key = 0;
+    bool mixed = false;
     bool closed = false, done = false;
     bool kernels_done = false;    // its kernels have left the GPU (the device-to-host copy may still run): the next batch may go
     // Deferred batches (by handle, operands that are still PENDING results of this pool): not in `filling` but in the pool's
@@ -231,6 +238,10 @@ struct spf_pool {
     spf_params prm{};
     size_t max_batch = 4096;
     std::chrono::microseconds max_wait{200};
+    // spf_pool_set_mixed_parameters: SampleExtract, MulXN, GLWE keyswitch and automorphism calls with different parameters share a
+    // batch, which runs the per-item kernels (each_launch_pool).  Fixed before the first submit (`submitted`, under `mu`).
+    bool mixed_parameters = false, submitted = false;
+    bool each_tables(int op) const { return mixed_parameters && spf_ops::has_each_form(op); }
     using Mutex = spf_pool_impl::PoolMutex;
     Mutex mu;
     std::condition_variable_any cv_work, cv_space, cv_set, cv_idle, cv_deliver;
@@ -362,6 +373,10 @@ struct spf_pool {
     // pointers of a handle batch's table: one row of `cap` per operand (a rows_in_place operation uses the first), or four per CMUX unit
     size_t table_pointers(int op, size_t cap) const
     {
+        // (a mixed batch: [cap] pointers and [cap] 32-bit parameters, or the unit and workgroup tables of the segment plan — 16
+        // bytes per unit and per workgroup; one unit per workgroup: 32 cap bytes; four: at most cap / 4 + 16 workgroups, one ragged
+        // workgroup for each of at most 16 slots or rounds)
+        if (each_tables(op)) return 4 * cap + 160;
         return spf_pool_impl::cmux_family(op) ? 4 * cap * (op == spf_pool_impl::OP_GLEV_CMUX ? prm.cbs_radix_count : 1) + 3 * cap : 3 * cap;
     }
     bool prepare_set(spf_pool_impl::Staging& s, int op, size_t cap, bool by_handle, bool table_set = false)
@@ -371,17 +386,18 @@ struct spf_pool {
         if (hipSetDevice(ctx->device) != hipSuccess) return false;
         for (int k = 0; k < 3; k++) {
             if (!in[k]) continue;
-            if (by_handle && (scattered_cmux(op) || rows_route(op))) continue; // read in place through the pointer table
+            if (by_handle && (scattered_cmux(op) || rows_route(op) || each_tables(op))) continue; // read in place through the pointer table
             if (!grow_dev(s.d_in[k], s.dcap_in[k], cap * in[k])) return false;
             if (!by_handle && !grow_host(s.h_in[k], s.cap_in[k], cap * in[k])) return false;
         }
-        if (by_handle) {
+        if (by_handle || each_tables(op)) { // (by host pointer a mixed batch keeps its tables there too)
             size_t bytes = s.cap_ptrs * sizeof(void*);
             void* p = s.h_ptrs;
             if (!grow_host(p, bytes, table_pointers(op, cap) * sizeof(void*))) { s.h_ptrs = nullptr; s.cap_ptrs = 0; return false; }
             s.h_ptrs = static_cast<void**>(p);
             s.cap_ptrs = bytes / sizeof(void*);
-        } else {
+        }
+        if (!by_handle) {
             if (!grow_dev(s.d_out, s.dcap_out, cap * out)) return false;
             if (!grow_host(s.h_out, s.cap_out, cap * out)) return false;
         }
@@ -454,7 +470,7 @@ struct spf_pool {
     // handle: `vin` are values of this pool, valid or still pending (checked by the caller, pool_submit_v); `vout` is a new value
     // that becomes valid when its batch has run (spf_pool_wait for the ticket, or spf_value_wait); `ticket` may be null
     spf_status submit_impl(int op, bool by_handle, const void* const* src, void* out, spf_value* const* vin, spf_value* vout,
-                           uint64_t* ticket, uint64_t param)
+                           uint64_t* ticket, uint64_t param, uint64_t ks_shape = 0)
     {
         using namespace spf_pool_impl;
         blocked++;
@@ -468,6 +484,11 @@ struct spf_pool {
             space_waiters--;
         }
         if (stop) return SPF_ERR_INVALID_ARGUMENT;
+        submitted = true;
+        // what the batch is keyed by (Batch::key): the parameter; with mixed parameters nothing, or the keyswitch key's radix
+        // shape (`ks_shape`, read by the caller where it checked the key)
+        const bool mix = each_tables(op);
+        const uint64_t key_param = mix ? (op == OP_GLWE_KEYSWITCH ? ks_shape : 0) : param;
         // The caller's group: dealt round-robin on the thread's first submit, kept from then on.  The threads of a group meet in
         // the same batches, call after call — so a group's batch is complete the moment the members of its previous batch are
         // back (everybody_is_back), whatever the other groups are doing, and a straggler only ever delays itself.
@@ -524,7 +545,7 @@ struct spf_pool {
                 // of rank r needs has rank <= r, whatever needs it has rank > r.  (The early members wait for the late ones — the gate
                 // graph's planner, which knows every consumer, moves them by their slack; here nothing is known about consumers.)
                 const int64_t key_depth = heavy(op) ? -1 : depth;
-                const auto key = std::make_tuple(key_depth, op, param, rank);
+                const auto key = std::make_tuple(key_depth, op, key_param, rank);
                 try {
                     auto it = deferred.find(key);
                     if (it != deferred.end()) b = it->second;
@@ -534,6 +555,7 @@ struct spf_pool {
                         b->slots.resize(cap);
                         b->tree.init(cap);
                         b->op = op; b->set = -1; b->cap = cap; b->lane = lane; b->param = param; b->by_handle = true;
+                        b->key = key_param; b->mixed = mix;
                         b->deferred = true; b->depth = depth; b->rank = rank;
                         const bool first = deferred.empty() && deferred_full.empty();
                         deferred.emplace(key, b);
@@ -549,7 +571,7 @@ struct spf_pool {
         }
         while (!b) {
             b = filling[lane];
-            if (b && b->param != param) { // (SampleExtract index / MulXN amount: the kernels take one value per launch)
+            if (b && b->key != key_param) { // (SampleExtract index / MulXN amount: the kernels take one value per launch — unless the pool mixes parameters)
                 close_batch(lane);
                 b.reset();
                 continue;
@@ -592,12 +614,13 @@ struct spf_pool {
                 return SPF_ERR_HIP;
             }
             b->op = op; b->set = set; b->cap = cap; b->lane = lane; b->param = param; b->by_handle = by_handle;
+            b->key = key_param; b->mixed = mix;
             filling[lane] = b;
             break;
         }
         const size_t slot = b->n;
         const uint64_t my_ticket = ticket ? next_ticket : 0; // (0: nobody will wait for this operation — spf_value_wait on its result instead)
-        b->slots[slot] = Slot{out, my_ticket, 0, who, (uint8_t)(ticket ? 0 : 2), {nullptr, nullptr, nullptr}, nullptr};
+        b->slots[slot] = Slot{out, my_ticket, 0, who, (uint8_t)(ticket ? 0 : 2), {nullptr, nullptr, nullptr}, nullptr, param};
         // a caller "comes back" when it submits with nothing else outstanding (the synchronous pattern); a thread that
         // submits many tickets before it waits for any is not waited for — its batches close on the timer or when full.
         // (Only where batches are closed by who is back: not for the cheap kinds by handle.)
@@ -639,7 +662,7 @@ struct spf_pool {
                 cap_hint[kind] = std::min(batch_cap(op), 2 * b->cap);
                 try {
                     deferred_full.push_back(b);
-                    deferred.erase(std::make_tuple(heavy(op) ? (int64_t)-1 : b->depth, op, param, b->rank));
+                    deferred.erase(std::make_tuple(heavy(op) ? (int64_t)-1 : b->depth, op, b->key, b->rank));
                 } catch (const std::exception&) {
                     flush_deferred();
                 }
@@ -1012,6 +1035,20 @@ struct spf_pool {
             std::stable_sort(units, units + n_units, [](const Unit& x, const Unit& y) { return x.p[0] < y.p[0]; });
             st = b.op == OP_ROT_CMUX ? launch_cmux_rot_scattered(ctx, sk, n_units, (uint32_t)b.param, (const void* const*)s.h_ptrs)
                                      : spf_cmux_scattered_dev(ctx, sk, n_units, (const void* const*)s.h_ptrs);
+        } else if (b.mixed) {
+            // parameters that differ: ONE per-item launch over the operands where they lie (a keyswitch: one per radix shape —
+            // the batch's key holds it to one), the tables in the set's pinned table
+            try {
+                std::vector<const uint64_t*> rows(B);
+                std::vector<uint64_t> params(B);
+                for (size_t i = 0; i < B; i++) {
+                    rows[i] = static_cast<const uint64_t*>(b.slots[i].vin[0]->ptr());
+                    params[i] = b.slots[i].param;
+                }
+                st = each_launch_pool(ctx, sk, b.op, B, nullptr, rows.data(), params.data(), s.h_ptrs, s.cap_ptrs * sizeof(void*), (uint64_t*)d_out);
+            } catch (const std::exception&) {
+                st = SPF_ERR_HIP;
+            }
         } else {
             void* d[3] = {nullptr, nullptr, nullptr};
             bool in_rows = false; // the batch has run over the pointer table (a rows_in_place operation)
@@ -1071,7 +1108,18 @@ struct spf_pool {
         for (int k = 0; k < 3; k++) // (a kernel that reads the pinned buffer, not an SDMA copy: spf_kernels.hpp, copy_words_kernel)
             if (in[k] && pool_copy_in(ctx, sk, s.h_in[k], s.d_in[k], B * in[k]) != SPF_OK) return SPF_ERR_HIP;
         if (hipEventRecord(b.ev_in, sk) != hipSuccess) return SPF_ERR_HIP;
-        const spf_status st = run_kernels(b, s, B, s.d_in, s.d_out);
+        spf_status st;
+        if (b.mixed) { // the per-item kernels over the staged consecutive rows
+            try {
+                std::vector<uint64_t> params(B);
+                for (size_t i = 0; i < B; i++) params[i] = b.slots[i].param;
+                st = each_launch_pool(ctx, sk, b.op, B, (const uint64_t*)s.d_in[0], nullptr, params.data(), s.h_ptrs, s.cap_ptrs * sizeof(void*), (uint64_t*)s.d_out);
+            } catch (const std::exception&) {
+                st = SPF_ERR_HIP;
+            }
+        } else {
+            st = run_kernels(b, s, B, s.d_in, s.d_out);
+        }
         if (st != SPF_OK) return st;
         if (hipEventRecord(b.ev_k, sk) != hipSuccess) return SPF_ERR_HIP;
         hipStream_t so = sk;

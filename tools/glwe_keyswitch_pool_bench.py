@@ -10,11 +10,14 @@ DEFAULT_128 with keys of uniform words from a fixed seed (timing only; the words
      of the trace and of a keyswitch, by handle and by host pointer, against spf_glwe_*_enqueue + synchronise on as many
      device-resident rows; operations per second, and the operations per launch the pool reached.
   3  the same callers of a keyswitch by handle over FOUR slots (caller t: slot t mod 4): a launch holds one slot, so a pool cycle is
-     four launches — their count per cycle and the time per launch.
+     four launches — their count per cycle and the time per launch.  Beside it the MIXED leg: a second pool with
+     spf_pool_set_mixed_parameters, the same callers over one slot and over four — the four slots of a cycle are then one launch of
+     glwe_ks_each_kernel.  At 64 callers also a 32-index SampleExtract cycle (caller t: index t mod 32) on both pools.
   4  trace batches by handle: ms per batch of the size a pool cycle holds (the `heavy` decision of spf_ops.hpp).
 
 Forms alternate in one process: one warm-up of each, then `repeats` timed runs of each in turn; median (min - max).
-usage: python tools/glwe_keyswitch_pool_bench.py [repeats] [seconds per run of part 2 and 3]      (default 7, 0.3)
+usage: python tools/glwe_keyswitch_pool_bench.py [repeats] [seconds per run of part 2 and 3] [slots]      (default 7, 0.3; "slots":
+part 3 alone)
 Prints one JSON line."""
 import ctypes as C
 import json
@@ -35,6 +38,7 @@ from spf_amd import FheOp, ValueKind  # noqa: E402
 
 repeats = max(5, int(sys.argv[1])) if len(sys.argv) > 1 else 7
 seconds = float(sys.argv[2]) if len(sys.argv) > 2 else 0.3
+only_slots = len(sys.argv) > 3 and sys.argv[3] == "slots"
 P = spf_amd.DEFAULT_128
 N, K1 = P.polynomial_degree, P.glwe_size + 1
 W = K1 * N
@@ -134,6 +138,7 @@ def part2_3_4(eng, rng, d):
     glwe = rng.integers(0, 1 << 64, size=W, dtype=np.uint64)
     one = (C.c_uint32 * 1)(0)
     four = (C.c_uint32 * 4)(0, 1, 2, 3)
+    thirty_two = (C.c_uint32 * 32)(*range(32))
     callers_out, slots_out, batch_out = [], [], []
     for T in (64, 256):
         pool = spf_amd.Pool(eng, max_batch=4096, max_wait_us=200)
@@ -143,7 +148,7 @@ def part2_3_4(eng, rng, d):
         y = torch.zeros(T * W, dtype=torch.int64, device=dev)
         el = C.c_double()
 
-        def by_handle(op, params, n):
+        def by_handle(op, params, n, pool=pool, arr=arr):
             before = pool.counters()
             done = d.glwe_ks_drive_v(pool._h, int(op), params, n, T, seconds, arr, C.byref(el))
             assert done > 0, done
@@ -172,7 +177,7 @@ def part2_3_4(eng, rng, d):
                 n += 1
             return {"ops_per_s": n * T / (time.perf_counter() - t0)}
 
-        for name in ("trace", "keyswitch"):
+        for name in () if only_slots else ("trace", "keyswitch"):
             op, _ = OPS[name]
             forms = {"by_handle": lambda: by_handle(op, one, 1), "by_host_pointer": lambda: by_pointer(op, one, 1), "device_resident_enqueue": lambda: resident(op)}
             got = {f: [] for f in forms}
@@ -191,7 +196,16 @@ def part2_3_4(eng, rng, d):
             row["by_host_pointer_over_resident"] = round(row["by_host_pointer"]["ops_per_s"]["median"] / res, 3)
             callers_out.append(row)
         # part 3: four slots against one
-        forms = {"one_slot": lambda: by_handle(FheOp.GLWE_KEYSWITCH, one, 1), "four_slots": lambda: by_handle(FheOp.GLWE_KEYSWITCH, four, 4)}
+        mixed = spf_amd.Pool(eng, max_batch=4096, max_wait_us=200)
+        mixed.set_mixed_parameters(True)
+        mvals = mixed.upload_batch(ValueKind.GLWE1, rng.integers(0, 1 << 64, size=(T, W), dtype=np.uint64))
+        marr = (C.c_void_p * T)(*[v._h for v in mvals])
+        forms = {"one_slot": lambda: by_handle(FheOp.GLWE_KEYSWITCH, one, 1), "four_slots": lambda: by_handle(FheOp.GLWE_KEYSWITCH, four, 4),
+                 "one_slot_mixed": lambda: by_handle(FheOp.GLWE_KEYSWITCH, one, 1, mixed, marr),
+                 "four_slots_mixed": lambda: by_handle(FheOp.GLWE_KEYSWITCH, four, 4, mixed, marr)}
+        if T == 64:   # the 32 SampleExtract(i) of a 32-bit unpack (caller t: index t mod 32), without mixing and with it
+            forms["sample_extract_32"] = lambda: by_handle(FheOp.SampleExtract, thirty_two, 32)
+            forms["sample_extract_32_mixed"] = lambda: by_handle(FheOp.SampleExtract, thirty_two, 32, mixed, marr)
         got = {f: [] for f in forms}
         for f, run in forms.items():
             run()
@@ -206,10 +220,15 @@ def part2_3_4(eng, rng, d):
                       "ms_per_launch": summary([1e3 * g["elapsed_s"] / g["launches"] for g in got[f]], 4),
                       "ms_per_cycle": summary([1e3 * g["elapsed_s"] / (g["ops"] / T) for g in got[f]], 4)}
         row["four_over_one_ops_per_s"] = round(row["four_slots"]["ops_per_s"]["median"] / row["one_slot"]["ops_per_s"]["median"], 3)
+        row["four_mixed_over_one_ops_per_s"] = round(row["four_slots_mixed"]["ops_per_s"]["median"] / row["one_slot"]["ops_per_s"]["median"], 3)
+        row["one_mixed_over_one_ops_per_s"] = round(row["one_slot_mixed"]["ops_per_s"]["median"] / row["one_slot"]["ops_per_s"]["median"], 3)
         slots_out.append(row)
-        for v in vals:
+        for v in vals + mvals:
             v.release()
         pool.close()
+        mixed.close()
+        if only_slots:
+            continue
         # part 4: a trace batch of T by handle, consecutive operands (close -> done), and the kernel alone by device events
         pool = spf_amd.Pool(eng, max_batch=4096, max_wait_us=1_000_000)
         vals = pool.upload_batch(ValueKind.GLWE1, rng.integers(0, 1 << 64, size=(T, W), dtype=np.uint64))
@@ -237,7 +256,7 @@ def main():
     rng = np.random.default_rng(34)
     load_keys(eng, rng)
     d = driver()
-    scattered = part1(eng, rng)
+    scattered = [] if only_slots else part1(eng, rng)
     callers, slots, batches = part2_3_4(eng, rng, d)
     print(json.dumps({"tool": "glwe_keyswitch_pool_bench", "repeats": repeats, "seconds_per_run": seconds, "library": spf_amd.lib_path(),
                       "scattered_rows_against_gather": scattered, "blocking_callers": callers, "four_slots": slots, "trace_batches": batches}))
