@@ -234,6 +234,13 @@ class Evaluation {
     {
         check(spf_group_glwe_trace_batch(grp_, B, input_glwes, output_glwes));
     }
+    // Ring packing (spf_lwe_ring_pack_batch; PackLWEs): B x p leaves (SPF_VAL_LWE1 or SPF_VAL_GLWE1 rows, output b's p leaves
+    // consecutive, p a power of two <= N) into B GLWEs under the automorphism key.  The layout is strided: leaf j's message is at
+    // coefficient j * N / p, every other coefficient holds 0.
+    void lwe_ring_pack(uint64_t* output_glwes, const uint64_t* leaves, size_t p, size_t B = 1, spf_value_kind leaf_kind = SPF_VAL_LWE1)
+    {
+        check(spf_group_lwe_ring_pack_batch(grp_, leaf_kind, p, B, leaves, output_glwes));
+    }
     // The parameter PER ITEM (spf_*_each_batch): item i under params[i], row i of the output its result, ONE launch where the
     // single-parameter methods above take one call per distinct parameter.  The output must not overlap the input.
     void sample_extract_l1_each(uint64_t* output, const uint64_t* input, const uint64_t* idx, size_t B)

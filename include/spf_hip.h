@@ -1003,6 +1003,45 @@ spf_status spf_cmux_scattered_dev(spf_ctx *ctx, void *stream, size_t units, cons
 spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t words,
                                const uint64_t *const *d_src_ptrs, uint64_t *d_dst);
 
+/* ---- ring packing: LWE or GLWE ciphertexts into one GLWE through the automorphism key ----
+ * PackLWEs (Chen, Dai, Kim, Song): p = 2^m leaves per output, 1 <= p <= N, through p - 1 automorphism rounds in a tree of depth m
+ * and the first log2 N - m rounds of the trace, under the automorphism key the circuit bootstrap already uses — no key of its own
+ * (the public functional keyswitch, spf_public_functional_keyswitch_*, does the same job in n * L dependent rounds under a key of
+ * 0.27 - 0.54 GB).  Not a function of the reference but a fixed composition of reference functions; with L = log2 N and
+ * round(x, r) = keyswitch(x(X^t), ak[r-1]), t = N / 2^(r-1) + 1, the round of spf_glwe_automorphism_*:
+ *   leaf   SPF_VAL_LWE1: g_j = the GLWE whose `sample_extract` at index 0 (ops/ciphertext/glwe_ciphertext_ops.rs:31-76) is leaf j and
+ *          whose body coefficients 1 .. N-1 are 0; SPF_VAL_GLWE1: g_j = leaf j.  c_j^(0) = `polynomial_shr_round`(g_j, L) on every
+ *          polynomial (the shift of `glwe_mod_switch_and_expand_pow_2`): the embedding first, the shift second.
+ *   tree   for l = 1 .. m, cnt = p / 2^l, r = 0 .. cnt-1: E = c_r^(l-1), O = X^(N/2^l) * c_(r+cnt)^(l-1) (`mul_xn`),
+ *          c_r^(l) = (E + O) + round(E - O, L - l + 1)                       (t = 2^l + 1)
+ *   tail   x = c_0^(m); x <- x + round(x, r) for r = 1 .. L - m in turn: `trace` (ops/automorphisms/mod.rs:53-85) cut after L - m
+ *          rounds.  p = N has no tail; p = 1 is the whole trace, what `mod_switch_trace_and_rotate` does to one level.
+ * All additions wrap mod 2^64; the only floating-point step is the keyswitch, on exact input: every word equals the composition's.
+ * LAYOUT: the result is STRIDED — the phase of coefficient j * N / p carries leaf j's message (as N * shr_round(., L) of it:
+ * the message itself up to the L low bits the shift drops), every other coefficient carries 0.  This is not the packed integers'
+ * "bit j at coefficient j" (spf_pack_*).  It is reached by spf_blind_rotation_* with log_stride = log2(N / p), by
+ * spf_sample_extract_l1_each_* at the indices j * N / p, and by the polynomial linear maps (spf_glwe_poly_linear_*).
+ * Leaves are [B][p] rows, output b's p leaves consecutive, of k*N+1 (SPF_VAL_LWE1) or (k+1)*N (SPF_VAL_GLWE1) words; the result
+ * is B GLWEs of (k+1)*N words.
+ * Launches: one per tree level over the nodes of all outputs, one for the tail: m + 1, m when p = N, 2 when p = 1 (the leaf's
+ * conversion, then the trace).  N = 2048, k = 1 with tr_radix 6 levels x 7 bits runs the hand-written "ring_pack_kernel", every
+ * other shape "generic_ring_pack_kernel" (spf_last_lwe_ring_pack_kernel); "lwe_ring_pack" of spf_last_kernel_ms has one entry per
+ * launch.
+ * Scratch: spf_lwe_ring_pack_scratch_words gives the words one call of B outputs needs (B * (p/2 + p/4) GLWEs, less for p <= 4).
+ * spf_lwe_ring_pack_batch takes host pointers and owns its scratch: a call that would need more than 1 GiB runs in slices over B
+ * (the environment variable SPF_LWE_RING_PACK_SCRATCH_BYTES, read at each call, overrides the cap: a testing knob).
+ * spf_lwe_ring_pack_enqueue takes device pointers under the contract of the `_dev` entry points: it only enqueues on `stream`,
+ * uses no buffer of the context, runs as ONE slice in the caller's scratch and leaves the scratch's contents undefined.
+ * Statuses, decided before anything is queued, nothing touched: B = 0 is SPF_OK; no automorphism key is SPF_ERR_NO_KEY;
+ * SPF_ERR_INVALID_ARGUMENT with the numbers in the message for p = 0, p not a power of two or p > N, a leaf kind other than
+ * SPF_VAL_LWE1 / SPF_VAL_GLWE1, a scratch below the words needed, and any overlap of the output with the leaves or the scratch
+ * (or of the scratch with the leaves).  The group form deals B in contiguous shards, an output's leaves with it. */
+spf_status spf_lwe_ring_pack_batch(spf_ctx *ctx, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t *leaves, uint64_t *glwe_out);
+spf_status spf_lwe_ring_pack_scratch_words(spf_ctx *ctx, size_t p, size_t B, size_t *words);
+spf_status spf_lwe_ring_pack_enqueue(spf_ctx *ctx, void *stream, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t *d_leaves,
+                                     uint64_t *d_scratch, size_t scratch_words, uint64_t *d_glwe_out);
+const char *spf_last_lwe_ring_pack_kernel(spf_ctx *ctx);
+
 /* ---- measurement hooks (bench.py) ------------------------------------------------------- */
 
 /* Average device time in milliseconds of the launches of one kernel family made through this
@@ -1011,10 +1050,10 @@ spf_status spf_gather_rows_dev(spf_ctx *ctx, void *stream, size_t rows, size_t w
  * "keyswitch" (digits + GEMM), "trace" (cbs_trace_kernel), "scheme_switch", "cmux" (contiguous
  * batched CMUX family), "pufks_prepass" (the transposing pre-pass of a public functional keyswitch at the hand-written radices,
  * with the gather in front of it where there is one), "lwe_linear_planes" and "lwe_linear" (the per-call byte planes and the product,
- * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only), "glwe_poly_linear" (the one launch of spf_glwe_poly_linear_enqueue), "glwe_keyswitch" (the one launch of spf_glwe_keyswitch_enqueue, spf_glwe_automorphism_enqueue or spf_glwe_trace_enqueue).  A host-pointer bootstrap of more than one chip round is launched in slices
+ * with its bias, of spf_lwe_linear_enqueue; the VALU form records "lwe_linear" only), "glwe_poly_linear" (the one launch of spf_glwe_poly_linear_enqueue), "glwe_keyswitch" (the one launch of spf_glwe_keyswitch_enqueue, spf_glwe_automorphism_enqueue or spf_glwe_trace_enqueue), "lwe_ring_pack" (every launch of spf_lwe_ring_pack_enqueue: one entry per tree level, one for the tail).  A host-pointer bootstrap of more than one chip round is launched in slices
  * of 1024 ciphertexts: it records one "pbs" entry per slice.  Enable with spf_set_timing(ctx, 1). */
 spf_status spf_set_timing(spf_ctx *ctx, int enabled);
-spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" | "glwe_poly_linear" | "glwe_keyswitch" */,
+spf_status spf_last_kernel_ms(spf_ctx *ctx, const char *kernel /* "pbs" | "keyswitch" | "trace" | "scheme_switch" | "cmux" | "pufks_prepass" | "lwe_linear_planes" | "lwe_linear" | "glwe_poly_linear" | "glwe_keyswitch" | "lwe_ring_pack" */,
                               double *avg_ms, int *launches);
 /* `generate_lut` (sunscreen_tfhe ops/bootstrapping/programmable_bootstrapping.rs:129-185) for
  * `programmable_bootstrap_univariate`: map_tables[f * 2^bits + x] = f(x) for n_maps functions over a
@@ -1235,6 +1274,10 @@ spf_status spf_group_load_glwe_keyswitch_key_std(spf_group *grp, uint32_t slot, 
 spf_status spf_group_glwe_keyswitch_batch(spf_group *grp, uint32_t slot, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 spf_status spf_group_glwe_automorphism_batch(spf_group *grp, uint32_t round, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
 spf_status spf_group_glwe_trace_batch(spf_group *grp, size_t B, const uint64_t *glwe_in, uint64_t *glwe_out);
+/* ring packing (spf_lwe_ring_pack_batch): the automorphism key is the members' own; a batch is sharded by output, an output's p
+ * leaves go with it */
+spf_status spf_group_lwe_ring_pack_batch(spf_group *grp, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t *leaves,
+                                         uint64_t *glwe_out);
 /* The per-item forms (spf_sample_extract_l1_each_batch, spf_glwe_mul_xn_each_batch, spf_glwe_keyswitch_each_batch,
  * spf_glwe_automorphism_each_batch): a batch is sharded by item and the parameter array is dealt in the same contiguous shards;
  * the checks are made on the whole batch before any member is touched */

@@ -33,6 +33,7 @@ class _CParams(C.Structure):
 
 # spf_value_kind of the LWE ciphertexts, and the number of weight slots of a context (include/spf_hip.h)
 VAL_LWE0, VAL_LWE1 = 0, 1
+VAL_GLWE1 = 2   # (the other leaf kind of Engine.lwe_ring_pack)
 LWE_LINEAR_SLOTS = 64
 # the limits of the plaintext polynomial weights over GLWE ciphertexts (spf_glwe_poly_limits)
 GLWE_POLY_SLOTS, GLWE_POLY_MAX_ROWS, GLWE_POLY_MAX_TERMS = 64, 4096, 1 << 24
@@ -122,6 +123,10 @@ SYMBOLS = [
     ("spf_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
     ("spf_glwe_trace_enqueue", _I, [_P, _P, _SZ, _P, _P]),
     ("spf_last_glwe_keyswitch_kernel", C.c_char_p, [_P]),
+    ("spf_lwe_ring_pack_batch", _I, [_P, _I, _SZ, _SZ, _P, _P]),
+    ("spf_lwe_ring_pack_scratch_words", _I, [_P, _SZ, _SZ, C.POINTER(_SZ)]),
+    ("spf_lwe_ring_pack_enqueue", _I, [_P, _P, _I, _SZ, _SZ, _P, _P, _SZ, _P]),
+    ("spf_last_lwe_ring_pack_kernel", C.c_char_p, [_P]),
     # the per-item forms: (ctx, [stream,] B, in, HOST array of B parameters, out)
     ("spf_sample_extract_l1_each_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_sample_extract_l1_each_devptr", _I, [_P, _P, _SZ, _P, _P, _P]),
@@ -260,6 +265,7 @@ SYMBOLS = [
     ("spf_group_glwe_keyswitch_each_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_group_glwe_automorphism_each_batch", _I, [_P, _SZ, _P, _P, _P]),
     ("spf_group_glwe_trace_batch", _I, [_P, _SZ, _P, _P]),
+    ("spf_group_lwe_ring_pack_batch", _I, [_P, _I, _SZ, _SZ, _P, _P]),
     ("spf_group_l1ggsw_constant", _I, [_P, _I, _P]),
     ("spf_pool_create_group", _I, [_P, _SZ, _U32, C.POINTER(_P)]),
     ("spf_group_graph_create", _I, [_P, C.POINTER(_P)]),
@@ -985,6 +991,27 @@ class Engine:
         self._ck(self._lib.spf_glwe_trace_batch(self._h, x.shape[0], _ptr(x), _ptr(out)))
         return out
 
+    def lwe_ring_pack(self, leaves, p: int, leaf_kind: int = VAL_LWE1, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """ring packing (`spf_lwe_ring_pack_batch`): (B, p, leaf words) LWE1 or GLWE1 leaves into (B, glwe_words) GLWEs under the
+        automorphism key; leaf j's message lands at coefficient j * N / p (the strided layout: spf_amd.packed.strided_positions)"""
+        p = int(p)
+        words = self.params.lwe1_words if int(leaf_kind) == VAL_LWE1 else self.params.glwe_words
+        x = _u64(leaves).reshape(-1)
+        if p < 1 or x.size % (p * words):
+            raise SpfError(-2, f"lwe_ring_pack: {x.size} words are no whole number of outputs of p = {p} leaves of {words} words")
+        B = x.size // (p * words)
+        if out is None:
+            out = np.empty((B, self.params.glwe_words), dtype=np.uint64)
+        else:
+            _out("lwe_ring_pack", out, np.uint64, B * self.params.glwe_words)
+        self._ck(self._lib.spf_lwe_ring_pack_batch(self._h, int(leaf_kind), p, B, _ptr(x), _ptr(out)))
+        return out
+
+    def lwe_ring_pack_scratch_words(self, p: int, B: int) -> int:
+        w = C.c_size_t()
+        self._ck(self._lib.spf_lwe_ring_pack_scratch_words(self._h, int(p), int(B), C.byref(w)))
+        return w.value
+
     def gate_bootstrap(self, lwe1, out: Optional[np.ndarray] = None) -> np.ndarray:
         x = _u64(lwe1).reshape(-1, self.params.lwe1_words)
         if out is None:
@@ -1147,6 +1174,12 @@ class Engine:
     def last_glwe_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_glwe_keyswitch_kernel(self._h) or b"").decode()
 
+    def lwe_ring_pack_enqueue(self, stream, leaf_kind, p, B, d_leaves, d_scratch, scratch_words, d_glwe_out):
+        self._ck(self._lib.spf_lwe_ring_pack_enqueue(self._h, stream, int(leaf_kind), int(p), B, d_leaves, d_scratch, int(scratch_words), d_glwe_out))
+
+    def last_lwe_ring_pack_kernel(self) -> str:
+        return (self._lib.spf_last_lwe_ring_pack_kernel(self._h) or b"").decode()
+
     def last_public_functional_keyswitch_kernel(self) -> str:
         return (self._lib.spf_last_public_functional_keyswitch_kernel(self._h) or b"").decode()
 
@@ -1265,6 +1298,9 @@ class Group(Engine):
 
     def last_glwe_keyswitch_kernel(self) -> str:
         return self.member(0).last_glwe_keyswitch_kernel()
+
+    def last_lwe_ring_pack_kernel(self) -> str:
+        return self.member(0).last_lwe_ring_pack_kernel()
 
     def run_graphs(self, graphs):
         """`spf_group_run_graphs`: graphs are `spf_amd.FheCircuit`s made over this group; dealt to the members by cost,

@@ -905,6 +905,20 @@ spf_status spf_group_glwe_trace_batch(spf_group* g, size_t B, const uint64_t* in
     return group_glwe_ks(g, GLWE_KS_TRACE, 0, B, in, out);
 }
 
+// ring packing: sharded by output, an output's p leaves go with it (the checks are made on the whole batch, on member 0)
+spf_status spf_group_lwe_ring_pack_batch(spf_group* g, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t* leaves, uint64_t* out)
+{
+    if (spf_status s = group_args(g, false)) return s;
+    spf_ctx* c0 = g->m[0]->ctx;
+    if (spf_status s = ring_pack_args(c0, leaf_kind, p, B)) return gfail(g, s, spf_last_error(c0));
+    if (B == 0) return SPF_OK;
+    if (!leaves || !out) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    const BatchShape sh{1, {p * ring_pack_leaf_words(c0->prm, leaf_kind), 0, 0}, glwe_words(c0->prm), kBatchMaxRows / p};
+    if (batch_overlaps(sh, B, out, leaves)) return gfail(g, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the leaves");
+    return group_batch(g, sh, B, {leaves}, out,
+                       [=](spf_ctx* c, size_t n, Rows in, Rows out) { return spf_lwe_ring_pack_batch(c, leaf_kind, p, n, in, out); });
+}
+
 // The per-item forms (spf_*_each_batch): sharded by item, the parameter array — the second operand of each_shape, one word per
 // item — dealt in the same contiguous shards; the checks are made on the whole batch, on member 0
 static spf_status group_each(spf_group* g, int op, size_t B, const uint64_t* in, const uint64_t* params, uint64_t* out)

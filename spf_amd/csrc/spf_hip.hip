@@ -14,6 +14,8 @@
 #include "spf_lwe_linear.hpp"
 #include "spf_glwe_poly.hpp"
 #include "spf_glwe_keyswitch.hpp"
+#include "spf_lwe_ring_pack.hpp"
+#include "spf_lwe_ring_pack_plan.hpp"
 #include "spf_each_plan.hpp"
 
 #include <hip/hip_runtime.h>
@@ -67,9 +69,9 @@ struct Scratch {
 };
 
 // kernels whose launches spf_set_timing brackets with hipEvents on the launch stream (spf_last_kernel_ms)
-enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_GLWE_POLY, T_GLWE_KS, T_COUNT };
+enum TimedKernel { T_PBS = 0, T_KS, T_TRACE, T_SS, T_CMUX, T_PUFKS_PRE, T_LIN_PLANES, T_LIN, T_GLWE_POLY, T_GLWE_KS, T_RING_PACK, T_COUNT };
 const char* const kTimedNames[T_COUNT] = {"pbs", "keyswitch", "trace", "scheme_switch", "cmux", "pufks_prepass", "lwe_linear_planes",
-                                          "lwe_linear", "glwe_poly_linear", "glwe_keyswitch"};
+                                          "lwe_linear", "glwe_poly_linear", "glwe_keyswitch", "lwe_ring_pack"};
 
 // one slot of plaintext weights for spf_lwe_linear_* (spf_lwe_linear.hpp): the int64 matrix as loaded, always; the int8 limbs of
 // -w and their sums where the matrix-core path takes the matrix (U > 0)
@@ -201,6 +203,9 @@ struct spf_ctx {
     bool glwe_ks_generic_ready = false;
     const char* last_glwe_ks_kernel = "";
     uint64_t gksk_epoch = 0; // bumped by every spf_load_glwe_keyswitch_key_std (captured gate graphs hold a slot's pointer and kernel)
+    // ring packing (spf_lwe_ring_pack.hpp): the scratch of the host-pointer form, one slice's worth
+    DevBuf ring_pack_scratch;
+    const char* last_ring_pack_kernel = "";
     // the per-item entry points (spf_*_each_*): the pointer, parameter, workgroup and unit tables of ONE call, built on the host in
     // `each_host` (pinned), copied to `each_tab` on the call's stream; `each_ev` says when that copy has read the host image
     DevBuf each_tab;
@@ -759,6 +764,8 @@ static spf_status glwe_ks_prepare_generic(spf_ctx* c)
                                   (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_each_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_ring_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)generic_trace_lds_bytes(N, c->prm.glwe_size)));
     c->glwe_ks_generic_ready = true;
     return SPF_OK;
 }
@@ -847,6 +854,8 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_glwe_ks_each_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)generic_trace_lds_bytes(N, params->glwe_size)));
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&generic_ring_pack_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)generic_trace_lds_bytes(N, params->glwe_size)));
         c->glwe_ks_generic_ready = true;
         *out = c;
         return SPF_OK;
@@ -901,6 +910,10 @@ spf_status spf_create(const spf_params* params, int device_id, spf_ctx** out)
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
     CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&glwe_ks_each_kernel<6, 7, GLWE_KS_KEYSWITCH>),
                            hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ring_pack_kernel<6, 7, true>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
+    CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ring_pack_kernel<6, 7, false>),
+                           hipFuncAttributeMaxDynamicSharedMemorySize, kTraceLds));
 #undef CK
     // an automorphism key of another radix than the hand-written kernel's: spf_glwe_automorphism_* / spf_glwe_trace_* run the
     // generic kernel (the *_enqueue forms only enqueue: its table is made here)
@@ -937,7 +950,7 @@ static void ctx_release(spf_ctx* c)
                     c->in.p, c->out.p, c->mid.p, c->aux.p, c->packed.p, c->unpack_l1.p, c->unpack_l0.p, c->brot_mid.p, c->brot_high.p, (void*)c->d_ksk_planes,
                     c->scr.ks_dig.p, c->scr.ks_rowsum.p, (void*)c->d_ak, (void*)c->d_ssk, c->scr.cbs_glwe.p, c->scr.cbs_glev.p, (void*)c->d_gen_tables,
                     (void*)c->d_pufks, c->pufks_dig.p, (void*)c->d_pfks, (void*)c->d_pfks_planes, c->pfks_dig.p, c->pfks_rowsum.p, c->pfks_glwe.p,
-                    c->pfks_lwe.p, c->lin_planes.p, c->each_tab.p})
+                    c->pfks_lwe.p, c->lin_planes.p, c->each_tab.p, c->ring_pack_scratch.p})
         if (p) (void)hipFree(p);
     if (c->each_ev) { (void)hipEventSynchronize(c->each_ev); (void)hipEventDestroy(c->each_ev); }
     if (c->each_host) (void)hipHostFree(c->each_host);
@@ -2334,7 +2347,7 @@ spf_status spf_last_kernel_ms(spf_ctx* c, const char* kernel, double* avg_ms, in
     std::vector<TimedLaunch>* v = nullptr;
     for (int k = 0; k < T_COUNT; k++)
         if (!strcmp(kernel, kTimedNames[k])) v = &c->timed[k];
-    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\", \"lwe_linear\", \"glwe_poly_linear\" or \"glwe_keyswitch\"");
+    if (!v) return fail(c, SPF_ERR_INVALID_ARGUMENT, "kernel must be \"pbs\", \"keyswitch\", \"trace\", \"scheme_switch\", \"cmux\", \"pufks_prepass\", \"lwe_linear_planes\", \"lwe_linear\", \"glwe_poly_linear\", \"glwe_keyswitch\" or \"lwe_ring_pack\"");
     double total = 0.0;
     int n = 0;
     for (auto& t : *v) {
@@ -3578,6 +3591,138 @@ spf_status spf_glwe_automorphism_batch(spf_ctx* c, uint32_t round, size_t B, con
 spf_status spf_glwe_trace_batch(spf_ctx* c, size_t B, const uint64_t* glwe_in, uint64_t* glwe_out)
 {
     return glwe_ks_batch(c, GLWE_KS_TRACE, 0, B, glwe_in, glwe_out);
+}
+
+// ---------------------------------------------------------------- ring packing: LWE / GLWE leaves into one GLWE (spf_lwe_ring_pack_*)
+// p = 2^m leaves per output through p - 1 automorphism rounds in a tree and the first log2 N - m rounds of the trace, under the
+// automorphism key: the composition include/spf_hip.h states; kernels spf_lwe_ring_pack.hpp, launches and rows
+// spf_lwe_ring_pack_plan.hpp.
+
+static size_t ring_pack_leaf_words(const spf_params& p, spf_value_kind kind)
+{
+    return kind == SPF_VAL_LWE1 ? (size_t)p.glwe_size * p.polynomial_degree + 1 : (size_t)(p.glwe_size + 1) * p.polynomial_degree;
+}
+
+// What every form checks before anything is touched, on `c` with its texts (B = 0 is SPF_OK once these hold; pointers are the
+// caller's business below).
+static spf_status ring_pack_args(spf_ctx* c, spf_value_kind leaf_kind, size_t p, size_t B)
+{
+    if (!c) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const size_t N = c->prm.polynomial_degree;
+    if (leaf_kind != SPF_VAL_LWE1 && leaf_kind != SPF_VAL_GLWE1)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "leaf kind " + std::to_string((int)leaf_kind) + ": the leaves are SPF_VAL_LWE1 (" +
+                                                     std::to_string((int)SPF_VAL_LWE1) + ") or SPF_VAL_GLWE1 (" + std::to_string((int)SPF_VAL_GLWE1) + ")");
+    if (!spf_ring_pack::valid_p(p, N))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "p = " + std::to_string(p) + ": the leaves per output are a power of two in 1 .. N = " + std::to_string(N));
+    if (B > kBatchMaxRows / p)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large: B * p = " + std::to_string(B) + " * " + std::to_string(p) + " > " + std::to_string(kBatchMaxRows));
+    if (!c->ak_ready) return fail(c, SPF_ERR_NO_KEY, "automorphism key not loaded");
+    if (!glwe_ks_tuned(c, c->prm.tr_radix_log, c->prm.tr_radix_count) && !c->glwe_ks_generic_ready)
+        return fail(c, SPF_ERR_UNSUPPORTED, "the context's tr_radix is served by no GLWE keyswitch kernel: " +
+                                                glwe_ks_radix_error(c->prm.tr_radix_log, c->prm.tr_radix_count));
+    return SPF_OK;
+}
+
+// the launches of one slice (spf_lwe_ring_pack_plan.hpp) on `s`; no buffer of the context
+static spf_status ring_pack_slice(spf_ctx* c, hipStream_t s, const spf_ring_pack::Slice& sl, spf_value_kind leaf_kind, const uint64_t* d_leaves,
+                                  uint64_t* d_scratch, uint64_t* d_out)
+{
+    using namespace spf_ring_pack;
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    const uint32_t N = c->prm.polynomial_degree, k = c->prm.glwe_size, count = c->prm.tr_radix_count, radix_log = c->prm.tr_radix_log;
+    const size_t gw = (size_t)(k + 1) * N, lw = ring_pack_leaf_words(c->prm, leaf_kind);
+    const size_t ksk_len = (size_t)k * count * (k + 1) * (N / 2);
+    const bool tuned = glwe_ks_tuned(c, radix_log, count);
+    c->last_ring_pack_kernel = tuned ? "ring_pack_kernel" : "generic_ring_pack_kernel";
+    for (const Launch& l : sl.launches) {
+        const bool leaves = l.src.space == LEAVES;
+        const uint64_t* src = leaves ? d_leaves + l.src.row0 * lw : d_scratch + l.src.row0 * gw; // (a launch never reads the output)
+        uint64_t* dst = l.dst.space == OUT ? d_out + l.dst.row0 * gw : d_scratch + l.dst.row0 * gw;
+        const uint32_t src_kind = leaves ? (uint32_t)leaf_kind : (uint32_t)RING_PACK_ROWS, src_words = (uint32_t)(leaves ? lw : gw);
+        TimedScope ts(c, s, T_RING_PACK);
+        spf_status st = ts.begin();
+        if (st != SPF_OK) return st;
+        if (l.kind == LEAF) {
+            hipLaunchKernelGGL(ring_pack_leaf_kernel, dim3(l.units), dim3(256), 0, s, src, dst, l.units, src_kind, src_words, N, k, c->log_n);
+        } else {
+            const c64* key = c->d_ak + (size_t)(l.round - 1) * ksk_len;
+            const uint32_t kk = (N >> (l.round - 1)) + 1;
+            if (tuned) {
+                RingPackArgs a{src, dst, key, c->d_tables, l.units, l.cnt, kk, l.x, l.rounds, src_kind, src_words};
+                const dim3 grid((l.units + kWavesPerBlock - 1) / kWavesPerBlock), block(512);
+                if (l.kind == COMBINE) hipLaunchKernelGGL((ring_pack_kernel<6, 7, true>), grid, block, kTraceLds, s, a);
+                else hipLaunchKernelGGL((ring_pack_kernel<6, 7, false>), grid, block, kTraceLds, s, a);
+            } else {
+                GenericRingPackArgs a{generic_shape(c), src, dst, key, radix_log, count, l.kind == COMBINE ? 1u : 0u,
+                                      l.cnt, kk, l.x, l.rounds, src_kind, src_words};
+                hipLaunchKernelGGL(generic_ring_pack_kernel, dim3(l.units), dim3(kGenericThreads), generic_trace_lds_bytes(N, k), s, a);
+            }
+        }
+        HIPCHK(c, hipGetLastError());
+        st = ts.end();
+        if (st != SPF_OK) return st;
+    }
+    return SPF_OK;
+}
+
+spf_status spf_lwe_ring_pack_scratch_words(spf_ctx* c, size_t p, size_t B, size_t* words)
+{
+    if (!c || !words) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t N = c->prm.polynomial_degree;
+    if (!spf_ring_pack::valid_p(p, N))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "p = " + std::to_string(p) + ": the leaves per output are a power of two in 1 .. N = " + std::to_string(N));
+    if (B > kBatchMaxRows / p) return fail(c, SPF_ERR_INVALID_ARGUMENT, "batch too large");
+    *words = spf_ring_pack::scratch_words(B, p, N, c->prm.glwe_size);
+    return SPF_OK;
+}
+
+spf_status spf_lwe_ring_pack_enqueue(spf_ctx* c, void* stream, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t* d_leaves,
+                                     uint64_t* d_scratch, size_t scratch_words, uint64_t* d_glwe_out)
+{
+    spf_status st = ring_pack_args(c, leaf_kind, p, B);
+    if (st != SPF_OK || B == 0) return st;
+    if (!d_leaves || !d_glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t N = c->prm.polynomial_degree, k = c->prm.glwe_size, gw = (k + 1) * N;
+    const size_t need = spf_ring_pack::scratch_words(B, p, N, k);
+    if (scratch_words < need || (need && !d_scratch))
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "scratch of " + std::to_string(d_scratch ? scratch_words : 0) + " words: B = " + std::to_string(B) +
+                                                     " outputs of p = " + std::to_string(p) + " leaves need " + std::to_string(need) +
+                                                     " words (spf_lwe_ring_pack_scratch_words)");
+    const size_t leaf_bytes = B * p * ring_pack_leaf_words(c->prm, leaf_kind) * 8;
+    if (ranges_overlap(d_glwe_out, B * gw * 8, d_leaves, leaf_bytes)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the leaves");
+    if (need && ranges_overlap(d_glwe_out, B * gw * 8, d_scratch, need * 8)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the scratch");
+    if (need && ranges_overlap(d_scratch, need * 8, d_leaves, leaf_bytes)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the scratch overlaps the leaves");
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    HIPCHK(c, hipSetDevice(c->device));
+    return ring_pack_slice(c, (hipStream_t)stream, spf_ring_pack::plan_slice(0, B, p, N), leaf_kind, d_leaves, d_scratch, d_glwe_out);
+}
+
+spf_status spf_lwe_ring_pack_batch(spf_ctx* c, spf_value_kind leaf_kind, size_t p, size_t B, const uint64_t* leaves, uint64_t* glwe_out)
+{
+    spf_status st = ring_pack_args(c, leaf_kind, p, B);
+    if (st != SPF_OK || B == 0) return st;
+    if (!leaves || !glwe_out) return fail(c, SPF_ERR_INVALID_ARGUMENT, "null argument");
+    const size_t N = c->prm.polynomial_degree, k = c->prm.glwe_size, gw = (k + 1) * N;
+    const size_t leaf_bytes = B * p * ring_pack_leaf_words(c->prm, leaf_kind) * 8;
+    if (ranges_overlap(glwe_out, B * gw * 8, leaves, leaf_bytes)) return fail(c, SPF_ERR_INVALID_ARGUMENT, "the output overlaps the leaves");
+    // the slices of the call under the cap (the slice loop is the plan's), each with the whole scratch: the stream orders them
+    const std::vector<spf_ring_pack::Slice> slices = spf_ring_pack::plan(B, p, N, k, spf_ring_pack::scratch_cap_bytes());
+    return host_call(c, {HostIn{c->in, leaves, leaf_bytes}}, B * gw * 8, glwe_out, [&]() -> spf_status {
+        spf_status s = ensure(c, c->ring_pack_scratch, spf_ring_pack::scratch_words(slices[0].nb, p, N, k) * 8);
+        for (const spf_ring_pack::Slice& sl : slices) {
+            if (s != SPF_OK) break;
+            s = ring_pack_slice(c, c->stream, sl, leaf_kind, (const uint64_t*)c->in.p, (uint64_t*)c->ring_pack_scratch.p, (uint64_t*)c->out.p);
+        }
+        return s;
+    });
+}
+
+const char* spf_last_lwe_ring_pack_kernel(spf_ctx* c)
+{
+    if (!c) return "";
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    return c->last_ring_pack_kernel;
 }
 
 // ---------------------------------------------------------------- one launch over items with a parameter each (spf_*_each_*)

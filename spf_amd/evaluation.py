@@ -129,6 +129,11 @@ class Evaluation:
     def trace(self, output: np.ndarray, input: np.ndarray):
         self._store(output, self.engine.glwe_trace(input))
 
+    # ring packing (spf_lwe_ring_pack_batch; PackLWEs): (B, p, leaf words) LWE1 (leaf_kind 1) or GLWE1 (2) leaves -> (B, k+1, N)
+    # under the automorphism key, leaf j's message at coefficient j * N / p (spf_amd.packed.strided_positions)
+    def lwe_ring_pack(self, output: np.ndarray, leaves: np.ndarray, p: int, leaf_kind: int = 1):
+        self._store(output, self.engine.lwe_ring_pack(leaves, p, leaf_kind))
+
     # one round (1 .. log2 N) of the trace's loop (ops/automorphisms/mod.rs:72-83).  The three as single-ciphertext operations of
     # a pool, by host pointer or on device-resident values: Pool.glwe_keyswitch / glwe_automorphism / glwe_trace and their `_v`
     # forms (FheOp.GLWE_KEYSWITCH / GLWE_AUTOMORPHISM / GLWE_TRACE through Pool.run_v / push_v)

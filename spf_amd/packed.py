@@ -1,7 +1,8 @@
 """The plaintext side of packed integers (`PackedDynamicGenericInt`, parasol_runtime/src/fluent/generic_int.rs:162-176): an
 n-bit integer in one L1 GLWE, bit i (least significant first, `to_bits`, fluent/int.rs:47-49, uint.rs:30-32) in coefficient
 X^i of the message polynomial at one plaintext bit.  Host only, no GPU; the ciphertext side is Engine.glwe_pack /
-glwe_unpack_l1 / unpack_circuit_bootstrap, and Engine.blind_rotation for the packed tables at the end of this file."""
+glwe_unpack_l1 / unpack_circuit_bootstrap, and Engine.blind_rotation for the packed tables.  The strided layout of
+Engine.lwe_ring_pack (message j at coefficient j * N / p) is at the end of this file."""
 from __future__ import annotations
 
 import numpy as np
@@ -75,3 +76,32 @@ def trivial_table_glwe(values, entry_bits: int, params: Params = DEFAULT_128):
     out = np.zeros(params.glwe_words, dtype=np.uint64)
     out[params.glwe_size * params.polynomial_degree:] = coeffs << np.uint64(63)
     return out, log_stride
+
+
+# ---- the strided layout of ring packing (Engine.lwe_ring_pack, spf_lwe_ring_pack_batch) ----------------------------------------
+
+def strided_positions(p: int, params: Params = DEFAULT_128) -> np.ndarray:
+    """the coefficients j * N / p, j < p, that hold the p messages of a ring-packed GLWE (p a power of two <= N); every other
+    coefficient of its phase holds 0.  They are the indices of sample_extract_l1_each, and log2(N / p) is the log_stride of
+    Engine.blind_rotation."""
+    N = params.polynomial_degree
+    p = int(p)
+    if p < 1 or p > N or p & (p - 1):
+        raise ValueError(f"p must be a power of two in 1 ..= {N}, got {p}")
+    return np.arange(p, dtype=np.int64) * (N // p)
+
+
+def strided_plaintext(messages, params: Params = DEFAULT_128) -> np.ndarray:
+    """the u64 message polynomial with messages[j] (torus words, taken mod 2^64) at coefficient j * N / p, p = len(messages)"""
+    m = [int(v) & 0xFFFFFFFFFFFFFFFF for v in messages]
+    out = np.zeros(params.polynomial_degree, dtype=np.uint64)
+    out[strided_positions(len(m), params)] = np.array(m, dtype=np.uint64)
+    return out
+
+
+def strided_decode(coeffs, p: int, params: Params = DEFAULT_128) -> np.ndarray:
+    """the p messages of a decoded (or raw) coefficient vector of N entries laid out by strided_plaintext"""
+    c = np.asarray(coeffs).reshape(-1)
+    if c.size != params.polynomial_degree:
+        raise ValueError(f"expected {params.polynomial_degree} coefficients, got {c.size}")
+    return c[strided_positions(p, params)]
