@@ -57,9 +57,10 @@ class KeyswitchOp(enum.IntEnum):
     """Three more `spf_graph_op` values that are no `FheOp` of the reference: `keyswitch_glwe_to_glwe` (fft_ops.rs:457-495) under
     the key of slot `param`, round `param` (1 .. log2 N) of the trace's loop, and `trace` (ops/automorphisms/mod.rs:53-85); one GLWE1
     operand, one GLWE1 result.  Taken wherever an FheOp is and reachable as `FheOp.GLWE_KEYSWITCH` / `GLWE_AUTOMORPHISM` /
-    `GLWE_TRACE`.  In a gate graph they are the nodes of `add_glwe_keyswitch` / `add_glwe_automorphism` / `add_glwe_trace`.  An
-    enum of its own, beside TableOp: the random graph generator of the differential tests draws every member of FheOp and TableOp,
-    and it cannot draw keyswitch keys."""
+    `GLWE_TRACE`.  In a gate graph they are the nodes of `add_glwe_keyswitch` / `add_glwe_automorphism` / `add_glwe_trace`
+    (NODE_GLWE_KEYSWITCH .. NODE_GLWE_TRACE below: `add_op` records them as those nodes, whichever door built them).  An enum of
+    its own, beside TableOp: the values 12 .. 14 never stand in a recorded circuit, so the random graph generator of the
+    differential tests, which draws every member of FheOp and TableOp as a node, draws these three as the NODE_* constants."""
     GLWE_KEYSWITCH = 12
     GLWE_AUTOMORPHISM = 13
     GLWE_TRACE = 14
@@ -91,17 +92,19 @@ LWE_LINEAR_NODE = NODE_LWE_LINEAR  # its name in the revision before: that revis
 LWE_LINEAR_SLOTS = 64            # SPF_LWE_LINEAR_SLOTS
 LWE_LINEAR_GRAPH_MAX_ROWS = 4096  # SPF_GRAPH_LWE_LINEAR_MAX_ROWS
 # spf_graph_add_glwe_poly_linear: one GLWE1 node per output row m, inputs = all K operands (one list shared by the M nodes of a
-# call), param = m.  Not a NODE_* name yet: the random graph generator of the differential tests draws every NODE_* of this module,
-# and it cannot draw polynomial weights.  This becomes NODE_GLWE_POLY_LINEAR in the change that teaches the generator to draw them.
-GLWE_POLY_LINEAR_NODE = 69
+# call), param = m.  A NODE_* name: the random graph generator of the differential tests draws every NODE_* of this module, and it
+# draws the polynomial weights apart from the circuit (tests/graph_fuzz_cases.py, draw_glwe_poly_slots).
+NODE_GLWE_POLY_LINEAR = 69
+GLWE_POLY_LINEAR_NODE = NODE_GLWE_POLY_LINEAR  # its name in the revisions before: their test modules and tools import it
 GLWE_POLY_SLOTS = 64       # SPF_GLWE_POLY_SLOTS
 GLWE_POLY_MAX_ROWS = 4096  # SPF_GLWE_POLY_MAX_ROWS
-_LINEAR_NODES = (NODE_LWE_LINEAR, GLWE_POLY_LINEAR_NODE)   # M nodes over one operand list, with a weight slot
+_LINEAR_NODES = (NODE_LWE_LINEAR, NODE_GLWE_POLY_LINEAR)   # M nodes over one operand list, with a weight slot
 # spf_graph_add_glwe_keyswitch / _automorphism / _trace: one GLWE1 node over one GLWE1 operand, param = the keyswitch-key slot / the
-# round / 0.  No NODE_* names, for the reason above: the random generator cannot draw keyswitch keys.
-GLWE_KEYSWITCH_NODE = 70
-GLWE_AUTOMORPHISM_NODE = 71
-GLWE_TRACE_NODE = 72
+# round / 0.  NODE_* names as well: the generator draws the keyswitch keys apart from the circuit (draw_glwe_ksk_slots)
+NODE_GLWE_KEYSWITCH = 70
+NODE_GLWE_AUTOMORPHISM = 71
+NODE_GLWE_TRACE = 72
+GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE = NODE_GLWE_KEYSWITCH, NODE_GLWE_AUTOMORPHISM, NODE_GLWE_TRACE  # (likewise)
 GLWE_KSK_SLOTS = 16   # SPF_GLWE_KSK_SLOTS
 _GLWE_KS_NODES = (GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE)
 # ... which spf_graph_add_op records for the three KeyswitchOp values as well (the same node, whichever door built it)

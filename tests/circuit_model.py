@@ -9,24 +9,29 @@ import numpy as np
 
 import oracle as O
 from spf_amd import FheOp, TableOp, ValueKind
-from spf_amd.graph import NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from spf_amd.graph import (NODE_GLWE_AUTOMORPHISM, NODE_GLWE_KEYSWITCH, NODE_GLWE_POLY_LINEAR, NODE_GLWE_TRACE, NODE_LWE_LINEAR, NODE_PACK,
+                           NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK)
+from tests import glwe_keyswitch_cases as KC
+from tests import glwe_poly_cases as GC
 from tests import lwe_linear_cases as LC
 from tests import pbs_graph_cases as K
 from tests import pufks_cases as PC
 from tests.polyref_cases import key_fft
 
 # ks: oracle KeySet; ak / ssk: automorphism and scheme-switch keys; pufks: None or (key as loaded (n, count, k+1, N), log, count);
-# linear: None or the weight slots as loaded, {slot: (weights int64 (M, K), bias uint64 (M,) or None)}
-Keys = namedtuple("Keys", "ks ak ssk pufks linear", defaults=(None, None))
+# linear: None or the weight slots as loaded, {slot: (weights int64 (M, K), bias uint64 (M,) or None)};
+# glwe_ksk: None or the GLWE keyswitch-key slots as loaded, {slot: (words (k, L, k+1, N), radix_log, radix_count)};
+# glwe_poly: None or the polynomial weight slots as loaded, {slot: (CSR triple, bias (M, N) or None, (M, K))}
+Keys = namedtuple("Keys", "ks ak ssk pufks linear glwe_ksk glwe_poly", defaults=(None, None, None, None))
 
 _BOOTSTRAPS = (int(FheOp.CircuitBootstrap), int(TableOp.PBS_UNIVARIATE), int(TableOp.PBS_BIVARIATE))
 
 
-def keys_of(which, pufks=None, linear=None) -> Keys:
-    """the keys of a context of pbs_graph_cases.CONTEXTS, with the public-functional-keyswitch key and the weight slots of the
-    linear maps if they are loaded"""
+def keys_of(which, pufks=None, linear=None, glwe_ksk=None, glwe_poly=None) -> Keys:
+    """the keys of a context of pbs_graph_cases.CONTEXTS, with the public-functional-keyswitch key, the weight slots of the
+    linear maps, the GLWE keyswitch-key slots and the polynomial weight slots if they are loaded"""
     _, ks, ak, ssk = K.keys_of(which)
-    return Keys(ks, ak, ssk, pufks, linear)
+    return Keys(ks, ak, ssk, pufks, linear, glwe_ksk, glwe_poly)
 
 
 def kind_name(rec, i) -> str:
@@ -36,7 +41,8 @@ def kind_name(rec, i) -> str:
     if op == -2:
         return f"Trivial{ValueKind(rec.kind[i]).name}({rec.param[i]})"
     names = {NODE_UNPACK: "Unpack", NODE_PACK: "Pack", NODE_ROT_CMUX: "RotCMux", NODE_PUFKS: "PublicFunctionalKeyswitch",
-             NODE_LWE_LINEAR: "LweLinear"}
+             NODE_LWE_LINEAR: "LweLinear", NODE_GLWE_POLY_LINEAR: "GlwePolyLinear", NODE_GLWE_KEYSWITCH: "GlweKeyswitch",
+             NODE_GLWE_AUTOMORPHISM: "GlweAutomorphism", NODE_GLWE_TRACE: "GlweTrace"}
     return names[op] if op in names else (TableOp(op).name if op in TableOp._value2member_map_ else FheOp(op).name)
 
 
@@ -55,15 +61,24 @@ def trivial(P, kind, bit) -> np.ndarray:
 
 
 _FFT_OF = []    # (key, its transform) of the last two keys: a level-1 key of the tuned set is 268 MB
+_KSK_FFT_OF = []    # the same for GLWE keyswitch keys (a few hundred KB each): the last two tables of three slots
 
 
-def _key_fft_once(key):
-    for k, f in _FFT_OF:
+def _key_fft_once(key, cache=_FFT_OF, keep=2):
+    for k, f in cache:
         if k is key:
             return f
-    _FFT_OF.append((key, key_fft(key)))
-    del _FFT_OF[:-2]
-    return _FFT_OF[-1][1]
+    cache.append((key, key_fft(key)))
+    del cache[:-keep]
+    return cache[-1][1]
+
+
+def oracle_round(P, ak_fft, x, rnd: int) -> np.ndarray:
+    """glwe_keyswitch_cases.oracle_round for a context that is no KsCase: round `rnd` in 1 .. log2 N of the trace's loop on the GLWE
+    x (k+1, N), without the add, under the automorphism key in transformed form as the contexts load it (any shape; row rnd - 1 of
+    its log2 N rows is the round's keyswitch key)"""
+    rows = np.asarray(ak_fft).reshape(KC.log2n(P), -1)
+    return KC.oracle_keyswitch(P, KC.oracle_pow_k(P, np.asarray(x, dtype=np.uint64).reshape(P.k + 1, P.N), KC.exponents(P)[rnd - 1]), rows[rnd - 1])
 
 
 def evaluate(rec, P, keys: Keys, hosts=None):
@@ -131,6 +146,18 @@ def evaluate(rec, P, keys: Keys, hosts=None):
             w, bias = keys.linear[slot]
             assert np.shape(w) == (rows, len(x)), f"node {i}: slot {slot} holds {np.shape(w)} weights, the layer is {(rows, len(x))}"
             v = LC.linear_ref(np.stack(x), w, bias)[par]
+        elif op == NODE_GLWE_POLY_LINEAR:   # row par of the layer, likewise
+            slot, rows = rec.linear_of(i)
+            triple, bias, shape = keys.glwe_poly[slot]
+            assert tuple(shape) == (rows, len(x)), f"node {i}: slot {slot} holds {tuple(shape)} weights, the layer is {(rows, len(x))}"
+            v = GC.poly_linear_ref(np.stack(x).reshape(1, len(x), k + 1, N), triple, rows, len(x), bias)[0, par]
+        elif op == NODE_GLWE_KEYSWITCH:     # under the key of slot par, at the key's own radix
+            words, log, count = keys.glwe_ksk[par]
+            v = KC.oracle_keyswitch(P, x[0].reshape(k + 1, N), _key_fft_once(words, _KSK_FFT_OF, 6), (log, count))
+        elif op == NODE_GLWE_AUTOMORPHISM:  # round par of the trace's loop: x(X^t) switched back under row par - 1 of the key
+            v = oracle_round(P, keys.ak, x[0], par)
+        elif op == NODE_GLWE_TRACE:
+            v = O.trace(x[0], np.asarray(keys.ak).reshape(-1), P)
         else:
             raise ValueError(f"node {i}: unknown operation {op}")
         vals.append(np.asarray(v).reshape(-1))

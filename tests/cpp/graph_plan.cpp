@@ -7,13 +7,15 @@
 // Checked: every operand's level is below its node's; a group's members share its key and stand in node order, the groups in key
 // order; blocks are 256-aligned and disjoint and a node's offset is its row in its group's block; a slot marked in place has
 // operands that are consecutive from first_off, any other slot a pointer row equal to its operands' offsets (member order;
-// layer-major for linear, int-major for unpack); the pointer rows tile the table; the CMUX units are the members' units,
+// layer-major for linear and polynomial linear, int-major for unpack, one per member for the GLWE keyswitch, automorphism and trace
+// nodes); the pointer rows tile the table; the CMUX units are the members' units,
 // non-decreasing in selector, ties in member order; the stage size is the largest gathered slot; planning twice gives one plan.
 //
 // File format (decimal numbers, white space between them):
 //   sizes  bytes(LWE0) bytes(LWE1) bytes(GLWE1) bytes(GGSW1) bytes(GLEV1)  cbs_radix_count  pufks_stage
 //   nodes  n      then per node    op kind param  unpack_width  linear_slot linear_rows  k  operand[0] ... operand[k-1]
-// (op: a spf_graph_op, 64 .. 68, -1 input, -2 constant; the nodes of one unpack or linear call each have their line)
+// (op: a spf_graph_op, 64 .. 72, -1 input, -2 constant; the nodes of one unpack, linear or polynomial linear call each have their
+// line; a polynomial linear node (69) gives its slot and rows as a linear node does, the nodes 70 .. 72 their slot / round / 0 as param)
 //
 // The plan as printed (what the test compares and digests):
 //   levels n l..    offsets n o..    per group: "group level op kind slot rows n | members out_off | (contiguous first_off
@@ -68,13 +70,17 @@ bool read_circuit(const char* path, P::Graph* g, P::Sizes* sz)
             ok = param == 0 && k == 1 && width > 0;
             n.n_in = 1; n.in[0] = ids[0]; n.count = (uint32_t)width;
             if (ok) g->add_numbered(n, (size_t)width);
-        } else if (op == P::kNodeLweLinear) {
-            ok = param == 0 && k > 0 && rows > 0;
+        } else if (op == P::kNodeLweLinear || op == P::kNodeGlwePolyLinear) {
+            ok = param == 0 && k > 0 && rows > 0 && (op == P::kNodeLweLinear || kind == SPF_VAL_GLWE1);
             n.lin_slot = (uint32_t)slot; n.lin_rows = (uint32_t)rows;
             if (ok) g->add_listed(n, ids.data(), ids.size(), (size_t)rows);
         } else if (op == P::kNodePack || op == P::kNodePufks) {
             ok = k > 0;
             if (ok) g->add_listed(n, ids.data(), ids.size());
+        } else if (op == P::kNodeGlweKeyswitch || op == P::kNodeGlweAutomorphism || op == P::kNodeGlweTrace) {
+            ok = k == 1 && kind == SPF_VAL_GLWE1 && (op != P::kNodeGlweTrace || param == 0);
+            n.n_in = 1; n.in[0] = ids[0];
+            if (ok) g->add(n);
         } else {
             ok = k <= 3 && (op < 0 ? k == 0 : op == P::kNodeRotCmux ? k == 2 : spf_ops::pool_op_of((int)op) != spf_ops::kNone && (int)k == P::op_row((int)op).arity);
             n.n_in = (uint32_t)k;
@@ -120,6 +126,10 @@ P::GroupKey expected_key(const P::Graph& g, const P::Node& n)
     case P::kNodePack: k.n = n.count; break;
     case P::kNodePufks: k.kind = (uint8_t)g.nodes[g.operand(n, 0)].kind; k.n = n.count; break;
     case P::kNodeLweLinear: k.kind = (uint8_t)n.kind; k.slot = (uint8_t)n.lin_slot; k.rows = (uint16_t)n.lin_rows; k.n = n.count; break;
+    case P::kNodeGlwePolyLinear: k.kind = (uint8_t)SPF_VAL_GLWE1; k.slot = (uint8_t)n.lin_slot; k.rows = (uint16_t)n.lin_rows; k.n = n.count; break;
+    case P::kNodeGlweKeyswitch: // the slot
+    case P::kNodeGlweAutomorphism: k.n = n.param; break; // the round
+    case P::kNodeGlweTrace: k.n = 0; break;
     default: break;
     }
     return k;
@@ -140,7 +150,17 @@ bool slot_of(const P::Graph& g, const P::Sizes& sz, const P::Group& gr, int s, S
         out->staged = op == P::kNodePufks && sz.pufks_stage;
         return true;
     }
-    if (op == P::kNodeLweLinear) { // layer-major: the list of every M-th member
+    if (op == P::kNodeGlweKeyswitch || op == P::kNodeGlweAutomorphism || op == P::kNodeGlweTrace) { // one GLWE per member
+        if (s) return false;
+        for (uint32_t id : gr.members) {
+            if (g.nodes[id].n_in != 1) fail("a node of the GLWE keyswitch family has not one operand", id);
+            out->offs.push_back(g.nodes[g.nodes[id].in[0]].off);
+        }
+        out->row_bytes = sz.of(SPF_VAL_GLWE1);
+        out->staged = false;
+        return true;
+    }
+    if (op == P::kNodeLweLinear || op == P::kNodeGlwePolyLinear) { // layer-major: the list of every M-th member
         if (s) return false;
         if (gr.members.size() % gr.key.rows) fail("a linear group is no whole number of layers", gr.members.size(), gr.key.rows);
         for (size_t i = 0; i < gr.members.size(); i += gr.key.rows) {
@@ -148,7 +168,7 @@ bool slot_of(const P::Graph& g, const P::Sizes& sz, const P::Group& gr, int s, S
                 if (gr.members[i + m] != gr.members[i] + m || g.nodes[gr.members[i + m]].param != m) fail("a layer's rows are not successive members", i, m);
             all_of(g.nodes[gr.members[i]]);
         }
-        out->row_bytes = sz.of(gr.key.kind);
+        out->row_bytes = op == P::kNodeGlwePolyLinear ? sz.of(SPF_VAL_GLWE1) : sz.of(gr.key.kind);
         out->staged = false;
         return true;
     }
@@ -234,13 +254,15 @@ void check(const P::Graph& g, const P::Sizes& sz, const P::Plan& p)
     if (p.arena_bytes % P::kAlign) fail("the arena is not 256-aligned", p.arena_bytes);
     // ---- operand access, the table, the stage size
     size_t table_at = 0, stage = 0;
-    bool any_pufks = false, any_linear = false;
+    bool any_pufks = false, any_linear = false, any_poly = false, any_glwe_ks = false;
     for (size_t gi = 0; gi < p.groups.size(); gi++) {
         const P::Group& gr = p.groups[gi];
         if (gr.members.empty()) continue;
         const int32_t op = gr.key.op;
         any_pufks = any_pufks || op == P::kNodePufks;
         any_linear = any_linear || op == P::kNodeLweLinear;
+        any_poly = any_poly || op == P::kNodeGlwePolyLinear;
+        any_glwe_ks = any_glwe_ks || op == P::kNodeGlweKeyswitch || op == P::kNodeGlweAutomorphism || op == P::kNodeGlweTrace;
         const bool rot = op == P::kNodeRotCmux;
         if (rot || (op < P::kNodeUnpack && P::op_row(op).cmux_family)) {
             // the members' units in member order
@@ -314,6 +336,7 @@ void check(const P::Graph& g, const P::Sizes& sz, const P::Plan& p)
     if (table_at != p.table.size()) fail("the pointer rows do not tile the table", table_at, p.table.size());
     if (stage != p.stage_bytes) fail("the stage size is not the largest gathered slot", stage, p.stage_bytes);
     if (any_pufks != p.has_pufks || any_linear != p.has_linear) fail("has_pufks / has_linear do not say what the graph holds");
+    if (any_poly != p.has_glwe_poly || any_glwe_ks != p.has_glwe_ks) fail("has_glwe_poly / has_glwe_ks do not say what the graph holds");
 }
 
 } // namespace

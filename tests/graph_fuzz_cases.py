@@ -3,8 +3,10 @@
 
 A circuit is a typed DAG over the five value kinds with every node kind of the executor in it: every operation of the table
 (spf_ops.hpp) that has a `spf_graph_op` and the five constructors (unpack, pack, blind rotation, public functional keyswitch,
-plaintext linear map).  The weights of the linear maps are no part of a circuit: `draw_linear_slots(linear_seed)` draws them for a
-fixed table of slot shapes, so that one engine (or one group) loads them once for every circuit it runs.
+plaintext linear map, plaintext polynomial linear map, GLWE keyswitch / automorphism round / trace).  The weights of the linear
+maps are no part of a circuit: `draw_linear_slots(linear_seed)` draws them for a fixed table of slot shapes, so that one engine
+(or one group) loads them once for every circuit it runs; `draw_glwe_poly_slots` and `draw_glwe_ksk_slots` do the same for the
+polynomial weights and the GLWE keyswitch keys.
 The generator BUILDS the layouts in which the executor's plan takes another branch (PATTERNS below) and, for each, records the
 claim that makes it one: which nodes have to share a group, lie in consecutive rows, or stand on different levels.  The claims
 are checked against `circuit_model.planned_levels`, the executor's own level passes, so `facts` names a pattern only if the
@@ -12,16 +14,21 @@ circuit really holds it once the planner has moved the bootstraps and the conver
 import numpy as np
 
 from spf_amd import FheOp, RecordedCircuit, TableOp, ValueKind
-from spf_amd.graph import NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK
+from spf_amd.graph import (GLWE_KSK_SLOTS, GLWE_POLY_SLOTS, NODE_GLWE_AUTOMORPHISM, NODE_GLWE_KEYSWITCH, NODE_GLWE_POLY_LINEAR,
+                           NODE_GLWE_TRACE, NODE_LWE_LINEAR, NODE_PACK, NODE_PUFKS, NODE_ROT_CMUX, NODE_UNPACK)
+from tests import glwe_poly_cases as GC
 from tests.blind_rotation_graph_cases import random_selectors
 from tests.circuit_model import kind_name, planned_levels
+from tests.glwe_keyswitch_cases import OTHER_RADIX
 from tests.lwe_linear_cases import class_weights
 
 PROFILES = ("full", "pushable", "small")
 CMUX_WIDTHS = (1, 2, 3, 5, 40, 70, 260, 300)           # test_gpu_fuzz.py's list: both CMUX kernels of the tuned context
 _WIDTH_SETS = ((260, 2, 5), (40, 70, 3), (300, 1))      # by seed % 3: three consecutive seeds draw every width
-MAX_NODES = 620                                         # "about 400" and the ~165 nodes of LINEAR_PATTERNS (rows are nodes)
-MAX_NODES_SMALL = 66                                    # ... and a 9-row and a 2-row layer with their user
+MAX_NODES = 850                                         # "about 400", the ~165 nodes of LINEAR_PATTERNS (rows are nodes) and the
+#                                                         ~225 of GLWE_PATTERNS (620 before the GLWE section)
+MAX_NODES_SMALL = 76                                    # ... a 9-row and a 2-row layer with their user; a 5-row and a 1-row
+#                                                         polynomial layer and a node of each keyswitch mode (66 before)
 MAX_BOOTSTRAPS = 16                                     # of each of the three kinds
 
 DEFAULT_CASES, DEFAULT_SEED = 3, 20260701               # of tests/test_gpu_graph_fuzz.py (SPF_FUZZ_CASES / SPF_FUZZ_SEED)
@@ -102,6 +109,89 @@ def draw_linear_slots(linear_seed) -> dict:
     return out
 
 
+# ---- the plaintext polynomial linear map (spf_graph_add_glwe_poly_linear) and the GLWE keyswitch, automorphism round and trace
+# (spf_graph_add_glwe_keyswitch / _automorphism / _trace).  "in place" and "scattered" as above: in place is claimed for ALL operand
+# rows of the node's whole group (`_View.in_place`), scattered rests on a repeat or a descending pair (`_View.scattered`)
+GLWE_KS_KINDS = (NODE_GLWE_KEYSWITCH, NODE_GLWE_AUTOMORPHISM, NODE_GLWE_TRACE)
+GLWE_MODES = (("keyswitch", NODE_GLWE_KEYSWITCH), ("automorphism", NODE_GLWE_AUTOMORPHISM), ("trace", NODE_GLWE_TRACE))
+_MODE_LAYOUTS = ("in_place_over_a_cmux_group", "in_place_over_a_pack_group", "in_place_over_a_polynomial_layer",
+                 "in_place_over_rotation_chains", "in_place_over_its_own_mode", "scattered_with_a_repeat", "scattered_descending",
+                 "group_of_1", "group_of_4", "group_of_5")
+_MODE_LAYOUTS_WITH_POLY = ("in_place_over_a_polynomial_layer",)        # what a circuit without polynomial layers cannot hold
+GLWE_KS_PATTERNS = tuple(f"glwe_{mode}_{layout}" for mode, _ in GLWE_MODES for layout in _MODE_LAYOUTS) + (
+    "glwe_two_keyswitch_slots_on_one_level", "glwe_other_radix_slot_and_trace_radix_slot_on_one_level",
+    "glwe_two_automorphism_rounds_on_one_level", "glwe_all_three_modes_over_one_operand_on_one_level",
+    "glwe_automorphism_round_1", "glwe_automorphism_round_log2_n", "glwe_last_keyswitch_group_scattered",
+    "glwe_result_as_unpack_source", "glwe_result_into_a_sample_extract_and_a_keyswitch", "glwe_result_as_pack_operand",
+    "glwe_results_as_cmux_low_and_high", "glwe_result_as_rotation_accumulator", "glwe_result_as_univariate_table",
+    "glwe_result_as_bivariate_table", "glwe_input_reaches_the_outputs_through_the_new_kinds_only")
+GLWE_POLY_PATTERNS = (
+    "poly_in_place_over_a_cmux_group", "poly_in_place_over_a_pack_group", "poly_in_place_over_a_previous_layer",
+    "poly_in_place_over_a_keyswitch_group", "poly_two_layers_in_place", "poly_scattered_previous_layer_permuted",
+    "poly_scattered_operand_repeated", "poly_scattered_three_levels_inputs_and_constants",
+    "poly_two_layers_one_consecutive_one_scattered", "poly_two_slots_of_one_shape_on_one_level",
+    "poly_constants_only_in_place", "poly_constants_only_scattered", "poly_general_in_place", "poly_general_scattered",
+    "poly_empty_matrix_with_a_bias", "poly_shape_1_1", "poly_follows_a_cmux_on_a_moved_circuit_bootstrap", "poly_layer_partly_used",
+    "poly_row_is_an_output_and_has_users", "poly_over_results_of_the_keyswitch_family", "poly_last_group_in_place_general",
+    "glwe_sample_extract_users_on_two_levels", "glwe_pulls_a_sample_extract_up")
+GLWE_PATTERNS = GLWE_KS_PATTERNS + GLWE_POLY_PATTERNS
+PATTERNS += GLWE_PATTERNS
+# what `pushable` holds of them: no polynomial layer (no submit by handle), so nothing that needs one, nor an LWE linear layer
+GLWE_PUSHABLE_PATTERNS = tuple(n for n in GLWE_KS_PATTERNS if not n.endswith(_MODE_LAYOUTS_WITH_POLY))
+
+# keyswitch-key slots: two at the context's trace radix, one at another radix (the generic kernel inside a tuned graph); ids 0 and last
+K_A, K_OTHER, K_B = 0, 9, GLWE_KSK_SLOTS - 1
+GLWE_KSK_TABLE = (K_A, K_OTHER, K_B)
+# polynomial weight slots: (slot, M, K, class, bias).  M below, at and above GLWE_POLY_VT = 4, K on and off the stream kernel's
+# unroll of 4 (glwe_poly_graph_cases.SCATTERED_SHAPES); P_A / P_B and P_ONE / P_UNIT and P_ROW / P_EMPTY are pairs of one shape
+# (P_A is the last slot id: of the polynomial groups of a level, its groups are the last in key order, so the last to be launched)
+P_EMPTY, P_B, P_ONE, P_UNIT, P_ROW, P_WIDE, P_TALL, P_A = 0, 1, 5, 17, 22, 40, 51, GLWE_POLY_SLOTS - 1
+GLWE_POLY_TABLE = (
+    (P_A, 4, 4, "general", True), (P_B, 4, 4, "constants", False), (P_ONE, 1, 1, "general", False), (P_UNIT, 1, 1, "constants", True),
+    (P_ROW, 1, 5, "constants", False), (P_WIDE, 5, 7, "general", True), (P_TALL, 9, 2, "general", False), (P_EMPTY, 1, 5, "empty", True))
+GLWE_POLY_SHAPE = {slot: (M, K) for slot, M, K, _, _ in GLWE_POLY_TABLE}
+GLWE_POLY_CLASS = {slot: cls for slot, _, _, cls, _ in GLWE_POLY_TABLE}
+
+
+def other_radix_of(P) -> tuple:
+    """(radix_log, radix_count) of slot K_OTHER: glwe_keyswitch_cases.OTHER_RADIX on the tuned shape (the hand-written kernel
+    serves the trace radix alone there), elsewhere any radix that is not the trace's"""
+    if (P.N, P.k) == (2048, 1):
+        return OTHER_RADIX
+    return (4, 3) if (P.tr_radix_log, P.tr_count) != (4, 3) else (5, 2)
+
+
+def draw_glwe_ksk_slots(key_seed, P, other_radix=None) -> dict:
+    """{slot: (words uint64 (k, L, k+1, N), radix_log, radix_count)} for GLWE_KSK_TABLE: K_A and K_B at the context's trace radix
+    with different words, K_OTHER at `other_radix` (`other_radix_of(P)` unless given).  Uniform words: parity needs no honest key
+    (pbs_graph_cases.pufks_key).  Only the contents depend on `key_seed`"""
+    trace = (P.tr_radix_log, P.tr_count)
+    out = {}
+    for slot, (lg, cnt) in ((K_A, trace), (K_OTHER, other_radix or other_radix_of(P)), (K_B, trace)):
+        words = np.random.default_rng([0x6A9, int(key_seed), slot, P.N, P.k]).integers(0, 1 << 64, (P.k, cnt, P.k + 1, P.N), dtype=np.uint64)
+        out[slot] = (words, int(lg), int(cnt))
+    return out
+
+
+def draw_glwe_poly_slots(poly_seed, N) -> dict:
+    """{slot: (CSR triple, bias uint64 (M, N) or None, (M, K))} for GLWE_POLY_TABLE.  "general": exponents from
+    glwe_poly_cases.seam_exponents(N), and polynomial (0, 0) holds every seam exponent and every EXTREME_COEFFICIENT;
+    "constants": exponent 0 only (the stream kernels), the extreme coefficients planted likewise; "empty": no term at all.
+    The shapes, the classes and which slots have a bias are fixed, the contents are drawn from `poly_seed`"""
+    seams, cs = GC.seam_exponents(N), GC.EXTREME_COEFFICIENTS
+    out = {}
+    for slot, M, K, cls, bias in GLWE_POLY_TABLE:
+        seed = 64 * int(poly_seed) + slot
+        if cls == "empty":
+            polys = [[[] for _ in range(K)] for _ in range(M)]
+        else:
+            polys = GC.random_polys(seed, M, K, N, terms=3 if cls == "general" else 2, cls="seams" if cls == "general" else "constants")
+            exps = seams if cls == "general" else [0]
+            polys[0][0] = polys[0][0][:1] + [(exps[i % len(exps)], cs[i % len(cs)]) for i in range(max(len(exps), len(cs)))]
+        out[slot] = (GC.csr(polys, M, K), GC.random_bias(seed, M, N) if bias else None, (M, K))
+    return out
+
+
 def words_of(P, kind) -> int:
     return {L0: P.lwe_n + 1, L1: P.k * P.N + 1, GL: P.glwe_len, GG: 2 * P.cbs_ggsw_fft_len, GV: P.cbs_count * P.glwe_len}[ValueKind(kind)]
 
@@ -135,7 +225,10 @@ def group_key(rec, levels, i):
     if op == NODE_LWE_LINEAR:       # K | M << 32 | slot << 48 | kind << 56
         slot, rows = rec.linear_of(i)
         return levels[i], op, len(rec.inputs[i]) | rows << 32 | slot << 48 | rec.kind[i] << 56
-    return levels[i], op, rec.param[i]
+    if op == NODE_GLWE_POLY_LINEAR:  # the same packing; the kind is GLWE1
+        slot, rows = rec.linear_of(i)
+        return levels[i], op, len(rec.inputs[i]) | rows << 32 | slot << 48 | int(GL) << 56
+    return levels[i], op, rec.param[i]      # (GLWE keyswitch: the slot, automorphism: the round, trace: 0)
 
 
 def groups_of(rec, levels) -> dict:
@@ -151,6 +244,8 @@ class _Builder:
     def __init__(self, seed, P, profile):
         self.P, self.profile = P, profile
         self.rng = np.random.default_rng([0x6A5, seed, P.N, P.k, P.lwe_n, PROFILES.index(profile)])
+        # the GLWE section's own generator: what it draws leaves every draw of the sections before it as it was
+        self.grng = np.random.default_rng([0x6A8, seed, P.N, P.k, P.lwe_n, PROFILES.index(profile)])
         self.rec = RecordedCircuit(P.N)
         self.pool = {k: [] for k in ValueKind}
         self.claims = []        # (name, f(view) -> bool)
@@ -196,6 +291,31 @@ class _Builder:
         M, K = LINEAR_SHAPE[slot]
         assert len(nodes) == K, (slot, K, len(nodes))
         return [self._note(r) for r in self.rec.add_lwe_linear(slot, nodes, M)]
+
+    def poly_linear(self, slot, nodes):
+        """one polynomial layer of weight slot `slot` -> its M row nodes"""
+        M, K = GLWE_POLY_SHAPE[slot]
+        assert len(nodes) == K, (slot, K, len(nodes))
+        return [self._note(r) for r in self.rec.add_glwe_poly_linear(slot, nodes, M)]
+
+    def glwe_keyswitch(self, slot, node):
+        return self._note(self.rec.add_glwe_keyswitch(slot, node))
+
+    def glwe_automorphism(self, round, node):
+        return self._note(self.rec.add_glwe_automorphism(round, node))
+
+    def glwe_trace(self, node):
+        return self._note(self.rec.add_glwe_trace(node))
+
+    def glwe_node(self, kind, param, node):
+        """a node of one of GLWE_KS_KINDS"""
+        if kind == NODE_GLWE_KEYSWITCH:
+            return self.glwe_keyswitch(param, node)
+        return self.glwe_automorphism(param, node) if kind == NODE_GLWE_AUTOMORPHISM else self.glwe_trace(node)
+
+    def ginp(self, kind):
+        """an input whose contents come from the GLWE section's generator"""
+        return self._note(self.rec.add_input(kind, random_value(self.grng, self.P, kind)))
 
     def rotation(self, acc, sels, log_stride=0):
         first = len(self.rec.op)
@@ -261,13 +381,16 @@ class _View:
         return any(self.position(b) <= self.position(a) for a, b in zip(nodes, nodes[1:]))
 
     def linear_operands(self, node):
-        """the operand rows of the whole group of a linear node, layer-major as plan() collects them"""
+        """the operand rows of the whole group of a linear or polynomial linear node, layer-major as plan() collects them; of a GLWE
+        keyswitch, automorphism or trace node: one per member"""
         members = self.groups[self.key(node)]
+        if self.rec.op[node] in GLWE_KS_KINDS:
+            return [self.rec.inputs[m][0] for m in members]
         M = self.rec.linear_of(node)[1]
         return [j for q in range(0, len(members), M) for j in self.rec.inputs[members[q]]]
 
     def in_place(self, node):
-        """the linear node's group reads its operands where they lie"""
+        """the node's group (linear, polynomial linear, GLWE keyswitch family) reads its operands where they lie"""
         ops = self.linear_operands(node)
         return all(self.rec.op[j] >= 0 for j in ops) and self.rows(ops)
 
@@ -477,6 +600,181 @@ def _draw_full(b, with_pufks, pufks_kind, width_set):
         b.claim("unpack_source_is_a_keyswitch_node", lambda v: rec.op[rec.inputs[as_source[0]][0]] == NODE_PUFKS)
         # ---- plaintext linear maps: like the keyswitch above they have no submit by handle, so `pushable` draws none
         _draw_linear(b, s, t, G, uni_one, base, levels, p_mid, ValueKind(pufks_kind))
+    # ---- polynomial linear maps and the GLWE keyswitch family, from a generator of their own: `pushable` draws the three modes
+    # (submits by handle since the pool learned them) and no polynomial layer (there is no submit by handle for one)
+    if b.glwe:
+        _draw_glwe(b, s, t, levels[0], base, (x_chain, y_chain), cbs_early, p_mid, with_poly=with_pufks)
+
+
+def _draw_glwe(b, s, t, cmux0, base, chains, cbs_early, p_mid, with_poly):
+    """every name of GLWE_PATTERNS (`with_poly`: else GLWE_PUSHABLE_PATTERNS), drawn last.  Nothing here lengthens the graph, no
+    bootstrap with a user is added, and the two table bootstraps it adds are ready late and have no users (the slack pass takes
+    its leads by latest level, so they lead nobody).  Every layout of a mode stands on a level of its own — (level, operation,
+    parameter) is the group key, and a trace has no parameter — so that each claim is about ONE whole group:
+      1 over inputs, one of them twice       2 over a pack group (5), other slots / rounds over four of those rows
+      3 over the last steps of two rotation chains      4 over two rows of one group in descending order
+      5 over four rows of the widest CMUX level         6 over the level-5 group of the same mode
+      7 one node of each mode over ONE node             9 over two rows of a 9-row polynomial layer (level 8)
+      top: one scattered keyswitch group, and one polynomial layer in place (the last polynomial group in key order: its slot is
+      the last id), over four XORs made for them"""
+    P, rec, rng = b.P, b.rec, b.grng
+    G, S = s[GL], s[GG]
+    log_n = P.N.bit_length() - 1
+    top = max(b.lvl)
+    assert top >= 10 and len(cmux0) >= 16 and all(b.lvl[i] == 3 for i in base[:2]), (top, len(cmux0))
+    KSW, AUT, TRC = GLWE_KS_KINDS
+    x_chain, y_chain = chains
+    only = b.ginp(GL)                                       # an input that reaches the outputs through the new kinds only
+    packs = [b.pack([G[(i + j) % 6] for j in range(3)]) for i in range(5)]      # level 1: one group of five
+    at = 2 + int(rng.integers(0, len(cmux0) - 14))          # twelve successive rows of the widest CMUX level
+
+    def par(kind):
+        """a drawn parameter: one of the two trace-radix slots, any round, nothing"""
+        return (K_A, K_B)[int(rng.integers(0, 2))] if kind == KSW else int(rng.integers(1, log_n + 1)) if kind == AUT else 0
+
+    def group(kind, param, operands):
+        return [b.glwe_node(kind, param, x) for x in operands]
+
+    def whole_in_place(nodes, op=None):
+        return lambda v: v.whole_group(nodes) and v.in_place(nodes[0]) and (op is None or all(rec.op[rec.inputs[n][0]] == op for n in nodes))
+
+    lv = {}                                                 # mode -> {level: its group}
+    for mode, kind in GLWE_MODES:
+        g = lv[mode] = {}
+        g[1] = group(kind, par(kind), [G[0], only, only, G[5]])
+        g[2] = group(kind, {KSW: K_A, AUT: 1, TRC: 0}[kind], packs)
+        g[3] = group(kind, par(kind), [x_chain[-1], y_chain[-1]])
+        g[4] = group(kind, par(kind), [base[1], base[0]])
+        g[5] = group(kind, par(kind), cmux0[at:at + 4])
+        g[6] = group(kind, par(kind), g[5])
+        b.claim(f"glwe_{mode}_scattered_with_a_repeat", lambda v, n=g[1]: v.whole_group(n) and v.scattered(v.linear_operands(n[0]))
+                and len(set(v.linear_operands(n[0]))) < len(n))
+        b.claim(f"glwe_{mode}_in_place_over_a_pack_group", whole_in_place(g[2], NODE_PACK))
+        b.claim(f"glwe_{mode}_group_of_5", lambda v, n=g[2]: v.whole_group(n) and len(n) == 5)
+        b.claim(f"glwe_{mode}_in_place_over_rotation_chains", whole_in_place(g[3], NODE_ROT_CMUX))
+        b.claim(f"glwe_{mode}_scattered_descending", lambda v, n=g[4]: v.whole_group(n) and len(set(v.linear_operands(n[0]))) == len(n)
+                and v.position(rec.inputs[n[1]][0]) < v.position(rec.inputs[n[0]][0]))
+        b.claim(f"glwe_{mode}_in_place_over_a_cmux_group", whole_in_place(g[5], int(FheOp.CMux)))
+        b.claim(f"glwe_{mode}_group_of_4", lambda v, n=g[5]: v.whole_group(n) and len(n) == 4)
+        b.claim(f"glwe_{mode}_in_place_over_its_own_mode", whole_in_place(g[6], kind))
+    # further slots and rounds on level 2, over four of the five pack rows; the other-radix slot scattered on level 1 as well
+    ks_b, ks_other, au_last = group(KSW, K_B, packs[1:]), group(KSW, K_OTHER, packs[:4]), group(AUT, log_n, packs[1:])
+    other_scattered = group(KSW, K_OTHER, [G[3], G[1], G[3]])
+    b.claim("glwe_two_keyswitch_slots_on_one_level", lambda v: v.level[ks_b[0]] == v.level[lv["keyswitch"][2][0]] and whole_in_place(ks_b)(v)
+            and whole_in_place(lv["keyswitch"][2])(v))
+    b.claim("glwe_other_radix_slot_and_trace_radix_slot_on_one_level", lambda v: v.level[ks_other[0]] == v.level[ks_b[0]] and whole_in_place(ks_other)(v)
+            and v.whole_group(other_scattered) and v.scattered(v.linear_operands(other_scattered[0])))
+    b.claim("glwe_two_automorphism_rounds_on_one_level", lambda v: v.level[au_last[0]] == v.level[lv["automorphism"][2][0]] and whole_in_place(au_last)(v)
+            and (log_n == 1 or rec.param[au_last[0]] != rec.param[lv["automorphism"][2][0]]))
+    b.claim("glwe_automorphism_round_1", lambda v: rec.param[lv["automorphism"][2][0]] == 1)
+    b.claim("glwe_automorphism_round_log2_n", lambda v: rec.param[au_last[0]] == log_n)
+    # one node of each mode over ONE node, the first row of the trace of traces
+    x_one = lv["trace"][6][0]
+    one = {mode: group(kind, par(kind), [x_one]) for mode, kind in GLWE_MODES}
+    for mode, _ in GLWE_MODES:
+        b.claim(f"glwe_{mode}_group_of_1", lambda v, n=one[mode]: v.whole_group(n))
+    b.claim("glwe_all_three_modes_over_one_operand_on_one_level", lambda v: len({v.level[n[0]] for n in one.values()}) == 1
+            and {rec.inputs[n[0]] for n in one.values()} == {(x_one,)})
+    b.claim("glwe_input_reaches_the_outputs_through_the_new_kinds_only", lambda v: v.users[only] and all(rec.op[u] in GLWE_KS_KINDS + (NODE_GLWE_POLY_LINEAR,) for u in v.users[only]))
+
+    # ---- the last launches: four XORs on the level below the top, made last of their group, so successive rows
+    x = one["automorphism"][0]
+    while b.lvl[x] < top - 2:
+        x = b.op(FheOp.Not, [x])
+    raised = [b.op(FheOp.GlweAdd, [x, G[i]]) for i in range(4)]
+    last_ks = group(KSW, K_A, [raised[2], raised[0], raised[2]])
+    b.claim("glwe_last_keyswitch_group_scattered", lambda v: v.whole_group(last_ks) and v.scattered(v.linear_operands(last_ks[0]))
+            and v.level[last_ks[0]] > max(v.level[i] for i, op in enumerate(rec.op) if op in GLWE_KS_KINDS and i not in last_ks))
+
+    # ---- consumers of the new rows
+    tr1, tr2, ks1, au1 = lv["trace"][1], lv["trace"][2], lv["keyswitch"][1], lv["automorphism"][1]
+    bits = b.unpack(tr2[0], 2)
+    se_two = b.op(FheOp.SampleExtract, [tr2[1]], int(rng.integers(0, P.N)))
+    ks_of_se = b.op(FheOp.KeyswitchL1toL0, [se_two])
+    packed = b.pack([tr1[0], ks1[0], au1[1]])
+    cm = b.op(FheOp.CMux, [S[0], ks1[1], au1[2]])
+    rot = b.rotation(tr1[3], [S[1]])
+    p_free = 40 if p_mid != 40 else 41          # plaintext bits of a bivariate group of its own (0, 63, p_mid and 1 .. 3 are taken)
+    uni = b.op(TableOp.PBS_UNIVARIATE, [s[L0][0], tr2[2]])
+    biv = b.op(TableOp.PBS_BIVARIATE, [s[L0][1], s[L0][0], lv["automorphism"][2][0]], p_free)
+    b.keep += [ks_of_se, packed, cm, rot[-1], uni, biv] + bits
+    is_new = lambda n: rec.op[n] in GLWE_KS_KINDS
+    b.claim("glwe_result_as_unpack_source", lambda v: is_new(rec.inputs[bits[0]][0]))
+    b.claim("glwe_result_into_a_sample_extract_and_a_keyswitch", lambda v: is_new(rec.inputs[se_two][0]) and rec.inputs[ks_of_se] == (se_two,))
+    b.claim("glwe_result_as_pack_operand", lambda v: all(is_new(n) for n in rec.inputs[packed]) and len({rec.op[n] for n in rec.inputs[packed]}) == 3)
+    b.claim("glwe_results_as_cmux_low_and_high", lambda v: all(is_new(n) for n in rec.inputs[cm][1:]))
+    b.claim("glwe_result_as_rotation_accumulator", lambda v: rec.op[rot[0]] == NODE_ROT_CMUX and is_new(rec.inputs[rot[0]][1]))
+    b.claim("glwe_result_as_univariate_table", lambda v: is_new(rec.inputs[uni][1]))
+    b.claim("glwe_result_as_bivariate_table", lambda v: is_new(rec.inputs[biv][2]) and v.whole_group([biv]))
+    if not with_poly:
+        return
+
+    # ---- polynomial layers
+    layer = b.poly_linear
+    slot_of = lambda nodes: rec.linear_of(nodes[0])[0]
+    cls_of = lambda nodes: GLWE_POLY_CLASS[slot_of(nodes)]
+    q_pack = layer(P_B, packs[:4])                                              # level 2
+    q_rows = [layer(P_ROW, packs), layer(P_ROW, [packs[4], packs[1], packs[0], packs[2], packs[2]])]
+    q_prev, q_ks = layer(P_A, q_pack), layer(P_B, au_last)                      # level 3
+    q_empty = layer(P_EMPTY, [q_pack[3], q_pack[0], tr2[1], G[1], q_pack[0]])
+    perm = [q_prev[int(i)] for i in rng.permutation(4)]
+    if perm == q_prev:
+        perm = perm[::-1]
+    q_perm, q_twice = layer(P_A, perm), layer(P_B, [q_prev[0], q_prev[1], q_prev[1], q_prev[3]])      # level 4
+    q_two = [layer(P_A, cmux0[at:at + 4]), layer(P_A, cmux0[at + 4:at + 8])]  # level 5
+    q_cmux = layer(P_B, cmux0[at + 8:at + 12])
+    q_mixed = layer(P_WIDE, [cmux0[at], q_pack[2], G[4], t[GL, 1], t[GL, 0], packs[3], only])
+    q_one = layer(P_ONE, [x_one])                                               # level 7
+    mul = b.op(FheOp.MultiplyGgswGlwe, [cbs_early, G[0]])   # ready early; runs behind the moved circuit bootstrap
+    q_moved = layer(P_UNIT, [mul])
+    q_tall = layer(P_TALL, [one["keyswitch"][0], one["trace"][0]])              # level 8: rows 0 and 1 are read, the rest is dead
+    over_tall = {mode: group(kind, par(kind), q_tall[:2]) for mode, kind in GLWE_MODES}  # level 9
+    q_last = layer(P_A, raised)                                                 # the top
+    b.dead |= set(q_tall[2:])
+    b.keep += q_pack
+    for mode, _ in GLWE_MODES:
+        b.claim(f"glwe_{mode}_in_place_over_a_polynomial_layer", whole_in_place(over_tall[mode], NODE_GLWE_POLY_LINEAR))
+    b.claim("poly_in_place_over_a_pack_group", lambda v: whole_in_place(q_pack, NODE_PACK)(v))
+    b.claim("poly_in_place_over_a_previous_layer", lambda v: v.whole_group(q_prev) and v.in_place(q_prev[0]) and rec.inputs[q_prev[0]] == tuple(q_pack))
+    b.claim("poly_in_place_over_a_keyswitch_group", lambda v: v.whole_group(q_ks) and v.in_place(q_ks[0]) and all(is_new(n) for n in rec.inputs[q_ks[0]]))
+    b.claim("poly_in_place_over_a_cmux_group", lambda v: v.whole_group(q_cmux) and v.in_place(q_cmux[0]) and all(rec.op[n] == int(FheOp.CMux) for n in rec.inputs[q_cmux[0]]))
+    b.claim("poly_two_layers_in_place", lambda v: v.whole_group(q_two[0] + q_two[1]) and v.in_place(q_two[0][0]) and v.rows(cmux0[at:at + 8]))
+    b.claim("poly_scattered_previous_layer_permuted", lambda v: v.whole_group(q_perm) and v.scattered(rec.inputs[q_perm[0]])
+            and sorted(rec.inputs[q_perm[0]]) == q_prev)
+    b.claim("poly_scattered_operand_repeated", lambda v: v.whole_group(q_twice) and v.scattered(rec.inputs[q_twice[0]])
+            and len(set(rec.inputs[q_twice[0]])) == 3)
+    b.claim("poly_scattered_three_levels_inputs_and_constants", lambda v: v.whole_group(q_mixed) and v.scattered(rec.inputs[q_mixed[0]])
+            and len({v.level[j] for j in rec.inputs[q_mixed[0]]}) >= 4 and {rec.op[j] for j in rec.inputs[q_mixed[0]]} >= {-1, -2}
+            and {(rec.kind[j], rec.param[j]) for j in rec.inputs[q_mixed[0]] if rec.op[j] == -2} == {(int(GL), 0), (int(GL), 1)})
+    b.claim("poly_two_layers_one_consecutive_one_scattered", lambda v: v.whole_group(q_rows[0] + q_rows[1]) and v.rows(list(rec.inputs[q_rows[0][0]]))
+            and v.scattered(rec.inputs[q_rows[1][0]]) and not v.in_place(q_rows[0][0]))
+    b.claim("poly_two_slots_of_one_shape_on_one_level", lambda v: v.level[q_prev[0]] == v.level[q_ks[0]] and slot_of(q_prev) != slot_of(q_ks)
+            and GLWE_POLY_SHAPE[slot_of(q_prev)] == GLWE_POLY_SHAPE[slot_of(q_ks)] and v.whole_group(q_prev) and v.whole_group(q_ks))
+    b.claim("poly_constants_only_in_place", lambda v: cls_of(q_pack) == "constants" and v.in_place(q_pack[0]))
+    b.claim("poly_general_in_place", lambda v: cls_of(q_prev) == "general" and v.in_place(q_prev[0]))
+    b.claim("poly_constants_only_scattered", lambda v: cls_of(q_twice) == "constants" and v.scattered(v.linear_operands(q_twice[0])))
+    b.claim("poly_general_scattered", lambda v: cls_of(q_perm) == "general" and v.scattered(v.linear_operands(q_perm[0])))
+    b.claim("poly_empty_matrix_with_a_bias", lambda v: cls_of(q_empty) == "empty" and v.whole_group(q_empty) and v.scattered(rec.inputs[q_empty[0]]))
+    b.claim("poly_shape_1_1", lambda v: GLWE_POLY_SHAPE[slot_of(q_one)] == (1, 1) and v.whole_group(q_one) and v.in_place(q_one[0]))
+    b.claim("poly_follows_a_cmux_on_a_moved_circuit_bootstrap", lambda v: v.asap[cbs_early] + 2 <= v.level[cbs_early] == v.level[mul] - 1
+            and v.level[q_moved[0]] == v.level[mul] + 1 > v.asap[q_moved[0]] and v.whole_group(q_moved))
+    b.claim("poly_layer_partly_used", lambda v: len(q_tall) == 9 and all(v.users[n] for n in q_tall[:2])
+            and not any(v.users[n] or n in rec.outputs for n in q_tall[2:]))
+    b.claim("poly_row_is_an_output_and_has_users", lambda v: all(n in rec.outputs and v.users[n] for n in q_pack))
+    b.claim("poly_over_results_of_the_keyswitch_family", lambda v: {rec.op[n] for n in rec.inputs[q_tall[0]]} == {KSW, TRC})
+    b.claim("poly_last_group_in_place_general", lambda v: cls_of(q_last) == "general" and v.whole_group(q_last) and v.in_place(q_last[0])
+            and v.key(q_last[0]) == max(v.key(i) for i, op in enumerate(rec.op) if op == NODE_GLWE_POLY_LINEAR))
+
+    # ---- sample extracts of trace results next to the LWE linear layers (profile `full` has their weight slots): one with users
+    # on two levels, and one that is ready on level 2 and first used by a layer above level 7, created right after a late head of
+    # its own group — the layer's two rows are consecutive only because the head was pulled up
+    index = int(rng.integers(0, P.N))
+    deep, early = b.op(FheOp.SampleExtract, [lv["trace"][6][1]], index), b.op(FheOp.SampleExtract, [tr1[1]], index)
+    pulled = b.linear(S_PAIR, [deep, early])
+    both = b.linear(S_TWICE, [se_two, deep])
+    b.claim("glwe_sample_extract_users_on_two_levels", lambda v: len(v.user_levels(se_two)) > 1 and is_new(rec.inputs[se_two][0]))
+    b.claim("glwe_pulls_a_sample_extract_up", lambda v: v.asap[early] + 2 <= v.level[pulled[0]] and v.level[early] == v.level[pulled[0]] - 1
+            and v.level[pulled[0]] == min(v.user_levels(early)) and v.whole_group(pulled) and v.in_place(pulled[0]) and is_new(rec.inputs[early][0]))
 
 
 def _draw_linear(b, s, t, G, uni_one, base, cmux_levels, p_mid, pufks_kind):
@@ -620,17 +918,36 @@ def _draw_small(b, with_pufks, pufks_kind):
     b.keep += [first[0], second[1]] + ([b.op(FheOp.KeyswitchL1toL0, [second[0]])] if kind == L1 else [])
     b.claim("linear_scattered_operand_repeated", lambda v: v.whole_group(first) and v.scattered(b.rec.inputs[first[0]]))
     b.claim("linear_in_place_over_a_previous_layer", lambda v: v.whole_group(second) and v.in_place(second[0]))
+    if not b.glwe:
+        return
+    # a polynomial layer of five rows (above GLWE_POLY_VT) over seven scattered operands, the first of them twice, one row in place
+    # over those five, and a node of each keyswitch mode over their rows: a drawn slot (either radix), a drawn round, the trace
+    g = b.grng
+    ops = [vals[int(a)] for a in g.integers(0, len(vals), size=6)]
+    wide = b.poly_linear(P_WIDE, ops + [ops[0]])
+    row = b.poly_linear(P_ROW, wide)
+    new = [b.glwe_keyswitch(GLWE_KSK_TABLE[int(g.integers(0, 3))], row[0]), b.glwe_automorphism(int(g.integers(1, P.N.bit_length())), wide[1]),
+           b.glwe_trace(wide[2])]
+    b.keep += new + [wide[4]]
+    b.claim("poly_scattered_operand_repeated", lambda v: v.whole_group(wide) and v.scattered(b.rec.inputs[wide[0]]))
+    b.claim("poly_in_place_over_a_previous_layer", lambda v: v.whole_group(row) and v.in_place(row[0]))
 
 
-def draw_circuit(seed, P, profile, pufks_kind=None, linear_seed=None):
+def draw_circuit(seed, P, profile, pufks_kind=None, linear_seed=None, glwe=True, glwe_key_seed=None, glwe_poly_seed=None, glwe_other_radix=None):
     """-> (RecordedCircuit, facts).  facts: "patterns": the names of PATTERNS the circuit holds (claimed by the construction and
     confirmed on the planned levels); "refused": claimed but not confirmed; "pufks_kind": the operand kind
     of its public functional keyswitch nodes (drawn unless given; None without such nodes); "nodes" / "groups": counts by kind
     name; "linear_slots": the weight slots its linear nodes name, `draw_linear_slots(linear_seed)` (derived from `seed` unless
-    given: circuits that share an engine or a group are drawn with one `linear_seed`), None for `pushable`."""
+    given: circuits that share an engine or a group are drawn with one `linear_seed`), None for `pushable`.
+    glwe: draw the polynomial linear maps and the GLWE keyswitch family too (GLWE_PATTERNS); without it the circuit is, node for
+    node, what this generator drew before it knew them.  "glwe_ksk_slots": `draw_glwe_ksk_slots(glwe_key_seed, P, glwe_other_radix)`,
+    "glwe_poly_slots": `draw_glwe_poly_slots(glwe_poly_seed, P.N)` (None for `pushable`); both seeds derived from `seed` unless given."""
     assert profile in PROFILES
     linear_seed = 0x11EA0000 + seed if linear_seed is None else linear_seed
+    glwe_key_seed = 0x6B500000 + seed if glwe_key_seed is None else glwe_key_seed
+    glwe_poly_seed = 0x61E00000 + seed if glwe_poly_seed is None else glwe_poly_seed
     b = _Builder(seed, P, profile)
+    b.glwe = bool(glwe)
     with_pufks = profile != "pushable"
     if with_pufks and pufks_kind is None:
         pufks_kind = L0 if b.rng.random() < 0.7 else L1
@@ -651,4 +968,7 @@ def draw_circuit(seed, P, profile, pufks_kind=None, linear_seed=None):
         groups[name] = groups.get(name, 0) + 1
     return b.rec, {"patterns": sorted(held), "refused": sorted({n for n, _ in b.claims} - held), "pufks_kind": pufks_kind,
                    "nodes": nodes, "groups": groups, "levels": max(v.level), "seed": seed, "profile": profile,
-                   "linear_seed": linear_seed if with_pufks else None, "linear_slots": draw_linear_slots(linear_seed) if with_pufks else None}
+                   "linear_seed": linear_seed if with_pufks else None, "linear_slots": draw_linear_slots(linear_seed) if with_pufks else None,
+                   "glwe_key_seed": glwe_key_seed if glwe else None, "glwe_poly_seed": glwe_poly_seed if glwe and with_pufks else None,
+                   "glwe_ksk_slots": draw_glwe_ksk_slots(glwe_key_seed, P, glwe_other_radix) if glwe else None,
+                   "glwe_poly_slots": draw_glwe_poly_slots(glwe_poly_seed, P.N) if glwe and with_pufks else None}

@@ -32,13 +32,15 @@ def read(*path):
         return f.read()
 
 
-def test_the_node_kinds_are_70_71_72_and_no_NODE_name_was_added():
-    """the random differential tests of gate graphs draw every NODE_* name of spf_amd.graph, and their generator cannot draw
-    keyswitch keys: the new kinds carry other names until it can"""
+def test_the_node_kinds_are_70_71_72_under_their_NODE_names_and_their_earlier_names():
+    """the random differential tests of gate graphs draw every NODE_* name of spf_amd.graph; since their generator draws keyswitch
+    keys the kinds are NODE_GLWE_KEYSWITCH / _AUTOMORPHISM / _TRACE, and the earlier names stay as aliases"""
     import spf_amd.graph as graph
     assert (GLWE_KEYSWITCH_NODE, GLWE_AUTOMORPHISM_NODE, GLWE_TRACE_NODE) == (70, 71, 72)
+    assert (graph.NODE_GLWE_KEYSWITCH, graph.NODE_GLWE_AUTOMORPHISM, graph.NODE_GLWE_TRACE) == (70, 71, 72)
     names = {n: getattr(graph, n) for n in dir(graph) if n.startswith("NODE_")}
-    assert names == {"NODE_UNPACK": 64, "NODE_PACK": 65, "NODE_ROT_CMUX": 66, "NODE_PUFKS": 67, "NODE_LWE_LINEAR": 68}
+    assert names == {"NODE_UNPACK": 64, "NODE_PACK": 65, "NODE_ROT_CMUX": 66, "NODE_PUFKS": 67, "NODE_LWE_LINEAR": 68,
+                     "NODE_GLWE_POLY_LINEAR": 69, "NODE_GLWE_KEYSWITCH": 70, "NODE_GLWE_AUTOMORPHISM": 71, "NODE_GLWE_TRACE": 72}
     assert GLWE_KSK_SLOTS == 16 and re.search(r"SPF_GLWE_KSK_SLOTS = 16\b", read("include", "spf_hip.h"))
     plan = read("spf_amd", "csrc", "spf_graph_plan.hpp")
     assert re.search(r"kNodeGlweKeyswitch = 70, kNodeGlweAutomorphism = 71, kNodeGlweTrace = 72\b", plan)

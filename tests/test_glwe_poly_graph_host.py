@@ -29,13 +29,14 @@ def circuit():
             rec.add_input(ValueKind.GGSW1, np.zeros(1)))
 
 
-def test_the_node_kind_is_69_and_no_NODE_name_was_added():
-    """the random differential tests of gate graphs draw every NODE_* name of spf_amd.graph (tests/test_graph_fuzz_host.py), and
-    their generator cannot draw polynomial weights yet: the new kind is GLWE_POLY_LINEAR_NODE until it can"""
+def test_the_node_kind_is_69_under_its_NODE_name_and_its_earlier_name():
+    """the random differential tests of gate graphs draw every NODE_* name of spf_amd.graph (tests/test_graph_fuzz_host.py); since
+    their generator draws polynomial weights the kind is NODE_GLWE_POLY_LINEAR, and GLWE_POLY_LINEAR_NODE stays as its alias"""
     import spf_amd.graph as graph
-    assert GLWE_POLY_LINEAR_NODE == 69
+    assert GLWE_POLY_LINEAR_NODE == graph.NODE_GLWE_POLY_LINEAR == 69
     names = {n: getattr(graph, n) for n in dir(graph) if n.startswith("NODE_")}
-    assert names == {"NODE_UNPACK": 64, "NODE_PACK": 65, "NODE_ROT_CMUX": 66, "NODE_PUFKS": 67, "NODE_LWE_LINEAR": 68}
+    assert names == {"NODE_UNPACK": 64, "NODE_PACK": 65, "NODE_ROT_CMUX": 66, "NODE_PUFKS": 67, "NODE_LWE_LINEAR": 68,
+                     "NODE_GLWE_POLY_LINEAR": 69, "NODE_GLWE_KEYSWITCH": 70, "NODE_GLWE_AUTOMORPHISM": 71, "NODE_GLWE_TRACE": 72}
     assert graph.GLWE_POLY_SLOTS == G.SLOTS == _ffi.GLWE_POLY_SLOTS and graph.GLWE_POLY_MAX_ROWS == G.MAX_ROWS == _ffi.GLWE_POLY_MAX_ROWS
 
 
