@@ -4,25 +4,23 @@
 // nodes) by spawning one rayon task per node as its operands become ready
 // (circuit_processor/mod.rs:130-253) and calling `Evaluation` with ONE ciphertext per task
 // (`exec_op`, :255-560).  On a GPU the same DAG is executed by topological level: all nodes of one
-// level and one kind become one batched launch, every intermediate value stays in HBM, and the whole
-// graph is enqueued on one HIP stream without a host round trip — inputs go up in one copy, outputs
-// come back at the end.  Operands of a level live wherever their producers wrote them: the CMUX
-// family reads them through a pointer table (`CmuxArgs::ptrs`; a 256 KiB GGSW per gate is not worth
-// copying), the small operands of the other kinds are packed by `gather_rows_kernel` unless they are
-// already contiguous (the common KeyswitchL1toL0 -> CircuitBootstrap chain).
+// level, one kind and one parameter are a *group* and become one batched launch, every intermediate value stays in HBM, and the
+// whole graph is enqueued on one HIP stream without a host round trip — inputs go up in one copy, outputs
+// come back at the end.
 //
-// Packed integers enter and leave a graph through two node constructors, as `PackedGenericInt::graph_input(..).unpack(..)` and
-// `.pack(..).collect_output(..)` do in the reference's fluent layer (fluent/packed_dynamic_generic_int_graph_node.rs:24-60,
-// fluent/dynamic_generic_int_graph_nodes.rs:139-200) — they are no `FheOp`s there and no spf_graph_op here.  Composed from
-// SampleExtract(i) / MulXN(i) / GlweAdd nodes, one 32-bit integer costs 32 + 31 launches and five more levels, because a level is
-// batched by parameter; spf_graph_add_unpack makes the n_bits LWEs of all integers of a level in ONE glwe_unpack_l1_kernel
-// launch, spf_graph_add_pack sums the rows of all packs of a level in ONE glwe_pack_rows_kernel launch that reads them where
-// they lie.
+// Operands of a group live wherever their producers wrote them, and a group reads each operand slot in one of two ways.  *In
+// place*: the rows lie consecutively in member order (the common KeyswitchL1toL0 -> CircuitBootstrap chain, the results of one
+// group feeding the next), and the batch entry point takes the first row's address.  *Through a pointer row* of the graph's
+// table: the CMUX family always (`CmuxArgs::ptrs`; a 256 KiB GGSW per gate is not worth copying); a kind that has a rows kernel
+// reads the table itself; the small operands of the others are packed into a stage buffer by `gather_rows_kernel` first.
 //
-// A blind rotation by an encrypted shift (`blind_rotation`, blind_rotation.rs:202-223) is a third constructor and no `FheOp` either:
-// spf_graph_add_blind_rotation creates one GLWE1 node per bit, acc' = cmux(bit, acc, X^-r * acc), whose high operand is a rotated
-// read of the low one — composed from MulXN(2N - r) + CMux nodes the same words cost two levels and two launches per bit.  All such
-// nodes of one level and one rotation are ONE launch over a pointer table (launch_cmux_rot_scattered), each writing its own row.
+// A node is a row of the operation table (spf_ops.hpp: the `FheOp`s and the bootstraps by a caller's table) or comes from one of
+// the nine node constructors, which are no `FheOp` in the reference and no spf_graph_op here: each stands for a composition that
+// would cost more levels and launches, because a level is batched by parameter.  What the planner knows of a constructor kind
+// is its row in spf_graph_plan.hpp's kNodeRows; what the executor knows is its launcher below (kNodeLaunchers, indexed like the
+// rows) and, where its groups need something that is loaded into the context, the check of that resource (kResourceChecks).  A
+// resource is read when the graph runs: it may be loaded, and loaded again, after the graph is built.  Each kind's particulars
+// — what it computes, its reference, its kernels — stand at its launcher and at its constructor.
 //
 // The bootstraps by a caller's table (SPF_OP_PBS_UNIVARIATE / SPF_OP_PBS_BIVARIATE: `programmable_bootstrap_univariate` / `_bivariate`,
 // programmable_bootstrapping.rs:291, 575-621) are rows of the operation table whose LAST operand is the table, a GLWE1 node.  A group
@@ -30,33 +28,6 @@
 // operand.  Bivariate inputs that do not lie consecutively are packed straight from where they lie (lwe_pack_rows_kernel: one launch
 // where two gathers and lwe_pack_kernel were three).  The slack rule (spf_graph_plan.hpp) batches each of the two kinds as it batches the circuit
 // bootstraps.
-//
-// A public functional keyswitch (`public_functional_keyswitch`, public_functional_keyswitch.rs:74-148, message j to coefficient j)
-// is a fourth constructor: spf_graph_add_public_functional_keyswitch packs lwe_count LWE nodes of one kind, from anywhere, into ONE
-// GLWE1 node — what brings the LWEs out of a bootstrap or a sample extract back into a packed integer or into CMUX-land.  All
-// such nodes of one level with one (lwe_count, kind) are one main launch (launch_pufks_rows; rows that lie consecutively take the
-// contiguous entry point).
-//
-// A plaintext linear map over LWE ciphertexts (spf_lwe_linear.hpp) is a fifth constructor: spf_graph_add_lwe_linear makes the M
-// rows of weight slot `slot` times K LWE nodes of one kind, from anywhere — what stands between two bootstraps by table (a layer,
-// then its activation).  All layers of one level with one (slot, M, K, kind) are one group whose output is [layers][M][W]; operand
-// rows that lie consecutively (the results of one bootstrap or keyswitch group, or of another layer) go to the batch dispatcher
-// in place, matrix cores included, anything else is ONE launch of lwe_linear_rows_kernel over a pointer table.  The slot is read
-// when the graph runs: it may be loaded, and loaded again, after the graph is built.
-//
-// A plaintext polynomial linear map over GLWE ciphertexts (spf_glwe_poly.hpp) is a sixth constructor, the same way:
-// spf_graph_add_glwe_poly_linear makes the M rows of polynomial weight slot `slot` times K GLWE1 nodes from anywhere — a packed
-// integer shifted and added to another one before it is unpacked, a lookup table that is a plaintext polynomial times an
-// encrypted GLWE.  All layers of one level with one (slot, M, K) are one group whose output is [layers][M][(k+1) N]; operand GLWEs
-// that lie consecutively go to the batch kernels in place, anything else is ONE launch of glwe_poly_lds_rows_kernel or
-// glwe_poly_stream_rows_kernel over a pointer table.  The slot is read when the graph runs, as a linear node's.
-//
-// The GLWE keyswitch, one automorphism round and the homomorphic trace (spf_glwe_keyswitch.hpp) are three more constructors over ONE
-// GLWE1 node from anywhere: spf_graph_add_glwe_keyswitch / _automorphism / _trace — a packed integer that changes its key, a GLWE
-// traced behind an X^-j polynomial map to isolate one coefficient.  All nodes of one level with one mode and one slot (or round) are
-// one group and ONE launch: operands that lie consecutively go to glwe_ks_kernel / generic_glwe_ks_kernel in place, anything else
-// to their rows twins over a pointer table.  The keyswitch-key slot is read when the graph runs; the automorphism key is the
-// context's, rewritten in place by a load, so a captured graph is kept over its reload as with circuit bootstrap nodes.
 //
 // What is decided before a device is touched — levels, groups and their order, arena offsets, in place or through a pointer row,
 // the order of the CMUX units, the size of the stage buffers — is spf_graph_plan.hpp's, free of HIP and checked on the CPU; here
@@ -135,9 +106,8 @@ struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
     // SPF_GRAPH_CAPTURE=1): captured on the second run after planning (the first one sizes the context's scratch buffers),
     // replayed afterwards; dropped when the graph is re-planned or a captured scratch buffer moved
     hipGraphExec_t exec = nullptr;
-    uint64_t exec_epoch = 0, exec_lin_epoch = 0; // (the second: the context's count of weight loads, for a graph with linear nodes)
-    uint64_t exec_gpoly_epoch = 0;               // (its count of polynomial weight loads, for a graph with polynomial linear nodes)
-    uint64_t exec_gksk_epoch = 0;                // (its count of GLWE keyswitch-key loads, for a graph with GLWE keyswitch nodes)
+    uint64_t exec_epoch = 0;
+    uint64_t exec_res_epoch[spf_graph_plan::kResources] = {}; // per resource: the context's count of its loads at the capture (kResourceEpochs)
     uint32_t runs_since_plan = 0, captured_launches = 0;
 
     void drop_exec()
@@ -162,13 +132,7 @@ struct spf_graph : spf_graph_plan::Graph, spf_graph_plan::Plan {
 
 namespace spf_graph_impl {
 
-using namespace spf_graph_plan; // (the node kinds, op_row, align_up, units_per_node)
-
-// GlweKsMode (spf_glwe_keyswitch.hpp) of a GLWE keyswitch, automorphism or trace node
-inline int glwe_ks_mode_of(int32_t op)
-{
-    return op == kNodeGlweKeyswitch ? GLWE_KS_KEYSWITCH : op == kNodeGlweAutomorphism ? GLWE_KS_AUTOMORPHISM : GLWE_KS_TRACE;
-}
+using namespace spf_graph_plan; // (the node kinds and their rows, op_row, align_up, units_per_node)
 
 // The plan of spf_graph_plan.hpp and its device memory.  Called by the first run after the graph changed.
 inline spf_status plan(spf_graph* g)
@@ -202,6 +166,180 @@ inline spf_status plan(spf_graph* g)
     return SPF_OK;
 }
 
+// ---- the constructor kinds: one launcher each, indexed like spf_graph_plan::kNodeRows ----------------------------------------------
+
+// A group of a constructor kind, resolved: its width, its output block, and operand slot 0 both ways — the first row in place
+// (meaningful when gr.contiguous[0]) and the pointer row of the table (when not)
+struct GroupLaunch {
+    spf_graph* g; spf_ctx* c; hipStream_t s;
+    const Group& gr;
+    size_t B; uint64_t* out;
+    const uint64_t* in; const uint64_t* const* rows;
+    spf_status launched(spf_status st) const // the status of a kind's one launch, counted when it was made
+    {
+        if (st == SPF_OK) g->n_launches++;
+        return st;
+    }
+};
+
+// Packed integers enter and leave a graph as `PackedGenericInt::graph_input(..).unpack(..)` and `.pack(..).collect_output(..)` do in
+// the reference's fluent layer (fluent/packed_dynamic_generic_int_graph_node.rs:24-60,
+// fluent/dynamic_generic_int_graph_nodes.rs:139-200).  Composed from SampleExtract(i) / MulXN(i) / GlweAdd nodes, one 32-bit
+// integer costs 32 + 31 launches and five more levels.  Unpack: the n_bits LWEs of all integers of a level in ONE
+// glwe_unpack_l1_kernel launch, behind a gather of the source GLWEs where they do not lie consecutively
+inline spf_status launch_unpack_group(const GroupLaunch& l)
+{
+    const size_t ints = l.B / l.gr.key.n;
+    const uint64_t* src = l.in;
+    if (!l.gr.contiguous[0]) {
+        src = (const uint64_t*)l.g->d_stage[0];
+        const spf_status st = l.launched(spf_gather_rows_dev(l.c, l.s, ints, value_bytes(l.g->prm, SPF_VAL_GLWE1) / 8, l.rows, (uint64_t*)l.g->d_stage[0]));
+        if (st != SPF_OK) return st;
+    }
+    return l.launched(launch_glwe_unpack(l.c, l.s, ints, l.gr.key.n, src, l.out));
+}
+
+// ... pack: the rows of all packs of a level summed in ONE glwe_pack_rows_kernel launch that reads them where they lie — always
+// through the table: the kernel has no other form
+inline spf_status launch_pack_group(const GroupLaunch& l)
+{
+    return l.launched(launch_glwe_pack_rows(l.c, l.s, l.B, l.gr.key.n, l.rows, l.out));
+}
+
+// One bit of a blind rotation by an encrypted shift (`blind_rotation`, blind_rotation.rs:202-223): acc' = cmux(bit, acc, X^-r * acc),
+// whose high operand is a rotated read of the low one — composed from MulXN(2N - r) + CMux nodes the same words cost two levels
+// and two launches per bit.  All such nodes of one level and one rotation are ONE launch over the units of the table
+// (launch_cmux_rot_scattered), each writing its own row
+inline spf_status launch_rot_cmux_group(const GroupLaunch& l)
+{
+    return l.launched(launch_cmux_rot_scattered(l.c, l.s, l.B, (uint32_t)l.gr.key.n, (const void* const*)l.rows));
+}
+
+// The public functional keyswitch (`public_functional_keyswitch`, public_functional_keyswitch.rs:74-148, message j to coefficient
+// j) packs lwe_count LWE nodes of one kind, from anywhere, into ONE GLWE1 node — what brings the LWEs out of a bootstrap or a
+// sample extract back into a packed integer or into CMUX-land.  All such nodes of one level with one (lwe_count, kind) are one
+// main launch: launch_pufks_rows (which counts its own launches), or the contiguous entry point where the rows lie consecutively
+// (the hand-written radices: a pre-pass and the main kernel)
+inline spf_status launch_pufks_group(const GroupLaunch& l)
+{
+    const size_t p = (size_t)l.gr.key.n;
+    if (!l.gr.contiguous[0])
+        return launch_pufks_rows(l.c, l.s, l.B, p, l.rows, l.g->pufks_stage ? (uint64_t*)l.g->d_stage[0] : nullptr, l.out, &l.g->n_launches);
+    l.g->n_launches += pufks_tuned(l.c) ? 2 : 1;
+    return spf_public_functional_keyswitch_enqueue(l.c, l.s, l.B, p, l.in, l.out);
+}
+
+// A plaintext linear map over LWE ciphertexts (spf_lwe_linear.hpp): the M rows of weight slot `slot` times K LWE nodes of one kind,
+// from anywhere — what stands between two bootstraps by table (a layer, then its activation).  All layers of one level with one
+// (slot, M, K, kind) are one group whose output is [layers][M][W]; operand rows that lie consecutively (the results of one
+// bootstrap or keyswitch group, or of another layer) go to the batch dispatcher in place, matrix cores included (it says how
+// many launches it took), anything else is ONE launch of lwe_linear_rows_kernel over a pointer row
+inline spf_status launch_lwe_linear_group(const GroupLaunch& l)
+{
+    const size_t layers = l.B / l.gr.key.rows;
+    const spf_value_kind kind = (spf_value_kind)l.gr.key.kind;
+    if (l.gr.contiguous[0]) {
+        const spf_status st = spf_lwe_linear_enqueue(l.c, l.s, l.gr.key.slot, kind, layers, l.in, l.out);
+        l.g->n_launches += l.c->last_lin_launches;
+        return st;
+    }
+    l.g->n_launches++;
+    return launch_lwe_linear_rows(l.c, l.s, l.gr.key.slot, kind, layers, l.rows, l.out);
+}
+
+// A plaintext polynomial linear map over GLWE ciphertexts (spf_glwe_poly.hpp), the same way: the M rows of polynomial weight slot
+// `slot` times K GLWE1 nodes from anywhere — a packed integer shifted and added to another one before it is unpacked, a lookup
+// table that is a plaintext polynomial times an encrypted GLWE.  All layers of one level with one (slot, M, K) are one group
+// whose output is [layers][M][(k+1) N]; operand GLWEs that lie consecutively go to the batch kernels in place, anything else is
+// ONE launch of glwe_poly_lds_rows_kernel or glwe_poly_stream_rows_kernel over a pointer row
+inline spf_status launch_glwe_poly_group(const GroupLaunch& l)
+{
+    const size_t layers = l.B / l.gr.key.rows;
+    return l.launched(l.gr.contiguous[0] ? spf_glwe_poly_linear_enqueue(l.c, l.s, l.gr.key.slot, layers, l.in, l.out)
+                                         : launch_glwe_poly_rows(l.c, l.s, l.gr.key.slot, layers, l.g->d_arena, l.rows, l.out));
+}
+
+// GlweKsMode (spf_glwe_keyswitch.hpp) of a GLWE keyswitch, automorphism or trace node
+inline int glwe_ks_mode_of(int32_t op)
+{
+    return op == kNodeGlweKeyswitch ? GLWE_KS_KEYSWITCH : op == kNodeGlweAutomorphism ? GLWE_KS_AUTOMORPHISM : GLWE_KS_TRACE;
+}
+
+// The GLWE keyswitch, one automorphism round and the homomorphic trace (spf_glwe_keyswitch.hpp) over ONE GLWE1 node from anywhere —
+// a packed integer that changes its key, a GLWE traced behind an X^-j polynomial map to isolate one coefficient.  All nodes of one
+// level with one mode and one slot (or round; key.n) are one group and ONE launch: operands that lie consecutively go to
+// glwe_ks_kernel / generic_glwe_ks_kernel in place, anything else to their rows twins over a pointer row.  The rows kernels park
+// into the output while other workgroups still read, so the output block must overlap no operand: operands are rows of earlier
+// levels (or inputs), and a group's output is a fresh block of its own level (spf_graph_plan::lay_out).  The automorphism key is
+// the context's, rewritten in place by a load, so a captured graph is kept over its reload as with circuit bootstrap nodes
+inline spf_status launch_glwe_ks_group(const GroupLaunch& l)
+{
+    const int mode = glwe_ks_mode_of(l.gr.key.op);
+    return l.launched(l.gr.contiguous[0] ? glwe_ks_enqueue(l.c, l.s, mode, (uint32_t)l.gr.key.n, l.B, l.in, l.out)
+                                         : launch_glwe_ks_rows(l.c, l.s, mode, (uint32_t)l.gr.key.n, l.B, l.rows, l.out));
+}
+
+using GroupLauncher = spf_status (*)(const GroupLaunch&);
+constexpr GroupLauncher kNodeLaunchers[] = {launch_unpack_group,     launch_pack_group,      launch_rot_cmux_group,
+                                            launch_pufks_group,      launch_lwe_linear_group, launch_glwe_poly_group,
+                                            launch_glwe_ks_group,    launch_glwe_ks_group,   launch_glwe_ks_group};
+static_assert(sizeof kNodeLaunchers / sizeof kNodeLaunchers[0] == kNodeRowCount, "one launcher per row of kNodeRows, in its order");
+
+// ---- what the groups need at run time: one check per spf_graph_plan::Resource, against a group's key ---------------------------------
+
+// the public functional keyswitch key comes with its own shape
+inline spf_status check_pufks_key(spf_graph* g, const GroupKey& key)
+{
+    spf_ctx* c = g->ctx;
+    if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "graph: public functional keyswitch key not loaded");
+    const size_t dim = value_bytes(g->prm, key.kind) / 8 - 1;
+    if (c->pufks_n != dim)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: the public functional keyswitch key's from_dimension " + std::to_string(c->pufks_n) +
+                                                     " is not the dimension " + std::to_string(dim) + " of its " +
+                                                     (key.kind == SPF_VAL_LWE0 ? "lwe0" : "lwe1") + " operands");
+    return SPF_OK;
+}
+
+// the shape of a weight slot against the (M, K) its nodes were built for; `poly`: " polynomial" or ""
+template <class Slot> inline spf_status check_weight_slot(spf_ctx* c, const Slot& l, const GroupKey& key, const std::string& poly)
+{
+    const size_t K = (size_t)key.n, M = key.rows;
+    const std::string slot = std::to_string(key.slot);
+    if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no" + poly + " weights loaded in slot " + slot);
+    if (l.M != M || l.K != K)
+        return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: slot " + slot + " holds " + std::to_string(l.M) + " x " + std::to_string(l.K) + poly +
+                                                     " weights, its" + poly + " linear nodes were built for " + std::to_string(M) + " x " +
+                                                     std::to_string(K));
+    return SPF_OK;
+}
+inline spf_status check_lwe_slot(spf_graph* g, const GroupKey& key) { return check_weight_slot(g->ctx, g->ctx->lin[key.slot], key, ""); }
+inline spf_status check_poly_slot(spf_graph* g, const GroupKey& key) { return check_weight_slot(g->ctx, g->ctx->gpoly[key.slot], key, " polynomial"); }
+
+// an empty keyswitch-key slot or a missing automorphism key is SPF_ERR_NO_KEY, a tr_radix no kernel serves SPF_ERR_UNSUPPORTED, with
+// the texts of the batch entry points (glwe_ks_args)
+inline spf_status check_glwe_ks_keys(spf_graph* g, const GroupKey& key)
+{
+    return glwe_ks_args(g->ctx, glwe_ks_mode_of(key.op), (uint32_t)key.n, 0, nullptr, nullptr);
+}
+
+using ResourceCheck = spf_status (*)(spf_graph*, const GroupKey&);
+constexpr ResourceCheck kResourceChecks[kResources] = {nullptr, check_pufks_key, check_lwe_slot, check_poly_slot, check_glwe_ks_keys};
+// the context's count of loads of a resource: a load frees the old image (a keyswitch-key slot may change its kernel too), so a
+// captured graph that holds its pointers is dropped when the count has moved.  (None for the public functional keyswitch key)
+constexpr uint64_t spf_ctx::* kResourceEpochs[kResources] = {nullptr, nullptr, &spf_ctx::lin_epoch, &spf_ctx::gpoly_epoch, &spf_ctx::gksk_epoch};
+
+// resource `r` against every group that needs it, in group order
+inline spf_status check_resource(spf_graph* g, Resource r)
+{
+    if (!g->has(r)) return SPF_OK;
+    for (const auto& gr : g->groups)
+        if (node_row(gr.key.op).needs == r) {
+            const spf_status st = kResourceChecks[r](g, gr.key);
+            if (st != SPF_OK) return st;
+        }
+    return SPF_OK;
+}
+
 // Everything a run puts on the stream between the input copy and the output copies: the GGSW constants
 // (device to device) and one launch per group.  No allocation, no synchronisation: capturable.
 inline spf_status enqueue(spf_graph* g, hipStream_t s)
@@ -214,94 +352,17 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
                                      hipMemcpyDeviceToDevice, s));
         }
     g->n_launches = 0;
-    // the public functional keyswitch key comes with its own shape: checked against the nodes before anything is enqueued
-    for (const auto& gr : g->groups)
-        if (gr.key.op == spf_graph_plan::kNodePufks) {
-            if (!c->pufks_ready) return fail(c, SPF_ERR_NO_KEY, "graph: public functional keyswitch key not loaded");
-            const int kind = gr.key.kind;
-            const size_t dim = value_bytes(g->prm, kind) / 8 - 1;
-            if (c->pufks_n != dim)
-                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: the public functional keyswitch key's from_dimension " + std::to_string(c->pufks_n) +
-                                                             " is not the dimension " + std::to_string(dim) + " of its " +
-                                                             (kind == SPF_VAL_LWE0 ? "lwe0" : "lwe1") + " operands");
-        }
+    // The public functional keyswitch key is checked here, before anything is enqueued — and so, unlike the resources run() checks,
+    // not before the replay of a captured graph.  Kept where it was: checking it in run() would change what a replay answers.
+    if (spf_status st = check_resource(g, kPufksKey)) return st;
     for (const auto& gr : g->groups) {
         const size_t B = gr.members.size();
         char* out = g->d_arena + gr.out_off;
-        if (gr.key.op == spf_graph_plan::kNodePufks) {
-            const size_t p = (size_t)gr.key.n;
-            spf_status st;
-            if (gr.contiguous[0]) {
-                st = spf_public_functional_keyswitch_enqueue(c, s, B, p, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
-                g->n_launches += pufks_tuned(c) ? 2 : 1;
-            } else {
-                st = launch_pufks_rows(c, s, B, p, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]),
-                                       g->pufks_stage ? (uint64_t*)g->d_stage[0] : nullptr, (uint64_t*)out, &g->n_launches);
-            }
+        const NodeRow& kind = node_row(gr.key.op);
+        if (kind.access != NodeRow::kTableOp) { // a constructor kind: the launcher of its row
+            const spf_status st = kNodeLaunchers[&kind - kNodeRows](GroupLaunch{g, c, s, gr, B, (uint64_t*)out, (const uint64_t*)(g->d_arena + gr.first_off[0]),
+                                                                                (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0])});
             if (st != SPF_OK) return st;
-            continue;
-        }
-        if (gr.key.op == spf_graph_plan::kNodeLweLinear) {
-            const size_t M = gr.key.rows;
-            const uint32_t slot = gr.key.slot;
-            const spf_value_kind kind = (spf_value_kind)gr.key.kind;
-            spf_status st;
-            if (gr.contiguous[0]) {
-                st = spf_lwe_linear_enqueue(c, s, slot, kind, B / M, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out);
-                g->n_launches += c->last_lin_launches;
-            } else {
-                st = launch_lwe_linear_rows(c, s, slot, kind, B / M, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
-                g->n_launches++;
-            }
-            if (st != SPF_OK) return st;
-            continue;
-        }
-        if (gr.key.op == spf_graph_plan::kNodeGlwePolyLinear) { // (one launch either way)
-            const size_t layers = B / gr.key.rows;
-            const spf_status st = gr.contiguous[0]
-                                      ? spf_glwe_poly_linear_enqueue(c, s, gr.key.slot, layers, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out)
-                                      : launch_glwe_poly_rows(c, s, gr.key.slot, layers, g->d_arena,
-                                                              (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
-            if (st != SPF_OK) return st;
-            g->n_launches++;
-            continue;
-        }
-        if (spf_graph_plan::is_glwe_ks_node(gr.key.op)) { // (one launch either way; the parameter is the slot or the round)
-            const int mode = glwe_ks_mode_of(gr.key.op);
-            // rows form: the output block overlaps no operand — operands are rows of earlier levels (or inputs), and a group's
-            // output is a fresh block of its own level (spf_graph_plan::lay_out), which is what the rows kernels' parking needs
-            const spf_status st = gr.contiguous[0]
-                                      ? glwe_ks_enqueue(c, s, mode, (uint32_t)gr.key.n, B, (const uint64_t*)(g->d_arena + gr.first_off[0]), (uint64_t*)out)
-                                      : launch_glwe_ks_rows(c, s, mode, (uint32_t)gr.key.n, B, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
-            if (st != SPF_OK) return st;
-            g->n_launches++;
-            continue;
-        }
-        if (gr.key.op == spf_graph_plan::kNodePack) {
-            spf_status st = launch_glwe_pack_rows(c, s, B, gr.key.n, (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)out);
-            if (st != SPF_OK) return st;
-            g->n_launches++;
-            continue;
-        }
-        if (gr.key.op == spf_graph_plan::kNodeUnpack) {
-            const size_t ints = B / gr.key.n;
-            const uint64_t* src = (const uint64_t*)(g->d_arena + gr.first_off[0]);
-            if (!gr.contiguous[0]) {
-                spf_status st = spf_gather_rows_dev(c, s, ints, value_bytes(g->prm, SPF_VAL_GLWE1) / 8,
-                                                    (const uint64_t* const*)(g->d_ptrs + gr.ptr_index[0]), (uint64_t*)g->d_stage[0]);
-                if (st != SPF_OK) return st;
-                g->n_launches++;
-                src = (const uint64_t*)g->d_stage[0];
-            }
-            spf_status st = launch_glwe_unpack(c, s, ints, gr.key.n, src, (uint64_t*)out);
-            if (st != SPF_OK) return st;
-            g->n_launches++;
-            continue;
-        }
-        if (gr.key.op == spf_graph_plan::kNodeRotCmux) {
-            spf_status st = launch_cmux_rot_scattered(c, s, B, (uint32_t)gr.key.n, (const void* const*)(g->d_ptrs + gr.ptr_index[0]));
-            if (st != SPF_OK) return st;
-            g->n_launches++;
             continue;
         }
         const spf_ops::OpRow& info = op_row(gr.key.op);
@@ -354,55 +415,6 @@ inline spf_status enqueue(spf_graph* g, hipStream_t s)
     return SPF_OK;
 }
 
-// The weight slots of the linear groups against their nodes: a slot comes with its own shape and may be loaded after the graph is
-// built.  Run before anything is enqueued, on the replay of a captured graph as well.
-inline spf_status check_linear_slots(spf_graph* g)
-{
-    spf_ctx* c = g->ctx;
-    for (const auto& gr : g->groups)
-        if (gr.key.op == spf_graph_plan::kNodeLweLinear) {
-            const size_t K = (size_t)gr.key.n, M = gr.key.rows;
-            const uint32_t slot = gr.key.slot;
-            const LweLinearSlot& l = c->lin[slot];
-            if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no weights loaded in slot " + std::to_string(slot));
-            if (l.M != M || l.K != K)
-                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: slot " + std::to_string(slot) + " holds " + std::to_string(l.M) + " x " +
-                                                             std::to_string(l.K) + " weights, its linear nodes were built for " +
-                                                             std::to_string(M) + " x " + std::to_string(K));
-        }
-    return SPF_OK;
-}
-
-// ... and the polynomial weight slots of the polynomial linear groups, the same way
-inline spf_status check_glwe_poly_slots(spf_graph* g)
-{
-    spf_ctx* c = g->ctx;
-    for (const auto& gr : g->groups)
-        if (gr.key.op == spf_graph_plan::kNodeGlwePolyLinear) {
-            const size_t K = (size_t)gr.key.n, M = gr.key.rows;
-            const uint32_t slot = gr.key.slot;
-            const GlwePolySlot& l = c->gpoly[slot];
-            if (!l.ready) return fail(c, SPF_ERR_NO_KEY, "graph: no polynomial weights loaded in slot " + std::to_string(slot));
-            if (l.M != M || l.K != K)
-                return fail(c, SPF_ERR_INVALID_ARGUMENT, "graph: slot " + std::to_string(slot) + " holds " + std::to_string(l.M) + " x " +
-                                                             std::to_string(l.K) + " polynomial weights, its polynomial linear nodes were built for " +
-                                                             std::to_string(M) + " x " + std::to_string(K));
-        }
-    return SPF_OK;
-}
-
-// ... and the keys of the GLWE keyswitch, automorphism and trace groups: an empty keyswitch-key slot or a missing automorphism key
-// is SPF_ERR_NO_KEY, a tr_radix no kernel serves SPF_ERR_UNSUPPORTED, with the texts of the batch entry points (glwe_ks_args)
-inline spf_status check_glwe_ks_keys(spf_graph* g)
-{
-    for (const auto& gr : g->groups)
-        if (spf_graph_plan::is_glwe_ks_node(gr.key.op)) {
-            const spf_status st = glwe_ks_args(g->ctx, glwe_ks_mode_of(gr.key.op), (uint32_t)gr.key.n, 0, nullptr, nullptr);
-            if (st != SPF_OK) return st;
-        }
-    return SPF_OK;
-}
-
 // Output staging (after plan(): needs the arena offsets): outputs grouped by value size, one pointer row per group
 inline spf_status plan_outputs(spf_graph* g)
 {
@@ -449,18 +461,10 @@ inline spf_status run(spf_graph* g)
         spf_status st = plan(g);
         if (st != SPF_OK) return st;
     }
-    if (g->has_linear) {
-        spf_status st = check_linear_slots(g);
-        if (st != SPF_OK) return st;
-    }
-    if (g->has_glwe_poly) {
-        spf_status st = check_glwe_poly_slots(g);
-        if (st != SPF_OK) return st;
-    }
-    if (g->has_glwe_ks) {
-        spf_status st = check_glwe_ks_keys(g);
-        if (st != SPF_OK) return st;
-    }
+    // what the groups need, resource by resource, before anything is enqueued and before the replay of a captured graph as well
+    // (the public functional keyswitch key: by enqueue)
+    for (int r = kLweSlot; r < kResources; r++)
+        if (spf_status st = check_resource(g, (Resource)r)) return st;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     const size_t k = g->prm.glwe_size, N = g->prm.polynomial_degree;
@@ -498,9 +502,8 @@ inline spf_status run(spf_graph* g)
     static const bool capture_on = [] { const char* e = getenv("SPF_GRAPH_CAPTURE"); return e && e[0] == '1'; }();
     g->runs_since_plan++;
     if (g->exec && g->exec_epoch != c->buf_epoch) g->drop_exec(); // a scratch buffer moved since the capture
-    if (g->exec && g->has_linear && g->exec_lin_epoch != c->lin_epoch) g->drop_exec(); // a weight slot was loaded: its old image is freed
-    if (g->exec && g->has_glwe_poly && g->exec_gpoly_epoch != c->gpoly_epoch) g->drop_exec(); // ... a polynomial weight slot
-    if (g->exec && g->has_glwe_ks && g->exec_gksk_epoch != c->gksk_epoch) g->drop_exec(); // ... a keyswitch-key slot (another buffer, maybe another kernel)
+    for (int r = 0; r < kResources; r++) // a resource of its groups was loaded again since the capture (not one of another graph's)
+        if (g->exec && kResourceEpochs[r] && g->has((Resource)r) && g->exec_res_epoch[r] != c->*kResourceEpochs[r]) g->drop_exec();
     if (g->exec) {
         HIPCHK(c, hipGraphLaunch(g->exec, s));
         g->n_launches = g->captured_launches;
@@ -515,9 +518,8 @@ inline spf_status run(spf_graph* g)
             if (st == SPF_OK && e == hipSuccess && graph && epoch0 == c->buf_epoch &&
                 hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) == hipSuccess) {
                 g->exec_epoch = c->buf_epoch;
-                g->exec_lin_epoch = c->lin_epoch;
-                g->exec_gpoly_epoch = c->gpoly_epoch;
-                g->exec_gksk_epoch = c->gksk_epoch;
+                for (int r = 0; r < kResources; r++)
+                    if (kResourceEpochs[r]) g->exec_res_epoch[r] = c->*kResourceEpochs[r];
                 g->captured_launches = g->n_launches;
             } else {
                 g->exec = nullptr;
@@ -645,6 +647,36 @@ spf_status spf_graph_add_op(spf_graph* g, spf_graph_op op, const uint32_t* input
     return SPF_OK;
 }
 
+// ---- the node constructors ---------------------------------------------------------------------------------------------------------
+// What they share.  The operands ids[0 .. n) of a call: nodes of this graph and L1 GLWEs — or, with `lwe`, LWEs of one kind;
+// `what` names the call in the texts
+static spf_status check_operands(spf_graph* g, const char* what, const uint32_t* ids, size_t n, bool lwe = false)
+{
+    const auto refuse = [&](const char* why) { return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph ") + what + why); };
+    for (size_t i = 0; i < n; i++) {
+        if (ids[i] >= g->nodes.size()) return refuse(": operand is not a node of this graph");
+        const int kind = g->nodes[ids[i]].kind;
+        if (lwe ? kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1 : kind != SPF_VAL_GLWE1) return refuse(lwe ? ": operand is not an LWE" : ": operand is not an L1 GLWE");
+        if (kind != g->nodes[ids[0]].kind) return refuse(": lwe0 and lwe1 operands mixed");
+    }
+    return SPF_OK;
+}
+
+// ... and the insertion: `add` adds all of the call's nodes or none (what does not fit is thrown, as std::vector throws it) and
+// returns the first one's id; the ids first .. first + n_out go to `out` once the nodes exist, and the graph is planned again
+template <class F> static spf_status add_nodes(spf_graph* g, uint32_t* out, size_t n_out, F add)
+{
+    uint32_t first;
+    try {
+        first = add();
+    } catch (const std::exception&) {
+        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
+    }
+    for (size_t i = 0; i < n_out; i++) out[i] = first + (uint32_t)i;
+    g->planned = false;
+    return SPF_OK;
+}
+
 // `PackedDynamicGenericIntGraphNode::unpack` as a node constructor: n_bits LWE1 nodes, node i = sample_extract(glwe_node, i)
 spf_status spf_graph_add_unpack(spf_graph* g, uint32_t glwe_node, size_t n_bits, uint32_t* nodes_out)
 {
@@ -652,19 +684,10 @@ spf_status spf_graph_add_unpack(spf_graph* g, uint32_t glwe_node, size_t n_bits,
     if (!nodes_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: null pointer");
     if (n_bits == 0 || n_bits > g->prm.polynomial_degree)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: n_bits must be in 1 ..= polynomial_degree");
-    if (glwe_node >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not a node of this graph");
-    if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph unpack: operand is not an L1 GLWE");
+    if (spf_status st = check_operands(g, "unpack", &glwe_node, 1)) return st;
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodeUnpack; n.kind = SPF_VAL_LWE1; n.n_in = 1; n.in[0] = glwe_node; n.count = (uint32_t)n_bits;
-    uint32_t first;
-    try {
-        first = g->add_numbered(n, n_bits); // all of the integer's nodes or none
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    for (size_t i = 0; i < n_bits; i++) nodes_out[i] = first + (uint32_t)i;
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, nodes_out, n_bits, [&] { return g->add_numbered(n, n_bits); });
 }
 
 // `DynamicGenericIntGraphNodes::pack` as a node constructor: one GLWE1 node = sum over i of X^i * nodes[i]
@@ -674,19 +697,10 @@ spf_status spf_graph_add_pack(spf_graph* g, const uint32_t* nodes, size_t n_bits
     if (!nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: null pointer");
     if (n_bits == 0 || n_bits > g->prm.polynomial_degree)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: n_bits must be in 1 ..= polynomial_degree");
-    for (size_t i = 0; i < n_bits; i++) {
-        if (nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not a node of this graph");
-        if (g->nodes[nodes[i]].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph pack: operand is not an L1 GLWE");
-    }
+    if (spf_status st = check_operands(g, "pack", nodes, n_bits)) return st;
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodePack; n.kind = SPF_VAL_GLWE1;
-    try {
-        *node_out = g->add_listed(n, nodes, n_bits);
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, node_out, 1, [&] { return g->add_listed(n, nodes, n_bits); });
 }
 
 // `public_functional_keyswitch` (public_functional_keyswitch.rs:74-148) as a node constructor: one GLWE1 node whose coefficient j
@@ -697,24 +711,10 @@ spf_status spf_graph_add_public_functional_keyswitch(spf_graph* g, const uint32_
     if (!lwe_nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: null pointer");
     if (lwe_count == 0 || lwe_count > g->prm.polynomial_degree)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: lwe_count must be in 1 ..= polynomial_degree");
-    for (size_t i = 0; i < lwe_count; i++) {
-        if (lwe_nodes[i] >= g->nodes.size())
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: operand is not a node of this graph");
-        const int kind = g->nodes[lwe_nodes[i]].kind;
-        if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1)
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: operand is not an LWE");
-        if (kind != g->nodes[lwe_nodes[0]].kind)
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph public functional keyswitch: lwe0 and lwe1 operands mixed");
-    }
+    if (spf_status st = check_operands(g, "public functional keyswitch", lwe_nodes, lwe_count, true)) return st;
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodePufks; n.kind = SPF_VAL_GLWE1;
-    try {
-        *node_out = g->add_listed(n, lwe_nodes, lwe_count);
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, node_out, 1, [&] { return g->add_listed(n, lwe_nodes, lwe_count); });
 }
 
 // The linear map of weight slot `slot` (spf_lwe_linear.hpp) as a node constructor: M nodes of the operands' kind, node m = row m of
@@ -731,24 +731,11 @@ spf_status spf_graph_add_lwe_linear(spf_graph* g, uint32_t slot, const uint32_t*
     if (M == 0 || M > SPF_GRAPH_LWE_LINEAR_MAX_ROWS)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: M must be in 1 ..= SPF_GRAPH_LWE_LINEAR_MAX_ROWS = " +
                                                           std::to_string(SPF_GRAPH_LWE_LINEAR_MAX_ROWS));
-    for (size_t i = 0; i < K; i++) {
-        if (lwe_nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: operand is not a node of this graph");
-        const int kind = g->nodes[lwe_nodes[i]].kind;
-        if (kind != SPF_VAL_LWE0 && kind != SPF_VAL_LWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: operand is not an LWE");
-        if (kind != g->nodes[lwe_nodes[0]].kind) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph linear map: lwe0 and lwe1 operands mixed");
-    }
+    if (spf_status st = check_operands(g, "linear map", lwe_nodes, K, true)) return st;
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodeLweLinear; n.kind = g->nodes[lwe_nodes[0]].kind;
     n.lin_slot = slot; n.lin_rows = (uint32_t)M;
-    uint32_t first;
-    try {
-        first = g->add_listed(n, lwe_nodes, K, M); // all of the layer's nodes or none
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    for (size_t m = 0; m < M; m++) nodes_out[m] = first + (uint32_t)m;
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, nodes_out, M, [&] { return g->add_listed(n, lwe_nodes, K, M); });
 }
 
 // The polynomial linear map of polynomial weight slot `slot` (spf_glwe_poly.hpp) as a node constructor: M GLWE1 nodes, node m = row
@@ -765,29 +752,17 @@ spf_status spf_graph_add_glwe_poly_linear(spf_graph* g, uint32_t slot, const uin
     if (M == 0 || M > SPF_GLWE_POLY_MAX_ROWS)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: M must be in 1 ..= SPF_GLWE_POLY_MAX_ROWS = " +
                                                           std::to_string(SPF_GLWE_POLY_MAX_ROWS));
-    for (size_t i = 0; i < K; i++) {
-        if (glwe_nodes[i] >= g->nodes.size())
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: operand is not a node of this graph");
-        if (g->nodes[glwe_nodes[i]].kind != SPF_VAL_GLWE1)
-            return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph polynomial linear map: operand is not an L1 GLWE");
-    }
+    if (spf_status st = check_operands(g, "polynomial linear map", glwe_nodes, K)) return st;
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodeGlwePolyLinear; n.kind = SPF_VAL_GLWE1;
     n.lin_slot = slot; n.lin_rows = (uint32_t)M;
-    uint32_t first;
-    try {
-        first = g->add_listed(n, glwe_nodes, K, M); // all of the layer's nodes or none
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    for (size_t m = 0; m < M; m++) nodes_out[m] = first + (uint32_t)m;
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, nodes_out, M, [&] { return g->add_listed(n, glwe_nodes, K, M); });
 }
 
 // `keyswitch_glwe_to_glwe`, one round of the trace's loop and `trace` (spf_glwe_keyswitch.hpp) as node constructors: one GLWE1
 // operand in Node::in[0], one GLWE1 node, Node::param = the keyswitch-key slot / the round / 0.  The keys are looked at by
-// spf_graph_run, not here.  `what` names the call in the messages; nothing is written to *node_out before the node exists
+// spf_graph_run, not here.  `what` names the call in the messages, which — unlike check_operands' — name the operand and the node
+// count; nothing is written to *node_out before the node exists
 static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, uint32_t param, uint32_t glwe_node, uint32_t* node_out)
 {
     if (!g) return SPF_ERR_INVALID_ARGUMENT;
@@ -806,15 +781,8 @@ static spf_status graph_add_glwe_ks(spf_graph* g, int32_t op, const char* what, 
     if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1)
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, w + ": operand " + std::to_string(glwe_node) + " is not an L1 GLWE (its kind is " +
                                                           std::to_string(g->nodes[glwe_node].kind) + ")");
-    uint32_t id;
-    try {
-        id = g->add(spf_graph_plan::op_node(pop, &glwe_node, p64)); // (the node spf_graph_add_op records for the same operation)
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
-    *node_out = id;
-    g->planned = false;
-    return SPF_OK;
+    // (the node spf_graph_add_op records for the same operation)
+    return add_nodes(g, node_out, 1, [&] { return g->add(spf_graph_plan::op_node(pop, &glwe_node, p64)); });
 }
 
 spf_status spf_graph_add_glwe_keyswitch(spf_graph* g, uint32_t slot, uint32_t glwe_node, uint32_t* node_out)
@@ -839,29 +807,24 @@ spf_status spf_graph_add_blind_rotation(spf_graph* g, uint32_t glwe_node, const 
     if (!shift_nodes || !node_out) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: null pointer");
     if (const char* why = blind_rotation_shape_error(g->prm, 1, n_bits, log_stride))
         return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, std::string("graph blind rotation: ") + why);
-    if (glwe_node >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: operand is not a node of this graph");
-    if (g->nodes[glwe_node].kind != SPF_VAL_GLWE1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: operand is not an L1 GLWE");
+    if (spf_status st = check_operands(g, "blind rotation", &glwe_node, 1)) return st;
     for (size_t i = 0; i < n_bits; i++) {
         if (shift_nodes[i] >= g->nodes.size()) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: selector is not a node of this graph");
         if (g->nodes[shift_nodes[i]].kind != SPF_VAL_GGSW1) return fail(g->ctx, SPF_ERR_INVALID_ARGUMENT, "graph blind rotation: selector is not an L1 GGSW");
     }
     if (!g->ctx->generic && (g->prm.cbs_radix_log != 4 || g->prm.cbs_radix_count != 4))
         return fail(g->ctx, SPF_ERR_UNSUPPORTED, "cmux kernel is built for cbs_radix 4 x 4 bits");
-    try {
-        g->nodes.reserve(g->nodes.size() + n_bits); // all of the chain's nodes or none
-    } catch (const std::exception&) {
-        return fail(g->ctx, SPF_ERR_HIP, "out of host memory");
-    }
     spf_graph_plan::Node n{};
     n.op = spf_graph_plan::kNodeRotCmux; n.kind = SPF_VAL_GLWE1; n.n_in = 2;
-    uint32_t acc = glwe_node;
-    for (size_t i = 0; i < n_bits; i++) {
-        n.in[0] = shift_nodes[i]; n.in[1] = acc; n.param = (uint64_t)1 << (i + log_stride);
-        acc = g->add(n);
-    }
-    *node_out = acc;
-    g->planned = false;
-    return SPF_OK;
+    return add_nodes(g, node_out, 1, [&] {
+        g->nodes.reserve(g->nodes.size() + n_bits); // all of the chain's nodes or none
+        uint32_t acc = glwe_node;
+        for (size_t i = 0; i < n_bits; i++) {
+            n.in[0] = shift_nodes[i]; n.in[1] = acc; n.param = (uint64_t)1 << (i + log_stride);
+            acc = g->add(n);
+        }
+        return acc;
+    });
 }
 
 spf_status spf_graph_add_output(spf_graph* g, uint32_t node, void* host)

@@ -1,6 +1,9 @@
 // spf_graph_plan.hpp — what the executor of gate graphs (spf_graph.hpp) decides before it touches a device: the graph's host-side
 // data, and the plan of a run.
 //
+//   * kNodeRows: one row per node constructor that is no row of the operation table (spf_ops.hpp) — where its operands are kept,
+//     what its group key is made of, how a group reads its operands, what it needs at run time.  Graph, key_of and plan_access
+//     know a constructor kind through its row only.
 //   * Graph: the node list and the operand lists of the nodes whose operands do not fit a node (pack, public functional keyswitch,
 //     linear map).  Where operand ids are kept is known here only: for_operands / operand read them, add / add_numbered /
 //     add_listed write them, append shifts them.
@@ -33,6 +36,61 @@ enum : int32_t {
 // the three nodes of spf_glwe_keyswitch.hpp: one GLWE1 operand in Node::in[0], one GLWE1 result; Node::param is the keyswitch-key
 // slot, the round, or 0
 inline bool is_glwe_ks_node(int32_t op) { return op >= kNodeGlweKeyswitch && op <= kNodeGlweTrace; }
+
+// What a kind's groups need at run time besides their operands.  It may be loaded, and loaded again, after the graph is built, so
+// it is looked at when the graph runs (spf_graph.hpp: one check per resource, in this order), and Plan::has(resource) says
+// whether any group needs it.
+enum Resource : uint8_t { kNoResource, kPufksKey, kLweSlot, kPolySlot, kGlweKsKeys, kResources };
+
+// A node kind as the planner sees it: where its operands are, what its group key is made of, and how a group reads its operands.
+// A group of a rows kind reads *records* of operand rows, one behind the other: every `step`-th member starts a record (its
+// operands, in order), the rows are of one size, and they are read in place where they lie consecutively, else through one
+// pointer row of the table.
+struct NodeRow {
+    int32_t op;
+    bool listed;                                               // the operands are in the graph's side list, not in Node::in
+    enum : uint8_t { kNoKind, kOperandKind, kNodeKind } kind;  // GroupKey::kind: 0, the first operand's kind, or the node's own
+    bool slot_rows;                                            // GroupKey::slot and ::rows are Node::lin_slot and ::lin_rows (else 0)
+    bool n_is_count;                                           // GroupKey::n is Node::count (else Node::param)
+    enum : uint8_t { kTableOp, kUnits, kRows } access;         // an operation of spf_ops.hpp / CMUX units / records of rows
+    enum : uint8_t { kEvery, kEveryRows, kEveryN } step;       // rows: a record starts at every member / key.rows-th / key.n-th
+    bool glwe_rows;                                            // rows: they are GLWE1s (else of key.kind)
+    bool in_place;                                             // rows: consecutive rows are read where they lie
+    enum : uint8_t { kNoStage, kStage, kStagePufks } stage;    // rows: scattered rows are gathered into the stage buffer: never,
+                                                               // always, or when Sizes::pufks_stage says so
+    Resource needs;
+};
+constexpr NodeRow kNodeRows[] = {
+    // {op, listed, kind, slot_rows, n_is_count, access, step, glwe_rows, in_place, stage, needs}
+    // one source GLWE per integer (every width-th member; the bit nodes of a call share Node::in[0]): gathered unless consecutive
+    {kNodeUnpack, false, NodeRow::kNoKind, false, true, NodeRow::kRows, NodeRow::kEveryN, true, true, NodeRow::kStage, kNoResource},
+    // the rows of every pack, where they lie: never in place — glwe_pack_rows_kernel, the one kernel there is for it, reads its rows
+    // through the table wherever they are, so consecutive rows go the same way and nothing is gathered
+    {kNodePack, true, NodeRow::kNoKind, false, true, NodeRow::kRows, NodeRow::kEvery, true, false, NodeRow::kNoStage, kNoResource},
+    // units {selector, accumulator, unused (the high operand is a rotated read of the accumulator), out}; key.n is the rotation
+    {kNodeRotCmux, false, NodeRow::kNoKind, false, false, NodeRow::kUnits, NodeRow::kEvery, true, false, NodeRow::kNoStage, kNoResource},
+    // the lwe_count rows of every output, output-major: in place when they lie consecutively; else read through the table by the
+    // pre-pass of the hand-written radices, or gathered for generic_pufks_kernel
+    {kNodePufks, true, NodeRow::kOperandKind, false, true, NodeRow::kRows, NodeRow::kEvery, false, true, NodeRow::kStagePufks, kPufksKey},
+    // the K rows of every layer, layer-major (the M nodes of a call share one list): in place when all of them lie consecutively
+    // (the batch dispatcher, matrix cores included), else read through the table by lwe_linear_rows_kernel
+    {kNodeLweLinear, true, NodeRow::kNodeKind, true, true, NodeRow::kRows, NodeRow::kEveryRows, false, true, NodeRow::kNoStage, kLweSlot},
+    // the K GLWEs of every layer, the same way (the node's kind is SPF_VAL_GLWE1): the batch kernels in place, else the rows kernels
+    {kNodeGlwePolyLinear, true, NodeRow::kNodeKind, true, true, NodeRow::kRows, NodeRow::kEveryRows, true, true, NodeRow::kNoStage, kPolySlot},
+    // one GLWE per member (Node::in[0]): the batch kernels in place, else the rows kernels, which park into the group's output rows
+    // while other workgroups still read: those rows are this group's own fresh block (lay_out), its operands rows of earlier
+    // levels — disjoint.  key.n is the slot, the round, or 0: the operation is the mode
+    {kNodeGlweKeyswitch, false, NodeRow::kNoKind, false, false, NodeRow::kRows, NodeRow::kEvery, true, true, NodeRow::kNoStage, kGlweKsKeys},
+    {kNodeGlweAutomorphism, false, NodeRow::kNoKind, false, false, NodeRow::kRows, NodeRow::kEvery, true, true, NodeRow::kNoStage, kGlweKsKeys},
+    {kNodeGlweTrace, false, NodeRow::kNoKind, false, false, NodeRow::kRows, NodeRow::kEvery, true, true, NodeRow::kNoStage, kGlweKsKeys},
+};
+constexpr size_t kNodeRowCount = sizeof kNodeRows / sizeof kNodeRows[0];
+// every node that is no constructor's — an operation of the table (spf_ops.hpp), an input, a constant: operands in Node::in, keyed
+// by its parameter
+constexpr NodeRow kTableOpRow = {-1, false, NodeRow::kNoKind, false, false, NodeRow::kTableOp, NodeRow::kEvery, false, false, NodeRow::kNoStage, kNoResource};
+constexpr bool node_rows_in_order(size_t i = 0) { return i == kNodeRowCount || (kNodeRows[i].op == kNodeUnpack + (int32_t)i && node_rows_in_order(i + 1)); }
+static_assert(kNodeRowCount == kNodeGlweTrace - kNodeUnpack + 1 && node_rows_in_order(), "one row per constructor kind, in the order of the enum");
+inline const NodeRow& node_row(int32_t op) { return op >= kNodeUnpack && op <= kNodeGlweTrace ? kNodeRows[op - kNodeUnpack] : kTableOpRow; }
 
 constexpr size_t kAlign = 256;        // inputs, constants and every group's block start on a multiple of this
 constexpr size_t kNull = (size_t)-1;  // a table entry that is no arena offset but a null pointer
@@ -130,8 +188,8 @@ struct Graph {
     }
 
 private:
-    static bool has_list(int32_t op) { return op == kNodePack || op == kNodePufks || op == kNodeLweLinear || op == kNodeGlwePolyLinear; }
-    std::vector<uint32_t> lists; // operand lists of the pack, the public functional keyswitch, the linear and the polynomial linear nodes
+    static bool has_list(int32_t op) { return node_row(op).listed; }
+    std::vector<uint32_t> lists; // the operand lists of the kinds whose row says `listed`
 };
 
 // What the planner needs to know of the parameter set and the context
@@ -197,6 +255,9 @@ struct Plan {
     bool has_linear = false; // linear nodes: any (their weight slots are checked at every run)
     bool has_glwe_poly = false; // polynomial linear nodes: any (likewise)
     bool has_glwe_ks = false;   // GLWE keyswitch, automorphism or trace nodes: any (their keys are checked at every run)
+    // the flag of a resource (not kNoResource): set by plan_access for every group whose kind needs it
+    bool& has(Resource r) { return r == kPufksKey ? has_pufks : r == kLweSlot ? has_linear : r == kPolySlot ? has_glwe_poly : has_glwe_ks; }
+    bool has(Resource r) const { return r != kNoResource && const_cast<Plan*>(this)->has(r); }
 };
 
 // the table row (spf_ops.hpp) of a node's operation: a spf_graph_op that spf_graph_add_op has accepted
@@ -268,19 +329,10 @@ inline uint32_t assign_levels(Graph& g)
 // the key of a node that has its level
 inline GroupKey key_of(const Graph& g, const Node& n)
 {
-    GroupKey k{n.level, n.op, 0, 0, 0, n.param};
-    if (n.op == kNodeUnpack || n.op == kNodePack) k.n = n.count;
-    if (n.op == kNodePufks) {
-        k.kind = (uint8_t)g.nodes[g.operand(n, 0)].kind;
-        k.n = n.count;
-    }
-    if (n.op == kNodeLweLinear || n.op == kNodeGlwePolyLinear) { // (polynomial linear nodes: the kind is SPF_VAL_GLWE1)
-        k.kind = (uint8_t)n.kind;
-        k.slot = (uint8_t)n.lin_slot;
-        k.rows = (uint16_t)n.lin_rows;
-        k.n = n.count;
-    }
-    return k;
+    const NodeRow& r = node_row(n.op);
+    return GroupKey{n.level, n.op,
+                    (uint8_t)(r.kind == NodeRow::kOperandKind ? g.nodes[g.operand(n, 0)].kind : r.kind == NodeRow::kNodeKind ? n.kind : 0),
+                    (uint8_t)(r.slot_rows ? n.lin_slot : 0), (uint16_t)(r.slot_rows ? n.lin_rows : 0), r.n_is_count ? n.count : n.param};
 }
 
 // One group per key, members in node order, groups in key order.  Unpack and pack nodes group by their width: the bit
@@ -367,64 +419,28 @@ inline void plan_access(const Graph& g, const Sizes& sz, Plan& p)
     for (auto& gr : p.groups) {
         const int32_t op = gr.key.op;
         const size_t B = gr.members.size();
-        // the operand lists of every `step`-th member, one behind the other
-        const auto listed = [&](size_t step) {
+        const NodeRow& kind = node_row(op);
+        if (kind.needs != kNoResource) p.has(kind.needs) = true;
+        if (kind.access == NodeRow::kRows) {
+            // the records: the operands of every `step`-th member, one behind the other
+            const size_t step = kind.step == NodeRow::kEveryN ? (size_t)gr.key.n : kind.step == NodeRow::kEveryRows ? gr.key.rows : 1;
             std::vector<size_t> offs;
             for (size_t i = 0; i < B; i += step) g.for_operands(g.nodes[gr.members[i]], [&](uint32_t in) { offs.push_back(off_of(in)); });
-            return offs;
-        };
-        if (op == kNodePufks) {
-            // the rows of every output, output-major: in place when they lie consecutively; else read through the table by the
-            // pre-pass of the hand-written radices, or gathered for generic_pufks_kernel
-            p.has_pufks = true;
-            const std::vector<size_t> offs = listed(1);
-            read_rows(p, gr, 0, offs, sz.of(gr.key.kind), consecutive(offs, sz.of(gr.key.kind)), sz.pufks_stage);
-        } else if (op == kNodeLweLinear) {
-            // the K rows of every layer, layer-major (every M-th member starts a layer): in place when all of them lie consecutively
-            // (the batch dispatcher, matrix cores included), else read through the table by lwe_linear_rows_kernel
-            p.has_linear = true;
-            const std::vector<size_t> offs = listed(gr.key.rows);
-            read_rows(p, gr, 0, offs, sz.of(gr.key.kind), consecutive(offs, sz.of(gr.key.kind)), false);
-        } else if (op == kNodeGlwePolyLinear) {
-            // the K GLWEs of every layer, layer-major: in place when all of them lie consecutively (the batch kernels), else read
-            // through the table by the rows kernels; nothing is gathered
-            p.has_glwe_poly = true;
-            const std::vector<size_t> offs = listed(gr.key.rows);
-            read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), false);
-        } else if (is_glwe_ks_node(op)) {
-            // one GLWE per member: in place when they lie consecutively (the batch kernels), else read through the table by the
-            // rows kernels, which park into the group's output rows while other workgroups still read: those rows are this group's
-            // own fresh block (lay_out), its operands rows of earlier levels — disjoint
-            p.has_glwe_ks = true;
-            std::vector<size_t> offs;
-            offs.reserve(B);
-            for (uint32_t id : gr.members) offs.push_back(off_of(g.nodes[id].in[0]));
-            read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), false);
-        } else if (op == kNodePack) {
-            // the rows of every pack, where they lie: glwe_pack_rows_kernel reads them through the table
-            read_rows(p, gr, 0, listed(1), sz.of(SPF_VAL_GLWE1), false, false);
-        } else if (op == kNodeUnpack) {
-            // one source GLWE per integer (every width-th member): in place when they are consecutive, else gathered
-            const std::vector<size_t> offs = listed((size_t)gr.key.n);
-            read_rows(p, gr, 0, offs, sz.of(SPF_VAL_GLWE1), consecutive(offs, sz.of(SPF_VAL_GLWE1)), true);
-        } else if (op == kNodeRotCmux) {
-            // units {selector, accumulator, unused (the high operand is a rotated read of the accumulator), out}
-            std::vector<Unit> units;
-            units.reserve(B);
-            for (uint32_t id : gr.members) {
-                const Node& n = g.nodes[id];
-                units.push_back(Unit{{off_of(n.in[0]), off_of(n.in[1]), kNull, n.off}});
-            }
-            read_units(p, gr, units);
-        } else if (op_row(op).cmux_family) {
-            // units: one per GLWE pair; {selector, low (a), high (b), out}
-            const size_t per = units_per_node(op, sz.cbs_radix_count), gw = sz.of(SPF_VAL_GLWE1);
+            const size_t row_bytes = sz.of(kind.glwe_rows ? (int)SPF_VAL_GLWE1 : (int)gr.key.kind);
+            read_rows(p, gr, 0, offs, row_bytes, kind.in_place && consecutive(offs, row_bytes),
+                      kind.stage == NodeRow::kStage || (kind.stage == NodeRow::kStagePufks && sz.pufks_stage));
+        } else if (kind.access == NodeRow::kUnits || op_row(op).cmux_family) {
+            // units: a rotate-CMUX node is one (its row), a node of the CMUX family one per GLWE pair, {selector, low (a), high (b), out}
+            const bool rot = kind.access == NodeRow::kUnits;
+            const size_t per = rot ? 1 : units_per_node(op, sz.cbs_radix_count), gw = sz.of(SPF_VAL_GLWE1);
             std::vector<Unit> units;
             units.reserve(B * per);
             for (uint32_t id : gr.members) {
                 const Node& n = g.nodes[id];
                 for (size_t j = 0; j < per; j++) {
-                    if (op == SPF_OP_MULTIPLY_GGSW_GLWE) // (low: the zero ciphertext)
+                    if (rot)
+                        units.push_back(Unit{{off_of(n.in[0]), off_of(n.in[1]), kNull, n.off}});
+                    else if (op == SPF_OP_MULTIPLY_GGSW_GLWE) // (low: the zero ciphertext)
                         units.push_back(Unit{{off_of(n.in[0]), kNull, off_of(n.in[1]), n.off + j * gw}});
                     else
                         units.push_back(Unit{{off_of(n.in[0]), off_of(n.in[1]) + j * gw, off_of(n.in[2]) + j * gw, n.off + j * gw}});
